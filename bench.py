@@ -8,9 +8,15 @@ BCE -> backward -> (RCCL gradient all-reduce) -> fused Adam-amsgrad.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` for the dominant
-kernel (HIP-event timed inside the timed region, on the stream the kernels run on) and, at N=1,
-`cpu_baseline` (the CPU oracle's ATen-autograd restatement of the same step, timed on the host)."""
+Rank 0 prints ONE JSON line: `metric`, `value` (clips/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of
+one timed step), `loss` and the workload's `config`.  A plain run does only that: set up, warm up, time --steps steps.
+
+--full adds everything else the line used to carry, each measured in runs of its own around the timed region: `roofline`
+for the dominant kernel, `layer_roofline`, `step_roofline` and `kernel_breakdown_ms` (HIP events around every launch of an
+instrumented pass of the same K steps after the timed region; box-measured peaks before it), the data-parallel `config.comm`
+figures and, at N=1, `cpu_baseline` (the CPU oracle's ATen-autograd restatement of the same step, timed on the host).
+
+--dump-outputs DIR writes what the last timed step computed as float32 .npy files (see dump_outputs)."""
 import argparse
 import importlib
 import json
@@ -218,6 +224,40 @@ def allreduce_times(dist, flat_g, buckets, iters, dev):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 21        # 8 MB per file: six files stay under 64 MB at every --config / --batch
+
+
+def dump_outputs(out_dir, trainer, model, loss, feats):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy.  loss (1,), logits (B, t, K: the
+    pre-interpolation logits the loss was taken on), params (the flat parameter buffer after the Adam-amsgrad update),
+    grads (the flat gradient buffer the update used), bn_running_stats (every floating buffer of the model, named_buffers
+    order, flattened and concatenated) and features (the log-mel input of the step).  An array of more than DUMP_MAX_ELEMS
+    elements is replaced by a fixed sample: the elements at DUMP_MAX_ELEMS sorted indices drawn by a generator seeded with
+    0, so that two runs with the same arguments sample the same positions."""
+    torch.cuda.synchronize()
+    plan = next(iter(trainer.engine._plans.values()))
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+    arrays = {"loss": loss.detach(), "logits": plan.pre, "params": trainer.flat.p, "grads": trainer.flat.g,
+              "bn_running_stats": torch.cat(bufs) if bufs else torch.zeros(0, device=loss.device),
+              "features": feats}
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1).float()
+        if flat.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randperm(flat.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            flat = flat[idx.to(flat.device)]
+            print(f"bench.py --dump-outputs: {name} ({t.numel()} elements) sampled at {DUMP_MAX_ELEMS} seeded positions",
+                  file=sys.stderr)
+            arr = flat.cpu().numpy()
+        else:
+            arr = flat.cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + ".npy"), arr.astype(np.float32, copy=False))
+        total += arr.nbytes
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes (limit 64 MB)"
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start N fresh ranks (one per GPU) with torch.distributed.run as a CHILD
     process, relay rank 0's single JSON line on this process's stdout, return the children's exit code.  The parent never
@@ -315,6 +355,12 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true", help="launcher rehearsal WITHOUT the GPU: the N ranks rendezvous over gloo, run "
                     "the barriers / MAX-reduce of the timed region around an empty step and rank 0 prints one line marked \"rehearsal\" "
                     "(tests/test_ddp_gloo.py runs the driver's 8-rank command shape this way; a GPU box admits 6 processes on its card, the test runner included)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: box-measured peaks, the "
+                    "instrumented per-kernel pass (roofline, layer / step roofline, kernel breakdown), the isolated all-reduce timings "
+                    "and exposed communication, and at N=1 the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "computed (loss, logits, parameters after the update, gradients, BatchNorm running statistics, features; float32 "
+                    ".npy, a fixed seeded sample of any array over 2M elements) under DIR; rank 0 only")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -382,7 +428,7 @@ def main():
         os.close(json_fd)
         return
     peaks = None
-    if rank == 0 and not a.no_measured_peaks:
+    if a.full and rank == 0 and not a.no_measured_peaks:
         peaks = measure_peaks(sed, dev)
     y = synth_targets(B, T, 1, 4321 + rank, dev)
     wave = None
@@ -404,7 +450,7 @@ def main():
         fe(wave, out=feats)
         del raw
     comm_iso = None
-    if grouped and trainer.reducer.enabled:
+    if a.full and grouped and trainer.reducer.enabled:
         comm_iso = allreduce_times(dist, trainer.flat.g, trainer.flat.buckets, 20, dev)
 
     # --overlap-frontend: the log-mel front-end of step i+1 runs on a second HIP stream beside the train step of batch i
@@ -436,9 +482,11 @@ def main():
         pf = pp.PrefetchingFrontEnd(fe, stream=side)
         pf.submit(wave)
 
+    last_x = [feats]           # the features the latest step trained on (--dump-outputs)
+
     def step():
         if pf is not None:
-            x = pf.get()
+            x = last_x[0] = pf.get()
             pf.timer = trainer.engine.timer
             pf.submit(wave)
             out = trainer.train_step(x, y)
@@ -465,43 +513,76 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # per-kernel HIP-event timings: an instrumented pass of the same K steps right after the timed
-    # region (two event records per launch would otherwise make the timed region host-bound)
-    # (every rank runs it -- the steps contain the gradient collectives -- but only rank 0 records events)
+    loss_val = float(loss.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, trainer, model, loss, last_x[0])
     timer = None
-    if rank == 0:
-        timer = sed.engine.KernelTimer()
-        trainer.engine.timer = timer
-    inst_steps = a.steps
-    if a.graph:
-        # a replayed graph has no per-launch host calls to bracket: the instrumented pass runs the same step eagerly
-        trainer.use_graph = False
-        inst_steps = min(a.steps, 20)
-    if trainer.reducer.enabled:
-        trainer.reducer.exposed_events = []
-    bn_calls0 = trainer.engine.bn_sync.calls if getattr(trainer.engine, "bn_sync", None) is not None else 0
-    for _ in range(inst_steps):
-        step()
-    torch.cuda.synchronize()
-    trainer.engine.timer = None
-    exposed_ms = None
-    if trainer.reducer.enabled:
-        ev = trainer.reducer.exposed_events
-        trainer.reducer.exposed_events = None
-        exposed_ms = sum(e0.elapsed_time(e1) for e0, e1 in ev) / max(1, inst_steps)
-    bn_calls = ((trainer.engine.bn_sync.calls - bn_calls0) / max(1, inst_steps)) if getattr(trainer.engine, "bn_sync", None) is not None else 0
+    exposed_ms = bn_calls = None
+    if a.full:
+        # per-kernel HIP-event timings: an instrumented pass of the same K steps right after the timed
+        # region (two event records per launch would otherwise make the timed region host-bound)
+        # (every rank runs it -- the steps contain the gradient collectives -- but only rank 0 records events)
+        if rank == 0:
+            timer = sed.engine.KernelTimer()
+            trainer.engine.timer = timer
+        inst_steps = a.steps
+        if a.graph:
+            # a replayed graph has no per-launch host calls to bracket: the instrumented pass runs the same step eagerly
+            trainer.use_graph = False
+            inst_steps = min(a.steps, 20)
+        if trainer.reducer.enabled:
+            trainer.reducer.exposed_events = []
+        bn_calls0 = trainer.engine.bn_sync.calls if getattr(trainer.engine, "bn_sync", None) is not None else 0
+        for _ in range(inst_steps):
+            step()
+        torch.cuda.synchronize()
+        trainer.engine.timer = None
+        if trainer.reducer.enabled:
+            ev = trainer.reducer.exposed_events
+            trainer.reducer.exposed_events = None
+            exposed_ms = sum(e0.elapsed_time(e1) for e0, e1 in ev) / max(1, inst_steps)
+        bn_calls = ((trainer.engine.bn_sync.calls - bn_calls0) / max(1, inst_steps)) if getattr(trainer.engine, "bn_sync", None) is not None else 0
     if grouped:
         dist.barrier()
     if grouped:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    loss_val = float(loss.item())
 
     result = None
     if rank == 0:
         clips = world * B * a.steps
         value = clips / elapsed
+        result = {
+            "metric": "SED train clips/sec (60s,64-mel,9-layer CNN)", "value": value, "unit": "clips/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.precision,
+            "data": "synthetic",
+            "config": {"workload": f"Cnn_AvgPooling {a.config} widths {[c for c, _ in cfg]}, "
+                                   + (f"{T}-frame log-mel crops ({fcfg.mel_bins} mel), " if a.frames else
+                                      f"{a.seconds:g} s / {fcfg.working_sample_rate // 1000} kHz / {fcfg.mel_bins}-mel clips (T={T} frames, "
+                                      f"NFFT {fcfg.NFFT}, hop {fcfg.hop_size}), ")
+                                   + f"batch {B}/GPU, train step = "
+                                   f"{'features->' if a.no_frontend else 'waveform->log-mel->'}fwd->BCE->bwd->Adam-amsgrad"
+                                   + (", HIP-graph replay" if a.graph else ""),
+                       "frontend_constants": a.frontend, "graph_replay": bool(a.graph),
+                       "global_batch": world * B, "frames": T, "parallelism": f"dp{world}",
+                       "frontend_in_step": not a.no_frontend, "frontend_overlapped": bool(pf is not None), "frontend_overlap_mode": int(a.overlap_frontend),
+                       "sync_bn": bool(a.sync_bn) and grouped, "rccl_group": bool(grouped and a.backend == "nccl"),
+                       "collectives_executed": bool(trainer.reducer.enabled),
+                       "grad_buckets": [list(k) for k, _, _ in trainer.flat.buckets],
+                       # where a data-parallel step's communication goes (round 6; --full): every bucket's all-reduce timed in isolation
+                       # before the timed region, the time the compute stream is blocked on the collectives after the backward's last kernel
+                       # (= exposed communication; instrumented pass), and the SyncBN collectives issued per step
+                       "comm": None if not (a.full and trainer.reducer.enabled) else {
+                           "backend": a.backend, "buckets": comm_iso[:-1], "flat_single_allreduce": comm_iso[-1],
+                           "exposed_ms_per_step": exposed_ms, "exposed_share_of_step": exposed_ms / (elapsed / a.steps * 1e3),
+                           "syncbn_collectives_per_step": bn_calls,
+                           "how": "isolated: 20 synchronous all-reduces per bucket, HIP events on the compute stream, MAX over ranks; exposed: "
+                                  "events around GradAllReducer.finish()'s waits (the compute stream idles there), rank 0, instrumented pass"}},
+            "loss": loss_val,
+        }
+    if rank == 0 and a.full:
         # ---- per-kernel roofline of the dominant kernel -------------------------------------
         summ = timer.summary()
         n_all = {k: len(v) for k, v in timer.samples().items()}
@@ -589,37 +670,9 @@ def main():
         if pk_f is not None:
             step_roof.update(frac_of_measured_mfma_peak=conv_fl / step_s / (pk_f * 1e12), frac_of_measured_hbm_peak=conv_by / step_s / (pk_b * 1e9))
         breakdown = {k: {"n": n, "ms_total": round(t, 3)} for k, (n, t) in top}
-        result = {
-            "metric": "SED train clips/sec (60s,64-mel,9-layer CNN)", "value": value, "unit": "clips/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.precision,
-            "data": "synthetic",
-            "config": {"workload": f"Cnn_AvgPooling {a.config} widths {[c for c, _ in cfg]}, "
-                                   + (f"{T}-frame log-mel crops ({fcfg.mel_bins} mel), " if a.frames else
-                                      f"{a.seconds:g} s / {fcfg.working_sample_rate // 1000} kHz / {fcfg.mel_bins}-mel clips (T={T} frames, "
-                                      f"NFFT {fcfg.NFFT}, hop {fcfg.hop_size}), ")
-                                   + f"batch {B}/GPU, train step = "
-                                   f"{'features->' if a.no_frontend else 'waveform->log-mel->'}fwd->BCE->bwd->Adam-amsgrad"
-                                   + (", HIP-graph replay" if a.graph else ""),
-                       "frontend_constants": a.frontend, "graph_replay": bool(a.graph),
-                       "global_batch": world * B, "frames": T, "parallelism": f"dp{world}",
-                       "frontend_in_step": not a.no_frontend, "frontend_overlapped": bool(pf is not None), "frontend_overlap_mode": int(a.overlap_frontend),
-                       "sync_bn": bool(a.sync_bn) and grouped, "rccl_group": bool(grouped and a.backend == "nccl"),
-                       "collectives_executed": bool(trainer.reducer.enabled),
-                       "grad_buckets": [list(k) for k, _, _ in trainer.flat.buckets],
-                       # where a data-parallel step's communication goes (round 6): every bucket's all-reduce timed in isolation before
-                       # the timed region, the time the compute stream is blocked on the collectives after the backward's last kernel
-                       # (= exposed communication; instrumented pass), and the SyncBN collectives issued per step
-                       "comm": None if not trainer.reducer.enabled else {
-                           "backend": a.backend, "buckets": comm_iso[:-1], "flat_single_allreduce": comm_iso[-1],
-                           "exposed_ms_per_step": exposed_ms, "exposed_share_of_step": exposed_ms / (elapsed / a.steps * 1e3),
-                           "syncbn_collectives_per_step": bn_calls,
-                           "how": "isolated: 20 synchronous all-reduces per bucket, HIP events on the compute stream, MAX over ranks; exposed: "
-                                  "events around GradAllReducer.finish()'s waits (the compute stream idles there), rank 0, instrumented pass"}},
-            "loss": loss_val, "roofline": roof, "layer_roofline": layer_roof, "step_roofline": step_roof,
-            "kernel_breakdown_ms": breakdown,
-            "gpu_time_ms_per_step_sum_of_kernels": sum(per_step.values()),
-        }
+        result.update({"roofline": roof, "layer_roofline": layer_roof, "step_roofline": step_roof,
+                       "kernel_breakdown_ms": breakdown,
+                       "gpu_time_ms_per_step_sum_of_kernels": sum(per_step.values())})
         # ---- CPU baseline (oracle = "port"), N=1 only ----------------------------------------
         if world == 1 and not a.no_cpu_baseline:
             from oracle import cnn_oracle as O
@@ -674,6 +727,7 @@ def main():
                                       "sample": f"{n} train steps of batch {Bc} (same T={T}, same model/optimizer, "
                                                 f"{'features' if a.no_frontend else 'numpy front-end + '}ATen autograd "
                                                 f"restatement in oracle/), after 1 warm-up step"}
+    if rank == 0:
         if json_fd is not None:
             sys.stdout.flush()
             os.write(json_fd, (json.dumps(result) + "\n").encode())

@@ -149,7 +149,7 @@ def test_bench_launches_its_own_ranks(sync_bn):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SED_DDP_FORCE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--batch", "2", "--seconds", "4",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--sync-bn", str(sync_bn)]
+           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full", "--sync-bn", str(sync_bn)]
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]

@@ -4,7 +4,7 @@ import json
 import subprocess
 import sys
 
-out = subprocess.run([sys.executable, "bench.py", "--steps", "30", "--warmup", "5", "--no-cpu-baseline"], capture_output=True, text=True).stdout
+out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "30", "--warmup", "5", "--no-cpu-baseline"], capture_output=True, text=True).stdout
 d = json.loads([l for l in out.splitlines() if l.startswith('{"metric"')][0])
 kb = d["kernel_breakdown_ms"]
 pat = sys.argv[1] if len(sys.argv) > 1 else ":fwd"

@@ -8,7 +8,7 @@ import sys
 
 rx = re.compile(sys.argv[1])
 steps = sys.argv[2] if len(sys.argv) > 2 else "40"
-out = subprocess.run([sys.executable, "bench.py", "--steps", steps, "--warmup", "8", "--no-cpu-baseline"], capture_output=True, text=True)
+out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", steps, "--warmup", "8", "--no-cpu-baseline"], capture_output=True, text=True)
 d = json.loads(out.stdout.strip().splitlines()[-1])
 tot = 0.0
 rows = []

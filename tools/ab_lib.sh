@@ -9,7 +9,7 @@ out=$(mktemp -d)
 for r in $(seq 1 $rounds); do
   for v in a b; do
     cp $pk/ab/lib_$v.so $pk/libsed_hip.so
-    python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-measured-peaks "$@" 2>/dev/null \
+    python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-measured-peaks "$@" 2>/dev/null \
       | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('lib_$v', round(d['ms_per_step'],4), 'ms/step', 'sum of kernels', round(d['gpu_time_ms_per_step_sum_of_kernels'],4))" | tee -a $out/$v.txt
   done
 done

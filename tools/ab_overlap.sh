@@ -3,7 +3,7 @@
 out=gpurun_out/r04_overlap; mkdir -p $out
 for rep in 1 2 3; do
   for m in 0 1 2 3; do
-    python3 bench.py --overlap-frontend $m --steps 300 --warmup 30 --no-cpu-baseline > $out/m${m}_r${rep}.json 2> $out/m${m}_r${rep}.err || { echo "mode $m failed"; tail -5 $out/m${m}_r${rep}.err; }
+    python3 bench.py --full --overlap-frontend $m --steps 300 --warmup 30 --no-cpu-baseline > $out/m${m}_r${rep}.json 2> $out/m${m}_r${rep}.err || { echo "mode $m failed"; tail -5 $out/m${m}_r${rep}.err; }
     python3 - <<PY
 import json
 try:

@@ -2,7 +2,7 @@
 """Per-kernel instruction mix and issue rate from a rocprofv3 --pmc counter_collection.csv.
 
     rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_MFMA \
-              -d DIR -o NAME --output-format csv -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline
+              -d DIR -o NAME --output-format csv -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline
     python tools/inst_mix.py DIR/.../NAME_counter_collection.csv [clock_GHz]
 
 SQ_INSTS_* count wave-instructions summed over the chip; the duration is the dispatch's own Start/End timestamp in the

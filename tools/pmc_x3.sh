@@ -6,7 +6,7 @@ tag=${1:-r06_x3}
 out=$PWD/gpurun_out/pmc_x3
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-B="python3 bench.py --precision f16x3 --steps 3 --warmup 2 --no-cpu-baseline --no-measured-peaks"
+B="python3 bench.py --full --precision f16x3 --steps 3 --warmup 2 --no-cpu-baseline --no-measured-peaks"
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d $out/mfma -o $tag --output-format csv -- $B > /dev/null 2> $out/mfma.err
 rocprofv3 --kernel-trace -d $out/trace -o $tag --output-format csv -- $B > /dev/null 2> $out/trace.err
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_MFMA -d $out/mix -o $tag --output-format csv -- $B > /dev/null 2> $out/mix.err
