@@ -100,7 +100,15 @@ int sed_conv3x3_c1_wgrad_fused(int dtype, const float* x, const float* mean, con
                                const float* cc, float* dw_partial, int B, int H, int W, int Coutp,
                                void* stream);
 
-/* Generic layer (Cinp, Coutp multiples of 32; W a power of two, 4..64): implicit GEMM on MFMA.
+/* Line widths.  The generic layer calls below (sed_conv3x3_fwd, sed_conv3x3_wgrad[_u], sed_conv3x3_wgrad_fused[_u]) take any
+ * width 1 <= W <= SED_ANYW_MAX_W.  W in {8, 16, 32, 64} runs the specialised kernels (every dtype); any other W runs the
+ * width-general kernels (sed_conv3x3_fwd_anyw / sed_conv3x3_wgrad_anyw below), which cover SED_BF16 and SED_F32 only: SED_F32X3 /
+ * SED_F32H3 there return an error.  The fused weight-gradient forms need dz_out at those widths (dz is produced by
+ * sed_pool_relu_bn_bwd_apply / sed_bn_bwd_apply into dz_out, then read back).  Every *_supported query answers 0 outside
+ * {8, 16, 32, 64}.                                                                                                        */
+#define SED_ANYW_MAX_W 256
+
+/* Generic layer (Cinp, Coutp multiples of 32; W as above): implicit GEMM on MFMA.
  * Serves forward (wpack of W) and data-gradient (wpack of W', transpose_flip).
  *   x [B][H][W][Cinp]; pro_scale/pro_shift fp32 [Cinp] (SED_PRO_BNRELU);
  *   z [B][H][W][Coutp];
@@ -131,6 +139,18 @@ size_t sed_conv_wgrad_ws_floats(int B, int H, int W, int Cinp, int Coutp);
 int sed_conv3x3_wgrad(int dtype, int pro, const void* x, const float* pro_scale,
                       const float* pro_shift, const void* dz, float* dwpack, float* workspace,
                       int B, int H, int W, int Cinp, int Coutp, void* stream);
+
+/* The width-general kernels called directly, at any 1 <= W <= SED_ANYW_MAX_W (the specialised widths included; SED_BF16 /
+ * SED_F32): same arguments and results as sed_conv3x3_fwd (every prologue x epilogue pair) and sed_conv3x3_wgrad.  The
+ * workspace of sed_conv_wgrad_ws_floats() suffices; nparts = sed_conv_nparts(B, H, W).                                   */
+int sed_conv3x3_fwd_anyw(int dtype, int pro, int epi, const void* x, const float* pro_scale,
+                         const float* pro_shift, const void* wpack, void* z, const void* zref,
+                         const float* epi_scale, const float* epi_shift, const float* epi_mean,
+                         const float* epi_invstd, float* partial, int B, int H, int W, int Cinp,
+                         int Coutp, void* stream);
+int sed_conv3x3_wgrad_anyw(int dtype, int pro, const void* x, const float* pro_scale,
+                           const float* pro_shift, const void* dz, float* dwpack, float* workspace,
+                           int B, int H, int W, int Cinp, int Coutp, void* stream);
 
 /* Same weight gradient with the layer's dz PRODUCED on load (fused BatchNorm/ReLU/avg-pool backward,
  * i.e. the autograd nodes between two convolutions of ConvBlock.forward, spectogram_models.py:155-158):

@@ -341,6 +341,12 @@ int launch_conv_x3pc(ConvParams& p, int W, hipStream_t st);
 int launch_wgrad_x3pc(int dzmode, Wgrad2Params& p, int W, hipStream_t st);
 int launch_wgrad_x3(int half, int dzmode, Wgrad2Params& p, int W, int wn, hipStream_t st);
 
+// sed_conv_anyw.hip: the width-general forward / data gradient and weight gradient (dz given; DZ_POOL / DZ_BN by composition through
+// p.dz_out), any 1 <= W <= SED_ANYW_MAX_W, dtype SED_BF16 / SED_F32.  0 or an error code; the weight gradient leaves p.strips = slabs written
+// (at most the p.strips it was called with).
+int launch_conv_anyw(int dtype, ConvParams& p, int W, hipStream_t st);
+int launch_wgrad_anyw(int dtype, int dzmode, Wgrad2Params& p, int W, hipStream_t st);
+
 // sed_conv_pc.hip: bf16 forward / data gradient through the producer/consumer kernel; -1 = shape not covered
 // (the caller falls back to conv_igemm_kernel / conv_wreg_kernel), otherwise 0 / an error code after the launch.
 int launch_conv_pc(ConvParams& p, int W, hipStream_t st);

@@ -1326,7 +1326,8 @@ __global__ __launch_bounds__(256) void conv_c1_fwd_kernel(const float* __restric
 // With zsrc != NULL the layer's dz is produced on load: dz = ca*g + cb*z + cc (g = `dz` argument = output of
 // the data-gradient epilogue, z = the layer's pre-BN output); nothing is written back -- block 0 has no
 // data gradient, so its dz1 never needs to exist in memory.
-template <typename T, bool FUSED>
+// NPF: staged input values per thread, (C1_TR + 2) * (W + 2) <= NPF * 256 (4: W <= 100; 11: W <= SED_ANYW_MAX_W; c1_npf)
+template <typename T, bool FUSED, int NPF>
 __global__ __launch_bounds__(256) void conv_c1_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                             const float* __restrict__ stdv, const T* __restrict__ dz,
                                                             const T* __restrict__ zsrc, const float* __restrict__ ca,
@@ -1352,7 +1353,6 @@ __global__ __launch_bounds__(256) void conv_c1_wgrad_kernel(const float* __restr
     const int bands = (H + C1_TR - 1) / C1_TR;
     // the band's input lines are fetched one band ahead into registers (the load -> LDS -> barrier -> compute chain of the
     // first version exposed a full memory latency per band: 31 bands x ~2.5 us per workgroup)
-    constexpr int NPF = 4;                                   // staged values per thread: (C1_TR + 2) * (W + 2) <= 4 * 256
     const int nstage = (C1_TR + 2) * WP2;
     float pf[NPF];
     auto fetch = [&](int band) {
@@ -1444,6 +1444,7 @@ __global__ __launch_bounds__(256) void conv_c1_wgrad_kernel(const float* __restr
 // sx[k] = sum_px xp[k] depend on the input alone: z1 is never read (and is exact instead of bf16-rounded).
 // conv_c1_gram_kernel: partial[block][54] = 45 products (j <= k, row-major upper triangle) then the 9 sums.
 // -------------------------------------------------------------------------------------------------
+template <int SIT>      // items per thread: (C1_TR + 2) * (W + 2) <= SIT * 256 (c1_npf)
 __global__ __launch_bounds__(256) void conv_c1_gram_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                            const float* __restrict__ stdv, float* __restrict__ partial,
                                                            int B, int H, int W) {
@@ -1459,7 +1460,6 @@ __global__ __launch_bounds__(256) void conv_c1_gram_kernel(const float* __restri
     // a thread's staging items are the same (row, column) of every band: index arithmetic and the z-score constants are hoisted out of
     // the band loop (they were more than half of the kernel's instructions); z-score as (v - mean) * (1 / std), the form of the
     // convolution kernels' input copy (conv_common.h / sed_conv_pc.hip)
-    constexpr int SIT = 4;                                  // items per thread: (C1_TR + 2) * (W + 2) <= 4 * 256 (checked by the launcher)
     int srow[SIT], scol[SIT];
     float smu[SIT], sinv[SIT];
 #pragma unroll
@@ -1891,11 +1891,14 @@ static int dispatch_wreg(ConvParams& p, int W, hipStream_t st) {
     return 1;
 }
 
+// the line widths the specialised kernels are compiled for; every other width takes csrc/sed_conv_anyw.hip
+static inline bool sed_w_specialised(int W) { return W == 8 || W == 16 || W == 32 || W == 64; }
+
 static int conv3x3_fwd_impl(int dtype, int pro, int epi, const void* x, const float* pro_scale,
                             const float* pro_shift, const void* wpack, void* z, const void* zref,
                             const float* epi_scale, const float* epi_shift, const float* epi_mean,
                             const float* epi_invstd, float* partial, int B, int H, int W, int Cinp, int Coutp,
-                            void* stream, int col_only) {
+                            void* stream, int col_only, bool anyw = false) {
     // SED_F32H3: bits 8..15 of dtype = signed power-of-two exponent applied to the streamed operand x before the fp16 split (gradients)
     const int xexp = (int)(signed char)((dtype >> 8) & 0xff);
     dtype &= 0xff;
@@ -1917,6 +1920,13 @@ static int conv3x3_fwd_impl(int dtype, int pro, int epi, const void* x, const fl
     { const char* d = sed_getenv("SED_DBG"); p.dbg = d ? atoi(d) : 0; }
     p.nparts = sed_conv_nparts(B, H, W);
     int rc;
+    // widths outside the specialised set (and the direct _anyw entry): the width-general kernels (csrc/sed_conv_anyw.hip)
+    if (anyw || !sed_w_specialised(W)) {
+        rc = launch_conv_anyw(dtype, p, W, (hipStream_t)stream);
+        if (rc) return rc;
+        SED_LAUNCH_CHECK();
+        return 0;
+    }
     // bf16: the register-stationary-weights kernel wins when a workgroup covers 128 output channels
     // (MFMA-bound layers); the LDS-weights kernel (2 workgroups/CU) wins on the low-channel,
     // memory-bound layers.  SED_CONV_KERNEL=lds|wreg forces one of them (A/B runs).
@@ -2057,11 +2067,20 @@ extern "C" int sed_conv3x3_fwd_col(int dtype, int pro, int epi, const void* x, c
                             partial, B, H, W, Cinp, Coutp, stream, 1);
 }
 
+extern "C" int sed_conv3x3_fwd_anyw(int dtype, int pro, int epi, const void* x, const float* pro_scale,
+                                    const float* pro_shift, const void* wpack, void* z, const void* zref,
+                                    const float* epi_scale, const float* epi_shift, const float* epi_mean,
+                                    const float* epi_invstd, float* partial, int B, int H, int W, int Cinp, int Coutp,
+                                    void* stream) {
+    return conv3x3_fwd_impl(dtype, pro, epi, x, pro_scale, pro_shift, wpack, z, zref, epi_scale, epi_shift, epi_mean, epi_invstd,
+                            partial, B, H, W, Cinp, Coutp, stream, 0, true);
+}
+
 static int wgrad_strips(int B, int H, int W, int Cinp, int Coutp, int* wn_out) {
     const int wn = Coutp % 128 == 0 ? 4 : (Coutp % 64 == 0 ? 2 : 1);
     if (wn_out) *wn_out = wn;
     const int ny = (Cinp / 32) * (Coutp / (32 * wn));
-    const int TH = 128 / W;
+    const int TH = (W >= 1 && W <= 128) ? 128 / W : 1;      // (W > 128: one row per tile)
     const long long tiles = (long long)B * cdiv(H, TH);
     long long target = (ny == 1) ? 1024 : 512;     // measured optimum (tools/bench_layer.py sweep); total workgroups
     if (const char* e = sed_getenv("SED_WGRAD_BLOCKS")) target = atoll(e) > 0 ? atoll(e) : target;   // tuning knob
@@ -2121,7 +2140,8 @@ static int dispatch_wgrad2(Wgrad2Params& p, int W, int wn, hipStream_t st) {
 static int wgrad_common(int dtype, int pro, int dzmode, const void* x, const float* pro_scale, const float* pro_shift,
                         const void* dz, const void* zsrc, const float* scale, const float* shift, const float* ca,
                         const float* cb, const float* cc, int pool, void* dz_out, float* dwpack, float* workspace,
-                        int B, int H, int W, int Cinp, int Coutp, hipStream_t st, float* dw = nullptr, int Cout = 0, int Cin = 0) {
+                        int B, int H, int W, int Cinp, int Coutp, hipStream_t st, float* dw = nullptr, int Cout = 0, int Cin = 0,
+                        bool anyw = false) {
     const int dzexp = (int)(signed char)((dtype >> 8) & 0xff);      // SED_F32H3: exponent applied to dz before the fp16 split
     dtype &= 0xff;
     if (dzexp != 0 && dtype != SED_F32H3) { sed_set_error("sed_conv3x3_wgrad: an operand exponent belongs to dtype SED_F32H3"); return 1; }
@@ -2138,7 +2158,10 @@ static int wgrad_common(int dtype, int pro, int dzmode, const void* x, const flo
     p.B = B; p.H = H; p.Cinp = Cinp; p.Coutp = Coutp; p.pro = pro; p.pool = pool < 1 ? 1 : pool;
     { const char* d = sed_getenv("SED_DBG"); p.dbg = d ? atoi(d) : 0; }
     int rc = 1;
-    if (dtype == SED_BF16) {           // producer/consumer kernel (sed_wgrad.hip) where the shape is covered
+    if (anyw || !sed_w_specialised(W)) {      // the width-general kernel (csrc/sed_conv_anyw.hip); p.strips: at most wgrad_strips()
+        if (B <= 0 || H <= 0) { sed_set_error("sed_conv3x3_wgrad: empty input"); return 1; }
+        rc = launch_wgrad_anyw(dtype, dzmode, p, W, st);
+    } else if (dtype == SED_BF16) {           // producer/consumer kernel (sed_wgrad.hip) where the shape is covered
         rc = launch_wgrad3(dzmode, p, W, st);
     } else {
         rc = -1;
@@ -2182,6 +2205,15 @@ extern "C" int sed_conv3x3_wgrad(int dtype, int pro, const void* x, const float*
     SED_REQUIRE(pro == SED_PRO_NONE || (pro_scale && pro_shift), "prologue operands");
     return wgrad_common(dtype, pro, DZ_GIVEN, x, pro_scale, pro_shift, dz, nullptr, nullptr, nullptr, nullptr, nullptr,
                         nullptr, 1, nullptr, dwpack, workspace, B, H, W, Cinp, Coutp, (hipStream_t)stream);
+}
+
+extern "C" int sed_conv3x3_wgrad_anyw(int dtype, int pro, const void* x, const float* pro_scale, const float* pro_shift,
+                                      const void* dz, float* dwpack, float* workspace, int B, int H, int W, int Cinp,
+                                      int Coutp, void* stream) {
+    SED_REQUIRE(Cinp % 32 == 0 && Coutp % 32 == 0, "channels must be padded to 32");
+    SED_REQUIRE(pro == SED_PRO_NONE || (pro_scale && pro_shift), "prologue operands");
+    return wgrad_common(dtype, pro, DZ_GIVEN, x, pro_scale, pro_shift, dz, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, 1, nullptr, dwpack, workspace, B, H, W, Cinp, Coutp, (hipStream_t)stream, nullptr, 0, 0, true);
 }
 
 extern "C" int sed_conv3x3_wgrad_u(int dtype, int pro, const void* x, const float* pro_scale, const float* pro_shift, const void* dz,
@@ -2319,6 +2351,13 @@ static int c1_wgrad_common(int dtype, const float* x, const float* mean, const f
                            const void* zsrc, const float* ca, const float* cb, const float* cc, float* dw_partial, int B,
                            int H, int W, int Coutp, void* stream);
 
+// staged values per thread of the first-layer kernels that hold a band of C1_TR + 2 input lines: 4 up to W = 100 (the specialised
+// widths), 11 up to SED_ANYW_MAX_W; 0 = W not covered
+static int c1_npf(int W) {
+    const int n = (C1_TR + 2) * (W + 2);
+    return W < 1 ? 0 : n <= 4 * 256 ? 4 : n <= 11 * 256 ? 11 : 0;
+}
+
 extern "C" int sed_conv3x3_c1_wgrad(int dtype, const float* x, const float* mean, const float* stdv, const void* dz,
                                     float* dw_partial, int B, int H, int W, int Coutp, void* stream) {
     return c1_wgrad_common(dtype, x, mean, stdv, dz, nullptr, nullptr, nullptr, nullptr, dw_partial, B, H, W, Coutp, stream);
@@ -2341,14 +2380,19 @@ static int c1_wgrad_common(int dtype, const float* x, const float* mean, const f
     const int grid = sed_conv_c1_nparts(B, H, W);
     const size_t lds = ((C1_TR + 2) * (size_t)(W + 2) + (size_t)PPB * Coutp) * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == SED_BF16)
-        if (zsrc) conv_c1_wgrad_kernel<bf16_t, true><<<grid, threads, lds, st>>>(x, mean, stdv, (const bf16_t*)dz, (const bf16_t*)zsrc, ca, cb, cc, dw_partial, B, H, W, Coutp, G, PPB);
-        else conv_c1_wgrad_kernel<bf16_t, false><<<grid, threads, lds, st>>>(x, mean, stdv, (const bf16_t*)dz, nullptr, ca, cb, cc, dw_partial, B, H, W, Coutp, G, PPB);
-    else if (dtype == SED_F32)
-        if (zsrc) conv_c1_wgrad_kernel<float, true><<<grid, threads, lds, st>>>(x, mean, stdv, (const float*)dz, (const float*)zsrc, ca, cb, cc, dw_partial, B, H, W, Coutp, G, PPB);
-        else conv_c1_wgrad_kernel<float, false><<<grid, threads, lds, st>>>(x, mean, stdv, (const float*)dz, nullptr, ca, cb, cc, dw_partial, B, H, W, Coutp, G, PPB);
-    else
+    const int npf = c1_npf(W);
+    SED_REQUIRE(npf > 0, "W must be in [1, SED_ANYW_MAX_W]");
+#define SED_C1W(N_)                                                                                                                         \
+    if (dtype == SED_BF16)                                                                                                                  \
+        if (zsrc) conv_c1_wgrad_kernel<bf16_t, true, N_><<<grid, threads, lds, st>>>(x, mean, stdv, (const bf16_t*)dz, (const bf16_t*)zsrc, ca, cb, cc, dw_partial, B, H, W, Coutp, G, PPB); \
+        else conv_c1_wgrad_kernel<bf16_t, false, N_><<<grid, threads, lds, st>>>(x, mean, stdv, (const bf16_t*)dz, nullptr, ca, cb, cc, dw_partial, B, H, W, Coutp, G, PPB); \
+    else if (dtype == SED_F32)                                                                                                              \
+        if (zsrc) conv_c1_wgrad_kernel<float, true, N_><<<grid, threads, lds, st>>>(x, mean, stdv, (const float*)dz, (const float*)zsrc, ca, cb, cc, dw_partial, B, H, W, Coutp, G, PPB); \
+        else conv_c1_wgrad_kernel<float, false, N_><<<grid, threads, lds, st>>>(x, mean, stdv, (const float*)dz, nullptr, ca, cb, cc, dw_partial, B, H, W, Coutp, G, PPB); \
+    else                                                                                                                                    \
         SED_REQUIRE(false, "bad dtype");
+    if (npf == 4) { SED_C1W(4) } else { SED_C1W(11) }
+#undef SED_C1W
     SED_LAUNCH_CHECK();
     return 0;
 }
@@ -2364,10 +2408,12 @@ extern "C" int sed_conv_c1_gram_nparts(int B, int H, int W) {
 extern "C" int sed_conv3x3_c1_gram(const float* x, const float* mean, const float* stdv, float* gram_partial, int B, int H,
                                    int W, void* stream) {
     SED_REQUIRE((mean == nullptr) == (stdv == nullptr), "mean/std must both be given or both NULL");
-    SED_REQUIRE(W >= 1 && (C1_TR + 2) * (W + 2) <= 4 * 256, "W must be <= 100 (one band of input lines is staged by 256 threads)");
+    const int npf = c1_npf(W);
+    SED_REQUIRE(npf > 0, "W must be in [1, SED_ANYW_MAX_W] (one band of input lines is staged by 256 threads)");
     const int grid = sed_conv_c1_gram_nparts(B, H, W); // every row of gram_partial is written (the combine reads nparts rows)
     const size_t lds = ((C1_TR + 2) * (size_t)(W + 2) + 4 * 54) * sizeof(float);
-    conv_c1_gram_kernel<<<grid, 256, lds, (hipStream_t)stream>>>(x, mean, stdv, gram_partial, B, H, W);
+    if (npf == 4) conv_c1_gram_kernel<4><<<grid, 256, lds, (hipStream_t)stream>>>(x, mean, stdv, gram_partial, B, H, W);
+    else conv_c1_gram_kernel<11><<<grid, 256, lds, (hipStream_t)stream>>>(x, mean, stdv, gram_partial, B, H, W);
     SED_LAUNCH_CHECK();
     return 0;
 }

@@ -40,6 +40,10 @@ def num_pools_of(model_config) -> int:
     return n
 
 
+SPECIALISED_WIDTHS = (8, 16, 32, 64)     # line widths of the specialised conv kernels; others: csrc/sed_conv_anyw.hip
+MAX_WIDTH = 256                          # SED_ANYW_MAX_W (include/sed_hip.h)
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -63,6 +67,7 @@ class _Layer:
     wpack_t: torch.Tensor = None    # data-gradient operator
     dwpack: torch.Tensor = None
     coef: torch.Tensor = None       # [3][Cp] ca, cb, cc
+    dt_mm: int = 0                  # dtype of the layer's GEMM-shaped launches (operator packing, forward, gradients)
 
 
 @dataclass
@@ -131,12 +136,15 @@ class KernelTimer:
 
 class CnnEngine:
     def __init__(self, classes_num: int, model_config: Sequence[Tuple[int, int]], in_channels: int = 1,
-                 precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False):
+                 precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
+                 mel_bins: Optional[int] = None):
         """head: 'fc' (Cnn_AvgPooling), 'gru' (CRNN) or 'none' (a bare stack of ConvBlocks: forward() stops at the last
         pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
         Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and backward() also produces the input gradient
         plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path keeps the dedicated Cin = 1
-        kernels (no input gradient exists there)."""
+        kernels (no input gradient exists there).  mel_bins: None -> every block's width must be one the specialised kernels
+        are built for (8 / 16 / 32 / 64); an integer F -> inputs must be F wide (1 <= F <= 256) and blocks at other widths run the
+        width-general kernels (csrc/sed_conv_anyw.hip; under 'f16x3' / 'bf16x3' those layers take the exact fp32 kernels)."""
         if precision not in ("bf16", "fp32", "bf16x3", "f16x3"):
             raise ValueError("precision must be 'bf16', 'fp32', 'f16x3' or 'bf16x3'")
         if head not in ("fc", "gru", "none"):
@@ -144,6 +152,7 @@ class CnnEngine:
         if head == "gru" and (gru_hidden % 32 or not 32 <= gru_hidden <= 256):
             raise ValueError("gru_hidden must be a multiple of 32 in [32, 256]")
         self.head, self.Hd = head, int(gru_hidden)
+        self.mel_bins = self.check_mel_bins(mel_bins)
         for (_, p) in model_config:
             if p not in (1, 2):
                 raise ValueError("pool sizes must be 1 or 2")
@@ -173,11 +182,36 @@ class CnnEngine:
         self.bn_sync = None
         self.wg_flush_per_group = False      # set by FusedTrainer under data parallel (see backward: group_done)
 
+    @staticmethod
+    def check_mel_bins(mel_bins):
+        """None or a positive int (the range against the kernels' limit is checked when a plan is built)"""
+        if mel_bins is None:
+            return None
+        if isinstance(mel_bins, bool) or not isinstance(mel_bins, int) or mel_bins < 1:
+            raise ValueError(f"mel_bins must be None or a positive integer, got {mel_bins!r}")
+        return int(mel_bins)
+
+    def _check_width(self, T: int, F: int) -> None:
+        """plan-time width checks of a declared model (before any launch)"""
+        if F != self.mel_bins:
+            raise ValueError(f"input width {F} differs from the declared mel_bins={self.mel_bins}")
+        if F > MAX_WIDTH:
+            raise ValueError(f"mel_bins={F} unsupported: the width-general kernels cover 1..{MAX_WIDTH}")
+        W = F
+        for bi, (_, pool) in enumerate(self.cfg):
+            if W < 1:
+                raise ValueError(f"mel_bins={F}: the pooling stack leaves block {bi} with width {W}")
+            W //= pool
+        if W < 1:
+            raise ValueError(f"mel_bins={F}: the pooling stack leaves the head with width {W}")
+
     def _grad_dtype(self, B: int, H: int, W: int) -> int:
         """dtype argument of a GEMM-shaped BACKWARD launch.  f16x3: fp16 pieces have five exponent bits and a loss gradient is ~1/(B*H*W)
         per element (mean-reduced BCE spread over the layer's pixels), so the streamed gradient operand is scaled by 2^e before the
         split, e = round(log2(B*H*W)) + 2 (the kernel scales the result back; bits 8..15 of dtype, include/sed_hip.h).  fp16's normal
         range leaves ~13 binades either side of that estimate."""
+        if W not in SPECIALISED_WIDTHS:
+            return self.dt           # width-general kernels: exact fp32 under the split-operand modes, no pre-scale exponent
         if self.dt_mm != L.SED_F32H3:
             return self.dt_mm
         import math
@@ -202,8 +236,8 @@ class CnnEngine:
         key = (B, T, F, str(device))
         if key in self._plans:
             return self._plans[key]
-        if F not in (8, 16, 32, 64) and len(self.cfg) > 0:
-            pass
+        if self.mel_bins is not None:
+            self._check_width(T, F)
         lib = self.lib
         dev = device
         p = _Plan(B, T, F)
@@ -213,7 +247,7 @@ class CnnEngine:
         max_wgrad_ws = 0
         max_bwd_parts = 0
         for bi, (c, pool) in enumerate(self.cfg):
-            if W not in (8, 16, 32, 64):
+            if W not in SPECIALISED_WIDTHS and self.mel_bins is None:
                 raise ValueError(f"mel width {W} at block {bi} unsupported (need 8/16/32/64)")
             if pool == 2 and (H < 2 or W < 2):
                 raise ValueError("input too short for the pooling stack")
@@ -222,6 +256,8 @@ class CnnEngine:
                 first = (bi == 0 and j == 0 and not self.generic_first)     # the dedicated Cin = 1 kernels
                 cinp = 1 if first else pad32(ci)
                 ly = _Layer(ci, co, cinp, pad32(co), H, W)
+                # the split-operand modes cover the specialised widths only: the width-general kernels run those layers in exact fp32
+                ly.dt_mm = self.dt_mm if W in SPECIALISED_WIDTHS else self.dt
                 nparts = lib.sed_conv_c1_nparts(B, H, W) if first else lib.sed_conv_nparts(B, H, W)
                 ly.z = torch.empty((B, H, W, ly.coutp), dtype=self.tdtype, device=dev)
                 ly.part = torch.empty((nparts, 2, ly.coutp), **f32)
@@ -525,22 +561,24 @@ class CnnEngine:
                     continue
                 ly = p.layers[bi][j]
                 w = P[f"conv_blocks.{bi}.conv{j + 1}.weight"]
-                ents.append((w.data_ptr(), ly.wpack.data_ptr(), ly.cout, ly.cin, ly.coutp, ly.cinp, 0))
+                ents.append((ly.dt_mm, (w.data_ptr(), ly.wpack.data_ptr(), ly.cout, ly.cin, ly.coutp, ly.cinp, 0)))
                 if training:
-                    ents.append((w.data_ptr(), ly.wpack_t.data_ptr(), ly.cout, ly.cin, ly.cinp, ly.coutp, 1))
-        key = tuple(ents)
+                    ents.append((ly.dt_mm, (w.data_ptr(), ly.wpack_t.data_ptr(), ly.cout, ly.cin, ly.cinp, ly.coutp, 1)))
         cache = getattr(p, "pack_tables", None)
         if cache is None:
             cache = p.pack_tables = {}
-        if key not in cache:
-            rows, blk = [], 0
-            for (wp, op, co, ci, pop, pip_, tf) in ents:
-                rows.append([wp, op, co, ci, pop, pip_, tf, blk])
-                blk += (pip_ * 9 * pop + 1023) // 1024
-            cache[key] = (torch.tensor(rows, dtype=torch.int64).to(p.layers[0][0].z.device), len(rows), blk)
-        desc, n, blocks = cache[key]
-        if n:
-            self._k("sed_pack_conv_weights_batch", self.lib.sed_pack_conv_weights_batch, self.dt_mm, L.ptr(desc), n, blocks, _stream())
+        # one launch per operator dtype (a single one unless a split-operand model has layers at non-specialised widths)
+        for dtm in sorted({d for d, _ in ents}, key=lambda d: d != self.dt_mm):
+            key = (dtm,) + tuple(e for d, e in ents if d == dtm)
+            if key not in cache:
+                rows, blk = [], 0
+                for (wp, op, co, ci, pop, pip_, tf) in key[1:]:
+                    rows.append([wp, op, co, ci, pop, pip_, tf, blk])
+                    blk += (pip_ * 9 * pop + 1023) // 1024
+                cache[key] = (torch.tensor(rows, dtype=torch.int64).to(p.layers[0][0].z.device), len(rows), blk)
+            desc, n, blocks = cache[key]
+            if n:
+                self._k("sed_pack_conv_weights_batch", self.lib.sed_pack_conv_weights_batch, dtm, L.ptr(desc), n, blocks, _stream())
 
     def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], training: bool,
                 feat_mean: Optional[torch.Tensor] = None, feat_std: Optional[torch.Tensor] = None,
@@ -591,7 +629,7 @@ class CnnEngine:
                     else:
                         l1 = p.layers[bi][0]
                         src, pro, ps, ph = l1.z, L.PRO_BNRELU, l1.scale, l1.shift
-                    self._k("sed_conv3x3_fwd", self.lib.sed_conv3x3_fwd, self.dt_mm, pro, L.EPI_STATS if training else L.EPI_STORE, L.ptr(src),
+                    self._k("sed_conv3x3_fwd", self.lib.sed_conv3x3_fwd, ly.dt_mm, pro, L.EPI_STATS if training else L.EPI_STORE, L.ptr(src),
                                                 L.ptr(ps), L.ptr(ph), L.ptr(ly.wpack), L.ptr(ly.z), None, None, None,
                                                 None, None, L.ptr(part), B, ly.H, ly.W, ly.cinp, ly.coutp, st)
                 if training and first and c1m:

@@ -26,6 +26,8 @@ def build_parser():
     p.add_argument("--mean_std", type=str, default="", help="features_mean_std pickle of the training set")
     p.add_argument("--threshold", type=float, default=0.5)
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "f16x3", "bf16x3"])
+    p.add_argument("--mel_bins", type=int, default=None,
+                   help="log-mel bins of the front-end and the model's declared input width, 1..256 (default: the config's 64)")
     return p
 
 
@@ -35,24 +37,36 @@ def onset_frames(decisions):
     return np.flatnonzero(np.diff(np.concatenate(([0], d))) == 1)
 
 
-def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, precision="bf16"):
+def load_mean_std(mean_std, mel_bins):
+    """(mean, std) of a features_mean_std pickle; each must hold one entry per mel bin"""
+    with open(mean_std, "rb") as f:
+        d = pickle.load(f)
+    mean, std = d["mean"], d["std"]
+    for name, v in (("mean", mean), ("std", std)):
+        if np.asarray(v).size != mel_bins:
+            raise ValueError(f"--mean_std {mean_std}: {name} has {np.asarray(v).size} entries, the model takes {mel_bins} mel bins")
+    return mean, std
+
+
+def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, precision="bf16", mel_bins=None):
+    import dataclasses
     from .dataset.dataset_utils import read_multichannel_audio
     from .dataset.spectogram.preprocess import LogMelFrontEnd
     from .dataset.spectogram.spectogram_configs import REF_NATIVE as cfg
     from .models.spectogram_models import Cnn_AvgPooling
+    n_mel = cfg.mel_bins if mel_bins is None else int(mel_bins)
+    cfg = dataclasses.replace(cfg, mel_bins=n_mel)
+    mean = std = None
+    if mean_std:
+        mean, std = load_mean_std(mean_std, n_mel)
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X visible: this build has no CPU inference path")
     dev = torch.device(device)
-    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)]).to(dev)
+    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel).to(dev)
     model.set_precision(precision)
     checkpoint = torch.load(ckpt, map_location=dev)
     model.load_state_dict(checkpoint["model"] if "model" in checkpoint else checkpoint)
     model.eval()
-    mean = std = None
-    if mean_std:
-        with open(mean_std, "rb") as f:
-            d = pickle.load(f)
-        mean, std = d["mean"], d["std"]
     print("Preprocessing audio file..")
     audio = read_multichannel_audio(audio_path=audio_file, target_fs=cfg.working_sample_rate, cfg=cfg)
     fe = LogMelFrontEnd(cfg, device=dev, mean=mean, std=std)
@@ -69,7 +83,7 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    res = infer_file(args.audio_file, args.ckpt, args.device, args.mean_std, args.threshold, args.precision)
+    res = infer_file(args.audio_file, args.ckpt, args.device, args.mean_std, args.threshold, args.precision, args.mel_bins)
     os.makedirs(args.outputs_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(args.audio_file))[0]
     fps = res["frames_per_second"]

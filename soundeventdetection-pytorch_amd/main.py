@@ -9,6 +9,7 @@ stand-in task for either feature type."""
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import os
 
 import torch
@@ -50,6 +51,8 @@ def build_parser():
                    help="accepted for compatibility: batches are assembled on the GPU, there are no workers")
     # this build only
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "f16x3", "bf16x3"])
+    p.add_argument("--mel_bins", type=int, default=None,
+                   help="log-mel bins of the features and the model's declared input width, 1..256 (default: the config's 64)")
     return p
 
 
@@ -72,10 +75,12 @@ def get_spectogram_dataset_model_and_criterion(args, device):
     from .dataset.synthetic import SyntheticSedDataset
     from .models.spectogram_models import Cnn_AvgPooling
     cfg = cfgs.REF_NATIVE
+    n_mel = cfg.mel_bins if getattr(args, "mel_bins", None) is None else int(args.mel_bins)
+    cfg = dataclasses.replace(cfg, mel_bins=n_mel)
     name = args.dataset_name.lower()
     if name == "synthetic":
         dataset = SyntheticSedDataset(n_train_crops=max(256, 4 * args.batch_size), crop=cfg.train_crop_size * 8,
-                                      classes=cfg.classes_num)
+                                      classes=cfg.classes_num, mel_bins=n_mel)
         descriptor = cfg.cfg_descriptor
     else:
         if name == "tau":
@@ -93,7 +98,7 @@ def get_spectogram_dataset_model_and_criterion(args, device):
                                     balance_classes=args.balance_classes,
                                     val_descriptor=_val_descriptor(args.val_descriptor),
                                     preprocessed_mode=args.preprocess_mode, cfg=cfg, device=device)
-    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)])
+    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel)
     model.set_precision(args.precision)
     if args.ckpt != "":
         checkpoint = torch.load(args.ckpt, map_location=device)

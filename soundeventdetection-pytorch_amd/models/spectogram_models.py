@@ -207,8 +207,12 @@ class _ModelFunction(torch.autograd.Function):
 
 
 class Cnn_AvgPooling(nn.Module):
-    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None):
+    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, mel_bins=None):
+        '''mel_bins: the declared input width (mel-bin count).  None: the specialised widths only (8 / 16 / 32 / 64 at every
+        block), as before.  An integer F in [1, 256]: inputs of width F only; blocks at other widths run the width-general
+        kernels.  The parameters do not depend on it: a checkpoint loads into a model of any declared width.'''
         super().__init__()
+        self.mel_bins = CnnEngine.check_mel_bins(mel_bins)
         self.model_config = model_config
         self.classes_num = classes_num
         self.precision = precision or DEFAULT_PRECISION
@@ -245,7 +249,7 @@ class Cnn_AvgPooling(nn.Module):
         self.event_fc = _LinearParams(c_last, classes_num)
 
     def _make_engine(self, precision):
-        return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision)
+        return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, mel_bins=self.mel_bins)
 
     def set_precision(self, precision: str):
         self.precision = precision
@@ -275,7 +279,7 @@ class Cnn_AvgPooling(nn.Module):
 
     def model_description(self, working_sample_rate=48000, hop_size=15840):
         print("Model description")
-        b, w = 'b', MEL_BINS
+        b, w = 'b', MEL_BINS if self.mel_bins is None else self.mel_bins
         h = 60 * working_sample_rate // hop_size
         c = AUDIO_CHANNELS
         print(f"\tInput: ({b}, {c}, {h}, {w})")
@@ -317,9 +321,9 @@ class Crnn_AvgPooling(Cnn_AvgPooling):
     Linear(512, classes) -> interpolate.  state_dict: conv_blocks.*, gru.{weight_ih_l0,...,
     bias_hh_l0_reverse} (loadable into torch.nn.GRU), event_fc.{weight (classes, 2*hidden), bias}."""
 
-    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, gru_hidden=256):
+    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, gru_hidden=256, mel_bins=None):
         self.gru_hidden = int(gru_hidden)
-        super().__init__(classes_num, model_config, precision)
+        super().__init__(classes_num, model_config, precision, mel_bins=mel_bins)
 
     def _build_head(self, c_last, classes_num):
         self.gru = _GruParams(c_last, self.gru_hidden)
@@ -327,4 +331,4 @@ class Crnn_AvgPooling(Cnn_AvgPooling):
 
     def _make_engine(self, precision):
         return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="gru",
-                         gru_hidden=self.gru_hidden)
+                         gru_hidden=self.gru_hidden, mel_bins=self.mel_bins)
