@@ -38,7 +38,9 @@ extern "C" {
  * LS = 2^11, ~5e-7 per product; because fp16 has five exponent bits, a call whose streamed operand is a GRADIENT (the data gradient's
  * x = dz, the weight gradient's dz) carries a signed power-of-two exponent e in bits 8..15 of the dtype argument
  * (dtype = SED_F32H3 | ((e & 0xff) << 8)): the operand is multiplied by 2^e before the split (and clamped to +-60000), the result by
- * 2^-e; e ~ log2(B*H*W) - 4 brings per-pixel loss gradients to O(1).  Every other entry point takes SED_F32 for such tensors.        */
+ * 2^-e; e = round(log2(B*H*W)) + 2 (engine.CnnEngine._grad_dtype) brings a per-pixel loss gradient ~1/(B*H*W) to ~4, and the f16x3
+ * gate holds for true gradient scales 2^(-e-12) .. 2^(-e+12) (tests/test_gpu_conv_exact_oracle.py).  Every other entry point takes
+ * SED_F32 for such tensors.                                                                                                         */
 enum { SED_F32 = 0, SED_BF16 = 1, SED_F32X3 = 2, SED_F32H3 = 3 };
 
 /* prologue applied to the conv input while it is staged into LDS */
