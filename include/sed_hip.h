@@ -541,6 +541,33 @@ int sed_bn_bwd_finalize_c1(const float* partial, int nparts, double count, const
                            const float* w1, const float* gamma, const float* mean, const float* invstd,
                            float* dgamma, float* dbeta, float* ca, float* cb, float* cc, int C, int Cp,
                            void* stream);
+/* ---- input gradient of the Cin = 1 first layer (csrc/sed_c1_dgrad.hip) ------------------------------------------------
+ * Replaces autograd through conv1 / BN1 of the first ConvBlock down to the model input (spectogram_models.py:153-160):
+ *   dz1 = ca*g + cb*z + cc  (BN1 backward, inside the image only),   dx[b][h][w] = sum_{c, tap} w1[c][tap] * dz1[b][h - dh][w - dw][c].
+ * g, z [B][H][W][Coutp] (dtype SED_BF16 or SED_F32 storage), w1 fp32 [Cout][1][3][3] torch layout, ca / cb / cc fp32 [Coutp],
+ * dx fp32 [B][H][W] (= the (B, 1, T, F) input gradient), fp32 accumulation.  z = NULL: z1 is recomputed from x [B][H][W] fp32
+ * (z-scored on load with fmean / fstd [W] when given, as sed_conv3x3_c1_fwd).  fmean / fstd given: dx is the gradient with
+ * respect to the RAW features (divided by fstd[w]).  1 <= W <= SED_ANYW_MAX_W, B <= 65535.                                     */
+int sed_conv3x3_c1_dgrad(int dtype, const void* g, const void* z, const float* x, const float* fmean, const float* fstd,
+                         const float* w1, const float* ca, const float* cb, const float* cc, float* dx, int B, int H, int W,
+                         int Cout, int Coutp, void* stream);
+/* ---- eval-mode (running-statistics) BatchNorm backward -------------------------------------------------------------------
+ * Autograd through nn.BatchNorm2d in eval mode (spectogram_models.py:155-158 under model.eval()): BN is the fixed affine map
+ * gamma*(z - mean_r)*invstd_r + beta.  sed_bn_eval_stats writes mean = running_mean, invstd = 1/sqrt(running_var + eps) (0 in
+ * the padded channels): the (mean, invstd) operands the backward statistics kernels take (their partial rows then hold
+ * (sum g, sum g*xhat) with xhat in running statistics).  The finalize reduces those rows: dbeta = sum g, dgamma = sum g*xhat,
+ * ca = gamma*invstd, cb = cc = 0.  The C1 form takes sum g from row 0 only and sum g*z1 = w1 . a_sum (a_sum [9][Cp], as
+ * sed_bn_bwd_finalize_c1).                                                                                                    */
+/* out[0] = max |x[i]| over n fp32 elements (one device float; the upstream-gradient magnitude behind the f16x3 pre-scale of an
+ * input-gradient or eval-mode backward, CnnEngine._grad_dtype).                                                               */
+int sed_absmax(const float* x, size_t n, float* out, void* stream);
+int sed_bn_eval_stats(const float* running_mean, const float* running_var, float eps, float* mean, float* invstd, int C, int Cp,
+                      void* stream);
+int sed_bn_eval_bwd_finalize(const float* partial, int nparts, const float* gamma, const float* mean, const float* invstd,
+                             float* dgamma, float* dbeta, float* ca, float* cb, float* cc, int C, int Cp, void* stream);
+int sed_bn_eval_bwd_finalize_c1(const float* partial, int nparts, const float* a_sum, const float* w1, const float* gamma,
+                                const float* mean, const float* invstd, float* dgamma, float* dbeta, float* ca, float* cb,
+                                float* cc, int C, int Cp, void* stream);
 int sed_conv3x3_wgrad_fused_c1(int dtype, const float* x1, const float* fmean, const float* fstd,
                                const float* w1, const float* pro_scale, const float* pro_shift,
                                const void* gsrc, const void* zsrc, const float* scale, const float* shift,

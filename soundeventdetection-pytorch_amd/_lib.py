@@ -49,6 +49,11 @@ PROTOTYPES = {
     "sed_conv3x3_dgrad_c1_stats": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "sed_conv3x3_dgrad_c1_stats_g": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "sed_bn_bwd_finalize_c1": (_I, [_P, _I, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "sed_conv3x3_c1_dgrad": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "sed_absmax": (_I, [_P, _Z, _P, _P]),
+    "sed_bn_eval_stats": (_I, [_P, _P, _F, _P, _P, _I, _I, _P]),
+    "sed_bn_eval_bwd_finalize": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "sed_bn_eval_bwd_finalize_c1": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "sed_conv3x3_wgrad_fused_c1": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I,
                                         _I, _I, _P]),
     "sed_pack_conv_weights_batch": (_I, [_I, _P, _I, _I, _P]),

@@ -93,6 +93,8 @@ class _Plan:
     x_ref: torch.Tensor = None      # the input of the last forward (first layer wgrad re-reads it)
     trained: bool = False
     gru: dict = None                # buffers of the recurrent head (head == 'gru')
+    keep: bool = False              # the last forward ran with keep_for_grad (input-gradient / eval-mode backward possible)
+    dx_in: torch.Tensor = None      # (B, 1, T, F) fp32 input gradient of the Cin = 1 model path (the last backward(need_dx=True))
 
 
 class KernelTimer:
@@ -181,6 +183,7 @@ class CnnEngine:
         # sums are reduced to one row per rank, summed over the ranks, and finalized with count * world.
         self.bn_sync = None
         self.wg_flush_per_group = False      # set by FusedTrainer under data parallel (see backward: group_done)
+        self._e_shift = 0                    # f16x3 pre-scale shift of the running backward (_grad_dtype; 0 outside the new backward kinds)
 
     @staticmethod
     def check_mel_bins(mel_bins):
@@ -215,8 +218,21 @@ class CnnEngine:
         if self.dt_mm != L.SED_F32H3:
             return self.dt_mm
         import math
-        e = max(-100, min(100, int(round(math.log2(max(1, B * H * W)))) + 2))
+        e = max(-100, min(100, int(round(math.log2(max(1, B * H * W)))) + 2 - self._e_shift))
         return L.SED_F32H3 | ((e & 0xff) << 8)
+
+    def _upstream_shift(self, p: _Plan, src: torch.Tensor, n_ref: int) -> int:
+        """Binades between the upstream gradient's largest magnitude and what the mean-reduced loss gives at this shape
+        (~1/n_ref per element): the f16x3 pre-scale of an input-gradient or eval-mode backward is shifted by it, so that a
+        sum-reduced or one-hot upstream gradient does not saturate the fp16 pieces.  0 when the gradient is all zeros."""
+        import math
+        if getattr(p, "amax", None) is None:
+            p.amax = torch.empty(1, dtype=torch.float32, device=src.device)
+        self._k("sed_absmax", self.lib.sed_absmax, L.ptr(src), src.numel(), L.ptr(p.amax), _stream())
+        a = float(p.amax.item())
+        if not (a > 0.0 and math.isfinite(a)):
+            return 0
+        return int(round(math.log2(a * n_ref)))
 
     def _sync_row(self, part, nparts: int, n: int, out):
         """this rank's partial rows [nparts][n] -> out[n] = sum over rows and over ranks"""
@@ -582,9 +598,11 @@ class CnnEngine:
 
     def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], training: bool,
                 feat_mean: Optional[torch.Tensor] = None, feat_std: Optional[torch.Tensor] = None,
-                update_running_stats: bool = True) -> _Plan:
+                update_running_stats: bool = True, keep_for_grad: bool = False) -> _Plan:
         """x: (B, 1, T, F) float32 cuda contiguous.  P: name -> fp32 cuda tensors (state_dict names).
-        Leaves pre-interpolation logits in plan.pre (B, t, K)."""
+        Leaves pre-interpolation logits in plan.pre (B, t, K).  keep_for_grad: the forward keeps what an input-gradient
+        backward (training) or an eval-mode backward needs beyond today's train step -- in C1 mode conv1's ReLU mask, under
+        the recurrent head the saved gates of an eval forward.  Outputs are the same bits either way; False keeps today's launches."""
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == self.cin0):
             raise ValueError(f"expected a float32 CUDA tensor of shape (B, {self.cin0}, T, F)")
         x = x.contiguous()
@@ -593,6 +611,12 @@ class CnnEngine:
         lib, dt, st = self.lib, self.dt, _stream()
         p.x_ref = x
         p.trained = training
+        p.keep = bool(keep_for_grad)
+        keep_mask = None
+        if p.keep and p.c1_mode:
+            if p.c1_mask is None and getattr(p, "c1_mask_keep", None) is None:
+                p.c1_mask_keep = torch.empty((B, T, F, 2), dtype=torch.int16, device=x.device)
+            keep_mask = p.c1_mask if p.c1_mask is not None else p.c1_mask_keep
         p.feat_mean, p.feat_std = feat_mean, feat_std
         prev = None
         if self.generic_first:
@@ -602,7 +626,7 @@ class CnnEngine:
                     p.x_nhwc.shape[3], st)
             prev = p.x_nhwc
         self._tag = ""
-        self._pack_weights(p, P, training)
+        self._pack_weights(p, P, training or p.keep)      # (a kept eval forward packs the data-gradient operators too)
         for bi, (c, pool) in enumerate(self.cfg):
             for j in range(2):
                 ly = p.layers[bi][j]
@@ -619,9 +643,12 @@ class CnnEngine:
                                                    L.ptr(ly.z), L.ptr(part), B, ly.H, ly.W, ly.cout, ly.coutp, st)
                 elif c1m and j == 1:
                     l1 = p.layers[bi][0]
-                    self._k("sed_conv3x3_fwd_c1", self.lib.sed_conv3x3_fwd_c1, dt, L.EPI_STATS if training else L.EPI_STORE, L.ptr(x),
-                            L.ptr(feat_mean), L.ptr(feat_std), L.ptr(P["conv_blocks.0.conv1.weight"]), L.ptr(l1.scale), L.ptr(l1.shift),
-                            L.ptr(ly.wpack), L.ptr(ly.z), L.ptr(part), L.ptr(p.c1_mask) if (training and p.c1_mask is not None) else None, B, ly.H, ly.W,
+                    # (the kernel writes conv1's ReLU mask in its statistics epilogue: an eval forward kept for a backward takes that
+                    #  epilogue with unused statistics; z2 is stored the same either way)
+                    mask = (L.ptr(p.c1_mask) if (training and p.c1_mask is not None) else None) if keep_mask is None else L.ptr(keep_mask)
+                    self._k("sed_conv3x3_fwd_c1", self.lib.sed_conv3x3_fwd_c1, dt, L.EPI_STATS if (training or keep_mask is not None) else L.EPI_STORE,
+                            L.ptr(x), L.ptr(feat_mean), L.ptr(feat_std), L.ptr(P["conv_blocks.0.conv1.weight"]), L.ptr(l1.scale), L.ptr(l1.shift),
+                            L.ptr(ly.wpack), L.ptr(ly.z), L.ptr(ly.part if keep_mask is not None else part), mask, B, ly.H, ly.W,
                             ly.coutp, st)
                 else:
                     if j == 0:
@@ -675,7 +702,7 @@ class CnnEngine:
         Cl = self.cfg[-1][0]
         self._tag = ""
         if self.head == "gru":
-            self._gru_forward(p, P, prev, training)
+            self._gru_forward(p, P, prev, training or p.keep)
             return p
         if self.head == "none":
             return p
@@ -702,12 +729,25 @@ class CnnEngine:
 
     # ------------------------------------------------------------------------------------------
     def backward(self, p: _Plan, P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor],
-                 dlogits: Optional[torch.Tensor] = None, debug: Optional[dict] = None, on_group_done=None):
-        """Backward of the last training-mode forward on plan p.  Gradient source: `dlogits`
+                 dlogits: Optional[torch.Tensor] = None, debug: Optional[dict] = None, on_group_done=None,
+                 need_dx: bool = False):
+        """Backward of the last forward on plan p.  Gradient source: `dlogits`
         (B, t*ratio, K) w.r.t. the interpolated logits, or plan.dpre when None.  Writes fp32 gradients
-        into G[name] (tensors shaped like the parameters; overwritten, not accumulated)."""
-        if not p.trained:
-            raise RuntimeError("backward() needs a training-mode forward (batch statistics)")
+        into G[name] (tensors shaped like the parameters; overwritten, not accumulated).
+        need_dx: also the input gradient of the Cin = 1 model path into plan.dx_in (B, 1, T, F) fp32 (csrc/sed_c1_dgrad.hip; the
+        generic_first path always fills plan.dx).  An eval-mode forward (BatchNorm with running statistics) can be differentiated
+        when it ran with keep_for_grad=True; so must a C1-mode training forward whose backward takes need_dx.  Without need_dx, a
+        training-mode backward launches exactly what it did before these two kinds existed."""
+        eval_bwd = not p.trained
+        if eval_bwd and not p.keep:
+            raise RuntimeError("backward() needs a training-mode forward (batch statistics) or a forward with keep_for_grad=True")
+        need_dx = bool(need_dx) and not self.generic_first
+        if need_dx and p.c1_mode and not p.keep:
+            raise RuntimeError("the input gradient in C1 mode needs a forward with keep_for_grad=True (conv1's ReLU mask)")
+        if (eval_bwd or need_dx) and self.bn_sync is not None:
+            raise RuntimeError("input-gradient and eval-mode backward are not available with SyncBN")
+        new_kind = eval_bwd or need_dx
+        c1_plain = new_kind and p.c1_mode     # C1 mode: the unfused block-0 route, which writes g1 and takes the forward's mask
         lib, dt, st = self.lib, self.dt, _stream()
         B = p.B
         Cl = self.cfg[-1][0]
@@ -717,6 +757,51 @@ class CnnEngine:
             src, ratio = p.dpre, 1
         else:
             src, ratio = dlogits.contiguous(), self.ratio
+        nb = len(self.cfg)
+        self._e_shift = 0
+        if new_kind and self.dt_mm == L.SED_F32H3:
+            if self.head == "none":
+                self._e_shift = self._upstream_shift(p, p.dy[nb - 1], B * self.cfg[-1][0] * p.t_out * p.w_out)
+            else:
+                self._e_shift = self._upstream_shift(p, src, B * p.t_out * self.ratio * self.K)
+        if eval_bwd:
+            # BatchNorm as the fixed affine map of its running statistics: (mean, invstd) for the backward statistics kernels
+            for bi in range(nb):
+                for j in range(2):
+                    ly = p.layers[bi][j]
+                    _, _, rmn, rvn = self._bn_names(bi, j)
+                    self._k("sed_bn_eval_stats", lib.sed_bn_eval_stats, L.ptr(P[rmn]), L.ptr(P[rvn]), BN_EPS, L.ptr(ly.mean),
+                            L.ptr(ly.invstd), ly.cout, ly.coutp, st)
+        # an eval forward keeps no pooled-tensor statistics (active-pixel counts): the per-pixel pass everywhere
+        pool_fused = [False] * nb if eval_bwd else p.pool_fused
+        c1_mask = p.c1_mask if p.c1_mask is not None else getattr(p, "c1_mask_keep", None)
+        try:
+            self._backward_blocks(p, P, G, src, ratio, debug, on_group_done, eval_bwd, pool_fused, c1_plain, c1_mask)
+        finally:
+            self._e_shift = 0
+        if need_dx:
+            l1 = p.layers[0][0]
+            p.dx_in = torch.empty((B, 1, p.T, p.F), dtype=torch.float32, device=p.x_ref.device)     # (fresh: autograd keeps it)
+            # dzB holds g1 (conv2's gated data gradient of block 0); (ca, cb, cc) of BN1 are in l1.coef
+            self._tag = f"bwd b0 dx H{p.T} W{p.F}"
+            self._k("sed_conv3x3_c1_dgrad", lib.sed_conv3x3_c1_dgrad, dt, L.ptr(p.scratch[1]), None if p.c1_mode else L.ptr(l1.z),
+                    L.ptr(p.x_ref), L.ptr(p.feat_mean), L.ptr(p.feat_std), L.ptr(P["conv_blocks.0.conv1.weight"]), L.ptr(l1.coef[0]),
+                    L.ptr(l1.coef[1]), L.ptr(l1.coef[2]), L.ptr(p.dx_in), B, p.T, p.F, l1.cout, l1.coutp, st)
+            self._tag = ""
+
+    def _bn_bwd_fin(self, eval_bwd, bpart, nparts, count, gamma, ly, dg, db):
+        ca, cb, cc = ly.coef[0], ly.coef[1], ly.coef[2]
+        if eval_bwd:
+            self._k("sed_bn_eval_bwd_finalize", self.lib.sed_bn_eval_bwd_finalize, L.ptr(bpart), nparts, L.ptr(gamma), L.ptr(ly.mean),
+                    L.ptr(ly.invstd), L.ptr(dg), L.ptr(db), L.ptr(ca), L.ptr(cb), L.ptr(cc), ly.cout, ly.coutp, _stream())
+            return
+        self._k("sed_bn_bwd_finalize", self.lib.sed_bn_bwd_finalize, L.ptr(bpart), nparts, count, L.ptr(gamma), L.ptr(ly.mean),
+                L.ptr(ly.invstd), L.ptr(dg), L.ptr(db), L.ptr(ca), L.ptr(cb), L.ptr(cc), ly.cout, ly.coutp, _stream())
+
+    def _backward_blocks(self, p, P, G, src, ratio, debug, on_group_done, eval_bwd, pool_fused, c1_plain, c1_mask):
+        lib, dt, st = self.lib, self.dt, _stream()
+        B = p.B
+        Cl = self.cfg[-1][0]
         nb = len(self.cfg)
         if self.head == "none":
             pass                      # the caller filled plan.dy[-1] (gradient of the last pooled block output)
@@ -729,7 +814,7 @@ class CnnEngine:
             if on_group_done is not None:
                 on_group_done("event_fc")
         dzA, dzB = p.scratch
-        if any(p.pool_fused):
+        if any(pool_fused):
             p.pool_flag.zero_()
         p.wg_pending = []
 
@@ -757,7 +842,7 @@ class CnnEngine:
             g2n, b2n, _, _ = self._bn_names(bi, 1)
             g1n, b1n, _, _ = self._bn_names(bi, 0)
             # ---- pool + ReLU + BN2 backward -> dz2 -------------------------------------------------
-            if p.pool_fused[bi]:
+            if pool_fused[bi]:
                 # the statistics came out of the data gradient that produced dy[bi] (end of the previous iteration); the per-pixel
                 # pass runs only if that kernel met a channel with gamma = 0 (device-side flag: the launch returns at once)
                 nparts = p.pool_nparts[bi]
@@ -775,9 +860,7 @@ class CnnEngine:
             bpart = p.bwd_part
             if sync is not None:        # (dgamma / dbeta then come out as GLOBAL sums: pre-divided by world, the gradient
                 bpart, nparts = self._sync_row(p.bwd_part, nparts, 2 * l2.coutp, p.sync_row), 1     # all-reduce sums them back)
-            self._k("sed_bn_bwd_finalize", self.lib.sed_bn_bwd_finalize, L.ptr(bpart), nparts, gcount, L.ptr(P[g2n]), L.ptr(l2.mean),
-                                            L.ptr(l2.invstd), L.ptr(G[g2n]), L.ptr(G[b2n]), L.ptr(ca), L.ptr(cb),
-                                            L.ptr(cc), l2.cout, l2.coutp, st)
+            self._bn_bwd_fin(eval_bwd, bpart, nparts, gcount, P[g2n], l2, G[g2n], G[b2n])
             if sync is not None:
                 G[g2n].mul_(1.0 / sync.world)
                 G[b2n].mul_(1.0 / sync.world)
@@ -796,7 +879,7 @@ class CnnEngine:
                         L.ptr(l2.wpack_t), L.ptr(dzB), L.EPI_RELUBWD, L.ptr(l1.z), None, L.ptr(l1.scale), L.ptr(l1.shift), L.ptr(l1.mean),
                         L.ptr(l1.invstd), L.ptr(p.bwd_part), lib.sed_conv_nparts(B, H, W), None, *self._wg_bufs(p, l2),
                         B, H, W, l2.cinp, l2.coutp, L.ptr(G[w2n]), l2.cout, l2.cin, st)
-            elif c1m and p.c1_bwd_fused and debug is None:
+            elif c1m and p.c1_bwd_fused and debug is None and not c1_plain:
                 # dW2 and the [A; sum g] partials of the gated data gradient from one dz2 tile in LDS: dz2 is never written
                 x1a = (L.ptr(p.x_ref), L.ptr(p.feat_mean), L.ptr(p.feat_std), L.ptr(P["conv_blocks.0.conv1.weight"]))
                 self._k("sed_conv3x3_bwd_fused_c1", self.lib.sed_conv3x3_bwd_fused_c1, dt, *x1a, L.ptr(l1.scale), L.ptr(l1.shift),
@@ -819,7 +902,7 @@ class CnnEngine:
             #  wpack_t was packed with the forward operators, sed_pack_conv_weights_batch)
             # ---- conv2: data gradient with fused ReLU mask + BN1 backward statistics ---------------
             nparts = lib.sed_conv_nparts(B, H, W)
-            c1f = c1m and p.c1_dg_fused and debug is None
+            c1f = c1m and p.c1_dg_fused and debug is None and not c1_plain
             if fused2 or (c1f and p.c1_bwd_fused):
                 pass
             elif c1f:
@@ -829,7 +912,7 @@ class CnnEngine:
                         L.ptr(p.x_ref), L.ptr(p.feat_mean), L.ptr(p.feat_std), L.ptr(p.c1_mask), L.ptr(p.c1_a10_part), B, H, W, st)
             elif c1m:
                 self._k("sed_conv3x3_dgrad_c1", self.lib.sed_conv3x3_dgrad_c1, dt, L.ptr(dzA), L.ptr(l2.wpack_t), L.ptr(dzB),
-                        L.ptr(p.c1_mask), L.ptr(p.bwd_part), B, H, W, l2.coutp, st)
+                        L.ptr(c1_mask), L.ptr(p.bwd_part), B, H, W, l2.coutp, st)
             else:
                 self._k("sed_conv3x3_fwd", self.lib.sed_conv3x3_fwd, dtg, L.PRO_NONE, L.EPI_RELUBWD, L.ptr(dzA), None, None, L.ptr(l2.wpack_t),
                                             L.ptr(dzB), L.ptr(l1.z), L.ptr(l1.scale), L.ptr(l1.shift), L.ptr(l1.mean),
@@ -868,16 +951,22 @@ class CnnEngine:
                         L.ptr(p.feat_std), L.ptr(dzB), L.ptr(p.c1_ws), B, H, W, l1.coutp, st)
                 self._k("sed_sum_partials", self.lib.sed_sum_partials, L.ptr(p.c1_ws), p.c1_ws.shape[0], 9 * l1.coutp,
                         L.ptr(p.c1_A), st)
-                self._k("sed_bn_bwd_finalize_c1", self.lib.sed_bn_bwd_finalize_c1, L.ptr(p.bwd_part), nparts, count, L.ptr(p.c1_A),
-                        L.ptr(P["conv_blocks.0.conv1.weight"]), L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]),
-                        L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc), l1.cout, l1.coutp, st)
+                if eval_bwd:
+                    self._k("sed_bn_eval_bwd_finalize_c1", self.lib.sed_bn_eval_bwd_finalize_c1, L.ptr(p.bwd_part), nparts, L.ptr(p.c1_A),
+                            L.ptr(P["conv_blocks.0.conv1.weight"]), L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]),
+                            L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc), l1.cout, l1.coutp, st)
+                    # (dW1 = ca*A: the Gram statistics enter with cb = cc = 0, but an eval forward did not compute them)
+                    self._k("sed_conv3x3_c1_gram", self.lib.sed_conv3x3_c1_gram, L.ptr(p.x_ref), L.ptr(p.feat_mean),
+                            L.ptr(p.feat_std), L.ptr(p.c1_gram), B, H, W, st)
+                else:
+                    self._k("sed_bn_bwd_finalize_c1", self.lib.sed_bn_bwd_finalize_c1, L.ptr(p.bwd_part), nparts, count, L.ptr(p.c1_A),
+                            L.ptr(P["conv_blocks.0.conv1.weight"]), L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]),
+                            L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc), l1.cout, l1.coutp, st)
             else:
                 bpart = p.bwd_part
                 if sync is not None:
                     bpart, nparts = self._sync_row(p.bwd_part, nparts, 2 * l1.coutp, p.sync_row), 1
-                self._k("sed_bn_bwd_finalize", self.lib.sed_bn_bwd_finalize, L.ptr(bpart), nparts, gcount, L.ptr(P[g1n]), L.ptr(l1.mean),
-                                                L.ptr(l1.invstd), L.ptr(G[g1n]), L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb),
-                                                L.ptr(cc), l1.cout, l1.coutp, st)
+                self._bn_bwd_fin(eval_bwd, bpart, nparts, gcount, P[g1n], l1, G[g1n], G[b1n])
             if sync is not None:
                 G[g1n].mul_(1.0 / sync.world)
                 G[b1n].mul_(1.0 / sync.world)
@@ -910,8 +999,9 @@ class CnnEngine:
                 # conv1 weight gradient with dz1 = BN1 backward produced on load from (g1, z1); dz1 lands
                 # in dzA (dz2 is dead by now) for the data-gradient call below
                 self._tag = f"bwd b{bi}c1 {l1.cin}->{l1.cout} H{H} W{W}"
-                if p.bwd_fused[bi][0] and debug is None:
-                    pst = bi > 0 and p.pool_fused[bi - 1]
+                # (the fused form was chosen for the plan's epilogue: an eval backward without pooled statistics takes the two kernels)
+                if p.bwd_fused[bi][0] and debug is None and not (eval_bwd and bi > 0 and p.pool_fused[bi - 1]):
+                    pst = bi > 0 and pool_fused[bi - 1]
                     q2 = p.layers[bi - 1][1] if pst else None
                     self._k("sed_conv3x3_bwd_fused", self.lib.sed_conv3x3_bwd_fused, dt, L.PRO_NONE, L.ptr(xin), None, None, L.DZ_BN, L.ptr(dzB),
                             L.ptr(l1.z), None, None, L.ptr(ca), L.ptr(cb), L.ptr(cc), 1, L.ptr(l1.wpack_t), L.ptr(dxout),
@@ -929,7 +1019,7 @@ class CnnEngine:
                         l1.cin, st)
                 self._wg_done(p, l1, G[w1n])
                 snap(f"dz1_{bi}", dzA, l1)
-                if bi > 0 and p.pool_fused[bi - 1]:
+                if bi > 0 and pool_fused[bi - 1]:
                     q2 = p.layers[bi - 1][1]      # the block whose pooled output this gradient belongs to
                     self._k("sed_conv3x3_dgrad_poolstats", self.lib.sed_conv3x3_dgrad_poolstats, dt, L.ptr(dzA), L.ptr(l1.wpack_t),
                             L.ptr(dxout), L.ptr(p.y[bi - 1]), L.ptr(p.pool_cnt[bi - 1]), L.ptr(q2.scale), L.ptr(q2.shift), L.ptr(q2.mean),

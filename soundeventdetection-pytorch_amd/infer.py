@@ -4,8 +4,8 @@ in eval mode -> per-frame probabilities, threshold decisions and onset times.
 
     python -m sed_amd.infer recording.wav --ckpt training_dir/.../iteration_5000.pth
 
-Writes <outputs_dir>/<name>.npz (probabilities, decisions, onset_frames, onset_seconds) and prints
-the onsets.  The features are z-scored with --mean_std (the pickle the preprocessing wrote) when given:
+Writes <outputs_dir>/<name>.npz (probabilities, decisions, onset_frames, onset_seconds; with --saliency also
+saliency (T, mel_bins, classes) = d(sum_t p_k(t)) / d(model input), the eval-mode input gradient) and prints the onsets.  The features are z-scored with --mean_std (the pickle the preprocessing wrote) when given:
 the reference's infer.py skips the normalisation the model was trained with."""
 from __future__ import annotations
 
@@ -28,6 +28,9 @@ def build_parser():
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "f16x3", "bf16x3"])
     p.add_argument("--mel_bins", type=int, default=None,
                    help="log-mel bins of the front-end and the model's declared input width, 1..256 (default: the config's 64)")
+    p.add_argument("--saliency", action="store_true",
+                   help="also write 'saliency' (T, mel_bins, classes): d(sum_t p_k(t)) / d(input) of the first channel per class k, "
+                        "taken with respect to the model input (the z-scored log-mel)")
     return p
 
 
@@ -48,7 +51,20 @@ def load_mean_std(mean_std, mel_bins):
     return mean, std
 
 
-def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, precision="bf16", mel_bins=None):
+def saliency_maps(model, x):
+    """x: (1, 1, T, F) model input.  (T, F, K): the gradient of each class's summed probability, d(sum_t p_k(t)) / dx, through
+    the eval-mode backward (BatchNorm with running statistics) -- one backward per class."""
+    K = model.classes_num
+    out = np.zeros((x.shape[2], x.shape[3], K), dtype=np.float32)
+    for k in range(K):
+        xg = x.detach().clone().requires_grad_(True)
+        probs = torch.sigmoid(model(xg))
+        probs[0, :, k].sum().backward()
+        out[:, :, k] = xg.grad[0, 0].cpu().numpy()
+    return out
+
+
+def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, precision="bf16", mel_bins=None, saliency=False):
     import dataclasses
     from .dataset.dataset_utils import read_multichannel_audio
     from .dataset.spectogram.preprocess import LogMelFrontEnd
@@ -77,19 +93,25 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     probs = torch.sigmoid(logits)[0].cpu().numpy()
     dec = probs > threshold
     onsets = [onset_frames(dec[:, k]) for k in range(dec.shape[1])]
-    return {"probabilities": probs, "decisions": dec, "onset_frames": onsets,
-            "frames_per_second": cfg.frames_per_second, "log_mel": feats[0, 0].cpu().numpy()}
+    res = {"probabilities": probs, "decisions": dec, "onset_frames": onsets,
+           "frames_per_second": cfg.frames_per_second, "log_mel": feats[0, 0].cpu().numpy()}
+    if saliency:
+        print("Saliency..")
+        res["saliency"] = saliency_maps(model, feats[:1])
+    return res
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    res = infer_file(args.audio_file, args.ckpt, args.device, args.mean_std, args.threshold, args.precision, args.mel_bins)
+    res = infer_file(args.audio_file, args.ckpt, args.device, args.mean_std, args.threshold, args.precision, args.mel_bins,
+                     args.saliency)
     os.makedirs(args.outputs_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(args.audio_file))[0]
     fps = res["frames_per_second"]
+    extra = {"saliency": res["saliency"]} if "saliency" in res else {}
     np.savez(os.path.join(args.outputs_dir, name + ".npz"), probabilities=res["probabilities"],
              decisions=res["decisions"], onset_frames=np.concatenate(res["onset_frames"]) if res["onset_frames"] else [],
-             onset_seconds=np.concatenate(res["onset_frames"]) / fps if res["onset_frames"] else [])
+             onset_seconds=np.concatenate(res["onset_frames"]) / fps if res["onset_frames"] else [], **extra)
     for k, on in enumerate(res["onset_frames"]):
         print(f"class {k}: {len(on)} onsets at " + ", ".join(f"{f / fps:.2f}s" for f in on[:50]))
 

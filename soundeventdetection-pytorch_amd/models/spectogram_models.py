@@ -91,11 +91,11 @@ class _BlockFunction(torch.autograd.Function):
     boundary like the reference module (spectogram_models.py:153-160), including the input gradient."""
 
     @staticmethod
-    def forward(ctx, block, x, w1, w2, g1, b1, g2, b2):
+    def forward(ctx, block, keep, x, w1, w2, g1, b1, g2, b2):
         eng = block._engine()
         P = block._tensor_dict()
         training = block.training
-        plan = eng.forward(x, P, training)
+        plan = eng.forward(x, P, training, keep_for_grad=keep)
         if training:
             block.bn1.num_batches_tracked += 1
             block.bn2.num_batches_tracked += 1
@@ -111,9 +111,6 @@ class _BlockFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         block, plan = ctx.block, ctx.plan
-        if not ctx.training:
-            raise RuntimeError("backward through an eval-mode ConvBlock is not supported (BatchNorm batch statistics "
-                               "are needed); call block.train()")
         if ctx.serial != block._fwd_serial:
             raise RuntimeError("the activations of this forward were overwritten by a later forward of the same shape")
         eng = block._engine()
@@ -129,7 +126,7 @@ class _BlockFunction(torch.autograd.Function):
         dx = torch.empty((B, cin, plan.T, plan.F), dtype=torch.float32, device=dy.device)
         L.check(L.lib().sed_nhwc_to_nchw(eng.dt, L.ptr(plan.dx), L.ptr(dx), B, cin, plan.T, plan.F, plan.dx.shape[3], _stream()),
                 "nhwc_to_nchw")
-        return (None, dx) + tuple(G["conv_blocks.0." + n] for n in names)
+        return (None, None, dx) + tuple(G["conv_blocks.0." + n] for n in names)
 
 
 class ConvBlock(nn.Module):
@@ -171,7 +168,9 @@ class ConvBlock(nn.Module):
             raise RuntimeError("ConvBlock runs on the MI355X only: move the module and the input to 'cuda' "
                                "(there is no CPU path)")
         x = input.float()
-        return _BlockFunction.apply(self, x, self.conv1.weight, self.conv2.weight, self.bn1.weight, self.bn1.bias,
+        # an eval forward under grad mode keeps what the eval-mode (running-statistics) backward needs; outputs are the same bits
+        keep = torch.is_grad_enabled() and not self.training
+        return _BlockFunction.apply(self, keep, x, self.conv1.weight, self.conv2.weight, self.bn1.weight, self.bn1.bias,
                                     self.bn2.weight, self.bn2.bias)
 
 
@@ -179,10 +178,10 @@ class _ModelFunction(torch.autograd.Function):
     """Whole-model forward/backward as ONE autograd node over the HIP pipeline."""
 
     @staticmethod
-    def forward(ctx, model, x, *params):
+    def forward(ctx, model, keep, x, *params):
         P = model._tensor_dict()
         training = model.training
-        plan = model.engine.forward(x, P, training)
+        plan = model.engine.forward(x, P, training, keep_for_grad=keep)
         if training:
             model._nbt_pending += 1
         model._fwd_serial += 1
@@ -193,17 +192,15 @@ class _ModelFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits):
         model = ctx.model
-        if not ctx.training:
-            raise RuntimeError("backward through an eval-mode forward is not supported (BatchNorm "
-                               "batch statistics are needed); call model.train()")
         if ctx.serial != model._fwd_serial:
             raise RuntimeError("the activations of this forward were overwritten by a later forward of the "
                                "same shape; call backward() before the next forward()")
         P = model._tensor_dict()
         names = [n for n, _ in model.named_parameters()]
         G = {n: torch.empty_like(P[n]) for n in names}
-        model.engine.backward(ctx.plan, P, G, dlogits=dlogits.contiguous().float())
-        return (None, None) + tuple(G[n] for n in names)
+        need_dx = bool(ctx.needs_input_grad[2])
+        model.engine.backward(ctx.plan, P, G, dlogits=dlogits.contiguous().float(), need_dx=need_dx)
+        return (None, None, ctx.plan.dx_in if need_dx else None) + tuple(G[n] for n in names)
 
 
 class Cnn_AvgPooling(nn.Module):
@@ -272,7 +269,10 @@ class Cnn_AvgPooling(nn.Module):
             raise RuntimeError("model parameters are on the CPU; call model.to('cuda')")
         x = x.float()
         params = [p for _, p in self.named_parameters()]
-        return _ModelFunction.apply(self, x, *params)
+        # grad mode: an eval forward keeps what the eval-mode (frozen-BatchNorm) backward needs, a training forward whose input
+        # needs a gradient keeps what the input gradient needs (C1 mode: conv1's ReLU mask).  Outputs are the same bits.
+        keep = torch.is_grad_enabled() and (not self.training or x.requires_grad)
+        return _ModelFunction.apply(self, keep, x, *params)
 
     def logits(self, x):
         return torch.sigmoid(self.forward(x))
