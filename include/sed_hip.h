@@ -172,25 +172,32 @@ int sed_conv3x3_wgrad_fused(int dtype, int pro, const void* x, const float* pro_
  * Training statistics from the conv epilogue partials [nparts][2][Cp]: batch mean, biased var ->
  * scale = gamma*invstd, shift = beta - mean*scale, saved mean/invstd, and the running-stat
  * update (unbiased var, n/(n-1)).  gamma/beta/running_* have C (unpadded) entries; outputs Cp
- * entries with padded channels forced to scale = shift = 0.  count = B*H*W.                    */
+ * entries with padded channels [C, Cp) forced to scale = shift = mean = invstd = 0 (the partials'
+ * padded columns are not used).  count = B*H*W; count = 1 keeps the biased variance.  The sums
+ * over nparts and var = q/n - mean^2 (clamped at 0) are formed in fp64.  running_* may both be
+ * NULL (no update).                                                                            */
 int sed_bn_train_finalize(const float* partial, int nparts, double count, const float* gamma,
                           const float* beta, float* running_mean, float* running_var,
                           float momentum, float eps, float* scale, float* shift, float* mean,
                           float* invstd, int C, int Cp, void* stream);
-/* Eval mode: scale/shift from the running statistics.                                         */
+/* Eval mode: scale/shift from the running statistics (padded channels [C, Cp) = 0).            */
 int sed_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
                        const float* running_var, float eps, float* scale, float* shift, int C,
                        int Cp, void* stream);
 /* Backward reduction finalize: partial [nparts][2][Cp] = (sum g, sum g*xhat) ->
  * dgamma[C], dbeta[C] and the coefficients of dz = ca*g + cb*z + cc (fp32 [Cp] each):
- *   ca = gamma*invstd, cb = -gamma*invstd^2*mgx, cc = -gamma*invstd*(mg - mean*invstd*mgx).   */
+ *   ca = gamma*invstd, cb = -gamma*invstd^2*mgx, cc = -gamma*invstd*(mg - mean*invstd*mgx),
+ * mg = sum g / count, mgx = sum g*xhat / count.  ca/cb/cc are 0 on the padded channels [C, Cp);
+ * the padded entries of partial, mean and invstd are not used.                                 */
 int sed_bn_bwd_finalize(const float* partial, int nparts, double count, const float* gamma,
                         const float* mean, const float* invstd, float* dgamma, float* dbeta,
                         float* ca, float* cb, float* cc, int C, int Cp, void* stream);
 
 /* ---- fused elementwise stages --------------------------------------------------------------
  * y = avg_pool2d(relu(scale*z+shift), pool) (spectogram_models.py:156-158), pool in {1,2};
- * z [B][H][W][Cp] -> y [B][H/pool][W/pool][Cp].                                                */
+ * z [B][H][W][Cp] -> y [B][H/pool][W/pool][Cp] (floor: a trailing odd row / column is dropped and
+ * never read).  relu'(0) = 0: a pixel with scale*z+shift == 0 is inactive, here and in the backward.
+ * All Cp channels are treated alike: padded channels stay 0 through scale = shift = 0.             */
 int sed_bn_relu_pool_fwd(int dtype, const void* z, const float* scale, const float* shift, void* y,
                          int B, int H, int W, int Cp, int pool, void* stream);
 /* backward, pass 1: g = up(dy)/pool^2 * (scale*z+shift > 0); partial [nparts][2][Cp] =
@@ -219,7 +226,8 @@ int sed_conv3x3_dgrad_poolstats(int dtype, const void* dz, const void* wpack_t, 
 int sed_pool_relu_bwd_stats_if(const int* flag, int dtype, const void* dy, const void* z, const float* scale,
                                const float* shift, const float* mean, const float* invstd, float* partial,
                                int nparts, int B, int H, int W, int Cp, int pool, void* stream);
-/* backward, pass 2: dz = ca*g + cb*z + cc with g recomputed as in pass 1.                      */
+/* backward, pass 2: dz = ca*g + cb*z + cc with g recomputed as in pass 1, on all H x W pixels:
+ * g = 0 on the row / column the pooling floor dropped (dz = cb*z + cc there); pass 1 skips them.  */
 int sed_pool_relu_bn_bwd_apply(int dtype, const void* dy, const void* z, const float* scale,
                                const float* shift, const float* ca, const float* cb,
                                const float* cc, void* dz, int B, int H, int W, int Cp, int pool,
@@ -232,7 +240,9 @@ int sed_bn_bwd_apply(int dtype, const void* g, const void* z, const float* ca, c
  * Cnn_AvgPooling.forward tail (spectogram_models.py:193-200): mean over mel (W) -> Linear(C,K)
  * -> raw logits; the x`ratio` interpolate() is NOT materialised here: pre [B][t][K] fp32.
  * feat [B][t][Wf][Cp] (post BN/ReLU/pool activations); fc_w [K][C], fc_b [K] fp32;
- * m_out [B][t][Cp] fp32 keeps the mel-mean for the backward pass.                              */
+ * m_out [B][t][Cp] fp32 keeps the mel-mean for the backward pass; its padded channels [C, Cp) are
+ * the mean of feat's padded channels (0 for a well-formed activation) and pre does not depend on
+ * them.                                                                                        */
 int sed_head_fwd(int dtype, const void* feat, const float* fc_w, const float* fc_b, float* m_out,
                  float* pre, int B, int t, int Wf, int C, int Cp, int K, void* stream);
 /* interpolate(): out[b][i][k] = pre[b][i/ratio][k] (spectogram_models.py:9-22)                 */
@@ -241,13 +251,17 @@ int sed_interpolate(const float* pre, float* out, int B, int t, int K, int ratio
  * them: N = min(t*ratio, Tt) frames; loss[0] = mean over B*N*K of
  * -(w*y*logsigmoid(x) + (1-y)*logsigmoid(-x)); dpre [B][t][K] = d loss / d pre (the x`ratio`
  * repeat backward already summed). target [B][Tt][K] fp32. loss_partial: fp32 scratch of at
- * least ceil(B*t*K/256) floats. dpre may be NULL (loss only).                                   */
+ * least ceil(B*t*K/256) floats. dpre may be NULL (loss only).  dpre is formed as (sum / numel) *
+ * grad_scale in that order: a gradient whose unscaled value is subnormal (logits below about -87)
+ * is rounded to a multiple of 2^-149 before grad_scale multiplies it.                           */
 int sed_bce_fwd_bwd(const float* pre, const float* target, float* loss, float* dpre,
                     float* loss_partial, int B, int t, int K, int ratio, int Tt, float recall_factor,
                     float grad_scale, void* stream);
 /* Head backward: dfc_w [K][C], dfc_b [K] (overwritten) and dfeat [B][t][Wf][Cp] =
  * (dpre @ fc_w)/Wf broadcast over mel.  `dpre` is [B][t*ratio][K]: with ratio > 1 it is the
- * gradient w.r.t. the interpolate()d logits and the repeat-backward sum is folded in.           */
+ * gradient w.r.t. the interpolate()d logits and the repeat-backward sum is folded in.  m is the
+ * forward's m_out [B][t][Cp] (padded channels not read); dfeat's padded channels [C, Cp) are 0.
+ * workspace: sed_head_bwd_ws_floats() floats (independent of Cp, Wf and ratio).                  */
 size_t sed_head_bwd_ws_floats(int B, int t, int C, int K);
 int sed_head_bwd(int dtype, const float* dpre, const float* m, const float* fc_w, float* dfc_w,
                  float* dfc_b, void* dfeat, float* workspace, int B, int t, int Wf, int C, int Cp, int K,
@@ -674,7 +688,9 @@ int sed_m5_head_bwd(int dtype, const float* dpre, const float* m, const float* f
 /* ---- utilities -----------------------------------------------------------------------------*/
 /* out[i] = sum_{s<nparts} partial[s][i], i < n (fixed order: deterministic)                     */
 int sed_sum_partials(const float* partial, int nparts, size_t n, float* out, void* stream);
-/* fp32 [n] <-> dtype [n] casts; NCHW fp32 (B,C,H,W) <-> NHWC dtype (B,H,W,Cp) re-layouts        */
+/* fp32 [n] <-> dtype [n] casts (fp32 -> bf16 rounds to nearest even, NaN stays NaN);
+ * NCHW fp32 (B,C,H,W) <-> NHWC dtype (B,H,W,Cp) re-layouts: sed_nchw_to_nhwc writes +0 to the padded
+ * channels [C, Cp), sed_nhwc_to_nchw does not read them                                         */
 int sed_cast(int dtype_dst, void* dst, int dtype_src, const void* src, size_t n, void* stream);
 int sed_nchw_to_nhwc(int dtype, const float* src, void* dst, int B, int C, int H, int W, int Cp,
                      void* stream);
