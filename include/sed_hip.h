@@ -345,7 +345,12 @@ int sed_mel_mean_bwd(int dtype, const float* dm, void* dfeat, size_t rows, int W
 /* C[M][N] = A[M][K] . B[N][K]^T (+ bias[N]); row-major fp32 in memory, MFMA compute in
  * compute_dtype (SED_BF16: bf16 operands, fp32 accumulate; SED_F32: fp32 MFMA).  ksplit > 1 splits
  * K over workgroups (fixed-order reduction through `workspace`, sed_gemm_nt_ws_floats floats; no
- * bias then).  lda/ldb multiples of 4, A/B 16-byte aligned.                                      */
+ * bias then).  lda/ldb multiples of 4, A/B 16-byte aligned.
+ * Pinned by tests/test_gpu_crnn_exact_oracle.py: the split is kchunk = ceil(ceil(K / ksplit) / 32) * 32 columns per slab and
+ * ceil(K / kchunk) slabs (fewer than ksplit when K is short; one slab = the unsplit path, no workspace touched); only columns
+ * 0 .. K-1 of a row of A / B are read (the padding up to lda / ldb may hold anything), only columns 0 .. N-1 of a row of C and the
+ * first sed_gemm_nt_ws_floats floats of the workspace are written.  Refused (non-zero, nothing launched): a bias or a NULL workspace
+ * with ksplit > 1, lda / ldb < K or not a multiple of 4, ldc < N, A or B not 16-byte aligned.                                     */
 size_t sed_gemm_nt_ws_floats(int M, int N, int ksplit);
 int sed_gemm_nt(int compute_dtype, const float* A, int lda, const float* B, int ldb,
                 const float* bias, float* C, int ldc, int M, int N, int K, int ksplit,
@@ -360,7 +365,13 @@ int sed_transpose_shift(const float* src, int ld_src, float* dst, int ld_dst, in
  * {-1, 0, +1} inside sequences of `seq` consecutive rows (K % seq == 0; a row that leaves its sequence contributes zero): shift = +1 /
  * -1 pairs a gate gradient with the PREVIOUS hidden state of a forward / reverse recurrence.  colsum (nullable) [M] = sum_k A[k][m] (the
  * bias gradients).  ksplit > 1 splits K over workgroups, fixed-order reduction through `workspace` (sed_gemm_tn_ws_floats floats).
- * lda/ldb multiples of 4, A/B 16-byte aligned.  Replaces sed_transpose_shift x 5 + sed_gemm_nt x 4 + sed_row_sums x 4 of the BPTT tail.  */
+ * lda/ldb multiples of 4, A/B 16-byte aligned.  Replaces sed_transpose_shift x 5 + sed_gemm_nt x 4 + sed_row_sums x 4 of the BPTT tail.
+ * Pinned by tests/test_gpu_crnn_exact_oracle.py: slabs of kchunk = ceil(ceil(K / ksplit) / 64) * 64 rows, ceil(K / kchunk) of them.
+ * M and N need not be multiples of 4: only columns 0 .. M-1 / 0 .. N-1 of a row of A / B are read.  The rows of B that a shift
+ * excludes (the last row of every sequence for shift = +1, the first for shift = -1) are never read; with seq = 1 and a shift C is
+ * exactly 0.  colsum is summed from the fp32 values of A (before any bf16 rounding) and written once per problem, whatever N is.
+ * Refused (non-zero, nothing launched): lda < M, ldb < N, ldc < N, lda / ldb not a multiple of 4, A or B not 16-byte aligned,
+ * K % seq != 0, a shift outside {-1, 0, +1}, ksplit > 1 without a workspace; for the batch, n outside 1 .. 8.                      */
 size_t sed_gemm_tn_ws_floats(int M, int N, int ksplit);
 int sed_gemm_tn(int compute_dtype, const float* A, int lda, const float* B, int ldb, float* C, int ldc, float* colsum, int M, int N,
                 int K, int seq, int shift, int ksplit, float* workspace, void* stream);
@@ -382,11 +393,21 @@ int sed_gru_pack_weights(int dtype, const float* whh_fwd, const float* whh_rev, 
                          void* pack_bwd, int Hd, void* stream);
 /* Forward recurrence of both directions.  gi [B*t][2][3Hd] = x.W_ih^T + b_ih (sed_gemm_nt);
  * bhh [2][3Hd]; hseq [B*t][2][Hd] (= nn.GRU output (B, t, 2Hd)); saved (nullable for inference)
- * [B*t][2][4][Hd] = r, z, n, W_hn h + b_hn for the backward pass.  h0 = 0.                       */
+ * [B*t][2][4][Hd] = r, z, n, W_hn h + b_hn for the backward pass.  h0 = 0.
+ * Where SED_BF16 rounds (pinned by tests/test_gpu_crnn_exact_oracle.py for every form the SED_GRU* variables select): W_hh and
+ * the previous state are rounded to bf16 (nearest even) as operands of the product W_h* h only; the accumulation, the gates, the
+ * blend h' = n + z (h - n) on the fp32 previous state, hseq and all four planes of `saved` are fp32.  saved == NULL gives the same
+ * hseq bits.  Rows of hseq / saved past B*t are never written, whatever part of its last chunk B fills.  Sizes: the kernels
+ * address with 32-bit byte offsets and B*t*8*Hd*4 bytes (the `saved` tensor) must stay below 4 GiB.  That check counts the real
+ * rows only: the offset of a chunk row PAST the batch is computed too, and within (chunk rows - 1) * t rows of the limit it can
+ * wrap back into range instead of being dropped -- stay clear of the limit by that margin (not tested: it takes a 4 GiB case). */
 int sed_gru_seq_fwd(int dtype, const float* gi, const float* bhh, const void* pack_fwd, float* hseq,
                     float* saved, int B, int t, int Hd, void* stream);
 /* BPTT: dhseq [B*t][2][Hd] -> dgi, dgh [B*t][2][3Hd] (gradients w.r.t. the input-side and the
- * hidden-side gate pre-activations).  The weight/bias/input gradients follow as plain GEMMs.     */
+ * hidden-side gate pre-activations).  The weight/bias/input gradients follow as plain GEMMs.
+ * A pure function of dhseq, hseq, saved, pack_bwd.  dgi = (dr, dz, dn), dgh = (dr, dz, dn * r), all fp32 from fp32 gate math;
+ * SED_BF16 rounds only the operands of the carry product dgh . W_hh (the step's dgh and W_hh, to bf16); the direct path dh * z
+ * and the carry itself stay fp32.  Same size limit and the same remark on rows past the batch as the forward call.              */
 int sed_gru_seq_bwd(int dtype, const float* dhseq, const float* hseq, const float* saved,
                     const void* pack_bwd, float* dgi, float* dgh, int B, int t, int Hd, void* stream);
 
