@@ -676,6 +676,18 @@ int sed_m5_conv1_wgrad_fused_pool(int dtype, const float* x, const void* dy, con
                                   const float* scale, const float* shift, const float* ca,
                                   const float* cb, const float* cc, float* dw_partial, int B, int L,
                                   void* stream);
+/* Data gradient of conv_block1.0 (/root/reference/models/waveform_models.py:15-24: what autograd leaves in the waveform's .grad),
+ * csrc/sed_m5_dgrad.hip:  dx[b][l] = sum_c sum_t dz[b][t][c] * w[c][l + 39 - 4t]  (0 <= l + 39 - 4t < 79, 0 <= t < L1),
+ * dz [B/8][L1][8][64] in the mode's type (SED_BF16 / SED_F32), w fp32 [64][79] (rounded to bf16 in bf16 mode, as the forward
+ * does), dx fp32 [B][L].  Every element of dx is written (no dependence on its previous contents) and the result is the same
+ * bits on every run.  bf16 runs on the bf16 matrix pipe, fp32 on the fp32 one (exact fp32 products, fp32 accumulation).
+ * sed_m5_conv1_dgrad_fused_pool (bf16): dz is rebuilt on load from the pooled gradient dy, the stored z, the layer's
+ * BatchNorm scale / shift and the (ca, cb, cc) rows of sed_bn_bwd_finalize / sed_bn_eval_bwd_finalize, exactly as
+ * sed_m5_conv1_wgrad_fused_pool rebuilds it: no dz tensor is written for the input gradient.                                  */
+int sed_m5_conv1_dgrad(int dtype, const void* dz, const float* w, float* dx, int B, int L, void* stream);
+int sed_m5_conv1_dgrad_fused_pool(int dtype, const void* dy, const void* zsrc, const float* scale, const float* shift,
+                                  const float* ca, const float* cb, const float* cc, const float* w, float* dx, int B,
+                                  int L, void* stream);
 /* BatchNorm1d -> ReLU -> MaxPool1d(4,4) over H (floor): y [N][H/4][W][Cp] = max relu(scale*z+shift) */
 int sed_bn_relu_maxpool4_fwd(int dtype, const void* z, const float* scale, const float* shift,
                              void* y, int N, int H, int W, int Cp, void* stream);

@@ -129,6 +129,8 @@ PROTOTYPES = {
     "sed_m5_conv1_wgrad": (_I, [_I, _P, _P, _P, _I, _I, _P]),
     "sed_m5_conv1_wgrad_fused": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "sed_m5_conv1_wgrad_fused_pool": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "sed_m5_conv1_dgrad": (_I, [_I, _P, _P, _P, _I, _I, _P]),
+    "sed_m5_conv1_dgrad_fused_pool": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "sed_m5_zfree_supported": (_I, [_I]),
     "sed_m5_alg_supported": (_I, [_I]),
     "sed_m5_conv1_gram_floats": (_Z, []),

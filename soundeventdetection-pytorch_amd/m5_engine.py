@@ -11,7 +11,8 @@ convolution, BN+ReLU+MaxPool1d(4) and its arg-max backward, the mean-over-time +
 Conv1d biases: every convolution feeds a BatchNorm1d, which subtracts the batch mean again, so the
 biases cannot influence the output (train or eval) and their true gradient is 0 (the reference's is
 fp32 rounding noise).  They are kept in the state_dict, folded into running_mean (which the reference
-tracks as mean(z + bias)) and get a zero gradient.
+tracks as mean(z + bias)) and get a zero gradient.  The one exception is the backward of an EVAL-mode forward
+(keep_for_grad): running statistics do not cancel the bias, whose gradient is then sum dz.
 
 PyTorch is plumbing (device memory, streams, parameter storage); there is no CPU fallback.
 """
@@ -132,19 +133,29 @@ class M5Engine:
                  [lib.sed_pool_bwd_nparts(N, l.H, 8, l.cout) for l in p.layers] + [lib.sed_conv_nparts(N, l.H, 8) for l in p.layers])
         p.bwd_part = torch.empty((nb, 2, max(l.cout for l in p.layers)), **f32)
         p.trained = False
+        p.keep = False             # the last forward ran with keep_for_grad (an eval-mode backward is possible)
+        p.dx_in = None             # (B, 1, L) fp32 input gradient of the last backward(need_dx=True)
         self._plans[key] = p
         return p
 
     # ------------------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], training: bool, update_running_stats: bool = True):
-        """x: (B, 1, L) float32 cuda, B % 8 == 0.  Leaves the logits in plan.pre (B, K)."""
+    def forward(self, x: torch.Tensor, P: Dict[str, torch.Tensor], training: bool, update_running_stats: bool = True,
+                keep_for_grad: bool = False):
+        """x: (B, 1, L) float32 cuda, B % 8 == 0.  Leaves the logits in plan.pre (B, K).
+        keep_for_grad: an eval-mode forward also stores what backward() needs -- conv_block1's z (which the two-pass eval forward
+        does not store otherwise) and every layer's (mean, invstd) from the running statistics; the logits are the same bits.
+        Without it the launches are exactly those of a plain forward; a training-mode forward keeps everything anyway."""
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[1] == 1):
             raise ValueError("expected a float32 CUDA tensor of shape (B, 1, L)")
         x = x.contiguous()
         B, _, Lw = x.shape
         p = self.plan(B, Lw, x.device)
         lib, dt, st, N = self.lib, self.dt, _stream(), p.N
-        p.x_ref, p.trained = x, training
+        keep = bool(keep_for_grad) and not training
+        if keep and (p.zfree or p.alg):
+            raise RuntimeError("SED_M5_ZFREE=1 / SED_M5_ALG=1 never form conv_block1's z / dz: an eval-mode forward kept for a "
+                               "backward is not available with them (unset the experiment)")
+        p.x_ref, p.trained, p.keep = x, training, bool(keep_for_grad)
         prev = None
         for i, ly in enumerate(p.layers):
             self._tag = f"fwd {ly.conv} {ly.cin}->{ly.cout} L{ly.H}"
@@ -191,10 +202,13 @@ class M5Engine:
                 torch.sub(rm, bias, out=ly.rm_nobias)
                 self._k("sed_bn_eval_coeffs", lib.sed_bn_eval_coeffs, L.ptr(g), L.ptr(b), L.ptr(ly.rm_nobias), L.ptr(rv), BN_EPS,
                         L.ptr(ly.scale), L.ptr(ly.shift), ly.cout, ly.cout, st)
+                if keep:      # BatchNorm as the fixed affine map of its running statistics: (mean, invstd) for the backward statistics
+                    self._k("sed_bn_eval_stats", lib.sed_bn_eval_stats, L.ptr(ly.rm_nobias), L.ptr(rv), BN_EPS, L.ptr(ly.mean),
+                            L.ptr(ly.invstd), ly.cout, ly.cout, st)
             if hasattr(ly, "y"):
                 if ly.first and p.fwd2:
                     self._k("sed_m5_conv1_bn_relu_pool_fwd", lib.sed_m5_conv1_bn_relu_pool_fwd, dt, L.ptr(x), L.ptr(w), L.ptr(ly.scale),
-                            L.ptr(ly.shift), L.ptr(ly.y), None if p.zfree else (L.ptr(ly.z) if training else None), B, Lw, st)
+                            L.ptr(ly.shift), L.ptr(ly.y), None if p.zfree else (L.ptr(ly.z) if (training or keep) else None), B, Lw, st)
                 elif ly.pool:
                     self._k("sed_bn_relu_maxpool4_fwd", lib.sed_bn_relu_maxpool4_fwd, dt, L.ptr(ly.z), L.ptr(ly.scale),
                             L.ptr(ly.shift), L.ptr(ly.y), N, ly.H, 8, ly.cout, st)
@@ -217,12 +231,26 @@ class M5Engine:
 
     # ------------------------------------------------------------------------------------------
     def backward(self, p, P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], dlogits: torch.Tensor = None,
-                 on_group_done=None):
-        """Backward of the last training-mode forward; gradients into G[name] (overwritten).  `on_group_done(key)` is
+                 on_group_done=None, need_dx: bool = False):
+        """Backward of the last forward; gradients into G[name] (overwritten).  `on_group_done(key)` is
         called when the gradients of a top-level module (fc, conv_block5 ... conv_block1) are enqueued: the
-        data-parallel trainer starts that bucket's all-reduce there (train.py: GradAllReducer)."""
-        if not p.trained:
-            raise RuntimeError("backward() needs a training-mode forward (batch statistics)")
+        data-parallel trainer starts that bucket's all-reduce there (train.py: GradAllReducer).
+        need_dx: also the gradient of the (B, 1, L) input, into a fresh plan.dx_in (csrc/sed_m5_dgrad.hip, launched after
+        conv_block1's weight gradient); the parameter gradients are the same bits with and without it.
+        An eval-mode forward (BatchNorm as the fixed affine map of its running statistics: ca = gamma*invstd, cb = cc = 0,
+        dgamma = sum g*xhat, dbeta = sum g) can be differentiated when it ran with keep_for_grad=True; the Conv1d biases, which
+        batch statistics cancel (zero gradient in training mode), then get d bias = sum dz = ca * dbeta.  Running statistics are
+        not touched.  Without need_dx a training-mode backward launches exactly what it did before these two kinds existed."""
+        eval_bwd = not p.trained
+        if eval_bwd and not getattr(p, "keep", False):
+            raise RuntimeError("backward() through an eval-mode forward needs forward(..., keep_for_grad=True); otherwise a "
+                               "training-mode forward (batch statistics)")
+        need_dx = bool(need_dx)
+        if (eval_bwd or need_dx) and getattr(self, "bn_sync", None) is not None:
+            raise RuntimeError("input-gradient and eval-mode backward are not available with SyncBN")
+        if (eval_bwd or need_dx) and (p.zfree or p.alg):
+            raise RuntimeError("SED_M5_ZFREE=1 / SED_M5_ALG=1 never form conv_block1's z / dz: the input gradient and the eval-mode "
+                               "backward are not available with them (unset the experiment)")
         lib, dt, st, N, B = self.lib, self.dt, _stream(), p.N, p.B
         src = p.dpre if dlogits is None else dlogits.contiguous().float()
         last = p.layers[-1]
@@ -237,7 +265,8 @@ class M5Engine:
             H, C = ly.H, ly.cout
             count = float(B * H)
             gname, bname = ly.bn + ".weight", ly.bn + ".bias"
-            G[ly.conv + ".bias"].zero_()          # BatchNorm removes the conv bias: zero gradient
+            if not eval_bwd:
+                G[ly.conv + ".bias"].zero_()          # BatchNorm removes the conv bias: zero gradient
             ca, cb, cc = ly.coef[0], ly.coef[1], ly.coef[2]
             if hasattr(ly, "y"):
                 # ---- block output layer: (pool +) ReLU + BN backward statistics from dy -------------------
@@ -257,9 +286,10 @@ class M5Engine:
                     nparts = lib.sed_maxpool4_bwd_nparts(N, H, 8, C)
                     # first layer, bf16: its matrix-pipe weight gradient rebuilds g from (dy, z) itself -> statistics only here
                     g_free = ly.first and dt == L.SED_BF16 and _os.environ.get("SED_M5_MFMA", "1") != "0"
-                    if g_free and _os.environ.get("SED_M5_POOLSTATS", "1") != "0":
+                    if g_free and not eval_bwd and _os.environ.get("SED_M5_POOLSTATS", "1") != "0":
                         # statistics from the pooled tensors (y, dy): a quarter of z's rows each; the z pass only runs when an
-                        # ill-conditioned channel (|beta| > 8 |gamma|) raised the flag.  ONE flag word: sed_maxpool4_relu_bwd_if resets it
+                        # ill-conditioned channel (|beta| > 8 |gamma|) raised the flag (training only: the shortcut rests on batch
+                    # statistics, an eval-mode backward takes the z pass below).  ONE flag word: sed_maxpool4_relu_bwd_if resets it
                         # on the stream after consuming it, so the same pointers serve every step (and a graph replay of them)
                         fl = p.pool_flag
                         self._k("sed_maxpool4_pooled_stats", lib.sed_maxpool4_pooled_stats, dt, L.ptr(ly.dy), L.ptr(ly.y), L.ptr(ly.scale),
@@ -281,8 +311,14 @@ class M5Engine:
                 #      data-gradient epilogue of the layer above (in dzB / bwd_part) -----------------------------
                 nparts = lib.sed_conv_nparts(N, H, 8)
                 dzmode, gsrc, pool = L.DZ_BN, dzB, 1
-            self._k("sed_bn_bwd_finalize", lib.sed_bn_bwd_finalize, L.ptr(p.bwd_part), nparts, count, L.ptr(P[gname]), L.ptr(ly.mean),
-                    L.ptr(ly.invstd), L.ptr(G[gname]), L.ptr(G[bname]), L.ptr(ca), L.ptr(cb), L.ptr(cc), C, C, st)
+            if eval_bwd:
+                self._k("sed_bn_eval_bwd_finalize", lib.sed_bn_eval_bwd_finalize, L.ptr(p.bwd_part), nparts, L.ptr(P[gname]),
+                        L.ptr(ly.mean), L.ptr(ly.invstd), L.ptr(G[gname]), L.ptr(G[bname]), L.ptr(ca), L.ptr(cb), L.ptr(cc), C, C, st)
+                # running statistics do not cancel the Conv1d bias: d bias = sum dz = ca * sum g
+                torch.mul(ca, G[bname], out=G[ly.conv + ".bias"])
+            else:
+                self._k("sed_bn_bwd_finalize", lib.sed_bn_bwd_finalize, L.ptr(p.bwd_part), nparts, count, L.ptr(P[gname]),
+                        L.ptr(ly.mean), L.ptr(ly.invstd), L.ptr(G[gname]), L.ptr(G[bname]), L.ptr(ca), L.ptr(cb), L.ptr(cc), C, C, st)
             if ly.first:
                 # dz1 = BN backward of g, then the k=79 weight gradient
                 if p.alg:         # dW1 = ca*G1 + cb*(w1 . Gram) + cc*Sp: dz1 is never formed
@@ -301,10 +337,19 @@ class M5Engine:
                     # matrix-pipe kernel, dz rebuilt on load from (g, z): no separate BatchNorm-backward pass, dz never written
                     self._k("sed_m5_conv1_wgrad_fused_pool", lib.sed_m5_conv1_wgrad_fused_pool, dt, L.ptr(p.x_ref), L.ptr(ly.dy),
                             L.ptr(ly.z), L.ptr(ly.scale), L.ptr(ly.shift), L.ptr(ca), L.ptr(cb), L.ptr(cc), L.ptr(p.c1_ws), B, p.L, st)
+                    if need_dx:       # the input gradient rebuilds dz the same way: still no dz tensor
+                        p.dx_in = torch.empty((B, 1, p.L), dtype=torch.float32, device=p.x_ref.device)     # (fresh: autograd keeps it)
+                        self._k("sed_m5_conv1_dgrad_fused_pool", lib.sed_m5_conv1_dgrad_fused_pool, dt, L.ptr(ly.dy), L.ptr(ly.z),
+                                L.ptr(ly.scale), L.ptr(ly.shift), L.ptr(ca), L.ptr(cb), L.ptr(cc), L.ptr(P[ly.conv + ".weight"]),
+                                L.ptr(p.dx_in), B, p.L, st)
                 else:
                     self._k("sed_bn_bwd_apply", lib.sed_bn_bwd_apply, dt, L.ptr(gsrc), L.ptr(ly.z), L.ptr(ca), L.ptr(cb), L.ptr(cc),
                             L.ptr(dzA), N * H * 8, C, st)
                     self._k("sed_m5_conv1_wgrad", lib.sed_m5_conv1_wgrad, dt, L.ptr(p.x_ref), L.ptr(dzA), L.ptr(p.c1_ws), B, p.L, st)
+                    if need_dx:       # from the dz this route materialises
+                        p.dx_in = torch.empty((B, 1, p.L), dtype=torch.float32, device=p.x_ref.device)
+                        self._k("sed_m5_conv1_dgrad", lib.sed_m5_conv1_dgrad, dt, L.ptr(dzA), L.ptr(P[ly.conv + ".weight"]),
+                                L.ptr(p.dx_in), B, p.L, st)
                 self._k("sed_sum_partials", lib.sed_sum_partials, L.ptr(p.c1_ws), p.c1_ws.shape[0], 80 * 64, L.ptr(p.c1_dw), st)
                 G[ly.conv + ".weight"].copy_(p.c1_dw[:79].t().reshape(64, 1, 79))
                 if on_group_done is not None:

@@ -136,6 +136,13 @@ def get_waveform_dataset_and_model(args, device):
     return dataset, model, criterion, cfg_descriptor
 
 
+def validate_args(args):
+    """Combinations that cannot run, refused before any dataset or device work."""
+    if args.train_features.lower() == "waveform" and args.precision not in ("bf16", "fp32"):
+        raise ValueError(f"--train_features Waveform (the M5 model) supports --precision bf16 and fp32 only, "
+                         f"'{args.precision}' given (f16x3 / bf16x3 exist for the spectrogram models)")
+
+
 def get_dataset_and_model(args, device):
     """main.py:77-83."""
     feats = args.train_features.lower()
@@ -165,6 +172,7 @@ def make_loader(dataset, batch_size):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    validate_args(args)
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X visible: this build has no CPU training path")
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -70,25 +70,34 @@ class _M5Function(torch.autograd.Function):
                 raise RuntimeError("M5 on the MI355X interleaves 8 frames per tile: training batches must be a "
                                    "multiple of 8 (BatchNorm statistics must not see padding frames)")
             x = torch.cat([x, x.new_zeros((pad,) + tuple(x.shape[1:]))], 0)
-        plan = model.engine.forward(x, P, model.training)
+        # an eval forward that something will be differentiated through (grad mode on -- M5.forward notes it, inside a Function's
+        # forward it is always off -- and an input that requires grad) keeps what the eval-mode backward needs; same logits
+        keep = (not model.training) and model._grad_mode and any(ctx.needs_input_grad)
+        plan = model.engine.forward(x, P, model.training, keep_for_grad=keep)
         if model.training:
             model._nbt_pending += 1
         model._fwd_serial += 1
-        ctx.model, ctx.plan, ctx.serial, ctx.training = model, plan, model._fwd_serial, model.training
+        ctx.model, ctx.plan, ctx.serial, ctx.training, ctx.keep = model, plan, model._fwd_serial, model.training, keep
+        ctx.batch = B
         return plan.pre[:B].clone()
 
     @staticmethod
     def backward(ctx, dlogits):
         model = ctx.model
-        if not ctx.training:
-            raise RuntimeError("backward through an eval-mode forward is not supported; call model.train()")
+        if not ctx.training and not getattr(ctx, "keep", False):
+            raise RuntimeError("backward through an eval-mode forward that was not kept for it (run the forward under grad mode "
+                               "with an input or parameter that requires grad), or call model.train()")
         if ctx.serial != model._fwd_serial:
             raise RuntimeError("the activations of this forward were overwritten by a later forward of the same shape")
         P = model._tensor_dict()
         names = [n for n, _ in model.named_parameters()]
         G = {n: torch.empty_like(P[n]) for n in names}
-        model.engine.backward(ctx.plan, P, G, dlogits=dlogits)
-        return (None, None) + tuple(G[n] for n in names)
+        B, need_dx = ctx.batch, bool(ctx.needs_input_grad[1])
+        dlogits = dlogits.contiguous().float()
+        if ctx.plan.B != B:       # eval batch padding: the padded frames carry no upstream gradient (and BatchNorm does not couple frames)
+            dlogits = torch.cat([dlogits, dlogits.new_zeros((ctx.plan.B - B,) + tuple(dlogits.shape[1:]))], 0)
+        model.engine.backward(ctx.plan, P, G, dlogits=dlogits, need_dx=need_dx)
+        return (None, ctx.plan.dx_in[:B] if need_dx else None) + tuple(G[n] for n in names)
 
 
 class M5(nn.Module):
@@ -114,6 +123,7 @@ class M5(nn.Module):
         self.engine = M5Engine(classes_num, self.precision)
         self._fwd_serial = 0
         self._nbt_pending = 0
+        self._grad_mode = False         # torch.is_grad_enabled() at the current forward() call
 
     def set_precision(self, precision: str):
         self.precision = precision
@@ -143,6 +153,7 @@ class M5(nn.Module):
         if not next(self.parameters()).is_cuda:
             raise RuntimeError("model parameters are on the CPU; call model.to('cuda')")
         params = [p for _, p in self.named_parameters()]
+        self._grad_mode = torch.is_grad_enabled()
         return _M5Function.apply(self, x.float(), *params)
 
     def model_description(self):
