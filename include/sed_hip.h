@@ -616,8 +616,17 @@ int sed_conv3x3_wgrad_fused_c1(int dtype, const float* x1, const float* fmean, c
  * with their weights expanded to 3x3 (zero side columns); these entry points add what only M5 has.
  * conv_block1.0 = Conv1d(1, 64, 79, stride 4, pad 39): x fp32 [B][L], w fp32 [64][79],
  * z [B/8][L1][8][64] with L1 = sed_m5_conv1_len(L); the bias is NOT applied (BatchNorm1d removes it).
- * stats_partial fp32 [sed_m5_conv1_nparts][2][64] (sum z, sum z^2; nullable).
- * wgrad: dw_partial fp32 [sed_m5_conv1_nparts][80][64] (tap-major, tap 79 is padding).            */
+ * stats_partial fp32 [sed_m5_conv1_nparts][2][64] (sum z, sum z^2; nullable).  What is summed: the fp32 kernels (SED_F32, and
+ * SED_BF16 under SED_M5_MFMA=0) sum their fp32 accumulators, also when z is stored as bf16; the matrix-pipe kernels
+ * (sed_m5_conv1_fwd in SED_BF16, sed_m5_conv1_stats) sum the bf16-rounded values as stored.
+ * wgrad: dw_partial fp32 [sed_m5_conv1_nparts][80][64] (tap-major).  Tap row 79 is padding: every kernel writes it, its
+ * value is UNSPECIFIED (the fp32 kernel leaves a contraction there, the matrix-pipe kernels 0) and consumers read rows
+ * 0..78 only (sed_m5_conv1_wgrad_combine does not read row 79 of g1).  Every one of the nparts rows is written.
+ * The pooled forms (sed_m5_conv1_bn_relu_pool_fwd, sed_m5_conv1_pool_bwd_stats, sed_m5_conv1_wgrad_fused_pool[_x],
+ * sed_m5_conv1_bwd_stats_g1, sed_m5_conv1_dgrad_fused_pool) need L1 >= 4, the sed_*maxpool4* entry points H >= 4: the
+ * pooled tensor must have at least one row.  All of them, the recomputing kernels included, decide as MaxPool1d does:
+ * the FIRST arg-max of relu(scale*z + shift) in a window of 4 (ties keep the earlier step) takes the gradient, and only
+ * when that maximum is > 0 (a window whose largest pre-activation is <= 0 passes nothing).          */
 int sed_m5_conv1_len(int L);
 int sed_m5_conv1_nparts(int B, int L);
 int sed_m5_conv1_fwd(int dtype, const float* x, const float* w, void* z, float* stats_partial, int B,
