@@ -280,6 +280,37 @@ int sed_adam_amsgrad_step(float* p, const float* g, float* m, float* v, float* v
 int sed_adam_amsgrad_step_dev(float* p, const float* g, float* m, float* v, float* vmax, size_t n,
                               float* hyper, int* step, float beta1, float beta2, float eps,
                               float grad_scale, float lr_decay, int decay_every, void* stream);
+/* Global L2 norm of the scaled gradient and the clip factor of torch.nn.utils.clip_grad_norm_(norm_type=2,
+ * error_if_nonfinite=False) on a flat fp32 buffer of n elements:
+ *   out[0] = (float)sqrt(sum_i ((double)(g[i] * grad_scale))^2)    -- fp64 accumulation: finite fp32 inputs never overflow, the
+ *                                                                     result is the float64 norm to within one fp32 ulp
+ *   out[1] = coef = min(1, max_norm / (out[0] + 1e-6f)) in fp32, torch's clamp(max=1.0); max_norm <= 0: measure only, coef = 1.
+ * A NaN or inf norm propagates the way torch's does (inf -> coef 0, NaN -> coef NaN): there is no skip-step policy.
+ * Two plain launches (per-workgroup fp64 partials, then one workgroup), fixed summation order, no atomics; the grid is a
+ * function of n alone, so two runs give the same bits.  g is not modified: the optimizer step below applies coef.
+ * partial: sed_grad_norm_nparts(n) doubles (8-byte aligned); nparts must be that value; out: 2 floats.               */
+int sed_grad_norm_nparts(size_t n);
+int sed_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, double* partial, int nparts,
+                  float* out, void* stream);
+/* torch.optim.Adam / torch.optim.AdamW step with optional amsgrad, weight decay and gradient clipping, on flat fp32 buffers of
+ * n elements (16-byte aligned).  Per element, with gse = grad_scale * coef[0] (coef: device pointer, e.g. out + 1 of
+ * sed_grad_norm; NULL = 1):
+ *   gr = g * gse                                                (clip_grad_norm_'s g.mul_(coef) of the averaged gradient)
+ *   !decoupled: gr += weight_decay * p                          (torch.optim.Adam(weight_decay=))
+ *    decoupled: p *= (float)(1 - lr * weight_decay)             (torch.optim.AdamW, before the update)
+ *   m, v, vmax, denom, p as sed_adam_amsgrad_step; vmax NULL = amsgrad off (v takes vmax's place in denom, vmax is not touched).
+ * The two scale factors are multiplied first so that the element arithmetic is sed_adam_amsgrad_step's own: with
+ * weight_decay = 0, vmax given and coef NULL or 1.0f the results are bit-identical to it.  weight_decay >= 0.         */
+int sed_adam_step_ex(float* p, const float* g, float* m, float* v, float* vmax, size_t n, float lr, float beta1,
+                     float beta2, float eps, int step, float grad_scale, float weight_decay, int decoupled,
+                     const float* coef, void* stream);
+/* The same with the per-step scalars in device memory, as sed_adam_amsgrad_step_dev (same hyper / step protocol, same
+ * bits in the same reduced case).  With decoupled decay (weight_decay > 0) hyper has FOUR floats: hyper[3] receives the
+ * learning rate of the step being taken (hyper[0] may already hold the decayed one), and the factor is
+ * (float)(1 - hyper[3] * weight_decay).                                                                               */
+int sed_adam_step_ex_dev(float* p, const float* g, float* m, float* v, float* vmax, size_t n, float* hyper,
+                         int* step, float beta1, float beta2, float eps, float grad_scale, float lr_decay,
+                         int decay_every, float weight_decay, int decoupled, const float* coef, void* stream);
 
 /* ---- log-mel front-end ---------------------------------------------------------------------
  * multichannel_stft + multichannel_complex_to_log_mel (+ transform) for one channel batch

@@ -1,5 +1,5 @@
-// BatchNorm finalisation, fused BN+ReLU+avg-pool (fwd/bwd), head, weighted BCE, Adam-amsgrad and
-// layout utilities for gfx950.  All HBM-bound: 16-byte vector accesses, fp32 math, deterministic
+// BatchNorm finalisation, fused BN+ReLU+avg-pool (fwd/bwd), head, weighted BCE, Adam-amsgrad (and its extended form: gradient
+// norm / clip factor, weight decay, AdamW) and layout utilities for gfx950.  All HBM-bound: 16-byte vector accesses, fp32 math, deterministic
 // two-stage reductions (per-workgroup partials + fixed-order finalise), no float atomics.
 #include "common.h"
 
@@ -1092,6 +1092,220 @@ extern "C" int sed_adam_amsgrad_step(float* p, const float* g, float* m, float* 
     const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
     adam_amsgrad_kernel<<<ew_grid((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(p, g, m, v, vmax, n, omb1, beta2, omb2,
                                                                                eps, step_size, inv_sqrt_bc2, grad_scale);
+    SED_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Global gradient norm + clip factor (torch.nn.utils.clip_grad_norm_, norm_type 2) on the flat gradient buffer.
+// Two plain launches, no atomics: every thread squares and adds its grid-strided elements in fp64 (finite fp32 inputs cannot
+// overflow, and the rounding of the sum is ~2^-53 * n relative whatever the order), a workgroup folds its 256 sums through LDS in
+// a fixed tree, one double per workgroup; a single workgroup folds those the same way.  The grid depends on n alone.
+// ---------------------------------------------------------------------------------------------
+#define SED_GNORM_MAX_PARTS 1024
+static inline int grad_norm_nparts(size_t n) {
+    const size_t g = (n + 1023) / 1024;               // >= 4 elements per thread before another workgroup is added
+    return (int)(g < 1 ? 1 : (g > SED_GNORM_MAX_PARTS ? SED_GNORM_MAX_PARTS : g));
+}
+
+__device__ __forceinline__ double block256_sum_f64(double t, double* sh) {
+    sh[threadIdx.x] = t;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s >= 1; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__global__ __launch_bounds__(256) void grad_sqsum_kernel(const float* __restrict__ g, size_t n, float grad_scale,
+                                                         double* __restrict__ partial) {
+    __shared__ double sh[256];
+    double t = 0.0;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const double x = (double)(g[i] * grad_scale);                  // the fp32 value the optimizer sees
+        t += x * x;
+    }
+    t = block256_sum_f64(t, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const double* __restrict__ partial, int nparts, float max_norm,
+                                                              float* __restrict__ out) {
+    __shared__ double sh[256];
+    double t = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) t += partial[i];
+    t = block256_sum_f64(t, sh);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(t);
+        float coef = 1.0f;
+        if (max_norm > 0.0f) {
+            // clip_coef = max_norm / (total_norm + 1e-6); clamp(max=1.0) -- fp32, a NaN stays a NaN like torch.clamp's
+            const float c = max_norm / (norm + 1e-6f);
+            coef = c > 1.0f ? 1.0f : c;
+        }
+        out[0] = norm;
+        out[1] = coef;
+    }
+}
+
+extern "C" int sed_grad_norm_nparts(size_t n) { return grad_norm_nparts(n); }
+
+extern "C" int sed_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, double* partial, int nparts, float* out,
+                             void* stream) {
+    SED_REQUIRE(g && partial && out, "null argument");
+    SED_REQUIRE(nparts == grad_norm_nparts(n), "nparts must be sed_grad_norm_nparts(n)");
+    SED_REQUIRE((((uintptr_t)partial) & 7) == 0, "partial must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    grad_sqsum_kernel<<<nparts, 256, 0, st>>>(g, n, grad_scale, partial);
+    SED_LAUNCH_CHECK();
+    grad_norm_final_kernel<<<1, 256, 0, st>>>(partial, nparts, max_norm, out);
+    SED_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adam / AdamW with optional amsgrad, weight decay and a device-resident clip factor.  The per-element expressions are those of
+// adam_amsgrad_kernel / adam_amsgrad_dev_kernel above, written once; the clip factor is folded into the gradient scale
+// (gse = grad_scale * coef, one scalar product per thread), so with coef absent or 1.0f, no decay and amsgrad on the element
+// arithmetic IS the existing kernels' -- whatever the compiler contracts -- and the results are the same bits.
+//   WD 0: none   1: L2, gr += wd * p (torch.optim.Adam(weight_decay=))   2: decoupled, p *= 1 - lr * wd first (torch.optim.AdamW)
+// ---------------------------------------------------------------------------------------------
+// The decay terms are new arithmetic, and the file is compiled with -ffp-contract=fast: left to the compiler, gr + wd * p becomes
+// fma(g, gse, wd * p) in the vectorised body and fma(wd, p, g * gse) in the scalar one, and the host and device forms disagree in
+// the last bit of m.  rounded() hands a value through an empty asm, so it is an fp32 number of its own that nothing fuses across:
+// the decay terms round where torch's do, in every form alike.  The WD 0 path does not use it.
+__device__ __forceinline__ float rounded(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+template <bool AMS, int WD>
+__device__ __forceinline__ void adam_ex_elem(float& p, const float g, float& m, float& v, float& x, const float gse, const float wd,
+                                             const float decay, const float one_minus_b1, const float b2, const float one_minus_b2,
+                                             const float eps, const float step_size, const float inv_sqrt_bc2) {
+    float gr = g * gse;
+    if (WD == 1) gr = rounded(gr) + rounded(wd * p);                   // grad.add(param, alpha=wd): product and sum each rounded
+    if (WD == 2) p = rounded(p * decay);                               // param.mul_(1 - lr * wd), rounded before the update
+    m = m + one_minus_b1 * (gr - m);
+    v = v * b2 + (one_minus_b2 * gr) * gr;
+    if (AMS) x = fmaxf(x, v);
+    const float denom = sqrtf(AMS ? x : v) * inv_sqrt_bc2 + eps;
+    p = p - step_size * (m / denom);
+}
+
+template <bool AMS, int WD>
+__global__ __launch_bounds__(256) void adam_ex_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, float* __restrict__ vmax, size_t n, float one_minus_b1,
+                                                      float b2, float one_minus_b2, float eps, float step_size, float inv_sqrt_bc2,
+                                                      float grad_scale, float wd, float decay, const float* __restrict__ coef) {
+    const float gse = coef ? grad_scale * coef[0] : grad_scale;
+    const size_t n4 = n >> 2;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+        f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
+        f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+        f32x4 xv = {0.f, 0.f, 0.f, 0.f};
+        if (AMS) xv = reinterpret_cast<f32x4*>(vmax)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float pe = pv[e], me = mv[e], ve = vv[e], xe = xv[e];
+            adam_ex_elem<AMS, WD>(pe, gv[e], me, ve, xe, gse, wd, decay, one_minus_b1, b2, one_minus_b2, eps, step_size,
+                                  inv_sqrt_bc2);
+            pv[e] = pe; mv[e] = me; vv[e] = ve; xv[e] = xe;
+        }
+        reinterpret_cast<f32x4*>(p)[i] = pv;
+        reinterpret_cast<f32x4*>(m)[i] = mv;
+        reinterpret_cast<f32x4*>(v)[i] = vv;
+        if (AMS) reinterpret_cast<f32x4*>(vmax)[i] = xv;
+    }
+    // tail
+    const size_t tail0 = n4 << 2;
+    const size_t gt = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (gt < n - tail0) {
+        const size_t i = tail0 + gt;
+        float pe = p[i], me = m[i], ve = v[i], xe = AMS ? vmax[i] : 0.f;
+        adam_ex_elem<AMS, WD>(pe, g[i], me, ve, xe, gse, wd, decay, one_minus_b1, b2, one_minus_b2, eps, step_size, inv_sqrt_bc2);
+        p[i] = pe; m[i] = me; v[i] = ve;
+        if (AMS) vmax[i] = xe;
+    }
+}
+
+// hyper[3] = the learning rate of the step about to be taken: adam_hyper_kernel may already replace hyper[0] by the next step's
+__global__ void adam_keep_lr_kernel(float* __restrict__ hyper) { hyper[3] = hyper[0]; }
+
+template <bool AMS, int WD>
+__global__ __launch_bounds__(256) void adam_ex_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, float* __restrict__ vmax, size_t n,
+                                                          float one_minus_b1, float b2, float one_minus_b2, float eps,
+                                                          const float* __restrict__ hyper, float grad_scale, float wd,
+                                                          const float* __restrict__ coef) {
+    const float step_size = hyper[1], inv_sqrt_bc2 = hyper[2];
+    const float gse = coef ? grad_scale * coef[0] : grad_scale;
+    const float decay = WD == 2 ? (float)(1.0 - (double)hyper[3] * (double)wd) : 1.0f;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float pe = p[i], me = m[i], ve = v[i], xe = AMS ? vmax[i] : 0.f;
+        adam_ex_elem<AMS, WD>(pe, g[i], me, ve, xe, gse, wd, decay, one_minus_b1, b2, one_minus_b2, eps, step_size, inv_sqrt_bc2);
+        p[i] = pe; m[i] = me; v[i] = ve;
+        if (AMS) vmax[i] = xe;
+    }
+}
+
+#define SED_ADAM_EX_DISPATCH(LAUNCH)                                   \
+    do {                                                               \
+        if (vmax) {                                                    \
+            if (wdm == 0) { LAUNCH(true, 0); }                         \
+            else if (wdm == 1) { LAUNCH(true, 1); }                    \
+            else { LAUNCH(true, 2); }                                  \
+        } else {                                                       \
+            if (wdm == 0) { LAUNCH(false, 0); }                        \
+            else if (wdm == 1) { LAUNCH(false, 1); }                   \
+            else { LAUNCH(false, 2); }                                 \
+        }                                                              \
+    } while (0)
+
+extern "C" int sed_adam_step_ex(float* p, const float* g, float* m, float* v, float* vmax, size_t n, float lr, float beta1,
+                                float beta2, float eps, int step, float grad_scale, float weight_decay, int decoupled,
+                                const float* coef, void* stream) {
+    SED_REQUIRE(step >= 1, "step is 1-based");
+    SED_REQUIRE(p && g && m && v, "null argument");
+    SED_REQUIRE(weight_decay >= 0.0f && weight_decay < INFINITY, "weight_decay must be finite and >= 0");
+    SED_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)vmax) & 15) == 0,
+                "flat buffers must be 16-byte aligned");
+    const double bc1 = 1.0 - pow((double)beta1, step);
+    const double bc2 = 1.0 - pow((double)beta2, step);
+    const float step_size = (float)((double)lr / bc1);
+    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
+    const float decay = (float)(1.0 - (double)lr * (double)weight_decay);        // param.mul_(1 - lr * weight_decay)
+    const int wdm = weight_decay == 0.0f ? 0 : (decoupled ? 2 : 1);
+    hipStream_t st = (hipStream_t)stream;
+#define SED_ADAM_EX_HOST(A, W)                                                                                                  \
+    adam_ex_kernel<A, W><<<ew_grid((n + 3) / 4), 256, 0, st>>>(p, g, m, v, vmax, n, omb1, beta2, omb2, eps, step_size,          \
+                                                               inv_sqrt_bc2, grad_scale, weight_decay, decay, coef)
+    SED_ADAM_EX_DISPATCH(SED_ADAM_EX_HOST);
+#undef SED_ADAM_EX_HOST
+    SED_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sed_adam_step_ex_dev(float* p, const float* g, float* m, float* v, float* vmax, size_t n, float* hyper, int* step,
+                                    float beta1, float beta2, float eps, float grad_scale, float lr_decay, int decay_every,
+                                    float weight_decay, int decoupled, const float* coef, void* stream) {
+    SED_REQUIRE(p && g && m && v && hyper && step, "null argument");
+    SED_REQUIRE(weight_decay >= 0.0f && weight_decay < INFINITY, "weight_decay must be finite and >= 0");
+    hipStream_t st = (hipStream_t)stream;
+    const int wdm = weight_decay == 0.0f ? 0 : (decoupled ? 2 : 1);
+    if (wdm == 2) adam_keep_lr_kernel<<<1, 1, 0, st>>>(hyper);
+    adam_hyper_kernel<<<1, 1, 0, st>>>(hyper, step, beta1, beta2, lr_decay, decay_every);
+    const float omb1 = (float)(1.0 - (double)beta1), omb2 = (float)(1.0 - (double)beta2);
+#define SED_ADAM_EX_DEV(A, W)                                                                                                   \
+    adam_ex_dev_kernel<A, W><<<ew_grid(n), 256, 0, st>>>(p, g, m, v, vmax, n, omb1, beta2, omb2, eps, hyper, grad_scale,        \
+                                                         weight_decay, coef)
+    SED_ADAM_EX_DISPATCH(SED_ADAM_EX_DEV);
+#undef SED_ADAM_EX_DEV
     SED_LAUNCH_CHECK();
     return 0;
 }

@@ -136,7 +136,34 @@ class KernelTimer:
         return out
 
 
-class CnnEngine:
+class OptimizerExtMixin:
+    """grad_norm() and the extended optimizer step (weight decay, AdamW, amsgrad off, clip factor) for an engine with
+    self.lib and self._k -- shared by CnnEngine and M5Engine.  Nothing here runs unless FusedTrainer was given an option."""
+
+    def grad_norm(self, flat_g, partial, out, grad_scale: float = 1.0, max_norm: float = 0.0):
+        """out[0] = ||flat_g * grad_scale||_2, out[1] = clip_grad_norm_'s factor (1 when max_norm <= 0).  partial: float64
+        workspace of sed_grad_norm_nparts(n) elements; out: fp32 (2,).  Two launches, no sync."""
+        self._k("sed_grad_norm", self.lib.sed_grad_norm, L.ptr(flat_g), flat_g.numel(), float(grad_scale), float(max_norm),
+                L.ptr(partial), partial.numel(), L.ptr(out), _stream())
+
+    def adam_step_ex(self, flat_p, flat_g, flat_m, flat_v, flat_vmax, lr: float, step: int, grad_scale: float = 1.0,
+                     betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, decoupled: bool = False, coef=None):
+        """flat_vmax None: amsgrad off; coef: device fp32 (1,) clip factor or None"""
+        self._k("sed_adam_step_ex", self.lib.sed_adam_step_ex, L.ptr(flat_p), L.ptr(flat_g), L.ptr(flat_m), L.ptr(flat_v),
+                L.ptr(flat_vmax), flat_p.numel(), float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
+                float(grad_scale), float(weight_decay), int(bool(decoupled)), L.ptr(coef), _stream())
+
+    def adam_step_ex_dev(self, flat_p, flat_g, flat_m, flat_v, flat_vmax, hyper, step_dev, grad_scale: float, lr_decay: float,
+                         decay_every: int, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                         decoupled: bool = False, coef=None):
+        """the same with the scalars in device memory (graph replay); hyper holds 4 floats (sed_hip.h)"""
+        self._k("sed_adam_step_ex_dev", self.lib.sed_adam_step_ex_dev, L.ptr(flat_p), L.ptr(flat_g), L.ptr(flat_m), L.ptr(flat_v),
+                L.ptr(flat_vmax), flat_p.numel(), L.ptr(hyper), L.ptr(step_dev), float(betas[0]), float(betas[1]), float(eps),
+                float(grad_scale), float(lr_decay), int(decay_every), float(weight_decay), int(bool(decoupled)), L.ptr(coef),
+                _stream())
+
+
+class CnnEngine(OptimizerExtMixin):
     def __init__(self, classes_num: int, model_config: Sequence[Tuple[int, int]], in_channels: int = 1,
                  precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
                  mel_bins: Optional[int] = None):

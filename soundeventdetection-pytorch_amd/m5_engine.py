@@ -25,7 +25,7 @@ import os as _os
 import torch
 
 from . import _lib as L
-from .engine import BN_EPS, BN_MOMENTUM, KernelTimer, _stream
+from .engine import BN_EPS, BN_MOMENTUM, KernelTimer, OptimizerExtMixin, _stream
 
 # (block name, [(conv idx, bn idx, cin, cout)], pooled)  -- waveform_models.py:15-56
 M5_BLOCKS = [
@@ -42,7 +42,7 @@ class _Ly:
         self.conv, self.bn, self.cin, self.cout, self.H, self.first, self.pool = conv, bn, cin, cout, H, first, pool
 
 
-class M5Engine:
+class M5Engine(OptimizerExtMixin):
     def __init__(self, classes_num: int, precision: str = "fp32"):
         if precision not in ("bf16", "fp32"):
             raise ValueError("precision must be 'bf16' or 'fp32'")

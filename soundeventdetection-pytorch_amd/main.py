@@ -53,6 +53,14 @@ def build_parser():
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "f16x3", "bf16x3"])
     p.add_argument("--mel_bins", type=int, default=None,
                    help="log-mel bins of the features and the model's declared input width, 1..256 (default: the config's 64)")
+    p.add_argument("--weight_decay", type=float, default=0.0,
+                   help="this build only: Adam weight decay (L2, added to the gradient); with --adamw decoupled (default 0)")
+    p.add_argument("--adamw", action="store_true", default=False,
+                   help="this build only: decoupled weight decay (torch.optim.AdamW) instead of L2")
+    p.add_argument("--no_amsgrad", action="store_true", default=False,
+                   help="this build only: plain Adam / AdamW without the amsgrad maximum (the reference trains with amsgrad)")
+    p.add_argument("--clip_grad_norm", type=float, default=0.0,
+                   help="this build only: clip the global gradient L2 norm to this value before the step (default 0 = off)")
     return p
 
 
@@ -141,6 +149,17 @@ def validate_args(args):
     if args.train_features.lower() == "waveform" and args.precision not in ("bf16", "fp32"):
         raise ValueError(f"--train_features Waveform (the M5 model) supports --precision bf16 and fp32 only, "
                          f"'{args.precision}' given (f16x3 / bf16x3 exist for the spectrogram models)")
+    if getattr(args, "clip_grad_norm", 0.0) < 0:
+        raise ValueError(f"--clip_grad_norm must be >= 0 (0 = off), {args.clip_grad_norm} given")
+    from .train import check_optimizer_options
+    check_optimizer_options(**optimizer_options(args))
+
+
+def optimizer_options(args):
+    """the FusedTrainer keyword arguments of --weight_decay / --adamw / --no_amsgrad / --clip_grad_norm"""
+    clip = float(getattr(args, "clip_grad_norm", 0.0))
+    return {"weight_decay": float(getattr(args, "weight_decay", 0.0)), "decoupled_weight_decay": bool(getattr(args, "adamw", False)),
+            "amsgrad": not getattr(args, "no_amsgrad", False), "max_grad_norm": clip if clip != 0.0 else None}
 
 
 def get_dataset_and_model(args, device):
@@ -200,7 +219,7 @@ def main(argv=None):
         train_name += "_AD"
     train(model, dataloader, criterion, num_steps=args.num_train_steps,
           outputs_dir=os.path.join(args.outputs_root, train_name), device=device, lr=args.lr,
-          log_freq=args.log_freq)
+          log_freq=args.log_freq, **optimizer_options(args))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -284,15 +284,52 @@ class ShardedBatchLoader:
 # ----------------------------------------------------------------------------------------------
 # the fused optimizer + step
 # ----------------------------------------------------------------------------------------------
+def check_optimizer_options(weight_decay=0.0, decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None):
+    """Validate the optimizer options of FusedTrainer / FusedAdamAmsgrad (host only, before any device work).  Returns
+    (weight_decay, decoupled, amsgrad, max_grad_norm or None, ext): `ext` is False when every option has the reference's value
+    (Adam, amsgrad=True, no decay, no clipping) -- the trainer then launches exactly the reference step's kernels."""
+    wd = float(weight_decay)
+    if not (0.0 <= wd < float("inf")):
+        raise ValueError(f"weight_decay must be finite and >= 0 (got {weight_decay!r})")
+    mgn = None
+    if max_grad_norm is not None:
+        mgn = float(max_grad_norm)
+        if not (0.0 < mgn < float("inf")):
+            raise ValueError(f"max_grad_norm must be finite and > 0, or None for no clipping (got {max_grad_norm!r})")
+    dec, ams = bool(decoupled_weight_decay), bool(amsgrad)
+    return wd, dec, ams, mgn, (wd != 0.0 or not ams or mgn is not None)
+
+
+def check_state_amsgrad(group, amsgrad: bool):
+    """Refuse an optimizer state whose amsgrad flag is not the trainer's: the max_exp_avg_sq buffers exist on one side only."""
+    got = bool(group.get("amsgrad", False))
+    if amsgrad and not got:
+        raise ValueError("the fused optimizer is Adam with amsgrad=True (train.py:85)")
+    if got and not amsgrad:
+        raise ValueError("optimizer state has amsgrad=True but this trainer was built with amsgrad=False: "
+                         "build it with amsgrad=True to resume from this state")
+
+
 class FusedTrainer:
-    """Owns the flat buffers, the Adam-amsgrad state and the step counter for one model."""
+    """Owns the flat buffers, the Adam state and the step counter for one model."""
 
     def __init__(self, model, lr: float, recall_factor: float = 5.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 group=None, graph: bool = False, sync_bn: bool = False, n_buckets: Optional[int] = None):
+                 group=None, graph: bool = False, sync_bn: bool = False, n_buckets: Optional[int] = None,
+                 weight_decay: float = 0.0, decoupled_weight_decay: bool = False, amsgrad: bool = True,
+                 max_grad_norm: Optional[float] = None):
         """graph=True (single process): after two eager steps per input shape the whole step -- forward, loss, backward,
         Adam-amsgrad with its step counter, learning rate and bias corrections in device memory -- is captured into a HIP
         graph and replayed.  For the reference's own small shapes (T = 30 crops, batch 4: ~90 launches of a few microseconds
-        each) the eager step is bound by launch overhead, not by the GPU."""
+        each) the eager step is bound by launch overhead, not by the GPU.
+
+        weight_decay / decoupled_weight_decay / amsgrad: torch.optim.Adam(weight_decay=, amsgrad=) or, decoupled,
+        torch.optim.AdamW.  max_grad_norm: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) between backward and the
+        step, computed on the device from the averaged gradient -- every rank reduces the same all-reduced buffer with
+        grad_scale = 1/world in the same fixed order, so all ranks get the same factor without another collective.  A
+        non-finite norm propagates as in torch (the step is not skipped).  With all four at their defaults the step launches
+        what it always did; any option switches to sed_grad_norm / sed_adam_step_ex."""
+        (self.weight_decay, self.decoupled_weight_decay, self.amsgrad, self.max_grad_norm,
+         self._opt_ext) = check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
         self.model = model
         self.engine = model.engine
         self.use_graph = bool(graph)
@@ -303,10 +340,18 @@ class FusedTrainer:
         self.flat = FlatParams(model, n_buckets)
         self.m = torch.zeros_like(self.flat.p)
         self.v = torch.zeros_like(self.flat.p)
-        self.vmax = torch.zeros_like(self.flat.p)
+        self.vmax = torch.zeros_like(self.flat.p) if self.amsgrad else None
         self.lr = float(lr)
         self.betas, self.eps = betas, eps
         self.recall_factor = float(recall_factor)
+        # clipping workspace, allocated once: fp64 partial sums, out = [norm, clip factor]; last_grad_norm is a view of out
+        self._gn_partial = self._gn_out = self._coef = self.last_grad_norm = None
+        if self.max_grad_norm is not None:
+            dev = self.flat.p.device
+            self._gn_partial = torch.zeros(L.lib().sed_grad_norm_nparts(self.flat.numel), dtype=torch.float64, device=dev)
+            self._gn_out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
+            self._coef = self._gn_out[1:2]
+            self.last_grad_norm = self._gn_out[0:1]     # device (1,), norm of the last step's averaged gradient; no sync
         self.step_count = 0
         self.reducer = GradAllReducer(self.flat.g, self.flat.buckets, group)
         self.sync_bn = bool(sync_bn) and self.reducer.enabled
@@ -329,7 +374,8 @@ class FusedTrainer:
             if not hasattr(self.engine, "adam_step_dev"):
                 raise RuntimeError("graph=True needs an engine with a device-scalar optimizer step (Cnn_AvgPooling / Crnn_AvgPooling)")
             dev = self.flat.p.device
-            self.hyper = torch.tensor([self.lr, 0.0, 0.0], dtype=torch.float32, device=dev)
+            # (the extended device step keeps this step's learning rate in a fourth slot, sed_hip.h)
+            self.hyper = torch.tensor([self.lr, 0.0, 0.0] + ([self.lr] if self._opt_ext else []), dtype=torch.float32, device=dev)
             self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def _check_alias(self):
@@ -353,16 +399,31 @@ class FusedTrainer:
     def optimizer_step(self):
         scale = self.reducer.finish()
         self.step_count += 1
-        self.engine.adam_step(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self.lr, self.step_count,
-                              grad_scale=scale, betas=self.betas, eps=self.eps)
+        if not self._opt_ext:
+            self.engine.adam_step(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self.lr, self.step_count,
+                                  grad_scale=scale, betas=self.betas, eps=self.eps)
+        else:
+            # after finish(): the norm is taken over the all-reduced buffer, the same bits on every rank
+            if self.max_grad_norm is not None:
+                self.engine.grad_norm(self.flat.g, self._gn_partial, self._gn_out, scale, self.max_grad_norm)
+            self.engine.adam_step_ex(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self.lr, self.step_count,
+                                     grad_scale=scale, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                                     decoupled=self.decoupled_weight_decay, coef=self._coef)
         if self.step_count % LR_DECAY_FREQ == 0:       # train.py:108-110 (after that iteration's step)
             self.lr *= LR_DECAY
 
     def _step_dev(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """forward + loss + backward + optimizer step with device-resident scalars: kernel launches only (capturable)."""
         loss = self.forward_backward(x, y)
-        self.engine.adam_step_dev(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self.hyper, self.step_dev, 1.0,
-                                  LR_DECAY, LR_DECAY_FREQ, betas=self.betas, eps=self.eps)
+        if not self._opt_ext:
+            self.engine.adam_step_dev(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self.hyper, self.step_dev, 1.0,
+                                      LR_DECAY, LR_DECAY_FREQ, betas=self.betas, eps=self.eps)
+            return loss
+        if self.max_grad_norm is not None:
+            self.engine.grad_norm(self.flat.g, self._gn_partial, self._gn_out, 1.0, self.max_grad_norm)
+        self.engine.adam_step_ex_dev(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self.hyper, self.step_dev, 1.0,
+                                     LR_DECAY, LR_DECAY_FREQ, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                                     decoupled=self.decoupled_weight_decay, coef=self._coef)
         return loss
 
     def _host_mirror(self):
@@ -412,7 +473,9 @@ class FusedTrainer:
     def state_dict(self):
         """torch.optim.Adam(amsgrad=True).state_dict() layout (what the reference saves under checkpoint['optimizer'],
         train.py:123-126): {'state': {i: {'step', 'exp_avg', 'exp_avg_sq', 'max_exp_avg_sq'}}, 'param_groups': [...]}, the
-        parameters numbered in model.parameters() order -- loadable into torch.optim.Adam and back into this trainer."""
+        parameters numbered in model.parameters() order -- loadable into torch.optim.Adam and back into this trainer.
+        The param group carries the trainer's weight_decay / amsgrad / decoupled_weight_decay (load a decoupled one into
+        torch.optim.AdamW); without amsgrad there is no 'max_exp_avg_sq'.  max_grad_norm is not optimizer state."""
         self._sync_host_scalars()
         state = {}
         for i, n in enumerate(self.flat.names):
@@ -420,20 +483,23 @@ class FusedTrainer:
             k = self.flat.P[n].numel()
             state[i] = {"step": torch.tensor(float(self.step_count)),
                         "exp_avg": self.m[o:o + k].view(shp).clone(),
-                        "exp_avg_sq": self.v[o:o + k].view(shp).clone(),
-                        "max_exp_avg_sq": self.vmax[o:o + k].view(shp).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": True,
+                        "exp_avg_sq": self.v[o:o + k].view(shp).clone()}
+            if self.amsgrad:
+                state[i]["max_exp_avg_sq"] = self.vmax[o:o + k].view(shp).clone()
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps,
+                 "weight_decay": self.weight_decay if self.weight_decay != 0.0 else 0, "amsgrad": self.amsgrad,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "decoupled_weight_decay": False, "params": list(range(len(self.flat.names)))}
+                 "decoupled_weight_decay": self.decoupled_weight_decay, "params": list(range(len(self.flat.names)))}
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
-        """Resume from state_dict() output or from a torch.optim.Adam(amsgrad=True) state_dict of the same model."""
+        """Resume from state_dict() output or from a torch.optim.Adam / AdamW state_dict of the same model whose amsgrad flag
+        is this trainer's.  lr, betas and eps come from the state; weight decay, its kind and max_grad_norm stay as the
+        trainer was built."""
         groups = sd["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != len(self.flat.names):
             raise ValueError("optimizer state does not match this model's parameter list")
-        if not groups[0].get("amsgrad", False):
-            raise ValueError("the fused optimizer is Adam with amsgrad=True (train.py:85)")
+        check_state_amsgrad(groups[0], self.amsgrad)
         self.lr = float(groups[0]["lr"])
         self.betas, self.eps = tuple(groups[0]["betas"]), float(groups[0]["eps"])
         step = 0
@@ -441,11 +507,14 @@ class FusedTrainer:
             o, k = self.flat.offsets[n], self.flat.P[n].numel()
             st = sd["state"].get(i)
             if st is None:
-                self.m[o:o + k].zero_(); self.v[o:o + k].zero_(); self.vmax[o:o + k].zero_()
+                self.m[o:o + k].zero_(); self.v[o:o + k].zero_()
+                if self.amsgrad:
+                    self.vmax[o:o + k].zero_()
                 continue
             self.m[o:o + k].copy_(st["exp_avg"].reshape(-1))
             self.v[o:o + k].copy_(st["exp_avg_sq"].reshape(-1))
-            self.vmax[o:o + k].copy_(st["max_exp_avg_sq"].reshape(-1))
+            if self.amsgrad:
+                self.vmax[o:o + k].copy_(st["max_exp_avg_sq"].reshape(-1))
             step = max(step, int(float(st["step"])))
         self.step_count = step
         if self.use_graph:
@@ -455,16 +524,25 @@ class FusedTrainer:
 
 class FusedAdamAmsgrad:
     """torch.optim-like facade over the fused kernel for code that calls loss.backward() itself
-    (gradients in p.grad): zero_grad() / step()."""
+    (gradients in p.grad): zero_grad() / step().  The four optimizer options are FusedTrainer's."""
 
-    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
+    def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False, amsgrad: bool = True, max_grad_norm: Optional[float] = None):
+        (self.weight_decay, self.decoupled_weight_decay, self.amsgrad, self.max_grad_norm,
+         self._opt_ext) = check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
         self.flat = FlatParams(model)
         self.model = model
         self.m = torch.zeros_like(self.flat.p)
         self.v = torch.zeros_like(self.flat.p)
-        self.vmax = torch.zeros_like(self.flat.p)
+        self.vmax = torch.zeros_like(self.flat.p) if self.amsgrad else None
         self.param_groups = [{"lr": float(lr)}]
         self.betas, self.eps, self.step_count = betas, eps, 0
+        self._gn_partial = self._gn_out = self._coef = self.last_grad_norm = None
+        if self.max_grad_norm is not None:
+            dev = self.flat.p.device
+            self._gn_partial = torch.zeros(L.lib().sed_grad_norm_nparts(self.flat.numel), dtype=torch.float64, device=dev)
+            self._gn_out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
+            self._coef, self.last_grad_norm = self._gn_out[1:2], self._gn_out[0:1]
 
     def zero_grad(self):
         for p in self.model.parameters():
@@ -476,6 +554,18 @@ class FusedAdamAmsgrad:
             if p.grad is not None:
                 self.flat.G[n].copy_(p.grad)
         self.step_count += 1
+        if self._opt_ext:
+            st = torch.cuda.current_stream().cuda_stream
+            if self.max_grad_norm is not None:
+                L.check(L.lib().sed_grad_norm(L.ptr(self.flat.g), self.flat.numel, 1.0, self.max_grad_norm,
+                                              L.ptr(self._gn_partial), self._gn_partial.numel(), L.ptr(self._gn_out), st),
+                        "grad_norm")
+            L.check(L.lib().sed_adam_step_ex(L.ptr(self.flat.p), L.ptr(self.flat.g), L.ptr(self.m), L.ptr(self.v),
+                                             L.ptr(self.vmax), self.flat.numel, float(self.param_groups[0]["lr"]),
+                                             float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_count, 1.0,
+                                             self.weight_decay, int(self.decoupled_weight_decay), L.ptr(self._coef), st),
+                    "adam_step_ex")
+            return
         L.check(L.lib().sed_adam_amsgrad_step(L.ptr(self.flat.p), L.ptr(self.flat.g), L.ptr(self.m), L.ptr(self.v),
                                               L.ptr(self.vmax), self.flat.numel, float(self.param_groups[0]["lr"]),
                                               float(self.betas[0]), float(self.betas[1]), float(self.eps),
@@ -517,9 +607,12 @@ def summarize_validation(val_losses, recal_sets, precision_sets, APs):
             "max_f5": float(np.max(f_score(p, r, precision_importance_factor=5)))}
 
 
-def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, device):
+def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, device, *, weight_decay=0.0,
+          decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None):
     """train.py:77-131.  `criterion` must be this package's WeightedBCE(multi_frame=True) (its
-    recall_factor feeds the fused loss kernel)."""
+    recall_factor feeds the fused loss kernel).  The keyword-only optimizer options are FusedTrainer's (this build only; their
+    defaults are the reference's Adam(amsgrad=True) without decay or clipping)."""
+    check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("the MI355X training path needs device='cuda' (there is no CPU path)")
@@ -536,7 +629,8 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
     if bool(criterion.multi_frame) != wants_multi:
         raise ValueError(f"{type(model).__name__} trains with WeightedBCE(multi_frame={wants_multi}) (main.py:44,71)")
     trainer = FusedTrainer(model, lr, recall_factor=criterion.recall_factor,
-                           sync_bn=os.environ.get("SED_SYNC_BN", "0") == "1")
+                           sync_bn=os.environ.get("SED_SYNC_BN", "0") == "1", weight_decay=weight_decay,
+                           decoupled_weight_decay=decoupled_weight_decay, amsgrad=amsgrad, max_grad_norm=max_grad_norm)
     rank0 = (not trainer.reducer.enabled) or trainer.reducer.dist.get_rank() == 0
     log_path = os.path.join(outputs_dir, "progress.jsonl")
     losses: List[float] = []
