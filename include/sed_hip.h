@@ -362,6 +362,26 @@ int sed_logmel_crops(const float* bank, size_t bank_frames, const int* starts_ho
                      const int* starts, const float* mean, const float* std, float* out, int B,
                      int crop, int n_mels, void* stream);
 
+/* ---- audio ingest: PCM decode + channel downmix + polyphase resampling (csrc/sed_resample.hip) ----
+ * read_multichannel_audio (dataset/dataset_utils.py:65-91): what the reference does with soundfile's float64 decode, the channel
+ * rule of :72-83 and librosa.resample, with scipy.signal.resample_poly(x, up, down)'s defaults (zero extension, Kaiser beta = 5)
+ * as the resampler (the documented deviation of this build's dataset_utils.py):
+ *   y[m] = sum_k h[m*down + half - k*up] * x[k],  m = 0 .. ceil(n_in*up/down) - 1,  half = 10*max(up, down),
+ *   h = up * firwin(2*half + 1, 1/max(up, down), window = ('kaiser', 5.0)); terms with an index outside h or x are absent.
+ * pcm [B][n_in][ch_in] interleaved frames of `pcm_dtype`: int16 (scaled by 2^-15), int32 (2^-31) or float32 (as is).
+ * out fp32 [B][ch_out][n_out].  Channel map: ch_out == 1 the mean over ch_in; ch_in < ch_out the mean, duplicated; ch_in > ch_out > 1
+ * the first ch_out channels; equal counts the identity.  Integer sums are exact and the scaling and division run in fp64 before the
+ * one rounding to fp32: with up == down == 1 (decode + downmix alone, taps may be NULL) integer PCM gives float32(host path) bit for bit.
+ * taps fp32 [up][Tp], designed by the caller in float64: taps[p][i] = (float)h[p + i*up], 0 where p + i*up > 2*half, with
+ * Tp = *h_phase_len of sed_resample_plan (20*max(up, down)/up + 1, made odd).  fp32 fmaf accumulation.
+ * up, down coprime in 1..640 (every pair among 8, 11.025, 16, 22.05, 24, 32, 44.1, 48 and 96 kHz except 11.025 kHz against 32 or
+ * 96 kHz, which reduce to 1280/441 and 1280/147); n_out must be ceil(n_in*up/down); B <= 65535; 1..64 channels.
+ * sed_resample_plan: host-only, no launch; *h_tile = outputs per workgroup (either pointer may be NULL).                        */
+enum { SED_PCM_I16 = 0, SED_PCM_I32 = 1, SED_PCM_F32 = 2 };
+int sed_resample_plan(int up, int down, int* h_phase_len, int* h_tile);
+int sed_resample_poly(int pcm_dtype, const void* pcm, const float* taps, float* out, int B, int n_in, int n_out, int ch_in,
+                      int ch_out, int up, int down, void* stream);
+
 /* ---- CRNN head: mean over mel -> bidirectional GRU -> Linear (BASELINE.json configs[3]) -------
  * Not in the reference repository; semantics are torch.nn.GRU's
  * (batch_first, bidirectional, gate order r,z,n; h' = (1-z) n + z h).  The FC on the GRU output

@@ -9,6 +9,7 @@ SED_F32, SED_BF16, SED_F32X3, SED_F32H3 = 0, 1, 2, 3
 PRO_NONE, PRO_BNRELU = 0, 1
 EPI_STORE, EPI_STATS, EPI_RELUBWD, EPI_POOLSTATS = 0, 1, 2, 4
 DZ_POOL, DZ_BN = 1, 2
+PCM_I16, PCM_I32, PCM_F32 = 0, 1, 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsed_hip.so")
@@ -112,6 +113,8 @@ PROTOTYPES = {
     "sed_complex_augment_logmel": (_I, [_P, _Z, _P, _P, _P, _P, _P, _P, C.c_ulonglong, _P, _P, _P, _P, _P, _P, _I, _I,
                                         _I, _I, _P]),
     "sed_logmel_crops": (_I, [_P, _Z, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "sed_resample_plan": (_I, [_I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sed_resample_poly": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sed_mel_mean_fwd": (_I, [_I, _P, _P, _Z, _I, _I, _I, _P]),
     "sed_mel_mean_bwd": (_I, [_I, _P, _P, _Z, _I, _I, _I, _P]),
     "sed_gemm_nt_ws_floats": (_Z, [_I, _I, _I]),

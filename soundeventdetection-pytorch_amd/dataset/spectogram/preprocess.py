@@ -60,9 +60,12 @@ def padded_window(cfg: SpectogramConfig) -> np.ndarray:
 
 
 class LogMelFrontEnd:
-    """GPU front-end for one parameter set.  wave (B, samples) float32 -> (B, 1, T, mel) float32."""
+    """GPU front-end for one parameter set.  wave (B, samples) float32 -> (B, 1, T, mel) float32.
 
-    def __init__(self, cfg: SpectogramConfig = DEFAULT_CONFIG, device="cuda", mean=None, std=None):
+    source_rate: the waveforms handed to __call__ / stft are at that sample rate; they are resampled to cfg.working_sample_rate on
+    the device (dataset_utils.AudioIngest, into its cached buffer) in front of the launch, and T follows the resampled length."""
+
+    def __init__(self, cfg: SpectogramConfig = DEFAULT_CONFIG, device="cuda", mean=None, std=None, source_rate=None):
         self.cfg = cfg
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -81,6 +84,13 @@ class LogMelFrontEnd:
         self.std = None if std is None else torch.as_tensor(std, dtype=torch.float32).to(dev).contiguous()
         self.ws = torch.empty(max(1, L.lib().sed_logmel_ws_bytes(1, 1, cfg.NFFT, cfg.hop_size) // 4),
                               dtype=torch.float32, device=dev)
+        self.source_rate = self._ingest = None
+        if source_rate is not None and int(source_rate) != cfg.working_sample_rate:
+            from ..dataset_utils import AudioIngest, resample_ratio
+            self.source_rate = int(source_rate)
+            self._ratio = resample_ratio(self.source_rate, cfg.working_sample_rate)
+            self._ingest = AudioIngest(dev, 1)
+            self._ingest.taps(*self._ratio)             # range errors surface here, not in the first step
 
     def _wave(self, wave) -> torch.Tensor:
         w = torch.as_tensor(wave)
@@ -88,8 +98,20 @@ class LogMelFrontEnd:
             raise ValueError("expected (B, samples)")
         return w.to(self.device, dtype=torch.float32).contiguous()
 
+    def _at_working_rate(self, w: torch.Tensor) -> torch.Tensor:
+        if self._ingest is None:
+            return w
+        return self._ingest(w.unsqueeze(-1), self.source_rate, self.cfg.working_sample_rate).view(w.shape[0], -1)
+
+    def num_frames(self, samples: int) -> int:
+        """frames of a waveform of `samples` samples as handed to __call__ (at source_rate when that is set)"""
+        if self._ingest is not None:
+            from ..dataset_utils import resampled_length
+            samples = resampled_length(samples, *self._ratio)
+        return self.cfg.num_frames(samples)
+
     def __call__(self, wave, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        w = self._wave(wave)
+        w = self._at_working_rate(self._wave(wave))
         B, n = w.shape
         T = self.cfg.num_frames(n)
         if out is None:
@@ -101,7 +123,7 @@ class LogMelFrontEnd:
         return out
 
     def stft(self, wave) -> torch.Tensor:
-        w = self._wave(wave)
+        w = self._at_working_rate(self._wave(wave))
         B, n = w.shape
         T = self.cfg.num_frames(n)
         spec = torch.empty((B, T, self.cfg.bins), dtype=torch.complex64, device=self.device)
@@ -156,7 +178,7 @@ class PrefetchingFrontEnd:
             raise RuntimeError("PrefetchingFrontEnd: every buffer is in flight (get/release one first)")
         k = self.head
         w = self.fe._wave(wave)
-        T = self.fe.cfg.num_frames(w.shape[1])
+        T = self.fe.num_frames(w.shape[1])
         shape = (w.shape[0], 1, T, self.fe.cfg.mel_bins)
         if self.buf[k] is None or tuple(self.buf[k].shape) != shape:
             self.buf[k] = torch.empty(shape, dtype=torch.float32, device=self.fe.device)
@@ -221,9 +243,10 @@ def calculate_scalar_of_tensor(x):
 
 
 def preprocess_data(audio_path_and_labels, output_dir, output_mean_std_file, preprocess_mode="logMel",
-                    cfg: SpectogramConfig = DEFAULT_CONFIG):
+                    cfg: SpectogramConfig = DEFAULT_CONFIG, host_resample=False):
     """preprocess.py:60-88 minus the debug plot: per recording STFT (+ log-mel) on the MI355X, the
-    reference's pickle layout on disk, then the dataset-wide mean / std."""
+    reference's pickle layout on disk, then the dataset-wide mean / std.  Channel downmix and resampling run on the
+    device too (dataset_utils.AudioIngest); host_resample=True takes the float64 scipy path instead."""
     import os
     import pickle
     from ..dataset_utils import read_multichannel_audio
@@ -231,8 +254,11 @@ def preprocess_data(audio_path_and_labels, output_dir, output_mean_std_file, pre
     os.makedirs(output_dir, exist_ok=True)
     all_features = []
     for (audio_path, start_times, end_times, audio_name) in audio_path_and_labels:
-        wave = read_multichannel_audio(audio_path=audio_path, target_fs=cfg.working_sample_rate, cfg=cfg)
-        feature = fe.stft(np.ascontiguousarray(wave.T))                    # (ch, T, bins) complex64, device
+        if host_resample:
+            wave = np.ascontiguousarray(read_multichannel_audio(audio_path, cfg.working_sample_rate, cfg).T)
+        else:
+            wave = read_multichannel_audio(audio_path, cfg.working_sample_rate, cfg, device=fe.device)     # (ch, samples), device
+        feature = fe.stft(wave)                                            # (ch, T, bins) complex64, device
         if preprocess_mode == "logMel":
             feature = fe.complex_to_log_mel(feature)
         feature = feature.cpu().numpy()

@@ -271,7 +271,7 @@ def _processed_dirs(root, descriptor, mode, suffix=""):
 
 
 def preprocess_tau_sed_data(data_dir, preprocess_mode, force_preprocess=False, fold_name="eval",
-                            cfg: SpectogramConfig = REF_NATIVE, labels=("doorslam",)):
+                            cfg: SpectogramConfig = REF_NATIVE, labels=("doorslam",), host_resample=False):
     """(:218-239) without the download step (no network on either box): expects the extracted
     TAU-SED-2019 tree under data_dir/Tau_sound_events_2019 and (re)builds the feature pickles."""
     from ..dataset_utils import get_tau_sed_paths_and_labels, tau_audio_and_meta_dirs
@@ -282,14 +282,14 @@ def preprocess_tau_sed_data(data_dir, preprocess_mode, force_preprocess=False, f
     if not os.path.exists(feats_dir) or force_preprocess:
         audio_dir, meta_dir = tau_audio_and_meta_dirs(root, fold_name)
         preprocess_data(get_tau_sed_paths_and_labels(audio_dir, meta_dir, labels), output_dir=feats_dir,
-                        output_mean_std_file=mean_std, preprocess_mode=preprocess_mode, cfg=cfg)
+                        output_mean_std_file=mean_std, preprocess_mode=preprocess_mode, cfg=cfg, host_resample=host_resample)
     else:
         print("Using existing mel features")
     return feats_dir, mean_std
 
 
 def preprocess_film_clap_data(data_dir, preprocessed_mode, force_preprocess=False, cfg: SpectogramConfig = REF_NATIVE,
-                              time_margin=0.33):
+                              time_margin=0.33, host_resample=False):
     """(:242-265)"""
     from ..dataset_utils import get_film_clap_paths_and_labels
     from .preprocess import preprocess_data
@@ -301,7 +301,7 @@ def preprocess_film_clap_data(data_dir, preprocessed_mode, force_preprocess=Fals
     if not os.path.exists(feats_dir) or force_preprocess:
         print("preprocessing raw data")
         preprocess_data(get_film_clap_paths_and_labels(film_clap_dir, time_margin=time_margin), output_dir=feats_dir,
-                        output_mean_std_file=mean_std, preprocess_mode=preprocessed_mode, cfg=cfg)
+                        output_mean_std_file=mean_std, preprocess_mode=preprocessed_mode, cfg=cfg, host_resample=host_resample)
     else:
         print("Using existing mel features")
     return feats_dir, mean_std

@@ -56,8 +56,10 @@ def split_train_val(tuples, val_descriptor):
 
 class WaveformDataset:
     def __init__(self, audio_paths_labels_and_names, val_descriptor=0.15, balance_classes=False, augment_data=False,
-                 waveforms=None, device=None):
-        """`waveforms`: optional {audio_path_or_key: (channels, samples) array} replacing file reads."""
+                 waveforms=None, device=None, host_resample=False):
+        """`waveforms`: optional {audio_path_or_key: (channels, samples) array} replacing file reads.  Files are downmixed and
+        resampled on the MI355X (`device`, default the current one; float32 values, kept as float64 on the host like before);
+        host_resample=True takes the float64 scipy path instead."""
         self.balance_classes, self.augment_data = balance_classes, augment_data
         self.device = torch.device(device) if device is not None else None
         print("WaveformDataset:")
@@ -67,7 +69,10 @@ class WaveformDataset:
             if waveforms is not None:
                 return np.asarray(waveforms[path], dtype=np.float64)
             from ..dataset_utils import read_multichannel_audio
-            return read_multichannel_audio(path, target_fs=cfg.working_sample_rate).T
+            if host_resample:
+                return read_multichannel_audio(path, target_fs=cfg.working_sample_rate).T
+            dev = self.device if self.device is not None else torch.device("cuda")
+            return read_multichannel_audio(path, target_fs=cfg.working_sample_rate, device=dev).cpu().numpy().astype(np.float64)
 
         long_waveform, labels, starts = [], [], []
         frame_index = 0

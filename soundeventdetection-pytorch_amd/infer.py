@@ -31,6 +31,10 @@ def build_parser():
     p.add_argument("--saliency", action="store_true",
                    help="also write 'saliency' (T, mel_bins, classes): d(sum_t p_k(t)) / d(input) of the first channel per class k, "
                         "taken with respect to the model input (the z-scored log-mel)")
+    p.add_argument("--config", default="ref_native", choices=["ref_native", "bench"],
+                   help="front-end parameter set: the reference's 48 kHz constants or the 32 kHz bench set")
+    p.add_argument("--host_resample", action="store_true",
+                   help="downmix and resample on the host in float64 (scipy) instead of on the MI355X")
     return p
 
 
@@ -64,12 +68,16 @@ def saliency_maps(model, x):
     return out
 
 
-def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, precision="bf16", mel_bins=None, saliency=False):
+def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, precision="bf16", mel_bins=None, saliency=False,
+               host_resample=False, cfg=None):
+    """cfg: a SpectogramConfig (default REF_NATIVE).  The file's PCM is downmixed and resampled to cfg.working_sample_rate on the
+    device (dataset_utils.AudioIngest); host_resample=True takes the float64 scipy path instead."""
     import dataclasses
     from .dataset.dataset_utils import read_multichannel_audio
     from .dataset.spectogram.preprocess import LogMelFrontEnd
-    from .dataset.spectogram.spectogram_configs import REF_NATIVE as cfg
+    from .dataset.spectogram.spectogram_configs import REF_NATIVE
     from .models.spectogram_models import Cnn_AvgPooling
+    cfg = REF_NATIVE if cfg is None else cfg
     n_mel = cfg.mel_bins if mel_bins is None else int(mel_bins)
     cfg = dataclasses.replace(cfg, mel_bins=n_mel)
     mean = std = None
@@ -84,9 +92,12 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     model.load_state_dict(checkpoint["model"] if "model" in checkpoint else checkpoint)
     model.eval()
     print("Preprocessing audio file..")
-    audio = read_multichannel_audio(audio_path=audio_file, target_fs=cfg.working_sample_rate, cfg=cfg)
+    if host_resample:
+        audio = np.ascontiguousarray(read_multichannel_audio(audio_file, cfg.working_sample_rate, cfg).T)
+    else:
+        audio = read_multichannel_audio(audio_file, cfg.working_sample_rate, cfg, device=dev)        # (channels, samples), device
     fe = LogMelFrontEnd(cfg, device=dev, mean=mean, std=std)
-    feats = fe(np.ascontiguousarray(audio.T))                     # (channels, 1, T, mel) = (batch, 1, T, mel)
+    feats = fe(audio)                                             # (channels, 1, T, mel) = (batch, 1, T, mel)
     print("Inference..")
     with torch.no_grad():
         logits = model(feats)                                       # (1, T', classes)
@@ -103,8 +114,10 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    from .dataset.spectogram import spectogram_configs
     res = infer_file(args.audio_file, args.ckpt, args.device, args.mean_std, args.threshold, args.precision, args.mel_bins,
-                     args.saliency)
+                     args.saliency, args.host_resample, {"ref_native": spectogram_configs.REF_NATIVE,
+                                                         "bench": spectogram_configs.BENCH}[args.config])
     os.makedirs(args.outputs_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(args.audio_file))[0]
     fps = res["frames_per_second"]
