@@ -477,6 +477,41 @@ int sed_metric_counts(const float* output, const float* target, float* prob_out,
                       unsigned long long* counts, double* gt_sum, void* workspace, size_t n_out,
                       size_t n_tgt, int K, void* stream);
 
+/* ---- event decoding (csrc/sed_events.hip) -----------------------------------------------------
+ * Between the frame probabilities and the event scores, without leaving the device.  Tensors are contiguous [B][T][K] (time in the
+ * middle, classes innermost).  Every output is a selection or an integer: the results are exact and the same from run to run.
+ *
+ * sed_median_time: out[b][t][k] = median of in[b][r(t + j)][k], j = -h .. h, win = 2h + 1 odd in 1..511 (1 copies), with the
+ * half-sample-symmetric reflection r(i): i mod 2T, then i if < T else 2T - 1 - i, applied as often as needed (win > T is legal):
+ * scipy.ndimage.median_filter(x, size=(1, win, 1), mode='reflect').  The result is one of the window's values bit for bit (the
+ * values are ordered as fp32 with -0 below +0; inputs are expected finite).  in == out is refused.  B <= 65535, T <= 2^30.
+ * sed_median_time_tile: host-only, the outputs per workgroup (no output depends on it).
+ *
+ * sed_decode_events: per (b, k) row, p[t] = prob[b][t][k] compared in fp32:
+ *   1. a candidate run is a maximal interval of p[t] > th_lo (strict); it is kept if one of its frames has p[t] > th_hi
+ *      (th_lo <= th_hi; equal: plain thresholding);
+ *   2. consecutive kept runs with at most max_gap (>= 0) frames between them merge, and merging chains;
+ *   3. a merged event [onset, offset) shorter than min_len (>= 1) frames is dropped -- merge first, then drop.
+ * decisions (nullable) uint8 [B][T][K]: 1 inside the surviving events (merged gaps filled), 0 elsewhere.  events int32
+ * [max_events][4] = (b, k, onset, offset), offset exclusive, in ascending (b, k, onset) order: rows are counted, the counts prefix-
+ * summed, and every row writes at its own offset.  row_counts int32 [B*K]; total int32 [1] = the true number of events: when it
+ * exceeds max_events exactly the first max_events are written (events may be NULL with max_events == 0).  A row has at most
+ * ceil(T/2) events; B*K*ceil(T/2) must stay below 2^31.  workspace: sed_decode_events_ws_bytes(B, T, K) bytes, 4-byte aligned
+ * (0 for a shape the call refuses).  sed_decode_events_chunk: host-only, the frames a wave takes per step (rows of any length work).
+ *
+ * sed_segment_counts: decisions uint8 [B][T][K], target fp32 [B][Tt][K]; n = min(T, Tt) frames are scored (the truncation of
+ * WeightedBCE and calculate_metrics).  Segment s = frames [s*seg_frames, min((s+1)*seg_frames, n)); it is active in the decisions
+ * if any frame is non-zero, in the target if any frame is > 0.5.  counts int64 [K][3] = (TP, FP, FN) over b and s.  K <= 65535.  */
+int sed_median_time_tile(void);
+int sed_median_time(const float* in, float* out, int B, int T, int K, int win, void* stream);
+int sed_decode_events_chunk(void);
+size_t sed_decode_events_ws_bytes(int B, int T, int K);
+int sed_decode_events(const float* prob, int B, int T, int K, float th_hi, float th_lo, int max_gap, int min_len,
+                      unsigned char* decisions, int* events, int max_events, int* row_counts, int* total, void* workspace,
+                      void* stream);
+int sed_segment_counts(const unsigned char* decisions, const float* target, int B, int T, int Tt, int K, int seg_frames,
+                       long long* counts, void* stream);
+
 /* First-layer weight gradient WITHOUT the layer's pre-BN output (z1 is never read):
  *   dW1[c][k] = ca[c]*A[c][k] + cb[c]*sum_j w1[c][j]*G[j][k] + cc[c]*sx[k],
  * A = plain sed_conv3x3_c1_wgrad of g (summed partials, [9][Coutp]); G / sx = Gram matrix and sums of the

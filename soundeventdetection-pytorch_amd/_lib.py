@@ -130,6 +130,12 @@ PROTOTYPES = {
     "sed_gru_seq_bwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "sed_metric_counts_ws_bytes": (_Z, [_I]),
     "sed_metric_counts": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _Z, _Z, _I, _P]),
+    "sed_median_time_tile": (_I, []),
+    "sed_median_time": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "sed_decode_events_chunk": (_I, []),
+    "sed_decode_events_ws_bytes": (_Z, [_I, _I, _I]),
+    "sed_decode_events": (_I, [_P, _I, _I, _I, _F, _F, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "sed_segment_counts": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "sed_m5_conv1_len": (_I, [_I]),
     "sed_m5_conv1_nparts": (_I, [_I, _I]),
     "sed_m5_conv1_fwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _P]),

@@ -4,7 +4,9 @@ in eval mode -> per-frame probabilities, threshold decisions and onset times.
 
     python -m sed_amd.infer recording.wav --ckpt training_dir/.../iteration_5000.pth
 
-Writes <outputs_dir>/<name>.npz (probabilities, decisions, onset_frames, onset_seconds; with --saliency also
+Writes <outputs_dir>/<name>.npz (probabilities, decisions, onset_frames, onset_seconds; with --median_window / --low_threshold / --max_gap /
+--min_event also events = (class, onset_s, offset_s) rows decoded on the MI355X (utils/event_utils.py) and event_frames, the same in frames;
+with --saliency also
 saliency (T, mel_bins, classes) = d(sum_t p_k(t)) / d(model input), the eval-mode input gradient) and prints the onsets.  The features are z-scored with --mean_std (the pickle the preprocessing wrote) when given:
 the reference's infer.py skips the normalisation the model was trained with."""
 from __future__ import annotations
@@ -35,7 +37,24 @@ def build_parser():
                    help="front-end parameter set: the reference's 48 kHz constants or the 32 kHz bench set")
     p.add_argument("--host_resample", action="store_true",
                    help="downmix and resample on the host in float64 (scipy) instead of on the MI355X")
+    p.add_argument("--median_window", type=float, default=0.0,
+                   help="median-filter the probabilities along time over this many seconds before deciding (nearest odd frame count; "
+                        "default 0 = off)")
+    p.add_argument("--low_threshold", type=float, default=None,
+                   help="hysteresis: an event starts where p > --threshold and extends over the frames with p > this lower value "
+                        "(default: --threshold, plain thresholding)")
+    p.add_argument("--max_gap", type=float, default=0.0, help="merge events at most this many seconds apart (default 0 = off)")
+    p.add_argument("--min_event", type=float, default=0.0, help="drop events shorter than this many seconds (default 0 = off)")
     return p
+
+
+def event_options(args, fps):
+    """The decode_events keyword arguments (in frames) of --median_window / --low_threshold / --max_gap / --min_event (seconds)."""
+    from .utils.event_utils import seconds_to_frames, seconds_to_window
+    return {"median_window": seconds_to_window(getattr(args, "median_window", 0.0), fps),
+            "low_threshold": getattr(args, "low_threshold", None),
+            "max_gap": seconds_to_frames(getattr(args, "max_gap", 0.0), fps),
+            "min_len": max(1, seconds_to_frames(getattr(args, "min_event", 0.0), fps))}
 
 
 def onset_frames(decisions):
@@ -69,9 +88,13 @@ def saliency_maps(model, x):
 
 
 def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, precision="bf16", mel_bins=None, saliency=False,
-               host_resample=False, cfg=None):
+               host_resample=False, cfg=None, median_window=1, low_threshold=None, max_gap=0, min_len=1):
     """cfg: a SpectogramConfig (default REF_NATIVE).  The file's PCM is downmixed and resampled to cfg.working_sample_rate on the
-    device (dataset_utils.AudioIngest); host_resample=True takes the float64 scipy path instead."""
+    device (dataset_utils.AudioIngest); host_resample=True takes the float64 scipy path instead.
+    median_window / max_gap / min_len (frames) and low_threshold are utils.event_utils.decode_events's: the result's 'events'
+    (n, 3) = (class, onset_s, offset_s) and 'event_frames' (n, 3) int are decoded on the device.  With all four at their defaults
+    they are the runs of probabilities > threshold, and 'decisions' / 'onset_frames' are what they always were; otherwise those two
+    follow the decoded events."""
     import dataclasses
     from .dataset.dataset_utils import read_multichannel_audio
     from .dataset.spectogram.preprocess import LogMelFrontEnd
@@ -101,11 +124,20 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     print("Inference..")
     with torch.no_grad():
         logits = model(feats)                                       # (1, T', classes)
-    probs = torch.sigmoid(logits)[0].cpu().numpy()
+    probs_dev = torch.sigmoid(logits)[0]
+    probs = probs_dev.cpu().numpy()
     dec = probs > threshold
+    from .utils.event_utils import decode_events
+    decoded = decode_events(probs_dev, threshold=threshold, low_threshold=low_threshold, median_window=median_window,
+                            max_gap=max_gap, min_len=min_len)
+    ev = decoded.numpy()[:, 1:].astype(np.int64)                    # (n, 3): class, onset, offset (exclusive), in frames
+    if (int(median_window), low_threshold, int(max_gap), int(min_len)) != (1, None, 0, 1):
+        dec = decoded.decisions.cpu().numpy().astype(bool)
     onsets = [onset_frames(dec[:, k]) for k in range(dec.shape[1])]
     res = {"probabilities": probs, "decisions": dec, "onset_frames": onsets,
-           "frames_per_second": cfg.frames_per_second, "log_mel": feats[0, 0].cpu().numpy()}
+           "frames_per_second": cfg.frames_per_second, "log_mel": feats[0, 0].cpu().numpy(), "event_frames": ev,
+           "events": np.stack([ev[:, 0].astype(np.float64), ev[:, 1] / cfg.frames_per_second, ev[:, 2] / cfg.frames_per_second],
+                              axis=1).reshape(-1, 3)}
     if saliency:
         print("Saliency..")
         res["saliency"] = saliency_maps(model, feats[:1])
@@ -115,18 +147,23 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
 def main(argv=None):
     args = build_parser().parse_args(argv)
     from .dataset.spectogram import spectogram_configs
+    cfg = {"ref_native": spectogram_configs.REF_NATIVE, "bench": spectogram_configs.BENCH}[args.config]
     res = infer_file(args.audio_file, args.ckpt, args.device, args.mean_std, args.threshold, args.precision, args.mel_bins,
-                     args.saliency, args.host_resample, {"ref_native": spectogram_configs.REF_NATIVE,
-                                                         "bench": spectogram_configs.BENCH}[args.config])
+                     args.saliency, args.host_resample, cfg, **event_options(args, cfg.frames_per_second))
     os.makedirs(args.outputs_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(args.audio_file))[0]
     fps = res["frames_per_second"]
     extra = {"saliency": res["saliency"]} if "saliency" in res else {}
+    if event_options(args, fps) != event_options(None, fps):        # an event flag was given: the file gains the event list
+        extra.update(events=res["events"], event_frames=res["event_frames"])
     np.savez(os.path.join(args.outputs_dir, name + ".npz"), probabilities=res["probabilities"],
              decisions=res["decisions"], onset_frames=np.concatenate(res["onset_frames"]) if res["onset_frames"] else [],
              onset_seconds=np.concatenate(res["onset_frames"]) / fps if res["onset_frames"] else [], **extra)
     for k, on in enumerate(res["onset_frames"]):
         print(f"class {k}: {len(on)} onsets at " + ", ".join(f"{f / fps:.2f}s" for f in on[:50]))
+    for k in range(res["decisions"].shape[1]):
+        rows = res["events"][res["events"][:, 0] == k]
+        print(f"class {k}: " + (", ".join(f"{a:.2f}-{b:.2f} s" for _, a, b in rows[:50]) if len(rows) else "no events"))
 
 
 if __name__ == "__main__":

@@ -64,6 +64,47 @@ def build_parser():
     return p
 
 
+def build_event_parser():
+    """The event-level evaluation options (this build only).  They live in a parser of their own -- build_parser() keeps exactly
+    the reference's flags plus the optimizer options -- and build_full_parser() joins the two for the command line."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--eval_events", action="store_true", default=False,
+                   help="this build only: the periodic evaluation also decodes events on the GPU and logs segment- and "
+                        "event-based scores")
+    p.add_argument("--median_window", type=float, default=0.0,
+                   help="--eval_events: median filter over this many seconds (nearest odd frame count; 0 = off)")
+    p.add_argument("--max_gap", type=float, default=0.0, help="--eval_events: merge events at most this many seconds apart")
+    p.add_argument("--min_event", type=float, default=0.0, help="--eval_events: drop events shorter than this many seconds")
+    p.add_argument("--segment", type=float, default=1.0, help="--eval_events: segment length in seconds of the segment-based scores")
+    p.add_argument("--collar", type=float, default=0.2, help="--eval_events: onset / offset collar in seconds of the event-based scores")
+    return p
+
+
+def build_full_parser():
+    """What main() parses: build_parser() and build_event_parser() together."""
+    return argparse.ArgumentParser(description="SED training on MI355X", parents=[build_parser(), build_event_parser()],
+                                   conflict_handler="resolve")
+
+
+def event_eval_options(args, fps):
+    """The eval_events keyword arguments (frames) of --eval_events and its parameters (seconds); None with the flag off."""
+    if not getattr(args, "eval_events", False):
+        return None
+    from .utils.event_utils import seconds_to_frames, seconds_to_window
+    return {"threshold": 0.5, "low_threshold": None, "median_window": seconds_to_window(args.median_window, fps),
+            "max_gap": seconds_to_frames(args.max_gap, fps), "min_len": max(1, seconds_to_frames(args.min_event, fps)),
+            "seg_frames": max(1, seconds_to_frames(args.segment, fps)), "collar_frames": seconds_to_frames(args.collar, fps)}
+
+
+def frames_per_second(args):
+    """Model output frames per second of the chosen feature type."""
+    if args.train_features.lower() == "spectogram":
+        from .dataset.spectogram import spectogram_configs as cfgs
+        return cfgs.REF_NATIVE.frames_per_second
+    from .dataset.waveform import waveform_configs
+    return waveform_configs.frames_per_second
+
+
 def _val_descriptor(v):
     """argparse hands a string for an explicit --val_descriptor; the reference's float default selects
     a percentage split: accept '0.2' as a float as well (main.py:102)."""
@@ -153,6 +194,11 @@ def validate_args(args):
         raise ValueError(f"--clip_grad_norm must be >= 0 (0 = off), {args.clip_grad_norm} given")
     from .train import check_optimizer_options
     check_optimizer_options(**optimizer_options(args))
+    for name in ("median_window", "max_gap", "min_event", "collar"):
+        if getattr(args, name, 0.0) < 0:
+            raise ValueError(f"--{name} must be >= 0 seconds, {getattr(args, name)} given")
+    if getattr(args, "segment", 1.0) <= 0:
+        raise ValueError(f"--segment must be > 0 seconds, {args.segment} given")
 
 
 def optimizer_options(args):
@@ -190,7 +236,7 @@ def make_loader(dataset, batch_size):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_full_parser().parse_args(argv)
     validate_args(args)
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X visible: this build has no CPU training path")
@@ -219,7 +265,7 @@ def main(argv=None):
         train_name += "_AD"
     train(model, dataloader, criterion, num_steps=args.num_train_steps,
           outputs_dir=os.path.join(args.outputs_root, train_name), device=device, lr=args.lr,
-          log_freq=args.log_freq, **optimizer_options(args))
+          log_freq=args.log_freq, event_eval=event_eval_options(args, frames_per_second(args)), **optimizer_options(args))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

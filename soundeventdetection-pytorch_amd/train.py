@@ -597,6 +597,52 @@ def eval(model, dataloader, criterion, outputs_dir, iteration, device, limit_val
     return losses, recal_sets, precision_sets, APs
 
 
+def eval_events(model, dataloader, device, *, threshold, low_threshold, median_window, max_gap, min_len, seg_frames,
+                collar_frames, limit_val_samples=None):
+    """Event-level validation (this build only): every recording of the validation sampler is run like eval() does, its
+    probabilities are decoded into events ON THE DEVICE (utils.event_utils.decode_events: median_window / max_gap / min_len /
+    seg_frames / collar_frames in frames, threshold / low_threshold on the probability), the reference events are the runs of the
+    target, and both are scored over the first min(frames) frames: segment-based counts on the device, summed there; event-based
+    (collar) matching on the host, for which each recording costs ONE device-to-host copy, of its two event lists.
+    Returns a dict of plain numbers (JSON-ready): segment_f1, segment_error_rate, event_f1 (micro averages), their per-class lists,
+    the counts behind them and the numbers of predicted / reference events."""
+    from .utils.event_utils import (decode_events, event_based_metrics, events_from_targets, events_to_host,
+                                    metrics_from_segment_counts, segment_counts_device)
+    val_sampler = dataloader.dataset.get_validation_sampler(max_validate_num=limit_val_samples)
+    seg_counts, pred_all, ref_all = None, [], []
+    for idx, (inp, target, file_name) in enumerate(val_sampler):
+        model.eval()
+        with torch.no_grad():
+            output = model(inp.to(device).float())
+        output = output[0] if inp.dim() == 4 else output
+        target = (target[0] if inp.dim() == 4 else target.reshape(-1, 1)).to(device).float()
+        n = min(output.shape[0], target.shape[0])
+        pred = decode_events(torch.sigmoid(output[:n]), threshold=threshold, low_threshold=low_threshold,
+                             median_window=median_window, max_gap=max_gap, min_len=min_len)
+        ref = events_from_targets(target[:n])
+        c = segment_counts_device(pred.decisions, target[:n], seg_frames)
+        seg_counts = c if seg_counts is None else seg_counts + c
+        pe, re_ = events_to_host(pred, ref)
+        pe[:, 0] = idx                       # (recording, class, onset, offset): events of different recordings never match
+        re_[:, 0] = idx
+        pred_all.append(pe)
+        ref_all.append(re_)
+    if seg_counts is None:
+        raise RuntimeError("the validation sampler produced no recording")
+    seg = metrics_from_segment_counts(seg_counts.cpu().numpy())
+    pred_all, ref_all = np.concatenate(pred_all), np.concatenate(ref_all)
+    evm = event_based_metrics(pred_all, ref_all, collar_frames)
+    return {"segment_f1": seg["micro"]["f1"], "segment_error_rate": seg["micro"]["error_rate"],
+            "segment_precision": seg["micro"]["precision"], "segment_recall": seg["micro"]["recall"],
+            "segment_f1_per_class": [c["f1"] for c in seg["per_class"]],
+            "segment_error_rate_per_class": [c["error_rate"] for c in seg["per_class"]],
+            "segment_counts": seg["counts"].tolist(),
+            "event_f1": evm["micro"]["f1"], "event_precision": evm["micro"]["precision"], "event_recall": evm["micro"]["recall"],
+            "event_f1_per_class": {int(k): v["f1"] for k, v in evm["per_class"].items()},
+            "event_counts": [evm["micro"]["tp"], evm["micro"]["fp"], evm["micro"]["fn"]],
+            "n_pred_events": int(len(pred_all)), "n_ref_events": int(len(ref_all))}
+
+
 def summarize_validation(val_losses, recal_sets, precision_sets, APs):
     """ProgressPlotter.report_validation_metrics (utils/common.py:46-56): F-scores of the
     validation-AVERAGED precision/recall curves, including the swapped-argument call convention."""
@@ -608,10 +654,11 @@ def summarize_validation(val_losses, recal_sets, precision_sets, APs):
 
 
 def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, device, *, weight_decay=0.0,
-          decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None):
+          decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None, event_eval=None):
     """train.py:77-131.  `criterion` must be this package's WeightedBCE(multi_frame=True) (its
     recall_factor feeds the fused loss kernel).  The keyword-only optimizer options are FusedTrainer's (this build only; their
-    defaults are the reference's Adam(amsgrad=True) without decay or clipping)."""
+    defaults are the reference's Adam(amsgrad=True) without decay or clipping).  event_eval: None, or the keyword arguments of
+    eval_events (threshold ... collar_frames): the periodic evaluation then also logs that dict; None launches nothing new."""
     check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -654,6 +701,8 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
                 if hasattr(data_loader.dataset, "get_validation_sampler"):
                     rec.update(summarize_validation(*eval(model, data_loader, criterion, outputs_dir,
                                                           iteration=iterations, device=dev, limit_val_samples=3)))
+                    if event_eval is not None:
+                        rec.update(eval_events(model, data_loader, dev, limit_val_samples=3, **event_eval))
                 if rank0:
                     print(f"epoch: {epoch}, step: {iterations}, loss: {host_losses[-1]:.2f}, "
                           f"im/sec: {im_sec:.1f}, lr: {trainer.lr:.8f}")
