@@ -662,7 +662,7 @@ int sed_bn_bwd_finalize_c1(const float* partial, int nparts, double count, const
                            const float* w1, const float* gamma, const float* mean, const float* invstd,
                            float* dgamma, float* dbeta, float* ca, float* cb, float* cc, int C, int Cp,
                            void* stream);
-/* ---- input gradient of the Cin = 1 first layer (csrc/sed_c1_dgrad.hip) ------------------------------------------------
+/* ---- input gradient of the Cin = 1 first layer (csrc/sed_c1_dx.hip) ------------------------------------------------
  * Replaces autograd through conv1 / BN1 of the first ConvBlock down to the model input (spectogram_models.py:153-160):
  *   dz1 = ca*g + cb*z + cc  (BN1 backward, inside the image only),   dx[b][h][w] = sum_{c, tap} w1[c][tap] * dz1[b][h - dh][w - dw][c].
  * g, z [B][H][W][Coutp] (dtype SED_BF16 or SED_F32 storage), w1 fp32 [Cout][1][3][3] torch layout, ca / cb / cc fp32 [Coutp],
@@ -672,7 +672,7 @@ int sed_bn_bwd_finalize_c1(const float* partial, int nparts, double count, const
 int sed_conv3x3_c1_dgrad(int dtype, const void* g, const void* z, const float* x, const float* fmean, const float* fstd,
                          const float* w1, const float* ca, const float* cb, const float* cc, float* dx, int B, int H, int W,
                          int Cout, int Coutp, void* stream);
-/* ---- eval-mode (running-statistics) BatchNorm backward -------------------------------------------------------------------
+/* ---- eval-mode (running-statistics) BatchNorm backward (csrc/sed_ops.hip; the C1 form: csrc/sed_c1_dx.hip) ---------------
  * Autograd through nn.BatchNorm2d in eval mode (spectogram_models.py:155-158 under model.eval()): BN is the fixed affine map
  * gamma*(z - mean_r)*invstd_r + beta.  sed_bn_eval_stats writes mean = running_mean, invstd = 1/sqrt(running_var + eps) (0 in
  * the padded channels): the (mean, invstd) operands the backward statistics kernels take (their partial rows then hold

@@ -52,6 +52,11 @@ static inline int sed_set_max_lds(size_t lds) {
     return 0;
 }
 
+// sed_ops.hip: the eval-mode BatchNorm backward finalizer; A, w given = its C1 form (sed_bn_eval_bwd_finalize_c1, sed_c1_dx.hip)
+void launch_bn_eval_bwd_finalize(const float* partial, int nparts, const float* A, const float* w, const float* gamma, const float* mean,
+                                 const float* invstd, float* dgamma, float* dbeta, float* ca, float* cb, float* cc, int C, int Cp,
+                                 hipStream_t st);
+
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 static inline size_t cdivz(size_t a, size_t b) { return (a + b - 1) / b; }
 

@@ -1,7 +1,12 @@
-// Device helpers shared by the convolution kernels (sed_conv.hip, sed_wgrad.hip): LDS swizzle, 16-byte raw
-// items, buffer-resource addressing, the tile-invariant halo staging plan and the transpose-read fragments.
+// Shared by the convolution translation units (sed_conv*.hip, sed_wgrad*.hip, sed_bwd_fused*.hip, sed_c1.hip, sed_dgrad_c1.hip) and by
+// the M5 / GRU kernels that reuse their device helpers.
+// Device helpers: LDS swizzle, 16-byte raw items, buffer-resource addressing, the tile-invariant halo staging plan, the
+// transpose-read fragments and the C1-mode recompute.  Host side: the parameter blocks and the launch_* / *_strips functions
+// through which the entry points (sed_conv.hip, sed_conv_wgrad.hip, sed_c1.hip) reach the kernels of the other files.
 #pragma once
 #include "common.h"
+
+#include <stdlib.h>
 
 // element-index XOR applied inside the 32-channel vector of LDS pixel column `col`
 template <typename T> __device__ __forceinline__ int swz(int col);
@@ -248,7 +253,7 @@ struct Wgrad2Params {
 
 
 // sed_wgrad.hip: producer/consumer weight-gradient kernel (bf16).  Returns -1 when the shape is not covered
-// (the caller then falls back to conv_wgrad2_kernel), otherwise 0 / an error code after the launch.
+// (the caller then falls back to conv_wgrad2_kernel, sed_conv_wgrad.hip), otherwise 0 / an error code after the launch.
 int wgrad3_strips(int B, int H, int W, int Cinp, int Coutp);     // 0 = shape not covered
 int launch_wgrad3(int dzmode, Wgrad2Params& p, int W, hipStream_t st);
 // sed_wgrad_wide.hip (round 5): the same contract for the wide layers (>= 128 channels on one side, >= 64 on the other; W = 8 / 16 / 32):
@@ -256,6 +261,12 @@ int launch_wgrad3(int dzmode, Wgrad2Params& p, int W, hipStream_t st);
 // it where it covers the shape (SED_WGRAD_WIDE=0: the A/B knob)
 int wgrad_wide_strips(int B, int H, int W, int Cinp, int Coutp);  // 0 = shape not covered
 int launch_wgrad_wide(int dzmode, Wgrad2Params& p, int W, hipStream_t st);
+// sed_conv_pack.hip: sums the `slabs` weight-gradient slabs of `ws` into dwpack (and dw, torch layout, when given) -- or, with
+// dwpack == NULL, launches nothing and leaves the count for sed_wgrad_last_slabs() (deferred reduction).  Always 0.
+int reduce_or_defer(const float* ws, float* dwpack, int slabs, size_t n, float* dw, int Cout, int Cin, int Cinp, int Coutp, hipStream_t st);
+
+// the line widths the specialised kernels are compiled for; every other width takes csrc/sed_conv_anyw.hip
+static inline bool sed_w_specialised(int W) { return W == 8 || W == 16 || W == 32 || W == 64; }
 
 // Run-time ablation switches (SED_DBG bits, wave priorities) exist only in ablation builds (make DEBUG_SWITCHES=1): an untaken
 // run-time branch per phase costs the step loops 5-15 %, so the product build compiles them out.
@@ -266,6 +277,8 @@ int launch_wgrad_wide(int dzmode, Wgrad2Params& p, int W, hipStream_t st);
 #define SED_DBG(p, bit) 0
 #define SED_SET_PRIO(x) ((void)0)
 #endif
+// the value the entry points copy into p.dbg (read in every build, tested by the kernels in ablation builds only)
+static inline int sed_dbg_env() { const char* d = sed_getenv("SED_DBG"); return d ? atoi(d) : 0; }
 
 // wave issue priority (s_setprio takes an immediate): the loader waves are dispatched after the MFMA waves, and with equal
 // priority the OLDER wave of a SIMD wins every arbitration (MI355X_MICROARCH.md, two waves per SIMD) -- the role that is the
@@ -348,7 +361,7 @@ int launch_conv_anyw(int dtype, ConvParams& p, int W, hipStream_t st);
 int launch_wgrad_anyw(int dtype, int dzmode, Wgrad2Params& p, int W, hipStream_t st);
 
 // sed_conv_pc.hip: bf16 forward / data gradient through the producer/consumer kernel; -1 = shape not covered
-// (the caller falls back to conv_igemm_kernel / conv_wreg_kernel), otherwise 0 / an error code after the launch.
+// (the caller falls back to conv_igemm_kernel / conv_wreg_kernel, sed_conv.hip), otherwise 0 / an error code after the launch.
 int launch_conv_pc(ConvParams& p, int W, hipStream_t st);
 // sed_conv_wir.hip: bf16 forward / data gradient with the weights resident in registers (>= 64 input channels, W <= 32);
 // -1 = shape not covered

@@ -17,6 +17,7 @@
 //     contraction), gates it and contracts it against the patch fragments: 36 + 4 MFMAs,
 //   * rebuilds one row of the NEXT stage's activation tile relu(bn1(conv1(x))): 2 MFMAs + their tails.
 // Nothing is stored per tile; the workgroup writes its weight-gradient slab and its [A; sum g] partial once at the end.
+// The entry point sed_conv3x3_bwd_fused_c1, with the slab reduction that follows the launch, is in csrc/sed_c1.hip.
 #include "conv_common.h"
 
 #include <stdlib.h>

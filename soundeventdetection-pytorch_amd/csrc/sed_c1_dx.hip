@@ -1,4 +1,4 @@
-// Input gradient of the Cin = 1 first layer and the eval-mode (running-statistics) BatchNorm backward.
+// Input gradient of the Cin = 1 first layer, and the C1 form of the eval-mode (running-statistics) BatchNorm backward.
 //
 // Reference: autograd through the first ConvBlock, models/spectogram_models.py:153-160 of the reference:
 //   dz1 = ca*g1 + cb*z1 + cc                     (BN1 backward; g1 = gradient at BN1's output)
@@ -8,8 +8,6 @@
 // shift-add of those partials.  z1 is read, or recomputed from the z-scored input (C1 mode keeps no z1 in memory).  Outside the image
 // dz1 = 0: cc never leaks into the zero padding.
 #include "common.h"
-
-#include <algorithm>
 
 namespace {
 
@@ -98,77 +96,7 @@ __global__ __launch_bounds__(DX_NT) void c1_dgrad_kernel(const T* __restrict__ g
     }
 }
 
-// eval-mode BatchNorm: the running statistics as (mean, invstd), the way sed_bn_eval_coeffs derives its scale
-__global__ void bn_eval_stats_kernel(const float* rmean, const float* rvar, float eps, float* mean, float* invstd, int C, int Cp) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= Cp) return;
-    if (c >= C) { mean[c] = 0.f; invstd[c] = 0.f; return; }
-    mean[c] = rmean[c];
-    invstd[c] = 1.0f / sqrtf(rvar[c] + eps);
-}
-
-// eval-mode BatchNorm backward: partial [nparts][2][Cp] = (sum g, sum g*xhat) with xhat taken with the running statistics
-// (sed_bn_eval_stats).  dbeta = sum g, dgamma = sum g*xhat, dz = gamma*invstd*g: ca = gamma*invstd, cb = cc = 0.
-// C1 form (A != NULL): row 1 is not read; sum g*z1 = w1 . A, sum g*xhat = invstd*(w1 . A - mean*sum g).
-__global__ __launch_bounds__(256) void bn_eval_bwd_finalize_kernel(const float* __restrict__ partial, int nparts,
-                                                                   const float* __restrict__ A, const float* __restrict__ w,
-                                                                   const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                                   const float* __restrict__ invstd, float* __restrict__ dgamma,
-                                                                   float* __restrict__ dbeta, float* __restrict__ ca,
-                                                                   float* __restrict__ cb, float* __restrict__ cc, int C, int Cp) {
-    __shared__ double sm[2][256];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    double s = 0.0, q = 0.0;
-    for (int i = tid; i < nparts; i += 256) {
-        s += (double)partial[((size_t)i * 2 + 0) * Cp + c];
-        if (!A) q += (double)partial[((size_t)i * 2 + 1) * Cp + c];
-    }
-    sm[0][tid] = s;
-    sm[1][tid] = q;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) { sm[0][tid] += sm[0][tid + o]; sm[1][tid] += sm[1][tid + o]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (c >= C) { ca[c] = 0.f; cb[c] = 0.f; cc[c] = 0.f; return; }
-        const double sg = sm[0][0], is = invstd[c];
-        double sgx = sm[1][0];
-        if (A) {
-            double sgz = 0.0;
-            for (int k = 0; k < 9; ++k) sgz += (double)w[c * 9 + k] * (double)A[k * Cp + c];
-            sgx = is * (sgz - (double)mean[c] * sg);
-        }
-        dbeta[c] = (float)sg;
-        dgamma[c] = (float)sgx;
-        ca[c] = (float)((double)gamma[c] * is);
-        cb[c] = 0.f;
-        cc[c] = 0.f;
-    }
-}
-
-// |x| max as the bits of a non-negative float (their integer order is the float order): one atomic per workgroup
-__global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x, size_t n, unsigned* __restrict__ out) {
-    __shared__ unsigned sm[4];
-    unsigned m = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = max(m, __float_as_uint(fabsf(x[i])));
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(out, max(max(sm[0], sm[1]), max(sm[2], sm[3])));
-}
-
 }  // namespace
-
-extern "C" int sed_absmax(const float* x, size_t n, float* out, void* stream) {
-    SED_REQUIRE(x && out && n > 0, "operands");
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, sizeof(float), st) != hipSuccess) { sed_set_error("sed_absmax: memset failed"); return 2; }
-    const int blocks = (int)std::min<size_t>(1024, cdivz(n, 256 * 8));
-    absmax_kernel<<<blocks, 256, 0, st>>>(x, n, reinterpret_cast<unsigned*>(out));
-    SED_LAUNCH_CHECK();
-    return 0;
-}
 
 extern "C" int sed_conv3x3_c1_dgrad(int dtype, const void* g, const void* z, const float* x, const float* fmean, const float* fstd,
                                     const float* w1, const float* ca, const float* cb, const float* cc, float* dx, int B, int H, int W,
@@ -198,29 +126,11 @@ extern "C" int sed_conv3x3_c1_dgrad(int dtype, const void* g, const void* z, con
     return 0;
 }
 
-extern "C" int sed_bn_eval_stats(const float* running_mean, const float* running_var, float eps, float* mean, float* invstd, int C,
-                                 int Cp, void* stream) {
-    SED_REQUIRE(running_mean && running_var && mean && invstd && C > 0 && C <= Cp, "operands");
-    bn_eval_stats_kernel<<<cdiv(Cp, 256), 256, 0, (hipStream_t)stream>>>(running_mean, running_var, eps, mean, invstd, C, Cp);
-    SED_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sed_bn_eval_bwd_finalize(const float* partial, int nparts, const float* gamma, const float* mean, const float* invstd,
-                                        float* dgamma, float* dbeta, float* ca, float* cb, float* cc, int C, int Cp, void* stream) {
-    SED_REQUIRE(partial && nparts > 0 && C > 0 && C <= Cp, "operands");
-    bn_eval_bwd_finalize_kernel<<<Cp, 256, 0, (hipStream_t)stream>>>(partial, nparts, nullptr, nullptr, gamma, mean, invstd, dgamma,
-                                                                     dbeta, ca, cb, cc, C, Cp);
-    SED_LAUNCH_CHECK();
-    return 0;
-}
-
 extern "C" int sed_bn_eval_bwd_finalize_c1(const float* partial, int nparts, const float* a_sum, const float* w1, const float* gamma,
                                            const float* mean, const float* invstd, float* dgamma, float* dbeta, float* ca, float* cb,
                                            float* cc, int C, int Cp, void* stream) {
     SED_REQUIRE(partial && nparts > 0 && a_sum && w1 && C > 0 && C <= Cp, "operands");
-    bn_eval_bwd_finalize_kernel<<<Cp, 256, 0, (hipStream_t)stream>>>(partial, nparts, a_sum, w1, gamma, mean, invstd, dgamma, dbeta,
-                                                                     ca, cb, cc, C, Cp);
+    launch_bn_eval_bwd_finalize(partial, nparts, a_sum, w1, gamma, mean, invstd, dgamma, dbeta, ca, cb, cc, C, Cp, (hipStream_t)stream);
     SED_LAUNCH_CHECK();
     return 0;
 }

@@ -1,5 +1,5 @@
 // Width-general 3x3 convolution kernels: any line width 1 <= W <= 256, chosen at run time (the mel-bin count of the input is a
-// model setting; the specialised kernels of sed_conv.hip / sed_conv_pc.hip / sed_wgrad*.hip are compiled for W = 8 / 16 / 32 / 64).
+// model setting; the specialised kernels of sed_conv.hip / sed_conv_wgrad.hip / sed_conv_pc.hip / sed_wgrad*.hip are compiled for W = 8 / 16 / 32 / 64).
 //
 // forward / data gradient (the contract of sed_conv3x3_fwd): implicit GEMM, D[cout][pixel] = W[cout][k] * X[k][pixel] with
 //   k = (tap, 32-channel chunk).  A tile is TH = max(1, 256 / W) whole image rows; its TH*W pixels are padded to 256 MFMA rows
@@ -12,7 +12,7 @@
 //   The reduction index runs over the tile's pixels in the halo's row pitch (W + 2): pixel (row, col) is k = row*(W+2) + col, and
 //   tap (ti, tj) reads halo pixel k + ti*(W+2) + tj -- a uniform shift for every lane.  dz is zero at the two pitch columns
 //   col >= W and at rows past the image, so those k contribute nothing.  Both operands are [pixel][channel] in LDS; bf16 fragments
-//   come from ds_read_b64_tr_b16 as in conv_wgrad2_kernel, whose wave layout (tap row x 32-cout slab) and per-strip fp32 slabs
+//   come from ds_read_b64_tr_b16 as in conv_wgrad2_kernel (sed_conv_wgrad.hip), whose wave layout (tap row x 32-cout slab) and per-strip fp32 slabs
 //   [strips][9][Cinp][Coutp] this kernel keeps, so the reduction (inline or deferred) is the existing one.
 // Storage types: bf16 (v_mfma_f32_32x32x16_bf16) and fp32 (v_mfma_f32_32x32x2f32, exact products as the other fp32 kernels); both
 // accumulate in fp32.

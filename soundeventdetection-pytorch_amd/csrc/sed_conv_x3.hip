@@ -25,7 +25,7 @@
 //                    16-bit images; BatchNorm+ReLU prologue in fp32 BEFORE the split; the epilogue (conv_igemm_kernel's, sed_conv.hip)
 //                    stages the fp32 results in LDS and writes whole lines one stage later; BatchNorm statistics / the ReLU-backward
 //                    gate and sums run in that pass on a thread's fixed 8 channels.
-//   wgrad_x3_kernel  weight gradient with dz produced on load (DZ_POOL / DZ_BN / given): conv_wgrad2_kernel's structure with both
+//   wgrad_x3_kernel  weight gradient with dz produced on load (DZ_POOL / DZ_BN / given): conv_wgrad2_kernel's (sed_conv_wgrad.hip) structure with both
 //                    operands as hi / lo planes read through ds_read_b64_tr_b16.
 // The operator images come from sed_pack_conv_weight(s_batch) with the same dtype: [hi image][lo image], each in the bf16 layout.
 #include "x3_common.h"

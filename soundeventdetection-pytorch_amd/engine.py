@@ -761,7 +761,7 @@ class CnnEngine(OptimizerExtMixin):
         """Backward of the last forward on plan p.  Gradient source: `dlogits`
         (B, t*ratio, K) w.r.t. the interpolated logits, or plan.dpre when None.  Writes fp32 gradients
         into G[name] (tensors shaped like the parameters; overwritten, not accumulated).
-        need_dx: also the input gradient of the Cin = 1 model path into plan.dx_in (B, 1, T, F) fp32 (csrc/sed_c1_dgrad.hip; the
+        need_dx: also the input gradient of the Cin = 1 model path into plan.dx_in (B, 1, T, F) fp32 (csrc/sed_c1_dx.hip; the
         generic_first path always fills plan.dx).  An eval-mode forward (BatchNorm with running statistics) can be differentiated
         when it ran with keep_for_grad=True; so must a C1-mode training forward whose backward takes need_dx.  Without need_dx, a
         training-mode backward launches exactly what it did before these two kinds existed."""
@@ -1010,7 +1010,7 @@ class CnnEngine(OptimizerExtMixin):
                             L.ptr(cc), L.ptr(tmp), B * H * W, l1.coutp, st)
                     snap(f"dz1_{bi}", tmp, l1)
                 # dW1 = ca*A + cb*(w1.G) + cc*sx: A = plain weight gradient of g1, G / sx = Gram statistics of the
-                # input patches -- z1 is not read (csrc/sed_conv.hip: conv_c1_gram_kernel)
+                # input patches -- z1 is not read (csrc/sed_c1.hip: conv_c1_gram_kernel)
                 if not c1m:          # (C1 mode: Gram statistics from the forward pass, A from the BN1 step above)
                     self._k("sed_conv3x3_c1_gram", self.lib.sed_conv3x3_c1_gram, L.ptr(p.x_ref), L.ptr(p.feat_mean),
                             L.ptr(p.feat_std), L.ptr(p.c1_gram), B, H, W, st)

@@ -1,4 +1,4 @@
-"""GPU: the reference-exact 3x3 conv kernels (dtype SED_F32 = fp32 MFMA, csrc/sed_conv.hip; SED_F32H3 / SED_F32X3 = split operands,
+"""GPU: the reference-exact 3x3 conv kernels (dtype SED_F32 = fp32 MFMA, csrc/sed_conv.hip and csrc/sed_conv_wgrad.hip; SED_F32H3 / SED_F32X3 = split operands,
 csrc/sed_conv_x3.hip and csrc/sed_wgrad_x3.hip) against float64, through the C ABI, at the specialised widths W in {8, 16, 32, 64}.
 
 Reference: the same contraction in float64 on the device (nine shifted float64 GEMMs over NHWC tensors), on the fp32 operands the

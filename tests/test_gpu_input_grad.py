@@ -1,6 +1,6 @@
 """Input gradients and eval-mode (frozen-BatchNorm) backward of the CNN / CRNN models.  Needs the MI355X:  pytest -m gpu.
 
-Kernel level (csrc/sed_c1_dgrad.hip, through the C ABI): conv1's data gradient onto the single input channel with BN1's backward
+Kernel level (csrc/sed_c1_dx.hip, through the C ABI): conv1's data gradient onto the single input channel with BN1's backward
 produced on load, and the eval-mode BatchNorm finalizes, against float64 formulas on the values the kernels see.
 Model level: x.grad and every parameter gradient against oracle/cnn_oracle.py (and a torch CRNN with the same weights) run in
 float64 and differentiated by torch.autograd, in training and in eval mode."""

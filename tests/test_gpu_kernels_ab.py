@@ -1,5 +1,5 @@
 """Kernel-level A/B on the MI355X: the producer/consumer convolution kernels (sed_conv_pc.hip, sed_wgrad.hip) against
-the previous-generation kernels (conv_igemm_kernel / conv_wgrad2_kernel, selected with SED_CONV_KERNEL=lds /
+the previous-generation kernels (conv_igemm_kernel of sed_conv.hip / conv_wgrad2_kernel of sed_conv_wgrad.hip, selected with SED_CONV_KERNEL=lds /
 SED_WGRAD_KERNEL=2) through the C ABI, on the same random bf16 operands.  Both accumulate the same bf16 products in
 fp32, so outputs agree to summation order (one bf16 ulp after rounding); shapes exercise ragged heights (last tile
 partly outside the image), single images, the pooling floor and every prologue / epilogue / dz mode of the path."""

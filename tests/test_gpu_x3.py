@@ -1,5 +1,5 @@
 """GPU: the split-operand convolution kernels of csrc/sed_conv_x3.hip ("f16x3" = dtype SED_F32H3, fp16 pieces; "bf16x3" = SED_F32X3,
-bf16 pieces) against the fp32-MFMA kernels of csrc/sed_conv.hip (the oracle-pinned parity mode) on the SAME fp32 operands, through
+bf16 pieces) against the fp32-MFMA kernels of csrc/sed_conv.hip and csrc/sed_conv_wgrad.hip (the oracle-pinned parity mode) on the SAME fp32 operands, through
 the C ABI.
 
 Every fp32 operand is split a = hi + lo/LS into two 16-bit pieces and a product runs as three 16-bit MFMAs (hi.hi + hi.lo + lo.hi) with

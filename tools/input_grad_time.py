@@ -1,4 +1,4 @@
-"""HIP-event times of the input-gradient and eval-mode backward paths (csrc/sed_c1_dgrad.hip, CnnEngine.backward(need_dx=True)).
+"""HIP-event times of the input-gradient and eval-mode backward paths (csrc/sed_c1_dx.hip, CnnEngine.backward(need_dx=True)).
 
   python tools/input_grad_time.py [--steps K] [--warmup W] [--batch B] [--frames T]
 
