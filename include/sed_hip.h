@@ -445,7 +445,7 @@ int sed_gru_pack_weights(int dtype, const float* whh_fwd, const float* whh_rev, 
 /* Forward recurrence of both directions.  gi [B*t][2][3Hd] = x.W_ih^T + b_ih (sed_gemm_nt);
  * bhh [2][3Hd]; hseq [B*t][2][Hd] (= nn.GRU output (B, t, 2Hd)); saved (nullable for inference)
  * [B*t][2][4][Hd] = r, z, n, W_hn h + b_hn for the backward pass.  h0 = 0.
- * Where SED_BF16 rounds (pinned by tests/test_gpu_crnn_exact_oracle.py for every form the SED_GRU* variables select): W_hh and
+ * Where SED_BF16 rounds (pinned by tests/test_gpu_crnn_exact_oracle.py for both forms of the kernels): W_hh and
  * the previous state are rounded to bf16 (nearest even) as operands of the product W_h* h only; the accumulation, the gates, the
  * blend h' = n + z (h - n) on the fp32 previous state, hseq and all four planes of `saved` are fp32.  saved == NULL gives the same
  * hseq bits.  Rows of hseq / saved past B*t are never written, whatever part of its last chunk B fills.  Sizes: the kernels

@@ -7,12 +7,16 @@
 //   * everything that is not sequential is a plain GEMM on MFMA (gemm_nt_kernel): the input projection
 //     gi = m.W_ih^T + b_ih for all time steps and both directions, and in the backward pass
 //     dW_ih = dgi^T.m, dW_hh = dgh^T.h_prev (split-K over the B*t rows), dm = dgi.W_ih;
-//   * the recurrence itself is latency bound (t = 750 dependent steps of a [32 x Hd]x[Hd x 3Hd] product):
-//     one workgroup per (direction, 32 batch rows) keeps h in registers (fp32) + LDS (MFMA operand
-//     copy) and streams the 3Hd x Hd recurrent matrix from L2 every step in MFMA-fragment order
-//     (pre-packed, 1 KB coalesced per fragment); wave w owns hidden units [32w, 32w+32) of all three
-//     gates, so the gate math is register-local and each step costs two workgroup barriers.
-//     No inter-workgroup synchronisation anywhere (nothing can spin).
+//   * the recurrence itself is latency bound (t = 750 dependent steps of a [rows x Hd]x[Hd x 3Hd] product):
+//     one workgroup per (direction, chunk of batch rows) keeps h in registers (fp32) + LDS (MFMA operand
+//     copy); wave w owns hidden units [32w, 32w+32) of all three gates, so the gate math is register-local
+//     and each step costs two workgroup barriers.  No inter-workgroup synchronisation anywhere (nothing can spin).
+//     Two forms, chosen by gru_use_mfma16():
+//       - bf16, Hd = 256 (the product's CRNN): 2 batch rows per workgroup on the 16x16x32 MFMA, the whole recurrent
+//         matrix resident on the CU (registers + LDS) -- gru_pack16_kernel, gru_seq_fwd16h_kernel, gru_seq_bwd16h_kernel;
+//       - every other hidden size, and fp32: 8 batch rows per workgroup on the 32x32 MFMA, the 3Hd x Hd recurrent matrix
+//         streamed from L2 every step in MFMA-fragment order (pre-packed, 1 KB coalesced per fragment) --
+//         gru_pack_kernel, gru_seq_fwd_kernel, gru_seq_bwd_kernel.
 #include "conv_common.h"
 
 #include <stdlib.h>
@@ -550,18 +554,6 @@ __device__ __forceinline__ float tanhf_(float x) {
     return copysignf(t, x);
 }
 
-template <typename T> __device__ __forceinline__ void lds_put4(T* p, const float (&v)[4]);
-template <> __device__ __forceinline__ void lds_put4<bf16_t>(bf16_t* p, const float (&v)[4]) {
-    bf16x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = (bf16_t)v[i];
-    *reinterpret_cast<bf16x4*>(p) = o;
-}
-template <> __device__ __forceinline__ void lds_put4<float>(float* p, const float (&v)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) p[i] = v[i];
-}
-
 struct GruSeqParams {
     const float* gi;       // [B*t][2*3Hd]  input projection incl. b_ih (fwd) / unused (bwd)
     const float* bhh;      // [2][3Hd]
@@ -579,16 +571,16 @@ struct GruSeqParams {
 // UNIT and its 16 accumulator registers are batch rows (i&3) + 8*(i>>2) + 4*(lane>>5).  Every load of gi and every store of
 // h / saved then covers two full 128-byte lines per instruction.  (The first version had lanes = batch rows: each 16-byte
 // access went to a different (b, t) row, 32 partial lines per instruction, and the recurrence ran at 24 GB/s: 14.6 us/step.)
-// RESN (bf16, Hd = 256): the n-gate fragments of every wave (16 KB each, 128 KB in all) stay in LDS for the whole sequence,
-// so a third of the 393 KB recurrent matrix no longer crosses the CU's memory pipe every step.
-template <typename T, bool RESN, int NREG>
+// A workgroup owns 8 batch rows, D rows 0..7 = accumulator registers 0..3 of every lane; registers 4..15 (D rows 8..31) carry no
+// batch row: they have no gate math, loads or stores and their h rows stay zero.  (The row arithmetic is written for all 16
+// registers, as the instruction lays them out.)
+template <typename T>
 __global__ __launch_bounds__(512) void gru_seq_fwd_kernel(GruSeqParams p) {
     constexpr int KR = EL<T>::KR, KSTEP = EL<T>::KSTEP, PAD = SeqLds<T>::PAD;
     typedef typename EL<T>::frag_t frag_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int Hd = p.Hd, HS = Hd + PAD, KS = Hd / KSTEP, NW = Hd / 32;
     T* hs = reinterpret_cast<T*>(smem);                     // [32][Hd + PAD]
-    frag_t* wn = reinterpret_cast<frag_t*>(hs + 32 * HS);   // RESN: [waves][KS][64 lanes]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int d = blockIdx.x & 1, bc = blockIdx.x >> 1;
     const int bl = lane & 31, hh = lane >> 5;
@@ -599,8 +591,6 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_kernel(GruSeqParams p) {
     const frag_t* __restrict__ wt[3];
 #pragma unroll
     for (int g = 0; g < 3; ++g) wt[g] = wp + ((size_t)(g * NW + w) * KS) * 64 + lane;
-    if (RESN)
-        for (int ks = 0; ks < KS; ++ks) wn[(w * KS + ks) * 64 + lane] = wt[2][(size_t)ks * 64];
     float bias[3];
 #pragma unroll
     for (int g = 0; g < 3; ++g) bias[g] = p.bhh[(size_t)d * 3 * Hd + g * Hd + unit];
@@ -612,12 +602,10 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_kernel(GruSeqParams p) {
     const size_t rows = (size_t)p.B * t;
     const __amdgpu_buffer_rsrc_t gis = make_srd(p.gi, rows * 6 * Hd * 4), hss = make_srd(p.hseq, rows * 2 * Hd * 4);
     const __amdgpu_buffer_rsrc_t svs = make_srd(p.saved, p.saved ? rows * 8 * Hd * 4 : 0);
-    const int b0t = (bc * (2 * NREG) + 4 * hh) * t;     // (first batch row of this lane) * t; NREG = 8: 16-row chunks
+    const int b0t = (bc * 8 + 4 * hh) * t;              // (first batch row of this lane) * t
     auto rowidx = [&](int i, int tt) { return b0t + ((i & 3) + 8 * (i >> 2)) * t + tt; };     // (b*t + tt) of register i
     __syncthreads();
-    // NREG = 8: a batch of at most 16 rows (BASELINE config 4: 16 clips per GPU) only uses registers 0..7 of the accumulators
-    // (rows 0..15): the gate math, loads and stores of the other eight are compiled out (their h rows stay zero)
-    constexpr int nreg = NREG;
+    constexpr int nreg = 4;                              // live accumulator registers per lane
     float gin[3][16];
     auto load_gi = [&](int tt) {
 #pragma unroll
@@ -642,7 +630,7 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_kernel(GruSeqParams p) {
             const frag_t af = *reinterpret_cast<const frag_t*>(hrow + ks * KSTEP);
             acc[0] = mfma(af, wt[0][(size_t)ks * 64], acc[0]);
             acc[1] = mfma(af, wt[1][(size_t)ks * 64], acc[1]);
-            acc[2] = mfma(af, RESN ? wn[(w * KS + ks) * 64 + lane] : wt[2][(size_t)ks * 64], acc[2]);
+            acc[2] = mfma(af, wt[2][(size_t)ks * 64], acc[2]);
         }
         // gates: register i <-> batch row (i&3) + 8*(i>>2) + 4*hh; stores issued as the values are produced
 #pragma unroll
@@ -670,118 +658,19 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_kernel(GruSeqParams p) {
     }
 }
 
-// ---- forward recurrence, bf16 / Hd = 256: the whole recurrent matrix stays on the CU ----------------------------------
-// Same orientation as above (lane = hidden unit).  Wave w keeps the r and z gate fragments of its 32 units in REGISTERS
-// (32 x 1 KB), the n gate fragments sit in LDS (16 KB per wave): the MFMA loop of a step touches no global memory at all.
-// The next step's r / z input projections are fetched straight into the accumulators (acc = b_hh + gi is the sigmoid's
-// argument before the recurrent product is added); only gi_n needs registers of its own.
-template <int NREG>
-__global__ __launch_bounds__(512) void gru_seq_fwd_res_kernel(GruSeqParams p) {
-    typedef bf16_t T;
-    constexpr int Hd = 256, KS = 16, PAD = SeqLds<T>::PAD, HS = Hd + PAD, NW = Hd / 32;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* hs = reinterpret_cast<T*>(smem);                               // [32][HS]
-    bf16x8* wn = reinterpret_cast<bf16x8*>(hs + 32 * HS);             // [8 waves][KS][64 lanes]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int d = blockIdx.x & 1, bc = blockIdx.x >> 1;
-    const int bl = lane & 31, hh = lane >> 5;
-    const int unit = 32 * w + bl;
-    const int t = p.t;
-    for (int i = tid; i < 32 * HS; i += 512) hs[i] = (T)0.f;
-    const bf16x8* __restrict__ wp = reinterpret_cast<const bf16x8*>(p.wpack) + (size_t)d * 3 * Hd * Hd / 8;
-    constexpr int NZR = NREG <= 8 ? 16 : 12;    // z fragments in registers; the last KS - NZR stream from L2 every step (16 spilled)
-    bf16x8 wr[KS], wz[NZR];
-    const bf16x8* __restrict__ wzg = wp + ((size_t)(1 * NW + w) * KS) * 64 + lane;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        wr[ks] = wp[((size_t)(0 * NW + w) * KS + ks) * 64 + lane];
-        if (ks < NZR) wz[ks] = wzg[(size_t)ks * 64];
-        wn[(w * KS + ks) * 64 + lane] = wp[((size_t)(2 * NW + w) * KS + ks) * 64 + lane];
-    }
-    float bias[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) bias[g] = p.bhh[(size_t)d * 3 * Hd + g * Hd + unit];
-    const size_t rows = (size_t)p.B * t;
-    const __amdgpu_buffer_rsrc_t gis = make_srd(p.gi, rows * 6 * Hd * 4), hss = make_srd(p.hseq, rows * 2 * Hd * 4);
-    const __amdgpu_buffer_rsrc_t svs = make_srd(p.saved, p.saved ? rows * 8 * Hd * 4 : 0);
-    const int b0t = (bc * (2 * NREG) + 4 * hh) * t;
-    auto rowidx = [&](int i, int tt) { return b0t + ((i & 3) + 8 * (i >> 2)) * t + tt; };
-    float h[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) h[i] = 0.f;
-    __syncthreads();
-    f32x16 acc[3];
-    float ginn[16];
-    // the loads of the NEXT step's projections are issued value by value inside the gate loop, into the accumulator registers
-    // the gate math has just released; b_hh is added when they are first used (top of the next step), so their latency hides
-    // behind the rest of the gate math and the two barriers
-    constexpr int nreg = NREG;                              // (see gru_seq_fwd_kernel)
-    auto issue_inputs = [&](int i, int tt) {
-        if (i >= nreg) { acc[0][i] = 0.f; acc[1][i] = 0.f; ginn[i] = 0.f; return; }
-        const unsigned o = (unsigned)((rowidx(i, tt) * 6 * Hd + d * 3 * Hd + unit) * 4);
-        acc[0][i] = buf_load_f32(gis, o);
-        acc[1][i] = buf_load_f32(gis, o + (unsigned)(Hd * 4));
-        ginn[i] = buf_load_f32(gis, o + (unsigned)(2 * Hd * 4));
-    };
-#pragma unroll
-    for (int i = 0; i < 16; ++i) issue_inputs(i, d == 0 ? 0 : t - 1);
-    for (int s = 0; s < t; ++s) {
-        const int tt = d == 0 ? s : t - 1 - s;
-        const int tn = d == 0 ? s + 1 : t - 2 - s;          // next step's time index
-        bf16x8 wzs[2];                                       // streamed z fragments: a two-deep ring, fetched six k-steps ahead
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[0][i] += bias[0]; acc[1][i] += bias[1]; acc[2][i] = bias[2]; }
-        const T* hrow = hs + bl * HS + 8 * hh;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            if (NZR < KS && ks == NZR - 6) wzs[0] = wzg[(size_t)(NZR < KS ? NZR : 0) * 64];
-            if (NZR < KS && ks == NZR - 5) wzs[1] = wzg[(size_t)(NZR < KS ? NZR + 1 : 0) * 64];
-            const bf16x8 af = *reinterpret_cast<const bf16x8*>(hrow + ks * 16);
-            acc[0] = mfma(af, wr[ks], acc[0]);
-            acc[1] = mfma(af, ks < NZR ? wz[ks < NZR ? ks : 0] : wzs[(ks - NZR) & 1], acc[1]);
-            acc[2] = mfma(af, wn[(w * KS + ks) * 64 + lane], acc[2]);
-            if (ks >= NZR && ks + 2 < KS) wzs[(ks - NZR) & 1] = wzg[(size_t)(ks + 2) * 64];
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            if (i >= nreg) continue;
-            const float rr = sigmoidf_(acc[0][i]);
-            const float zz = sigmoidf_(acc[1][i]);
-            const float ghn = acc[2][i];
-            const float nn = tanhf_(fmaf(rr, ghn, ginn[i]));
-            h[i] = fmaf(zz, h[i] - nn, nn);
-            const int r0 = rowidx(i, tt);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h[i]), hss, (unsigned)((r0 * 2 * Hd + d * Hd + unit) * 4), 0, 0);
-            const unsigned so = (unsigned)((r0 * 8 * Hd + d * 4 * Hd + unit) * 4);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, rr), svs, so, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, zz), svs, so + (unsigned)(Hd * 4), 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, nn), svs, so + (unsigned)(2 * Hd * 4), 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ghn), svs, so + (unsigned)(3 * Hd * 4), 0, 0);
-            if (s + 1 < t) issue_inputs(i, tn);             // (wave-uniform)
-        }
-        __syncthreads();                                     // every wave has read hs for this step
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if (i < nreg) hs[((i & 3) + 8 * (i >> 2) + 4 * hh) * HS + unit] = (T)h[i];
-        __syncthreads();
-    }
-}
-
 // ---- backward recurrence (BPTT) ------------------------------------------------------------------
 // Same orientation as the forward kernels: D[batch][unit] = dgh[batch][gate unit j] . W_hh[j][unit], a lane is the hidden unit
 // whose dh_prev it accumulates AND whose gate gradients it computes, its 16 registers are batch rows; all gate tensors move
 // in full 128-byte lines.  The step's inputs (dh, r, z, n, W_hn h + b_hn, h_prev: 96 values per lane) are fetched one step
-// ahead, behind the MFMA loop.  NL fragments of the wave's 3Hd/KSTEP recurrent-operator fragments stay in LDS for the whole
-// sequence (bf16, Hd = 256: 13 of 48 -- what fits beside the dgh image), the rest streams from L2.
-template <typename T, int NREG, int NL, int NR = 0>
+// ahead, behind the MFMA loop.  8 batch rows per workgroup as in the forward kernel; the recurrent operator streams from L2.
+template <typename T>
 __global__ __launch_bounds__(512) void gru_seq_bwd_kernel(GruSeqParams p) {
     constexpr int KR = EL<T>::KR, KSTEP = EL<T>::KSTEP, PAD = SeqLds<T>::PAD;
     typedef typename EL<T>::frag_t frag_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* dgs = reinterpret_cast<T*>(smem);                    // [DR][3Hd + PAD]: dgh of the current step (DR = 16 rows when NREG = 8)
-    constexpr int DR = 2 * NREG;
+    T* dgs = reinterpret_cast<T*>(smem);                    // [DR][3Hd + PAD]: dgh of the current step
+    constexpr int DR = 8;
     const int Hd = p.Hd, GS = 3 * Hd + PAD, KS = 3 * Hd / KSTEP;
-    frag_t* wl = reinterpret_cast<frag_t*>(dgs + DR * GS);  // [waves][NL][64 lanes]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int d = blockIdx.x & 1, bc = blockIdx.x >> 1;
     const int bl = lane & 31, hh = lane >> 5;
@@ -789,21 +678,16 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_kernel(GruSeqParams p) {
     const int t = p.t;
     const frag_t* __restrict__ wt = reinterpret_cast<const frag_t*>(p.wpack) + (size_t)d * 3 * Hd * Hd / KR +
                                     ((size_t)w * KS) * 64 + lane;
-#pragma unroll
-    for (int ks = 0; ks < NL; ++ks) wl[(w * NL + ks) * 64 + lane] = wt[(size_t)ks * 64];
-    frag_t wrg[NR > 0 ? NR : 1];                           // NR more fragments in registers
-#pragma unroll
-    for (int ks = 0; ks < NR; ++ks) wrg[ks] = wt[(size_t)(NL + ks) * 64];
     const size_t rows = (size_t)p.B * t;
     const __amdgpu_buffer_rsrc_t dhs = make_srd(p.dhseq, rows * 2 * Hd * 4), hqs = make_srd(p.hseq, rows * 2 * Hd * 4);
     const __amdgpu_buffer_rsrc_t svs = make_srd(p.saved, rows * 8 * Hd * 4);
     const __amdgpu_buffer_rsrc_t gis = make_srd(p.dgi, rows * 6 * Hd * 4), ghs = make_srd(p.dgh, rows * 6 * Hd * 4);
-    const int b0t = (bc * (2 * NREG) + 4 * hh) * t;
+    const int b0t = (bc * DR + 4 * hh) * t;
     auto rowidx = [&](int i, int tt) { return b0t + ((i & 3) + 8 * (i >> 2)) * t + tt; };     // (b*t + tt) of register i
     float dhc[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) dhc[i] = 0.f;
-    constexpr int nreg = NREG;                              // (see gru_seq_fwd_kernel; the dgh rows of the skipped registers stay zero)
+    constexpr int nreg = 4;                                 // (see gru_seq_fwd_kernel)
     for (int i = tid; i < DR * GS; i += blockDim.x) dgs[i] = from_f<T>(0.f);
     float in_dh[16], in_r[16], in_z[16], in_n[16], in_g[16], in_hp[16];
     auto fetch = [&](int s) {          // inputs of step s (reverse of the forward order); rows past the batch read 0
@@ -860,19 +744,9 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_kernel(GruSeqParams p) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[e] = 0.f;
         const T* grow = dgs + (bl & (DR - 1)) * GS + KR * hh;     // A operand: batch row bl, KR consecutive gate units per k-group
-                                                                  // (DR = 16: rows 16..31 of D are never used, their lanes re-read rows 0..15)
-#pragma unroll
-        for (int ks = 0; ks < NL; ++ks) {
-            const frag_t af = *reinterpret_cast<const frag_t*>(grow + ks * KSTEP);
-            acc = mfma(af, wl[(w * NL + ks) * 64 + lane], acc);
-        }
-#pragma unroll
-        for (int ks = 0; ks < NR; ++ks) {
-            const frag_t af = *reinterpret_cast<const frag_t*>(grow + (NL + ks) * KSTEP);
-            acc = mfma(af, wrg[ks], acc);
-        }
+                                                                  // (rows 8..31 of D are never used, their lanes re-read rows 0..7)
 #pragma unroll 8
-        for (int ks = NL + NR; ks < KS; ++ks) {
+        for (int ks = 0; ks < KS; ++ks) {
             const frag_t af = *reinterpret_cast<const frag_t*>(grow + ks * KSTEP);
             acc = mfma(af, wt[(size_t)ks * 64], acc);
         }
@@ -881,15 +755,12 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_kernel(GruSeqParams p) {
     }
 }
 
-
 // ---------------------------------------------------------------------------------------------
-// Round 4: the 8-row chunks on v_mfma_f32_16x16x32_bf16 (bf16, Hd = 256).
-// A 32x32x16 MFMA computes 32 batch rows of which an 8-row chunk uses 8; the 16x16x32 instruction (16 rows x 16 units x 32 k in
-// 16 cycles) does the same products in half the matrix-pipe time (a step was 96 MFMAs of 32 cycles per SIMD = 1.5 of its 2.6 us).
+// bf16, Hd = 256 on v_mfma_f32_16x16x32_bf16.
+// A 32x32x16 MFMA computes 32 batch rows of which a small chunk uses few; the 16x16x32 instruction (16 rows x 16 units x 32 k in
+// 16 cycles) does the same products in half the matrix-pipe time.
 // Orientation as before, D[batch][unit]: A = the h (or dgh) fragment, B = the packed operator, a lane is a hidden unit:
-//   lane l: n = l & 15 (unit 16*nt + n of the wave's 32), q = l >> 4;  D register i <-> row m = 4q + i
-// The chunk's 8 batch rows sit at m = 4*(b >> 1) + (b & 1), so EVERY lane holds two live rows (registers 0, 1 <-> b = 2q + i) of
-// its two units: the gate math keeps all 64 lanes busy with 12 values each, as in the 32-wide form.
+//   lane l: n = l & 15 (unit 16*nt + n of the wave's 32, nt = 0, 1), q = l >> 4;  D register i <-> row m = 4q + i
 //   pack16 fwd: [gate][wave][nt][ks (8)][lane] bf16x8:  W_hh[gate*Hd + 32w + 16nt + n][32ks + 8q + e]
 //   pack16 bwd: [wave][nt][ks (24)][lane] bf16x8:       W_hh[32ks + 8q + e][32w + 16nt + n]
 // ---------------------------------------------------------------------------------------------
@@ -926,225 +797,9 @@ __global__ __launch_bounds__(256) void gru_pack16_kernel(const float* __restrict
     }
 }
 
-// NLIVE live rows per lane: 2 = 8-row chunks (m = 4q + i, b = 2q + i), 1 = 4-row chunks (m = 4q, b = q): twice the workgroups, half the
-// gate math (the step's other half besides the MFMAs) per workgroup
-template <int NLIVE>
-__global__ __launch_bounds__(512) void gru_seq_fwd16_kernel(GruSeqParams p) {
-    typedef bf16_t T;
-    constexpr int Hd = 256, KS = 8, PAD = SeqLds<T>::PAD, HS = Hd + PAD, NW = 8;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* hs = reinterpret_cast<T*>(smem);                               // [16][HS]   rows m = 4*(b >> 1) + (b & 1) live
-    bf16x8* wn = reinterpret_cast<bf16x8*>(hs + 16 * HS);             // [8 waves][2][KS][64 lanes]   n-gate fragments
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int d = blockIdx.x & 1, bc = blockIdx.x >> 1;
-    const int n = lane & 15, q = lane >> 4;
-    const int t = p.t;
-    for (int i = tid; i < 16 * HS; i += 512) hs[i] = (T)0.f;
-    const bf16x8* __restrict__ wp = reinterpret_cast<const bf16x8*>(p.wpack) + (size_t)d * 3 * Hd * Hd / 8;
-    bf16x8 wr[2][KS], wz[2][KS];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            wr[nt][ks] = wp[((size_t)((0 * NW + w) * 2 + nt) * KS + ks) * 64 + lane];
-            wz[nt][ks] = wp[((size_t)((1 * NW + w) * 2 + nt) * KS + ks) * 64 + lane];
-            wn[((w * 2 + nt) * KS + ks) * 64 + lane] = wp[((size_t)((2 * NW + w) * 2 + nt) * KS + ks) * 64 + lane];
-        }
-    int unit[2];
-    float bias[3][2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-        unit[nt] = 32 * w + 16 * nt + n;
-#pragma unroll
-        for (int g = 0; g < 3; ++g) bias[g][nt] = p.bhh[(size_t)d * 3 * Hd + g * Hd + unit[nt]];
-    }
-    const size_t rows = (size_t)p.B * t;
-    const __amdgpu_buffer_rsrc_t gis = make_srd(p.gi, rows * 6 * Hd * 4), hss = make_srd(p.hseq, rows * 2 * Hd * 4);
-    const __amdgpu_buffer_rsrc_t svs = make_srd(p.saved, p.saved ? rows * 8 * Hd * 4 : 0);
-    // register i (0, 1) <-> batch row bc*8 + 2q + i (rows past the batch: out of range -> loads 0, stores dropped)
-    auto rowidx = [&](int i, int tt) { return (bc * (4 * NLIVE) + NLIVE * q + i) * t + tt; };
-    float h[2][NLIVE];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int i = 0; i < NLIVE; ++i) h[nt][i] = 0.f;
-    __syncthreads();
-    gru_f32x4 acc[3][2];
-    float ginn[2][NLIVE];
-    // the next step's r / z projections go straight into the accumulator registers the gate math has just released
-    auto issue_inputs = [&](int nt, int i, int tt) {
-        const unsigned o = (unsigned)((rowidx(i, tt) * 6 * Hd + d * 3 * Hd + unit[nt]) * 4);
-        acc[0][nt][i] = buf_load_f32(gis, o);
-        acc[1][nt][i] = buf_load_f32(gis, o + (unsigned)(Hd * 4));
-        ginn[nt][i] = buf_load_f32(gis, o + (unsigned)(2 * Hd * 4));
-    };
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { acc[0][nt][i] = 0.f; acc[1][nt][i] = 0.f; }
-#pragma unroll
-        for (int i = 0; i < NLIVE; ++i) issue_inputs(nt, i, d == 0 ? 0 : t - 1);
-    }
-    for (int s = 0; s < t; ++s) {
-        const int tt = d == 0 ? s : t - 1 - s;
-        const int tn = d == 0 ? s + 1 : t - 2 - s;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { acc[0][nt][i] += bias[0][nt]; acc[1][nt][i] += bias[1][nt]; acc[2][nt][i] = bias[2][nt]; }
-        }
-        const T* hrow = hs + n * HS + 8 * q;                 // A operand: row m = n, 8 consecutive units of h per k-group
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const bf16x8 af = *reinterpret_cast<const bf16x8*>(hrow + ks * 32);
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                acc[0][nt] = mfma16(af, wr[nt][ks], acc[0][nt]);
-                acc[1][nt] = mfma16(af, wz[nt][ks], acc[1][nt]);
-                acc[2][nt] = mfma16(af, wn[((w * 2 + nt) * KS + ks) * 64 + lane], acc[2][nt]);
-            }
-        }
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i = 0; i < NLIVE; ++i) {
-                const float rr = sigmoidf_(acc[0][nt][i]);
-                const float zz = sigmoidf_(acc[1][nt][i]);
-                const float ghn = acc[2][nt][i];
-                const float nn = tanhf_(fmaf(rr, ghn, ginn[nt][i]));
-                h[nt][i] = fmaf(zz, h[nt][i] - nn, nn);
-                const int r0 = rowidx(i, tt);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h[nt][i]), hss, (unsigned)((r0 * 2 * Hd + d * Hd + unit[nt]) * 4), 0, 0);
-                const unsigned so = (unsigned)((r0 * 8 * Hd + d * 4 * Hd + unit[nt]) * 4);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, rr), svs, so, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, zz), svs, so + (unsigned)(Hd * 4), 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, nn), svs, so + (unsigned)(2 * Hd * 4), 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ghn), svs, so + (unsigned)(3 * Hd * 4), 0, 0);
-                if (s + 1 < t) issue_inputs(nt, i, tn);     // (wave-uniform)
-            }
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)                       // the dead rows' accumulators restart from 0 (+ bias) every step
-#pragma unroll
-            for (int i = NLIVE; i < 4; ++i) { acc[0][nt][i] = 0.f; acc[1][nt][i] = 0.f; }
-        __syncthreads();                                     // every wave has read hs for this step
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i = 0; i < NLIVE; ++i) hs[(4 * q + i) * HS + unit[nt]] = (T)h[nt][i];
-        __syncthreads();
-    }
-}
-
-// NL of a wave's 48 operator fragments in LDS, the other 48 - NL in registers (as gru_seq_bwd_kernel<bf16, 4, 17, 31>)
-template <int NL, int NLIVE>
-__global__ __launch_bounds__(512) void gru_seq_bwd16_kernel(GruSeqParams p) {
-    typedef bf16_t T;
-    constexpr int Hd = 256, PAD = SeqLds<T>::PAD, GS = 3 * Hd + PAD, KS = 24, NF = 2 * KS, NR = NF - NL;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* dgs = reinterpret_cast<T*>(smem);                    // [16][GS]: dgh of the current step, rows m = 4*(b >> 1) + (b & 1) live
-    bf16x8* wl = reinterpret_cast<bf16x8*>(dgs + 16 * GS);  // [waves][NL][64 lanes]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int d = blockIdx.x & 1, bc = blockIdx.x >> 1;
-    const int n = lane & 15, q = lane >> 4;
-    const int t = p.t;
-    // fragment f = nt*KS + ks of this wave
-    const bf16x8* __restrict__ wt = reinterpret_cast<const bf16x8*>(p.wpack) + (size_t)d * 3 * Hd * Hd / 8 + ((size_t)w * NF) * 64 + lane;
-#pragma unroll
-    for (int f = 0; f < NL; ++f) wl[(w * NL + f) * 64 + lane] = wt[(size_t)f * 64];
-    bf16x8 wrg[NR];
-#pragma unroll
-    for (int f = 0; f < NR; ++f) wrg[f] = wt[(size_t)(NL + f) * 64];
-    int unit[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) unit[nt] = 32 * w + 16 * nt + n;
-    const size_t rows = (size_t)p.B * t;
-    const __amdgpu_buffer_rsrc_t dhs = make_srd(p.dhseq, rows * 2 * Hd * 4), hqs = make_srd(p.hseq, rows * 2 * Hd * 4);
-    const __amdgpu_buffer_rsrc_t svs = make_srd(p.saved, rows * 8 * Hd * 4);
-    const __amdgpu_buffer_rsrc_t gis = make_srd(p.dgi, rows * 6 * Hd * 4), ghs = make_srd(p.dgh, rows * 6 * Hd * 4);
-    auto rowidx = [&](int i, int tt) { return (bc * (4 * NLIVE) + NLIVE * q + i) * t + tt; };
-    float dhc[2][NLIVE];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int i = 0; i < NLIVE; ++i) dhc[nt][i] = 0.f;
-    for (int i = tid; i < 16 * GS; i += 512) dgs[i] = (T)0.f;
-    float in_dh[2][NLIVE], in_r[2][NLIVE], in_z[2][NLIVE], in_n[2][NLIVE], in_g[2][NLIVE], in_hp[2][NLIVE];
-    auto fetch = [&](int s) {          // inputs of step s (reverse of the forward order); rows past the batch read 0
-        const int tt = d == 0 ? t - 1 - s : s;
-        const int tp = d == 0 ? tt - 1 : tt + 1;             // where h_prev of this step lives
-        const bool has_prev = tp >= 0 && tp < t;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i = 0; i < NLIVE; ++i) {
-                const int r0 = rowidx(i, tt);
-                in_dh[nt][i] = buf_load_f32(dhs, (unsigned)((r0 * 2 * Hd + d * Hd + unit[nt]) * 4));
-                const unsigned so = (unsigned)((r0 * 8 * Hd + d * 4 * Hd + unit[nt]) * 4);
-                in_r[nt][i] = buf_load_f32(svs, so);
-                in_z[nt][i] = buf_load_f32(svs, so + (unsigned)(Hd * 4));
-                in_n[nt][i] = buf_load_f32(svs, so + (unsigned)(2 * Hd * 4));
-                in_g[nt][i] = buf_load_f32(svs, so + (unsigned)(3 * Hd * 4));
-                in_hp[nt][i] = has_prev ? buf_load_f32(hqs, (unsigned)((rowidx(i, tp) * 2 * Hd + d * Hd + unit[nt]) * 4)) : 0.f;
-            }
-    };
-    fetch(0);
-    __syncthreads();
-    for (int s = 0; s < t; ++s) {
-        const int tt = d == 0 ? t - 1 - s : s;
-        float dzk[2][NLIVE];  // dh * z: the direct path into dh_prev
-        __syncthreads();                                     // previous step's MFMA reads of dgs are done
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i = 0; i < NLIVE; ++i) {
-                const float rr = in_r[nt][i], zz = in_z[nt][i], nn = in_n[nt][i], ghn = in_g[nt][i];
-                const float dh = in_dh[nt][i] + dhc[nt][i];
-                const float dn_pre = dh * (1.f - zz) * (1.f - nn * nn);
-                const float dz_pre = dh * (in_hp[nt][i] - nn) * zz * (1.f - zz);
-                const float dr_pre = dn_pre * ghn * rr * (1.f - rr);
-                const float ghn_r = dn_pre * rr;
-                dzk[nt][i] = dh * zz;
-                const int r0 = rowidx(i, tt);
-                const unsigned go = (unsigned)((r0 * 6 * Hd + d * 3 * Hd + unit[nt]) * 4);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dr_pre), gis, go, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dz_pre), gis, go + (unsigned)(Hd * 4), 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dn_pre), gis, go + (unsigned)(2 * Hd * 4), 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dr_pre), ghs, go, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dz_pre), ghs, go + (unsigned)(Hd * 4), 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ghn_r), ghs, go + (unsigned)(2 * Hd * 4), 0, 0);
-                T* grow_w = dgs + (4 * q + i) * GS + unit[nt];
-                grow_w[0] = (T)dr_pre;
-                grow_w[Hd] = (T)dz_pre;
-                grow_w[2 * Hd] = (T)ghn_r;
-            }
-        __syncthreads();
-        if (s + 1 < t) fetch(s + 1);                         // flies behind the MFMA loop
-        // dh_prev[b][unit k] = sum_j dgh[b][j] W_hh[j][k]
-        gru_f32x4 acc[2];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[nt][e] = 0.f;
-        const T* grow = dgs + n * GS + 8 * q;                // A operand: row m = n, 8 consecutive gate units per k-group
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const bf16x8 af = *reinterpret_cast<const bf16x8*>(grow + ks * 32);
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                const int f = nt * KS + ks;
-                acc[nt] = mfma16(af, f < NL ? wl[(w * NL + (f < NL ? f : 0)) * 64 + lane] : wrg[f >= NL ? f - NL : 0], acc[nt]);
-            }
-        }
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int i = 0; i < NLIVE; ++i) dhc[nt][i] = dzk[nt][i] + acc[nt][i];
-    }
-}
-
-// ---- 2-row chunks with split gate ownership (round 4) ------------------------------------------------------------------------------
-// In the 4-row form every lane evaluates the gates of TWO hidden units (nt = 0, 1) of one batch row, and that gate math (six quarter-rate
-// transcendentals per value) is the part of a step that does not shrink with the rows.  With two rows per workgroup the rows sit at D
+// ---- 2-row chunks with split gate ownership --------------------------------------------------------------------------------------
+// The gate math (six quarter-rate transcendentals per value) is the part of a step that the faster instruction does not shrink; it
+// shrinks with the rows per workgroup.  With two rows per workgroup the rows sit at D
 // rows m = 0 and 4 (lanes q = 0, 1) and the lanes q = 2, 3 would idle: v_permlane32_swap hands them the nt = 1 accumulators of lanes
 // q = 0, 1 (lane l <-> l + 32, one instruction per gate: the result register holds the nt = 0 value in the lower and the nt = 1 value in
 // the upper half-wave), so every lane evaluates ONE unit of one row and keeps that unit's state, inputs and stores to itself.
@@ -1152,17 +807,11 @@ __device__ __forceinline__ float gru_own(float v_nt0, float v_nt1) {       // la
     const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v_nt0), __builtin_bit_cast(unsigned, v_nt1), false, false);
     return __builtin_bit_cast(float, r[0]);
 }
-// DB (round 6, SED_GRU_1BAR=1; measured neutral, off): ONE barrier per step.  Only D rows m = 0 and 4 are live, so the h image is three rows (row 0, row 4, one shared
-// zero row for the other fourteen lanes' A-operand reads) and fits twice in the space of the 16-row image: step s reads buffer s & 1 and
-// writes the new state into the other one -- a wave still reading buffer s & 1 is never overtaken by a write to it, because that write
-// belongs to step s + 1 and sits behind the barrier that ends step s.  (The two-barrier form: write-after-read and read-after-write on
-// one image.)
-template <bool DB = false>
 __global__ __launch_bounds__(512) void gru_seq_fwd16h_kernel(GruSeqParams p) {
     typedef bf16_t T;
     constexpr int Hd = 256, KS = 8, PAD = SeqLds<T>::PAD, HS = Hd + PAD, NW = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* hs = reinterpret_cast<T*>(smem);                               // [16][HS]   rows m = 0, 4 live  (DB: [2][3][HS])
+    T* hs = reinterpret_cast<T*>(smem);                               // [16][HS]   rows m = 0, 4 live
     bf16x8* wn = reinterpret_cast<bf16x8*>(hs + 16 * HS);             // [8 waves][2][KS][64 lanes]   n-gate fragments
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int d = blockIdx.x & 1, bc = blockIdx.x >> 1;
@@ -1208,7 +857,7 @@ __global__ __launch_bounds__(512) void gru_seq_fwd16h_kernel(GruSeqParams p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) { acc[0][nt][i] = bias[0][nt]; acc[1][nt][i] = bias[1][nt]; acc[2][nt][i] = bias[2][nt]; }
         // A operand: row m = n, 8 consecutive units of h per k-group
-        const T* hrow = DB ? hs + ((s & 1) * 3 + (n == 0 ? 0 : n == 4 ? 1 : 2)) * HS + 8 * q : hs + n * HS + 8 * q;
+        const T* hrow = hs + n * HS + 8 * q;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const bf16x8 af = *reinterpret_cast<const bf16x8*>(hrow + ks * 32);
@@ -1220,7 +869,6 @@ __global__ __launch_bounds__(512) void gru_seq_fwd16h_kernel(GruSeqParams p) {
             }
         }
         // D row 4q, register 0: lanes q = 0, 1 hold rows 0 / 1 of the chunk for both unit halves; the upper half-wave takes nt = 1
-        // ((b + h W^T) + gi: the 4-row form adds gi first -- same values to fp32 rounding, not the same bits)
         const float rr = sigmoidf_(gir + gru_own(acc[0][0][0], acc[0][1][0]));
         const float zz = sigmoidf_(giz + gru_own(acc[1][0][0], acc[1][1][0]));
         const float ghn = gru_own(acc[2][0][0], acc[2][1][0]);
@@ -1234,23 +882,18 @@ __global__ __launch_bounds__(512) void gru_seq_fwd16h_kernel(GruSeqParams p) {
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, nn), svs, so + (unsigned)(2 * Hd * 4), 0, 0);
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ghn), svs, so + (unsigned)(3 * Hd * 4), 0, 0);
         if (s + 1 < t) issue_inputs(tn);                     // (wave-uniform)
-        if (DB) {
-            hs[(((s + 1) & 1) * 3 + (q & 1)) * HS + uo] = (T)h;
-            __syncthreads();
-        } else {
-            __syncthreads();                                 // every wave has read hs for this step
-            hs[(4 * (q & 1)) * HS + uo] = (T)h;
-            __syncthreads();
-        }
+        __syncthreads();                                     // every wave has read hs for this step
+        hs[(4 * (q & 1)) * HS + uo] = (T)h;
+        __syncthreads();
     }
 }
 
-template <int NL, bool DB = false>
+// NL = 16 of a wave's 48 operator fragments in LDS (beside the 16-row dgh image), the other 32 in registers
 __global__ __launch_bounds__(512) void gru_seq_bwd16h_kernel(GruSeqParams p) {
     typedef bf16_t T;
-    constexpr int Hd = 256, PAD = SeqLds<T>::PAD, GS = 3 * Hd + PAD, KS = 24, NF = 2 * KS, NR = NF - NL;
+    constexpr int Hd = 256, PAD = SeqLds<T>::PAD, GS = 3 * Hd + PAD, KS = 24, NF = 2 * KS, NL = 16, NR = NF - NL;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* dgs = reinterpret_cast<T*>(smem);                    // [16][GS]: dgh of the current step, rows m = 0, 4 live  (DB: [2][3][GS], one barrier per step)
+    T* dgs = reinterpret_cast<T*>(smem);                    // [16][GS]: dgh of the current step, rows m = 0, 4 live
     bf16x8* wl = reinterpret_cast<bf16x8*>(dgs + 16 * GS);  // [waves][NL][64 lanes]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int d = blockIdx.x & 1, bc = blockIdx.x >> 1;
@@ -1288,7 +931,7 @@ __global__ __launch_bounds__(512) void gru_seq_bwd16h_kernel(GruSeqParams p) {
     __syncthreads();
     for (int s = 0; s < t; ++s) {
         const int tt = d == 0 ? t - 1 - s : s;
-        if (!DB) __syncthreads();                            // previous step's MFMA reads of dgs are done
+        __syncthreads();                                     // previous step's MFMA reads of dgs are done
         const float rr = in_r, zz = in_z, nn = in_n, ghn = in_g;
         const float dh = in_dh + dhc;
         const float dn_pre = dh * (1.f - zz) * (1.f - nn * nn);
@@ -1305,7 +948,7 @@ __global__ __launch_bounds__(512) void gru_seq_bwd16h_kernel(GruSeqParams p) {
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dr_pre), ghs, go, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, dz_pre), ghs, go + (unsigned)(Hd * 4), 0, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ghn_r), ghs, go + (unsigned)(2 * Hd * 4), 0, 0);
-            T* grow_w = DB ? dgs + ((s & 1) * 3 + (q & 1)) * GS + uo : dgs + (4 * (q & 1)) * GS + uo;
+            T* grow_w = dgs + (4 * (q & 1)) * GS + uo;
             grow_w[0] = (T)dr_pre;
             grow_w[Hd] = (T)dz_pre;
             grow_w[2 * Hd] = (T)ghn_r;
@@ -1319,7 +962,7 @@ __global__ __launch_bounds__(512) void gru_seq_bwd16h_kernel(GruSeqParams p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[nt][e] = 0.f;
         // A operand: row m = n, 8 consecutive gate units per k-group
-        const T* grow = DB ? dgs + ((s & 1) * 3 + (n == 0 ? 0 : n == 4 ? 1 : 2)) * GS + 8 * q : dgs + n * GS + 8 * q;
+        const T* grow = dgs + n * GS + 8 * q;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const bf16x8 af = *reinterpret_cast<const bf16x8*>(grow + ks * 32);
@@ -1333,22 +976,10 @@ __global__ __launch_bounds__(512) void gru_seq_bwd16h_kernel(GruSeqParams p) {
     }
 }
 
-// which form the 8-row chunks of the bf16 / Hd = 256 recurrence take (pack layout and kernels must agree): SED_GRU_MFMA16=0 keeps
-// the 32x32x16 kernels of round 3
-// batch rows per workgroup of the 16x16x32 form (SED_GRU16_ROWS = 8 | 4 | 2, default 2: gru_seq_*16h_kernel above, 0.76 / 0.98 ms).  Measured (round 4, B = 32 / t = 750, forward / backward):
-// 32x32x16 8-row chunks 1.91 / 2.00 ms, 16x16x32 8-row chunks 1.60 / 1.80 ms, 16x16x32 4-row chunks 1.06 / 1.12 ms -- once the matrix
-// work is halved the gate math (six quarter-rate transcendentals per value) is the other half of a step, and it halves with the rows.
-static int gru16_rows() {
-    if (const char* e = sed_getenv("SED_GRU16_ROWS")) return atoi(e) == 8 ? 8 : atoi(e) == 4 ? 4 : 2;
-    return 2;
-}
-static bool gru_use_mfma16(int dtype, int Hd) {
-    if (!(dtype == SED_BF16 && Hd == 256)) return false;
-    if (const char* e = sed_getenv("SED_GRU_MFMA16")) if (e[0] == '0') return false;
-    if (sed_getenv("SED_GRU_RESIDENT")) return false;                                  // (A/B forms of round 3)
-    if (const char* e = sed_getenv("SED_GRU_ROWS")) if (atoi(e) != 8) return false;
-    return true;
-}
+// bf16 with Hd = 256 runs the two-row 16x16x32 kernels (gru_pack16_kernel's layout, gru_seq_*16h_kernel); every other size and fp32
+// run the 8-row generic kernels.  The pack layout and the kernels must agree, so all three entry points ask this one function.
+// (Why two rows: LABNOTES, round 4 -- B = 32 / t = 750 forward / backward 0.76 / 0.98 ms.)
+static bool gru_use_mfma16(int dtype, int Hd) { return dtype == SED_BF16 && Hd == 256; }
 
 extern "C" size_t sed_gru_pack_elems(int Hd) { return (size_t)2 * 3 * Hd * Hd; }   // per operator: both directions
 
@@ -1373,13 +1004,15 @@ extern "C" int sed_gru_pack_weights(int dtype, const float* whh_fwd, const float
     return 0;
 }
 
-template <typename T, typename K>
-static int set_lds(K kernel, size_t lds) {
+// one recurrence launch; above 64 KB of dynamic LDS the kernel's limit is raised first
+template <typename K>
+static int gru_launch(K kernel, int grid, int threads, size_t lds, hipStream_t st, const GruSeqParams& p) {
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)lds);
         if (e != hipSuccess) { sed_set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return 3; }
     }
+    kernel<<<grid, threads, lds, st>>>(p);
     return 0;
 }
 
@@ -1391,59 +1024,22 @@ extern "C" int sed_gru_seq_fwd(int dtype, const float* gi, const float* bhh, con
     SED_REQUIRE((double)B * t * 8 * Hd * 4 < 4294967296.0, "B*t*8*Hd floats must stay below 4 GiB (32-bit buffer offsets)");
     GruSeqParams p{};
     p.gi = gi; p.bhh = bhh; p.wpack = pack_fwd; p.hseq = hseq; p.saved = saved; p.B = B; p.t = t; p.Hd = Hd;
-    // 8-row chunks (the 4-register kernels) for every batch size: four times the workgroups of the 32-row form, each with a quarter
-    // of the gate math, loads and stores per step and the whole recurrent matrix resident -- B = 32 runs on eight CUs instead of two
-    const char* rows_env = sed_getenv("SED_GRU_ROWS");
-    int crows = 8;                                                    // rows per chunk (SED_GRU_ROWS = 8 / 16 / 32 overrides; measured at
-                                                                      // B = 32: 32 rows 4.65 / 6.5 ms, 16 rows 2.5 / 3.25 ms, 8 rows 1.9 / 2.0 ms)
-    if (rows_env) crows = atoi(rows_env) == 32 ? 32 : atoi(rows_env) == 8 ? 8 : 16;
-    const bool half = crows == 16, quarter = crows == 8;
-    int grid = 2 * cdiv(B, crows);
     const int threads = 64 * (Hd / 32);
     hipStream_t st = (hipStream_t)stream;
-    const char* res_env = sed_getenv("SED_GRU_RESIDENT");
-#define SED_GRU_FWD(KERNEL, THREADS)                                          \
-    do {                                                                      \
-        if (int rc = set_lds<bf16_t>(&KERNEL, lds)) return rc;                \
-        KERNEL<<<grid, THREADS, lds, st>>>(p);                                \
-    } while (0)
-    if (gru_use_mfma16(dtype, Hd)) {           // 8-row chunks on the 16x16x32 instruction, recurrent matrix resident (r, z registers; n LDS)
+    int rc = 0;
+    if (gru_use_mfma16(dtype, Hd)) {           // 2-row chunks on the 16x16x32 instruction, recurrent matrix resident (r, z registers; n LDS)
         const size_t lds = (size_t)16 * (Hd + SeqLds<bf16_t>::PAD) * sizeof(bf16_t) + (size_t)8 * 16 * 64 * 16;
-        // SED_GRU_1BAR=1: one barrier per step (double-buffered three-row state image).  Measured NEUTRAL (4.4358 / 4.4449 against 4.4382 /
-        // 4.4365 ms per CRNN step, profiles/r06_o_ab_gru_one_barrier.txt): the step is the MFMA chain + the gate math, not its barriers.
-        const char* b1 = sed_getenv("SED_GRU_1BAR");
-        if (gru16_rows() == 2) {
-            grid = 2 * cdiv(B, 2);
-            if (b1 && b1[0] == '1') SED_GRU_FWD(gru_seq_fwd16h_kernel<true>, 512);
-            else SED_GRU_FWD(gru_seq_fwd16h_kernel<false>, 512);
-        }
-        else if (gru16_rows() == 4) { grid = 2 * cdiv(B, 4); SED_GRU_FWD(gru_seq_fwd16_kernel<1>, 512); }
-        else SED_GRU_FWD(gru_seq_fwd16_kernel<2>, 512);
-    } else if (dtype == SED_BF16 && Hd == 256 && !(res_env && res_env[0] == '0')) {       // recurrent matrix resident on the CU
-        const size_t lds = (size_t)32 * (Hd + SeqLds<bf16_t>::PAD) * sizeof(bf16_t) + (size_t)8 * 16 * 64 * 16;
-        if (res_env && res_env[0] == '1') {      // (n gate in LDS, r / z streamed: the intermediate form, kept for A/B runs)
-            if (quarter) SED_GRU_FWD((gru_seq_fwd_kernel<bf16_t, true, 4>), threads);
-            else if (half) SED_GRU_FWD((gru_seq_fwd_kernel<bf16_t, true, 8>), threads);
-            else SED_GRU_FWD((gru_seq_fwd_kernel<bf16_t, true, 16>), threads);
-        } else {
-            if (quarter) SED_GRU_FWD(gru_seq_fwd_res_kernel<4>, 512);
-            else if (half) SED_GRU_FWD(gru_seq_fwd_res_kernel<8>, 512);
-            else SED_GRU_FWD(gru_seq_fwd_res_kernel<16>, 512);
-        }
-    } else if (dtype == SED_BF16) {
+        rc = gru_launch(&gru_seq_fwd16h_kernel, 2 * cdiv(B, 2), 512, lds, st, p);
+    } else if (dtype == SED_BF16) {            // 8-row chunks: the h image keeps the MFMA's 32 rows, 8 of them live
         const size_t lds = (size_t)32 * (Hd + SeqLds<bf16_t>::PAD) * sizeof(bf16_t);
-        if (quarter) SED_GRU_FWD((gru_seq_fwd_kernel<bf16_t, false, 4>), threads);
-        else if (half) SED_GRU_FWD((gru_seq_fwd_kernel<bf16_t, false, 8>), threads);
-        else SED_GRU_FWD((gru_seq_fwd_kernel<bf16_t, false, 16>), threads);
+        rc = gru_launch(&gru_seq_fwd_kernel<bf16_t>, 2 * cdiv(B, 8), threads, lds, st, p);
     } else if (dtype == SED_F32) {
         const size_t lds = (size_t)32 * (Hd + SeqLds<float>::PAD) * sizeof(float);
-        if (quarter) SED_GRU_FWD((gru_seq_fwd_kernel<float, false, 4>), threads);
-        else if (half) SED_GRU_FWD((gru_seq_fwd_kernel<float, false, 8>), threads);
-        else SED_GRU_FWD((gru_seq_fwd_kernel<float, false, 16>), threads);
-#undef SED_GRU_FWD
+        rc = gru_launch(&gru_seq_fwd_kernel<float>, 2 * cdiv(B, 8), threads, lds, st, p);
     } else {
         SED_REQUIRE(false, "bad dtype");
     }
+    if (rc) return rc;
     SED_LAUNCH_CHECK();
     return 0;
 }
@@ -1457,59 +1053,23 @@ extern "C" int sed_gru_seq_bwd(int dtype, const float* dhseq, const float* hseq,
     GruSeqParams p{};
     p.dhseq = dhseq; p.hseq = const_cast<float*>(hseq); p.saved = const_cast<float*>(saved); p.wpack = pack_bwd;
     p.dgi = dgi; p.dgh = dgh; p.B = B; p.t = t; p.Hd = Hd;
-    // 8-row chunks (the 4-register kernels) for every batch size: four times the workgroups of the 32-row form, each with a quarter
-    // of the gate math, loads and stores per step and the whole recurrent matrix resident -- B = 32 runs on eight CUs instead of two
-    const char* rows_env = sed_getenv("SED_GRU_ROWS");
-    int crows = 8;                                                    // rows per chunk (SED_GRU_ROWS = 8 / 16 / 32 overrides; measured at
-                                                                      // B = 32: 32 rows 4.65 / 6.5 ms, 16 rows 2.5 / 3.25 ms, 8 rows 1.9 / 2.0 ms)
-    if (rows_env) crows = atoi(rows_env) == 32 ? 32 : atoi(rows_env) == 8 ? 8 : 16;
-    const bool half = crows == 16, quarter = crows == 8;
-    int grid = 2 * cdiv(B, crows);
     const int threads = 64 * (Hd / 32);
     hipStream_t st = (hipStream_t)stream;
-    const char* res_env = sed_getenv("SED_GRU_RESIDENT");
-#define SED_GRU_BWD(KERNEL)                                                   \
-    do {                                                                      \
-        if (int rc = set_lds<bf16_t>(&KERNEL, lds)) return rc;                \
-        KERNEL<<<grid, threads, lds, st>>>(p);                                \
-    } while (0)
-    if (gru_use_mfma16(dtype, Hd)) {           // 16x16x32 form: 16 of a wave's 48 operator fragments in LDS (beside the 16-row dgh image), 32 in registers
+    int rc = 0;
+    if (gru_use_mfma16(dtype, Hd)) {           // 16 of a wave's 48 operator fragments in LDS (beside the 16-row dgh image), 32 in registers
         const size_t lds = (size_t)16 * (3 * Hd + SeqLds<bf16_t>::PAD) * sizeof(bf16_t) + (size_t)8 * 16 * 64 * 16;
-        const char* b1 = sed_getenv("SED_GRU_1BAR");
-        if (gru16_rows() == 2) {
-            grid = 2 * cdiv(B, 2);
-            if (b1 && b1[0] == '1') SED_GRU_BWD((gru_seq_bwd16h_kernel<16, true>));
-            else SED_GRU_BWD((gru_seq_bwd16h_kernel<16, false>));
-        }
-        else if (gru16_rows() == 4) { grid = 2 * cdiv(B, 4); SED_GRU_BWD((gru_seq_bwd16_kernel<16, 1>)); }
-        else SED_GRU_BWD((gru_seq_bwd16_kernel<16, 2>));
-    } else if (dtype == SED_BF16 && Hd == 256 && !(res_env && res_env[0] == '0')) {       // 13 of a wave's 48 operator fragments in LDS
-        const size_t lds = (size_t)crows * (3 * Hd + SeqLds<bf16_t>::PAD) * sizeof(bf16_t) +
-                           (size_t)8 * (quarter ? 17 : half ? 16 : 13) * 64 * 16;
-        if (res_env && res_env[0] == '1') {
-            if (quarter) SED_GRU_BWD((gru_seq_bwd_kernel<bf16_t, 4, 17>));
-            else if (half) SED_GRU_BWD((gru_seq_bwd_kernel<bf16_t, 8, 16>));
-            else SED_GRU_BWD((gru_seq_bwd_kernel<bf16_t, 16, 13>));
-        } else {                                 // + fragments in registers: 23 (32-row chunks), 44 (16 rows), all 48 (8 rows) never leave the CU
-            if (quarter) SED_GRU_BWD((gru_seq_bwd_kernel<bf16_t, 4, 17, 31>));
-            else if (half) SED_GRU_BWD((gru_seq_bwd_kernel<bf16_t, 8, 16, 28>));
-            else SED_GRU_BWD((gru_seq_bwd_kernel<bf16_t, 16, 13, 10>));
-        }
-    } else if (dtype == SED_BF16) {
-        const size_t lds = (size_t)crows * (3 * Hd + SeqLds<bf16_t>::PAD) * sizeof(bf16_t);
-        if (quarter) SED_GRU_BWD((gru_seq_bwd_kernel<bf16_t, 4, 0>));
-        else if (half) SED_GRU_BWD((gru_seq_bwd_kernel<bf16_t, 8, 0>));
-        else SED_GRU_BWD((gru_seq_bwd_kernel<bf16_t, 16, 0>));
+        rc = gru_launch(&gru_seq_bwd16h_kernel, 2 * cdiv(B, 2), threads, lds, st, p);
+    } else if (dtype == SED_BF16) {            // 8-row dgh image
+        const size_t lds = (size_t)8 * (3 * Hd + SeqLds<bf16_t>::PAD) * sizeof(bf16_t);
+        rc = gru_launch(&gru_seq_bwd_kernel<bf16_t>, 2 * cdiv(B, 8), threads, lds, st, p);
     } else if (dtype == SED_F32) {
-        const size_t lds = (size_t)crows * (3 * Hd + SeqLds<float>::PAD) * sizeof(float);
+        const size_t lds = (size_t)8 * (3 * Hd + SeqLds<float>::PAD) * sizeof(float);
         SED_REQUIRE(lds <= 160 * 1024, "hidden size too large for the fp32 recurrence");
-        if (quarter) SED_GRU_BWD((gru_seq_bwd_kernel<float, 4, 0>));
-        else if (half) SED_GRU_BWD((gru_seq_bwd_kernel<float, 8, 0>));
-        else SED_GRU_BWD((gru_seq_bwd_kernel<float, 16, 0>));
-#undef SED_GRU_BWD
+        rc = gru_launch(&gru_seq_bwd_kernel<float>, 2 * cdiv(B, 8), threads, lds, st, p);
     } else {
         SED_REQUIRE(false, "bad dtype");
     }
+    if (rc) return rc;
     SED_LAUNCH_CHECK();
     return 0;
 }

@@ -15,6 +15,8 @@ happens in the HIP kernels.  There is no CPU fallback.
 """
 from __future__ import annotations
 
+import ctypes as _C
+import os as _os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -424,14 +426,13 @@ class CnnEngine(OptimizerExtMixin):
 
 
     def _plan_gru(self, B, t, C, dev):
-        """Buffers of the recurrent head; R = B*t rows, Rp = R padded to 4 (16-byte aligned GEMM rows)."""
+        """Buffers of the recurrent head; R = B*t rows."""
         lib, Hd = self.lib, self.Hd
         if C % 4:
             raise ValueError("the GRU head needs a channel count that is a multiple of 4")
         f32 = dict(dtype=torch.float32, device=dev)
         R = B * t
-        Rp = (R + 3) // 4 * 4
-        g = dict(R=R, Rp=Rp)
+        g = dict(R=R)
         g["m"] = torch.empty((R, C), **f32)
         g["gi"] = torch.empty((R, 6 * Hd), **f32)
         g["hseq"] = torch.empty((R, 2 * Hd), **f32)
@@ -440,10 +441,6 @@ class CnnEngine(OptimizerExtMixin):
         g["dhseq"] = torch.empty((R, 2 * Hd), **f32)
         g["dgi"] = torch.empty((R, 6 * Hd), **f32)
         g["dgh"] = torch.empty((R, 6 * Hd), **f32)
-        g["dgiT"] = torch.zeros((6 * Hd, Rp), **f32)
-        g["dghT"] = torch.zeros((6 * Hd, Rp), **f32)
-        g["mT"] = torch.zeros((C, Rp), **f32)
-        g["hprevT"] = torch.zeros((2 * Hd, Rp), **f32)
         g["wihT"] = torch.empty((C, 6 * Hd), **f32)
         g["dm"] = torch.empty((R, C), **f32)
         g["bhh"] = torch.empty((2, 3 * Hd), **f32)
@@ -452,19 +449,13 @@ class CnnEngine(OptimizerExtMixin):
         g["pack_b"] = torch.empty(n, dtype=self.tdtype, device=dev)
         # split-K of the weight-gradient GEMMs (K = B*t rows): SED_GRU_KSPLIT, read here -- when the plan is built, like the other engine-side
         # SED_* knobs -- and kept with the plan, because the workspace below is sized for it
-        import os as _os
         g["ksplit"] = max(1, int(_os.environ.get("SED_GRU_KSPLIT", "64")))
         ws = max(lib.sed_gemm_nt_ws_floats(3 * Hd, C, g["ksplit"]), lib.sed_gemm_nt_ws_floats(3 * Hd, Hd, g["ksplit"]),
                  lib.sed_gemm_tn_ws_floats(3 * Hd, C, g["ksplit"]), lib.sed_gemm_tn_ws_floats(3 * Hd, Hd, g["ksplit"]))
-        g["ws"] = torch.empty(max(1, ws), **f32)
-        # the four weight-gradient products in one launch (sed_gemm_tn_batch) need a workspace each.  SED_GRU_TN_BATCH=0: four calls (A/B).
-        g["tn_batch"] = _os.environ.get("SED_GRU_TN_BATCH", "1") != "0"
-        g["ws4"] = [torch.empty(max(1, ws), **f32) for _ in range(4)] if g["tn_batch"] else None
+        # the BPTT tail's weight / bias gradients come straight from the row-major gate gradients, all four products in one launch
+        # (sed_gemm_tn_batch: reduction index on the rows, shifted hidden-state rows, column sums as a by-product): a workspace each
+        g["ws4"] = [torch.empty(max(1, ws), **f32) for _ in range(4)]
         g["tn_desc"] = (L.GemmTnDesc * 4)()
-        # Round 6: the BPTT tail's weight / bias gradients straight from the row-major gate gradients (sed_gemm_tn: reduction index on the
-        # rows, shifted hidden-state rows, column sums as a by-product) -- no transposes, no separate bias sums.  SED_GRU_TN=0: the
-        # transpose + sed_gemm_nt + sed_row_sums form (A/B).
-        g["tn"] = _os.environ.get("SED_GRU_TN", "1") != "0"
         return g
 
     GRU_DIRS = ("", "_reverse")
@@ -492,7 +483,7 @@ class CnnEngine(OptimizerExtMixin):
         lib, dt, st, Hd, g = self.lib, self.dt, _stream(), self.Hd, p.gru
         B, t = p.B, p.t_out
         Cl = self.cfg[-1][0]
-        R, Rp = g["R"], g["Rp"]
+        R = g["R"]
         self._tag = "gru"
         self._k("sed_head_bwd", lib.sed_head_bwd, L.SED_F32, L.ptr(src), L.ptr(g["fc_m"]), L.ptr(P["event_fc.weight"]),
                 L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(g["dhseq"]), L.ptr(p.head_ws), B, t, 1,
@@ -502,54 +493,21 @@ class CnnEngine(OptimizerExtMixin):
         self._k("sed_gru_seq_bwd", lib.sed_gru_seq_bwd, dt, L.ptr(g["dhseq"]), L.ptr(g["hseq"]), L.ptr(g["saved"]),
                 L.ptr(g["pack_b"]), L.ptr(g["dgi"]), L.ptr(g["dgh"]), B, t, Hd, st)
         ks = max(1, min(g["ksplit"], R // 256))
-        if g["tn"] and g["tn_batch"]:
-            # dW_ih = dgi_d^T . m (+ db_ih = column sums of dgi_d);  dW_hh = dgh_d^T . h_prev (+ db_hh), both directions: ONE product
-            # launch and ONE reduction launch (twelve launches as four sed_gemm_tn calls)
-            ds = g["tn_desc"]
-            for d, sfx in enumerate(self.GRU_DIRS):
-                for j, (a, b, ldb, wname, bname, n, shift) in enumerate((
-                        (g["dgi"].data_ptr() + 4 * d * 3 * Hd, L.ptr(g["m"]), Cl, "gru.weight_ih_l0", "gru.bias_ih_l0", Cl, 0),
-                        (g["dgh"].data_ptr() + 4 * d * 3 * Hd, g["hseq"].data_ptr() + 4 * d * Hd, 2 * Hd, "gru.weight_hh_l0", "gru.bias_hh_l0", Hd,
-                         1 if d == 0 else -1))):
-                    e = ds[2 * d + j]
-                    e.A, e.B, e.C, e.colsum = a, b, L.ptr(G[wname + sfx]), L.ptr(G[bname + sfx])
-                    e.workspace = L.ptr(g["ws4"][2 * d + j]) if ks > 1 else None
-                    e.lda, e.ldb, e.ldc, e.M, e.N, e.K, e.seq, e.shift, e.ksplit = 6 * Hd, ldb, n, 3 * Hd, n, R, t, shift, ks
-            import ctypes as _C
-            self._k("sed_gemm_tn_batch", lib.sed_gemm_tn_batch, dt, _C.cast(ds, _C.c_void_p), 4, st)
-            for d, sfx in enumerate(self.GRU_DIRS):
-                self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P["gru.weight_ih_l0" + sfx]), Cl,
-                        g["wihT"].data_ptr() + 4 * d * 3 * Hd, 6 * Hd, 3 * Hd, Cl, 3 * Hd, 0, st)
-        elif g["tn"]:
-            for d, sfx in enumerate(self.GRU_DIRS):
-                ws = L.ptr(g["ws"]) if ks > 1 else None
-                # dW_ih = dgi_d^T . m (+ db_ih = column sums of dgi_d);  dW_hh = dgh_d^T . h_prev (+ db_hh): h_prev = hseq shifted by one
-                # step inside each clip's sequence (forward direction looks one step back, reverse one step ahead)
-                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, g["dgi"].data_ptr() + 4 * d * 3 * Hd, 6 * Hd, L.ptr(g["m"]), Cl,
-                        L.ptr(G["gru.weight_ih_l0" + sfx]), Cl, L.ptr(G["gru.bias_ih_l0" + sfx]), 3 * Hd, Cl, R, t, 0, ks, ws, st)
-                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, g["dgh"].data_ptr() + 4 * d * 3 * Hd, 6 * Hd, g["hseq"].data_ptr() + 4 * d * Hd,
-                        2 * Hd, L.ptr(G["gru.weight_hh_l0" + sfx]), Hd, L.ptr(G["gru.bias_hh_l0" + sfx]), 3 * Hd, Hd, R, t,
-                        1 if d == 0 else -1, ks, ws, st)
-                self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P["gru.weight_ih_l0" + sfx]), Cl,
-                        g["wihT"].data_ptr() + 4 * d * 3 * Hd, 6 * Hd, 3 * Hd, Cl, 3 * Hd, 0, st)
-        else:
-            # (round-4 form) transposes so that the B*t reduction axis is contiguous
-            self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(g["dgi"]), 6 * Hd, L.ptr(g["dgiT"]), Rp, R, 6 * Hd, R, 0, st)
-            self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(g["dgh"]), 6 * Hd, L.ptr(g["dghT"]), Rp, R, 6 * Hd, R, 0, st)
-            self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(g["m"]), Cl, L.ptr(g["mT"]), Rp, R, Cl, R, 0, st)
-        for d, sfx in enumerate(self.GRU_DIRS if not g["tn"] else ()):
-            # h_prev of every step, transposed: forward direction looks one step back, reverse one step ahead
-            self._k("sed_transpose_shift", lib.sed_transpose_shift, g["hseq"].data_ptr() + 4 * d * Hd, 2 * Hd,
-                    g["hprevT"].data_ptr() + 4 * d * Hd * Rp, Rp, R, Hd, t, 1 if d == 0 else -1, st)
-            a_gi = g["dgiT"].data_ptr() + 4 * d * 3 * Hd * Rp
-            a_gh = g["dghT"].data_ptr() + 4 * d * 3 * Hd * Rp
-            ws = L.ptr(g["ws"]) if ks > 1 else None
-            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, a_gi, Rp, L.ptr(g["mT"]), Rp, None,
-                    L.ptr(G["gru.weight_ih_l0" + sfx]), Cl, 3 * Hd, Cl, R, ks, ws, st)
-            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, a_gh, Rp, g["hprevT"].data_ptr() + 4 * d * Hd * Rp, Rp, None,
-                    L.ptr(G["gru.weight_hh_l0" + sfx]), Hd, 3 * Hd, Hd, R, ks, ws, st)
-            self._k("sed_row_sums", lib.sed_row_sums, a_gi, Rp, L.ptr(G["gru.bias_ih_l0" + sfx]), 3 * Hd, R, st)
-            self._k("sed_row_sums", lib.sed_row_sums, a_gh, Rp, L.ptr(G["gru.bias_hh_l0" + sfx]), 3 * Hd, R, st)
+        # dW_ih = dgi_d^T . m (+ db_ih = column sums of dgi_d);  dW_hh = dgh_d^T . h_prev (+ db_hh), both directions: ONE product
+        # launch and ONE reduction launch.  h_prev = hseq shifted by one step inside each clip's sequence (the forward direction looks
+        # one step back, the reverse one step ahead)
+        ds = g["tn_desc"]
+        for d, sfx in enumerate(self.GRU_DIRS):
+            for j, (a, b, ldb, wname, bname, n, shift) in enumerate((
+                    (g["dgi"].data_ptr() + 4 * d * 3 * Hd, L.ptr(g["m"]), Cl, "gru.weight_ih_l0", "gru.bias_ih_l0", Cl, 0),
+                    (g["dgh"].data_ptr() + 4 * d * 3 * Hd, g["hseq"].data_ptr() + 4 * d * Hd, 2 * Hd, "gru.weight_hh_l0", "gru.bias_hh_l0", Hd,
+                     1 if d == 0 else -1))):
+                e = ds[2 * d + j]
+                e.A, e.B, e.C, e.colsum = a, b, L.ptr(G[wname + sfx]), L.ptr(G[bname + sfx])
+                e.workspace = L.ptr(g["ws4"][2 * d + j]) if ks > 1 else None
+                e.lda, e.ldb, e.ldc, e.M, e.N, e.K, e.seq, e.shift, e.ksplit = 6 * Hd, ldb, n, 3 * Hd, n, R, t, shift, ks
+        self._k("sed_gemm_tn_batch", lib.sed_gemm_tn_batch, dt, _C.cast(ds, _C.c_void_p), 4, st)
+        for d, sfx in enumerate(self.GRU_DIRS):
             self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P["gru.weight_ih_l0" + sfx]), Cl,
                     g["wihT"].data_ptr() + 4 * d * 3 * Hd, 6 * Hd, 3 * Hd, Cl, 3 * Hd, 0, st)
         if on_group_done is not None:

@@ -118,6 +118,44 @@ def test_every_kernel_source_is_in_the_makefile():
     assert not missing, f"in csrc/ but not in the Makefile's SRCS: {missing}"
 
 
+def test_knob_table_lists_the_variables_the_sources_read():
+    """INTEGRATION.md section 5 is the one list of SED_* environment variables: its first column equals the names the library passes to
+    sed_getenv / getenv (csrc/*.hip, *.h) together with the names the package's Python reads from os.environ, and a row says "library"
+    in its reader column exactly when the library reads the name -- a knob added or removed without its row fails here."""
+    pkg = os.path.join(ROOT, "soundeventdetection-pytorch_amd")
+    csrc = os.path.join(pkg, "csrc")
+    c_names = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")):
+            c_names |= set(re.findall(r'getenv\(\s*"(SED_[A-Z0-9_]+)"', open(os.path.join(csrc, f)).read()))
+    py_names = set()
+    for dp, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                txt = open(os.path.join(dp, f)).read()
+                py_names |= set(re.findall(r'environ(?:\.get\(|\[)\s*["\'](SED_[A-Z0-9_]+)["\']', txt))
+                py_names |= set(re.findall(r'getenv\(\s*["\'](SED_[A-Z0-9_]+)["\']', txt))
+    assert len(c_names) >= 20 and len(py_names) >= 5, "the patterns no longer find the reads"
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc[doc.index("## 5. Knobs"):]
+    section = section[:section.index("\n## ", 5)] if "\n## " in section[5:] else section
+    rows = {}
+    for ln in section.split("\n"):
+        m = re.match(r"\|\s*`(SED_[A-Z0-9_]+)`\s*\|", ln)
+        if m:
+            assert m.group(1) not in rows, f"{m.group(1)} has two rows"
+            rows[m.group(1)] = [c.strip() for c in ln.strip().strip("|").split("|")]
+    read = c_names | py_names
+    assert sorted(set(rows) - read) == [], "in the table but read nowhere"
+    assert sorted(read - set(rows)) == [], "read by the sources but not in the table"
+    for name, cells in rows.items():
+        assert len(cells) == 5, f"{name}: a row has five columns"
+        who = cells[2]
+        assert ("library" in who) == (name in c_names), f"{name}: the reader column and csrc/ disagree about the library"
+        other = who.replace("library, cached until `sed_config_reload`", "").strip(" ;")
+        assert bool(other) == (name in py_names), f"{name}: the reader column and the package's Python disagree"
+
+
 def test_metrics_match_reference_golden(sed):
     mu = importlib.import_module("soundeventdetection-pytorch_amd.utils.metric_utils")
     g = load_golden("g5_metrics.npz")

@@ -1,6 +1,6 @@
 """GPU: the recurrent half of the CRNN (csrc/sed_gru.hip) element by element against float64, through the C ABI -- sed_gemm_nt,
 sed_gemm_tn / sed_gemm_tn_batch, sed_transpose_shift, sed_row_sums and sed_gru_pack_weights + sed_gru_seq_fwd + sed_gru_seq_bwd in
-every form the library can be switched to.  tests/test_gpu_crnn.py keeps the whole-sequence / whole-model (norm) checks.
+both forms the library has.  tests/test_gpu_crnn.py keeps the whole-sequence / whole-model (norm) checks.
 
 Reference: float64 (torch, on the device) on THE OPERANDS THE KERNEL READS.  In SED_BF16 the GEMMs and the recurrence round their
 fp32 operands to bf16 (round to nearest even) before the product; the reference rounds the same values the same way (torch's
@@ -49,21 +49,19 @@ SAFE = 4 over the operation counts below; nothing was set from a measurement.
                  M .. lda - 1 / N .. ldb - 1 of a TN operand, the rows of B a shift excludes) is NaN inside the allocation: a
                  finite in-gate result proves it was not used.  Nothing here runs out of its allocation.
 
-Forms (the case ids name them): gemm_nt / gemm_tn fp32 and bf16, split and unsplit; the recurrence: generic fp32 and bf16 kernels
-for Hd = 32 .. 256 (1 .. 8 waves) in 8-, 16- and 32-row chunks (SED_GRU_ROWS), and for bf16 / Hd = 256 the two-row 16x16x32 form
-(default), its one-barrier variant (SED_GRU_1BAR=1), the 4- and 8-row 16x16x32 forms (SED_GRU16_ROWS), the resident 32x32x16
-kernels (SED_GRU_MFMA16=0; SED_GRU_ROWS = 16, 32), the n-gate-resident form (SED_GRU_RESIDENT=1) and the streamed generic kernel
-(SED_GRU_RESIDENT=0).  The batch sizes put B = chunk - 1, chunk, chunk + 1 against every chunk size; t = 1 (no prefetch), 2, 33.
+Forms (the case ids name them): gemm_nt / gemm_tn fp32 and bf16, split and unsplit; the recurrence: the generic fp32 and bf16
+kernels for Hd = 32 .. 256 (1 .. 8 waves) in 8-row chunks, and for bf16 / Hd = 256 the two-row 16x16x32 form.  The batch sizes put
+B = chunk - 1, chunk, chunk + 1 against both chunk sizes; t = 1 (no prefetch), 2, 33.
 
 Measured max err / gate on the MI355X (summarised at the end of the module with -s; 0.25 = the operation count without its safety
 factor):
   gemm_nt        fp32 0.16 (split 0.023), bf16 0.095 (split 0.009)
   gemm_tn        fp32 C 0.045 (split 0.012), bf16 C 0.014 (split 0.004); colsum 0.027 (split 0.010) in both modes
   row_sums       0.014;  transposes, batch against single calls, saved == NULL against the training call: bit for bit
-  gru forward    every form and Hd, fp32 and bf16 alike: hseq 0.013 .. 0.019, r and z 0.06 .. 0.10, n 0.037 .. 0.045,
-                 W_hn h + b_hn 0.001 .. 0.028
-  gru backward   every form: dgi / dgh r 0.09 .. 0.12, z 0.14 .. 0.17, n 0.11 .. 0.13, n * r 0.10 .. 0.13
-No kernel missed its gate; no form rounds anywhere else than the generic kernel.  The module runs in about 6 s.
+  gru forward    both forms, every Hd, fp32 and bf16 alike: hseq 0.018 .. 0.019, r and z 0.07 .. 0.09, n 0.041,
+                 W_hn h + b_hn 0.002 .. 0.028
+  gru backward   both forms: dgi / dgh r 0.10 .. 0.12, z 0.15 .. 0.16, n 0.11 .. 0.13, n * r 0.12
+No kernel missed its gate; the two-row form rounds nowhere else than the generic kernel.  The module runs in about 5 s.
 """
 import ctypes
 import importlib
@@ -82,7 +80,6 @@ NAN = float("nan")
 WS_GUARD = 256                  # NaN floats behind every workspace
 EXTRA_ROWS = 3                  # NaN rows behind B * t in every recurrence output
 RATIOS = {}                     # (group, check) -> max err / gate
-GRU_ENV = ("SED_GRU16_ROWS", "SED_GRU_MFMA16", "SED_GRU_RESIDENT", "SED_GRU_ROWS", "SED_GRU_1BAR")
 
 
 @pytest.fixture(scope="module")
@@ -583,52 +580,20 @@ def run_gru(L, dt, grp, Hd, B, t, seed):
     gru_backward_checks(dt, grp, where, Hd, dh.view(B, t, 2, Hd), whh, hs, sv, dgi[:R].view(B, t, 2, 3, Hd), dgh[:R].view(B, t, 2, 3, Hd))
 
 
-def set_form(L, monkeypatch, env):
-    for name in GRU_ENV:
-        monkeypatch.delenv(name, raising=False)
-    for name, value in env.items():
-        monkeypatch.setenv(name, value)
-    L.lib().sed_config_reload()
-
-
-# generic kernels, 8-row chunks (the default of everything but bf16 / Hd = 256): every Hd meets an odd B, B = 7, 8, 9 and t = 1, 2, 33
+# generic kernels, 8-row chunks (everything but bf16 / Hd = 256): every Hd meets an odd B, B = 7, 8, 9 and t = 1, 2, 33
 GRU_GRID = {32: [(1, 1), (7, 33), (8, 2)], 64: [(9, 33), (2, 1), (33, 2)], 96: [(3, 33), (7, 2), (17, 1)], 128: [(8, 33), (9, 2), (1, 33)],
             160: [(7, 33), (33, 1), (2, 2)], 192: [(9, 33), (8, 1), (3, 2)], 224: [(17, 33), (7, 1), (8, 2)], 256: [(33, 33), (9, 2), (7, 1)]}
 
 
 @pytest.mark.parametrize("Hd", sorted(GRU_GRID))
 @pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
-def test_gru_hidden_sizes(L, monkeypatch, dt, Hd):
-    """Hd / 32 = 1 .. 8 waves per workgroup, default configuration: generic kernels in 8-row chunks; bf16 / Hd = 256 takes the two-row
-    16x16x32 form (chunk 2: B = 1, 2, 3 added)"""
-    set_form(L, monkeypatch, {})
+def test_gru_hidden_sizes(L, dt, Hd):
+    """Hd / 32 = 1 .. 8 waves per workgroup: generic kernels in 8-row chunks; bf16 / Hd = 256 takes the two-row 16x16x32 form
+    (chunk 2: B = 1, 2, 3 added)"""
     two_row = dt == BF16 and Hd == 256
     grp = "gru " + NAME[dt] + (" 16x16x32 2-row" if two_row else " generic")
     for i, (B, t) in enumerate(GRU_GRID[Hd] + ([(1, 33), (2, 2), (3, 33)] if two_row else [])):
         run_gru(L, dt, grp, Hd, B, t, 600 + Hd + i)
-
-
-# bf16 / Hd = 256: every form the library keeps.  (env, chunk rows, name); B = chunk - 1, chunk, chunk + 1 and t = 1, 2, 33 in each
-GRU_FORMS_256 = [({"SED_GRU16_ROWS": "4"}, 4, "16x16x32 4-row"), ({"SED_GRU16_ROWS": "8"}, 8, "16x16x32 8-row"),
-                 ({"SED_GRU_1BAR": "1"}, 2, "16x16x32 2-row one-barrier"), ({"SED_GRU_MFMA16": "0"}, 8, "32x32x16 resident 8-row"),
-                 ({"SED_GRU_RESIDENT": "0"}, 8, "streamed generic 8-row"), ({"SED_GRU_RESIDENT": "1"}, 8, "n-gate-resident 8-row"),
-                 ({"SED_GRU_ROWS": "16"}, 16, "32x32x16 resident 16-row"), ({"SED_GRU_ROWS": "32"}, 32, "32x32x16 resident 32-row")]
-
-
-@pytest.mark.parametrize("env,chunk,name", GRU_FORMS_256, ids=[f[2].replace(" ", "-") for f in GRU_FORMS_256])
-def test_gru_bf16_256_forms(L, monkeypatch, env, chunk, name):
-    set_form(L, monkeypatch, env)
-    for i, (B, t) in enumerate([(chunk - 1, 33), (chunk, 2), (chunk + 1, 33), (chunk + 1, 1)]):
-        run_gru(L, BF16, "gru bf16 " + name, 256, B, t, 700 + chunk + i)
-
-
-@pytest.mark.parametrize("rows", [16, 32])
-@pytest.mark.parametrize("dt,Hd", [(F32, 96), (BF16, 160)], ids=["f32-Hd96", "bf16-Hd160"])
-def test_gru_generic_chunk_rows(L, monkeypatch, dt, Hd, rows):
-    """SED_GRU_ROWS = 16 / 32: the generic kernels' larger chunks (NREG = 8 / 16), 3 and 5 waves"""
-    set_form(L, monkeypatch, {"SED_GRU_ROWS": str(rows)})
-    for i, (B, t) in enumerate([(rows - 1, 33), (rows, 2), (rows + 1, 33), (rows + 1, 1)]):
-        run_gru(L, dt, f"gru {NAME[dt]} generic {rows}-row", Hd, B, t, 800 + rows + i)
 
 
 def test_gru_refusals(L):
