@@ -362,6 +362,30 @@ int sed_logmel_crops(const float* bank, size_t bank_frames, const int* starts_ho
                      const int* starts, const float* mean, const float* std, float* out, int B,
                      int crop, int n_mels, void* stream);
 
+/* Log-mel batch augmentation (csrc/sed_augment.hip), this build only: crop gather + per-mel z-score as in sed_logmel_crops, then a
+ * circular time shift, an additive band gain, mixup with a partner sample and SpecAugment time / frequency masks, for features and
+ * labels, without an intermediate tensor.  Every decision is the caller's: row b of the int32 table tab [B][row_ints],
+ * row_ints = sed_logmel_augment_row_ints(n_tmask, n_fmask) = 4 + 2*(n_tmask + n_fmask), holds
+ *   start, shift, partner, lam (float bits), t0_0, w_0, ... (n_tmask pairs), f0_0, w_0, ... (n_fmask pairs).
+ * With T = crop, all feature arithmetic in fp32:
+ *   z_b[t][f]   = bank[start_b + t][f], with mean / std given (bank[start_b + t][f] - mean[f]) / std[f]
+ *   u_b[t][f]   = z_b[(t - shift_b) mod T][f] + gain[b][f]            (the shift wraps inside the crop; gain NULL = no term)
+ *   v_b         = u_b if partner_b == b, else lam_b * u_b + (1 - lam_b) * u_partner_b   (the partner's own start, shift, gain)
+ *   out[b][t][f] = mask_value if t lies in a time interval [t0, t0 + w) or f in a frequency interval of row b, else v_b[t][f]
+ *   r_b[t][k]   = events[start_b + (t - shift_b) mod T][k]
+ *   ev_out[b]   = r_b if partner_b == b, else max(r_b, r_p) (label_mix 0) or lam * r_b + (1 - lam) * r_p in double (label_mix 1);
+ *                 masks do not touch labels.  events NULL = no labels (K, ev_out ignored); the labels are a second small launch.
+ * bank fp32 [bank_frames][n_mels], events double [bank_frames][K], gain fp32 [B][n_mels], out fp32 [B][crop][n_mels], ev_out
+ * double [B][crop][K].  A plain (B, T, F) tensor is bank = x, start_b = b*T.  float4 loads / stores when n_mels % 4 == 0 and bank,
+ * gain and out are 16-byte aligned, element-wise otherwise.  tab_host is the HOST copy of tab.  Refused before any launch
+ * (non-zero): sizes <= 0, more than 8 masks of a kind, mean without std, events without ev_out or K <= 0, start + crop >
+ * bank_frames, shift outside [0, crop), partner outside [0, B), lam NaN or outside [0, 1], an interval with t0 < 0, w < 0 or
+ * t0 + w > crop (n_mels for the frequency ones), out overlapping bank or gain, ev_out overlapping events; last, a NULL out / tab. */
+int sed_logmel_augment_row_ints(int n_tmask, int n_fmask);
+int sed_logmel_augment(const float* bank, size_t bank_frames, const double* events, int K, const float* mean, const float* std,
+                       const int* tab_host, const int* tab, const float* gain, float mask_value, int label_mix, float* out,
+                       double* ev_out, int B, int crop, int n_mels, int n_tmask, int n_fmask, void* stream);
+
 /* ---- audio ingest: PCM decode + channel downmix + polyphase resampling (csrc/sed_resample.hip) ----
  * read_multichannel_audio (dataset/dataset_utils.py:65-91): what the reference does with soundfile's float64 decode, the channel
  * rule of :72-83 and librosa.resample, with scipy.signal.resample_poly(x, up, down)'s defaults (zero extension, Kaiser beta = 5)

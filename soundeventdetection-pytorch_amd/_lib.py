@@ -113,6 +113,8 @@ PROTOTYPES = {
     "sed_complex_augment_logmel": (_I, [_P, _Z, _P, _P, _P, _P, _P, _P, C.c_ulonglong, _P, _P, _P, _P, _P, _P, _I, _I,
                                         _I, _I, _P]),
     "sed_logmel_crops": (_I, [_P, _Z, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "sed_logmel_augment_row_ints": (_I, [_I, _I]),
+    "sed_logmel_augment": (_I, [_P, _Z, _P, _I, _P, _P, _P, _P, _P, _F, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sed_resample_plan": (_I, [_I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sed_resample_poly": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sed_mel_mean_fwd": (_I, [_I, _P, _P, _Z, _I, _I, _I, _P]),

@@ -98,7 +98,7 @@ def _read_train_data_to_memory(train_feature_paths, crop_size, balance_classes, 
 class SpectogramDataset(Dataset):
     def __init__(self, features_and_labels_dir, mean_std_file, val_descriptor, balance_classes=False,
                  augment_data=False, preprocessed_mode="Complex", cfg: SpectogramConfig = REF_NATIVE,
-                 device="cuda", noise_seed=0):
+                 device="cuda", noise_seed=0, spec_augment=None):
         assert preprocessed_mode in ["logMel", "Complex"], "Spectogram type should be either logmel or complex"
         assert not (preprocessed_mode == "logMel" and augment_data), "Can't perform augmentation in logMel spectograms"
         self.device = torch.device(device)
@@ -110,6 +110,10 @@ class SpectogramDataset(Dataset):
         self.augment_data = augment_data
         self.train_crop_size = cfg.train_crop_size
         self.noise_seed = int(noise_seed)
+        # this build only: a dataset.spectogram.augment.SpecAugmentConfig -- training batches are augmented on the log-mel
+        # features (both modes); transform() / get_validation_sampler() never are.  last_tab / last_gain: the last batch's tables
+        self.spec_augment = spec_augment
+        self.last_tab = self.last_gain = None
         self._noise_calls = 0
 
         d = _load(mean_std_file)
@@ -174,6 +178,14 @@ class SpectogramDataset(Dataset):
             starts_h[b, :len(st)] = st
             nmix_h[b] = len(st)
             nstd_h[b] = ns
+        if self.preprocessed_mode == "logMel" and self.spec_augment is not None:
+            # one call: gather + z-score + shift + band gain + mixup + masks, labels from the label bank alongside
+            from . import augment as A
+            std_mel = np.broadcast_to(np.asarray(self.std, dtype=np.float64), (cfg.mel_bins,))
+            self.last_tab, self.last_gain = A.draw(self.spec_augment, starts_h[:, 0], crop, cfg.mel_bins, std_mel=std_mel)
+            feats, ev = A.launch(self.bank, self.bank_frames, self.d_events, self.d_events.shape[1], self.d_mean, self.d_std,
+                                 self.last_tab, self.last_gain, self.spec_augment, B, crop, cfg.mel_bins, _stream())
+            return feats.view(B, 1, crop, cfg.mel_bins), ev
         dev = self.device
         starts_d = torch.from_numpy(starts_h).to(dev)
         out = torch.empty((B, 1, crop, cfg.mel_bins), dtype=torch.float32, device=dev)
@@ -203,6 +215,14 @@ class SpectogramDataset(Dataset):
             if bool((nmix_h > j).any()):
                 evj = self.d_events[st[:, j:j + 1] + ar[None, :]]
                 ev = torch.where(sel[:, None, None], torch.maximum(ev, evj), ev)
+        if self.spec_augment is not None:
+            # 'Complex' mode: a second launch over the complex kernel's log-mel output and the already-mixed labels
+            from . import augment as A
+            K = ev.shape[2]
+            self.last_tab, self.last_gain = A.draw(self.spec_augment, np.arange(B, dtype=np.int64) * crop, crop, cfg.mel_bins)
+            feats, ev = A.launch(out.view(B * crop, cfg.mel_bins), B * crop, ev.contiguous().view(B * crop, K), K, None, None,
+                                 self.last_tab, self.last_gain, self.spec_augment, B, crop, cfg.mel_bins, _stream())
+            return feats.view(B, 1, crop, cfg.mel_bins), ev
         return out, ev
 
     def __getitem__(self, idx):

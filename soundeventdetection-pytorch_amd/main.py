@@ -80,10 +80,46 @@ def build_event_parser():
     return p
 
 
+def build_augment_parser():
+    """The log-mel batch augmentation options (this build only), in a parser of their own like the event options."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--spec_augment", action="store_true", default=False,
+                   help="this build only: augment every log-mel training batch on the GPU (masks, shift, mixup, band gains); "
+                        "the flags below take effect only with it")
+    p.add_argument("--time_masks", type=int, default=2, help="--spec_augment: time masks per sample (0..8)")
+    p.add_argument("--time_mask_frames", type=int, default=4, help="--spec_augment: a time mask is 0..this many frames wide")
+    p.add_argument("--freq_masks", type=int, default=2, help="--spec_augment: frequency masks per sample (0..8)")
+    p.add_argument("--freq_mask_bins", type=int, default=8, help="--spec_augment: a frequency mask is 0..this many mel bins wide")
+    p.add_argument("--time_shift", action="store_true", default=False, help="--spec_augment: circular time shift inside the crop")
+    p.add_argument("--mixup_prob", type=float, default=0.0, help="--spec_augment: probability that a sample is mixed with a partner")
+    p.add_argument("--mixup_alpha", type=float, default=0.2, help="--spec_augment: lam = max(l, 1 - l), l ~ beta(alpha, alpha)")
+    p.add_argument("--soft_labels", action="store_true", default=False,
+                   help="--spec_augment: mixed labels are lam * y + (1 - lam) * y_partner instead of the maximum")
+    p.add_argument("--filter_augment", type=float, default=0.0,
+                   help="--spec_augment: probability of a piecewise-linear band gain (3..6 bands, -6..6 dB) per sample")
+    return p
+
+
 def build_full_parser():
-    """What main() parses: build_parser() and build_event_parser() together."""
-    return argparse.ArgumentParser(description="SED training on MI355X", parents=[build_parser(), build_event_parser()],
+    """What main() parses: build_parser(), build_event_parser() and build_augment_parser() together."""
+    return argparse.ArgumentParser(description="SED training on MI355X",
+                                   parents=[build_parser(), build_event_parser(), build_augment_parser()],
                                    conflict_handler="resolve")
+
+
+def spec_augment_config(args):
+    """The SpecAugmentConfig of --spec_augment and its parameters; None with the flag off (a Namespace built by hand may lack any
+    of them)."""
+    if not getattr(args, "spec_augment", False):
+        return None
+    from .dataset.spectogram.augment import SpecAugmentConfig
+    p = build_augment_parser()
+    g = {k: getattr(args, k, p.get_default(k)) for k in ("time_masks", "time_mask_frames", "freq_masks", "freq_mask_bins",
+                                                         "time_shift", "mixup_prob", "mixup_alpha", "soft_labels", "filter_augment")}
+    return SpecAugmentConfig(time_masks=g["time_masks"], time_mask_frames=g["time_mask_frames"], freq_masks=g["freq_masks"],
+                             freq_mask_bins=g["freq_mask_bins"], time_shift=bool(g["time_shift"]), mixup_prob=g["mixup_prob"],
+                             mixup_alpha=g["mixup_alpha"], label_mix="soft" if g["soft_labels"] else "max",
+                             filter_prob=g["filter_augment"])
 
 
 def event_eval_options(args, fps):
@@ -146,7 +182,8 @@ def get_spectogram_dataset_model_and_criterion(args, device):
         dataset = SpectogramDataset(feats_dir, mean_std, augment_data=args.augment_data,
                                     balance_classes=args.balance_classes,
                                     val_descriptor=_val_descriptor(args.val_descriptor),
-                                    preprocessed_mode=args.preprocess_mode, cfg=cfg, device=device)
+                                    preprocessed_mode=args.preprocess_mode, cfg=cfg, device=device,
+                                    spec_augment=spec_augment_config(args))
     model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel)
     model.set_precision(args.precision)
     if args.ckpt != "":
@@ -199,6 +236,17 @@ def validate_args(args):
             raise ValueError(f"--{name} must be >= 0 seconds, {getattr(args, name)} given")
     if getattr(args, "segment", 1.0) <= 0:
         raise ValueError(f"--segment must be > 0 seconds, {args.segment} given")
+    for name in ("time_masks", "time_mask_frames", "freq_masks", "freq_mask_bins", "mixup_prob", "mixup_alpha", "filter_augment"):
+        if not getattr(args, name, 0) >= 0:
+            raise ValueError(f"--{name} must be >= 0, {getattr(args, name)} given")
+    for name in ("mixup_prob", "filter_augment"):
+        if not getattr(args, name, 0.0) <= 1:
+            raise ValueError(f"--{name} is a probability in [0, 1], {getattr(args, name)} given")
+    if getattr(args, "spec_augment", False):
+        if args.train_features.lower() == "waveform":
+            raise ValueError("--spec_augment works on log-mel features: it needs --train_features Spectogram "
+                             "(there is no waveform-domain augmentation for the M5 model)")
+        spec_augment_config(args)           # the config's own checks (at most 8 masks of a kind, alpha > 0)
 
 
 def optimizer_options(args):
@@ -206,6 +254,16 @@ def optimizer_options(args):
     clip = float(getattr(args, "clip_grad_norm", 0.0))
     return {"weight_decay": float(getattr(args, "weight_decay", 0.0)), "decoupled_weight_decay": bool(getattr(args, "adamw", False)),
             "amsgrad": not getattr(args, "no_amsgrad", False), "max_grad_norm": clip if clip != 0.0 else None}
+
+
+def synthetic_batch_augment(args):
+    """train()'s batch_augment: the spectrogram datasets augment inside their own batch launch; the synthetic dataset hands plain
+    tensors over, so --spec_augment is applied to its device batch.  None otherwise."""
+    cfg = spec_augment_config(args)
+    if cfg is None or args.dataset_name.lower() != "synthetic" or args.train_features.lower() != "spectogram":
+        return None
+    from .dataset.spectogram.augment import LogMelAugment
+    return LogMelAugment(cfg)
 
 
 def get_dataset_and_model(args, device):
@@ -265,7 +323,8 @@ def main(argv=None):
         train_name += "_AD"
     train(model, dataloader, criterion, num_steps=args.num_train_steps,
           outputs_dir=os.path.join(args.outputs_root, train_name), device=device, lr=args.lr,
-          log_freq=args.log_freq, event_eval=event_eval_options(args, frames_per_second(args)), **optimizer_options(args))
+          log_freq=args.log_freq, event_eval=event_eval_options(args, frames_per_second(args)),
+          batch_augment=synthetic_batch_augment(args), **optimizer_options(args))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

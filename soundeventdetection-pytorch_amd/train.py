@@ -654,11 +654,13 @@ def summarize_validation(val_losses, recal_sets, precision_sets, APs):
 
 
 def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, device, *, weight_decay=0.0,
-          decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None, event_eval=None):
+          decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None, event_eval=None, batch_augment=None):
     """train.py:77-131.  `criterion` must be this package's WeightedBCE(multi_frame=True) (its
     recall_factor feeds the fused loss kernel).  The keyword-only optimizer options are FusedTrainer's (this build only; their
     defaults are the reference's Adam(amsgrad=True) without decay or clipping).  event_eval: None, or the keyword arguments of
-    eval_events (threshold ... collar_frames): the periodic evaluation then also logs that dict; None launches nothing new."""
+    eval_events (threshold ... collar_frames): the periodic evaluation then also logs that dict; None launches nothing new.
+    batch_augment: None, or a callable (features, labels) -> (features, labels) applied to every device batch before the step
+    (dataset.spectogram.augment.LogMelAugment for loaders that hand plain log-mel tensors over); validation never sees it."""
     check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -688,8 +690,11 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
         seen = 0
         for (batch_features, event_labels) in data_loader:
             seen += 1
-            loss = trainer.train_step(batch_features.to(dev, non_blocking=True).float(),
-                                      event_labels.to(dev, non_blocking=True).float())
+            batch_features = batch_features.to(dev, non_blocking=True).float()
+            event_labels = event_labels.to(dev, non_blocking=True).float()
+            if batch_augment is not None:
+                batch_features, event_labels = batch_augment(batch_features, event_labels)
+            loss = trainer.train_step(batch_features, event_labels)
             losses.append(loss.clone())              # device scalars (the step's loss buffer is reused): no host sync
             iterations += 1
             if iterations % log_freq == 0:
