@@ -257,6 +257,42 @@ int sed_interpolate(const float* pre, float* out, int B, int t, int K, int ratio
 int sed_bce_fwd_bwd(const float* pre, const float* target, float* loss, float* dpre,
                     float* loss_partial, int B, int t, int K, int ratio, int Tt, float recall_factor,
                     float grad_scale, void* stream);
+/* ---- weak-label (clip-level) loss: csrc/sed_weak.hip ------------------------------------------
+ * The frame probabilities of a clip are pooled over time into one clip probability per class and
+ * WeightedBCE is taken against the clip label, on pre [B][t][K] fp32 like sed_bce_fwd_bwd (the
+ * x`ratio` interpolate() is not materialised): with N = min(t*ratio, Tt) virtual frames, row i of
+ * pre stands for c_i = clamp(N - i*ratio, 0, ratio) frames; rows with c_i = 0 take no part (not in
+ * the max either) and get gradient exactly 0.  For one (b, k), x_i the logit, all in double:
+ *   p_i = 1/(1+exp(-x_i)), q_i = 1/(1+exp(x_i));  P the clip probability, Q = 1 - P from its own sums
+ *   SED_POOL_MAX     P = p_j, Q = q_j, j the smallest index of the largest x_i;   dP/dp_i = [i == j]
+ *   SED_POOL_MEAN    P = sum c_i p_i / N, Q = sum c_i q_i / N;                     dP/dp_i = c_i / N
+ *   SED_POOL_LINEAR  P = S2/S1, S1 = sum c_i p_i, S2 = sum c_i p_i^2, Q = sum c_i p_i q_i / S1;
+ *                    dP/dp_i = c_i (2 p_i - P) / S1   (S1 == 0: P = 0, Q = 1, gradient 0)
+ *   SED_POOL_EXP     P = sum c_i p_i e^{p_i} / E, E = sum c_i e^{p_i}, Q = sum c_i q_i e^{p_i} / E;
+ *                    dP/dp_i = c_i e^{p_i} (1 + p_i - P) / E
+ *   l = -(w Y max(ln P, -100) + (1 - Y) max(ln Q, -100)), loss = weight * mean over B*K of l,
+ *   dl/dP = -w Y / max(P, 1e-12) + (1 - Y) / max(Q, 1e-12),
+ *   dpre_i = weight * grad_scale / (B*K) * dl/dP * dP/dp_i * p_i q_i, rounded once to fp32.
+ * Every sum is taken in a fixed order without atomics (the same bits on every run); there is no
+ * host synchronisation, so the calls can be captured in a HIP graph.                             */
+#define SED_POOL_MAX 0
+#define SED_POOL_MEAN 1
+#define SED_POOL_LINEAR 2
+#define SED_POOL_EXP 3
+/* clip_prob [B][K] = P only (inference); one launch.                                             */
+int sed_clip_pool_fwd(const float* pre, float* clip_prob, int B, int t, int K, int ratio, int Tt,
+                      int mode, void* stream);
+/* target_frames == 0: target is the clip labels [B][K] and Tt only sets N.  target_frames == Tt:
+ * target is the strong [B][Tt][K] tensor and Y is the maximum over its first N frames, taken by the
+ * kernel.  Y may be soft.  clip_prob [B][K] and dpre [B][t][K] may be NULL.  accumulate = 1 adds to
+ * loss[0] and to dpre (one fp32 add per element) instead of overwriting them: the strong loss runs
+ * first and the weak one lands on top.  workspace: sed_weak_bce_ws_bytes() bytes, 8-byte aligned.
+ * Two launches.                                                                                  */
+size_t sed_weak_bce_ws_bytes(int B, int t, int K);
+int sed_weak_bce_fwd_bwd(const float* pre, const float* target, int target_frames, float* clip_prob,
+                         float* loss, float* dpre, int accumulate, int B, int t, int K, int ratio,
+                         int Tt, int mode, float recall_factor, float weight, float grad_scale,
+                         void* workspace, void* stream);
 /* Head backward: dfc_w [K][C], dfc_b [K] (overwritten) and dfeat [B][t][Wf][Cp] =
  * (dpre @ fc_w)/Wf broadcast over mel.  `dpre` is [B][t*ratio][K]: with ratio > 1 it is the
  * gradient w.r.t. the interpolate()d logits and the repeat-backward sum is folded in.  m is the

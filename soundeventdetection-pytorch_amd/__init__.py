@@ -11,8 +11,8 @@ from .models.spectogram_models import (Cnn_AvgPooling, ConvBlock, Crnn_AvgPoolin
                                        init_layer, interpolate)
 from .models.waveform_models import M5  # noqa: F401
 from .m5_engine import M5Engine  # noqa: F401
-from .utils.common import WeightedBCE  # noqa: F401
+from .utils.common import WeakBCE, WeightedBCE  # noqa: F401
 from . import train  # noqa: F401,E402
 from .train import FusedTrainer, FusedAdamAmsgrad  # noqa: F401,E402
 
-__all__ = ["M5", "Cnn_AvgPooling", "Crnn_AvgPooling", "ConvBlock", "WeightedBCE", "CnnEngine", "interpolate", "init_layer", "init_bn"]
+__all__ = ["M5", "Cnn_AvgPooling", "Crnn_AvgPooling", "ConvBlock", "WeightedBCE", "WeakBCE", "CnnEngine", "interpolate", "init_layer", "init_bn"]

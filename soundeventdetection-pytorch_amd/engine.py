@@ -50,6 +50,13 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def check_pooling(mode) -> int:
+    """The SED_POOL_* id of a pooling name of the weak-label loss (host only)."""
+    if mode not in L.POOL_MODES:
+        raise ValueError(f"unknown pooling {mode!r}: choose one of {', '.join(L.POOL_MODES)}")
+    return L.POOL_MODES[mode]
+
+
 @dataclass
 class _Layer:
     """One conv+BN layer of the plan."""
@@ -97,6 +104,8 @@ class _Plan:
     gru: dict = None                # buffers of the recurrent head (head == 'gru')
     keep: bool = False              # the last forward ran with keep_for_grad (input-gradient / eval-mode backward possible)
     dx_in: torch.Tensor = None      # (B, 1, T, F) fp32 input gradient of the Cin = 1 model path (the last backward(need_dx=True))
+    weak_ws: torch.Tensor = None    # workspace of the weak-label loss (csrc/sed_weak.hip), allocated at its first use
+    clip_prob: torch.Tensor = None  # (B, K) clip probabilities of the last weak-label loss / clip_probs()
 
 
 class KernelTimer:
@@ -701,16 +710,59 @@ class CnnEngine(OptimizerExtMixin):
         return out
 
     def loss_and_grad(self, p: _Plan, target: torch.Tensor, recall_factor: float, need_grad: bool = True,
-                      grad_scale: float = 1.0) -> torch.Tensor:
-        """WeightedBCE on the virtually interpolated logits; fills plan.dpre; returns plan.loss (1,)."""
-        if not (target.is_cuda and target.dtype == torch.float32 and target.dim() == 3):
-            raise ValueError("target must be a float32 CUDA tensor (B, T, K)")
+                      grad_scale: float = 1.0, weak=None) -> torch.Tensor:
+        """WeightedBCE on the virtually interpolated logits; fills plan.dpre; returns plan.loss (1,).
+        weak: None, or (mode, weight, only) -- the pooled clip-level loss of csrc/sed_weak.hip, mode one of max / mean / linear /
+        exp, scaled by weight.  only=False: the strong kernel runs as always, then the weak loss of the same (B, T, K) target is
+        added on top of plan.loss and plan.dpre.  only=True: the weak loss alone; the target may then be (B, K) clip labels.
+        None launches exactly what it always did."""
+        if weak is None:
+            if not (target.is_cuda and target.dtype == torch.float32 and target.dim() == 3):
+                raise ValueError("target must be a float32 CUDA tensor (B, T, K)")
+            target = target.contiguous()
+            self._strong_loss(p, target, recall_factor, need_grad, grad_scale)
+            return p.loss
+        mode, weight, only = weak
+        mode_id = check_pooling(mode)
+        if self.head == "none":
+            raise ValueError("the weak-label loss needs a model with a classification head")
+        if not (target.is_cuda and target.dtype == torch.float32 and target.dim() in ((2, 3) if only else (3,))):
+            raise ValueError("target must be a float32 CUDA tensor (B, T, K) or, for the weak loss alone, (B, K) clip labels")
+        if target.shape[0] != p.B or target.shape[-1] != self.K:
+            raise ValueError(f"target {tuple(target.shape)} does not fit {p.B} clips of {self.K} classes")
         target = target.contiguous()
+        if not only:
+            self._strong_loss(p, target, recall_factor, need_grad, grad_scale)
+        self._weak_bufs(p)
+        frames = target.shape[1] if target.dim() == 3 else 0
+        self._k("sed_weak_bce_fwd_bwd", self.lib.sed_weak_bce_fwd_bwd, L.ptr(p.pre), L.ptr(target), frames, L.ptr(p.clip_prob),
+                L.ptr(p.loss), L.ptr(p.dpre) if need_grad else None, 0 if only else 1, p.B, p.t_out, self.K, self.ratio,
+                frames if frames else p.t_out * self.ratio, mode_id, float(recall_factor), float(weight), float(grad_scale),
+                L.ptr(p.weak_ws), _stream())
+        return p.loss
+
+    def _strong_loss(self, p: _Plan, target: torch.Tensor, recall_factor: float, need_grad: bool, grad_scale: float):
         self._k("sed_bce_fwd_bwd", self.lib.sed_bce_fwd_bwd, L.ptr(p.pre), L.ptr(target), L.ptr(p.loss),
                                          L.ptr(p.dpre) if need_grad else None, L.ptr(p.loss_partial), p.B, p.t_out,
                                          self.K, self.ratio, target.shape[1], float(recall_factor), float(grad_scale),
                                          _stream())
-        return p.loss
+
+    def _weak_bufs(self, p: _Plan):
+        if p.clip_prob is None:
+            dev = p.pre.device
+            p.clip_prob = torch.empty((p.B, self.K), dtype=torch.float32, device=dev)
+            p.weak_ws = torch.empty(max(1, self.lib.sed_weak_bce_ws_bytes(p.B, p.t_out, self.K) // 8), dtype=torch.float64, device=dev)
+
+    def clip_probs(self, p: _Plan, mode: str) -> torch.Tensor:
+        """(B, K) clip probabilities of the last forward's logits, pooled over all t_out * ratio output frames by `mode` (max /
+        mean / linear / exp).  Returns plan.clip_prob: valid until the next call on this plan."""
+        mode_id = check_pooling(mode)
+        if self.head == "none":
+            raise ValueError("clip_probs needs a model with a classification head")
+        self._weak_bufs(p)
+        self._k("sed_clip_pool_fwd", self.lib.sed_clip_pool_fwd, L.ptr(p.pre), L.ptr(p.clip_prob), p.B, p.t_out, self.K, self.ratio,
+                p.t_out * self.ratio, mode_id, _stream())
+        return p.clip_prob
 
     # ------------------------------------------------------------------------------------------
     def backward(self, p: _Plan, P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor],

@@ -6,7 +6,7 @@ in eval mode -> per-frame probabilities, threshold decisions and onset times.
 
 Writes <outputs_dir>/<name>.npz (probabilities, decisions, onset_frames, onset_seconds; with --median_window / --low_threshold / --max_gap /
 --min_event also events = (class, onset_s, offset_s) rows decoded on the MI355X (utils/event_utils.py) and event_frames, the same in frames;
-with --saliency also
+with --clip_pooling also clip_probs (classes,), the frame probabilities pooled into one clip probability per class; with --saliency also
 saliency (T, mel_bins, classes) = d(sum_t p_k(t)) / d(model input), the eval-mode input gradient) and prints the onsets.  The features are z-scored with --mean_std (the pickle the preprocessing wrote) when given:
 the reference's infer.py skips the normalisation the model was trained with."""
 from __future__ import annotations
@@ -45,6 +45,9 @@ def build_parser():
                         "(default: --threshold, plain thresholding)")
     p.add_argument("--max_gap", type=float, default=0.0, help="merge events at most this many seconds apart (default 0 = off)")
     p.add_argument("--min_event", type=float, default=0.0, help="drop events shorter than this many seconds (default 0 = off)")
+    p.add_argument("--clip_pooling", default=None, choices=["max", "mean", "linear", "exp"],
+                   help="also print and write 'clip_probs' (classes,): the frame probabilities pooled over the recording into one "
+                        "clip probability per class, the way the weak-label loss pools them")
     return p
 
 
@@ -88,14 +91,19 @@ def saliency_maps(model, x):
 
 
 def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, precision="bf16", mel_bins=None, saliency=False,
-               host_resample=False, cfg=None, median_window=1, low_threshold=None, max_gap=0, min_len=1):
+               host_resample=False, cfg=None, median_window=1, low_threshold=None, max_gap=0, min_len=1, clip_pooling=None):
     """cfg: a SpectogramConfig (default REF_NATIVE).  The file's PCM is downmixed and resampled to cfg.working_sample_rate on the
     device (dataset_utils.AudioIngest); host_resample=True takes the float64 scipy path instead.
     median_window / max_gap / min_len (frames) and low_threshold are utils.event_utils.decode_events's: the result's 'events'
     (n, 3) = (class, onset_s, offset_s) and 'event_frames' (n, 3) int are decoded on the device.  With all four at their defaults
     they are the runs of probabilities > threshold, and 'decisions' / 'onset_frames' are what they always were; otherwise those two
-    follow the decoded events."""
+    follow the decoded events.
+    clip_pooling: None, or max / mean / linear / exp: the result gains 'clip_probs' (channels, classes), the frame probabilities
+    pooled over the recording on the device (CnnEngine.clip_probs)."""
     import dataclasses
+    if clip_pooling is not None:
+        from .engine import check_pooling
+        check_pooling(clip_pooling)
     from .dataset.dataset_utils import read_multichannel_audio
     from .dataset.spectogram.preprocess import LogMelFrontEnd
     from .dataset.spectogram.spectogram_configs import REF_NATIVE
@@ -124,6 +132,10 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     print("Inference..")
     with torch.no_grad():
         logits = model(feats)                                       # (1, T', classes)
+    clip = None
+    if clip_pooling is not None:        # the plan of the forward just run still holds its logits
+        plan = model.engine.plan(feats.shape[0], feats.shape[2], feats.shape[3], feats.device)
+        clip = model.engine.clip_probs(plan, clip_pooling).cpu().numpy()
     probs_dev = torch.sigmoid(logits)[0]
     probs = probs_dev.cpu().numpy()
     dec = probs > threshold
@@ -138,6 +150,8 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
            "frames_per_second": cfg.frames_per_second, "log_mel": feats[0, 0].cpu().numpy(), "event_frames": ev,
            "events": np.stack([ev[:, 0].astype(np.float64), ev[:, 1] / cfg.frames_per_second, ev[:, 2] / cfg.frames_per_second],
                               axis=1).reshape(-1, 3)}
+    if clip is not None:
+        res["clip_probs"] = clip
     if saliency:
         print("Saliency..")
         res["saliency"] = saliency_maps(model, feats[:1])
@@ -149,11 +163,14 @@ def main(argv=None):
     from .dataset.spectogram import spectogram_configs
     cfg = {"ref_native": spectogram_configs.REF_NATIVE, "bench": spectogram_configs.BENCH}[args.config]
     res = infer_file(args.audio_file, args.ckpt, args.device, args.mean_std, args.threshold, args.precision, args.mel_bins,
-                     args.saliency, args.host_resample, cfg, **event_options(args, cfg.frames_per_second))
+                     args.saliency, args.host_resample, cfg, **event_options(args, cfg.frames_per_second),
+                     clip_pooling=getattr(args, "clip_pooling", None))
     os.makedirs(args.outputs_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(args.audio_file))[0]
     fps = res["frames_per_second"]
     extra = {"saliency": res["saliency"]} if "saliency" in res else {}
+    if "clip_probs" in res:
+        extra["clip_probs"] = res["clip_probs"][0]
     if event_options(args, fps) != event_options(None, fps):        # an event flag was given: the file gains the event list
         extra.update(events=res["events"], event_frames=res["event_frames"])
     np.savez(os.path.join(args.outputs_dir, name + ".npz"), probabilities=res["probabilities"],
@@ -164,6 +181,8 @@ def main(argv=None):
     for k in range(res["decisions"].shape[1]):
         rows = res["events"][res["events"][:, 0] == k]
         print(f"class {k}: " + (", ".join(f"{a:.2f}-{b:.2f} s" for _, a, b in rows[:50]) if len(rows) else "no events"))
+    if "clip_probs" in res:
+        print(f"clip probabilities ({args.clip_pooling} pooling): " + ", ".join(f"class {k}: {v:.4f}" for k, v in enumerate(res["clip_probs"][0])))
 
 
 if __name__ == "__main__":

@@ -100,11 +100,34 @@ def build_augment_parser():
     return p
 
 
+def build_weak_parser():
+    """The weak-label (clip-level loss) options (this build only), in a parser of their own like the event options."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--weak_labels", default="off", choices=["off", "both", "only"],
+                   help="this build only: train from clip-level labels -- the frame probabilities are pooled over time and the "
+                        "loss is taken against the clip label (the maximum of the frame labels); 'both' adds it to the frame-level "
+                        "loss, 'only' replaces that loss")
+    p.add_argument("--weak_pooling", default="linear", choices=["max", "mean", "linear", "exp"],
+                   help="--weak_labels: the pooling function (linear = linear softmax, exp = exponential softmax)")
+    p.add_argument("--weak_weight", type=float, default=1.0, help="--weak_labels: factor on the clip-level loss (> 0)")
+    return p
+
+
 def build_full_parser():
-    """What main() parses: build_parser(), build_event_parser() and build_augment_parser() together."""
+    """What main() parses: build_parser(), build_event_parser(), build_augment_parser() and build_weak_parser() together."""
     return argparse.ArgumentParser(description="SED training on MI355X",
-                                   parents=[build_parser(), build_event_parser(), build_augment_parser()],
+                                   parents=[build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser()],
                                    conflict_handler="resolve")
+
+
+def weak_options(args):
+    """the FusedTrainer keyword arguments of --weak_labels / --weak_pooling / --weak_weight (a Namespace built by hand may lack
+    any of them)"""
+    labels = getattr(args, "weak_labels", "off")
+    if labels == "off":
+        return {}
+    return {"weak_pooling": getattr(args, "weak_pooling", "linear"), "weak_weight": float(getattr(args, "weak_weight", 1.0)),
+            "weak_only": labels == "only"}
 
 
 def spec_augment_config(args):
@@ -247,6 +270,14 @@ def validate_args(args):
             raise ValueError("--spec_augment works on log-mel features: it needs --train_features Spectogram "
                              "(there is no waveform-domain augmentation for the M5 model)")
         spec_augment_config(args)           # the config's own checks (at most 8 masks of a kind, alpha > 0)
+    if getattr(args, "weak_labels", "off") not in ("off", "both", "only"):
+        raise ValueError(f"--weak_labels is off, both or only, '{args.weak_labels}' given")
+    if weak_options(args):
+        if args.train_features.lower() == "waveform":
+            raise ValueError("--weak_labels pools frame probabilities over time: it needs --train_features Spectogram "
+                             "(the M5 model has no time axis in its output)")
+        from .train import check_weak_options
+        check_weak_options(**weak_options(args))
 
 
 def optimizer_options(args):
@@ -324,7 +355,7 @@ def main(argv=None):
     train(model, dataloader, criterion, num_steps=args.num_train_steps,
           outputs_dir=os.path.join(args.outputs_root, train_name), device=device, lr=args.lr,
           log_freq=args.log_freq, event_eval=event_eval_options(args, frames_per_second(args)),
-          batch_augment=synthetic_batch_augment(args), **optimizer_options(args))
+          batch_augment=synthetic_batch_augment(args), **optimizer_options(args), **weak_options(args))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -300,6 +300,25 @@ def check_optimizer_options(weight_decay=0.0, decoupled_weight_decay=False, amsg
     return wd, dec, ams, mgn, (wd != 0.0 or not ams or mgn is not None)
 
 
+def check_weak_options(weak_pooling=None, weak_weight=1.0, weak_only=False, model=None):
+    """Validate the weak-label options of FusedTrainer / train() (host only, before any device work).  Returns None when
+    weak_pooling is None -- the step then launches exactly what it always did -- else the (mode, weight, only) triple of
+    CnnEngine.loss_and_grad."""
+    if weak_pooling is None:
+        if weak_only:
+            raise ValueError("weak_only needs a weak_pooling (max, mean, linear or exp)")
+        return None
+    from .engine import check_pooling
+    check_pooling(weak_pooling)
+    w = float(weak_weight)
+    if not (0.0 < w < float("inf")):
+        raise ValueError(f"weak_weight must be finite and > 0 (got {weak_weight!r})")
+    if model is not None and not hasattr(model, "conv_blocks"):
+        raise ValueError(f"the weak-label loss pools frame probabilities over time: {type(model).__name__} has no time axis in "
+                         "its output (use Cnn_AvgPooling / Crnn_AvgPooling)")
+    return weak_pooling, w, bool(weak_only)
+
+
 def check_state_amsgrad(group, amsgrad: bool):
     """Refuse an optimizer state whose amsgrad flag is not the trainer's: the max_exp_avg_sq buffers exist on one side only."""
     got = bool(group.get("amsgrad", False))
@@ -316,7 +335,8 @@ class FusedTrainer:
     def __init__(self, model, lr: float, recall_factor: float = 5.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  group=None, graph: bool = False, sync_bn: bool = False, n_buckets: Optional[int] = None,
                  weight_decay: float = 0.0, decoupled_weight_decay: bool = False, amsgrad: bool = True,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, weak_pooling: Optional[str] = None, weak_weight: float = 1.0,
+                 weak_only: bool = False):
         """graph=True (single process): after two eager steps per input shape the whole step -- forward, loss, backward,
         Adam-amsgrad with its step counter, learning rate and bias corrections in device memory -- is captured into a HIP
         graph and replayed.  For the reference's own small shapes (T = 30 crops, batch 4: ~90 launches of a few microseconds
@@ -327,9 +347,15 @@ class FusedTrainer:
         step, computed on the device from the averaged gradient -- every rank reduces the same all-reduced buffer with
         grad_scale = 1/world in the same fixed order, so all ranks get the same factor without another collective.  A
         non-finite norm propagates as in torch (the step is not skipped).  With all four at their defaults the step launches
-        what it always did; any option switches to sed_grad_norm / sed_adam_step_ex."""
+        what it always did; any option switches to sed_grad_norm / sed_adam_step_ex.
+
+        weak_pooling: None, or max / mean / linear / exp -- train from clip-level labels (csrc/sed_weak.hip): the frame
+        probabilities are pooled over time and WeightedBCE is taken against the clip label, times weak_weight.  weak_only=False
+        adds it to the strong loss, with the clip label taken from the (B, T, K) target on the device; weak_only=True trains on it
+        alone, and the target may be (B, K).  None launches nothing new."""
         (self.weight_decay, self.decoupled_weight_decay, self.amsgrad, self.max_grad_norm,
          self._opt_ext) = check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
+        self.weak = check_weak_options(weak_pooling, weak_weight, weak_only, model)
         self.model = model
         self.engine = model.engine
         self.use_graph = bool(graph)
@@ -392,7 +418,10 @@ class FusedTrainer:
         plan = eng.forward(x, P, training=True)
         self.model._nbt_pending += 1
         self.model._fwd_serial += 1
-        loss = eng.loss_and_grad(plan, y, self.recall_factor)
+        if self.weak is None:
+            loss = eng.loss_and_grad(plan, y, self.recall_factor)
+        else:
+            loss = eng.loss_and_grad(plan, y, self.recall_factor, weak=self.weak)
         eng.backward(plan, P, self.flat.G, on_group_done=self.reducer.bucket_ready)
         return loss
 
@@ -654,14 +683,23 @@ def summarize_validation(val_losses, recal_sets, precision_sets, APs):
 
 
 def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, device, *, weight_decay=0.0,
-          decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None, event_eval=None, batch_augment=None):
+          decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None, event_eval=None, batch_augment=None,
+          weak_pooling=None, weak_weight=1.0, weak_only=False):
     """train.py:77-131.  `criterion` must be this package's WeightedBCE(multi_frame=True) (its
     recall_factor feeds the fused loss kernel).  The keyword-only optimizer options are FusedTrainer's (this build only; their
     defaults are the reference's Adam(amsgrad=True) without decay or clipping).  event_eval: None, or the keyword arguments of
     eval_events (threshold ... collar_frames): the periodic evaluation then also logs that dict; None launches nothing new.
     batch_augment: None, or a callable (features, labels) -> (features, labels) applied to every device batch before the step
-    (dataset.spectogram.augment.LogMelAugment for loaders that hand plain log-mel tensors over); validation never sees it."""
+    (dataset.spectogram.augment.LogMelAugment for loaders that hand plain log-mel tensors over); validation never sees it.
+    weak_pooling / weak_weight / weak_only: FusedTrainer's weak-label options.  A utils.common.WeakBCE as `criterion` is shorthand
+    for weak_only=True with its pooling and recall_factor; the loader may then hand (B, K) clip labels over."""
+    from .utils.common import WeakBCE, WeightedBCE
     check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
+    if isinstance(criterion, WeakBCE):
+        if weak_pooling is not None and weak_pooling != criterion.pooling:
+            raise ValueError(f"criterion pools with {criterion.pooling!r} but weak_pooling={weak_pooling!r}")
+        weak_pooling, weak_only = criterion.pooling, True
+    check_weak_options(weak_pooling, weak_weight, weak_only, model)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("the MI355X training path needs device='cuda' (there is no CPU path)")
@@ -670,16 +708,16 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
     os.makedirs(os.path.join(outputs_dir, "checkpoints"), exist_ok=True)
     model.to(dev)
     # the fused step computes WeightedBCE (utils/common.py:11-30) itself: honour exactly that criterion, refuse anything else
-    from .utils.common import WeightedBCE
-    if not isinstance(criterion, WeightedBCE):
+    if not isinstance(criterion, (WeightedBCE, WeakBCE)):
         raise TypeError("train() runs the fused WeightedBCE loss kernel: pass this package's WeightedBCE "
                         f"(got {type(criterion).__name__}); other criteria would be silently ignored")
     wants_multi = hasattr(model, "conv_blocks")       # spectrogram models: frame-wise targets; M5: one label per frame
-    if bool(criterion.multi_frame) != wants_multi:
+    if isinstance(criterion, WeightedBCE) and bool(criterion.multi_frame) != wants_multi:
         raise ValueError(f"{type(model).__name__} trains with WeightedBCE(multi_frame={wants_multi}) (main.py:44,71)")
     trainer = FusedTrainer(model, lr, recall_factor=criterion.recall_factor,
                            sync_bn=os.environ.get("SED_SYNC_BN", "0") == "1", weight_decay=weight_decay,
-                           decoupled_weight_decay=decoupled_weight_decay, amsgrad=amsgrad, max_grad_norm=max_grad_norm)
+                           decoupled_weight_decay=decoupled_weight_decay, amsgrad=amsgrad, max_grad_norm=max_grad_norm,
+                           weak_pooling=weak_pooling, weak_weight=weak_weight, weak_only=weak_only)
     rank0 = (not trainer.reducer.enabled) or trainer.reducer.dist.get_rank() == 0
     log_path = os.path.join(outputs_dir, "progress.jsonl")
     losses: List[float] = []

@@ -1,0 +1,450 @@
+"""GPU: sed_clip_pool_fwd / sed_weak_bce_fwd_bwd (csrc/sed_weak.hip) through the C ABI, and the layers on top of them
+(CnnEngine.loss_and_grad(weak=...), CnnEngine.clip_probs, FusedTrainer(weak_pooling=...), utils.common.WeakBCE, infer_file).
+
+Reference: tests/weak_formula.py (float64; checked against torch autograd on the host in tests/test_weak_host.py).
+
+Tolerance, for clip_prob, loss and dpre: |got - ref| <= 2^-23 |ref| + 2^-40 s, with s the largest |ref| of that (b, k) row (for the
+loss: the loss itself).  Derivation: the kernel computes in double and rounds ONCE to fp32 (relative 2^-24); its double sums have
+at most 2^10-odd terms (relative 2^-43) and go through a few factors; the second term covers the cancellation in 2 p_i - P and
+1 + p_i - P, which is relative to the row's scale, not to the element.  Derived, not measured.  Rows of pre with c_i = 0 and the
+non-argmax rows under max pooling are compared with np.array_equal to 0.
+Every output lies in a sentinel-filled buffer between two canary regions; every input must be unmodified afterwards."""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+from weak_formula import MODES, frame_counts, weak_loop, weak_vectorised
+
+pytestmark = pytest.mark.gpu
+
+PKG = "soundeventdetection-pytorch_amd"
+GUARD = 1024
+FILL = {torch.float32: (float("nan"), -1024.0), torch.float64: (float("nan"), -4096.0)}
+SHAPES = [(2, 5, 3), (1, 1, 1), (3, 63, 1), (3, 64, 14), (2, 65, 17), (2, 257, 2), (1, 1025, 1), (4, 750, 14)]
+W = 5.0                     # recall factor
+
+
+@pytest.fixture(scope="module")
+def sed():
+    assert torch.cuda.is_available(), "GPU tests need the MI355X"
+    return importlib.import_module(PKG)
+
+
+@pytest.fixture(scope="module")
+def L(sed):
+    return sed._lib
+
+
+class Guards:
+    """output buffers: a sentinel inside, a canary region on both sides"""
+
+    def __init__(self):
+        self.bufs = []
+
+    def new(self, dtype, *shape):
+        n = int(np.prod(shape))
+        inside, canary = FILL[dtype]
+        buf = torch.full((n + 2 * GUARD,), canary, dtype=dtype, device="cuda")
+        buf[GUARD:GUARD + n] = inside
+        self.bufs.append((buf, n, canary))
+        return buf[GUARD:GUARD + n].view(shape)
+
+    def intact(self):
+        torch.cuda.synchronize()
+        for buf, n, canary in self.bufs:
+            assert bool((buf[:GUARD] == canary).all()) and bool((buf[GUARD + n:] == canary).all()), "write outside an output buffer"
+
+
+def stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def run_weak(L, pre, target, ratio, Tt, mode, weight=1.0, grad_scale=1.0, with_clip=True, with_grad=True, into=None):
+    """through the C ABI into guarded buffers -> (clip_prob (B, K) or None, loss float32, dpre (B, t, K) or None) as numpy.
+    into = (loss, dpre) device tensors: accumulate = 1 on top of them (they are returned updated)."""
+    B, t, K = pre.shape
+    lib = L.lib()
+    g = Guards()
+    d_pre, d_tgt = dev(pre), dev(target)
+    clip = g.new(torch.float32, B, K) if with_clip else None
+    if into is None:
+        loss, dpre = g.new(torch.float32, 1), (g.new(torch.float32, B, t, K) if with_grad else None)
+    else:
+        loss, dpre = g.new(torch.float32, 1), g.new(torch.float32, B, t, K)
+        loss.copy_(into[0])
+        dpre.copy_(into[1])
+    nws = lib.sed_weak_bce_ws_bytes(B, t, K)
+    assert nws % 8 == 0 and nws >= 8
+    ws = g.new(torch.float64, nws // 8)
+    frames = target.shape[1] if target.ndim == 3 else 0
+    assert frames in (0, Tt)
+    L.check(lib.sed_weak_bce_fwd_bwd(L.ptr(d_pre), L.ptr(d_tgt), frames, L.ptr(clip), L.ptr(loss), L.ptr(dpre),
+                                     0 if into is None else 1, B, t, K, ratio, Tt, L.POOL_MODES[mode], W, weight, grad_scale,
+                                     L.ptr(ws), stream()), "weak_bce_fwd_bwd")
+    g.intact()
+    assert np.array_equal(d_pre.cpu().numpy(), pre) and np.array_equal(d_tgt.cpu().numpy(), target), "an input was modified"
+    out = (None if clip is None else clip.cpu().numpy(), loss.cpu().numpy()[0], None if dpre is None else dpre.cpu().numpy())
+    for a in out:
+        assert a is None or not np.isnan(a).any(), "an output cell was not written"
+    return out
+
+
+def run_pool(L, pre, ratio, Tt, mode):
+    B, t, K = pre.shape
+    g = Guards()
+    d_pre = dev(pre)
+    clip = g.new(torch.float32, B, K)
+    L.check(L.lib().sed_clip_pool_fwd(L.ptr(d_pre), L.ptr(clip), B, t, K, ratio, Tt, L.POOL_MODES[mode], stream()), "clip_pool_fwd")
+    g.intact()
+    assert np.array_equal(d_pre.cpu().numpy(), pre), "the input was modified"
+    return clip.cpu().numpy()
+
+
+def within(got, ref, s, tag):
+    """the module docstring's bound; prints the worst ratio error / bound before asserting"""
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    assert np.isfinite(got).all() and np.isfinite(ref).all(), tag
+    bound = 2.0 ** -23 * np.abs(ref) + 2.0 ** -40 * np.asarray(s, dtype=np.float64)
+    err = np.abs(got - ref)
+    bad = err > bound
+    worst = float((err / np.where(bound > 0, bound, 1.0)).max()) if err.size else 0.0
+    print(f"{tag}: worst error / bound {worst:.3f}")
+    assert not bad.any(), (tag, int(bad.sum()), worst)
+
+
+def check(got, ref, pre, ratio, Tt, mode, tag):
+    """(clip_prob, loss, dpre) from the kernel against (P, Y, loss, dpre) of the formula"""
+    clip, loss, dpre = got
+    P, _, lref, dref = ref
+    if clip is not None:
+        within(clip, P, np.abs(P), (tag, "clip_prob"))
+    within(loss, lref, abs(lref), (tag, "loss"))
+    if dpre is not None:
+        within(dpre, dref, np.abs(dref).max(axis=1, keepdims=True), (tag, "dpre"))
+        zero = dref == 0.0
+        _, c = frame_counts(pre.shape[1], ratio, Tt)
+        zero[:, c == 0] = True
+        if mode == "max":
+            assert (zero.sum(axis=1) >= pre.shape[1] - 1).all()
+        assert np.array_equal(dpre[zero], np.zeros(int(zero.sum()), dtype=np.float32)), (tag, "cells that must be exactly 0")
+
+
+def targets(rng, B, K, Tt):
+    """clip labels (B, K) with soft values, and a strong (B, Tt, K) tensor with events, empty classes and soft frames"""
+    clip = np.where(rng.random((B, K)) > 0.5, rng.uniform(0.3, 1.0, (B, K)), 0.0).astype(np.float32)
+    clip[rng.random((B, K)) > 0.7] = 1.0
+    strong = np.zeros((B, Tt, K), dtype=np.float32)
+    for b in range(B):
+        for k in range(K):
+            if rng.random() > 0.4:
+                a = int(rng.integers(0, Tt))
+                strong[b, a:a + 1 + int(rng.integers(0, max(1, Tt // 3))), k] = 1.0 if rng.random() > 0.3 else 0.625
+    return clip, strong
+
+
+def frame_totals(t, ratio):
+    """Tt = t*ratio, t*ratio - 3 (a partial last row), t*ratio + 5, and Tt < ratio (only row 0 counts), where such a Tt exists"""
+    return sorted({Tt for Tt in (t * ratio, t * ratio - 3, t * ratio + 5, ratio - 5) if Tt > 0})
+
+
+# ---- the kernels against the formula ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("ratio", [1, 8])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_weak_loss_against_formula(L, shape, ratio, mode):
+    B, t, K = shape
+    rng = np.random.default_rng(B * 100000 + t * 100 + K + ratio)
+    pre = rng.normal(0.0, 3.0, shape).astype(np.float32)
+    totals = frame_totals(t, ratio)
+    assert len(totals) == (4 if ratio == 8 else 3 if t > 3 else 2)
+    for Tt in totals:
+        clip_t, strong_t = targets(rng, B, K, Tt)
+        for target in (clip_t, strong_t):
+            tag = (shape, ratio, Tt, mode, target.ndim)
+            ref = weak_vectorised(pre, target, ratio, Tt, mode, W, 0.75, 0.5)
+            got = run_weak(L, pre, target, ratio, Tt, mode, 0.75, 0.5)
+            check(got, ref, pre, ratio, Tt, mode, tag)
+            if Tt < ratio:              # only row 0 counts: the others get exactly 0 and cannot win the max
+                assert np.array_equal(got[2][:, 1:], np.zeros_like(got[2][:, 1:])), tag
+        # the forward-only call gives the same clip probabilities, bit for bit; the optional outputs may be left out
+        assert np.array_equal(run_pool(L, pre, ratio, Tt, mode), got[0]), (shape, ratio, Tt, mode)
+        bare = run_weak(L, pre, strong_t, ratio, Tt, mode, 0.75, 0.5, with_clip=False, with_grad=False)
+        assert bare[0] is None and bare[2] is None and bare[1] == got[1]
+    if B * t * K <= 64:                 # the loop form of the formula, where it is quick
+        Tt = totals[-1]
+        ref = weak_loop(pre, strong_t, ratio, Tt, mode, W, 0.75, 0.5)
+        check(got, ref, pre, ratio, Tt, mode, (shape, ratio, Tt, mode, "loop"))
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_only_row_zero_counts_even_if_a_later_row_is_larger(L, mode):
+    pre = np.array([[[0.25], [9.0], [-3.0]], [[-1.5], [4.0], [8.0]]], dtype=np.float32)
+    target = np.array([[1.0], [0.0]], dtype=np.float32)
+    got = run_weak(L, pre, target, 8, 3, mode)
+    check(got, weak_loop(pre, target, 8, 3, mode, W), pre, 8, 3, mode, ("row 0 only", mode))
+    p0 = 1.0 / (1.0 + np.exp(-pre[:, 0].astype(np.float64)))
+    within(got[0], p0, np.abs(p0), ("row 0 only: every pooling of one row is that row's probability", mode))
+    assert (got[2][:, 0] != 0).all() and np.array_equal(got[2][:, 1:], np.zeros((2, 2, 1), dtype=np.float32))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("ratio", [1, 8])
+def test_saturated_logits(L, mode, ratio):
+    rng = np.random.default_rng(5)
+    B, t, K = 3, 70, 4
+    pre = np.where(rng.random((B, t, K)) > 0.5, 60.0, -60.0).astype(np.float32)
+    pre[0, :, 0] = -1000.0              # every probability is 0: P = 0, Q = 1, loss w * Y * 100, no gradient
+    pre[1, :, 1] = -60.0
+    pre[2, :, 2] = 60.0
+    pre[1, :, 3] = 1000.0
+    Tt = t * ratio - 3
+    clip_t, strong_t = targets(rng, B, K, Tt)
+    clip_t[0, 0], strong_t[0, 5, 0] = 1.0, 1.0
+    for target in (clip_t, strong_t):
+        ref = weak_vectorised(pre, target, ratio, Tt, mode, W)
+        got = run_weak(L, pre, target, ratio, Tt, mode)
+        assert all(np.isfinite(a).all() for a in got)
+        check(got, ref, pre, ratio, Tt, mode, ("saturated", mode, ratio, target.ndim))
+        assert got[0][0, 0] == 0.0 and np.array_equal(got[2][0, :, 0], np.zeros(t, dtype=np.float32))
+    small = (slice(0, 1), slice(0, 4), slice(0, 2))
+    ref = weak_loop(pre[small], clip_t[:1, :2], ratio, 4 * ratio, mode, W)
+    check(run_weak(L, np.ascontiguousarray(pre[small]), np.ascontiguousarray(clip_t[:1, :2]), ratio, 4 * ratio, mode), ref,
+          pre[small], ratio, 4 * ratio, mode, ("saturated, loop form", mode, ratio))
+
+
+@pytest.mark.parametrize("t,first,second", [(6, 2, 4), (300, 1, 257), (700, 255, 256), (700, 300, 44 + 512)])
+def test_max_ties_take_the_smaller_index(L, t, first, second):
+    rng = np.random.default_rng(t + first)
+    pre = rng.normal(0.0, 1.0, (2, t, 2)).astype(np.float32)
+    pre[:, first, :] = pre[:, second, :] = 7.5
+    target = np.array([[1.0, 0.0], [0.5, 1.0]], dtype=np.float32)
+    got = run_weak(L, pre, target, 8, t * 8, "max")
+    check(got, weak_vectorised(pre, target, 8, t * 8, "max", W), pre, 8, t * 8, "max", ("tie", t, first, second))
+    nz = got[2] != 0
+    assert nz[:, first, :].all() and int(nz.sum()) == 4
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_accumulate_on_top_of_the_strong_loss_and_determinism(L, mode):
+    B, t, K, ratio, Tt = 3, 65, 5, 8, 65 * 8 - 3
+    rng = np.random.default_rng(11)
+    pre = rng.normal(0.0, 3.0, (B, t, K)).astype(np.float32)
+    _, strong_t = targets(rng, B, K, Tt)
+    lib = L.lib()
+    d_pre, d_tgt = dev(pre), dev(strong_t)
+    loss_s, dpre_s = torch.empty(1, device="cuda"), torch.empty(B, t, K, device="cuda")
+    part = torch.empty((B * t * K + 255) // 256, device="cuda")
+    L.check(lib.sed_bce_fwd_bwd(L.ptr(d_pre), L.ptr(d_tgt), L.ptr(loss_s), L.ptr(dpre_s), L.ptr(part), B, t, K, ratio, Tt, W, 0.5,
+                                stream()), "bce_fwd_bwd")
+    alone = run_weak(L, pre, strong_t, ratio, Tt, mode, 0.75, 0.5)
+    again = run_weak(L, pre, strong_t, ratio, Tt, mode, 0.75, 0.5)
+    for a, b in zip(alone, again):      # two runs: the same bits
+        assert np.array_equal(a.view(np.uint32) if a.ndim else a, b.view(np.uint32) if b.ndim else b)
+    both = run_weak(L, pre, strong_t, ratio, Tt, mode, 0.75, 0.5, into=(loss_s, dpre_s))
+    ls, ds = loss_s.cpu().numpy()[0], dpre_s.cpu().numpy()
+    assert np.array_equal((ds + alone[2]).view(np.uint32), both[2].view(np.uint32))      # ONE IEEE add per element
+    assert np.float32(ls + alone[1]) == both[1] and np.array_equal(alone[0], both[0])
+
+
+# ---- the layers ------------------------------------------------------------------------------------------------------------------
+CFG = [(4, 2), (8, 2), (8, 2), (8, 1)]
+K_CLASSES = 3
+
+
+def make_model(sed, kind):
+    torch.manual_seed(0)
+    if kind == "cnn":
+        return sed.Cnn_AvgPooling(K_CLASSES, CFG, precision="fp32").cuda()
+    return sed.Crnn_AvgPooling(K_CLASSES, CFG, precision="fp32", gru_hidden=32).cuda()
+
+
+def batch():
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(2, 1, 32, 64, generator=g)
+    y = torch.zeros(2, 32, K_CLASSES)
+    y[0, 4:13, 0] = 1.0
+    y[1, 20:30, 1] = 1.0
+    y[1, 2:6, 0] = 0.5
+    return x.cuda(), y.cuda()
+
+
+def the_plan(model):
+    plans = list(model.engine._plans.values())
+    assert len(plans) == 1
+    return plans[0]
+
+
+@pytest.mark.parametrize("kind", ["cnn", "crnn"])
+@pytest.mark.parametrize("mode", ["linear", "max"])
+def test_trainer_weak_only_and_both(sed, L, kind, mode):
+    x, y = batch()
+    yn = y.cpu().numpy()
+    model = make_model(sed, kind)
+    ratio = model.engine.ratio
+    tr = sed.FusedTrainer(model, lr=1e-3, recall_factor=W, weak_pooling=mode, weak_weight=0.5, weak_only=True)
+    loss = tr.forward_backward(x, y).clone()
+    plan = the_plan(model)
+    pre = plan.pre.cpu().numpy()
+    assert pre.shape == (2, 4, K_CLASSES) and ratio == 8
+    ref = weak_vectorised(pre, yn, ratio, 32, mode, W, 0.5)
+    got = (plan.clip_prob.cpu().numpy(), loss.cpu().numpy()[0], plan.dpre.cpu().numpy())
+    check(got, ref, pre, ratio, 32, mode, (kind, mode, "only"))
+    assert float(tr.flat.g.abs().max()) > 0 and bool(torch.isfinite(tr.flat.g).all())
+    # (B, K) clip labels: the same step, bit for bit
+    loss2 = tr.forward_backward(x, y.max(dim=1).values.contiguous()).clone()
+    assert torch.equal(loss2, loss) and np.array_equal(plan.dpre.cpu().numpy(), got[2])
+    assert np.array_equal(model.engine.clip_probs(plan, mode).cpu().numpy(), got[0])
+
+    # both: the strong kernel's result plus the weak one's, ONE IEEE add per element
+    model_b = make_model(sed, kind)
+    trb = sed.FusedTrainer(model_b, lr=1e-3, recall_factor=W, weak_pooling=mode, weak_weight=0.5)
+    loss_b = trb.forward_backward(x, y).clone()
+    plan_b = the_plan(model_b)
+    assert np.array_equal(plan_b.pre.cpu().numpy(), pre)
+    ls, ds = torch.empty(1, device="cuda"), torch.empty_like(plan_b.dpre)
+    part = torch.empty(max(1, (pre.size * ratio + 255) // 256), device="cuda")
+    L.check(L.lib().sed_bce_fwd_bwd(L.ptr(plan_b.pre), L.ptr(y), L.ptr(ls), L.ptr(ds), L.ptr(part), 2, 4, K_CLASSES, ratio, 32, W, 1.0,
+                                    stream()), "bce_fwd_bwd")
+    assert np.array_equal(plan_b.dpre.cpu().numpy(), ds.cpu().numpy() + got[2])
+    assert loss_b.cpu().numpy()[0] == np.float32(ls.cpu().numpy()[0] + got[1])
+    with pytest.raises(ValueError, match="clip labels"):
+        trb.forward_backward(x, y.max(dim=1).values.contiguous())
+
+
+@pytest.mark.parametrize("kind", ["cnn", "crnn"])
+def test_graph_replay_gives_the_eager_loss_bits(sed, kind):
+    x, y = batch()
+    yc = y.max(dim=1).values.contiguous()
+
+    def fresh():
+        return sed.FusedTrainer(make_model(sed, kind), lr=1e-3, recall_factor=W, graph=True, weak_pooling="linear", weak_only=True)
+
+    eager, graph = fresh(), fresh()
+    for i in range(4):                  # the same device-scalar step, enqueued launch by launch / captured after two steps and replayed
+        le = eager._step_dev(x, yc).clone()
+        eager._host_mirror()
+        lg = graph.train_step(x, yc).clone()
+        assert torch.equal(le, lg), (i, float(le), float(lg))
+    assert len(graph._graphs) == 1 and len(eager._graphs) == 0
+    # a (B, T, K) target is another shape key: eager again, then its own graph
+    graph.train_step(x, y)
+    assert len(graph._graphs) == 1
+
+
+@pytest.mark.parametrize("kind", ["cnn", "crnn"])
+@pytest.mark.parametrize("mode", MODES)
+def test_weak_bce_criterion_backward(sed, kind, mode):
+    x, y = batch()
+    model = make_model(sed, kind).train()
+    ratio = model.engine.ratio
+    out = model(x)
+    out.retain_grad()
+    loss = sed.WeakBCE(W, mode, ratio=ratio)(out, y)
+    loss.backward()
+    plan = the_plan(model)
+    pre = plan.pre.cpu().numpy()
+    ref = weak_vectorised(pre, y.cpu().numpy(), ratio, 32, mode, W)
+    dlog = out.grad.cpu().numpy()
+    dpre = dlog.reshape(2, 4, ratio, K_CLASSES).sum(axis=2)             # the repeat backward: the gradient sits on the first copy
+    assert np.array_equal(dlog[:, ::ratio], dpre)
+    check((None, loss.detach().cpu().numpy(), dpre), ref, pre, ratio, 32, mode, (kind, mode, "WeakBCE"))
+    assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in model.parameters())
+    # ratio = 1 on the repeated logits and clip labels: the same loss as a formula over every frame
+    loss1 = sed.WeakBCE(W, mode)(out.detach(), y.max(dim=1).values)
+    ref1 = weak_vectorised(out.detach().cpu().numpy(), y.max(dim=1).values.cpu().numpy(), 1, 32, mode, W)
+    within(loss1.cpu().numpy(), ref1[2], abs(ref1[2]), (kind, mode, "WeakBCE ratio 1"))
+
+
+def test_weak_only_training_lowers_the_weak_loss(sed):
+    x, y = batch()
+    torch.manual_seed(0)
+    tr = sed.FusedTrainer(make_model(sed, "cnn"), lr=3e-3, recall_factor=W, weak_pooling="linear", weak_only=True)
+    losses = [float(tr.train_step(x, y)) for _ in range(31)]           # losses[i]: before update i
+    assert all(np.isfinite(losses)) and losses[30] < losses[0], losses
+
+
+def test_launch_lists(sed):
+    x, y = batch()
+
+    def names(**kw):
+        mdl = make_model(sed, "cnn")
+        tr = sed.FusedTrainer(mdl, lr=1e-3, recall_factor=W, **kw)
+        tr.train_step(x, y)             # (first step: allocations)
+        mdl.engine.timer = sed.engine.KernelTimer()
+        tr.train_step(x, y)
+        torch.cuda.synchronize()
+        return [lbl.split(":")[0] for lbl, _, _ in mdl.engine.timer.records]
+
+    plain = names()
+    assert plain.count("sed_bce_fwd_bwd") == 1 and not [n for n in plain if "weak" in n or "clip_pool" in n], plain
+    i = plain.index("sed_bce_fwd_bwd")
+    assert names(weak_pooling="mean") == plain[:i + 1] + ["sed_weak_bce_fwd_bwd"] + plain[i + 1:]
+    assert names(weak_pooling="mean", weak_only=True) == plain[:i] + ["sed_weak_bce_fwd_bwd"] + plain[i + 1:]
+
+
+def test_train_with_the_weak_criterion_and_clip_labels(sed, tmp_path):
+    """train(criterion=WeakBCE) is weak_only=True with its pooling; the loader hands (B, K) clip labels over"""
+    x, y = batch()
+    yc = y.max(dim=1).values.contiguous()
+
+    class Loader:
+        batch_size = 2
+        dataset = None
+
+        def __iter__(self):
+            return iter([(x, yc), (x, yc)])
+
+    torch.manual_seed(0)
+    tr = sed.train.train(make_model(sed, "cnn"), Loader(), sed.WeakBCE(W, "exp"), 4, 1e-3, 100, str(tmp_path), "cuda", weak_weight=2.0)
+    assert tr.weak == ("exp", 2.0, True) and tr.step_count == 4
+    plan = the_plan(tr.model)
+    ref = weak_vectorised(plan.pre.cpu().numpy(), yc.cpu().numpy(), 8, 32, "exp", W, 2.0)
+    check((plan.clip_prob.cpu().numpy(), plan.loss.cpu().numpy()[0], plan.dpre.cpu().numpy()), ref, plan.pre.cpu().numpy(), 8, 32,
+          "exp", "train(WeakBCE)")
+
+
+def test_infer_file_clip_probs(sed, tmp_path, capsys):
+    from scipy.io import wavfile
+    infer = importlib.import_module(PKG + ".infer")
+    sc = importlib.import_module(PKG + ".dataset.spectogram.spectogram_configs")
+    rng = np.random.default_rng(4)
+    n = 32000 * 2
+    wav = 0.05 * rng.standard_normal(n)
+    wav[20000:30000] += 0.4 * np.sin(2 * np.pi * 700.0 * np.arange(10000) / 32000.0)
+    p = str(tmp_path / "clip.wav")
+    wavfile.write(p, 32000, (wav.clip(-1, 1) * 32767).astype(np.int16))
+    cfg = [(32, 2), (64, 2), (128, 2), (128, 1)]        # the model infer_file builds
+    torch.manual_seed(0)
+    model = sed.Cnn_AvgPooling(sc.BENCH.classes_num, cfg, precision="fp32", mel_bins=sc.BENCH.mel_bins)
+    ck = str(tmp_path / "m.pth")
+    torch.save({"iterations": 0, "model": model.state_dict()}, ck)
+    plain = infer.infer_file(p, ck, precision="fp32", cfg=sc.BENCH)
+    assert "clip_probs" not in plain
+    model = model.cuda().eval()
+    feats = torch.from_numpy(plain["log_mel"]).cuda()[None, None]
+    for mode in MODES:
+        res = infer.infer_file(p, ck, precision="fp32", cfg=sc.BENCH, clip_pooling=mode)
+        assert np.array_equal(res["probabilities"], plain["probabilities"])
+        with torch.no_grad():
+            model(feats)
+        plan = the_plan(model)
+        assert np.array_equal(res["clip_probs"], model.engine.clip_probs(plan, mode).cpu().numpy())
+        pre = plan.pre.cpu().numpy()
+        P = weak_vectorised(pre, np.zeros((1, sc.BENCH.classes_num)), model.engine.ratio, pre.shape[1] * model.engine.ratio, mode, W)[0]
+        within(res["clip_probs"], P, np.abs(P), ("infer_file clip_probs", mode))
+    # the command line: clip_probs are printed, and written only with the flag
+    capsys.readouterr()
+    infer.main([p, "--ckpt", ck, "--outputs_dir", str(tmp_path / "plain"), "--precision", "fp32", "--config", "bench"])
+    assert "clip probabilities" not in capsys.readouterr().out
+    infer.main([p, "--ckpt", ck, "--outputs_dir", str(tmp_path / "clip"), "--precision", "fp32", "--config", "bench",
+                "--clip_pooling", "exp"])
+    assert "clip probabilities (exp pooling): class 0: " in capsys.readouterr().out
+    z0, z1 = np.load(tmp_path / "plain" / "clip.npz"), np.load(tmp_path / "clip" / "clip.npz")
+    assert sorted(z1.files) == sorted(z0.files + ["clip_probs"]) and "clip_probs" not in z0.files
+    assert np.array_equal(z1["clip_probs"], res["clip_probs"][0]) and np.array_equal(z0["probabilities"], z1["probabilities"])
