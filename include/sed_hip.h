@@ -293,6 +293,58 @@ int sed_weak_bce_fwd_bwd(const float* pre, const float* target, int target_frame
                          float* loss, float* dpre, int accumulate, int B, int t, int K, int ratio,
                          int Tt, int mode, float recall_factor, float weight, float grad_scale,
                          void* workspace, void* stream);
+/* ---- semi-supervised training: csrc/sed_semi.hip, csrc/sed_weak.hip ---------------------------
+ * Batches that mix strongly labelled, weakly labelled and unlabelled clips, and a mean teacher (an
+ * exponential moving average of the student's weights whose frame and clip probabilities the student
+ * is pulled towards).  The three losses work on pre [B][t][K] fp32 like sed_bce_fwd_bwd: N =
+ * min(t*ratio, Tt) virtual frames, row i stands for the frames [i*ratio, i*ratio + c_i), c_i =
+ * clamp(N - i*ratio, 0, ratio).  clip_sel [B] is a byte per clip, nonzero = the clip takes part; NULL =
+ * all clips.  S, the number of selected clips, is counted on the device (no host synchronisation).
+ * All arithmetic is double, p = 1/(1+exp(-x)) and q = 1/(1+exp(x)) each from its own expression;
+ * every result is rounded once to fp32; every sum is taken in a fixed order without atomics (the same
+ * bits on every run).  accumulate = 0 overwrites loss[0] and dpre; accumulate = 1 adds to them, one
+ * IEEE fp32 add per element.  Cells of unselected clips and of rows with c_i = 0 are written as exact
+ * 0 under accumulate = 0 and are not touched under accumulate = 1.  S == 0: the loss term is exactly
+ * 0 and so is the gradient.  dpre may be NULL (loss only).  Two launches each.
+ *
+ * sed_bce_sel_fwd_bwd: WeightedBCE over the selected clips.  target [B][Tt][K] fp32.
+ *   l_f = -(w y_f ln sigma(x) + (1 - y_f) ln sigma(-x)), ln sigma(x) = min(x, 0) - log1p(exp(-|x|))
+ *   (no -100 clamp, as in sed_bce_fwd_bwd);  loss = weight * sum_{b in sel} sum_{f<N} sum_k l_f / (S N K)
+ *   dpre[b][i][k] = weight * grad_scale / (S N K) * sum_{f of row i, f<N} ((1 - y_f) p - w y_f q)
+ * workspace: sed_bce_sel_ws_bytes() bytes, 8-byte aligned.                                        */
+size_t sed_bce_sel_ws_bytes(int B, int t, int K);
+int sed_bce_sel_fwd_bwd(const float* pre, const float* target, const unsigned char* clip_sel, float* loss,
+                        float* dpre, int accumulate, int B, int t, int K, int ratio, int Tt,
+                        float recall_factor, float weight, float grad_scale, void* workspace, void* stream);
+/* sed_weak_bce_fwd_bwd with a clip selection and a criterion; the pooling modes, P, Q and dP/dp_i are
+ * those of the weak-label block above, and so are target / target_frames, clip_prob (written for every
+ * clip, selected or not) and the workspace (sed_weak_bce_ws_bytes()).
+ *   SED_CRIT_BCE  l = -(w Y max(ln P, -100) + (1 - Y) max(ln Q, -100)), dl/dP as above
+ *   SED_CRIT_MSE  l = (P - Y)^2, dl/dP = 2 (P - Y); recall_factor is not used
+ *   loss = weight * sum_{b in sel} sum_k l / (S K),
+ *   dpre_i = weight * grad_scale / (S K) * dl/dP * dP/dp_i * p_i q_i
+ * clip_sel == NULL with SED_CRIT_BCE is sed_weak_bce_fwd_bwd, bit for bit.                         */
+#define SED_CRIT_BCE 0
+#define SED_CRIT_MSE 1
+int sed_weak_bce_fwd_bwd_ex(const float* pre, const float* target, int target_frames,
+                            const unsigned char* clip_sel, int criterion, float* clip_prob, float* loss,
+                            float* dpre, int accumulate, int B, int t, int K, int ratio, int Tt, int mode,
+                            float recall_factor, float weight, float grad_scale, void* workspace,
+                            void* stream);
+/* Frame-level consistency: pre_teacher [B][t][K] fp32 are the teacher's logits, p_T its probabilities.
+ *   loss = weight * sum_{b in sel} sum_i c_i sum_k (p - p_T)^2 / (S N K)
+ *   dpre[b][i][k] = weight * grad_scale / (S N K) * c_i * 2 (p - p_T) p q
+ * The teacher gets no gradient.  workspace: sed_frame_mse_ws_bytes() bytes, 8-byte aligned.        */
+size_t sed_frame_mse_ws_bytes(int B, int t, int K);
+int sed_frame_mse_fwd_bwd(const float* pre, const float* pre_teacher, const unsigned char* clip_sel,
+                          float* loss, float* dpre, int accumulate, int B, int t, int K, int ratio, int Tt,
+                          float weight, float grad_scale, void* workspace, void* stream);
+/* teacher[i] = alpha * teacher[i] + (1 - alpha) * student[i] over n >= 1 fp32 elements, in double,
+ * rounded once; alpha in [0, 1]; alpha = 0 copies the student's bits and alpha = 1 leaves the teacher's,
+ * whatever the values (infinities, NaN, -0).  Any 4-byte aligned pointers: 16-byte accesses where both buffers
+ * reach a 16-byte boundary after the same number of elements, element-wise before and after it (and
+ * throughout when they do not).  The buffers must not overlap.  One launch.                        */
+int sed_ema_update(float* teacher, const float* student, size_t n, double alpha, void* stream);
 /* Head backward: dfc_w [K][C], dfc_b [K] (overwritten) and dfeat [B][t][Wf][Cp] =
  * (dpre @ fc_w)/Wf broadcast over mel.  `dpre` is [B][t*ratio][K]: with ratio > 1 it is the
  * gradient w.r.t. the interpolate()d logits and the repeat-backward sum is folded in.  m is the

@@ -12,6 +12,7 @@ DZ_POOL, DZ_BN = 1, 2
 PCM_I16, PCM_I32, PCM_F32 = 0, 1, 2
 POOL_MAX, POOL_MEAN, POOL_LINEAR, POOL_EXP = 0, 1, 2, 3
 POOL_MODES = {"max": POOL_MAX, "mean": POOL_MEAN, "linear": POOL_LINEAR, "exp": POOL_EXP}
+CRIT_BCE, CRIT_MSE = 0, 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsed_hip.so")
@@ -103,6 +104,12 @@ PROTOTYPES = {
     "sed_clip_pool_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sed_weak_bce_ws_bytes": (_Z, [_I, _I, _I]),
     "sed_weak_bce_fwd_bwd": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
+    "sed_bce_sel_ws_bytes": (_Z, [_I, _I, _I]),
+    "sed_bce_sel_fwd_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
+    "sed_weak_bce_fwd_bwd_ex": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
+    "sed_frame_mse_ws_bytes": (_Z, [_I, _I, _I]),
+    "sed_frame_mse_fwd_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P]),
+    "sed_ema_update": (_I, [_P, _P, _Z, _D, _P]),
     "sed_head_bwd_ws_floats": (_Z, [_I, _I, _I, _I]),
     "sed_head_bwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sed_adam_amsgrad_step": (_I, [_P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _I, _F, _P]),

@@ -19,6 +19,11 @@
 //   dpre_i = weight * grad_scale / (B*K) * dl/dP * dP/dp_i * p_i q_i, rounded once to fp32
 // (tests/weak_formula.py is the same in numpy).  Y is the clip label [B][K], or the maximum of the strong target over the first N
 // frames, taken here; it may be soft.
+// sed_weak_bce_fwd_bwd_ex adds two things to the same kernels.  A clip selection, clip_sel [B] bytes (nonzero: the clip takes part):
+// the mean is then over S*K for the S selected clips, counted here; unselected clips get no loss term and gradient exactly 0 (under
+// accumulate their cells are not touched); S = 0 gives loss term 0 and gradient 0.  And a criterion: SED_CRIT_BCE is the l above,
+// SED_CRIT_MSE is l = (P - Y)^2, dl/dP = 2 (P - Y), without the recall factor (the clip-level consistency loss of a mean teacher,
+// Y its clip probabilities).  Without a selection and with SED_CRIT_BCE every value takes the path it always took.
 //
 // Shape: the work is small (tens to hundreds of thousands of logits) and latency-bound, so it is spread wide and takes two launches.
 // First launch: one workgroup of 256 threads per (b, k) row -- strided partial sums in a fixed order, a fixed LDS tree -- leaves the
@@ -26,9 +31,7 @@
 // of its [Tt][K] slab, coalesced, for the partial maxima of every class (one workgroup per row reading its own column would pull
 // each 128-byte line K times).  Second launch: one thread per logit forms dpre from its row's workspace entries, and workgroup 0 adds
 // the B*K row losses in a fixed order.  No atomics, and no sum depends on an order that could vary: the same bits on every run.
-#include "common.h"
-
-#include <math.h>
+#include "loss_common.h"
 
 #define WEAK_SLICE_VALUES 8192      // target values per label workgroup (32 per thread)
 #define WEAK_MAX_SLICES 64          // per clip; sed_weak_bce_ws_bytes() sizes the partial maxima for it
@@ -47,27 +50,11 @@ struct WeakParams {
     int rows, nslice, slice_frames;      // rows = B*K; the first N target frames in nslice slices of slice_frames
     int target_frames, mode, accumulate;
     double wpos, coef, loss_scale;       // recall factor; weight * grad_scale / (B*K); weight / (B*K)
+    const unsigned char* clip_sel;       // [B], nonzero: the clip takes part; NULL: all do, with coef and loss_scale as above
+    int B, criterion;                    // SED_CRIT_BCE or SED_CRIT_MSE
+    double wg, wt;                       // weight * grad_scale and weight: with clip_sel the mean is over S*K, S counted here
     size_t total;            // B*t*K
 };
-
-// fixed-order tree over the 256 threads' values; the total is valid in every thread
-__device__ __forceinline__ double block_sum(double v, double* sm) {
-    const int tid = threadIdx.x;
-    __syncthreads();                 // sm may still be read from the previous reduction
-    sm[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sm[tid] += sm[tid + s];
-        __syncthreads();
-    }
-    return sm[0];
-}
-
-__device__ __forceinline__ void sigmoids(double x, double& p, double& q) {
-    p = 1.0 / (1.0 + exp(-x));
-    q = 1.0 / (1.0 + exp(x));
-}
 
 // maxima of one slice of a clip's strong target, for every class: thread = (frame offset fo, class kk), so that a wave reads
 // consecutive floats of the [Tt][K] slab; classes beyond 256 take further passes
@@ -197,19 +184,29 @@ __device__ __forceinline__ double clip_label(const WeakParams& a, int r, int b, 
 
 __global__ __launch_bounds__(256) void weak_grad_kernel(const WeakParams a) {
     __shared__ double sm[256];
+    __shared__ int smi[256];
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    double coef = a.coef, loss_scale = a.loss_scale;
+    if (a.clip_sel != nullptr) {             // the mean over the selected clips; S == 0: no loss, no gradient
+        const int S = selected_count(a.clip_sel, a.B, smi);
+        coef = S > 0 ? a.wg / ((double)S * (double)a.K) : 0.0;
+        loss_scale = S > 0 ? a.wt / ((double)S * (double)a.K) : 0.0;
+    }
     if (a.dpre != nullptr && idx < a.total) {
         const int k = (int)(idx % a.K);
         const size_t bt = idx / a.K;
         const int i = (int)(bt % a.t), b = (int)(bt / a.t), r = b * a.K + k;
+        const bool off = a.clip_sel != nullptr && a.clip_sel[b] == 0;      // not selected: exactly 0, or what was there
         double v = 0.0;
-        if (i < a.nrows) {
+        if (i < a.nrows && !off) {
             const double* __restrict__ st = a.stats + (size_t)r * 4;
             const double P = st[0], Q = st[1], den = st[2];
             const bool takes_part = a.mode == SED_POOL_MAX ? i == (int)st[3] : !(a.mode == SED_POOL_LINEAR && den == 0.0);
             if (takes_part) {
                 const double Y = clip_label(a, r, b, k);
-                const double g = a.coef * (-a.wpos * Y / fmax(P, 1e-12) + (1.0 - Y) / fmax(Q, 1e-12));       // coef * dl/dP
+                const double g = a.criterion == SED_CRIT_MSE
+                                     ? coef * (2.0 * (P - Y))
+                                     : coef * (-a.wpos * Y / fmax(P, 1e-12) + (1.0 - Y) / fmax(Q, 1e-12));       // coef * dl/dP
                 double p, q;
                 sigmoids((double)a.pre[idx], p, q);
                 const int left = a.N - i * a.ratio;
@@ -222,18 +219,20 @@ __global__ __launch_bounds__(256) void weak_grad_kernel(const WeakParams a) {
                 v = g * dP * (p * q);
             }
         }
-        a.dpre[idx] = a.accumulate ? a.dpre[idx] + (float)v : (float)v;
+        if (!(off && a.accumulate)) a.dpre[idx] = a.accumulate ? a.dpre[idx] + (float)v : (float)v;
     }
     if (blockIdx.x != 0) return;
     double s = 0.0;
     for (int r = threadIdx.x; r < a.rows; r += 256) {
+        if (a.clip_sel != nullptr && a.clip_sel[r / a.K] == 0) continue;
         const double P = a.stats[(size_t)r * 4], Q = a.stats[(size_t)r * 4 + 1];
         const double Y = clip_label(a, r, r / a.K, r % a.K);
-        s -= a.wpos * Y * fmax(log(P), -100.0) + (1.0 - Y) * fmax(log(Q), -100.0);
+        if (a.criterion == SED_CRIT_MSE) s += (P - Y) * (P - Y);
+        else s -= a.wpos * Y * fmax(log(P), -100.0) + (1.0 - Y) * fmax(log(Q), -100.0);
     }
     s = block_sum(s, sm);
     if (threadIdx.x == 0) {
-        const float v = (float)(s * a.loss_scale);
+        const float v = (float)(s * loss_scale);
         a.loss[0] = a.accumulate ? a.loss[0] + v : v;
     }
 }
@@ -270,10 +269,13 @@ extern "C" int sed_clip_pool_fwd(const float* pre, float* clip_prob, int B, int 
     return 0;
 }
 
-extern "C" int sed_weak_bce_fwd_bwd(const float* pre, const float* target, int target_frames, float* clip_prob, float* loss,
-                                    float* dpre, int accumulate, int B, int t, int K, int ratio, int Tt, int mode,
-                                    float recall_factor, float weight, float grad_scale, void* workspace, void* stream) {
+extern "C" int sed_weak_bce_fwd_bwd_ex(const float* pre, const float* target, int target_frames, const unsigned char* clip_sel,
+                                       int criterion, float* clip_prob, float* loss, float* dpre, int accumulate, int B, int t, int K,
+                                       int ratio, int Tt, int mode, float recall_factor, float weight, float grad_scale,
+                                       void* workspace, void* stream) {
     WeakParams p = {};
+    SED_REQUIRE(criterion == SED_CRIT_BCE || criterion == SED_CRIT_MSE, "criterion is SED_CRIT_BCE or SED_CRIT_MSE");
+    p.clip_sel = clip_sel; p.criterion = criterion;
     if (int rc = weak_geometry(p, B, t, K, ratio, Tt, mode)) return rc;
     SED_REQUIRE(target_frames == 0 || target_frames == Tt, "target_frames is 0 (clip labels [B][K]) or Tt (strong labels [B][Tt][K])");
     SED_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate is 0 or 1");
@@ -289,6 +291,9 @@ extern "C" int sed_weak_bce_fwd_bwd(const float* pre, const float* target, int t
     p.wpos = (double)recall_factor;
     p.coef = (double)weight * (double)grad_scale / (double)p.rows;
     p.loss_scale = (double)weight / (double)p.rows;
+    p.B = B;
+    p.wg = (double)weight * (double)grad_scale;
+    p.wt = (double)weight;
     if (target_frames != 0) {        // slices of about WEAK_SLICE_VALUES target values, none of them empty
         size_t ns = cdivz((size_t)p.N * K, WEAK_SLICE_VALUES);
         if (ns > WEAK_MAX_SLICES) ns = WEAK_MAX_SLICES;
@@ -302,4 +307,11 @@ extern "C" int sed_weak_bce_fwd_bwd(const float* pre, const float* target, int t
     weak_grad_kernel<<<(unsigned)nblk, 256, 0, st>>>(p);
     SED_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int sed_weak_bce_fwd_bwd(const float* pre, const float* target, int target_frames, float* clip_prob, float* loss,
+                                    float* dpre, int accumulate, int B, int t, int K, int ratio, int Tt, int mode,
+                                    float recall_factor, float weight, float grad_scale, void* workspace, void* stream) {
+    return sed_weak_bce_fwd_bwd_ex(pre, target, target_frames, nullptr, SED_CRIT_BCE, clip_prob, loss, dpre, accumulate, B, t, K, ratio, Tt,
+                                   mode, recall_factor, weight, grad_scale, workspace, stream);
 }

@@ -36,13 +36,30 @@ def _features(rng, y, mel_bins, snr=1.6):
 
 
 class SyntheticSedDataset(Dataset):
-    def __init__(self, n_train_crops=256, crop=240, n_val=6, val_frames=808, mel_bins=64, classes=1, seed=0):
+    def __init__(self, n_train_crops=256, crop=240, n_val=6, val_frames=808, mel_bins=64, classes=1, seed=0, label_kinds=None):
+        """label_kinds: None, or three shares (strong, weak, unlabelled) >= 0: every training clip gets a fixed kind 0 / 1 / 2
+        drawn with those probabilities from a generator of its own (the clips are the same with and without it), and
+        __getitem__ returns (features, events, kind).  A weak clip's events carry its clip label -- the maximum over its frames
+        -- on every frame; an unlabelled clip's are all 0.  Validation recordings keep their frame labels."""
         rng = np.random.default_rng(seed)
         self.crop, self.mel_bins, self.classes = crop, mel_bins, classes
         self.train = []
         for _ in range(n_train_crops):
             y = _events(rng, crop, classes, rate=0.15, min_run=8)
             self.train.append((_features(rng, y, mel_bins)[None], y))
+        self.kinds = None
+        if label_kinds is not None:
+            shares = np.asarray(label_kinds, dtype=np.float64)
+            if shares.shape != (3,) or not (shares >= 0).all() or not np.isfinite(shares).all() or shares.sum() <= 0:
+                raise ValueError(f"label_kinds is three shares >= 0, not all 0 (got {label_kinds!r})")
+            self.kinds = np.random.default_rng([seed, 1]).choice(3, size=n_train_crops, p=shares / shares.sum()).astype(np.int64)
+            for i, kind in enumerate(self.kinds):
+                f, y = self.train[i]
+                if kind == 1:
+                    y = np.broadcast_to(y.max(axis=0, keepdims=True), y.shape).copy()
+                elif kind == 2:
+                    y = np.zeros_like(y)
+                self.train[i] = (f, y)
         self.val = []
         for i in range(n_val):
             y = _events(rng, val_frames, classes, rate=0.15, min_run=8)
@@ -53,6 +70,8 @@ class SyntheticSedDataset(Dataset):
 
     def __getitem__(self, idx):
         f, y = self.train[idx]
+        if self.kinds is not None:
+            return torch.from_numpy(f), torch.from_numpy(y), torch.tensor(int(self.kinds[idx]))
         return torch.from_numpy(f), torch.from_numpy(y)
 
     def get_validation_sampler(self, max_validate_num=None):

@@ -106,6 +106,9 @@ class _Plan:
     dx_in: torch.Tensor = None      # (B, 1, T, F) fp32 input gradient of the Cin = 1 model path (the last backward(need_dx=True))
     weak_ws: torch.Tensor = None    # workspace of the weak-label loss (csrc/sed_weak.hip), allocated at its first use
     clip_prob: torch.Tensor = None  # (B, K) clip probabilities of the last weak-label loss / clip_probs()
+    semi_ws: torch.Tensor = None    # workspace of the label-kind / mean-teacher losses (csrc/sed_semi.hip), allocated at their first use
+    consistency: torch.Tensor = None    # (2,) the frame and clip consistency terms of the last mean-teacher loss
+    teacher_clip: torch.Tensor = None   # (B, K) the teacher's pooled clip probabilities
 
 
 class KernelTimer:
@@ -710,36 +713,93 @@ class CnnEngine(OptimizerExtMixin):
         return out
 
     def loss_and_grad(self, p: _Plan, target: torch.Tensor, recall_factor: float, need_grad: bool = True,
-                      grad_scale: float = 1.0, weak=None) -> torch.Tensor:
+                      grad_scale: float = 1.0, weak=None, kind=None, teacher_pre=None, consistency=None) -> torch.Tensor:
         """WeightedBCE on the virtually interpolated logits; fills plan.dpre; returns plan.loss (1,).
         weak: None, or (mode, weight, only) -- the pooled clip-level loss of csrc/sed_weak.hip, mode one of max / mean / linear /
         exp, scaled by weight.  only=False: the strong kernel runs as always, then the weak loss of the same (B, T, K) target is
         added on top of plan.loss and plan.dpre.  only=True: the weak loss alone; the target may then be (B, K) clip labels.
-        None launches exactly what it always did."""
-        if weak is None:
+        kind: None, or an integer (B,) device tensor, 0 = strongly labelled, 1 = weakly labelled, 2 = unlabelled: the strong term
+        then takes the clips with kind == 0 (sed_bce_sel_fwd_bwd) and the weak term those with kind <= 1 (sed_weak_bce_fwd_bwd_ex);
+        the clip label of the weak term is the maximum over the clip's target frames as always, so a weak clip's target carries
+        its clip label on every frame.  Each term is a mean over its own clips.
+        teacher_pre: None, or the (B, t, K) logits a mean teacher gave for the same clips; consistency is then the weight of the
+        consistency terms over all clips, added on top: the frame MSE (csrc/sed_semi.hip) and, with a weak pooling, the MSE of
+        the pooled clip probabilities.  Their values land in plan.consistency (2,): frame, clip.
+        All of them None launches exactly what it always did."""
+        if weak is None and kind is None and teacher_pre is None:
             if not (target.is_cuda and target.dtype == torch.float32 and target.dim() == 3):
                 raise ValueError("target must be a float32 CUDA tensor (B, T, K)")
             target = target.contiguous()
             self._strong_loss(p, target, recall_factor, need_grad, grad_scale)
             return p.loss
-        mode, weight, only = weak
-        mode_id = check_pooling(mode)
         if self.head == "none":
-            raise ValueError("the weak-label loss needs a model with a classification head")
+            raise ValueError("the weak-label loss needs a model with a classification head" if weak is not None else
+                             "label kinds and the mean teacher need a model with a classification head")
+        mode, weight, only = weak if weak is not None else (None, 0.0, False)
+        mode_id = check_pooling(mode) if weak is not None else None
         if not (target.is_cuda and target.dtype == torch.float32 and target.dim() in ((2, 3) if only else (3,))):
             raise ValueError("target must be a float32 CUDA tensor (B, T, K) or, for the weak loss alone, (B, K) clip labels")
         if target.shape[0] != p.B or target.shape[-1] != self.K:
             raise ValueError(f"target {tuple(target.shape)} does not fit {p.B} clips of {self.K} classes")
         target = target.contiguous()
-        if not only:
-            self._strong_loss(p, target, recall_factor, need_grad, grad_scale)
-        self._weak_bufs(p)
+        sel_strong = sel_weak = None
+        if kind is not None:
+            if not (kind.is_cuda and kind.dim() == 1 and kind.shape[0] == p.B and not kind.dtype.is_floating_point
+                    and kind.dtype != torch.bool):
+                raise ValueError(f"kind must be an integer CUDA tensor ({p.B},): 0 strong, 1 weak, 2 unlabelled")
+            sel_strong, sel_weak = (kind == 0).to(torch.uint8), (kind <= 1).to(torch.uint8)
+        if teacher_pre is not None:
+            if not (teacher_pre.is_cuda and teacher_pre.dtype == torch.float32 and teacher_pre.shape == p.pre.shape
+                    and teacher_pre.is_contiguous()):
+                raise ValueError(f"teacher_pre must be a contiguous float32 CUDA tensor {tuple(p.pre.shape)}")
+            if consistency is None or not (0.0 <= float(consistency) < float("inf")):
+                raise ValueError(f"teacher_pre needs a finite consistency weight >= 0 (got {consistency!r})")
+        if kind is not None or teacher_pre is not None:
+            self._semi_bufs(p)
+        dpre = L.ptr(p.dpre) if need_grad else None
         frames = target.shape[1] if target.dim() == 3 else 0
-        self._k("sed_weak_bce_fwd_bwd", self.lib.sed_weak_bce_fwd_bwd, L.ptr(p.pre), L.ptr(target), frames, L.ptr(p.clip_prob),
-                L.ptr(p.loss), L.ptr(p.dpre) if need_grad else None, 0 if only else 1, p.B, p.t_out, self.K, self.ratio,
-                frames if frames else p.t_out * self.ratio, mode_id, float(recall_factor), float(weight), float(grad_scale),
-                L.ptr(p.weak_ws), _stream())
+        Tt = frames if frames else p.t_out * self.ratio
+        dims = (p.B, p.t_out, self.K, self.ratio, Tt)
+        if not only:
+            if kind is None:
+                self._strong_loss(p, target, recall_factor, need_grad, grad_scale)
+            else:
+                self._k("sed_bce_sel_fwd_bwd", self.lib.sed_bce_sel_fwd_bwd, L.ptr(p.pre), L.ptr(target), L.ptr(sel_strong), L.ptr(p.loss),
+                        dpre, 0, *dims, float(recall_factor), 1.0, float(grad_scale), L.ptr(p.semi_ws), _stream())
+        if weak is not None:
+            self._weak_bufs(p)
+            if kind is None:
+                self._k("sed_weak_bce_fwd_bwd", self.lib.sed_weak_bce_fwd_bwd, L.ptr(p.pre), L.ptr(target), frames, L.ptr(p.clip_prob),
+                        L.ptr(p.loss), dpre, 0 if only else 1, *dims, mode_id, float(recall_factor), float(weight), float(grad_scale),
+                        L.ptr(p.weak_ws), _stream())
+            else:
+                self._k("sed_weak_bce_fwd_bwd_ex", self.lib.sed_weak_bce_fwd_bwd_ex, L.ptr(p.pre), L.ptr(target), frames,
+                        L.ptr(sel_weak), L.CRIT_BCE, L.ptr(p.clip_prob), L.ptr(p.loss), dpre, 0 if only else 1, *dims, mode_id,
+                        float(recall_factor), float(weight), float(grad_scale), L.ptr(p.weak_ws), _stream())
+        if teacher_pre is None:
+            return p.loss
+        cw = float(consistency)
+        # each term into its own zeroed cell (0 + term is the term), the gradient on top of plan.dpre; then one add per term
+        p.consistency.zero_()
+        self._k("sed_frame_mse_fwd_bwd", self.lib.sed_frame_mse_fwd_bwd, L.ptr(p.pre), L.ptr(teacher_pre), None, L.ptr(p.consistency),
+                dpre, 1, *dims, cw, float(grad_scale), L.ptr(p.semi_ws), _stream())
+        p.loss.add_(p.consistency[0:1])
+        if weak is not None:
+            self._k("sed_clip_pool_fwd", self.lib.sed_clip_pool_fwd, L.ptr(teacher_pre), L.ptr(p.teacher_clip), p.B, p.t_out, self.K,
+                    self.ratio, Tt, mode_id, _stream())
+            self._k("sed_weak_bce_fwd_bwd_ex", self.lib.sed_weak_bce_fwd_bwd_ex, L.ptr(p.pre), L.ptr(p.teacher_clip), 0, None, L.CRIT_MSE,
+                    L.ptr(p.clip_prob), L.ptr(p.consistency[1:2]), dpre, 1, *dims, mode_id, float(recall_factor), cw,
+                    float(grad_scale), L.ptr(p.weak_ws), _stream())
+            p.loss.add_(p.consistency[1:2])
         return p.loss
+
+    def _semi_bufs(self, p: _Plan):
+        if p.semi_ws is None:
+            dev = p.pre.device
+            nb = max(self.lib.sed_bce_sel_ws_bytes(p.B, p.t_out, self.K), self.lib.sed_frame_mse_ws_bytes(p.B, p.t_out, self.K))
+            p.semi_ws = torch.empty(max(1, nb // 8), dtype=torch.float64, device=dev)
+            p.consistency = torch.zeros(2, dtype=torch.float32, device=dev)
+            p.teacher_clip = torch.empty((p.B, self.K), dtype=torch.float32, device=dev)
 
     def _strong_loss(self, p: _Plan, target: torch.Tensor, recall_factor: float, need_grad: bool, grad_scale: float):
         self._k("sed_bce_fwd_bwd", self.lib.sed_bce_fwd_bwd, L.ptr(p.pre), L.ptr(target), L.ptr(p.loss),

@@ -48,6 +48,8 @@ def build_parser():
     p.add_argument("--clip_pooling", default=None, choices=["max", "mean", "linear", "exp"],
                    help="also print and write 'clip_probs' (classes,): the frame probabilities pooled over the recording into one "
                         "clip probability per class, the way the weak-label loss pools them")
+    p.add_argument("--teacher", action="store_true",
+                   help="load the mean teacher's weights (the checkpoint's 'teacher' entry, written by training with --mean_teacher)")
     return p
 
 
@@ -91,7 +93,8 @@ def saliency_maps(model, x):
 
 
 def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, precision="bf16", mel_bins=None, saliency=False,
-               host_resample=False, cfg=None, median_window=1, low_threshold=None, max_gap=0, min_len=1, clip_pooling=None):
+               host_resample=False, cfg=None, median_window=1, low_threshold=None, max_gap=0, min_len=1, clip_pooling=None,
+               teacher=False):
     """cfg: a SpectogramConfig (default REF_NATIVE).  The file's PCM is downmixed and resampled to cfg.working_sample_rate on the
     device (dataset_utils.AudioIngest); host_resample=True takes the float64 scipy path instead.
     median_window / max_gap / min_len (frames) and low_threshold are utils.event_utils.decode_events's: the result's 'events'
@@ -99,7 +102,8 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     they are the runs of probabilities > threshold, and 'decisions' / 'onset_frames' are what they always were; otherwise those two
     follow the decoded events.
     clip_pooling: None, or max / mean / linear / exp: the result gains 'clip_probs' (channels, classes), the frame probabilities
-    pooled over the recording on the device (CnnEngine.clip_probs)."""
+    pooled over the recording on the device (CnnEngine.clip_probs).
+    teacher: load the checkpoint's 'teacher' entry (the mean teacher of a --mean_teacher training) in place of 'model'."""
     import dataclasses
     if clip_pooling is not None:
         from .engine import check_pooling
@@ -120,7 +124,12 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel).to(dev)
     model.set_precision(precision)
     checkpoint = torch.load(ckpt, map_location=dev)
-    model.load_state_dict(checkpoint["model"] if "model" in checkpoint else checkpoint)
+    if teacher:
+        if "teacher" not in checkpoint:
+            raise ValueError(f"{ckpt} holds no 'teacher' entry: it was not written by a mean-teacher training")
+        model.load_state_dict(checkpoint["teacher"])
+    else:
+        model.load_state_dict(checkpoint["model"] if "model" in checkpoint else checkpoint)
     model.eval()
     print("Preprocessing audio file..")
     if host_resample:
@@ -164,7 +173,7 @@ def main(argv=None):
     cfg = {"ref_native": spectogram_configs.REF_NATIVE, "bench": spectogram_configs.BENCH}[args.config]
     res = infer_file(args.audio_file, args.ckpt, args.device, args.mean_std, args.threshold, args.precision, args.mel_bins,
                      args.saliency, args.host_resample, cfg, **event_options(args, cfg.frames_per_second),
-                     clip_pooling=getattr(args, "clip_pooling", None))
+                     clip_pooling=getattr(args, "clip_pooling", None), teacher=getattr(args, "teacher", False))
     os.makedirs(args.outputs_dir, exist_ok=True)
     name = os.path.splitext(os.path.basename(args.audio_file))[0]
     fps = res["frames_per_second"]

@@ -113,11 +113,53 @@ def build_weak_parser():
     return p
 
 
+def build_semi_parser():
+    """The semi-supervised options (this build only), in a parser of their own like the weak-label options."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--mean_teacher", action="store_true",
+                   help="this build only: keep a teacher whose weights are an exponential moving average of the model's and add "
+                        "the MSE between the model's and the teacher's frame (and, with --weak_labels, clip) probabilities")
+    p.add_argument("--ema_decay", type=float, default=0.999, help="--mean_teacher: the EMA factor, in [0, 1)")
+    p.add_argument("--consistency_weight", type=float, default=2.0, help="--mean_teacher: factor on the consistency terms (>= 0)")
+    p.add_argument("--consistency_rampup", type=int, default=0,
+                   help="--mean_teacher: steps over which the consistency weight is ramped up (0 = constant)")
+    p.add_argument("--eval_teacher", action="store_true", help="--mean_teacher: the periodic evaluation runs the teacher")
+    p.add_argument("--label_kinds", type=str, default=None, metavar="S:W:U",
+                   help="--dataset_name synthetic only: the shares of strongly labelled, weakly labelled and unlabelled clips, "
+                        "e.g. 1:2:5; the frame-level loss then takes the strong clips and the clip-level loss the labelled ones")
+    return p
+
+
 def build_full_parser():
-    """What main() parses: build_parser(), build_event_parser(), build_augment_parser() and build_weak_parser() together."""
+    """What main() parses: build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser() and
+    build_semi_parser() together."""
     return argparse.ArgumentParser(description="SED training on MI355X",
-                                   parents=[build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser()],
+                                   parents=[build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser(),
+                                            build_semi_parser()],
                                    conflict_handler="resolve")
+
+
+def parse_label_kinds(text):
+    """'S:W:U' -> three shares (floats >= 0, not all 0) of strong, weak and unlabelled clips; None for None"""
+    if text is None:
+        return None
+    parts = str(text).split(":")
+    try:
+        shares = tuple(float(v) for v in parts)
+    except ValueError:
+        shares = ()
+    if len(parts) != 3 or len(shares) != 3 or not all(0.0 <= v < float("inf") for v in shares) or sum(shares) <= 0.0:
+        raise ValueError(f"--label_kinds is S:W:U, three shares >= 0 that are not all 0 (e.g. 1:2:5), '{text}' given")
+    return shares
+
+
+def semi_options(args):
+    """the train() keyword arguments of --mean_teacher and its parameters (a Namespace built by hand may lack any of them)"""
+    if not getattr(args, "mean_teacher", False):
+        return {}
+    return {"mean_teacher": True, "ema_decay": float(getattr(args, "ema_decay", 0.999)),
+            "consistency_weight": float(getattr(args, "consistency_weight", 2.0)),
+            "consistency_rampup": int(getattr(args, "consistency_rampup", 0)), "eval_teacher": bool(getattr(args, "eval_teacher", False))}
 
 
 def weak_options(args):
@@ -188,7 +230,8 @@ def get_spectogram_dataset_model_and_criterion(args, device):
     name = args.dataset_name.lower()
     if name == "synthetic":
         dataset = SyntheticSedDataset(n_train_crops=max(256, 4 * args.batch_size), crop=cfg.train_crop_size * 8,
-                                      classes=cfg.classes_num, mel_bins=n_mel)
+                                      classes=cfg.classes_num, mel_bins=n_mel,
+                                      label_kinds=parse_label_kinds(getattr(args, "label_kinds", None)))
         descriptor = cfg.cfg_descriptor
     else:
         if name == "tau":
@@ -278,6 +321,24 @@ def validate_args(args):
                              "(the M5 model has no time axis in its output)")
         from .train import check_weak_options
         check_weak_options(**weak_options(args))
+    semi = semi_options(args)
+    kinds = parse_label_kinds(getattr(args, "label_kinds", None))
+    if getattr(args, "eval_teacher", False) and not semi:
+        raise ValueError("--eval_teacher needs --mean_teacher")
+    if semi or kinds is not None:
+        if args.train_features.lower() == "waveform":
+            raise ValueError("--mean_teacher and --label_kinds work on frame-wise outputs: they need --train_features Spectogram "
+                             "(the M5 model has no time axis in its output)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 and semi:
+            raise ValueError("--mean_teacher is the single-process path")
+    if kinds is not None and args.dataset_name.lower() != "synthetic":
+        raise ValueError("--label_kinds assigns kinds to the clips of --dataset_name synthetic only")
+    if kinds is not None and getattr(args, "spec_augment", False) and getattr(args, "mixup_prob", 0.0) > 0:
+        raise ValueError("--label_kinds with --spec_augment needs --mixup_prob 0: mixup mixes the features and labels of two clips but "
+                         "not their kinds, so a strong clip mixed with a weak or unlabelled partner would keep wrong frame labels")
+    if semi:
+        from .train import check_semi_options
+        check_semi_options(**{k: v for k, v in semi.items() if k != "eval_teacher"})
 
 
 def optimizer_options(args):
@@ -355,7 +416,7 @@ def main(argv=None):
     train(model, dataloader, criterion, num_steps=args.num_train_steps,
           outputs_dir=os.path.join(args.outputs_root, train_name), device=device, lr=args.lr,
           log_freq=args.log_freq, event_eval=event_eval_options(args, frames_per_second(args)),
-          batch_augment=synthetic_batch_augment(args), **optimizer_options(args), **weak_options(args))
+          batch_augment=synthetic_batch_augment(args), **optimizer_options(args), **weak_options(args), **semi_options(args))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

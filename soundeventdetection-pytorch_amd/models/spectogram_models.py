@@ -253,6 +253,17 @@ class Cnn_AvgPooling(nn.Module):
         self.engine = self._make_engine(precision)
         return self
 
+    def clone_without_engines(self):
+        """A deep copy of the parameters, buffers and settings with an engine of its own (the mean teacher of FusedTrainer).  An
+        engine holds the library handle and the plans' device buffers, neither of which is to be copied: deepcopy's memo maps
+        an object's id to its copy, so entering the engines there as None makes the copy carry None in their place."""
+        import copy
+        memo = {id(self.engine): None}
+        memo.update({id(blk._eng): None for blk in self.conv_blocks if blk._eng is not None})
+        twin = copy.deepcopy(self, memo)
+        twin.engine = twin._make_engine(twin.precision)
+        return twin
+
     def _tensor_dict(self) -> Dict[str, torch.Tensor]:
         d = {n: p.data for n, p in self.named_parameters()}
         d.update({n: b for n, b in self.named_buffers()})

@@ -17,6 +17,7 @@ per rank (the torch DDP convention); optimizer state is replicated.
 from __future__ import annotations
 
 import json
+import math
 import os
 from time import time
 from typing import Dict, List, Optional
@@ -39,9 +40,10 @@ class FlatParams:
     of another), in nn.Module.parameters() order, each start padded to 4 floats.  The per-block
     slices [start, end) are the all-reduce buckets."""
 
-    def __init__(self, model: torch.nn.Module, n_buckets: Optional[int] = None):
+    def __init__(self, model: torch.nn.Module, n_buckets: Optional[int] = None, grads: bool = True):
         """n_buckets: how many all-reduce buckets the per-group slices are merged into (None: $SED_DDP_BUCKETS, default 2;
-        0: one bucket per top-level group, the round-1 layout kept for A/B runs; 1: a single flat all-reduce)."""
+        0: one bucket per top-level group, the round-1 layout kept for A/B runs; 1: a single flat all-reduce).
+        grads=False: no gradient buffer (a mean teacher's parameters are never differentiated)."""
         named = list(model.named_parameters())
         if not named:
             raise ValueError("model has no parameters")
@@ -54,7 +56,7 @@ class FlatParams:
             off += (p.numel() + 3) // 4 * 4
         self.numel = off
         self.p = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.g = torch.zeros(off, dtype=torch.float32, device=dev)
+        self.g = torch.zeros(off, dtype=torch.float32, device=dev) if grads else None
         self.P: Dict[str, torch.Tensor] = {}
         self.G: Dict[str, torch.Tensor] = {}
         for n, p in named:
@@ -63,7 +65,8 @@ class FlatParams:
             view.copy_(p.data)
             p.data = view                      # the nn.Parameter now aliases the flat buffer
             self.P[n] = view
-            self.G[n] = self.g[o:o + p.numel()].view(p.shape)
+            if grads:
+                self.G[n] = self.g[o:o + p.numel()].view(p.shape)
         self.model = model
         self.groups = self._make_buckets()
         if n_buckets is None:
@@ -129,6 +132,15 @@ class FlatParams:
         return d
 
 
+def data_parallel_enabled(group=None) -> bool:
+    """True when the trainer runs its collectives on `group`: a process group of more than one rank, or any initialised group
+    under SED_DDP_FORCE=1 (test hook: the collectives then run on a world-size-1 group too, so that one GPU can execute the RCCL
+    path -- librccl, async handles, stream ordering -- tests/test_gpu_ddp.py)."""
+    import torch.distributed as dist
+    force = os.environ.get("SED_DDP_FORCE", "0") == "1"
+    return dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or force)
+
+
 class GradAllReducer:
     """Bucketed, overlapped gradient averaging over torch.distributed (RCCL on the GPU box, gloo
     in the CPU tests).  No-op for world_size 1.  `buckets`: [(keys, start, end)] from FlatParams (a bare (key, start, end)
@@ -137,10 +149,7 @@ class GradAllReducer:
     def __init__(self, flat_g: torch.Tensor, buckets, group=None):
         import torch.distributed as dist
         self.dist = dist
-        # SED_DDP_FORCE=1 (test hook): run the collectives on a world-size-1 group too, so that one GPU can execute the RCCL path
-        # (librccl, async handles, stream ordering) -- tests/test_gpu_ddp.py
-        force = os.environ.get("SED_DDP_FORCE", "0") == "1"
-        self.enabled = dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or force)
+        self.enabled = data_parallel_enabled(group)
         self.world = dist.get_world_size(group) if self.enabled else 1
         self.rank = dist.get_rank(group) if self.enabled else 0
         self.flat_g, self.group = flat_g, group
@@ -319,6 +328,42 @@ def check_weak_options(weak_pooling=None, weak_weight=1.0, weak_only=False, mode
     return weak_pooling, w, bool(weak_only)
 
 
+def check_semi_options(mean_teacher=False, ema_decay=0.999, consistency_weight=2.0, consistency_rampup=0, model=None):
+    """Validate the mean-teacher options of FusedTrainer / train() (host only, before any device work).  Returns None when
+    mean_teacher is off -- the step then launches exactly what it always did -- else (ema_decay, consistency_weight,
+    consistency_rampup)."""
+    if not mean_teacher:
+        return None
+    d, w = float(ema_decay), float(consistency_weight)
+    if not (0.0 <= d < 1.0):
+        raise ValueError(f"ema_decay must lie in [0, 1) (got {ema_decay!r})")
+    if not (0.0 <= w < float("inf")):
+        raise ValueError(f"consistency_weight must be finite and >= 0 (got {consistency_weight!r})")
+    if isinstance(consistency_rampup, bool) or int(consistency_rampup) != consistency_rampup or consistency_rampup < 0:
+        raise ValueError(f"consistency_rampup is a number of steps, an integer >= 0 (got {consistency_rampup!r})")
+    if model is not None:
+        if not hasattr(model, "conv_blocks"):
+            raise ValueError(f"the mean teacher compares frame probabilities over time: {type(model).__name__} has no time axis in "
+                             "its output (use Cnn_AvgPooling / Crnn_AvgPooling)")
+        if getattr(getattr(model, "engine", None), "head", "fc") == "none":
+            raise ValueError("the mean teacher needs a model with a classification head")
+    return d, w, int(consistency_rampup)
+
+
+def ema_factor(n: int, ema_decay: float) -> float:
+    """The teacher's EMA factor after the n-th step (n = 1, 2, ...): min(1 - 1/n, ema_decay), so the first update copies the
+    student and the early teacher is the plain average of the students so far."""
+    return min(1.0 - 1.0 / n, float(ema_decay))
+
+
+def consistency_weight_at(n: int, weight: float, rampup: int) -> float:
+    """The consistency weight at step n (n = 1, 2, ...): weight * exp(-5 (1 - min(n, R)/R)^2) for R = rampup > 0 (the sigmoid
+    ramp-up of Tarvainen and Valpola 2017), constant for R = 0."""
+    if rampup <= 0:
+        return float(weight)
+    return float(weight) * math.exp(-5.0 * (1.0 - min(n, rampup) / rampup) ** 2)
+
+
 def check_state_amsgrad(group, amsgrad: bool):
     """Refuse an optimizer state whose amsgrad flag is not the trainer's: the max_exp_avg_sq buffers exist on one side only."""
     got = bool(group.get("amsgrad", False))
@@ -336,7 +381,8 @@ class FusedTrainer:
                  group=None, graph: bool = False, sync_bn: bool = False, n_buckets: Optional[int] = None,
                  weight_decay: float = 0.0, decoupled_weight_decay: bool = False, amsgrad: bool = True,
                  max_grad_norm: Optional[float] = None, weak_pooling: Optional[str] = None, weak_weight: float = 1.0,
-                 weak_only: bool = False):
+                 weak_only: bool = False, mean_teacher: bool = False, ema_decay: float = 0.999, consistency_weight: float = 2.0,
+                 consistency_rampup: int = 0, teacher_augment=None):
         """graph=True (single process): after two eager steps per input shape the whole step -- forward, loss, backward,
         Adam-amsgrad with its step counter, learning rate and bias corrections in device memory -- is captured into a HIP
         graph and replayed.  For the reference's own small shapes (T = 30 crops, batch 4: ~90 launches of a few microseconds
@@ -352,7 +398,25 @@ class FusedTrainer:
         weak_pooling: None, or max / mean / linear / exp -- train from clip-level labels (csrc/sed_weak.hip): the frame
         probabilities are pooled over time and WeightedBCE is taken against the clip label, times weak_weight.  weak_only=False
         adds it to the strong loss, with the clip label taken from the (B, T, K) target on the device; weak_only=True trains on it
-        alone, and the target may be (B, K).  None launches nothing new."""
+        alone, and the target may be (B, K).  None launches nothing new.
+
+        mean_teacher: keep self.teacher, a copy of the model whose parameters are an exponential moving average of the
+        student's (csrc/sed_semi.hip), with its own engine, plans and flat parameter buffer.  Every step the teacher runs a
+        training-mode forward on teacher_augment(x) (a callable, None: x itself) and the student is pulled towards its frame
+        probabilities and, with a weak_pooling, its pooled clip probabilities: MSE terms over all clips times
+        consistency_weight, ramped up over the first consistency_rampup steps (consistency_weight_at).  After the optimizer step
+        teacher <- a_n teacher + (1 - a_n) student, a_n = ema_factor(n, ema_decay).  self.last_consistency is a device (2,)
+        tensor, the frame and clip terms of the last step.  Single process, eager steps only."""
+        self.semi = check_semi_options(mean_teacher, ema_decay, consistency_weight, consistency_rampup, model)
+        # every refusal comes before the teacher is made and before the model's parameters move into the flat buffer: a refused
+        # constructor leaves the model as it found it
+        if graph and self.semi is not None:
+            raise RuntimeError("graph=True does not capture the mean teacher (its weights change on the host's schedule)")
+        if self.semi is not None and data_parallel_enabled(group):
+            raise RuntimeError("mean_teacher is the single-process path (the teacher's BatchNorm statistics and the order of "
+                               "the EMA across ranks are not defined yet)")
+        self.teacher = self.teacher_flat = self.last_consistency = None
+        self.teacher_augment = teacher_augment
         (self.weight_decay, self.decoupled_weight_decay, self.amsgrad, self.max_grad_norm,
          self._opt_ext) = check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
         self.weak = check_weak_options(weak_pooling, weak_weight, weak_only, model)
@@ -363,6 +427,10 @@ class FusedTrainer:
         self._eager_seen = {}
         if not next(model.parameters()).is_cuda:
             raise RuntimeError("FusedTrainer needs the model on the GPU (model.to('cuda')); there is no CPU path")
+        if self.semi is not None:           # before the student's parameters become views of its flat buffer
+            self.teacher = model.clone_without_engines()
+            for p in self.teacher.parameters():
+                p.requires_grad_(False)
         self.flat = FlatParams(model, n_buckets)
         self.m = torch.zeros_like(self.flat.p)
         self.v = torch.zeros_like(self.flat.p)
@@ -380,6 +448,8 @@ class FusedTrainer:
             self.last_grad_norm = self._gn_out[0:1]     # device (1,), norm of the last step's averaged gradient; no sync
         self.step_count = 0
         self.reducer = GradAllReducer(self.flat.g, self.flat.buckets, group)
+        if self.teacher is not None:
+            self.teacher_flat = FlatParams(self.teacher, grads=False)
         self.sync_bn = bool(sync_bn) and self.reducer.enabled
         if self.reducer.enabled and hasattr(self.engine, "wg_flush_per_group"):
             self.engine.wg_flush_per_group = True      # weight gradients complete before their bucket's all-reduce goes out
@@ -409,16 +479,36 @@ class FusedTrainer:
             raise RuntimeError("model parameters were re-allocated after FusedTrainer was built "
                                "(e.g. model.to()); build the trainer after moving the model")
 
-    def forward_backward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        """One forward + loss + backward; gradients land in flat.g; returns the device loss (1,)."""
+    def forward_backward(self, x: torch.Tensor, y: torch.Tensor, kind: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One forward + loss + backward; gradients land in flat.g; returns the device loss (1,).
+        kind: None, or an integer (B,) device tensor of label kinds -- 0 strong, 1 weak, 2 unlabelled (CnnEngine.loss_and_grad)."""
         self._check_alias()
         eng = self.engine
+        if kind is not None:
+            if self.use_graph:
+                raise RuntimeError("graph=True does not take label kinds (the selections are made by torch comparisons per step)")
+            if not hasattr(self.model, "conv_blocks"):
+                raise ValueError(f"label kinds select clips of frame-wise targets: {type(self.model).__name__} has none")
+        teacher_pre = None
+        if self.teacher is not None:        # first: the teacher's forward, in training mode like the student's
+            if not self.teacher_flat.aliased():
+                raise RuntimeError("the teacher's parameters were re-allocated after FusedTrainer was built")
+            self.teacher.train()
+            xt = x if self.teacher_augment is None else self.teacher_augment(x)
+            teacher_pre = self.teacher.engine.forward(xt, self.teacher_flat.tensor_dict(), training=True).pre
+            self.teacher._nbt_pending += 1
+            self.teacher._fwd_serial += 1
         P = self.flat.tensor_dict()
         self.model.train()
         plan = eng.forward(x, P, training=True)
         self.model._nbt_pending += 1
         self.model._fwd_serial += 1
-        if self.weak is None:
+        if kind is not None or teacher_pre is not None:
+            cw = None if self.semi is None else consistency_weight_at(self.step_count + 1, self.semi[1], self.semi[2])
+            loss = eng.loss_and_grad(plan, y, self.recall_factor, weak=self.weak, kind=kind, teacher_pre=teacher_pre, consistency=cw)
+            if teacher_pre is not None:
+                self.last_consistency = plan.consistency
+        elif self.weak is None:
             loss = eng.loss_and_grad(plan, y, self.recall_factor)
         else:
             loss = eng.loss_and_grad(plan, y, self.recall_factor, weak=self.weak)
@@ -438,6 +528,9 @@ class FusedTrainer:
             self.engine.adam_step_ex(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self.lr, self.step_count,
                                      grad_scale=scale, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
                                      decoupled=self.decoupled_weight_decay, coef=self._coef)
+        if self.teacher is not None:
+            self.engine._k("sed_ema_update", self.engine.lib.sed_ema_update, L.ptr(self.teacher_flat.p), L.ptr(self.flat.p),
+                           self.flat.numel, ema_factor(self.step_count, self.semi[0]), torch.cuda.current_stream().cuda_stream)
         if self.step_count % LR_DECAY_FREQ == 0:       # train.py:108-110 (after that iteration's step)
             self.lr *= LR_DECAY
 
@@ -460,12 +553,14 @@ class FusedTrainer:
         if self.step_count % LR_DECAY_FREQ == 0:
             self.lr *= LR_DECAY
 
-    def train_step(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    def train_step(self, x: torch.Tensor, y: torch.Tensor, kind: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Returns the device loss buffer (1,) of this shape's plan: valid until the next step (clone to keep)."""
         if not self.use_graph:
-            loss = self.forward_backward(x, y)
+            loss = self.forward_backward(x, y) if kind is None else self.forward_backward(x, y, kind)
             self.optimizer_step()
             return loss
+        if kind is not None:
+            raise RuntimeError("graph=True does not take label kinds (the selections are made by torch comparisons per step)")
         key = (tuple(x.shape), tuple(y.shape))
         ent = self._graphs.get(key)
         if ent is None:
@@ -519,12 +614,17 @@ class FusedTrainer:
                  "weight_decay": self.weight_decay if self.weight_decay != 0.0 else 0, "amsgrad": self.amsgrad,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "decoupled_weight_decay": self.decoupled_weight_decay, "params": list(range(len(self.flat.names)))}
-        return {"state": state, "param_groups": [group]}
+        sd = {"state": state, "param_groups": [group]}
+        if self.teacher is not None:        # the mean teacher's parameters and BatchNorm buffers
+            sd["teacher"] = {k: v.clone() for k, v in self.teacher.state_dict().items()}
+        return sd
 
-    def load_state_dict(self, sd):
+    def load_state_dict(self, sd, teacher=None):
         """Resume from state_dict() output or from a torch.optim.Adam / AdamW state_dict of the same model whose amsgrad flag
         is this trainer's.  lr, betas and eps come from the state; weight decay, its kind and max_grad_norm stay as the
-        trainer was built."""
+        trainer was built.  The mean teacher is restored from `teacher` (a checkpoint of train() keeps it beside the optimizer
+        state: trainer.load_state_dict(ck['optimizer'], teacher=ck.get('teacher'))), else from sd['teacher'], else -- a state
+        from before the teacher -- it starts as a copy of the student as the model is now."""
         groups = sd["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != len(self.flat.names):
             raise ValueError("optimizer state does not match this model's parameter list")
@@ -546,6 +646,11 @@ class FusedTrainer:
                 self.vmax[o:o + k].copy_(st["max_exp_avg_sq"].reshape(-1))
             step = max(step, int(float(st["step"])))
         self.step_count = step
+        if self.teacher is not None:
+            if teacher is not None or "teacher" in sd:
+                self.teacher.load_state_dict(teacher if teacher is not None else sd["teacher"])
+            else:                           # a checkpoint from before the teacher: it starts as a copy of the student
+                self.teacher.load_state_dict(self.model.state_dict())
         if self.use_graph:
             self.hyper[0] = self.lr
             self.step_dev.fill_(step)
@@ -684,7 +789,8 @@ def summarize_validation(val_losses, recal_sets, precision_sets, APs):
 
 def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, device, *, weight_decay=0.0,
           decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None, event_eval=None, batch_augment=None,
-          weak_pooling=None, weak_weight=1.0, weak_only=False):
+          weak_pooling=None, weak_weight=1.0, weak_only=False, mean_teacher=False, ema_decay=0.999, consistency_weight=2.0,
+          consistency_rampup=0, teacher_augment=None, eval_teacher=False):
     """train.py:77-131.  `criterion` must be this package's WeightedBCE(multi_frame=True) (its
     recall_factor feeds the fused loss kernel).  The keyword-only optimizer options are FusedTrainer's (this build only; their
     defaults are the reference's Adam(amsgrad=True) without decay or clipping).  event_eval: None, or the keyword arguments of
@@ -692,7 +798,12 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
     batch_augment: None, or a callable (features, labels) -> (features, labels) applied to every device batch before the step
     (dataset.spectogram.augment.LogMelAugment for loaders that hand plain log-mel tensors over); validation never sees it.
     weak_pooling / weak_weight / weak_only: FusedTrainer's weak-label options.  A utils.common.WeakBCE as `criterion` is shorthand
-    for weak_only=True with its pooling and recall_factor; the loader may then hand (B, K) clip labels over."""
+    for weak_only=True with its pooling and recall_factor; the loader may then hand (B, K) clip labels over.
+    The loader yields (features, labels) or (features, labels, kind), kind the (B,) label kinds of FusedTrainer.train_step.
+    mean_teacher ... teacher_augment: FusedTrainer's mean-teacher options; eval_teacher=True runs every periodic evaluation on
+    trainer.teacher.  Checkpoints carry the teacher's state under 'teacher', beside 'optimizer' (resume with
+    trainer.load_state_dict(ck['optimizer'], teacher=ck['teacher'])).  batch_augment does not see the kinds: an augmentation that
+    mixes clips (mixup) must not be combined with them."""
     from .utils.common import WeakBCE, WeightedBCE
     check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
     if isinstance(criterion, WeakBCE):
@@ -700,6 +811,12 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
             raise ValueError(f"criterion pools with {criterion.pooling!r} but weak_pooling={weak_pooling!r}")
         weak_pooling, weak_only = criterion.pooling, True
     check_weak_options(weak_pooling, weak_weight, weak_only, model)
+    check_semi_options(mean_teacher, ema_decay, consistency_weight, consistency_rampup, model)
+    if eval_teacher and not mean_teacher:
+        raise ValueError("eval_teacher needs mean_teacher")
+    if mean_teacher and data_parallel_enabled():
+        raise RuntimeError("mean_teacher is the single-process path (the teacher's BatchNorm statistics and the order of the EMA "
+                           "across ranks are not defined yet)")
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("the MI355X training path needs device='cuda' (there is no CPU path)")
@@ -717,7 +834,10 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
     trainer = FusedTrainer(model, lr, recall_factor=criterion.recall_factor,
                            sync_bn=os.environ.get("SED_SYNC_BN", "0") == "1", weight_decay=weight_decay,
                            decoupled_weight_decay=decoupled_weight_decay, amsgrad=amsgrad, max_grad_norm=max_grad_norm,
-                           weak_pooling=weak_pooling, weak_weight=weak_weight, weak_only=weak_only)
+                           weak_pooling=weak_pooling, weak_weight=weak_weight, weak_only=weak_only, mean_teacher=mean_teacher,
+                           ema_decay=ema_decay, consistency_weight=consistency_weight, consistency_rampup=consistency_rampup,
+                           teacher_augment=teacher_augment)
+    eval_model = trainer.teacher if eval_teacher else model
     rank0 = (not trainer.reducer.enabled) or trainer.reducer.dist.get_rank() == 0
     log_path = os.path.join(outputs_dir, "progress.jsonl")
     losses: List[float] = []
@@ -726,13 +846,16 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
     world = trainer.reducer.world
     while iterations < num_steps:
         seen = 0
-        for (batch_features, event_labels) in data_loader:
+        for item in data_loader:
+            batch_features, event_labels = item[0], item[1]
+            kind = item[2].to(dev, non_blocking=True) if len(item) > 2 else None
             seen += 1
             batch_features = batch_features.to(dev, non_blocking=True).float()
             event_labels = event_labels.to(dev, non_blocking=True).float()
             if batch_augment is not None:
                 batch_features, event_labels = batch_augment(batch_features, event_labels)
-            loss = trainer.train_step(batch_features, event_labels)
+            loss = trainer.train_step(batch_features, event_labels) if kind is None else \
+                trainer.train_step(batch_features, event_labels, kind)
             losses.append(loss.clone())              # device scalars (the step's loss buffer is reused): no host sync
             iterations += 1
             if iterations % log_freq == 0:
@@ -742,17 +865,19 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
                 rec = {"epoch": epoch, "step": iterations, "train_loss": float(np.mean(host_losses)),
                        "im_sec": im_sec, "lr": trainer.lr}
                 if hasattr(data_loader.dataset, "get_validation_sampler"):
-                    rec.update(summarize_validation(*eval(model, data_loader, criterion, outputs_dir,
+                    rec.update(summarize_validation(*eval(eval_model, data_loader, criterion, outputs_dir,
                                                           iteration=iterations, device=dev, limit_val_samples=3)))
                     if event_eval is not None:
-                        rec.update(eval_events(model, data_loader, dev, limit_val_samples=3, **event_eval))
+                        rec.update(eval_events(eval_model, data_loader, dev, limit_val_samples=3, **event_eval))
                 if rank0:
                     print(f"epoch: {epoch}, step: {iterations}, loss: {host_losses[-1]:.2f}, "
                           f"im/sec: {im_sec:.1f}, lr: {trainer.lr:.8f}")
                     with open(log_path, "a") as f:
                         f.write(json.dumps(rec) + "\n")
-                    torch.save({"iterations": iterations, "model": model.state_dict(),
-                                "optimizer": trainer.state_dict()},
+                    ck = {"iterations": iterations, "model": model.state_dict(), "optimizer": trainer.state_dict()}
+                    if trainer.teacher is not None:
+                        ck["teacher"] = ck["optimizer"].pop("teacher")
+                    torch.save(ck,
                                os.path.join(outputs_dir, "checkpoints", f"iteration_{iterations}.pth"))
             if iterations == num_steps:
                 break
