@@ -285,8 +285,20 @@ def test_first_layer_kernels_at_any_width(L, dt, W):
     torch.cuda.synchronize()
     tol = 2.0 ** -7 if dt == "bf16" else 1e-5
     assert (host(z) - ref).abs().max().item() <= tol * ref.abs().max().item() + 1e-5
+    # statistics: the float64 sums of the float64 z and z^2 (the kernel sums its fp32 accumulators in either storage type) under the
+    # propagated gates of tests/test_gpu_c1_exact_oracle.py: z's gate gz = 4 (9 + 2) u sum |xp||w| through the sums, plus the thread's
+    # chain n_t = ceil(W / PPB) * 8 * ceil(bands / grid) and the PPB = 256 / (Cout / 8) lanes (one more for the fma of z^2)
+    assert not bool(torch.isnan(part).any()), "a partial row was not written"
     s = part.double().cpu().sum(0)
-    assert (s[0] - ref.sum((0, 2, 3))).abs().max().item() <= 1e-4 * ref.abs().sum().item() / Cout + 1e-3
+    u, ppb = 2.0 ** -24, 256 // (Cout // 8)
+    n_t = -(-W // ppb) * 8 * -(-(B * -(-H // 8)) // nparts)
+    gz = 4 * 11 * u * O.conv3x3_fwd(xn.abs(), w.to(F64).abs())
+    a1, a2 = ref.abs().sum((0, 2, 3)), (ref * ref).sum((0, 2, 3))
+    gate1 = gz.sum((0, 2, 3)) + 4 * (n_t + ppb) * u * a1
+    gate2 = (2 * ref.abs() * gz + gz * gz).sum((0, 2, 3)) + 4 * (n_t + ppb + 1) * u * a2
+    assert bool((gate1 <= 1e-4 * ref.abs().sum().item() / Cout + 1e-3).all())      # (never looser than the bound it replaces)
+    assert bool(((s[0] - ref.sum((0, 2, 3))).abs() <= gate1).all()), ((s[0] - ref.sum((0, 2, 3))).abs() / gate1).max().item()
+    assert bool(((s[1] - a2).abs() <= gate2).all()), ((s[1] - a2).abs() / gate2).max().item()
     dz = torch.randn(B, Cout, H, W, generator=g).to(F64)
     dz = rnd(dt, dz)
     ws = torch.empty(nparts, 9, Cout, device="cuda")
