@@ -624,6 +624,38 @@ int sed_decode_events(const float* prob, int B, int T, int K, float th_hi, float
 int sed_segment_counts(const unsigned char* decisions, const float* target, int B, int T, int Tt, int K, int seg_frames,
                        long long* counts, void* stream);
 
+/* ---- rank metrics (csrc/sed_rank.hip) ---------------------------------------------------------
+ * Corpus-level average precision, ROC-AUC and the best-F1 operating point per class: a key-only segmented radix sort and one scan.
+ * Every count is an integer and AP is a fixed-shape double sum: a given (n, K) and data give the same bits on every run.
+ *
+ * Scored elements, per class k: the first n = min(n_score, n_tgt) rows of score / target fp32 [rows][K] (classes innermost; the
+ * truncation of calculate_metrics).  An element is positive if target > 0.5 (the rule of sed_segment_counts).  A score is valid if
+ * 0 <= p <= 1 in fp32; -0 counts as +0.  key = (bits(p) << 1) | positive: below 2^31, ordered like (p, label).  NaN and
+ * out-of-range scores are packed as key 0 and counted in invalid[k].
+ * Tie groups: with the keys sorted, walk from the highest score down; a tie group g is a maximal run of equal key >> 1, tp_g / fp_g
+ * its positives / negatives, TP_g / n_g the positives / elements down to and including it, P = sum tp_g, Nneg = n - P.
+ *   AP          = sum_g (tp_g / P) * (TP_g / n_g) in double, the two divisions and the product in that order (sklearn's
+ *                 average_precision_score); NaN when P = 0.
+ *   auc2        = sum_g fp_g * (2 TP_{g-1} + tp_g), an integer: AUC = auc2 / (2 P Nneg) (undefined when P = 0 or Nneg = 0).
+ *   best point  = the group maximising F1_g = 2 TP_g / (n_g + P), chosen by exact 64-bit cross-multiplication, an F1 tie going to the
+ *                 higher score: best_tp = TP_g, best_npred = n_g, best_score = the group's score; the decision rule is
+ *                 p >= best_score.  P = 0: (0, 0, +1.0).
+ *
+ * sed_rank_pack: the append step; writes keys[k][offset .. offset + n) of the class-major uint32 buffer [K][capacity] and ADDS the
+ * number of invalid scores of class k to invalid[k] (the caller zeroes it once).  offset + n > capacity is refused.
+ * sed_rank_sort: sorts the first n keys of each of the K rows ascending; [n, capacity) of every row is left alone.
+ * sed_rank_curve: keys_sorted as sed_rank_sort leaves them -> ap double [K], counts uint64 [K][6] = (P, n, auc2, best_tp,
+ * best_npred, number of tie groups), best_score fp32 [K].  n = 0 is legal (P = 0; nothing that reads memory is launched).
+ * workspace (sort and curve; they may share it): sed_rank_ws_bytes(K, n) bytes, 16-byte aligned; 0 for a shape the calls refuse.
+ * K <= 65535, n and capacity <= 2^30.  sed_rank_tile: host-only, the keys one workgroup takes per pass (rows of any length work). */
+int sed_rank_tile(void);
+size_t sed_rank_ws_bytes(int K, size_t n);
+int sed_rank_pack(const float* score, const float* target, size_t n_score, size_t n_tgt, int K, unsigned* keys, size_t capacity,
+                  size_t offset, unsigned long long* invalid, void* stream);
+int sed_rank_sort(unsigned* keys, int K, size_t n, size_t capacity, void* workspace, void* stream);
+int sed_rank_curve(const unsigned* keys_sorted, int K, size_t n, size_t capacity, double* ap, unsigned long long* counts,
+                   float* best_score, void* workspace, void* stream);
+
 /* First-layer weight gradient WITHOUT the layer's pre-BN output (z1 is never read):
  *   dW1[c][k] = ca[c]*A[c][k] + cb[c]*sum_j w1[c][j]*G[j][k] + cc[c]*sx[k],
  * A = plain sed_conv3x3_c1_wgrad of g (summed partials, [9][Coutp]); G / sx = Gram matrix and sums of the

@@ -150,6 +150,11 @@ PROTOTYPES = {
     "sed_decode_events_ws_bytes": (_Z, [_I, _I, _I]),
     "sed_decode_events": (_I, [_P, _I, _I, _I, _F, _F, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "sed_segment_counts": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "sed_rank_tile": (_I, []),
+    "sed_rank_ws_bytes": (_Z, [_I, _Z]),
+    "sed_rank_pack": (_I, [_P, _P, _Z, _Z, _I, _P, _Z, _Z, _P, _P]),
+    "sed_rank_sort": (_I, [_P, _I, _Z, _Z, _P, _P]),
+    "sed_rank_curve": (_I, [_P, _I, _Z, _Z, _P, _P, _P, _P, _P]),
     "sed_m5_conv1_len": (_I, [_I]),
     "sed_m5_conv1_nparts": (_I, [_I, _I]),
     "sed_m5_conv1_fwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _P]),

@@ -130,12 +130,23 @@ def build_semi_parser():
     return p
 
 
+def build_ranking_parser():
+    """The rank-metric evaluation options (this build only), in a parser of their own like the event options."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--eval_ranking", action="store_true", default=False,
+                   help="this build only: the periodic evaluation also logs corpus-level AP, ROC-AUC, d' and the best-F1 threshold "
+                        "per class, sorted and scanned on the GPU")
+    p.add_argument("--eval_clip_pooling", default=None, choices=["max", "mean", "linear", "exp"],
+                   help="--eval_ranking: also rank the recordings by their pooled clip probability against the clip label")
+    return p
+
+
 def build_full_parser():
-    """What main() parses: build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser() and
-    build_semi_parser() together."""
+    """What main() parses: build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser(),
+    build_semi_parser() and build_ranking_parser() together."""
     return argparse.ArgumentParser(description="SED training on MI355X",
                                    parents=[build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser(),
-                                            build_semi_parser()],
+                                            build_semi_parser(), build_ranking_parser()],
                                    conflict_handler="resolve")
 
 
@@ -185,6 +196,15 @@ def spec_augment_config(args):
                              freq_mask_bins=g["freq_mask_bins"], time_shift=bool(g["time_shift"]), mixup_prob=g["mixup_prob"],
                              mixup_alpha=g["mixup_alpha"], label_mix="soft" if g["soft_labels"] else "max",
                              filter_prob=g["filter_augment"])
+
+
+def ranking_eval_options(args):
+    """train()'s ranking_eval of --eval_ranking / --eval_clip_pooling; None with the flag off (a Namespace built by hand may lack
+    them)."""
+    if not getattr(args, "eval_ranking", False):
+        return None
+    pooling = getattr(args, "eval_clip_pooling", None)
+    return {} if pooling is None else {"clip_pooling": pooling}
 
 
 def event_eval_options(args, fps):
@@ -339,6 +359,14 @@ def validate_args(args):
     if semi:
         from .train import check_semi_options
         check_semi_options(**{k: v for k, v in semi.items() if k != "eval_teacher"})
+    if getattr(args, "eval_clip_pooling", None) is not None:
+        if not getattr(args, "eval_ranking", False):
+            raise ValueError("--eval_clip_pooling needs --eval_ranking")
+        if args.train_features.lower() == "waveform":
+            raise ValueError("--eval_clip_pooling pools frame probabilities over time: it needs --train_features Spectogram "
+                             "(the M5 model has no time axis in its output)")
+        from .train import check_ranking_options
+        check_ranking_options(args.eval_clip_pooling)
 
 
 def optimizer_options(args):
@@ -416,7 +444,8 @@ def main(argv=None):
     train(model, dataloader, criterion, num_steps=args.num_train_steps,
           outputs_dir=os.path.join(args.outputs_root, train_name), device=device, lr=args.lr,
           log_freq=args.log_freq, event_eval=event_eval_options(args, frames_per_second(args)),
-          batch_augment=synthetic_batch_augment(args), **optimizer_options(args), **weak_options(args), **semi_options(args))
+          batch_augment=synthetic_batch_augment(args), ranking_eval=ranking_eval_options(args), **optimizer_options(args),
+          **weak_options(args), **semi_options(args))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -777,6 +777,58 @@ def eval_events(model, dataloader, device, *, threshold, low_threshold, median_w
             "n_pred_events": int(len(pred_all)), "n_ref_events": int(len(ref_all))}
 
 
+def check_ranking_options(clip_pooling=None, model=None):
+    """Validate eval_ranking's clip_pooling (host only): None, or max / mean / linear / exp on a model with a time axis."""
+    if clip_pooling is None:
+        return None
+    from .engine import check_pooling
+    check_pooling(clip_pooling)
+    if model is not None and not hasattr(model, "conv_blocks"):
+        raise ValueError(f"clip pooling pools frame probabilities over time: {type(model).__name__} has no time axis in its "
+                         "output (use Cnn_AvgPooling / Crnn_AvgPooling)")
+    return clip_pooling
+
+
+def eval_ranking(model, dataloader, device, *, clip_pooling=None, limit_val_samples=None):
+    """Corpus-level rank metrics of the validation set (this build only): every recording of the validation sampler is run like
+    eval() does, its frame probabilities -- the sigmoid of sed_metric_counts, the one eval() uses -- and its targets are appended
+    ON THE DEVICE to a utils.ranking_utils.RankingAccumulator over the first min(frames) frames, and one sort + scan at the end
+    gives per-class AP, ROC-AUC, d' and the best-F1 threshold over all recordings; the host receives 68 bytes per class.
+    clip_pooling (max / mean / linear / exp): a second accumulator takes one element per recording and class, CnnEngine.clip_probs
+    of the whole recording against the clip label (the target's maximum over the scored frames); its result sits under 'clip'.
+    Returns the JSON-ready dict of metrics_from_rank_counts plus 'n_recordings'."""
+    from .utils.metric_utils import metric_counts_device
+    from .utils.ranking_utils import RankingAccumulator
+    check_ranking_options(clip_pooling, model)
+    val_sampler = dataloader.dataset.get_validation_sampler(max_validate_num=limit_val_samples)
+    frames, clips, count = None, None, 0
+    for idx, (inp, target, file_name) in enumerate(val_sampler):
+        model.eval()
+        inp = inp.to(device).float()
+        with torch.no_grad():
+            output = model(inp)
+        output = output[0] if inp.dim() == 4 else output
+        target = (target[0] if inp.dim() == 4 else target.reshape(-1, 1)).to(device).float()
+        probs = metric_counts_device(output, target, raw_logits=True, return_probs=True)[3]
+        if frames is None:
+            frames = RankingAccumulator(probs.shape[1], probs.device)
+            clips = RankingAccumulator(probs.shape[1], probs.device) if clip_pooling is not None else None
+        frames.update(probs, target)
+        if clips is not None:        # the plan of the forward just run still holds its logits
+            plan = model.engine.plan(inp.shape[0], inp.shape[2], inp.shape[3], inp.device)
+            clip = model.engine.clip_probs(plan, clip_pooling)[:1]
+            clips.update(clip, target[:probs.shape[0]].max(dim=0, keepdim=True)[0])
+        count += 1
+    if frames is None:
+        raise RuntimeError("the validation sampler produced no recording")
+    res = frames.compute()
+    res["n_recordings"] = count
+    if clips is not None:
+        res["clip"] = clips.compute()
+        res["clip"]["pooling"] = clip_pooling
+    return res
+
+
 def summarize_validation(val_losses, recal_sets, precision_sets, APs):
     """ProgressPlotter.report_validation_metrics (utils/common.py:46-56): F-scores of the
     validation-AVERAGED precision/recall curves, including the swapped-argument call convention."""
@@ -790,7 +842,7 @@ def summarize_validation(val_losses, recal_sets, precision_sets, APs):
 def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, device, *, weight_decay=0.0,
           decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None, event_eval=None, batch_augment=None,
           weak_pooling=None, weak_weight=1.0, weak_only=False, mean_teacher=False, ema_decay=0.999, consistency_weight=2.0,
-          consistency_rampup=0, teacher_augment=None, eval_teacher=False):
+          consistency_rampup=0, teacher_augment=None, eval_teacher=False, ranking_eval=None):
     """train.py:77-131.  `criterion` must be this package's WeightedBCE(multi_frame=True) (its
     recall_factor feeds the fused loss kernel).  The keyword-only optimizer options are FusedTrainer's (this build only; their
     defaults are the reference's Adam(amsgrad=True) without decay or clipping).  event_eval: None, or the keyword arguments of
@@ -803,7 +855,9 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
     mean_teacher ... teacher_augment: FusedTrainer's mean-teacher options; eval_teacher=True runs every periodic evaluation on
     trainer.teacher.  Checkpoints carry the teacher's state under 'teacher', beside 'optimizer' (resume with
     trainer.load_state_dict(ck['optimizer'], teacher=ck['teacher'])).  batch_augment does not see the kinds: an augmentation that
-    mixes clips (mixup) must not be combined with them."""
+    mixes clips (mixup) must not be combined with them.  ranking_eval: None, or the keyword arguments of eval_ranking ({} or
+    {'clip_pooling': ...}): the periodic evaluation then also logs that dict under 'ranking' (the teacher's with eval_teacher);
+    None launches nothing new."""
     from .utils.common import WeakBCE, WeightedBCE
     check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
     if isinstance(criterion, WeakBCE):
@@ -814,6 +868,10 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
     check_semi_options(mean_teacher, ema_decay, consistency_weight, consistency_rampup, model)
     if eval_teacher and not mean_teacher:
         raise ValueError("eval_teacher needs mean_teacher")
+    if ranking_eval is not None:
+        if set(ranking_eval) - {"clip_pooling"}:
+            raise ValueError(f"ranking_eval takes clip_pooling only (got {sorted(ranking_eval)})")
+        check_ranking_options(ranking_eval.get("clip_pooling"), model)
     if mean_teacher and data_parallel_enabled():
         raise RuntimeError("mean_teacher is the single-process path (the teacher's BatchNorm statistics and the order of the EMA "
                            "across ranks are not defined yet)")
@@ -869,6 +927,8 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
                                                           iteration=iterations, device=dev, limit_val_samples=3)))
                     if event_eval is not None:
                         rec.update(eval_events(eval_model, data_loader, dev, limit_val_samples=3, **event_eval))
+                    if ranking_eval is not None:
+                        rec["ranking"] = eval_ranking(eval_model, data_loader, dev, limit_val_samples=3, **ranking_eval)
                 if rank0:
                     print(f"epoch: {epoch}, step: {iterations}, loss: {host_losses[-1]:.2f}, "
                           f"im/sec: {im_sec:.1f}, lr: {trainer.lr:.8f}")
