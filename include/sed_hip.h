@@ -656,6 +656,35 @@ int sed_rank_sort(unsigned* keys, int K, size_t n, size_t capacity, void* worksp
 int sed_rank_curve(const unsigned* keys_sorted, int K, size_t n, size_t capacity, double* ap, unsigned long long* counts,
                    float* best_score, void* workspace, void* stream);
 
+/* ---- PSDS intersection counts (csrc/sed_psds.hip) ---------------------------------------------
+ * The integer counts behind the polyphonic sound detection score (Bilen et al., ICASSP 2020) for a whole threshold sweep in one
+ * launch, on the frame grid.  Every count is an integer added with integer atomics: the same bits on every run.
+ *
+ * prob fp32 [B][T][K] (median-filtered by the caller if wanted: sed_median_time), target fp32 [B][Tt][K], contiguous, classes
+ * innermost; the first n = min(T, Tt) frames of each recording are scored.  th: HOST array of nth fp32 thresholds, 1 <= nth <= 64,
+ * in any order, copied by value into the launch (the call can be captured).  Criteria as integer fractions num/den with
+ * 0 < num <= den <= 2^15: DTC, GTC, CTTC.
+ *   ground-truth event of class c in recording b: a maximal run of target[b][t][c] > 0.5 within [0, n).
+ *   detection of class k at threshold i: a maximal run of prob[b][t][k] > th[i] within [0, n); strict, in fp32, a NaN never detects
+ *     (sed_decode_events with th_lo == th_hi, max_gap = 0, min_len = 1).
+ * Per (i, b, k), in integers (the products stay below 2^31 * 2^15):
+ *   DTC   a detection d of length |d| is relevant if I * den_dtc >= num_dtc * |d|, I = the number of d's frames with
+ *         target[..][k] > 0.5; otherwise d is a false positive.
+ *   GTC   a ground-truth event g of class k is a true positive if J * den_gtc >= num_gtc * |g|, J = the number of g's frames covered
+ *         by RELEVANT detections of class k.
+ *   CTTC  a false-positive detection d of class k is a cross-trigger against class c != k if Ic * den_cttc >= num_cttc * |d|, Ic =
+ *         the number of d's frames with target[..][c] > 0.5.  One detection may cross-trigger several classes; it still counts once
+ *         as a false positive.
+ * Outputs, device int64, the call ADDS to them (the caller zeroes them once, so recordings of different lengths accumulate):
+ *   counts [nth][K][K + 3] = (tp, fp, ndet, ct[0..K-1]) for detected class k; ct[k] is always 0;
+ *   gt     [K][2]          = (number of ground-truth events, their total frames), added once per call, not once per threshold.
+ * K <= 64, B <= 65535, n <= sed_psds_max_frames(K, nth) (host-only; 0 for K / nth out of range; >= 8192 for K <= 16, nth <= 64).  A
+ * shape or parameter the call cannot serve returns non-zero and launches nothing; n = 0 is legal and adds nothing.  No workspace. */
+int sed_psds_max_frames(int K, int nth);
+int sed_psds_counts(const float* prob, const float* target, int B, int T, int Tt, int K, const float* th, int nth, int dtc_num,
+                    int dtc_den, int gtc_num, int gtc_den, int cttc_num, int cttc_den, long long* counts, long long* gt,
+                    void* stream);
+
 /* First-layer weight gradient WITHOUT the layer's pre-BN output (z1 is never read):
  *   dW1[c][k] = ca[c]*A[c][k] + cb[c]*sum_j w1[c][j]*G[j][k] + cc[c]*sx[k],
  * A = plain sed_conv3x3_c1_wgrad of g (summed partials, [9][Coutp]); G / sx = Gram matrix and sums of the

@@ -155,6 +155,8 @@ PROTOTYPES = {
     "sed_rank_pack": (_I, [_P, _P, _Z, _Z, _I, _P, _Z, _Z, _P, _P]),
     "sed_rank_sort": (_I, [_P, _I, _Z, _Z, _P, _P]),
     "sed_rank_curve": (_I, [_P, _I, _Z, _Z, _P, _P, _P, _P, _P]),
+    "sed_psds_max_frames": (_I, [_I, _I]),
+    "sed_psds_counts": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sed_m5_conv1_len": (_I, [_I]),
     "sed_m5_conv1_nparts": (_I, [_I, _I]),
     "sed_m5_conv1_fwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _P]),

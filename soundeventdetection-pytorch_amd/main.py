@@ -141,12 +141,26 @@ def build_ranking_parser():
     return p
 
 
+def build_psds_parser():
+    """The PSDS evaluation options (this build only), in a parser of their own like the rank-metric options."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--eval_psds", action="store_true", default=False,
+                   help="this build only: the periodic evaluation also logs the polyphonic sound detection score (PSDS, the DCASE "
+                        "task-4 ranking number) over a 50-threshold sweep, counted on the GPU")
+    p.add_argument("--psds_scenario", type=int, default=1, choices=[1, 2],
+                   help="--eval_psds: the DCASE 2021-23 task-4 scenario (1: DTC = GTC = 0.7, no cross-trigger cost; 2: DTC = GTC = "
+                        "0.1, CTTC = 0.3, cross-trigger cost 0.5)")
+    p.add_argument("--psds_median_window", type=float, default=0.0,
+                   help="--eval_psds: median-filter length in seconds applied to the probabilities first (0 = none)")
+    return p
+
+
 def build_full_parser():
     """What main() parses: build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser(),
-    build_semi_parser() and build_ranking_parser() together."""
+    build_semi_parser(), build_ranking_parser() and build_psds_parser() together."""
     return argparse.ArgumentParser(description="SED training on MI355X",
                                    parents=[build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser(),
-                                            build_semi_parser(), build_ranking_parser()],
+                                            build_semi_parser(), build_ranking_parser(), build_psds_parser()],
                                    conflict_handler="resolve")
 
 
@@ -205,6 +219,16 @@ def ranking_eval_options(args):
         return None
     pooling = getattr(args, "eval_clip_pooling", None)
     return {} if pooling is None else {"clip_pooling": pooling}
+
+
+def psds_eval_options(args, fps):
+    """train()'s psds_eval of --eval_psds / --psds_scenario / --psds_median_window (seconds -> frames); None with the flag off (a
+    Namespace built by hand may lack them)."""
+    if not getattr(args, "eval_psds", False):
+        return None
+    from .utils.event_utils import seconds_to_window
+    return {"scenario": int(getattr(args, "psds_scenario", 1)), "fps": float(fps),
+            "median_window": seconds_to_window(getattr(args, "psds_median_window", 0.0), fps)}
 
 
 def event_eval_options(args, fps):
@@ -367,6 +391,15 @@ def validate_args(args):
                              "(the M5 model has no time axis in its output)")
         from .train import check_ranking_options
         check_ranking_options(args.eval_clip_pooling)
+    if getattr(args, "psds_median_window", 0.0) < 0:
+        raise ValueError(f"--psds_median_window must be >= 0 seconds, {args.psds_median_window} given")
+    if getattr(args, "eval_psds", False):
+        if args.train_features.lower() == "waveform":
+            raise ValueError("--eval_psds scores events along time: it needs --train_features Spectogram "
+                             "(the M5 model has no time axis in its output)")
+        from .train import check_psds_options
+        opts = psds_eval_options(args, frames_per_second(args))
+        check_psds_options(opts["scenario"], None, opts["median_window"])
 
 
 def optimizer_options(args):
@@ -444,7 +477,8 @@ def main(argv=None):
     train(model, dataloader, criterion, num_steps=args.num_train_steps,
           outputs_dir=os.path.join(args.outputs_root, train_name), device=device, lr=args.lr,
           log_freq=args.log_freq, event_eval=event_eval_options(args, frames_per_second(args)),
-          batch_augment=synthetic_batch_augment(args), ranking_eval=ranking_eval_options(args), **optimizer_options(args),
+          batch_augment=synthetic_batch_augment(args), ranking_eval=ranking_eval_options(args),
+          psds_eval=psds_eval_options(args, frames_per_second(args)), **optimizer_options(args),
           **weak_options(args), **semi_options(args))
     if world > 1:
         import torch.distributed as dist

@@ -829,6 +829,55 @@ def eval_ranking(model, dataloader, device, *, clip_pooling=None, limit_val_samp
     return res
 
 
+def check_psds_options(scenario=1, thresholds=None, median_window=1, model=None):
+    """Validate eval_psds's options (host only): scenario 1, 2 or a dict, 1..64 thresholds, an odd median window in frames, and a
+    model with a time axis.  Returns the checked scenario."""
+    from .utils.event_utils import MAX_MEDIAN_WINDOW
+    from .utils.psds_utils import check_thresholds, resolve_scenario
+    s = resolve_scenario(scenario)
+    check_thresholds(thresholds)
+    w = int(median_window)
+    if w < 1 or w > MAX_MEDIAN_WINDOW or w % 2 == 0:
+        raise ValueError(f"median window must be odd, 1..{MAX_MEDIAN_WINDOW} frames (got {median_window})")
+    if model is not None and not hasattr(model, "conv_blocks"):
+        raise ValueError(f"PSDS scores events along time: {type(model).__name__} has no time axis in its output (use "
+                         "Cnn_AvgPooling / Crnn_AvgPooling)")
+    return s
+
+
+def eval_psds(model, dataloader, device, *, scenario=1, thresholds=None, median_window=1, fps, limit_val_samples=None):
+    """The polyphonic sound detection score of the validation set (this build only): every recording of the validation sampler is
+    run like eval() does, its frame probabilities -- the sigmoid of sed_metric_counts, the one eval_ranking takes -- and its targets
+    go ON THE DEVICE through utils.psds_utils.PsdsAccumulator (median_window frames of median filter, then one sed_psds_counts per
+    recording for the whole threshold sweep), and one copy of the integer counts at the end gives the score.  scenario: 1 or 2 (the
+    DCASE task-4 settings) or a dict; thresholds: None = 50 from 0.01 to 0.99; fps: the model's output frames per second.
+    Returns {'psds', 'classes_scored', 'best_macro_f1', 'best_macro_f1_threshold', 'scenario', 'n_recordings'} (JSON-ready)."""
+    from .utils.metric_utils import metric_counts_device
+    from .utils.psds_utils import PsdsAccumulator
+    check_psds_options(scenario, thresholds, median_window, model)
+    val_sampler = dataloader.dataset.get_validation_sampler(max_validate_num=limit_val_samples)
+    acc, count = None, 0
+    for idx, (inp, target, file_name) in enumerate(val_sampler):
+        model.eval()
+        inp = inp.to(device).float()
+        with torch.no_grad():
+            output = model(inp)
+        output = output[0] if inp.dim() == 4 else output
+        target = (target[0] if inp.dim() == 4 else target.reshape(-1, 1)).to(device).float()
+        probs = metric_counts_device(output, target, raw_logits=True, return_probs=True)[3]
+        if acc is None:
+            acc = PsdsAccumulator(probs.shape[1], probs.device, thresholds=thresholds, scenario=scenario,
+                                  median_window=median_window)
+        acc.update(probs, target)
+        count += 1
+    if acc is None:
+        raise RuntimeError("the validation sampler produced no recording")
+    res = acc.compute(fps)
+    return {"psds": res["psds"], "classes_scored": res["classes_scored"], "best_macro_f1": res["best_macro_f1"],
+            "best_macro_f1_threshold": res["best_macro_f1_threshold"],
+            "scenario": scenario if not isinstance(scenario, dict) else "custom", "n_recordings": count}
+
+
 def summarize_validation(val_losses, recal_sets, precision_sets, APs):
     """ProgressPlotter.report_validation_metrics (utils/common.py:46-56): F-scores of the
     validation-AVERAGED precision/recall curves, including the swapped-argument call convention."""
@@ -842,7 +891,7 @@ def summarize_validation(val_losses, recal_sets, precision_sets, APs):
 def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, device, *, weight_decay=0.0,
           decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None, event_eval=None, batch_augment=None,
           weak_pooling=None, weak_weight=1.0, weak_only=False, mean_teacher=False, ema_decay=0.999, consistency_weight=2.0,
-          consistency_rampup=0, teacher_augment=None, eval_teacher=False, ranking_eval=None):
+          consistency_rampup=0, teacher_augment=None, eval_teacher=False, ranking_eval=None, psds_eval=None):
     """train.py:77-131.  `criterion` must be this package's WeightedBCE(multi_frame=True) (its
     recall_factor feeds the fused loss kernel).  The keyword-only optimizer options are FusedTrainer's (this build only; their
     defaults are the reference's Adam(amsgrad=True) without decay or clipping).  event_eval: None, or the keyword arguments of
@@ -857,6 +906,8 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
     trainer.load_state_dict(ck['optimizer'], teacher=ck['teacher'])).  batch_augment does not see the kinds: an augmentation that
     mixes clips (mixup) must not be combined with them.  ranking_eval: None, or the keyword arguments of eval_ranking ({} or
     {'clip_pooling': ...}): the periodic evaluation then also logs that dict under 'ranking' (the teacher's with eval_teacher);
+    None launches nothing new.  psds_eval: None, or the keyword arguments of eval_psds ({'fps': ...} and optionally scenario,
+    thresholds, median_window): the periodic evaluation then also logs that dict under 'psds' (the teacher's with eval_teacher);
     None launches nothing new."""
     from .utils.common import WeakBCE, WeightedBCE
     check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
@@ -872,6 +923,12 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
         if set(ranking_eval) - {"clip_pooling"}:
             raise ValueError(f"ranking_eval takes clip_pooling only (got {sorted(ranking_eval)})")
         check_ranking_options(ranking_eval.get("clip_pooling"), model)
+    if psds_eval is not None:
+        if set(psds_eval) - {"scenario", "thresholds", "median_window", "fps"} or "fps" not in psds_eval:
+            raise ValueError(f"psds_eval takes fps and optionally scenario, thresholds, median_window (got {sorted(psds_eval)})")
+        if not float(psds_eval["fps"]) > 0:
+            raise ValueError(f"psds_eval: fps must be > 0 (got {psds_eval['fps']})")
+        check_psds_options(psds_eval.get("scenario", 1), psds_eval.get("thresholds"), psds_eval.get("median_window", 1), model)
     if mean_teacher and data_parallel_enabled():
         raise RuntimeError("mean_teacher is the single-process path (the teacher's BatchNorm statistics and the order of the EMA "
                            "across ranks are not defined yet)")
@@ -929,6 +986,8 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
                         rec.update(eval_events(eval_model, data_loader, dev, limit_val_samples=3, **event_eval))
                     if ranking_eval is not None:
                         rec["ranking"] = eval_ranking(eval_model, data_loader, dev, limit_val_samples=3, **ranking_eval)
+                    if psds_eval is not None:
+                        rec["psds"] = eval_psds(eval_model, data_loader, dev, limit_val_samples=3, **psds_eval)
                 if rank0:
                     print(f"epoch: {epoch}, step: {iterations}, loss: {host_losses[-1]:.2f}, "
                           f"im/sec: {im_sec:.1f}, lr: {trainer.lr:.8f}")
