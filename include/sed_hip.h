@@ -716,9 +716,10 @@ int sed_pack_conv_weights_batch(int dtype, const void* desc, int n, int total_bl
  * operands, same results (dwpack / dw = conv2's weight gradient, a_partial [sed_conv_dgrad_c1_nparts()][10][32] = per-workgroup
  * partials of [A (9 taps); sum g]); dz2 is produced into an LDS row ring and never written.  workspace:
  * sed_conv_wgrad_ws_floats(B, H, 64, 32, 32) floats.  Covered: bf16, W = 64, 32 -> 32, pool 2 (..._supported).
- * relu_mask may be NULL (round 5, what the engine passes): the kernel then takes conv1's ReLU decisions from the activation tile it
- * rebuilds for the weight gradient (a1 > 0 -- the same MFMA, the same bits as the forward's mask), and the forward call
- * sed_conv3x3_fwd_c1 can be given relu_mask = NULL as well: no mask tensor exists.                                            */
+ * relu_mask must be NULL (a non-NULL value is an error): the kernel takes conv1's ReLU decisions from the activation tile it rebuilds
+ * for the weight gradient (a1 > 0 -- the same MFMA, the same bits as the forward's mask), so the forward call sed_conv3x3_fwd_c1 can
+ * be given relu_mask = NULL as well and no mask tensor exists.  The argument keeps its place in the signature; the mask-given form
+ * of the kernel (round 4) is gone.                                                                                              */
 int sed_conv3x3_bwd_fused_c1_supported(int dtype, int W, int Coutp, int pool);
 int sed_conv3x3_bwd_fused_c1(int dtype, const float* x1, const float* fmean, const float* fstd, const float* w1,
                              const float* pro_scale, const float* pro_shift, const void* gsrc, const void* zsrc,
@@ -998,18 +999,12 @@ int sed_nchw_to_nhwc(int dtype, const float* src, void* dst, int B, int C, int H
 int sed_nhwc_to_nchw(int dtype, const void* src, float* dst, int B, int C, int H, int W, int Cp,
                      void* stream);
 
-/* ---- deferred weight-gradient reduction (round 6) ------------------------------------------------------------------------------
+/* ---- weight-gradient reduction ---------------------------------------------------------------------------------------------
  * Every weight-gradient entry point (sed_conv3x3_wgrad*, sed_conv3x3_bwd_fused, sed_conv3x3_bwd_fused_c1) ends with a launch that sums its
- * per-workgroup slabs workspace[slab][9][Cinp][Coutp] into dwpack (and dw, torch layout).  Called with dwpack == NULL it launches its
- * main kernel only and leaves the slabs in `workspace`; sed_wgrad_last_slabs() then returns their count (per calling thread, like
- * sed_last_error).  The caller reduces later: one layer with sed_wgrad_reduce, or several layers in ONE launch with
- * sed_wgrad_reduce_batch -- desc = device array of n descriptors of ten 64-bit words {workspace, dwpack (nullable), dw (nullable),
- * slabs, 9*Cinp*Coutp, Cout, Cin, Cinp, Coutp, first_block}; descriptor i owns blocks [first_block_i, first_block_{i+1}) of 64 outputs
- * each; total_blocks = the sum.  Same arithmetic and summation order as the inline reduction (bit-identical).  The weight gradients
- * feed only the optimizer / the gradient all-reduce (train.py:101-103), so a train step's seven dependent 10 us launches become one.  */
-int sed_wgrad_last_slabs(void);
-int sed_wgrad_reduce(const float* workspace, int nslabs, float* dwpack, float* dw, int Cout, int Cin, int Cinp, int Coutp, void* stream);
-int sed_wgrad_reduce_batch(const void* desc, int n, int total_blocks, void* stream);
+ * per-workgroup slabs workspace[slab][9][Cinp][Coutp] into dwpack (and dw, torch layout, where the entry point takes one): dwpack is
+ * required.  Changelog: the deferred form of round 6 (dwpack == NULL, then sed_wgrad_last_slabs / sed_wgrad_reduce /
+ * sed_wgrad_reduce_batch) was measured neutral and is removed with its three functions.  sed_abi_version() stays 1: the library and
+ * its only binding (_lib.py, which resolves every prototype at load) ship together.                                              */
 
 /* ---- box-measured peaks (bench.py: roofline.peak_measured) ------------------------------------------------------------------
  * SURVEY.md 8(d) asks for box-measured peaks beside the spec ones.  Both are plain launches on `stream`; the caller times them.

@@ -261,9 +261,8 @@ int launch_wgrad3(int dzmode, Wgrad2Params& p, int W, hipStream_t st);
 // it where it covers the shape (SED_WGRAD_WIDE=0: the A/B knob)
 int wgrad_wide_strips(int B, int H, int W, int Cinp, int Coutp);  // 0 = shape not covered
 int launch_wgrad_wide(int dzmode, Wgrad2Params& p, int W, hipStream_t st);
-// sed_conv_pack.hip: sums the `slabs` weight-gradient slabs of `ws` into dwpack (and dw, torch layout, when given) -- or, with
-// dwpack == NULL, launches nothing and leaves the count for sed_wgrad_last_slabs() (deferred reduction).  Always 0.
-int reduce_or_defer(const float* ws, float* dwpack, int slabs, size_t n, float* dw, int Cout, int Cin, int Cinp, int Coutp, hipStream_t st);
+// sed_conv_pack.hip: sums the `slabs` weight-gradient slabs of `ws` into dwpack (and dw, torch layout, when given).  Always 0.
+int reduce_wgrad_slabs(const float* ws, float* dwpack, int slabs, size_t n, float* dw, int Cout, int Cin, int Cinp, int Coutp, hipStream_t st);
 
 // the line widths the specialised kernels are compiled for; every other width takes csrc/sed_conv_anyw.hip
 static inline bool sed_w_specialised(int W) { return W == 8 || W == 16 || W == 32 || W == 64; }
@@ -410,7 +409,7 @@ int launch_bwd_fused_cs(BwdFusedParams& p, int W, hipStream_t st);      // -1 = 
 // sed_bwd_fused_c1.hip: block 0 (C1 mode), conv2's weight gradient + gated data gradient + [A; sum g] in one launch; -1 = not covered
 int launch_bwd_fused_c1(const float* x1, const float* fmean, const float* fstd, const float* w1, const float* sc1, const float* sh1,
                         const void* dy, const void* z2, const float* sc2, const float* sh2, const float* ca, const float* cb,
-                        const float* cc, const void* wpack_t, const void* mask, float* a_part, int nparts, float* ws, int B, int H,
+                        const float* cc, const void* wpack_t, float* a_part, int nparts, float* ws, int B, int H,
                         int* nwg, hipStream_t st);
 
 // ---- "C1 mode": the first ConvBlock without materialising conv1's output -----------------------------------

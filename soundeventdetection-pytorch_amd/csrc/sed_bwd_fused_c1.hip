@@ -4,11 +4,14 @@
 //   dz2 = BN2 / ReLU / 2x2 avg-pool backward of (dy, z2)                       produced on load into an LDS row ring
 //   dW2 = relu(bn1(conv1(x))) (x) dz2                                          (sed_conv3x3_wgrad_fused_c1: activation rebuilt on the
 //                                                                               matrix pipe from the 1-channel input, never read)
-//   g   = relu'(bn1(z1)) * conv2^T(dz2)                                        never written: gated with conv1's ReLU bit mask in
-//   A[tap][c] = sum_px g[px][c] * x[px + tap],  sum g                           registers and contracted over the pixels on the matrix
+//   g   = relu'(bn1(z1)) * conv2^T(dz2)                                        never written: gated in registers with conv1's ReLU
+//   A[tap][c] = sum_px g[px][c] * x[px + tap],  sum g                           decisions and contracted over the pixels on the matrix
 //                                                                               pipe (sed_conv3x3_dgrad_c1_stats, csrc/sed_dgrad_c1.hip)
 // It merges the two kernels named in the right column, which moved dz2 (786 MB at B = 32) through HBM twice; the operands left
-// are one streaming read of z2, dy (a quarter of it), the fp32 input and the mask.
+// are one streaming read of z2, dy (a quarter of it) and the fp32 input.  The ReLU gate is derived from the activation tile the
+// kernel rebuilds for its weight gradient (below): the forward's bit mask is neither read nor staged.
+// One kernel form.  The mask-gated, loader-rebuild and tap-split forms that lost or tied their A/B are gone (LABNOTES.md,
+// profiles/r05_d_ab_block0_gate_derived.txt).
 //
 // Structure as csrc/sed_bwd_fused.hip (row ring with contiguous windows, one s_barrier per stage, waves 4-7 produce, waves 0-3
 // consume); per 256-pixel stage a consumer wave
@@ -47,7 +50,8 @@ struct BwdC1Params {
     const float* cb;
     const float* cc;
     const void* wpack_t;     // conv2's data-gradient operator [36][32][8] bf16
-    const unsigned* mask;    // conv1's ReLU decisions [B][H][64] (one word per pixel)
+    const unsigned* unused;  // always NULL: the slot of the former mask pointer -- the kernel-argument offsets behind it, and with them the
+                             // scalar loads and their scheduling, stay the measured ones (dropping it regroups the s_load instructions)
     float* a_part;           // [nparts][10][32]
     float* ws;               // [nwg][9][32][32]
     int B, H;
@@ -70,18 +74,13 @@ struct BwdC1Params {
 #endif
 __device__ __forceinline__ int ab_chunk(int c8, int col) { return (SED_BC_ABSWZ ? (c8 ^ ((col >> 1) & 7)) : c8) * 4; }
 
-// TS (make EXPERIMENTS=1, SED_BC_TS=1): the weight-gradient accumulators split over the consumer waves by tap instead of by k share
-// LB (SED_BC_LB): the conv1 tile relu(bn1(conv1(x))) of a stage is rebuilt by the LOADER waves (one tile row each, in the iteration
-// that stages the stage's dz chunk) instead of by the consumer waves at the end of the stage before: the consumers are this kernel's
-// critical path (their stage is weight gradient 1520 + data gradient / gate / contraction 2480 + rebuild 1540 cycles and they never
-// wait at the barrier), the loaders have the slack
-// DG (round 5, the default form: relu_mask = NULL at the C ABI): the ReLU gate of the data gradient is DERIVED from the activation tile the
-// kernel rebuilds for its weight gradient anyway (a1 > 0 <=> the forward's decision bit: same MFMA, same bits) -- the forward then
-// neither builds nor stores conv1's bit mask (16 of the ~36 instructions of its rebuild tail per 32-pixel block, 4 B/pixel of stores)
-// and this kernel neither loads nor stages it.  The consumer lane of channel r takes four pixels of its channel with one
-// ds_read_b64_tr_b16 (the weight gradient's A-operand read pattern) and gates the bf16 PAIRS of g: v_pk_min_u16 (activation bits
-// -> 0 / 1) + v_pk_mul_lo_u16 -- two instructions per pair instead of four (bit-field extract + and per value).
-template <bool TS, bool LB = false, bool DG = false>
+// The derived gate: the ReLU gate of the data gradient comes from the activation tile the kernel rebuilds for its weight gradient
+// anyway (a1 > 0 <=> the forward's decision bit: same MFMA, same bits) -- the forward then neither builds nor stores conv1's bit
+// mask (16 of the ~36 instructions of its rebuild tail per 32-pixel block, 4 B/pixel of stores) and this kernel neither loads nor
+// stages it.  The consumer lane of channel r takes four pixels of its channel with one ds_read_b64_tr_b16 (the weight gradient's
+// A-operand read pattern) and gates the bf16 PAIRS of g: v_pk_min_u16 (activation bits -> 0 / 1) + v_pk_mul_lo_u16.
+// The consumer waves are the critical path (per stage: weight gradient 1520 + data gradient / gate / contraction 2480 + rebuild of
+// the next stage's activation row 1540 cycles, and they never wait at the barrier); the loader waves have the slack.
 __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
     typedef bf16_t T;
     constexpr int W = 64, TH = 4, BM = TH * W, WP = 68, ROWE = WP * 32;
@@ -93,7 +92,6 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
     constexpr int XTW = W + 2, XTR = TH + 2, XTN = XTR * XTW;
     typedef C1Tile<W, XTR> XTL;
     constexpr int XCN = XTR * XTL::XP;                             // one constant region (ones / zeros), laid out like a tile's copy A
-    static_assert((3 * XTL::N * 2) % 16 == 0, "the mask tile behind the input tiles is read with 16-byte loads");
     constexpr int NP = 256, NTHR = 512;
     constexpr int XTIPT = (XTN + NP - 1) / NP;
 
@@ -102,8 +100,10 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
     T* ab = dzr + DZIMG;                                     // [2][BM][32]          relu(bn1(conv1(x))) of the tile's rows
     T* wsm = ab + 2 * ABUF;                                  // [WS]                 resident data-gradient operator
     T* xt0 = wsm + WS;                                       // [3][XTL::N]          input tiles (bf16, two copies each)
-    unsigned* mk0 = reinterpret_cast<unsigned*>(xt0 + 3 * XTL::N);    // [2][BM]
-    T* cst0 = reinterpret_cast<T*>(mk0 + 2 * BM);            // [2][XCN]: all ones (tap 9 -> sum g), all zeros (taps 10..31)
+    // (2 KB unused: the staged mask tile [2][BM] of the former mask-gated form sat here.  The constants behind it and the launch's LDS
+    //  byte count keep their values, so the instruction stream is the measured one; reclaiming the gap moves constants in the ISA and
+    //  is a change to measure on its own)
+    T* cst0 = reinterpret_cast<T*>(reinterpret_cast<unsigned*>(xt0 + 3 * XTL::N) + 2 * BM);     // [2][XCN]: all ones (tap 9 -> sum g), all zeros (taps 10..31)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -200,12 +200,12 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
             xtmu[u] = (ok && p.fmean) ? p.fmean[c] : 0.f;
             xtis[u] = ok ? (p.fstd ? 1.0f / p.fstd[c] : 1.0f) : 0.f;
         }
-        struct RawSet { Raw8<T> a[TH / 2]; Raw8<T> b[TH]; float xr[XTIPT]; unsigned m; };
+        struct RawSet { Raw8<T> a[TH / 2]; Raw8<T> b[TH]; float xr[XTIPT]; };
 
         // every load is issued unconditionally (a dead stage gets zero-sized descriptors): exact vmcnt bookkeeping
         auto issue = [&](RawSet& r, const StInfo& si) {
             const bool live = si.live;
-            const size_t zimg = live ? zimg_ : 0, pimg = live ? pimg_ : 0, mimg = (live && si.mainst) ? x1img_ : 0;
+            const size_t zimg = live ? zimg_ : 0, pimg = live ? pimg_ : 0;
             const unsigned dt = (unsigned)(TH * si.j * W * 32 * 2);
             const __amdgpu_buffer_rsrc_t zs = make_srd(zsg + (size_t)si.b * zimg, zimg * 2);
             const __amdgpu_buffer_rsrc_t gs = make_srd(gg + (size_t)si.b * pimg, pimg * 2);
@@ -214,10 +214,6 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
             for (int u2 = 0; u2 < TH / 2; ++u2) r.a[u2] = buf_load8<T>(gs, pvoff[u2] + ptq);
 #pragma unroll
             for (int u = 0; u < TH; ++u) r.b[u] = buf_load8<T>(zs, dvoff0 + (unsigned)(u * W * 32 * 2) + dt);
-            if constexpr (!DG) {
-                const __amdgpu_buffer_rsrc_t sm = make_srd(p.mask + (size_t)si.b * mimg, mimg * 4);
-                r.m = __builtin_amdgcn_raw_buffer_load_b32(sm, (unsigned)(((TH * si.j - 1) * W + pt) * 4), 0, 0);     // rows outside: 0 -> gated off
-            }
         };
         // the input tile of the stage after next rides in the same register set
         auto issue_x1 = [&](RawSet& r, const StInfo& si) {
@@ -285,41 +281,8 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
                 store8<T>(dst + u * ROWE, v);
                 if (u >= TH - 2 && dup) store8<T>(dzr + dlds0 + (u - (TH - 2)) * ROWE, v);
             }
-            if constexpr (!DG) { if (si.mainst) mk0[(s & 1) * BM + pt] = r.m; }
         };
 
-        // LB: row (wave - 4) of stage si's activation tile from the input tile xt (two 32-pixel blocks), as the consumers' build()
-        C1Mma c1m;
-        int c1o[2][2] = {{0, 0}, {0, 0}};
-        if constexpr (LB) {
-            c1mma_init(c1m, p.w1, p.sc1, p.sh1, lane);
-            c1tile_lane_offsets<W, XTR>(0, lane, c1o[0][0], c1o[0][1]);
-            c1tile_lane_offsets<W, XTR>(1, lane, c1o[1][0], c1o[1][1]);
-        }
-        auto lbuild = [&](const StInfo& si, int s) {
-            if constexpr (LB) {
-                if (!si.live || !si.mainst) return;
-                const int bw = wave - 4, r = lane & 31, hh = lane >> 5;
-                const T* xt = xt0 + (s % 3) * XTL::N;
-                const int row = TH * si.j - 1 + bw;
-                const bool inimg = row >= 0 && row < H;
-                T* abuf = ab + (s & 1) * ABUF;
-                f32x16 dd[2];
-#pragma unroll
-                for (int half = 0; half < 2; ++half) dd[half] = c1mma_block_mfma_b(c1m, xt + bw * XTL::XP, c1o[half][0], c1o[half][1]);
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    T* dst = abuf + (bw * W + half * 32 + r) * 32;
-                    unsigned w8[8], mkd;
-                    c1mma_block_tail_pk<false>(dd[half], w8, mkd);
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const u32x2 v2 = {inimg ? w8[2 * g4] : 0u, inimg ? w8[2 * g4 + 1] : 0u};
-                        *reinterpret_cast<u32x2*>(dst + ab_chunk(hh + 2 * g4, r)) = v2;
-                    }
-                }
-            }
-        };
         RawSet ra, rb;
         StInfo sc = st_first();
         StInfo sn = st_next(sc, 1), sf = st_next(sn, 2);      // sn = stage s + 1, sf = stage s + 2
@@ -331,7 +294,6 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
         auto pstamp = [&]() -> unsigned long long { return kBcStamps ? __builtin_amdgcn_s_memtime() : 0ull; };
         auto iter = [&](int s, RawSet& r) {
             const unsigned long long s0 = pstamp();
-            lbuild(sc, s);                                    // (its input tile was written in iteration s - 1 / by the set-up, before a barrier)
             commit(r, sc, s);
             write_xt(r, sn, s + 1);
             const unsigned long long s1 = pstamp();
@@ -351,7 +313,6 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
         bc_barrier();
         bc_barrier();
     } else {
-        if constexpr (!TS) {
         // =============================== CONSUMERS =====================================================
         const int r = lane & 31, hh = lane >> 5;
         f32x16 accw[9], accA;
@@ -369,7 +330,6 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
             for (int ks = 0; ks < 2; ++ks) xoff[tj][ks] = (r + tj) * 32 + (((ks * 2 + hh) ^ bc_xswz(r + tj)) * 8);
         const int woff = (hh * 32 + r) * 8;
         // second contraction: this lane is channel r of g (B operand) and tap r of the patch matrix (A operand)
-        const unsigned bitpos = 16 * ((r >> 2) & 1) + (r & 3) + 4 * (r >> 3);
         const int tap = r < 9 ? r : 0;
         const int pdx = tap % 3;
         const int ptap = (tap / 3) * XTL::XP + ((pdx & 1) ? XTL::XB + pdx - 1 : pdx) + 4 * hh;      // (copy B for dx = 1: 4-byte-aligned 8-byte reads)
@@ -387,7 +347,7 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
                 for (int sj = 0; sj < 3; ++sj) offB[sj][half] = (kl + sj) * 32 + (ch ^ swz<T>(kl + sj));
             }
         }
-        // DG: the gate's transposed reads of the activation tile -- lane (channel r, half hh) takes pixels 8*i4 + 4*hh + 0..3 of its 32-pixel
+        // the gate's transposed reads of the activation tile -- lane (channel r, half hh) takes pixels 8*i4 + 4*hh + 0..3 of its 32-pixel
         // half; the address-supplying lane i16 = 4*qq + pp of a 16-lane group points at (pixel + qq, channels 16*gbit + 4*pp ..)
         // (pixels 8 further: + 256 elements and chunk position ^ 4, i.e. element offset ^ 16 -- formed at the use: one register less)
         int offG0;
@@ -455,7 +415,7 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
         unsigned long long tc[5] = {0, 0, 0, 0, 0};
         auto cstamp = [&]() -> unsigned long long { return kBcStamps ? __builtin_amdgcn_s_memtime() : 0ull; };
         StInfo csi = st_first();
-        if constexpr (!LB) build(csi, 0);                     // (stage 0's input tile was staged by the whole workgroup)
+        build(csi, 0);                                        // (stage 0's input tile was staged by the whole workgroup)
         auto citer = [&](int s) {
             const unsigned long long c0 = cstamp();
             bc_barrier();
@@ -538,14 +498,12 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
                 {
                     const T* __restrict__ dbase = win + wave * ROWE;
                     const T* __restrict__ xtb = xt0 + (s % 3) * XTL::N;
-                    const unsigned* __restrict__ mkb = mk0 + (s & 1) * BM;
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt) {
                         f32x16 acc;
 #pragma unroll
                         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
                         // gate / patch operands of this half: requested before the k loop, so their LDS round trips hide behind it
-                        const unsigned* mrow = mkb + wave * W + mt * 32 + 4 * hh;
                         const T* prow_x = (r < 9 ? xtb : cbase) + wave * XTL::XP + mt * 32 + ptap;
                         u32x4 pfw[2];
 #pragma unroll
@@ -555,7 +513,7 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
                                 const c1_u32x2_a4 q4 = *reinterpret_cast<const c1_u32x2_a4*>(prow_x + 16 * sx + 8 * jj);
                                 pfw[sx][2 * jj] = q4[0]; pfw[sx][2 * jj + 1] = q4[1];
                             }
-                        // DG: the gate operand = this half's activations of the wave's own tile row (the tile the weight gradient just read)
+                        // the gate operand = this half's activations of the wave's own tile row (the tile the weight gradient just read)
                         // (requested at the LAST k-step, when the fragment ring has drained: eight more registers across the whole loop spill)
                         s16x4 gact[4];
                         const T* grow = abuf + (wave * W + mt * 32) * 32;
@@ -576,68 +534,45 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
 #pragma unroll
                         for (int k = 0; k < 18; ++k) {
                             if (k + DR - 1 < 18) ld(k + DR - 1, xf[(k + DR - 1) % DR], wf[(k + DR - 1) % DR]);
-                            if constexpr (DG) {
-                                if (k == SED_BC_GATE_AT) {
-                                    int offG1;
-                                    asm volatile("v_xor_b32 %0, %1, %2" : "=v"(offG1) : "v"(offG0), "v"(SED_BC_ABSWZ ? 16 : 0));
-#pragma unroll
-                                    for (int i4 = 0; i4 < 4; ++i4) gact[i4] = ds_read_tr16_b64(grow + (16 * (i4 >> 1) + 8 * (i4 & 1)) * 32 + ((i4 & 1) ? offG1 : offG0));
-                                }
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            acc = mfma(xf[k % DR], wf[k % DR], acc);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        if constexpr (DG) {
-                            if (SED_BC_GATE_AT >= 18) {
+                            if (k == SED_BC_GATE_AT) {
                                 int offG1;
                                 asm volatile("v_xor_b32 %0, %1, %2" : "=v"(offG1) : "v"(offG0), "v"(SED_BC_ABSWZ ? 16 : 0));
 #pragma unroll
                                 for (int i4 = 0; i4 < 4; ++i4) gact[i4] = ds_read_tr16_b64(grow + (16 * (i4 >> 1) + 8 * (i4 & 1)) * 32 + ((i4 & 1) ? offG1 : offG0));
                             }
-                            unsigned gw[8];
+                            __builtin_amdgcn_sched_barrier(0);
+                            acc = mfma(xf[k % DR], wf[k % DR], acc);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        if (SED_BC_GATE_AT >= 18) {
+                            int offG1;
+                            asm volatile("v_xor_b32 %0, %1, %2" : "=v"(offG1) : "v"(offG0), "v"(SED_BC_ABSWZ ? 16 : 0));
 #pragma unroll
-                            for (int i4 = 0; i4 < 4; ++i4) {
-                                const u32x2 aw = __builtin_bit_cast(u32x2, gact[i4]);
-#pragma unroll
-                                for (int h2 = 0; h2 < 2; ++h2) {
-                                    const f32x2 pr = {acc[4 * i4 + 2 * h2], acc[4 * i4 + 2 * h2 + 1]};
-                                    const unsigned gb = __builtin_bit_cast(unsigned, __builtin_convertvector(pr, bf16x2));
-                                    unsigned on;
-                                    asm("v_pk_min_u16 %0, %1, %2" : "=v"(on) : "v"(aw[h2]), "s"(0x00010001u));
-                                    asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(gw[2 * i4 + h2]) : "v"(gb), "v"(on));
-                                }
-                            }
-#pragma unroll
-                            for (int sx = 0; sx < 2; ++sx) {
-                                const u32x4 g4 = {gw[4 * sx], gw[4 * sx + 1], gw[4 * sx + 2], gw[4 * sx + 3]};
-                                accA = mfma(__builtin_bit_cast(bf16x8, pfw[sx]), __builtin_bit_cast(bf16x8, g4), accA);
-                            }
-                        } else {
-                        unsigned gv[16];
+                            for (int i4 = 0; i4 < 4; ++i4) gact[i4] = ds_read_tr16_b64(grow + (16 * (i4 >> 1) + 8 * (i4 & 1)) * 32 + ((i4 & 1) ? offG1 : offG0));
+                        }
+                        unsigned gw[8];
 #pragma unroll
                         for (int i4 = 0; i4 < 4; ++i4) {
-                            const u32x4 m4 = *reinterpret_cast<const u32x4*>(mrow + 8 * i4);
+                            const u32x2 aw = __builtin_bit_cast(u32x2, gact[i4]);
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const int t = __builtin_amdgcn_sbfe((int)m4[e], bitpos, 1u);
-                                const float av = acc[4 * i4 + e];
-                                gv[4 * i4 + e] = __builtin_bit_cast(unsigned, av) & (unsigned)t;
+                            for (int h2 = 0; h2 < 2; ++h2) {
+                                const f32x2 pr = {acc[4 * i4 + 2 * h2], acc[4 * i4 + 2 * h2 + 1]};
+                                const unsigned gb = __builtin_bit_cast(unsigned, __builtin_convertvector(pr, bf16x2));
+                                unsigned on;
+                                asm("v_pk_min_u16 %0, %1, %2" : "=v"(on) : "v"(aw[h2]), "s"(0x00010001u));
+                                asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(gw[2 * i4 + h2]) : "v"(gb), "v"(on));
                             }
                         }
 #pragma unroll
                         for (int sx = 0; sx < 2; ++sx) {
-                            bf16x8 gf;
-#pragma unroll
-                            for (int jj = 0; jj < 8; ++jj) gf[jj] = (bf16_t)__builtin_bit_cast(float, gv[8 * sx + jj]);
-                            accA = mfma(__builtin_bit_cast(bf16x8, pfw[sx]), gf, accA);
-                        }
+                            const u32x4 g4 = {gw[4 * sx], gw[4 * sx + 1], gw[4 * sx + 2], gw[4 * sx + 3]};
+                            accA = mfma(__builtin_bit_cast(bf16x8, pfw[sx]), __builtin_bit_cast(bf16x8, g4), accA);
                         }
                     }
                 }
             }
             c3 = cstamp();
-            if constexpr (!LB) build(csi, s + 1);             // the next stage's activation row (its input tile was written before this barrier)
+            build(csi, s + 1);                                // the next stage's activation row (its input tile was written before this barrier)
             if (kBcStamps) { tc[0] += c1 - c0; tc[1] += c2 - c1; tc[2] += c3 - c2; tc[3] += cstamp() - c3; }
         };
         for (int s = 0; s < NI; s += 2) {
@@ -686,237 +621,6 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_c1_kernel(BwdC1Params p) {
                 for (int row = bx + nbx; row < p.nparts; row += nbx) p.a_part[((size_t)row * 10 + k) * 32 + c] = 0.f;
             }
         }
-            } else {
-        // =============================== CONSUMERS, taps split over the waves (TS) ===================================
-        // The nine weight-gradient accumulators are divided by TAP (wave 0: shifts 0-2, waves 1-3: two each), every wave walks all 16
-        // k-steps of the tile: 48 / 32 accumulator registers instead of 144.  The room is spent on what the k-share form could not
-        // afford: both halves of the data gradient together (one weight fragment for two MFMAs), a fragment ring of three, the gate
-        // and patch operands requested BEFORE the k loop, and the conv1 rebuild (waves 1-3: 3 / 3 / 2 blocks) issued at the top of the
-        // iteration with its tails after the weight-gradient loop.  No cross-wave reduction of dW at the end.
-        auto consumer_ts = [&](auto nt_c, auto nb_c) {
-        constexpr int NT = decltype(nt_c)::value, NB = decltype(nb_c)::value;
-        const int r = lane & 31, hh = lane >> 5;
-        f32x16 accw[NT], accA;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) accw[t][i] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) accA[i] = 0.f;
-        const int tfirst = wave == 0 ? 0 : 1 + 2 * wave;           // shift index t = si*3 + sj: 0-2 | 3,4 | 5,6 | 7,8
-        constexpr bool three = NT == 3;
-        int xoff[3][2];
-#pragma unroll
-        for (int tj = 0; tj < 3; ++tj)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) xoff[tj][ks] = (r + tj) * 32 + (((ks * 2 + hh) ^ bc_xswz(r + tj)) * 8);
-        const int woff = (hh * 32 + r) * 8;
-        const unsigned bitpos = 16 * ((r >> 2) & 1) + (r & 3) + 4 * (r >> 3);
-        const int tap = r < 9 ? r : 0;
-        const int pdx = tap % 3;
-        const int ptap = (tap / 3) * XTL::XP + ((pdx & 1) ? XTL::XB + pdx - 1 : pdx) + 4 * hh;      // (copy B for dx = 1: 4-byte-aligned 8-byte reads)
-        const T* cbase = cst0 + (r == 9 ? 0 : XCN);
-        int offA[2], offT[NT][2];
-        {
-            const int i16 = lane & 15, gbit = (lane >> 4) & 1;
-            const int qq = i16 >> 2, pp = i16 & 3, ch = 16 * gbit + 4 * pp;
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int kl = 8 * hh + qq + 4 * half;
-                offA[half] = kl * 32 + ab_chunk(ch >> 2, kl);
-#pragma unroll
-                for (int k = 0; k < NT; ++k) {
-                    const int t = tfirst + k;
-                    const int si = t / 3, sj = t - 3 * si;
-                    offT[k][half] = si * ROWE + (kl + sj) * 32 + (ch ^ swz<T>(kl + sj));
-                }
-            }
-        }
-        C1Mma c1m;
-        c1mma_init(c1m, p.w1, p.sc1, p.sh1, lane);
-        int c1o[2][2];
-        c1tile_lane_offsets<W, XTR>(0, lane, c1o[0][0], c1o[0][1]);
-        c1tile_lane_offsets<W, XTR>(1, lane, c1o[1][0], c1o[1][1]);
-        // conv1 rebuild: blocks b = 2*row + half of the next stage's activation tile; wave 1: 0-2, wave 2: 3-5, wave 3: 6, 7
-        constexpr int nbld = NB;
-        const int bld0 = wave == 0 ? 0 : 3 * (wave - 1);
-        f32x16 dd[NB > 0 ? NB : 1];
-        auto build_issue = [&](const StInfo& si, int s) {
-            if (!si.live || !si.mainst) return;
-            const T* xt = xt0 + (s % 3) * XTL::N;
-#pragma unroll
-            for (int k = 0; k < nbld; ++k)
-                dd[k] = c1mma_block_mfma_b(c1m, xt + ((bld0 + k) >> 1) * XTL::XP, c1o[(bld0 + k) & 1][0], c1o[(bld0 + k) & 1][1]);
-        };
-        auto build_finish = [&](const StInfo& si, int s) {
-            if (!si.live || !si.mainst) return;
-            T* abuf = ab + (s & 1) * ABUF;
-#pragma unroll
-            for (int k = 0; k < nbld; ++k) {
-                const int b = bld0 + k, brow = b >> 1, half = b & 1;
-                const int row = TH * si.j - 1 + brow;
-                const bool inimg = row >= 0 && row < H;
-                float a[16];
-                unsigned mkd;
-                c1mma_block_tail<false>(c1m, dd[k], a, mkd);
-                if (!inimg) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) a[i] = 0.f;
-                }
-                T* dst = abuf + (brow * W + half * 32 + r) * 32;
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    float v4[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v4[e] = a[4 * g4 + e];
-                    store4<T>(dst + ab_chunk(hh + 2 * g4, r), v4);
-                }
-            }
-        };
-
-        StInfo csi = st_first();
-        build_issue(csi, 0);
-        build_finish(csi, 0);
-        auto citer = [&](int s) {
-            bc_barrier();
-            const StInfo cs = csi;
-            csi = st_next(csi, s + 1);
-            build_issue(csi, s + 1);                          // next stage's conv1 blocks: reads + MFMAs now, tails after the weight gradient
-            if (cs.live && cs.mainst) {
-                const T* __restrict__ win = dzr + cs.pos * TH * ROWE;
-                const T* __restrict__ abuf = ab + (s & 1) * ABUF;
-                // ---- weight gradient: this wave's taps over all 16 k-steps of the tile ----------------------------------------
-                {
-                    constexpr int NKS = BM / 16;
-                    bf16x8 afr[3], bfr[3][NT];
-                    auto ldk = [&](int kk, bf16x8& a, bf16x8 (&b)[NT]) {
-                        const int aimm = kk * 16 * 32;
-                        const int dimm = (kk / 4) * ROWE + (kk % 4) * 16 * 32;
-                        a = join_tr(ds_read_tr16_b64(abuf + aimm + offA[0]), ds_read_tr16_b64(abuf + aimm + offA[1]));
-                        b[0] = join_tr(ds_read_tr16_b64(win + dimm + offT[0][0]), ds_read_tr16_b64(win + dimm + offT[0][1]));
-                        b[1] = join_tr(ds_read_tr16_b64(win + dimm + offT[1][0]), ds_read_tr16_b64(win + dimm + offT[1][1]));
-                        if constexpr (three) b[2] = join_tr(ds_read_tr16_b64(win + dimm + offT[2][0]), ds_read_tr16_b64(win + dimm + offT[2][1]));
-                    };
-                    ldk(0, afr[0], bfr[0]);
-                    ldk(1, afr[1], bfr[1]);
-#pragma unroll
-                    for (int kk = 0; kk < NKS; ++kk) {
-                        if (kk + 2 < NKS) ldk(kk + 2, afr[(kk + 2) % 3], bfr[(kk + 2) % 3]);
-                        __builtin_amdgcn_sched_barrier(0);
-                        accw[0] = mfma(afr[kk % 3], bfr[kk % 3][0], accw[0]);
-                        accw[1] = mfma(afr[kk % 3], bfr[kk % 3][1], accw[1]);
-                        if constexpr (three) accw[2] = mfma(afr[kk % 3], bfr[kk % 3][2], accw[2]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-                build_finish(csi, s + 1);
-                // ---- data gradient of tile row `wave` (both 32-pixel halves), D[pixel][channel]; gate; contract over the pixels ----------
-                {
-                    const T* __restrict__ dbase = win + wave * ROWE;
-                    const T* __restrict__ xtb = xt0 + (s % 3) * XTL::N;
-                    const unsigned* __restrict__ mkb = mk0 + (s & 1) * BM;
-                    f32x16 acc[2];
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) acc[mt][i] = 0.f;
-                    bf16x8 xf[3][2], wf[3];
-                    auto ld = [&](int k, bf16x8 (&xd)[2], bf16x8& wd) {
-                        const int tp = k >> 1, ks = k & 1, ti = tp / 3, tj = tp % 3;
-#pragma unroll
-                        for (int mt = 0; mt < 2; ++mt)
-                            xd[mt] = *reinterpret_cast<const bf16x8*>(dbase + (ti * ROWE + mt * 32 * 32) + xoff[tj][ks]);
-                        wd = *reinterpret_cast<const bf16x8*>(wsm + woff + ((tp * 4 + ks * 2) * 32) * 8);
-                    };
-                    ld(0, xf[0], wf[0]);
-                    ld(1, xf[1], wf[1]);
-#pragma unroll
-                    for (int k = 0; k < 18; ++k) {
-                        if (k + 2 < 18) ld(k + 2, xf[(k + 2) % 3], wf[(k + 2) % 3]);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int mt = 0; mt < 2; ++mt) acc[mt] = mfma(xf[k % 3][mt], wf[k % 3], acc[mt]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    // gate / patch operands: requested before the k loop
-                    u32x4 m4v[2][4];
-                    u32x4 pfw[2][2];
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) {
-                        const unsigned* mrow = mkb + wave * W + mt * 32 + 4 * hh;
-                        const T* prow_x = (r < 9 ? xtb : cbase) + wave * XTL::XP + mt * 32 + ptap;
-#pragma unroll
-                        for (int i4 = 0; i4 < 4; ++i4) m4v[mt][i4] = *reinterpret_cast<const u32x4*>(mrow + 8 * i4);
-#pragma unroll
-                        for (int sx = 0; sx < 2; ++sx)
-#pragma unroll
-                            for (int jj = 0; jj < 2; ++jj) {
-                                const c1_u32x2_a4 q4 = *reinterpret_cast<const c1_u32x2_a4*>(prow_x + 16 * sx + 8 * jj);
-                                pfw[mt][sx][2 * jj] = q4[0]; pfw[mt][sx][2 * jj + 1] = q4[1];
-                            }
-                    }
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt) {
-                        unsigned gv[16];
-#pragma unroll
-                        for (int i4 = 0; i4 < 4; ++i4)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const int t = __builtin_amdgcn_sbfe((int)m4v[mt][i4][e], bitpos, 1u);
-                                const float av = acc[mt][4 * i4 + e];
-                                gv[4 * i4 + e] = __builtin_bit_cast(unsigned, av) & (unsigned)t;
-                            }
-#pragma unroll
-                        for (int sx = 0; sx < 2; ++sx) {
-                            bf16x8 gf;
-#pragma unroll
-                            for (int jj = 0; jj < 8; ++jj) gf[jj] = (bf16_t)__builtin_bit_cast(float, gv[8 * sx + jj]);
-                            accA = mfma(__builtin_bit_cast(bf16x8, pfw[mt][sx]), gf, accA);
-                        }
-                    }
-                }
-            } else {
-                build_finish(csi, s + 1);                     // (a loader-only stage)
-            }
-        };
-        for (int s = 0; s < NI; s += 2) {
-            citer(s);
-            citer(s + 1);
-        }
-        // ---- this workgroup's slabs: every wave owns its taps of dW; the four row partials of [A; sum g] are summed through LDS ----
-        bc_barrier();
-        {
-            float* out = p.ws + (size_t)bx * 9 * 32 * 32;
-#pragma unroll
-            for (int k = 0; k < NT; ++k) {
-                const int t = tfirst + k, tp = (2 - t / 3) * 3 + (2 - t % 3);
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int cin = (i & 3) + 8 * (i >> 2) + 4 * hh;
-                    out[((size_t)tp * 32 + cin) * 32 + r] = accw[k][i];
-                }
-            }
-        }
-        float* redA = reinterpret_cast<float*>(smem);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) redA[(wave * 16 + i) * 64 + lane] = accA[i];
-        bc_barrier();
-        if (wave == 1) {
-            for (int q = lane; q < 320; q += 64) {
-                const int k = q >> 5, c = q & 31;
-                const int i = 4 * (k >> 3) + (k & 3), ln = c + 32 * ((k >> 2) & 1);
-                float tot = 0.f;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) tot += redA[(w * 16 + i) * 64 + ln];
-                p.a_part[((size_t)bx * 10 + k) * 32 + c] = tot;
-                for (int row = bx + nbx; row < p.nparts; row += nbx) p.a_part[((size_t)row * 10 + k) * 32 + c] = 0.f;
-            }
-        }
-        };
-        if (wave == 0) consumer_ts(std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{});
-        else if (wave == 3) consumer_ts(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
-        else consumer_ts(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{});
-        }
     }
 }
 
@@ -933,12 +637,12 @@ int bwd_fused_c1_nwg(int B, int H) {
 // -1 = not covered (SED_BWD_FUSED_C1=0 keeps the two-kernel form); workgroups launched are returned through *nwg
 int launch_bwd_fused_c1(const float* x1, const float* fmean, const float* fstd, const float* w1, const float* sc1, const float* sh1,
                         const void* dy, const void* z2, const float* sc2, const float* sh2, const float* ca, const float* cb,
-                        const float* cc, const void* wpack_t, const void* mask, float* a_part, int nparts, float* ws, int B, int H,
+                        const float* cc, const void* wpack_t, float* a_part, int nparts, float* ws, int B, int H,
                         int* nwg, hipStream_t st) {
     if (const char* e = sed_getenv("SED_BWD_FUSED_C1")) if (e[0] == '0') return -1;
     BwdC1Params p = {};
     p.x1 = x1; p.fmean = fmean; p.fstd = fstd; p.w1 = w1; p.sc1 = sc1; p.sh1 = sh1; p.dy = dy; p.z2 = z2; p.sc2 = sc2; p.sh2 = sh2;
-    p.ca = ca; p.cb = cb; p.cc = cc; p.wpack_t = wpack_t; p.mask = reinterpret_cast<const unsigned*>(mask); p.a_part = a_part;
+    p.ca = ca; p.cb = cb; p.cc = cc; p.wpack_t = wpack_t; p.a_part = a_part;
     p.ws = ws; p.B = B; p.H = H; p.nparts = nparts;
     if (const char* e = sed_getenv("SED_BC_PRIO")) p.prio = atoi(e);
     int n = bwd_fused_c1_nwg(B, H);
@@ -948,29 +652,9 @@ int launch_bwd_fused_c1(const float* x1, const float* fmean, const float* fstd, 
     p.totalTiles = B * p.tilesPerImg;
     p.tpb = cdiv(p.totalTiles, n);
     constexpr size_t lds = ((size_t)18 * 68 * 32 + (size_t)2 * 256 * 32 + 9 * 32 * 32) * sizeof(bf16_t) + (size_t)(3 * C1Tile<64, 6>::N + 2 * 6 * C1Tile<64, 6>::XP) * sizeof(bf16_t) +
-                           (size_t)2 * 256 * sizeof(unsigned);
+                           (size_t)2 * 256 * sizeof(unsigned);      // (the last term: the unused 2 KB gap in front of the constant tiles, see the kernel)
     static_assert(lds <= 160 * 1024 && lds >= (size_t)(3 * 9 + 4) * 16 * 64 * 4, "LDS budget (the final reductions reuse it)");
-#ifdef SED_EXPERIMENTS
-    // tap-split consumers (SED_BC_TS=1): parity-green, 0.73 vs 0.61 ms (30 spilled registers, 88 instead of 78 MFMAs on the busiest wave)
-    if (const char* e = sed_getenv("SED_BC_TS"); e && e[0] == '1') {
-        if (int rc_ = sed_set_max_lds<&conv_bwd_fused_c1_kernel<true>>(lds)) return rc_;
-        conv_bwd_fused_c1_kernel<true><<<dim3(n), dim3(512), lds, st>>>(p);
-        return 0;
-    }
-#endif
-    bool lb = false;
-    if (const char* e = sed_getenv("SED_BC_LB")) lb = e[0] == '1';
-    if (lb && mask != nullptr) {
-        if (int rc_ = sed_set_max_lds<&conv_bwd_fused_c1_kernel<false, true>>(lds)) return rc_;
-        conv_bwd_fused_c1_kernel<false, true><<<dim3(n), dim3(512), lds, st>>>(p);
-        return 0;
-    }
-    if (mask == nullptr) {       // derived gate (round 5, what the engine runs)
-        if (int rc_ = sed_set_max_lds<&conv_bwd_fused_c1_kernel<false, false, true>>(lds)) return rc_;
-        conv_bwd_fused_c1_kernel<false, false, true><<<dim3(n), dim3(512), lds, st>>>(p);
-        return 0;
-    }
-    if (int rc_ = sed_set_max_lds<&conv_bwd_fused_c1_kernel<false>>(lds)) return rc_;
-    conv_bwd_fused_c1_kernel<false><<<dim3(n), dim3(512), lds, st>>>(p);
+    if (int rc_ = sed_set_max_lds<&conv_bwd_fused_c1_kernel>(lds)) return rc_;
+    conv_bwd_fused_c1_kernel<<<dim3(n), dim3(512), lds, st>>>(p);
     return 0;
 }

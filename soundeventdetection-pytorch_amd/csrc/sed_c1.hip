@@ -745,8 +745,8 @@ static int wgrad_fused_c1_impl(int dtype, const float* x1, const float* fmean, c
                                const float* scale, const float* shift, const float* ca, const float* cb,
                                const float* cc, int pool, void* dz_out, float* dwpack, float* workspace, int B, int H,
                                int W, int Coutp, void* stream, float* dw, int Cout, int Cin) {
-    SED_REQUIRE(dtype == SED_BF16 && x1 && w1 && pro_scale && pro_shift && gsrc && zsrc && scale && shift && ca && cb && cc,
-                "operands");
+    SED_REQUIRE(dtype == SED_BF16 && x1 && w1 && pro_scale && pro_shift && gsrc && zsrc && scale && shift && ca && cb && cc &&
+                dwpack, "operands");
     Wgrad2Params p = {};
     p.x = nullptr; p.pro_scale = pro_scale; p.pro_shift = pro_shift; p.dz = gsrc; p.zsrc = zsrc; p.scale = scale; p.shift = shift;
     p.ca = ca; p.cb = cb; p.cc = cc; p.dz_out = dz_out; p.ws = workspace;
@@ -759,7 +759,7 @@ static int wgrad_fused_c1_impl(int dtype, const float* x1, const float* fmean, c
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) { sed_set_error(std::string("C1 mode wgrad launch failed: ") + hipGetErrorString(e_)); return 2; }
     const size_t n = (size_t)9 * 32 * Coutp;
-    reduce_or_defer(workspace, dwpack, p.strips, n, dw, Cout, Cin, 32, Coutp, (hipStream_t)stream);
+    reduce_wgrad_slabs(workspace, dwpack, p.strips, n, dw, Cout, Cin, 32, Coutp, (hipStream_t)stream);
     SED_LAUNCH_CHECK();
     return 0;
 }
@@ -796,18 +796,19 @@ extern "C" int sed_conv3x3_bwd_fused_c1(int dtype, const float* x1, const float*
                                         float* workspace, int B, int H, int W, int Coutp, float* dw, int Cout, int Cin, void* stream) {
     SED_REQUIRE(sed_conv3x3_bwd_fused_c1_supported(dtype, W, Coutp, pool), "covered: bf16, W = 64, 32 -> 32 channels, 2x2 pooling");
     SED_REQUIRE(x1 && w1 && pro_scale && pro_shift && gsrc && zsrc && scale && shift && ca && cb && cc && wpack_t &&
-                a_partial && workspace && B > 0 && H > 0, "operands");      // (dwpack == NULL: deferred reduction)
+                a_partial && dwpack && workspace && B > 0 && H > 0, "operands");
+    SED_REQUIRE(relu_mask == nullptr, "the ReLU gate is derived from the rebuilt activation tile: relu_mask must be NULL");
     SED_REQUIRE((fmean == nullptr) == (fstd == nullptr), "mean/std must both be given or both NULL");
     SED_REQUIRE(dw == nullptr || (Cout > 0 && Cin > 0 && Cout <= 32 && Cin <= 32), "unpacked gradient operands");
     SED_REQUIRE((double)H * W * 32 * 2 < 2147483648.0, "one image must stay below 2 GiB");
     int nwg = 0;
-    const int rc = launch_bwd_fused_c1(x1, fmean, fstd, w1, pro_scale, pro_shift, gsrc, zsrc, scale, shift, ca, cb, cc, wpack_t, relu_mask,
+    const int rc = launch_bwd_fused_c1(x1, fmean, fstd, w1, pro_scale, pro_shift, gsrc, zsrc, scale, shift, ca, cb, cc, wpack_t,
                                        a_partial, sed_conv_dgrad_c1_nparts(), workspace, B, H, &nwg, (hipStream_t)stream);
     SED_REQUIRE(rc >= 0, "not covered");
     if (rc) return rc;
     SED_LAUNCH_CHECK();
     const size_t n = (size_t)9 * 32 * 32;
-    reduce_or_defer(workspace, dwpack, nwg, n, dw, Cout, Cin, 32, 32, (hipStream_t)stream);
+    reduce_wgrad_slabs(workspace, dwpack, nwg, n, dw, Cout, Cin, 32, 32, (hipStream_t)stream);
     SED_LAUNCH_CHECK();
     return 0;
 }

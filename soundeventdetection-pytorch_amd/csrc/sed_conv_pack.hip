@@ -4,7 +4,7 @@
 // autograd returns their gradient in the same layout.  The MFMA kernels read the operator as [chunk][tap][32/KR][Coutp][KR]
 // (sed_conv.hip) -- transposed and tap-flipped for the data gradient, as two 16-bit images for the split-operand dtypes
 // (sed_conv_x3.hip) -- and leave the weight gradient as one [9][Cinp][Coutp] slab per workgroup.  This file holds the pack / unpack
-// kernels, the fixed-order slab reduction (immediate, deferred or batched over layers) and their entry points.
+// kernels, the fixed-order slab reduction and their entry points.
 #include "conv_common.h"
 
 // =================================================================================================
@@ -181,59 +181,9 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restr
     }
 }
 
-// Round 6: the reduction can be DEFERRED.  An entry point called with dwpack == NULL leaves its per-workgroup slabs in the caller's
-// workspace, reports their count through sed_wgrad_last_slabs() (per calling thread, like sed_last_error) and launches nothing; the
-// caller reduces later -- sed_wgrad_reduce for one layer, sed_wgrad_reduce_batch for several layers in ONE launch (the weight gradients
-// feed only the optimizer / the gradient all-reduce: seven dependent 10 us launches of a train step become one at its end).
-static thread_local int g_last_slabs = 0;
-int reduce_or_defer(const float* ws, float* dwpack, int slabs, size_t n, float* dw, int Cout, int Cin, int Cinp, int Coutp, hipStream_t st) {
-    g_last_slabs = slabs;
-    if (dwpack == nullptr) return 0;
+int reduce_wgrad_slabs(const float* ws, float* dwpack, int slabs, size_t n, float* dw, int Cout, int Cin, int Cinp, int Coutp, hipStream_t st) {
     wgrad_reduce_kernel<<<cdiv(n, 64), 1024, 0, st>>>(ws, dwpack, slabs, n, dw, Cout, Cin, Cinp, Coutp);
     return 0;
-}
-extern "C" int sed_wgrad_last_slabs(void) { return g_last_slabs; }
-
-// desc[i] = {ws, dwpack, dw, slabs, n, Cout, Cin, Cinp, Coutp, first_block} as ten 64-bit words; block b serves 64 outputs of the
-// descriptor whose block range holds b (same arithmetic and summation order as wgrad_reduce_kernel: bit-identical results)
-__global__ __launch_bounds__(1024) void wgrad_reduce_batch_kernel(const long long* __restrict__ desc, int nd) {
-    __shared__ float red[16][64];
-    int d = 0;
-    for (int i = 1; i < nd; ++i)
-        if ((int)desc[i * 10 + 9] <= (int)blockIdx.x) d = i;
-    const long long* e = desc + d * 10;
-    const float* __restrict__ ws = reinterpret_cast<const float*>(e[0]);
-    float* __restrict__ out = reinterpret_cast<float*>(e[1]);
-    float* __restrict__ dw = reinterpret_cast<float*>(e[2]);
-    const int strips = (int)e[3];
-    const size_t n = (size_t)e[4];
-    const int Cout = (int)e[5], Cin = (int)e[6], Cinp = (int)e[7], Coutp = (int)e[8];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const size_t i = (size_t)((int)blockIdx.x - (int)e[9]) * 64 + lane;
-    float t = 0.f;
-    if (i < n) {
-        int sidx = wv;
-        for (; sidx + 16 * 7 < strips; sidx += 16 * 8) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = ws[(size_t)(sidx + 16 * u) * n + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t += v[u];
-        }
-        for (; sidx < strips; sidx += 16) t += ws[(size_t)sidx * n + i];
-    }
-    red[wv][lane] = t;
-    __syncthreads();
-    if (wv == 0 && i < n) {
-        float tot = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) tot += red[k][lane];
-        if (out != nullptr) out[i] = tot;
-        if (dw != nullptr) {
-            const int co = (int)(i % Coutp), ci = (int)((i / Coutp) % Cinp), tap = (int)(i / ((size_t)Coutp * Cinp));
-            if (co < Cout && ci < Cin) dw[((size_t)co * Cin + ci) * 9 + tap] = tot;
-        }
-    }
 }
 
 // =================================================================================================
@@ -278,23 +228,6 @@ extern "C" int sed_pack_conv_weights_batch(int dtype, const void* desc, int n, i
         pack_weight_batch_x3_kernel<<<total_blocks, 256, 0, (hipStream_t)stream>>>((const long long*)desc, n, dtype == SED_F32H3);
     else
         SED_REQUIRE(false, "bad dtype");
-    SED_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sed_wgrad_reduce(const float* workspace, int nslabs, float* dwpack, float* dw, int Cout, int Cin, int Cinp, int Coutp,
-                                void* stream) {
-    SED_REQUIRE(workspace && nslabs > 0 && dwpack && Cinp > 0 && Coutp > 0, "operands");
-    SED_REQUIRE(dw == nullptr || (Cout > 0 && Cin > 0 && Cout <= Coutp && Cin <= Cinp), "unpacked gradient operands");
-    const size_t n = (size_t)9 * Cinp * Coutp;
-    wgrad_reduce_kernel<<<cdiv(n, 64), 1024, 0, (hipStream_t)stream>>>(workspace, dwpack, nslabs, n, dw, Cout, Cin, Cinp, Coutp);
-    SED_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sed_wgrad_reduce_batch(const void* desc, int n, int total_blocks, void* stream) {
-    SED_REQUIRE(desc && n > 0 && n <= 64 && total_blocks > 0, "descriptor table");
-    wgrad_reduce_batch_kernel<<<total_blocks, 1024, 0, (hipStream_t)stream>>>((const long long*)desc, n);
     SED_LAUNCH_CHECK();
     return 0;
 }

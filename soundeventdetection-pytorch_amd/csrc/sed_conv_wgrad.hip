@@ -299,6 +299,7 @@ static int wgrad_common(int dtype, int pro, int dzmode, const void* x, const flo
                         const float* cb, const float* cc, int pool, void* dz_out, float* dwpack, float* workspace,
                         int B, int H, int W, int Cinp, int Coutp, hipStream_t st, float* dw = nullptr, int Cout = 0, int Cin = 0,
                         bool anyw = false) {
+    SED_REQUIRE(dwpack, "the reduced gradient (dwpack) is required");
     const int dzexp = (int)(signed char)((dtype >> 8) & 0xff);      // SED_F32H3: exponent applied to dz before the fp16 split
     dtype &= 0xff;
     if (dzexp != 0 && dtype != SED_F32H3) { sed_set_error("sed_conv3x3_wgrad: an operand exponent belongs to dtype SED_F32H3"); return 1; }
@@ -347,7 +348,7 @@ static int wgrad_common(int dtype, int pro, int dzmode, const void* x, const flo
         if (e_ != hipSuccess) { sed_set_error(std::string("sed_conv3x3_wgrad: launch failed: ") + hipGetErrorString(e_)); return 2; }
     }
     const size_t n = (size_t)9 * Cinp * Coutp;
-    reduce_or_defer(workspace, dwpack, p.strips, n, dw, Cout, Cin, Cinp, Coutp, st);
+    reduce_wgrad_slabs(workspace, dwpack, p.strips, n, dw, Cout, Cin, Cinp, Coutp, st);
     {
         hipError_t e_ = hipGetLastError();
         if (e_ != hipSuccess) { sed_set_error(std::string("sed_conv3x3_wgrad: reduce launch failed: ") + hipGetErrorString(e_)); return 2; }
@@ -435,7 +436,7 @@ extern "C" int sed_conv3x3_bwd_fused(int dtype, int pro, const void* x, const fl
     SED_REQUIRE(sed_conv3x3_bwd_fused_supported_pool(dtype, W, Cinp, Coutp, dzmode, pro, epi, dzmode == SED_DZ_POOL ? pool : 2),
                 "covered: bf16; W = 32: 32 -> 64 (DZ_BN, no prologue, STORE / POOLSTATS) or 64 -> 64 (DZ_POOL pool 2, BN+ReLU prologue, "
                 "RELUBWD); W = 16 / 8: 64 / 128 -> 128 in the same two forms (DZ_POOL with pool 1 or 2)");
-    SED_REQUIRE(B > 0 && H > 0 && x && gsrc && zsrc && ca && cb && cc && wpack_t && dx && workspace, "operands");      // (dwpack == NULL: deferred reduction)
+    SED_REQUIRE(B > 0 && H > 0 && x && gsrc && zsrc && ca && cb && cc && wpack_t && dx && dwpack && workspace, "operands");
     SED_REQUIRE(pro == SED_PRO_NONE || (pro_scale && pro_shift), "prologue operands");
     SED_REQUIRE(dzmode != SED_DZ_POOL || (scale && shift && (pool == 1 || pool == 2)), "pool-backward operands");
     SED_REQUIRE(epi == SED_EPI_STORE || (zref && epi_scale && epi_shift && epi_mean && epi_invstd && partial && nparts > 0), "epilogue operands");
@@ -458,7 +459,7 @@ extern "C" int sed_conv3x3_bwd_fused(int dtype, int pro, const void* x, const fl
     if (rc) return rc;
     SED_LAUNCH_CHECK();
     const size_t n = (size_t)9 * Cinp * Coutp;
-    reduce_or_defer(workspace, dwpack, p.nwg, n, dw, Cout, Cin, Cinp, Coutp, (hipStream_t)stream);
+    reduce_wgrad_slabs(workspace, dwpack, p.nwg, n, dw, Cout, Cin, Cinp, Coutp, (hipStream_t)stream);
     SED_LAUNCH_CHECK();
     return 0;
 }

@@ -46,6 +46,28 @@ SPECIALISED_WIDTHS = (8, 16, 32, 64)     # line widths of the specialised conv k
 MAX_WIDTH = 256                          # SED_ANYW_MAX_W (include/sed_hip.h)
 
 
+C1_ROUTES = ("z1", "c1_fused", "c1_stats")
+
+
+def block0_route(lib, precision: str, mel_bins: int, channels: int, pool: int, generic_first: bool, environ=_os.environ) -> str:
+    """How block 0 runs, decided once per plan (host only: no tensor, no device):
+      'z1'        conv1's output z1 lives in memory like every other layer's (fp32, the split-operand modes, widths other than 64,
+                  channel counts other than 32, generic_first, SED_C1_MODE=0)
+      'c1_fused'  C1 mode -- z1 is never written, its consumers rebuild it from the 1-channel input (csrc/conv_common.h) -- with
+                  conv2's weight gradient and gated data gradient in one launch (csrc/sed_bwd_fused_c1.hip), which derives conv1's
+                  ReLU gate itself: the forward stores no mask
+      'c1_stats'  C1 mode with the two-kernel backward (block-0 pool 1, SED_BWD_FUSED=0): sed_conv3x3_wgrad_fused_c1_u, then
+                  sed_conv3x3_dgrad_c1_stats gated with the bit mask the forward stores
+    A backward that needs g1 in memory (need_dx, eval mode) takes the 'c1_plain' launches in either C1 route: chosen per backward."""
+    dt = L.SED_BF16 if precision == "bf16" else L.SED_F32
+    if generic_first or environ.get("SED_C1_MODE", "1") == "0" or not lib.sed_c1_mode_supported(dt, mel_bins, channels, channels):
+        return "z1"
+    if precision == "bf16" and environ.get("SED_BWD_FUSED", "1") != "0" and \
+            lib.sed_conv3x3_bwd_fused_c1_supported(dt, mel_bins, channels, pool):
+        return "c1_fused"
+    return "c1_stats"
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -223,7 +245,6 @@ class CnnEngine(OptimizerExtMixin):
         # reference's single process does (spectogram_models.py:142-143 under train.py:95-97): the per-workgroup partial
         # sums are reduced to one row per rank, summed over the ranks, and finalized with count * world.
         self.bn_sync = None
-        self.wg_flush_per_group = False      # set by FusedTrainer under data parallel (see backward: group_done)
         self._e_shift = 0                    # f16x3 pre-scale shift of the running backward (_grad_dtype; 0 outside the new backward kinds)
 
     @staticmethod
@@ -357,22 +378,21 @@ class CnnEngine(OptimizerExtMixin):
         p.c1_ws = torch.empty((lib.sed_conv_c1_nparts(B, T, F), 9, l0.coutp), **f32)
         p.c1_gram = torch.empty((lib.sed_conv_c1_gram_nparts(B, T, F), 54), **f32)
         # "C1 mode": block 0 without conv1's output in memory (csrc/conv_common.h): conv2's forward and weight gradient
-        # rebuild relu(bn1(conv1(x))) on the matrix pipe from the 1-channel input, the data gradient gates with a bit
-        # mask of conv1's ReLU decisions, BN1's statistics and backward come from Gram statistics of the input patches.
+        # rebuild relu(bn1(conv1(x))) on the matrix pipe from the 1-channel input, the data gradient gates with conv1's ReLU
+        # decisions, BN1's statistics and backward come from Gram statistics of the input patches.
         # Removes 4 of block 0's 12.75 HBM passes (6.41 -> 6.2 ms/step); SED_C1_MODE=0 restores the z1 dataflow.
-        import os as _os
-        p.c1_mode = bool(lib.sed_c1_mode_supported(self.dt, F, self.cfg[0][0], self.cfg[0][0])) and \
-            _os.environ.get("SED_C1_MODE", "1") != "0" and self.cfg[0][1] in (1, 2) and not self.generic_first
+        p.c1_route = block0_route(lib, self.precision, F, self.cfg[0][0], self.cfg[0][1], self.generic_first)
+        p.c1_mode = p.c1_route != "z1"
         if self.generic_first:
             c0p = pad32(self.cin0)
             p.x_nhwc = torch.zeros((B, T, F, c0p), dtype=self.tdtype, device=dev)
             p.dx = torch.empty((B, T, F, c0p), dtype=self.tdtype, device=dev)
         p.c1_A = torch.empty((9, l0.coutp), **f32)
-        # fused data gradient of block 0 (csrc/sed_dgrad_c1.hip): per-workgroup partials and sums of [A (9 taps); sum g]
-        p.c1_dg_fused = p.c1_mode and _os.environ.get("SED_DGRAD_FUSED", "1") != "0"
+        # block 0's gated data gradient in C1 mode: per-workgroup partials and sums of [A (9 taps); sum g]
         p.c1_a10_part = torch.empty((lib.sed_conv_dgrad_c1_nparts(), 10, 32), **f32)
         p.c1_a10 = torch.empty((10, 32), **f32)
-        p.c1_mask = None          # C1 mode: conv1's ReLU decisions as a bit mask -- only when the backward does not derive them (below)
+        # conv1's ReLU decisions as a bit mask, stored by the training forward for the one route whose backward reads it
+        p.c1_mask = torch.empty((B, T, F, 2), dtype=torch.int16, device=dev) if p.c1_route == "c1_stats" else None
         # Pool + ReLU + BN2 backward statistics from POOLED tensors (include/sed_hip.h, sed_conv3x3_dgrad_poolstats): a 2x2-pooled
         # block whose output gradient comes from the next block's conv1 data gradient gets its statistics in that kernel's
         # epilogue (forward: active-pixel counts beside the pooled activation) -- no separate pass over z2.  SED_POOL_STATS=z
@@ -402,30 +422,8 @@ class CnnEngine(OptimizerExtMixin):
                 if not (p.c1_mode and bi == 0):
                     p.bwd_fused[bi][1] = bool(lib.sed_conv3x3_bwd_fused_supported_pool(self.dt, l2.W, l2.cinp, l2.coutp, L.DZ_POOL, L.PRO_BNRELU,
                                                                                         L.EPI_RELUBWD, self.cfg[bi][1]))
-        # block 0 in C1 mode: weight gradient + fused data gradient of conv2 in one launch (csrc/sed_bwd_fused_c1.hip)
-        p.c1_bwd_fused = bool(p.c1_mode and p.c1_dg_fused and self.precision == "bf16" and _os.environ.get("SED_BWD_FUSED", "1") != "0"
-                              and lib.sed_conv3x3_bwd_fused_c1_supported(self.dt, F, self.cfg[0][0], self.cfg[0][1]))
-        # Round 5: the fused block-0 backward derives conv1's ReLU gate from the activation tile it rebuilds for its weight gradient, so
-        # the forward neither builds nor stores the bit mask (SED_C1_GATE=mask: the round-4 form, for the A/B); the unfused kernels
-        # (sed_conv3x3_dgrad_c1_stats / sed_conv3x3_dgrad_c1) still take the forward's mask
-        # Round 5: block 0's conv1 backward tail (partial sums of [A; sum g] -> BN1 backward coefficients -> dW1 combine) in one launch with
-        # the forward's reduced Gram statistics (sed_c1_bwd_tail); SED_C1_TAIL=0 keeps the three kernels (and SyncBN always does)
+        # block 0's conv1 backward tail in C1 mode (sed_c1_bwd_tail) takes the Gram statistics the forward's finalize reduced
         p.c1_gsum = torch.empty(54, dtype=torch.float64, device=dev)
-        p.c1_tail = bool(p.c1_mode and p.c1_dg_fused and not self.generic_first and _os.environ.get("SED_C1_TAIL", "1") != "0")
-        p.c1_gate_derived = bool(p.c1_bwd_fused and _os.environ.get("SED_C1_GATE", "derived") != "mask")
-        if p.c1_mode and not p.c1_gate_derived:
-            p.c1_mask = torch.empty((B, T, F, 2), dtype=torch.int16, device=dev)
-        # Round 6, SED_WGRAD_REDUCE=batch: the weight-gradient reductions of a step in ONE launch at the end of the backward (every layer then
-        # keeps its own slab workspace, ~0.25 GB at the bench shape).  Bit-identical gradients; measured NEUTRAL in an interleaved A/B
-        # (4.0922 vs 4.0933 ms/step, profiles/r06_l_ab_wgrad_reduce_batch.txt: the seven 10 us reductions are bandwidth, and the launch
-        # boundaries around them already overlap the neighbouring kernels' ramps) -- so the default stays one reduction per layer.
-        p.wg_defer = _os.environ.get("SED_WGRAD_REDUCE", "inline") == "batch"
-        p.wg_pending, p.wg_tables = [], {}
-        if p.wg_defer:
-            for blk in p.layers:
-                for ly in blk:
-                    if ly.cinp != 1:
-                        ly.wgrad_ws = torch.empty(max(1, lib.sed_conv_wgrad_ws_floats(B, ly.H, ly.W, ly.cinp, ly.coutp)), **f32)
         p.pool_flag = torch.zeros(nb, dtype=torch.int32, device=dev)
         p.bwd_part = torch.empty(max(1, max_bwd_parts), **f32)
         maxc = max(ly.coutp for blk in p.layers for ly in blk)
@@ -535,34 +533,6 @@ class CnnEngine(OptimizerExtMixin):
         pre = f"conv_blocks.{bi}.bn{j + 1}."
         return pre + "weight", pre + "bias", pre + "running_mean", pre + "running_var"
 
-    def _wg_bufs(self, p: _Plan, ly: _Layer):
-        """(dwpack, workspace) pointers of a weight-gradient launch: deferred reduction -> (NULL, the layer's own slab workspace)"""
-        if p.wg_defer:
-            return None, L.ptr(ly.wgrad_ws)
-        return L.ptr(ly.dwpack), L.ptr(p.wgrad_ws)
-
-    def _wg_done(self, p: _Plan, ly: _Layer, gw: torch.Tensor):
-        """after a weight-gradient launch: remember the slabs it left for the batched reduction"""
-        if p.wg_defer:
-            p.wg_pending.append((ly.wgrad_ws.data_ptr(), 0, gw.data_ptr(), int(self.lib.sed_wgrad_last_slabs()), 9 * ly.cinp * ly.coutp,
-                                 ly.cout, ly.cin, ly.cinp, ly.coutp))
-
-    def _wg_flush(self, p: _Plan):
-        """one launch reduces every pending layer's slabs into the torch-layout gradients (same summation order as the inline reduction)"""
-        if not p.wg_pending:
-            return
-        key = tuple(p.wg_pending)
-        ent = p.wg_tables.get(key)
-        if ent is None:
-            rows, blk = [], 0
-            for r in p.wg_pending:
-                rows.append(list(r) + [blk])
-                blk += (r[4] + 63) // 64
-            ent = p.wg_tables[key] = (torch.tensor(rows, dtype=torch.int64).to(p.layers[0][0].z.device), len(rows), blk)
-        desc, n, blocks = ent
-        self._k("sed_wgrad_reduce_batch", self.lib.sed_wgrad_reduce_batch, L.ptr(desc), n, blocks, _stream())
-        p.wg_pending = []
-
     def _pack_weights(self, p: _Plan, P: Dict[str, torch.Tensor], training: bool) -> None:
         """Every conv layer's MFMA operand images in ONE launch: the forward operators and, for a train step, the
         data-gradient operators (the weights do not change between a step's forward and backward).  The descriptor table
@@ -664,7 +634,7 @@ class CnnEngine(OptimizerExtMixin):
                     gram, ng, cnt = p.c1_gram, p.c1_gram.shape[0], float(B * ly.H * ly.W)
                     if self.bn_sync is not None:
                         gram, ng, cnt = self._sync_row(p.c1_gram, ng, 54, p.sync_gram), 1, cnt * self.bn_sync.world
-                    if p.c1_tail and self.bn_sync is None:
+                    if self.bn_sync is None:      # (the backward's tail kernel reads the reduced Gram statistics: p.c1_gsum)
                         self._k("sed_bn_train_finalize_c1", self.lib.sed_bn_train_finalize_c1_g, L.ptr(gram), ng,
                                 cnt, L.ptr(w), L.ptr(P[gname]), L.ptr(P[bname]), L.ptr(rm), L.ptr(rv), BN_MOMENTUM, BN_EPS,
                                 L.ptr(ly.scale), L.ptr(ly.shift), L.ptr(ly.mean), L.ptr(ly.invstd), ly.cout, ly.coutp, L.ptr(p.c1_gsum), st)
@@ -871,9 +841,8 @@ class CnnEngine(OptimizerExtMixin):
                             L.ptr(ly.invstd), ly.cout, ly.coutp, st)
         # an eval forward keeps no pooled-tensor statistics (active-pixel counts): the per-pixel pass everywhere
         pool_fused = [False] * nb if eval_bwd else p.pool_fused
-        c1_mask = p.c1_mask if p.c1_mask is not None else getattr(p, "c1_mask_keep", None)
         try:
-            self._backward_blocks(p, P, G, src, ratio, debug, on_group_done, eval_bwd, pool_fused, c1_plain, c1_mask)
+            self._backward_blocks(p, P, G, src, ratio, debug, on_group_done, eval_bwd, pool_fused, c1_plain)
         finally:
             self._e_shift = 0
         if need_dx:
@@ -895,7 +864,7 @@ class CnnEngine(OptimizerExtMixin):
         self._k("sed_bn_bwd_finalize", self.lib.sed_bn_bwd_finalize, L.ptr(bpart), nparts, count, L.ptr(gamma), L.ptr(ly.mean),
                 L.ptr(ly.invstd), L.ptr(dg), L.ptr(db), L.ptr(ca), L.ptr(cb), L.ptr(cc), ly.cout, ly.coutp, _stream())
 
-    def _backward_blocks(self, p, P, G, src, ratio, debug, on_group_done, eval_bwd, pool_fused, c1_plain, c1_mask):
+    def _backward_blocks(self, p, P, G, src, ratio, debug, on_group_done, eval_bwd, pool_fused, c1_plain):
         lib, dt, st = self.lib, self.dt, _stream()
         B = p.B
         Cl = self.cfg[-1][0]
@@ -913,15 +882,6 @@ class CnnEngine(OptimizerExtMixin):
         dzA, dzB = p.scratch
         if any(pool_fused):
             p.pool_flag.zero_()
-        p.wg_pending = []
-
-        def group_done(key):
-            # data parallel: a group's gradients must be complete before its bucket's all-reduce is issued -- the pending reductions go out
-            # per block there (four launches instead of seven); single process: one launch at the end of the backward
-            if self.wg_flush_per_group:
-                self._wg_flush(p)
-            if on_group_done is not None:
-                on_group_done(key)
 
         def snap(name, buf, ly):
             if debug is not None:
@@ -965,105 +925,41 @@ class CnnEngine(OptimizerExtMixin):
             #      (and written to dzA for the data-gradient call); its input a1 = relu(bn1(z1)) is
             #      recomputed on load as well -----------------------------------------------------------
             w2n = f"conv_blocks.{bi}.conv2.weight"
-            c1m = p.c1_mode and bi == 0
-            if c1m and debug is not None:
-                raise RuntimeError("stage snapshots need conv1's output in memory: set SED_C1_MODE=0 (or use precision='fp32')")
+            if bi == 0 and p.c1_mode:
+                if debug is not None:
+                    raise RuntimeError("stage snapshots need conv1's output in memory: set SED_C1_MODE=0 (or use precision='fp32')")
+                self._backward_block0_c1(p, P, G, eval_bwd, c1_plain, gcount)
+                if on_group_done is not None:
+                    on_group_done("conv_blocks.0")
+                continue
             fused2 = p.bwd_fused[bi][1] and debug is None
             if fused2:
                 # weight gradient AND gated data gradient from one dz2 tile in LDS: dz2 is never written, z1 is read once
                 self._k("sed_conv3x3_bwd_fused", self.lib.sed_conv3x3_bwd_fused, dt, L.PRO_BNRELU, L.ptr(l1.z), L.ptr(l1.scale), L.ptr(l1.shift),
                         L.DZ_POOL, L.ptr(p.dy[bi]), L.ptr(l2.z), L.ptr(l2.scale), L.ptr(l2.shift), L.ptr(ca), L.ptr(cb), L.ptr(cc), pool,
                         L.ptr(l2.wpack_t), L.ptr(dzB), L.EPI_RELUBWD, L.ptr(l1.z), None, L.ptr(l1.scale), L.ptr(l1.shift), L.ptr(l1.mean),
-                        L.ptr(l1.invstd), L.ptr(p.bwd_part), lib.sed_conv_nparts(B, H, W), None, *self._wg_bufs(p, l2),
+                        L.ptr(l1.invstd), L.ptr(p.bwd_part), lib.sed_conv_nparts(B, H, W), None, L.ptr(l2.dwpack), L.ptr(p.wgrad_ws),
                         B, H, W, l2.cinp, l2.coutp, L.ptr(G[w2n]), l2.cout, l2.cin, st)
-            elif c1m and p.c1_bwd_fused and debug is None and not c1_plain:
-                # dW2 and the [A; sum g] partials of the gated data gradient from one dz2 tile in LDS: dz2 is never written
-                x1a = (L.ptr(p.x_ref), L.ptr(p.feat_mean), L.ptr(p.feat_std), L.ptr(P["conv_blocks.0.conv1.weight"]))
-                self._k("sed_conv3x3_bwd_fused_c1", self.lib.sed_conv3x3_bwd_fused_c1, dt, *x1a, L.ptr(l1.scale), L.ptr(l1.shift),
-                        L.ptr(p.dy[bi]), L.ptr(l2.z), L.ptr(l2.scale), L.ptr(l2.shift), L.ptr(ca), L.ptr(cb), L.ptr(cc), pool,
-                        L.ptr(l2.wpack_t), None if p.c1_gate_derived else L.ptr(p.c1_mask), L.ptr(p.c1_a10_part), *self._wg_bufs(p, l2),
-                        B, H, W, l2.coutp, L.ptr(G[w2n]), l2.cout, l2.cin, st)
-            elif c1m:
-                x1a = (L.ptr(p.x_ref), L.ptr(p.feat_mean), L.ptr(p.feat_std), L.ptr(P["conv_blocks.0.conv1.weight"]))
-                self._k("sed_conv3x3_wgrad_fused_c1", self.lib.sed_conv3x3_wgrad_fused_c1_u, dt, *x1a, L.ptr(l1.scale), L.ptr(l1.shift),
-                        L.ptr(p.dy[bi]), L.ptr(l2.z), L.ptr(l2.scale), L.ptr(l2.shift), L.ptr(ca), L.ptr(cb), L.ptr(cc), pool,
-                        L.ptr(dzA), *self._wg_bufs(p, l2), B, H, W, l2.coutp, L.ptr(G[w2n]), l2.cout, l2.cin, st)
             else:
                 self._k("sed_conv3x3_wgrad_fused", self.lib.sed_conv3x3_wgrad_fused_u, dtg, L.PRO_BNRELU, L.ptr(l1.z),
                         L.ptr(l1.scale), L.ptr(l1.shift), L.DZ_POOL, L.ptr(p.dy[bi]), L.ptr(l2.z), L.ptr(l2.scale),
-                        L.ptr(l2.shift), L.ptr(ca), L.ptr(cb), L.ptr(cc), pool, L.ptr(dzA), *self._wg_bufs(p, l2),
+                        L.ptr(l2.shift), L.ptr(ca), L.ptr(cb), L.ptr(cc), pool, L.ptr(dzA), L.ptr(l2.dwpack), L.ptr(p.wgrad_ws),
                         B, H, W, l2.cinp, l2.coutp, L.ptr(G[w2n]), l2.cout, l2.cin, st)
-            self._wg_done(p, l2, G[w2n])
             snap(f"dz2_{bi}", dzA, l2)
             # (the reduction kernel of the weight gradient stores G[w2n] in torch layout itself; the data-gradient operator
             #  wpack_t was packed with the forward operators, sed_pack_conv_weights_batch)
             # ---- conv2: data gradient with fused ReLU mask + BN1 backward statistics ---------------
             nparts = lib.sed_conv_nparts(B, H, W)
-            c1f = c1m and p.c1_dg_fused and debug is None and not c1_plain
-            if fused2 or (c1f and p.c1_bwd_fused):
-                pass
-            elif c1f:
-                # g is never written: the kernel gates conv2^T(dz2) with the ReLU mask in registers and reduces it to
-                # A = sum_px g (x) patch and sum g on the matrix pipe
-                self._k("sed_conv3x3_dgrad_c1_stats", self.lib.sed_conv3x3_dgrad_c1_stats, dt, L.ptr(dzA), L.ptr(l2.wpack_t),
-                        L.ptr(p.x_ref), L.ptr(p.feat_mean), L.ptr(p.feat_std), L.ptr(p.c1_mask), L.ptr(p.c1_a10_part), B, H, W, st)
-            elif c1m:
-                self._k("sed_conv3x3_dgrad_c1", self.lib.sed_conv3x3_dgrad_c1, dt, L.ptr(dzA), L.ptr(l2.wpack_t), L.ptr(dzB),
-                        L.ptr(c1_mask), L.ptr(p.bwd_part), B, H, W, l2.coutp, st)
-            else:
+            if not fused2:
                 self._k("sed_conv3x3_fwd", self.lib.sed_conv3x3_fwd, dtg, L.PRO_NONE, L.EPI_RELUBWD, L.ptr(dzA), None, None, L.ptr(l2.wpack_t),
                                             L.ptr(dzB), L.ptr(l1.z), L.ptr(l1.scale), L.ptr(l1.shift), L.ptr(l1.mean),
                                             L.ptr(l1.invstd), L.ptr(p.bwd_part), B, H, W, l2.coutp, l2.cinp, st)
             snap(f"g1_{bi}", dzB, l1)
             ca, cb, cc = l1.coef[0], l1.coef[1], l1.coef[2]
-            c1_A = p.c1_A
-            c1_tail = bool(c1f and p.c1_tail and sync is None and bi == 0)
-            if c1_tail:
-                # [A; sum g] partial rows -> BN1 backward coefficients -> dW1 in one launch, Gram statistics from the forward's finalize
-                self._tag = f"bwd b{bi}c1 {l1.cin}->{l1.cout} H{H} W{W}"
-                w1n_ = f"conv_blocks.{bi}.conv1.weight"
-                self._k("sed_c1_bwd_tail", self.lib.sed_c1_bwd_tail, L.ptr(p.c1_a10_part), p.c1_a10_part.shape[0], L.ptr(p.c1_gsum), gcount,
-                        L.ptr(P[w1n_]), L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]), L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb),
-                        L.ptr(cc), L.ptr(p.c1_a10), L.ptr(l1.dwpack), l1.cout, l1.coutp, L.ptr(G[w1n_]), st)
-            elif c1f:
-                self._tag = f"bwd b{bi}c1 {l1.cin}->{l1.cout} H{H} W{W}"
-                self._k("sed_sum_partials", self.lib.sed_sum_partials, L.ptr(p.c1_a10_part), p.c1_a10_part.shape[0], 10 * 32,
-                        L.ptr(p.c1_a10), st)
-                c1_A = p.c1_a10           # rows 0..8 = A, row 9 = sum g (read as a one-row statistics partial)
-                a10 = p.c1_a10
-                if sync is not None:      # BN1's backward statistics over the global batch; dW1's combine keeps the LOCAL A / Gram
-                    p.sync_a10.copy_(p.c1_a10)
-                    sync.all_reduce(p.sync_a10)
-                    a10 = p.sync_a10
-                self._k("sed_bn_bwd_finalize_c1", self.lib.sed_bn_bwd_finalize_c1, L.ptr(a10[9]), 1, gcount, L.ptr(a10),
-                        L.ptr(P["conv_blocks.0.conv1.weight"]), L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]),
-                        L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc), l1.cout, l1.coutp, st)
-            elif c1m:
-                # BN1 backward needs sum g*z1 = w1 . A with A = the plain first-layer weight gradient of g1: that
-                # kernel runs first, the coefficients come from sed_bn_bwd_finalize_c1
-                if sync is not None:
-                    raise RuntimeError("SyncBN needs the fused block-0 data gradient (SED_DGRAD_FUSED=1) or SED_C1_MODE=0")
-                self._tag = f"bwd b{bi}c1 {l1.cin}->{l1.cout} H{H} W{W}"
-                self._k("sed_conv3x3_c1_wgrad", self.lib.sed_conv3x3_c1_wgrad, dt, L.ptr(p.x_ref), L.ptr(p.feat_mean),
-                        L.ptr(p.feat_std), L.ptr(dzB), L.ptr(p.c1_ws), B, H, W, l1.coutp, st)
-                self._k("sed_sum_partials", self.lib.sed_sum_partials, L.ptr(p.c1_ws), p.c1_ws.shape[0], 9 * l1.coutp,
-                        L.ptr(p.c1_A), st)
-                if eval_bwd:
-                    self._k("sed_bn_eval_bwd_finalize_c1", self.lib.sed_bn_eval_bwd_finalize_c1, L.ptr(p.bwd_part), nparts, L.ptr(p.c1_A),
-                            L.ptr(P["conv_blocks.0.conv1.weight"]), L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]),
-                            L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc), l1.cout, l1.coutp, st)
-                    # (dW1 = ca*A: the Gram statistics enter with cb = cc = 0, but an eval forward did not compute them)
-                    self._k("sed_conv3x3_c1_gram", self.lib.sed_conv3x3_c1_gram, L.ptr(p.x_ref), L.ptr(p.feat_mean),
-                            L.ptr(p.feat_std), L.ptr(p.c1_gram), B, H, W, st)
-                else:
-                    self._k("sed_bn_bwd_finalize_c1", self.lib.sed_bn_bwd_finalize_c1, L.ptr(p.bwd_part), nparts, count, L.ptr(p.c1_A),
-                            L.ptr(P["conv_blocks.0.conv1.weight"]), L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]),
-                            L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc), l1.cout, l1.coutp, st)
-            else:
-                bpart = p.bwd_part
-                if sync is not None:
-                    bpart, nparts = self._sync_row(p.bwd_part, nparts, 2 * l1.coutp, p.sync_row), 1
-                self._bn_bwd_fin(eval_bwd, bpart, nparts, gcount, P[g1n], l1, G[g1n], G[b1n])
+            bpart = p.bwd_part
+            if sync is not None:
+                bpart, nparts = self._sync_row(p.bwd_part, nparts, 2 * l1.coutp, p.sync_row), 1
+            self._bn_bwd_fin(eval_bwd, bpart, nparts, gcount, P[g1n], l1, G[g1n], G[b1n])
             if sync is not None:
                 G[g1n].mul_(1.0 / sync.world)
                 G[b1n].mul_(1.0 / sync.world)
@@ -1081,17 +977,15 @@ class CnnEngine(OptimizerExtMixin):
                     snap(f"dz1_{bi}", tmp, l1)
                 # dW1 = ca*A + cb*(w1.G) + cc*sx: A = plain weight gradient of g1, G / sx = Gram statistics of the
                 # input patches -- z1 is not read (csrc/sed_c1.hip: conv_c1_gram_kernel)
-                if not c1m:          # (C1 mode: Gram statistics from the forward pass, A from the BN1 step above)
-                    self._k("sed_conv3x3_c1_gram", self.lib.sed_conv3x3_c1_gram, L.ptr(p.x_ref), L.ptr(p.feat_mean),
-                            L.ptr(p.feat_std), L.ptr(p.c1_gram), B, H, W, st)
-                    self._k("sed_conv3x3_c1_wgrad", self.lib.sed_conv3x3_c1_wgrad, dt, L.ptr(p.x_ref), L.ptr(p.feat_mean),
-                            L.ptr(p.feat_std), L.ptr(dzB), L.ptr(p.c1_ws), B, H, W, l1.coutp, st)
-                    self._k("sed_sum_partials", self.lib.sed_sum_partials, L.ptr(p.c1_ws), p.c1_ws.shape[0], 9 * l1.coutp,
-                            L.ptr(p.c1_A), st)
-                if not c1_tail:      # (the tail kernel above has stored dW1 already)
-                    self._k("sed_conv3x3_c1_wgrad_combine", self.lib.sed_conv3x3_c1_wgrad_combine_u, L.ptr(c1_A), L.ptr(p.c1_gram),
-                            p.c1_gram.shape[0], L.ptr(P[w1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc), L.ptr(l1.dwpack), l1.cout,
-                            l1.coutp, L.ptr(G[w1n]), st)
+                self._k("sed_conv3x3_c1_gram", self.lib.sed_conv3x3_c1_gram, L.ptr(p.x_ref), L.ptr(p.feat_mean),
+                        L.ptr(p.feat_std), L.ptr(p.c1_gram), B, H, W, st)
+                self._k("sed_conv3x3_c1_wgrad", self.lib.sed_conv3x3_c1_wgrad, dt, L.ptr(p.x_ref), L.ptr(p.feat_mean),
+                        L.ptr(p.feat_std), L.ptr(dzB), L.ptr(p.c1_ws), B, H, W, l1.coutp, st)
+                self._k("sed_sum_partials", self.lib.sed_sum_partials, L.ptr(p.c1_ws), p.c1_ws.shape[0], 9 * l1.coutp,
+                        L.ptr(p.c1_A), st)
+                self._k("sed_conv3x3_c1_wgrad_combine", self.lib.sed_conv3x3_c1_wgrad_combine_u, L.ptr(p.c1_A), L.ptr(p.c1_gram),
+                        p.c1_gram.shape[0], L.ptr(P[w1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc), L.ptr(l1.dwpack), l1.cout,
+                        l1.coutp, L.ptr(G[w1n]), st)
             else:
                 # conv1 weight gradient with dz1 = BN1 backward produced on load from (g1, z1); dz1 lands
                 # in dzA (dz2 is dead by now) for the data-gradient call below
@@ -1105,16 +999,15 @@ class CnnEngine(OptimizerExtMixin):
                             L.EPI_POOLSTATS if pst else L.EPI_STORE, L.ptr(p.y[bi - 1]) if pst else None,
                             L.ptr(p.pool_cnt[bi - 1]) if pst else None, L.ptr(q2.scale) if pst else None, L.ptr(q2.shift) if pst else None,
                             L.ptr(q2.mean) if pst else None, L.ptr(q2.invstd) if pst else None, L.ptr(p.bwd_part) if pst else None,
-                            p.pool_nparts[bi - 1] if pst else 0, L.ptr(p.pool_flag[bi - 1:]) if pst else None, *self._wg_bufs(p, l1),
+                            p.pool_nparts[bi - 1] if pst else 0, L.ptr(p.pool_flag[bi - 1:]) if pst else None, L.ptr(l1.dwpack), L.ptr(p.wgrad_ws),
                             B, H, W, l1.cinp, l1.coutp, L.ptr(G[w1n]), l1.cout, l1.cin, st)
-                    self._wg_done(p, l1, G[w1n])
-                    group_done(f"conv_blocks.{bi}")
+                    if on_group_done is not None:
+                        on_group_done(f"conv_blocks.{bi}")
                     continue
                 self._k("sed_conv3x3_wgrad_fused", self.lib.sed_conv3x3_wgrad_fused_u, dtg, L.PRO_NONE, L.ptr(xin),
                         None, None, L.DZ_BN, L.ptr(dzB), L.ptr(l1.z), None, None, L.ptr(ca), L.ptr(cb), L.ptr(cc), 1,
-                        L.ptr(dzA), *self._wg_bufs(p, l1), B, H, W, l1.cinp, l1.coutp, L.ptr(G[w1n]), l1.cout,
+                        L.ptr(dzA), L.ptr(l1.dwpack), L.ptr(p.wgrad_ws), B, H, W, l1.cinp, l1.coutp, L.ptr(G[w1n]), l1.cout,
                         l1.cin, st)
-                self._wg_done(p, l1, G[w1n])
                 snap(f"dz1_{bi}", dzA, l1)
                 if bi > 0 and pool_fused[bi - 1]:
                     q2 = p.layers[bi - 1][1]      # the block whose pooled output this gradient belongs to
@@ -1128,9 +1021,86 @@ class CnnEngine(OptimizerExtMixin):
                             l1.cinp, st)
                 if debug is not None and bi > 0:
                     debug[f"dy{bi - 1}"] = p.dy[bi - 1].float().clone()
-            group_done(f"conv_blocks.{bi}")
-        self._wg_flush(p)
+            if on_group_done is not None:
+                on_group_done(f"conv_blocks.{bi}")
         self._tag = ""
+
+    def _backward_block0_c1(self, p, P, G, eval_bwd, plain, gcount):
+        """Block 0's backward in C1 mode, from the pooled gradient plan.dy[0] (BN2's coefficients are in place) to dW2, BN1's
+        gradients and dW1.  One section per route (block0_route); `plain`: this backward needs g1 in memory (need_dx, eval mode)."""
+        lib, dt, st, sync = self.lib, self.dt, _stream(), self.bn_sync
+        l1, l2 = p.layers[0]
+        B, H, W, pool = p.B, l2.H, l2.W, self.cfg[0][1]
+        dzA, dzB = p.scratch
+        w1n, w2n = "conv_blocks.0.conv1.weight", "conv_blocks.0.conv2.weight"
+        g1n, b1n, _, _ = self._bn_names(0, 0)
+        ca, cb, cc = l1.coef[0], l1.coef[1], l1.coef[2]
+        tag1 = f"bwd b0c1 {l1.cin}->{l1.cout} H{H} W{W}"
+        # conv2's weight-gradient launches rebuild a1 = relu(bn1(conv1(x))) from the input; dz2 = BN2 / ReLU / pool backward on load
+        conv2 = (dt, L.ptr(p.x_ref), L.ptr(p.feat_mean), L.ptr(p.feat_std), L.ptr(P[w1n]), L.ptr(l1.scale), L.ptr(l1.shift),
+                 L.ptr(p.dy[0]), L.ptr(l2.z), L.ptr(l2.scale), L.ptr(l2.shift), L.ptr(l2.coef[0]), L.ptr(l2.coef[1]), L.ptr(l2.coef[2]), pool)
+        dw2 = (L.ptr(l2.dwpack), L.ptr(p.wgrad_ws), B, H, W, l2.coutp, L.ptr(G[w2n]), l2.cout, l2.cin, st)
+
+        if plain:
+            # ---- c1_plain: g1 is written (dzB; backward() turns it into the input gradient), with the mask of the kept forward --------
+            mask = p.c1_mask if p.c1_mask is not None else p.c1_mask_keep
+            self._k("sed_conv3x3_wgrad_fused_c1", lib.sed_conv3x3_wgrad_fused_c1_u, *conv2, L.ptr(dzA), *dw2)
+            self._k("sed_conv3x3_dgrad_c1", lib.sed_conv3x3_dgrad_c1, dt, L.ptr(dzA), L.ptr(l2.wpack_t), L.ptr(dzB),
+                    L.ptr(mask), L.ptr(p.bwd_part), B, H, W, l2.coutp, st)
+            # BN1 backward needs sum g*z1 = w1 . A with A = the plain first-layer weight gradient of g1: that kernel runs first
+            self._tag = tag1
+            self._k("sed_conv3x3_c1_wgrad", lib.sed_conv3x3_c1_wgrad, dt, L.ptr(p.x_ref), L.ptr(p.feat_mean),
+                    L.ptr(p.feat_std), L.ptr(dzB), L.ptr(p.c1_ws), B, H, W, l1.coutp, st)
+            self._k("sed_sum_partials", lib.sed_sum_partials, L.ptr(p.c1_ws), p.c1_ws.shape[0], 9 * l1.coutp, L.ptr(p.c1_A), st)
+            fin = (L.ptr(p.c1_A), L.ptr(P[w1n]), L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]),
+                   L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc), l1.cout, l1.coutp, st)
+            nparts = lib.sed_conv_nparts(B, H, W)
+            if eval_bwd:
+                self._k("sed_bn_eval_bwd_finalize_c1", lib.sed_bn_eval_bwd_finalize_c1, L.ptr(p.bwd_part), nparts, *fin)
+                # (dW1 = ca*A: the Gram statistics enter with cb = cc = 0, but an eval forward did not compute them)
+                self._k("sed_conv3x3_c1_gram", lib.sed_conv3x3_c1_gram, L.ptr(p.x_ref), L.ptr(p.feat_mean),
+                        L.ptr(p.feat_std), L.ptr(p.c1_gram), B, H, W, st)
+            else:
+                self._k("sed_bn_bwd_finalize_c1", lib.sed_bn_bwd_finalize_c1, L.ptr(p.bwd_part), nparts, float(B * H * W), *fin)
+            self._c1_combine(p, P, G, p.c1_A)
+            return
+
+        if p.c1_route == "c1_fused":
+            # ---- c1_fused: dW2 and the [A; sum g] partials of the gated data gradient from one dz2 tile in LDS; dz2 and g are never
+            #      written, the ReLU gate is derived in the kernel (mask NULL) ------------------------------------------------------
+            self._k("sed_conv3x3_bwd_fused_c1", lib.sed_conv3x3_bwd_fused_c1, *conv2, L.ptr(l2.wpack_t), None, L.ptr(p.c1_a10_part), *dw2)
+        else:
+            # ---- c1_stats: dz2 through memory (dzA); g is never written: the data gradient gates conv2^T(dz2) with the forward's
+            #      mask in registers and reduces it to A = sum_px g (x) patch and sum g on the matrix pipe -----------------------------
+            self._k("sed_conv3x3_wgrad_fused_c1", lib.sed_conv3x3_wgrad_fused_c1_u, *conv2, L.ptr(dzA), *dw2)
+            self._k("sed_conv3x3_dgrad_c1_stats", lib.sed_conv3x3_dgrad_c1_stats, dt, L.ptr(dzA), L.ptr(l2.wpack_t),
+                    L.ptr(p.x_ref), L.ptr(p.feat_mean), L.ptr(p.feat_std), L.ptr(p.c1_mask), L.ptr(p.c1_a10_part), B, H, W, st)
+        # ---- the tail of both: [A; sum g] partial rows -> BN1 backward coefficients -> dW1 --------------------------------------------
+        self._tag = tag1
+        if sync is None:
+            # one launch, with the Gram statistics the forward's finalize reduced
+            self._k("sed_c1_bwd_tail", lib.sed_c1_bwd_tail, L.ptr(p.c1_a10_part), p.c1_a10_part.shape[0], L.ptr(p.c1_gsum), gcount,
+                    L.ptr(P[w1n]), L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]), L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb),
+                    L.ptr(cc), L.ptr(p.c1_a10), L.ptr(l1.dwpack), l1.cout, l1.coutp, L.ptr(G[w1n]), st)
+            return
+        # SyncBN: BN1's backward statistics over the global batch; dW1's combine keeps the LOCAL A / Gram
+        self._k("sed_sum_partials", lib.sed_sum_partials, L.ptr(p.c1_a10_part), p.c1_a10_part.shape[0], 10 * 32, L.ptr(p.c1_a10), st)
+        p.sync_a10.copy_(p.c1_a10)
+        sync.all_reduce(p.sync_a10)
+        a10 = p.sync_a10          # rows 0..8 = A, row 9 = sum g (read as a one-row statistics partial)
+        self._k("sed_bn_bwd_finalize_c1", lib.sed_bn_bwd_finalize_c1, L.ptr(a10[9]), 1, gcount, L.ptr(a10), L.ptr(P[w1n]),
+                L.ptr(P[g1n]), L.ptr(l1.mean), L.ptr(l1.invstd), L.ptr(G[g1n]), L.ptr(G[b1n]), L.ptr(ca), L.ptr(cb), L.ptr(cc),
+                l1.cout, l1.coutp, st)
+        G[g1n].mul_(1.0 / sync.world)
+        G[b1n].mul_(1.0 / sync.world)
+        self._c1_combine(p, P, G, p.c1_a10)
+
+    def _c1_combine(self, p, P, G, a_sum):
+        """dW1 = ca*A + cb*(w1.G) + cc*sx: A = the weight gradient of g1 (rows 0..8 of a_sum), G / sx = Gram statistics of the input patches"""
+        l1, w1n = p.layers[0][0], "conv_blocks.0.conv1.weight"
+        self._k("sed_conv3x3_c1_wgrad_combine", self.lib.sed_conv3x3_c1_wgrad_combine_u, L.ptr(a_sum), L.ptr(p.c1_gram),
+                p.c1_gram.shape[0], L.ptr(P[w1n]), L.ptr(l1.coef[0]), L.ptr(l1.coef[1]), L.ptr(l1.coef[2]), L.ptr(l1.dwpack), l1.cout,
+                l1.coutp, L.ptr(G[w1n]), _stream())
 
     # ------------------------------------------------------------------------------------------
     def adam_step_dev(self, flat_p, flat_g, flat_m, flat_v, flat_vmax, hyper, step_dev, grad_scale: float, lr_decay: float,

@@ -451,8 +451,6 @@ class FusedTrainer:
         if self.teacher is not None:
             self.teacher_flat = FlatParams(self.teacher, grads=False)
         self.sync_bn = bool(sync_bn) and self.reducer.enabled
-        if self.reducer.enabled and hasattr(self.engine, "wg_flush_per_group"):
-            self.engine.wg_flush_per_group = True      # weight gradients complete before their bucket's all-reduce goes out
         if self.reducer.enabled:
             # replicas start from rank 0's parameters and BatchNorm buffers (the DDP constructor's broadcast): identical
             # seeds are not something to rely on

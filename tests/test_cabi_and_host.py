@@ -65,6 +65,19 @@ def test_argument_validation_without_gpu(sed):
     assert rc != 0 and b"1-based" in lib.sed_last_error()
 
 
+def test_block0_fused_backward_refuses_a_mask(sed):
+    """sed_conv3x3_bwd_fused_c1 has one kernel form, which derives conv1's ReLU gate from the activation tile it rebuilds: a non-NULL
+    relu_mask is refused on the host, before any launch (the pointers below are never dereferenced)."""
+    lib = sed._lib.lib()
+    q = 4096
+    rc = lib.sed_conv3x3_bwd_fused_c1(1, q, None, None, q, q, q, q, q, q, q, q, q, q, 2, q, q, q, q, q, 2, 12, 64, 32, q, 32, 32, None)
+    assert rc != 0
+    msg = lib.sed_last_error()
+    assert b"sed_conv3x3_bwd_fused_c1" in msg and b"derived" in msg and b"relu_mask" in msg, msg
+    with pytest.raises(RuntimeError, match="derived"):
+        sed._lib.check(rc, "sed_conv3x3_bwd_fused_c1")
+
+
 def test_state_dict_contract_and_seeded_init(sed):
     g = load_golden("g2_train_steps.npz")
     torch.manual_seed(0)

@@ -109,7 +109,7 @@ def test_config2_bf16_T6001_train_step_vs_oracle(sed):
     tr = sed.FusedTrainer(model, lr=1e-3, recall_factor=5.0)
     loss = tr.forward_backward(x.cuda(), y.cuda())
     plan = next(iter(model.engine._plans.values()))
-    assert plan.c1_mode and plan.c1_dg_fused, "the bench's block-0 dataflow (C1 mode, fused data gradient) must be the one tested"
+    assert plan.c1_route == "c1_fused", "the bench's block-0 dataflow (C1 mode, fused backward launch) must be the one tested"
     logits = model.engine.interpolate(plan)
     assert logits.shape == logits_o.shape == (B, 6000, 1)
     assert rel_l2(logits, logits_o) < 3e-2

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Interleaved A/B of the bench step between two values of ONE environment knob, in alternating fresh processes on one box:
-#   tools/ab_env.sh SED_WGRAD_REDUCE inline batch [rounds] [extra bench.py args...]
+#   tools/ab_env.sh SED_POOL_STATS p z [rounds] [extra bench.py args...]
 # prints ms/step of every run and the medians (the boxes of the pool differ by 5-15 %: only same-box alternations compare).
 var=$1; a=$2; b=$3; rounds=${4:-3}; shift 4 2>/dev/null
 out=$(mktemp -d)

@@ -43,7 +43,7 @@ def unfused():
 
 def fused():
     L.check(lib.sed_conv3x3_bwd_fused_c1(1, P(x1), P(fmean), P(fstd), P(w1), P(sc1), P(sh1), P(dy), P(z2), P(sc2), P(sh2), P(ca), P(cb), P(cc), 2,
-                                         P(wt), P(mask), P(part), P(dwp), P(ws), B, H, W, C, P(dw), C, C, st))
+                                         P(wt), None, P(part), P(dwp), P(ws), B, H, W, C, P(dw), C, C, st))      # (the gate is derived: no mask)
 
 
 def timeit(fn, iters=10):
