@@ -987,6 +987,39 @@ int sed_m5_head_fwd(int dtype, const void* feat, const float* fc_w, const float*
 int sed_m5_head_bwd(int dtype, const float* dpre, const float* m, const float* fc_w, float* dfc_w,
                     float* dfc_b, void* dfeat, int B, int H, int C, int Cp, int K, void* stream);
 
+/* ---- PCEN front-end layer: csrc/sed_pcen.hip --------------------------------------------------
+ * Per-channel energy normalisation (Wang et al., ICASSP 2017) with trainable per-bin parameters, forward
+ * and backward.  x, y, gy, dx fp32 [B][T][F] (the models' (B, 1, T, F) layout), F in 1..256.
+ * theta fp32 [4][F] = (a, d, rho, sigma):  alpha = e^a, delta = e^d, r = e^rho, s = 1/(1 + e^-sigma).
+ * eps > 0 and gain > 0 are double constants.
+ *   E_t = gain 10^((x_t std_f + mean_f)/10)     kind 0: dB log-mel; mean / std fp32 [F], both NULL = 0 / 1
+ *   E_t = gain max(x_t, 0)                      kind 1: linear mel power (mean / std must be NULL)
+ *   M_0 = E_0;  M_t = (1 - s) M_{t-1} + s E_t
+ *   u_t = eps + M_t;  G_t = E_t u_t^-alpha;  y_t = (G_t + delta)^r - delta^r
+ * Backward, g = dL/dy:
+ *   q_t = g_t r (G_t + delta)^(r-1);  direct_t = q_t u_t^-alpha;  m_t = -q_t alpha G_t / u_t
+ *   lambda_t = m_t + (1 - s) lambda_{t+1}, lambda_T = 0
+ *   dE_t = direct_t + s lambda_t (t >= 1);  dE_0 = direct_0 + lambda_0
+ *   dx_t = dE_t E_t (ln 10 / 10) std_f (kind 0);  gain dE_t [x_t > 0] (kind 1: exactly 0 where x_t <= 0)
+ *   dtheta[0] = alpha sum -q_t G_t ln u_t
+ *   dtheta[1] = delta sum g_t r ((G_t + delta)^(r-1) - delta^(r-1))
+ *   dtheta[2] = r sum g_t ((G_t + delta)^r ln(G_t + delta) - delta^r ln delta)
+ *   dtheta[3] = s (1 - s) sum_{t >= 1} lambda_t (E_t - M_{t-1})            (sums over b and t)
+ * All arithmetic is double (a power p^e is exp(e ln p)), every output is rounded once to fp32, M is not
+ * stored.  Time is cut into chunks of sed_pcen_chunk() frames whose carries go through the workspace
+ * between launches, every sum is taken in a fixed order without atomics: the same bits on every run.
+ * sed_pcen_bwd depends on its arguments only (it rebuilds M from x).  dx NULL: no input gradient; dtheta
+ * NULL: a fixed layer; either leaves the other output's bits as they are with both; not both NULL.
+ * y and dx must not overlap x (dx nor gy).  workspace: sed_pcen_ws_bytes() bytes, 8-byte aligned.
+ * Launches: forward 2, backward 3 and one more with dtheta.                                        */
+int sed_pcen_chunk(void);
+size_t sed_pcen_ws_bytes(int B, int T, int F);
+int sed_pcen_fwd(const float* x, const float* mean, const float* std, const float* theta, int kind, double eps,
+                 double gain, float* y, void* workspace, int B, int T, int F, void* stream);
+int sed_pcen_bwd(const float* x, const float* mean, const float* std, const float* theta, int kind, double eps,
+                 double gain, const float* gy, float* dx, float* dtheta, void* workspace, int B, int T, int F,
+                 void* stream);
+
 /* ---- utilities -----------------------------------------------------------------------------*/
 /* out[i] = sum_{s<nparts} partial[s][i], i < n (fixed order: deterministic)                     */
 int sed_sum_partials(const float* partial, int nparts, size_t n, float* out, void* stream);

@@ -157,6 +157,10 @@ PROTOTYPES = {
     "sed_rank_curve": (_I, [_P, _I, _Z, _Z, _P, _P, _P, _P, _P]),
     "sed_psds_max_frames": (_I, [_I, _I]),
     "sed_psds_counts": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "sed_pcen_chunk": (_I, []),
+    "sed_pcen_ws_bytes": (_Z, [_I, _I, _I]),
+    "sed_pcen_fwd": (_I, [_P, _P, _P, _P, _I, _D, _D, _P, _P, _I, _I, _I, _P]),
+    "sed_pcen_bwd": (_I, [_P, _P, _P, _P, _I, _D, _D, _P, _P, _P, _P, _I, _I, _I, _P]),
     "sed_m5_conv1_len": (_I, [_I]),
     "sed_m5_conv1_nparts": (_I, [_I, _I]),
     "sed_m5_conv1_fwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _P]),

@@ -7,7 +7,8 @@ in eval mode -> per-frame probabilities, threshold decisions and onset times.
 Writes <outputs_dir>/<name>.npz (probabilities, decisions, onset_frames, onset_seconds; with --median_window / --low_threshold / --max_gap /
 --min_event also events = (class, onset_s, offset_s) rows decoded on the MI355X (utils/event_utils.py) and event_frames, the same in frames;
 with --clip_pooling also clip_probs (classes,), the frame probabilities pooled into one clip probability per class; with --saliency also
-saliency (T, mel_bins, classes) = d(sum_t p_k(t)) / d(model input), the eval-mode input gradient) and prints the onsets.  The features are z-scored with --mean_std (the pickle the preprocessing wrote) when given:
+saliency (T, mel_bins, classes) = d(sum_t p_k(t)) / d(model input), the eval-mode input gradient; for a checkpoint of a --pcen
+training the layer is rebuilt from its 'frontend.*' keys and the map is with respect to the log-mel input, through the layer) and prints the onsets.  The features are z-scored with --mean_std (the pickle the preprocessing wrote) when given:
 the reference's infer.py skips the normalisation the model was trained with."""
 from __future__ import annotations
 
@@ -121,15 +122,21 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     if not torch.cuda.is_available():
         raise RuntimeError("no MI355X visible: this build has no CPU inference path")
     dev = torch.device(device)
-    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel).to(dev)
-    model.set_precision(precision)
     checkpoint = torch.load(ckpt, map_location=dev)
     if teacher:
         if "teacher" not in checkpoint:
             raise ValueError(f"{ckpt} holds no 'teacher' entry: it was not written by a mean-teacher training")
-        model.load_state_dict(checkpoint["teacher"])
+        weights = checkpoint["teacher"]
     else:
-        model.load_state_dict(checkpoint["model"] if "model" in checkpoint else checkpoint)
+        weights = checkpoint["model"] if "model" in checkpoint else checkpoint
+    frontend = None
+    if "frontend.log_alpha" in weights:       # a --pcen training: the layer is rebuilt from the checkpoint's own keys
+        from .models.frontend_layers import PCEN
+        frontend = PCEN.from_state_dict(weights, prefix="frontend.")
+    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel,
+                           frontend=frontend).to(dev)
+    model.set_precision(precision)
+    model.load_state_dict(weights)
     model.eval()
     print("Preprocessing audio file..")
     if host_resample:

@@ -155,13 +155,56 @@ def build_psds_parser():
     return p
 
 
+def build_pcen_parser():
+    """The PCEN front-end layer (this build only): models/frontend_layers.py, csrc/sed_pcen.hip."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--pcen", action="store_true", default=False,
+                   help="put a trainable PCEN layer (per-channel energy normalisation) between the log-mel features and the CNN; it "
+                        "un-normalises the dataset's z-score with the mean / std file values (--train_features Spectogram, single "
+                        "process, not with --mean_teacher)")
+    p.add_argument("--pcen_fixed", action="store_true", default=False,
+                   help="the PCEN layer with fixed parameters (implies --pcen): nothing of it is trained")
+    p.add_argument("--pcen_alpha", type=float, default=0.98, help="--pcen: initial gain-control exponent alpha (> 0)")
+    p.add_argument("--pcen_delta", type=float, default=2.0, help="--pcen: initial bias delta (> 0)")
+    p.add_argument("--pcen_r", type=float, default=0.5, help="--pcen: initial root-compression exponent r (> 0)")
+    p.add_argument("--pcen_s", type=float, default=0.025, help="--pcen: initial smoothing coefficient s, in (0, 1)")
+    p.add_argument("--pcen_eps", type=float, default=1e-6, help="--pcen: the constant added to the smoother (> 0)")
+    p.add_argument("--pcen_gain", type=float, default=1.0, help="--pcen: factor on the mel power before the layer (> 0)")
+    return p
+
+
 def build_full_parser():
     """What main() parses: build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser(),
-    build_semi_parser(), build_ranking_parser() and build_psds_parser() together."""
+    build_semi_parser(), build_ranking_parser(), build_psds_parser() and build_pcen_parser() together."""
     return argparse.ArgumentParser(description="SED training on MI355X",
                                    parents=[build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser(),
-                                            build_semi_parser(), build_ranking_parser(), build_psds_parser()],
+                                            build_semi_parser(), build_ranking_parser(), build_psds_parser(), build_pcen_parser()],
                                    conflict_handler="resolve")
+
+
+def pcen_options(args):
+    """None without --pcen / --pcen_fixed, else the PCEN keyword arguments of the command line (a Namespace built by hand may lack
+    any of them); mel_bins, mean and std are the dataset's."""
+    if not (getattr(args, "pcen", False) or getattr(args, "pcen_fixed", False)):
+        return None
+    return {"alpha": float(getattr(args, "pcen_alpha", 0.98)), "delta": float(getattr(args, "pcen_delta", 2.0)),
+            "r": float(getattr(args, "pcen_r", 0.5)), "s": float(getattr(args, "pcen_s", 0.025)),
+            "eps": float(getattr(args, "pcen_eps", 1e-6)), "gain": float(getattr(args, "pcen_gain", 1.0)),
+            "trainable": not getattr(args, "pcen_fixed", False)}
+
+
+def build_pcen(args, mel_bins, mean=None, std=None):
+    """The layer of --pcen for a dataset whose features were z-scored with mean / std (scalars or per-bin; None: plain dB), or
+    None without the option."""
+    opts = pcen_options(args)
+    if opts is None:
+        return None
+    import numpy as np
+    from .models.frontend_layers import PCEN
+    if mean is not None:
+        mean = np.broadcast_to(np.asarray(mean, dtype=np.float32).reshape(-1), (mel_bins,)).copy()
+        std = np.broadcast_to(np.asarray(std, dtype=np.float32).reshape(-1), (mel_bins,)).copy()
+    return PCEN(mel_bins, input="db", mean=mean, std=std, **opts)
 
 
 def parse_label_kinds(text):
@@ -294,7 +337,8 @@ def get_spectogram_dataset_model_and_criterion(args, device):
                                     val_descriptor=_val_descriptor(args.val_descriptor),
                                     preprocessed_mode=args.preprocess_mode, cfg=cfg, device=device,
                                     spec_augment=spec_augment_config(args))
-    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel)
+    frontend = build_pcen(args, n_mel, getattr(dataset, "mean", None), getattr(dataset, "std", None))
+    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel, frontend=frontend)
     model.set_precision(args.precision)
     if args.ckpt != "":
         checkpoint = torch.load(args.ckpt, map_location=device)
@@ -383,6 +427,20 @@ def validate_args(args):
     if semi:
         from .train import check_semi_options
         check_semi_options(**{k: v for k, v in semi.items() if k != "eval_teacher"})
+    pcen = pcen_options(args)
+    if pcen is not None:
+        if args.train_features.lower() == "waveform":
+            raise ValueError("--pcen works on log-mel features: it needs --train_features Spectogram (the M5 model reads the raw "
+                             "waveform)")
+        if semi:
+            raise ValueError("--pcen does not go with --mean_teacher")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError("--pcen is the single-process path (its backward takes the input gradient)")
+        for name in ("alpha", "delta", "r", "eps", "gain"):
+            if not (0.0 < pcen[name] < float("inf")):
+                raise ValueError(f"--pcen_{name} must be finite and > 0, {pcen[name]} given")
+        if not (0.0 < pcen["s"] < 1.0):
+            raise ValueError(f"--pcen_s must lie in (0, 1), {pcen['s']} given")
     if getattr(args, "eval_clip_pooling", None) is not None:
         if not getattr(args, "eval_ranking", False):
             raise ValueError("--eval_clip_pooling needs --eval_ranking")

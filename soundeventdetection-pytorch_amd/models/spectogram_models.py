@@ -196,7 +196,7 @@ class _ModelFunction(torch.autograd.Function):
             raise RuntimeError("the activations of this forward were overwritten by a later forward of the "
                                "same shape; call backward() before the next forward()")
         P = model._tensor_dict()
-        names = [n for n, _ in model.named_parameters()]
+        names = [n for n, _ in model._core_named_parameters()]
         G = {n: torch.empty_like(P[n]) for n in names}
         need_dx = bool(ctx.needs_input_grad[2])
         model.engine.backward(ctx.plan, P, G, dlogits=dlogits.contiguous().float(), need_dx=need_dx)
@@ -204,12 +204,16 @@ class _ModelFunction(torch.autograd.Function):
 
 
 class Cnn_AvgPooling(nn.Module):
-    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, mel_bins=None):
+    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, mel_bins=None, frontend=None):
         '''mel_bins: the declared input width (mel-bin count).  None: the specialised widths only (8 / 16 / 32 / 64 at every
         block), as before.  An integer F in [1, 256]: inputs of width F only; blocks at other widths run the width-general
-        kernels.  The parameters do not depend on it: a checkpoint loads into a model of any declared width.'''
+        kernels.  The parameters do not depend on it: a checkpoint loads into a model of any declared width.
+        frontend: None, or a models.frontend_layers.PCEN applied to the input before the first block (submodule `frontend`,
+        first in parameter order; its width must be the model's, MEL_BINS when mel_bins is None).  None adds no key to the
+        state_dict and launches nothing new.'''
         super().__init__()
         self.mel_bins = CnnEngine.check_mel_bins(mel_bins)
+        self.frontend = self._check_frontend(frontend, self.mel_bins)      # before conv_blocks: first in named_parameters()
         self.model_config = model_config
         self.classes_num = classes_num
         self.precision = precision or DEFAULT_PRECISION
@@ -224,6 +228,22 @@ class Cnn_AvgPooling(nn.Module):
         self.engine = self._make_engine(self.precision)
         self._fwd_serial = 0
         self._nbt_pending = 0     # training forwards not yet added to the num_batches_tracked buffers
+
+    @staticmethod
+    def _check_frontend(frontend, mel_bins):
+        if frontend is None:
+            return None
+        from .frontend_layers import PCEN
+        if not isinstance(frontend, PCEN):
+            raise TypeError(f"frontend must be a PCEN layer or None (got {type(frontend).__name__})")
+        width = MEL_BINS if mel_bins is None else mel_bins
+        if frontend.mel_bins != width:
+            raise ValueError(f"the front-end was built for {frontend.mel_bins} mel bins, the model takes {width}")
+        return frontend
+
+    def _core_named_parameters(self):
+        """The parameters the engine owns: every one but the front-end layer's, which has an autograd node of its own."""
+        return [(n, p) for n, p in self.named_parameters() if not n.startswith("frontend.")]
 
     def _flush_counters(self):
         """BatchNorm's num_batches_tracked buffers are bookkeeping only (momentum is fixed): training
@@ -260,6 +280,8 @@ class Cnn_AvgPooling(nn.Module):
         import copy
         memo = {id(self.engine): None}
         memo.update({id(blk._eng): None for blk in self.conv_blocks if blk._eng is not None})
+        if self.frontend is not None:       # its workspace is a device buffer like the plans'
+            memo[id(self.frontend._ws)] = None
         twin = copy.deepcopy(self, memo)
         twin.engine = twin._make_engine(twin.precision)
         return twin
@@ -279,7 +301,10 @@ class Cnn_AvgPooling(nn.Module):
         if not first.is_cuda:
             raise RuntimeError("model parameters are on the CPU; call model.to('cuda')")
         x = x.float()
-        params = [p for _, p in self.named_parameters()]
+        if self.frontend is not None:
+            # the layer's own autograd node; a trainable one makes x require a gradient, so the keep / need_dx route below runs
+            x = self.frontend(x if x.dim() == 4 else x.unsqueeze(1))
+        params = [p for _, p in self._core_named_parameters()]
         # grad mode: an eval forward keeps what the eval-mode (frozen-BatchNorm) backward needs, a training forward whose input
         # needs a gradient keeps what the input gradient needs (C1 mode: conv1's ReLU mask).  Outputs are the same bits.
         keep = torch.is_grad_enabled() and (not self.training or x.requires_grad)
@@ -332,9 +357,10 @@ class Crnn_AvgPooling(Cnn_AvgPooling):
     Linear(512, classes) -> interpolate.  state_dict: conv_blocks.*, gru.{weight_ih_l0,...,
     bias_hh_l0_reverse} (loadable into torch.nn.GRU), event_fc.{weight (classes, 2*hidden), bias}."""
 
-    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, gru_hidden=256, mel_bins=None):
+    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, gru_hidden=256, mel_bins=None,
+                 frontend=None):
         self.gru_hidden = int(gru_hidden)
-        super().__init__(classes_num, model_config, precision, mel_bins=mel_bins)
+        super().__init__(classes_num, model_config, precision, mel_bins=mel_bins, frontend=frontend)
 
     def _build_head(self, c_last, classes_num):
         self.gru = _GruParams(c_last, self.gru_hidden)

@@ -103,8 +103,10 @@ class _M5Function(torch.autograd.Function):
 class M5(nn.Module):
     """Model described in "Very deep convolutional neural networks for raw waveforms" (waveform_models.py:9-12)."""
 
-    def __init__(self, classes_num, precision=None):
+    def __init__(self, classes_num, precision=None, frontend=None):
         super().__init__()
+        if frontend is not None:
+            raise ValueError("M5 reads the raw waveform: a spectrogram front-end layer (PCEN) does not apply to it")
         self.classes_num = classes_num
         self.precision = precision or DEFAULT_PRECISION
         for name, convs, pooled in M5_BLOCKS:

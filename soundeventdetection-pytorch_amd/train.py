@@ -350,6 +350,23 @@ def check_semi_options(mean_teacher=False, ema_decay=0.999, consistency_weight=2
     return d, w, int(consistency_rampup)
 
 
+def check_frontend_options(model, graph=False, group=None, mean_teacher=False):
+    """Refuse what a model with a front-end layer (Cnn_AvgPooling(frontend=PCEN(...))) does not train under: a captured graph, a
+    process group and the mean teacher.  Returns the layer, or None for a model without one -- the step then launches exactly
+    what it always did."""
+    fe = getattr(model, "frontend", None)
+    if fe is None:
+        return None
+    if graph:
+        raise RuntimeError("graph=True does not capture a front-end layer (PCEN): build the trainer with graph=False")
+    if data_parallel_enabled(group):
+        raise RuntimeError("a front-end layer (PCEN) trains in a single process: its backward takes the input gradient, which "
+                           "the data-parallel path (and SyncBN) does not provide")
+    if mean_teacher:
+        raise RuntimeError("mean_teacher does not take a model with a front-end layer (PCEN) yet")
+    return fe
+
+
 def ema_factor(n: int, ema_decay: float) -> float:
     """The teacher's EMA factor after the n-th step (n = 1, 2, ...): min(1 - 1/n, ema_decay), so the first update copies the
     student and the early teacher is the plain average of the students so far."""
@@ -400,6 +417,11 @@ class FusedTrainer:
         adds it to the strong loss, with the clip label taken from the (B, T, K) target on the device; weak_only=True trains on it
         alone, and the target may be (B, K).  None launches nothing new.
 
+        A model built with frontend=PCEN(...) brings its layer: the step runs the layer's forward, the engine's forward with
+        keep_for_grad, the losses, the engine's backward with need_dx, then sed_pcen_bwd on the input gradient into
+        flat.G['frontend.*'] (a fixed layer, trainable=False: its forward only).  The layer's parameters sit in the flat buffer like
+        the others.  Refused with graph=True, a process group or mean_teacher.
+
         mean_teacher: keep self.teacher, a copy of the model whose parameters are an exponential moving average of the
         student's (csrc/sed_semi.hip), with its own engine, plans and flat parameter buffer.  Every step the teacher runs a
         training-mode forward on teacher_augment(x) (a callable, None: x itself) and the student is pulled towards its frame
@@ -420,6 +442,7 @@ class FusedTrainer:
         (self.weight_decay, self.decoupled_weight_decay, self.amsgrad, self.max_grad_norm,
          self._opt_ext) = check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
         self.weak = check_weak_options(weak_pooling, weak_weight, weak_only, model)
+        self.frontend = check_frontend_options(model, graph, group, self.semi is not None)
         self.model = model
         self.engine = model.engine
         self.use_graph = bool(graph)
@@ -498,7 +521,16 @@ class FusedTrainer:
             self.teacher._fwd_serial += 1
         P = self.flat.tensor_dict()
         self.model.train()
-        plan = eng.forward(x, P, training=True)
+        fe = self.frontend
+        fe_train = fe is not None and fe.trainable
+        if fe is None:
+            plan = eng.forward(x, P, training=True)
+        else:
+            eng._tag = ""
+            x_raw = x.float() if x.dim() == 4 else x.float().unsqueeze(1)
+            fe_theta = fe.theta()
+            x = fe.run_forward(x_raw, fe_theta, launch=eng._k)
+            plan = eng.forward(x, P, training=True, keep_for_grad=True) if fe_train else eng.forward(x, P, training=True)
         self.model._nbt_pending += 1
         self.model._fwd_serial += 1
         if kind is not None or teacher_pre is not None:
@@ -510,7 +542,16 @@ class FusedTrainer:
             loss = eng.loss_and_grad(plan, y, self.recall_factor)
         else:
             loss = eng.loss_and_grad(plan, y, self.recall_factor, weak=self.weak)
-        eng.backward(plan, P, self.flat.G, on_group_done=self.reducer.bucket_ready)
+        if not fe_train:
+            eng.backward(plan, P, self.flat.G, on_group_done=self.reducer.bucket_ready)
+            return loss
+        eng.backward(plan, P, self.flat.G, on_group_done=self.reducer.bucket_ready, need_dx=True)
+        eng._tag = ""
+        _, dtheta = fe.run_backward(x_raw, fe_theta, plan.dx_in, need_dx=False, need_dtheta=True, launch=eng._k)
+        from .models.frontend_layers import PARAM_NAMES
+        for i, n in enumerate(PARAM_NAMES):
+            self.flat.G["frontend." + n].copy_(dtheta[i])
+        self.reducer.bucket_ready("frontend")        # the last group in backward-completion order
         return loss
 
     def optimizer_step(self):
@@ -915,6 +956,7 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
         weak_pooling, weak_only = criterion.pooling, True
     check_weak_options(weak_pooling, weak_weight, weak_only, model)
     check_semi_options(mean_teacher, ema_decay, consistency_weight, consistency_rampup, model)
+    check_frontend_options(model, mean_teacher=mean_teacher)
     if eval_teacher and not mean_teacher:
         raise ValueError("eval_teacher needs mean_teacher")
     if ranking_eval is not None:
