@@ -406,7 +406,9 @@ int sed_adam_step_ex_dev(float* p, const float* g, float* m, float* v, float* vm
  * wave fp32 [B][samples] -> out fp32 [B][T][n_mels], T = 1 + samples/hop; window fp32 [nfft]
  * (already zero-padded/centred); melT fp32 [n_mels][nfft/2+1] (MEL_FILTER_BANK_MATRIX^T);
  * mel_lo/mel_hi int32 [n_mels] = first/last+1 non-zero bin of each filter; mean/std [n_mels] or
- * NULL.  nfft a power of two in [64, 32768].  workspace: sed_logmel_ws_bytes() -- always required, used for the
+ * NULL.  melT must be zero outside [mel_lo[m], mel_hi[m]) (the batched nfft-1024 kernel multiplies the whole bin
+ * range of a 16-filter tile); the nfft-1024 kernels are taken for n_mels <= 64 only, more filters fall back to
+ * the generic kernel.  nfft a power of two in [64, 32768].  workspace: sed_logmel_ws_bytes() -- always required, used for the
  * FFT twiddle table only while the stream is being captured or beyond four transform sizes per device; otherwise
  * the library keeps one table per (device, nfft) of its own: the FIRST call for a size allocates it, builds it
  * on `stream` and synchronises that stream once (round 5: no per-call table launch).                             */

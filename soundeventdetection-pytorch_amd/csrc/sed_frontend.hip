@@ -31,6 +31,11 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
+// log10(max(1e-10, p)), floored at exactly -10 so that silence comes out at exactly -100 dB as the reference's double arithmetic
+// gives: log10f(1e-10f) is an ulp low here (10 * it = -100.00001).  The callers keep the `10.0f * ...` in their own expression so that
+// it contracts with the z-score's subtraction as before.
+__device__ __forceinline__ float fe_log10(float p) { return fmaxf(-10.0f, log10f(fmaxf(1e-10f, p))); }
+
 struct FrontParams {
     const float* wave;
     const float* window;
@@ -141,7 +146,7 @@ __global__ __launch_bounds__(256) void frontend_kernel(FrontParams p) {
         acc += dpp_mov<0xB1>(acc);
         acc += dpp_mov<0x4E>(acc);
         if (quad == 0) {
-            float v = 10.0f * log10f(fmaxf(1e-10f, acc));
+            float v = 10.0f * fe_log10(acc);
             if (p.mean) v = (v - p.mean[m]) / p.stdv[m];
             p.out[((size_t)b * p.T + frame) * p.n_mels + m] = v;
         }
@@ -294,7 +299,7 @@ __global__ __launch_bounds__(1024) void frontend_big_kernel(FrontParams p) {
         for (; k < hi; k += 64) a0 = fmaf(row[k], (k < M) ? Z[fe_zi(k)].x : Z[0].y, a0);
         const float acc = wave_sum((a0 + a1) + (a2 + a3));
         if (lane == 0) {
-            float v = 10.0f * log10f(fmaxf(1e-10f, acc));
+            float v = 10.0f * fe_log10(acc);
             if (p.mean) v = (v - p.mean[m]) / p.stdv[m];
             p.out[((size_t)b * p.T + frame) * p.n_mels + m] = v;
         }
@@ -621,7 +626,7 @@ __global__ __launch_bounds__(256, 5) void frontend1024_kernel(FrontParams p, int
                 const float* __restrict__ row = p.melT + (size_t)m * 513 + lo;
                 for (int j = 0; j < cnt; ++j) acc = fmaf(row[j], pr[j], acc);
             }
-            float val = 10.0f * log10f(fmaxf(1e-10f, acc));
+            float val = 10.0f * fe_log10(acc);
             if (p.mean) val = (val - p.mean[m]) / p.stdv[m];
             if (live) p.out[(size_t)fidx * p.n_mels + m] = val;
         }
@@ -971,7 +976,7 @@ __global__ __launch_bounds__(512, 4) void frontend1024c_kernel(FrontParams p, in
             if (tw_cnt > 2) s += rp[256];
             if (tw_cnt > 3) s += rp[384];
             if (tw_cnt > 4) s += rp[512];
-            float val = 10.0f * log10f(fmaxf(1e-10f, s));
+            float val = 10.0f * fe_log10(s);
             if (p.mean) val = (val - zmean) * zinv;
             if (t0 + fr < T && fm < nm) p.out[((size_t)cb * T + t0 + fr) * nm + fm] = val;
         }
@@ -1017,7 +1022,7 @@ __global__ __launch_bounds__(256) void complex_to_logmel_kernel(const float2* __
         acc += dpp_mov<0xB1>(acc);
         acc += dpp_mov<0x4E>(acc);
         if (quad == 0) {
-            float v = 10.0f * log10f(fmaxf(1e-10f, acc));
+            float v = 10.0f * fe_log10(acc);
             if (mean) v = (v - mean[m]) / stdv[m];
             out[frame * n_mels + m] = v;
         }
@@ -1106,7 +1111,7 @@ __global__ __launch_bounds__(256) void complex_augment_logmel_kernel(
         for (int k = lo + quad; k < hi; k += 4) acc = fmaf(row[k], P[k], acc);
         acc += dpp_mov<0xB1>(acc);
         acc += dpp_mov<0x4E>(acc);
-        if (quad == 0) out[frame * n_mels + m] = 10.0f * log10f(fmaxf(1e-10f, acc));
+        if (quad == 0) out[frame * n_mels + m] = 10.0f * fe_log10(acc);
     }
 }
 
