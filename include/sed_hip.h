@@ -883,10 +883,9 @@ int sed_conv3x3_wgrad_fused_c1(int dtype, const float* x1, const float* fmean, c
  * (sed_m5_conv1_fwd in SED_BF16, sed_m5_conv1_stats) sum the bf16-rounded values as stored.
  * wgrad: dw_partial fp32 [sed_m5_conv1_nparts][80][64] (tap-major).  Tap row 79 is padding: every kernel writes it, its
  * value is UNSPECIFIED (the fp32 kernel leaves a contraction there, the matrix-pipe kernels 0) and consumers read rows
- * 0..78 only (sed_m5_conv1_wgrad_combine does not read row 79 of g1).  Every one of the nparts rows is written.
- * The pooled forms (sed_m5_conv1_bn_relu_pool_fwd, sed_m5_conv1_pool_bwd_stats, sed_m5_conv1_wgrad_fused_pool[_x],
- * sed_m5_conv1_bwd_stats_g1, sed_m5_conv1_dgrad_fused_pool) need L1 >= 4, the sed_*maxpool4* entry points H >= 4: the
- * pooled tensor must have at least one row.  All of them, the recomputing kernels included, decide as MaxPool1d does:
+ * 0..78 only.  Every one of the nparts rows is written.
+ * The pooled forms (sed_m5_conv1_bn_relu_pool_fwd, sed_m5_conv1_wgrad_fused_pool, sed_m5_conv1_dgrad_fused_pool) need
+ * L1 >= 4, the sed_*maxpool4* entry points H >= 4: the pooled tensor must have at least one row.  All of them decide as MaxPool1d does:
  * the FIRST arg-max of relu(scale*z + shift) in a window of 4 (ties keep the earlier step) takes the gradient, and only
  * when that maximum is > 0 (a window whose largest pre-activation is <= 0 passes nothing).          */
 int sed_m5_conv1_len(int L);
@@ -900,47 +899,19 @@ int sed_m5_conv1_wgrad(int dtype, const float* x, const void* dz, float* dw_part
 int sed_m5_conv1_wgrad_fused(int dtype, const float* x, const void* g, const void* zsrc, const float* ca,
                              const float* cb, const float* cc, float* dw_partial, int B, int L,
                              void* stream);
-/* Round 4, "z-free" first block (bf16): conv_block1's output z1 (8x its input: 2.9 GB at 2880 frames) is never stored.  With one input
- * channel a 128-step tile is 10 MFMAs per wave away from the staged input window, so the three consumers of z1 recompute it
- * (bit-identical to the stored tensor: the same MFMA sequence, rounded to bf16 where sed_m5_conv1_fwd stored it):
+/* Two-pass forward of conv_block1 (bf16, matrix pipe): z1 is 8x its input (2.9 GB at 2880 frames) and, with one input channel, a
+ * 128-step tile is 10 MFMAs per wave away from the staged input window, so the second pass computes it again (bit-identical: the same
+ * MFMA sequence, rounded to bf16 where sed_m5_conv1_fwd stores it) instead of reading it back:
  *   sed_m5_conv1_stats             the BatchNorm1d statistics of sed_m5_conv1_fwd (stats_partial as there), no z
  *   sed_m5_conv1_bn_relu_pool_fwd  sed_m5_conv1_fwd + sed_bn_relu_maxpool4_fwd: y [B/8][L1/4][8][64]
- *   sed_m5_conv1_pool_bwd_stats    sed_maxpool4_relu_bwd with g = NULL: partial [sed_m5_conv1_nparts][2][64] = (sum g, sum g*xhat)
- *   sed_m5_conv1_wgrad_fused_pool_x  sed_m5_conv1_wgrad_fused_pool without zsrc (w = conv1's weights [64][79])
- * /root/reference/models/waveform_models.py:15-24 (conv_block1) forward and backward.  sed_m5_zfree_supported(): bf16 with the
- * matrix-pipe first layer on (SED_M5_MFMA != 0) and SED_M5_ZFREE=1 -- opt-in: the same values as the stored-z path (block 1's own
- * gradients to fp32 rounding) and measured slower as built (step 9.73 against 8.80 ms at 2880 frames: the recomputing backward kernels lose more than the forward gains). */
-int sed_m5_zfree_supported(int dtype);
-/* The algebraic backward of conv_block1 (round 4; opt-in, SED_M5_ALG=1: parity-green, measured slower -- the Gram kernel costs more than
- * the merged pass saves).  g = MaxPool / ReLU
- * backward of dy; BatchNorm1d backward dz = ca*g + cb*z + cc; with ONE input channel
- *     dW1[c][k] = sum_t dz[c][t] x[4t + k - 39] = ca[c]*G1[k][c] + cb[c] * (w1 . Gram)[c][k] + cc[c]*Sp[k]
- * where G1 = sum_t g (x) patch comes from the ONE pass that also yields the statistics (sum g, sum g*xhat) -- z is read once instead of
- * twice -- and Gram[k'][k] = sum_t x[4t+k'-39] x[4t+k-39], Sp[k] = sum_t x[4t+k-39] (bf16-rounded x, steps t < L1) depend on the input
- * only.  dz is never formed (and not rounded to bf16: the result is the exact contraction of the coefficients' form).
- *   sed_m5_conv1_gram            gram_partial fp32 [sed_m5_conv1_nparts][sed_m5_conv1_gram_floats()]  (sum the rows: sed_sum_partials)
- *   sed_m5_conv1_bwd_stats_g1    stats_partial [nparts][2][64] (as sed_maxpool4_relu_bwd), g1_partial [nparts][80][64] (as dw_partial)
- *   sed_m5_conv1_wgrad_combine   g1 [80][64], gram [gram_floats], w [64][79] -> dw [64][79]
- * /root/reference/models/waveform_models.py:15-24 backward.                                                                       */
-int sed_m5_alg_supported(int dtype);
-size_t sed_m5_conv1_gram_floats(void);
-int sed_m5_conv1_gram(const float* x, float* gram_partial, int B, int L, void* stream);
-int sed_m5_conv1_bwd_stats_g1(int dtype, const float* x, const void* dy, const void* zsrc, const float* scale, const float* shift,
-                              const float* mean, const float* invstd, float* stats_partial, float* g1_partial, int B, int L,
-                              void* stream);
-int sed_m5_conv1_wgrad_combine(const float* g1, const float* gram, const float* w, const float* ca, const float* cb, const float* cc,
-                               float* dw, void* stream);
+ * models/waveform_models.py:15-24 (conv_block1) forward.                                                                          */
 int sed_m5_conv1_stats(int dtype, const float* x, const float* w, float* stats_partial, int B, int L, void* stream);
 int sed_m5_conv1_bn_relu_pool_fwd(int dtype, const float* x, const float* w, const float* scale, const float* shift, void* y,
                                   void* z_out, int B, int L, void* stream);
 /* z_out (nullable): also store z [B/8][L1][8][64] for a backward that reads it -- the default bf16 forward of conv_block1 (round 4,
  * sed_m5_fwd2_supported): sed_m5_conv1_stats, the finalize, then this launch; sed_bn_relu_maxpool4_fwd's pass over z is gone.     */
 int sed_m5_fwd2_supported(int dtype);
-int sed_m5_conv1_pool_bwd_stats(int dtype, const float* x, const float* w, const void* dy, const float* scale, const float* shift,
-                                const float* mean, const float* invstd, float* partial, int B, int L, void* stream);
-int sed_m5_conv1_wgrad_fused_pool_x(int dtype, const float* x, const float* w, const void* dy, const float* scale, const float* shift,
-                                    const float* ca, const float* cb, const float* cc, float* dw_partial, int B, int L, void* stream);
-/* ... and with g rebuilt on load too: the MaxPool1d(4) + ReLU backward of the pooled gradient dy [B/8][L1/4][8][64]
+/* sed_m5_conv1_wgrad_fused with g rebuilt on load too: the MaxPool1d(4) + ReLU backward of the pooled gradient dy [B/8][L1/4][8][64]
  * (dy goes to the first arg-max of relu(scale*zsrc + shift) in each window of 4 when that maximum is > 0).  Pairs with
  * sed_maxpool4_relu_bwd(..., g = NULL, ...), which then only produces the BatchNorm-backward statistics.             */
 int sed_m5_conv1_wgrad_fused_pool(int dtype, const float* x, const void* dy, const void* zsrc,

@@ -65,7 +65,7 @@ def tie_tolerance(z, scale):
 
 
 def train_step_grads_bf16(x, target, sd: Dict[str, torch.Tensor], recall_factor: float, rb: Callable = round_bf16,
-                          alg_first: bool = False, take_decisions=None, decision_stats=None):
+                          take_decisions=None, decision_stats=None):
     """x (B, 1, L) float32, target (B,) or (B, classes).  Returns (loss, logits, grads, new BN running statistics).
     take_decisions (round 5): one entry per layer, dict(mask=bool (B, C, L) -- the ENGINE's ReLU decisions relu'(scale*z + shift) --,
     idx=int64 (B, C, L/4) or None -- the engine's MaxPool1d arg-max positions along L).  Both pipelines compute the same bf16 values
@@ -74,10 +74,7 @@ def train_step_grads_bf16(x, target, sd: Dict[str, torch.Tensor], recall_factor:
     /root/reference/models/waveform_models.py:59-71 -- but each switched branch moves a whole gradient path and costs cosine.  There,
     and only there, the oracle takes the engine's branch; decision_stats (a dict, filled in) counts per layer how many decisions were
     BORROWED (differed from the oracle's own) out of how many elements.  Far from a tie the oracle's own decision always stands, so a
-    wrong engine decision still shows.
-    alg_first: conv_block1's weight gradient in the engine's algebraic form (csrc/sed_m5_mfma.hip, round 4): dW1 = ca*G1 + cb*(w1 .
-    Gram) + cc*Sp = the contraction of dz = ca*g + cb*z' + cc with z' the UNROUNDED convolution of the bf16 operands and dz itself
-    not rounded (the engine never forms it; opt-in SED_M5_ALG=1); False (the default engine path): dz rounded to bf16 from the stored z."""
+    wrong engine decision still shows.  conv_block1's dz, like every layer's, is rounded to bf16 from the stored z."""
     if decision_stats is None:
         decision_stats = {}
     P = {k: v.to(F64) for k, v in sd.items()}
@@ -153,15 +150,7 @@ def train_step_grads_bf16(x, target, sd: Dict[str, torch.Tensor], recall_factor:
         dz = rb(_c(gam * co["invstd"]) * (g - _c(dbeta) / n - xhat * _c(dgamma) / n))
         w = P[c["conv"] + ".weight"]
         grads[c["conv"] + ".bias"] = torch.zeros_like(P[c["conv"] + ".bias"])
-        if li == 0 and alg_first:
-            is_ = co["invstd"]
-            ca_, cb_ = gam * is_, -gam * is_ * is_ * dgamma / n
-            cc_ = -gam * is_ * (dbeta / n - co["mean"] * is_ * dgamma / n)
-            z_unr = F.conv1d(c["a"], rb(w), None, stride=c["s"], padding=c["p"])
-            dz_w = _c(ca_) * g + _c(cb_) * z_unr + _c(cc_)
-            grads[c["conv"] + ".weight"] = torch.nn.grad.conv1d_weight(c["a"], w.shape, dz_w, stride=c["s"], padding=c["p"])
-        else:
-            grads[c["conv"] + ".weight"] = torch.nn.grad.conv1d_weight(c["a"], w.shape, dz, stride=c["s"], padding=c["p"])
+        grads[c["conv"] + ".weight"] = torch.nn.grad.conv1d_weight(c["a"], w.shape, dz, stride=c["s"], padding=c["p"])
         if li > 0:
             d_in = torch.nn.grad.conv1d_input(c["a"].shape, rb(w), dz, stride=c["s"], padding=c["p"])
             below = cache[li - 1]

@@ -36,6 +36,27 @@ M5_BLOCKS = [
     ("conv_block5", [(0, 1, 128, 256), (3, 4, 256, 256)], False),
 ]
 
+CONV1_ROUTES = ("valu", "mfma")
+
+
+def conv1_route(lib, precision: str, environ=_os.environ):
+    """How conv_block1 runs, decided once per plan (host only: no tensor, no device).  Returns (route, fwd2, poolstats):
+      'valu'  fp32, or bf16 under SED_M5_MFMA=0: sed_m5_conv1_fwd, sed_bn_relu_maxpool4_fwd; backward sed_maxpool4_relu_bwd writing g,
+              sed_bn_bwd_apply + sed_m5_conv1_wgrad (input gradient: sed_m5_conv1_dgrad from the dz that route materialises)
+      'mfma'  bf16 on the matrix pipe: the weight gradient (sed_m5_conv1_wgrad_fused_pool; input gradient
+              sed_m5_conv1_dgrad_fused_pool) rebuilds g and dz from (dy, z) on load, so the pass before it yields statistics only
+        fwd2       two-pass forward (sed_m5_conv1_stats, then sed_m5_conv1_bn_relu_pool_fwd) instead of sed_m5_conv1_fwd + the
+                   pool pass (SED_M5_FWD2=0)
+        poolstats  a training backward takes those statistics from the pooled tensors (sed_maxpool4_pooled_stats +
+                   sed_maxpool4_relu_bwd_if) instead of sed_maxpool4_relu_bwd with g = NULL (SED_M5_POOLSTATS=0); an eval-mode
+                   backward takes the latter either way: chosen per backward
+    Both flags are False on the 'valu' route."""
+    dt = L.SED_BF16 if precision == "bf16" else L.SED_F32
+    if precision != "bf16" or environ.get("SED_M5_MFMA", "1") == "0":
+        return "valu", False, False
+    fwd2 = environ.get("SED_M5_FWD2", "1") != "0" and bool(lib.sed_m5_fwd2_supported(dt))
+    return "mfma", fwd2, environ.get("SED_M5_POOLSTATS", "1") != "0"
+
 
 class _Ly:
     def __init__(self, conv, bn, cin, cout, H, first, pool):
@@ -76,19 +97,15 @@ class M5Engine(OptimizerExtMixin):
         p = type("Plan", (), {})()
         p.B, p.N, p.L = B, N, Lw
         p.layers: List[_Ly] = []
-        # "z-free" first block (csrc/sed_m5_mfma.hip, round 4): conv_block1's output is never stored, its three consumers recompute it
-        p.zfree = bool(lib.sed_m5_zfree_supported(self.dt))
-        # two-pass forward of the first block: statistics without z, then conv + BN + ReLU + MaxPool (+ the z store the backward reads)
-        p.fwd2 = p.zfree or bool(lib.sed_m5_fwd2_supported(self.dt))
-        # algebraic backward of the first block: statistics + G1 = sum g (x) patch in ONE pass over z, dW1 from G1 and the input's Gram
-        # statistics (csrc/sed_m5_mfma.hip); not with the z-free experiment (which has no z to read)
-        p.alg = (not p.zfree) and bool(lib.sed_m5_alg_supported(self.dt))
+        # conv_block1's route (csrc/sed_m5_mfma.hip); fwd2: statistics without z, then conv + BN + ReLU + MaxPool (+ the z store the
+        # backward reads) in one launch
+        p.route, p.fwd2, p.poolstats = conv1_route(lib, self.precision)
         p.pool_flag = torch.zeros(1, device=dev, dtype=torch.int32)       # sed_maxpool4_pooled_stats raises it, sed_maxpool4_relu_bwd_if resets it
         H = lib.sed_m5_conv1_len(Lw)
         for name, convs, pooled in M5_BLOCKS:
             for i, (ci, bi, cin, cout) in enumerate(convs):
                 ly = _Ly(f"{name}.{ci}", f"{name}.{bi}", cin, cout, H, cin == 1, pooled and i == len(convs) - 1)
-                ly.z = None if (ly.first and p.zfree) else torch.empty((N, H, 8, cout), **T)
+                ly.z = torch.empty((N, H, 8, cout), **T)
                 ly.scale, ly.shift, ly.mean, ly.invstd = (torch.empty(cout, **f32) for _ in range(4))
                 ly.coef = torch.empty((3, cout), **f32)
                 if ly.first:
@@ -119,16 +136,11 @@ class M5Engine(OptimizerExtMixin):
         p.dpre = torch.empty((B, self.K), **f32)
         p.loss = torch.zeros(1, **f32)
         p.loss_partial = torch.empty(max(1, (B * self.K + 255) // 256), **f32)
-        maxact = max(l.z.numel() for l in p.layers if l.z is not None)
+        maxact = max(l.z.numel() for l in p.layers)
         p.scratch = [torch.empty(maxact, **T) for _ in range(3)]
         p.wgrad_ws = torch.empty(max(1, max(lib.sed_conv_wgrad_ws_floats(N, l.H, 8, l.cin, l.cout) for l in p.layers if not l.first)), **f32)
         p.c1_ws = torch.empty((lib.sed_m5_conv1_nparts(B, Lw), 80, 64), **f32)
         p.c1_dw = torch.empty((80, 64), **f32)
-        if p.alg:
-            gn = lib.sed_m5_conv1_gram_floats()
-            p.gram_part = torch.empty((lib.sed_m5_conv1_nparts(B, Lw), gn), **f32)
-            p.gram = torch.empty(gn, **f32)
-            p.dw1 = torch.empty((64, 79), **f32)
         nb = max([lib.sed_m5_conv1_nparts(B, Lw)] + [lib.sed_maxpool4_bwd_nparts(N, l.H, 8, l.cout) for l in p.layers if l.pool] +
                  [lib.sed_pool_bwd_nparts(N, l.H, 8, l.cout) for l in p.layers] + [lib.sed_conv_nparts(N, l.H, 8) for l in p.layers])
         p.bwd_part = torch.empty((nb, 2, max(l.cout for l in p.layers)), **f32)
@@ -152,9 +164,6 @@ class M5Engine(OptimizerExtMixin):
         p = self.plan(B, Lw, x.device)
         lib, dt, st, N = self.lib, self.dt, _stream(), p.N
         keep = bool(keep_for_grad) and not training
-        if keep and (p.zfree or p.alg):
-            raise RuntimeError("SED_M5_ZFREE=1 / SED_M5_ALG=1 never form conv_block1's z / dz: an eval-mode forward kept for a "
-                               "backward is not available with them (unset the experiment)")
         p.x_ref, p.trained, p.keep = x, training, bool(keep_for_grad)
         prev = None
         for i, ly in enumerate(p.layers):
@@ -163,9 +172,6 @@ class M5Engine(OptimizerExtMixin):
             g, b = P[ly.bn + ".weight"], P[ly.bn + ".bias"]
             rm, rv = P[ly.bn + ".running_mean"], P[ly.bn + ".running_var"]
             part = ly.part if training else None
-            if ly.first and training and p.alg:      # Gram statistics of the input patches (input only: any time before the backward)
-                self._k("sed_m5_conv1_gram", lib.sed_m5_conv1_gram, L.ptr(x), L.ptr(p.gram_part), B, Lw, st)
-                self._k("sed_sum_partials", lib.sed_sum_partials, L.ptr(p.gram_part), p.gram_part.shape[0], p.gram.numel(), L.ptr(p.gram), st)
             if ly.first and p.fwd2:
                 if training:      # BatchNorm statistics of z1 without z1 (eval: the running statistics need no pass at all)
                     self._k("sed_m5_conv1_stats", lib.sed_m5_conv1_stats, dt, L.ptr(x), L.ptr(w), L.ptr(part), B, Lw, st)
@@ -208,7 +214,7 @@ class M5Engine(OptimizerExtMixin):
             if hasattr(ly, "y"):
                 if ly.first and p.fwd2:
                     self._k("sed_m5_conv1_bn_relu_pool_fwd", lib.sed_m5_conv1_bn_relu_pool_fwd, dt, L.ptr(x), L.ptr(w), L.ptr(ly.scale),
-                            L.ptr(ly.shift), L.ptr(ly.y), None if p.zfree else (L.ptr(ly.z) if (training or keep) else None), B, Lw, st)
+                            L.ptr(ly.shift), L.ptr(ly.y), L.ptr(ly.z) if (training or keep) else None, B, Lw, st)
                 elif ly.pool:
                     self._k("sed_bn_relu_maxpool4_fwd", lib.sed_bn_relu_maxpool4_fwd, dt, L.ptr(ly.z), L.ptr(ly.scale),
                             L.ptr(ly.shift), L.ptr(ly.y), N, ly.H, 8, ly.cout, st)
@@ -248,9 +254,6 @@ class M5Engine(OptimizerExtMixin):
         need_dx = bool(need_dx)
         if (eval_bwd or need_dx) and getattr(self, "bn_sync", None) is not None:
             raise RuntimeError("input-gradient and eval-mode backward are not available with SyncBN")
-        if (eval_bwd or need_dx) and (p.zfree or p.alg):
-            raise RuntimeError("SED_M5_ZFREE=1 / SED_M5_ALG=1 never form conv_block1's z / dz: the input gradient and the eval-mode "
-                               "backward are not available with them (unset the experiment)")
         lib, dt, st, N, B = self.lib, self.dt, _stream(), p.N, p.B
         src = p.dpre if dlogits is None else dlogits.contiguous().float()
         last = p.layers[-1]
@@ -270,23 +273,11 @@ class M5Engine(OptimizerExtMixin):
             ca, cb, cc = ly.coef[0], ly.coef[1], ly.coef[2]
             if hasattr(ly, "y"):
                 # ---- block output layer: (pool +) ReLU + BN backward statistics from dy -------------------
-                if ly.first and p.zfree:
-                    # statistics of the pool / ReLU backward with z1 recomputed from the input (one partial row per workgroup)
-                    nparts = lib.sed_m5_conv1_nparts(B, p.L)
-                    self._k("sed_m5_conv1_pool_bwd_stats", lib.sed_m5_conv1_pool_bwd_stats, dt, L.ptr(p.x_ref), L.ptr(P[ly.conv + ".weight"]),
-                            L.ptr(ly.dy), L.ptr(ly.scale), L.ptr(ly.shift), L.ptr(ly.mean), L.ptr(ly.invstd), L.ptr(p.bwd_part), B, p.L, st)
-                    dzmode, gsrc, pool = L.DZ_BN, gbuf, 1
-                elif ly.first and p.alg:
-                    # ONE pass over z1: the pool / ReLU backward statistics and G1 = sum g (x) patch (per-workgroup partials)
-                    nparts = lib.sed_m5_conv1_nparts(B, p.L)
-                    self._k("sed_m5_conv1_bwd_stats_g1", lib.sed_m5_conv1_bwd_stats_g1, dt, L.ptr(p.x_ref), L.ptr(ly.dy), L.ptr(ly.z),
-                            L.ptr(ly.scale), L.ptr(ly.shift), L.ptr(ly.mean), L.ptr(ly.invstd), L.ptr(p.bwd_part), L.ptr(p.c1_ws), B, p.L, st)
-                    dzmode, gsrc, pool = L.DZ_BN, gbuf, 1
-                elif ly.pool:
+                if ly.pool:
                     nparts = lib.sed_maxpool4_bwd_nparts(N, H, 8, C)
-                    # first layer, bf16: its matrix-pipe weight gradient rebuilds g from (dy, z) itself -> statistics only here
-                    g_free = ly.first and dt == L.SED_BF16 and _os.environ.get("SED_M5_MFMA", "1") != "0"
-                    if g_free and not eval_bwd and _os.environ.get("SED_M5_POOLSTATS", "1") != "0":
+                    # first layer on the matrix pipe: its weight gradient rebuilds g from (dy, z) itself -> statistics only here
+                    g_free = ly.first and p.route == "mfma"
+                    if g_free and p.poolstats and not eval_bwd:
                         # statistics from the pooled tensors (y, dy): a quarter of z's rows each; the z pass only runs when an
                         # ill-conditioned channel (|beta| > 8 |gamma|) raised the flag (training only: the shortcut rests on batch
                     # statistics, an eval-mode backward takes the z pass below).  ONE flag word: sed_maxpool4_relu_bwd_if resets it
@@ -321,19 +312,7 @@ class M5Engine(OptimizerExtMixin):
                         L.ptr(ly.mean), L.ptr(ly.invstd), L.ptr(G[gname]), L.ptr(G[bname]), L.ptr(ca), L.ptr(cb), L.ptr(cc), C, C, st)
             if ly.first:
                 # dz1 = BN backward of g, then the k=79 weight gradient
-                if p.alg:         # dW1 = ca*G1 + cb*(w1 . Gram) + cc*Sp: dz1 is never formed
-                    self._k("sed_sum_partials", lib.sed_sum_partials, L.ptr(p.c1_ws), p.c1_ws.shape[0], 80 * 64, L.ptr(p.c1_dw), st)
-                    self._k("sed_m5_conv1_wgrad_combine", lib.sed_m5_conv1_wgrad_combine, L.ptr(p.c1_dw), L.ptr(p.gram),
-                            L.ptr(P[ly.conv + ".weight"]), L.ptr(ca), L.ptr(cb), L.ptr(cc), L.ptr(p.dw1), st)
-                    G[ly.conv + ".weight"].copy_(p.dw1.reshape(64, 1, 79))
-                    if on_group_done is not None:
-                        on_group_done(ly.conv.split(".")[0])
-                    continue
-                if p.zfree:       # z1 recomputed from the input inside the weight-gradient kernel as well
-                    self._k("sed_m5_conv1_wgrad_fused_pool_x", lib.sed_m5_conv1_wgrad_fused_pool_x, dt, L.ptr(p.x_ref),
-                            L.ptr(P[ly.conv + ".weight"]), L.ptr(ly.dy), L.ptr(ly.scale), L.ptr(ly.shift), L.ptr(ca), L.ptr(cb), L.ptr(cc),
-                            L.ptr(p.c1_ws), B, p.L, st)
-                elif dt == L.SED_BF16 and _os.environ.get("SED_M5_MFMA", "1") != "0":
+                if p.route == "mfma":
                     # matrix-pipe kernel, dz rebuilt on load from (g, z): no separate BatchNorm-backward pass, dz never written
                     self._k("sed_m5_conv1_wgrad_fused_pool", lib.sed_m5_conv1_wgrad_fused_pool, dt, L.ptr(p.x_ref), L.ptr(ly.dy),
                             L.ptr(ly.z), L.ptr(ly.scale), L.ptr(ly.shift), L.ptr(ca), L.ptr(cb), L.ptr(cc), L.ptr(p.c1_ws), B, p.L, st)

@@ -1,6 +1,6 @@
 """GPU: the raw-waveform M5 kernels of csrc/sed_m5.hip and csrc/sed_m5_mfma.hip -- the k = 79 / stride 4 first convolution in every
-form (forward, statistics, fused BN + ReLU + MaxPool forward, the weight-gradient family, the recomputing "z-free" kernels, the
-algebraic Gram / G1 / combine pieces), the MaxPool1d(4) kernels on a given z and the mean-over-time + Linear head -- per element
+form (forward, statistics, fused BN + ReLU + MaxPool forward, the weight-gradient family), the MaxPool1d(4) kernels on a given z
+and the mean-over-time + Linear head -- per element
 against float64, through the C ABI.  (sed_m5_conv1_dgrad* has its own gate in tests/test_gpu_m5_input_grad.py.)
 
 Reference: the same operation in float64 (torch) ON THE OPERANDS THE KERNEL READS: where a kernel rounds x, w, z or dy to bf16 on load
@@ -24,7 +24,7 @@ ulps, which are hard bounds).  Nothing below was set from a measurement.  tpb = 
                  per tile, the workgroup 32 threads per channel: c = SAFE * (4 tpb + 32) u of sum |v|, one more (the fma) for v^2.
   y              fused BN + ReLU + MaxPool: a maximum is 1-Lipschitz, so |y - yref| <= max over the window of |scale| * (z's gate)
                  + SAFE * u * (|scale z| + |shift|) (the fma), plus the bf16 store.  No arg-max decision enters.
-  decisions      the kernels that recompute z and decide on it (sed_m5_conv1_pool_bwd_stats, sed_m5_conv1_wgrad_fused_pool_x) get
+  decisions      sed_m5_conv1_wgrad_fused_pool decides on the stored z; next to separated pre-activations it gets
                  inputs for which z and every pre-activation are exact in fp32 AND bf16 (integer x in [-8, 8], six taps of +-1 per
                  channel, scale = +-2^k, shift = (j + 1/2)/8; asserted on the CPU first), so ties and non-positive windows are
                  genuine and "first arg-max, maximum > 0" is applied exactly by the reference.
@@ -35,15 +35,9 @@ ulps, which are hard bounds).  Nothing below was set from a measurement.  tpb = 
                  slop): 2^-9 |v| only at the top of a binade, up to 2^-8 |v| at its bottom (bf16 has 8 significand bits), so a flat
                  2^-9 * S is NOT a bound -- the first version of this module assumed it and integer-valued data showed 1.36 x.
   tap row 79     unspecified (the VALU kernel leaves a contraction there, the MFMA kernels 0): consumers read rows 0..78.  The
-                 tests never read it as dW, require it to be written, and hand sed_m5_conv1_wgrad_combine a g1 whose row 79 is NaN.
-  pool stats     (sum g, sum g*xhat): g is dy or 0 exactly; a thread adds 4 terms per window and owns one window per tile (conv1
-                 forms: c = SAFE * (4 tpb + 32) u; the sed_maxpool4 kernels: n = 4 * windows per thread + 256 / (Cp/8)), xhat =
-                 (z - mean) * invstd and the fma add 3.
-  Gram, Sp       products of bf16 values are exact; 32 tpb accumulations + 3 adds + the fp32 cast of the row sum: c = SAFE * (32 tpb
-                 + 4) u of sum |p||p'|; Sp: 16 tpb + 8 + 1.  G1 as the MFMA weight gradient without the dz roundings.
-  composed       ca G1 + cb (w . Gram) + cc Sp is evaluated in double by the kernel and rounded once: the gate is |ca| (G1's gate)
-                 + |cb| sum_k' |w| (Gram's gate) + |cc| (Sp's gate) + SAFE * u * (sum of the three magnitudes), against the float64
-                 dW of dz = ca g + cb conv64(bf16 x, bf16 w) + cc (dz is NOT rounded in this form).
+                 tests never read it as dW and require it to be written.
+  pool stats     (sum g, sum g*xhat): g is dy or 0 exactly; a thread adds 4 terms per window (the sed_maxpool4 kernels: n = 4 *
+                 windows per thread + 256 / (Cp/8)), xhat = (z - mean) * invstd and the fma add 3.
   maxpool4       forward: one fma, c = SAFE * u of max over the window of |scale z| + |shift|, plus the bf16 store.  Backward: g bit
                  for bit (dy or +0; rows dropped by the floor +0).  pooled_stats: the float64 value of the kernel's own formula on
                  the y it is given; q = (rt - beta st) * (invstd / scale) costs the accumulation and 6 more roundings of
@@ -56,10 +50,8 @@ ulps, which are hard bounds).  Nothing below was set from a measurement.  tpb = 
 Measured max err / gate on the MI355X (printed per check at the end of the module with -s; head / tail / all agree to the digits shown):
   z              f32 0.020; bf16 VALU 0.991, bf16 MFMA 0.992 (the storage half ulp is the error and the gate); y 0.989
   z statistics   sum z 0.003 (VALU) / 0.0004 (MFMA), sum z^2 0.017: worst-case operation counts against errors that add like a random walk
-  weight grads   VALU f32 / bf16 0.002 (a 128 tpb chain, tpb up to 27); fused 0.84, fused_pool 0.85 separated / 0.74 exact, fused_pool_x 0.74
+  weight grads   VALU f32 / bf16 0.002 (a 128 tpb chain, tpb up to 27); fused 0.84, fused_pool 0.85 separated / 0.74 exact
                  (the bf16 rounding of dz is the error and the gate)
-  pool stats     conv1_pool_bwd_stats 0.007, bwd_stats_g1 0.007; G1 0.002 separated, 0.0005 on the integer data (most partial sums exact)
-  Gram, Sp       0.009, 0.0004; composed dW 0.007
   maxpool4       forward f32 0.25 (one rounding = the count without SAFE; 0 on the exact data), bf16 0.9999; relu_bwd statistics 0.04;
                  pooled_stats sum g 0.06, sum g*xhat 0.04; g, dropped rows, zero rows, flags bit for bit
   head           m 0.20, pre 0.04, dfc_w 0.05, dfc_b 0.06, dfeat 0.24 (f32) / 0.9999 (bf16)
@@ -350,7 +342,7 @@ def test_conv1_forward_family(L, monkeypatch, Lx, B):
     assert not bool(torch.isnan(xbuf[XPAD:-XPAD]).any()) and bool(torch.isnan(xbuf[:XPAD]).all()) and bool(torch.isnan(xbuf[-XPAD:]).all())
 
 
-# ---- inputs of the pooled / recomputing kernels ----------------------------------------------------------------------------------
+# ---- inputs of the pooled weight gradient ------------------------------------------------------------------------------------------
 def exact_case(B, Lx, gen):
     """x, w, scale, shift for which z = conv1(x, w) and every pre-activation scale*z + shift are exact in fp32 and z in bf16: ties and
     non-positive windows are genuine.  Returns CPU tensors (x [B][L], w [64][79], z [B][L1][64] float64, scale, shift)."""
@@ -392,22 +384,22 @@ def pool_case(B, L1, gen):
     return z, scale, shift
 
 
-def run_pooled_family(L, env, tag, Lx, B, x, w, z_eng, scale, shift, gen, recompute):
-    """Every kernel that rebuilds g (and dz) from the pooled gradient, on one set of inputs, at every grid.  z_eng: the stored z
-    (bf16-exact, engine layout, CPU).  recompute: z_eng = conv1(x, w) exactly, so the z-free kernels and the algebraic form run too."""
+def run_pooled_family(L, env, tag, Lx, B, x, z_eng, scale, shift, gen, exact):
+    """sed_m5_conv1_wgrad_fused_pool, which rebuilds g (and dz) from the pooled gradient, at every grid.  z_eng: the stored z
+    (bf16-exact, engine layout, CPU).  exact: the inputs of exact_case, which hold genuine ties and non-positive windows."""
     lib, P, st = L.lib(), L.ptr, _stream()
     L1 = conv_len(Lx)
     N, Ho = B // 8, L1 // 4
     dy = torch.randn(N, Ho, 8, 64, generator=gen).bfloat16().cuda()
     ca = (torch.rand(64, generator=gen) + 0.5).cuda()
     cb, cc = (torch.randn(64, generator=gen) * 0.1).cuda(), (torch.randn(64, generator=gen) * 0.1).cuda()
-    mean, invstd = (torch.randn(64, generator=gen) * 0.3).cuda(), (torch.rand(64, generator=gen) + 0.5).cuda()
+    torch.randn(64, generator=gen), torch.rand(64, generator=gen)      # (two draws the removed statistics checks took: dy .. cc keep their values)
     xg, xbuf = guarded_x(x)
     zb = z_eng.bfloat16().cuda()
-    w, scale, shift = w.cuda(), scale.cuda(), shift.cuda()
+    scale, shift = scale.cuda(), shift.cuda()
     z64 = zb.double()
     g64, ties, nonpos = first_argmax_g(z64 * scale.double() + shift.double(), dy.double())
-    if recompute:
+    if exact:
         assert ties >= 4 and nonpos >= 4, (ties, nonpos)           # the data really hold tied maxima and windows without a positive one
     else:
         assert ties == 0
@@ -418,18 +410,12 @@ def run_pooled_family(L, env, tag, Lx, B, x, w, z_eng, scale, shift, gen, recomp
     dz64, dabs = terms[0] + terms[1] + terms[2], terms[0].abs() + terms[1].abs() + terms[2].abs()
     dw_ref, dw_S = torch.einsum("btk,btc->kc", Pm, dz64), torch.einsum("btk,btc->kc", Pa, dabs)
     dw_H = torch.einsum("btk,btc->kc", Pa, bf16_half_ulp(dz64.abs() + 2 * U * dabs))       # the one bf16 rounding of dz
-    g1_ref, g1_S = torch.einsum("btk,btc->kc", Pm, gb), torch.einsum("btk,btc->kc", Pa, gb.abs())
-    xhat = (zf - mean.double()) * invstd.double()
-    st_ref = torch.stack([gb.sum((0, 1)), (gb * xhat).sum((0, 1))])
-    st_S = torch.stack([gb.abs().sum((0, 1)), (gb * xhat).abs().sum((0, 1))])
     regw = dw_regions(Lx, L1)
     G = Guards()
     for blocks in BLOCKS:
         env.set(SED_M5_BLOCKS=blocks)
         npt, tpb = nparts_and_tpb(lib, B, Lx, blocks)
         g_dw = dw_H + SAFE * (32 * tpb + 5) * U * dw_S
-        c_g1 = SAFE * (32 * tpb + 4) * U
-        c_st = torch.tensor([SAFE * (4 * tpb + 32) * U, SAFE * (4 * tpb + 35) * U], device="cuda", dtype=torch.float64).view(2, 1)
 
         def dw_of(part, what):
             assert part.shape == (npt, 80, 64)
@@ -440,55 +426,18 @@ def run_pooled_family(L, env, tag, Lx, B, x, w, z_eng, scale, shift, gen, recomp
                 "sed_m5_conv1_wgrad_fused_pool")
         G.intact()
         gate_check("conv1_wgrad_fused_pool", tag, dw_of(ws, "wgrad_fused_pool"), dw_ref, g_dw, regw)
-        sp, g1p = G.new((npt, 2, 64)), G.new((npt, 80, 64))
-        L.check(lib.sed_m5_conv1_bwd_stats_g1(BF16, P(xg), P(dy), P(zb), P(scale), P(shift), P(mean), P(invstd), P(sp), P(g1p), B, Lx, st),
-                "sed_m5_conv1_bwd_stats_g1")
-        G.intact()
-        g1 = dw_of(g1p, "bwd_stats_g1")
-        gate_check("conv1_bwd_stats_g1", f"{tag} G1", g1, g1_ref, c_g1 * g1_S, regw)
-        gate_check("conv1_bwd_stats_g1", f"{tag} stats", sum_rows(sp, "bwd_stats_g1 stats"), st_ref, c_st * st_S)
-        if not recompute:
-            continue
-        ws = G.new((npt, 80, 64))
-        L.check(lib.sed_m5_conv1_wgrad_fused_pool_x(BF16, P(xg), P(w), P(dy), P(scale), P(shift), P(ca), P(cb), P(cc), P(ws), B, Lx, st),
-                "sed_m5_conv1_wgrad_fused_pool_x")
-        G.intact()
-        gate_check("conv1_wgrad_fused_pool_x", tag, dw_of(ws, "wgrad_fused_pool_x"), dw_ref, g_dw, regw)
-        pp = G.new((npt, 2, 64))
-        L.check(lib.sed_m5_conv1_pool_bwd_stats(BF16, P(xg), P(w), P(dy), P(scale), P(shift), P(mean), P(invstd), P(pp), B, Lx, st),
-                "sed_m5_conv1_pool_bwd_stats")
-        G.intact()
-        gate_check("conv1_pool_bwd_stats", tag, sum_rows(pp, "pool_bwd_stats"), st_ref, c_st * st_S)
-        # the algebraic form: ca*G1 + cb*(w . Gram) + cc*Sp, from this grid's G1 and Gram
-        nf = int(lib.sed_m5_conv1_gram_floats())
-        gp = G.new((npt, nf))
-        L.check(lib.sed_m5_conv1_gram(P(xg), P(gp), B, Lx, st), "sed_m5_conv1_gram")
-        G.intact()
-        gram = sum_rows(gp, "gram").float()
-        g1in = torch.full((80, 64), float("nan"), device="cuda")    # row 79: unspecified, so the consumer must not read it
-        g1in[:79] = g1.float()
-        dwc = G.new((64, 79))
-        L.check(lib.sed_m5_conv1_wgrad_combine(P(g1in), P(gram), P(w), P(ca), P(cb), P(cc), P(dwc), st), "sed_m5_conv1_wgrad_combine")
-        G.intact()
-        wq = rbf(w)
-        SG, SSp = torch.einsum("btk,btj->kj", Pa, Pa), Pa.sum((0, 1))
-        wG = torch.einsum("ck,kj->jc", wq, torch.einsum("btk,btj->kj", Pm, Pm))
-        mag = ca.double().abs() * g1_ref.abs() + cb.double().abs() * wG.abs() + cc.double().abs() * Pm.sum((0, 1)).abs().view(-1, 1)
-        gate = (ca.double().abs() * c_g1 * g1_S + cb.double().abs() * c_g1 * torch.einsum("ck,kj->jc", wq.abs(), SG)
-                + cc.double().abs() * SAFE * (16 * tpb + 9) * U * SSp.view(-1, 1) + SAFE * U * mag)
-        gate_check("conv1 algebraic dW", tag, dwc.t(), dw_ref, gate, regw)
     assert bool(torch.isnan(xbuf[:XPAD]).all()) and bool(torch.isnan(xbuf[-XPAD:]).all())
 
 
-# ---- 2. kernels that decide on a recomputed z (and the exact-tie case of the stored-z forms) --------------------------------------
+# ---- 2. the pooled weight gradient deciding on exact data: genuine ties and non-positive windows -------------------------------------
 @pytest.mark.parametrize("B", [8, 16])
 @pytest.mark.parametrize("Lx", LENGTHS)
 def test_conv1_decisions_on_exact_z(L, monkeypatch, Lx, B):
     gen = torch.Generator().manual_seed(200 + 7 * Lx + B)
-    x, w, z, scale, shift = exact_case(B, Lx, gen)
+    x, _, z, scale, shift = exact_case(B, Lx, gen)
     env = Env(L, monkeypatch)
     try:
-        run_pooled_family(L, env, "exact", Lx, B, x, w, to_eng(z), scale, shift, gen, recompute=True)
+        run_pooled_family(L, env, "exact", Lx, B, x, to_eng(z), scale, shift, gen, exact=True)
     finally:
         env.restore()
 
@@ -535,59 +484,12 @@ def test_conv1_weight_gradients(L, monkeypatch, Lx, B):
         assert bool(torch.isnan(xbuf[:XPAD]).all()) and bool(torch.isnan(xbuf[-XPAD:]).all())
         # the stored-z pooled forms on separated pre-activations (no decision within rounding of a tie or of zero)
         z, scale, shift = pool_case(B, L1, gen)
-        run_pooled_family(L, env, "separated", Lx, B, x, torch.zeros(64, 79), z, scale, shift, gen, recompute=False)
+        run_pooled_family(L, env, "separated", Lx, B, x, z, scale, shift, gen, exact=False)
     finally:
         env.restore()
 
 
-# ---- 4. the Gram kernel, every entry, probed through the combine kernel's unpacking ---------------------------------------------
-@pytest.mark.parametrize("B", [8, 16])
-@pytest.mark.parametrize("Lx", LENGTHS)
-def test_conv1_gram_every_entry(L, monkeypatch, Lx, B):
-    lib, P, st = L.lib(), L.ptr, _stream()
-    gen = torch.Generator().manual_seed(400 + 7 * Lx + B)
-    L1 = conv_len(Lx)
-    xg, xbuf = guarded_x(torch.randn(B, Lx, generator=gen) * 0.3)
-    Pm = patches(rbf(xg), L1)
-    Pa = Pm.abs()
-    G_ref, G_S = torch.einsum("btk,btj->kj", Pm, Pm), torch.einsum("btk,btj->kj", Pa, Pa)
-    Sp_ref, Sp_S = Pm.sum((0, 1)), Pa.sum((0, 1))
-    nf = int(lib.sed_m5_conv1_gram_floats())
-    zero, one = torch.zeros(64, device="cuda"), torch.ones(64, device="cuda")
-    g1 = torch.zeros(80, 64, device="cuda")
-    g1[79] = float("nan")                                            # tap row 79: the combine kernel must not read it
-    env, G = Env(L, monkeypatch), Guards()
-    try:
-        for blocks in BLOCKS:
-            env.set(SED_M5_BLOCKS=blocks)
-            npt, tpb = nparts_and_tpb(lib, B, Lx, blocks)
-            gp = G.new((npt, nf))
-            L.check(lib.sed_m5_conv1_gram(P(xg), P(gp), B, Lx, st), "sed_m5_conv1_gram")
-            G.intact()
-            gram = sum_rows(gp, "gram").float()
-            got = torch.empty(79, 79, device="cuda")                 # G[k'][k], both triangles
-            for first in (0, 64):
-                w = torch.zeros(64, 79, device="cuda")
-                nk = min(64, 79 - first)
-                w[torch.arange(nk), first + torch.arange(nk)] = 1.0
-                dw = G.new((64, 79))
-                L.check(lib.sed_m5_conv1_wgrad_combine(P(g1), P(gram), P(w), P(zero), P(one), P(zero), P(dw), st), "combine (Gram probe)")
-                G.intact()
-                assert not bool(torch.isnan(dw).any())
-                got[first:first + nk] = dw[:nk]
-                assert bool((dw[nk:] == 0).all()), "a channel with zero weights got a Gram term"
-            gate_check("conv1_gram", "G", got, G_ref, SAFE * (32 * tpb + 4) * U * G_S)
-            dw = G.new((64, 79))
-            L.check(lib.sed_m5_conv1_wgrad_combine(P(g1), P(gram), P(torch.zeros(64, 79, device="cuda")), P(zero), P(zero), P(one), P(dw), st),
-                    "combine (Sp probe)")
-            G.intact()
-            gate_check("conv1_gram", "Sp", dw, Sp_ref.expand(64, 79), SAFE * (16 * tpb + 9) * U * Sp_S.expand(64, 79))
-    finally:
-        env.restore()
-    assert bool(torch.isnan(xbuf[:XPAD]).all()) and bool(torch.isnan(xbuf[-XPAD:]).all())
-
-
-# ---- 5. MaxPool1d(4) kernels on a given z ----------------------------------------------------------------------------------------
+# ---- 4. MaxPool1d(4) kernels on a given z ----------------------------------------------------------------------------------------
 def maxpool_case(N, H, Cp, gen):
     """exact data: z = k/8, scale = +-2^k, shift = (j + 1/2)/8 on even channels and j/8 on odd ones (a pre-activation of exactly 0 can
     occur there); one planted window with a tied positive maximum and one whose maximum pre-activation is exactly 0."""
@@ -723,7 +625,7 @@ def test_maxpool4_pooled_stats_flag(L, dt):
     assert flag.tolist() == [0, 0x5A5A5A5A], "the flag is reset after the conditional pass"
 
 
-# ---- 6. head -----------------------------------------------------------------------------------------------------------------------
+# ---- 5. head -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("C,Cp", [(256, 256), (40, 64), (300, 304), (512, 512)])
 @pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
 def test_head(L, dt, C, Cp):
