@@ -993,6 +993,53 @@ int sed_pcen_bwd(const float* x, const float* mean, const float* std, const floa
                  double gain, const float* gy, float* dx, float* dtheta, void* workspace, int B, int T, int F,
                  void* stream);
 
+/* ---- attention pooling head: csrc/sed_attn.hip -------------------------------------------------
+ * Beside event_fc a second linear layer att_fc scores every frame per class (decision-level attention
+ * of PANNs / the DCASE task-4 baseline CRNN); the clip probability is the attention-weighted average of
+ * the frame probabilities, the weights a softmax over time, per class.  pre, att [B][t][K] fp32 are the
+ * frame and attention logits before interpolate(): N = min(t*ratio, Tt) virtual frames, row i stands for
+ * c_i = clamp(N - i*ratio, 0, ratio) of them; rows with c_i = 0 take no part, not in the maximum either.
+ * For one (b, k), x_i = pre, a_i = att, all in double, every result rounded once to fp32:
+ *   p_i = 1/(1+exp(-x_i)), q_i = 1/(1+exp(x_i));  e_i = exp(a_i - a_max), a_max over the rows with c_i > 0
+ *   Z = sum c_i e_i,  P = sum c_i e_i p_i / Z,  Q = sum c_i e_i q_i / Z (from its own sum)
+ *   SED_CRIT_BCE  l = -(w Y max(ln P, -100) + (1 - Y) max(ln Q, -100)),
+ *                 dl/dP = -w Y / max(P, 1e-12) + (1 - Y) / max(Q, 1e-12)
+ *   SED_CRIT_MSE  l = (P - Y)^2, dl/dP = 2 (P - Y); recall_factor is not used
+ *   loss = weight * mean of l over B*K, or over S*K for the S clips clip_sel picks (counted on the
+ *   device; S = 0: loss 0 and gradient 0);  coef = weight * grad_scale / (B*K), or / (S*K)
+ *   dpre_i = coef * dl/dP * (c_i e_i / Z) * p_i q_i
+ *   datt_i = coef * dl/dP * c_i e_i (p_i - P) / Z        (sum_i datt_i = 0 in exact arithmetic)
+ * Rows with c_i = 0 and all rows of unselected clips get exact zeros; under accumulate = 1 their dpre cells
+ * are left untouched.  Every sum is taken in a fixed order without atomics (the same bits on every run);
+ * no host synchronisation.
+ *
+ * sed_att_logits_fwd: att[r][k] = att_b[k] + sum_c m[r][c] att_w[k][c] in fp32.  m [rows][Cp] fp32 is the
+ *   mel-mean sed_head_fwd leaves behind (the padded channels [C, Cp) are not read), att_w [K][C], att
+ *   [rows][K]; C <= 2048.  One launch that reads every row of m once, whatever K is.
+ * sed_att_pool_fwd: clip_prob [B][K] = P only (inference); one launch.
+ * sed_att_loss_fwd_bwd: target / target_frames / clip_sel / criterion / clip_prob as in
+ *   sed_weak_bce_fwd_bwd_ex.  dpre and datt [B][t][K] are given together or both NULL (loss only).
+ *   accumulate = 1 adds to loss[0] and dpre (one fp32 add per element); datt is always overwritten.
+ *   workspace: sed_att_loss_ws_bytes() bytes, 8-byte aligned.  Two launches.
+ * Backward of the two linear layers through sed_head_bwd: sed_att_bwd_pack writes dcat [rows][2K] =
+ *   (dpre | datt) and wcat [2K][C] = (fc_w; att_w); sed_head_bwd on them with K' = 2K and ratio 1 gives the
+ *   feature gradient (dpre@fc_w + datt@att_w)/Wf, summed in fp32 and rounded once, and [2K][C] / [2K]
+ *   weight and bias gradients (size its workspace for 2K); sed_att_bwd_split copies those into dfc_w
+ *   [K][C], dfc_b [K], datt_w [K][C], datt_b [K].  One launch each.                                   */
+int sed_att_logits_fwd(const float* m, const float* att_w, const float* att_b, float* att, int rows, int C,
+                       int Cp, int K, void* stream);
+int sed_att_pool_fwd(const float* pre, const float* att, float* clip_prob, int B, int t, int K, int ratio,
+                     int Tt, void* stream);
+size_t sed_att_loss_ws_bytes(int B, int t, int K);
+int sed_att_loss_fwd_bwd(const float* pre, const float* att, const float* target, int target_frames,
+                         const unsigned char* clip_sel, int criterion, float* clip_prob, float* loss,
+                         float* dpre, float* datt, int accumulate, int B, int t, int K, int ratio, int Tt,
+                         float recall_factor, float weight, float grad_scale, void* workspace, void* stream);
+int sed_att_bwd_pack(const float* dpre, const float* datt, const float* fc_w, const float* att_w, float* dcat,
+                     float* wcat, int rows, int C, int K, void* stream);
+int sed_att_bwd_split(const float* dwcat, const float* dbcat, float* dfc_w, float* dfc_b, float* datt_w,
+                      float* datt_b, int C, int K, void* stream);
+
 /* ---- utilities -----------------------------------------------------------------------------*/
 /* out[i] = sum_{s<nparts} partial[s][i], i < n (fixed order: deterministic)                     */
 int sed_sum_partials(const float* partial, int nparts, size_t n, float* out, void* stream);

@@ -161,6 +161,12 @@ PROTOTYPES = {
     "sed_pcen_ws_bytes": (_Z, [_I, _I, _I]),
     "sed_pcen_fwd": (_I, [_P, _P, _P, _P, _I, _D, _D, _P, _P, _I, _I, _I, _P]),
     "sed_pcen_bwd": (_I, [_P, _P, _P, _P, _I, _D, _D, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "sed_att_logits_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sed_att_pool_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "sed_att_loss_ws_bytes": (_Z, [_I, _I, _I]),
+    "sed_att_loss_fwd_bwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
+    "sed_att_bwd_pack": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "sed_att_bwd_split": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "sed_m5_conv1_len": (_I, [_I]),
     "sed_m5_conv1_nparts": (_I, [_I, _I]),
     "sed_m5_conv1_fwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _P]),

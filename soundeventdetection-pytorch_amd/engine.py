@@ -79,6 +79,20 @@ def check_pooling(mode) -> int:
     return L.POOL_MODES[mode]
 
 
+ATT_POOLING = "att"      # the learned pooling of the attention head (csrc/sed_attn.hip); not one of the parameter-free L.POOL_MODES
+
+
+def check_clip_pooling(mode, model=None):
+    """check_pooling() that also takes the attention pooling 'att', which needs a model (or engine) built with attention=True
+    (host only).  Returns the mode's name."""
+    if mode != ATT_POOLING:
+        check_pooling(mode)
+        return mode
+    if model is not None and not getattr(model, "attention", False):
+        raise ValueError("the 'att' pooling needs a model with the attention head (attention=True / --attention_head)")
+    return mode
+
+
 @dataclass
 class _Layer:
     """One conv+BN layer of the plan."""
@@ -131,6 +145,15 @@ class _Plan:
     semi_ws: torch.Tensor = None    # workspace of the label-kind / mean-teacher losses (csrc/sed_semi.hip), allocated at their first use
     consistency: torch.Tensor = None    # (2,) the frame and clip consistency terms of the last mean-teacher loss
     teacher_clip: torch.Tensor = None   # (B, K) the teacher's pooled clip probabilities
+    att: torch.Tensor = None        # (B, t, K) attention logits of the last forward (engines with attention=True; csrc/sed_attn.hip)
+    datt: torch.Tensor = None       # (B, t, K) their gradient, written by loss_and_grad(weak=("att", ...))
+    att_pending: bool = False       # the last loss_and_grad on this plan produced datt: backward() takes the attention route
+    datt_clip: torch.Tensor = None  # (B, t, K) datt of the clip consistency term of a mean teacher, added to datt
+    att_ws: torch.Tensor = None     # workspace of sed_att_loss_fwd_bwd
+    att_dcat: torch.Tensor = None   # (B*t, 2K) dpre | datt and
+    att_wcat: torch.Tensor = None   # (2K, C) event_fc.weight; att_fc.weight: the operands of the two layers' backward through sed_head_bwd
+    att_dw: torch.Tensor = None     # (2K, C) and
+    att_db: torch.Tensor = None     # (2K,) its results, split into the four gradient tensors
 
 
 class KernelTimer:
@@ -202,8 +225,11 @@ class OptimizerExtMixin:
 class CnnEngine(OptimizerExtMixin):
     def __init__(self, classes_num: int, model_config: Sequence[Tuple[int, int]], in_channels: int = 1,
                  precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
-                 mel_bins: Optional[int] = None):
-        """head: 'fc' (Cnn_AvgPooling), 'gru' (CRNN) or 'none' (a bare stack of ConvBlocks: forward() stops at the last
+                 mel_bins: Optional[int] = None, attention: bool = False):
+        """attention: a second linear layer att_fc beside event_fc scores every frame per class (csrc/sed_attn.hip): forward()
+        also leaves the attention logits in plan.att, loss_and_grad(weak=("att", ...)) pools with them and backward() then takes
+        both layers.  False launches exactly what it always did.
+        head: 'fc' (Cnn_AvgPooling), 'gru' (CRNN) or 'none' (a bare stack of ConvBlocks: forward() stops at the last
         pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
         Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and backward() also produces the input gradient
         plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path keeps the dedicated Cin = 1
@@ -217,6 +243,9 @@ class CnnEngine(OptimizerExtMixin):
         if head == "gru" and (gru_hidden % 32 or not 32 <= gru_hidden <= 256):
             raise ValueError("gru_hidden must be a multiple of 32 in [32, 256]")
         self.head, self.Hd = head, int(gru_hidden)
+        self.attention = bool(attention)
+        if self.attention and head == "none":
+            raise ValueError("the attention head sits beside event_fc: it needs a model with a classification head")
         self.mel_bins = self.check_mel_bins(mel_bins)
         for (_, p) in model_config:
             if p not in (1, 2):
@@ -370,7 +399,9 @@ class CnnEngine(OptimizerExtMixin):
         p.loss = torch.zeros(1, **f32)
         p.loss_partial = torch.empty(max(1, (B * H * self.ratio * self.K + 255) // 256), **f32)
         Cfc = 2 * self.Hd if self.head == "gru" else Cl
-        p.head_ws = torch.empty(max(1, lib.sed_head_bwd_ws_floats(B, H, Cfc, max(1, self.K))), **f32)
+        p.head_ws = torch.empty(max(1, lib.sed_head_bwd_ws_floats(B, H, Cfc, max(1, self.K) * (2 if self.attention else 1))), **f32)
+        if self.attention:
+            self._plan_att(p, B, H, Cfc, dev)
         if self.head == "gru":
             p.gru = self._plan_gru(B, H, Cl, dev)
         p.wgrad_ws = torch.empty(max(1, max_wgrad_ws), **f32)
@@ -435,6 +466,60 @@ class CnnEngine(OptimizerExtMixin):
         return p
 
 
+    def _plan_att(self, p, B, t, C, dev):
+        """Buffers of the attention head, allocated with the plan (a captured step allocates nothing): the logits and their
+        gradients, the loss workspace, and the packed operands / results of the two layers' backward through sed_head_bwd."""
+        f32 = dict(dtype=torch.float32, device=dev)
+        K = self.K
+        p.att = torch.empty((B, t, K), **f32)
+        p.datt = torch.empty((B, t, K), **f32)
+        p.datt_clip = torch.empty((B, t, K), **f32)      # the clip consistency term's, added to datt
+        p.att_ws = torch.empty(max(1, self.lib.sed_att_loss_ws_bytes(B, t, K) // 8), dtype=torch.float64, device=dev)
+        p.att_dcat = torch.empty((B * t, 2 * K), **f32)
+        p.att_wcat = torch.empty((2 * K, C), **f32)
+        p.att_dw = torch.empty((2 * K, C), **f32)
+        p.att_db = torch.empty(2 * K, **f32)
+        p.clip_prob = torch.empty((B, K), **f32)
+        p.weak_ws = torch.empty(max(1, self.lib.sed_weak_bce_ws_bytes(B, t, K) // 8), dtype=torch.float64, device=dev)
+
+    def _head_operands(self, p):
+        """(dtype, m, rows, Wf, C, Cp, feature gradient) of the linear layer(s) on top: the mel-mean the head forward left behind"""
+        if self.head == "gru":
+            g = p.gru
+            return L.SED_F32, g["fc_m"], g["R"], 1, 2 * self.Hd, 2 * self.Hd, g["dhseq"]
+        Cl = self.cfg[-1][0]
+        return self.dt, p.m, p.B * p.t_out, p.w_out, Cl, pad32(Cl), p.dy[len(self.cfg) - 1]
+
+    def _att_forward(self, p, P):
+        _, m, rows, _, C, Cp, _ = self._head_operands(p)
+        self._k("sed_att_logits_fwd", self.lib.sed_att_logits_fwd, L.ptr(m), L.ptr(P["att_fc.weight"]), L.ptr(P["att_fc.bias"]),
+                L.ptr(p.att), rows, C, Cp, self.K, _stream())
+
+    def _att_head_backward(self, p, P, G, src, ratio, on_group_done):
+        """The head backward of an engine with attention.  After loss_and_grad(weak=("att", ...)): both layers through ONE
+        sed_head_bwd on the packed [rows][2K] gradients and [2K][C] weight -- the feature gradient is (dpre@fc_w + datt@att_w)/Wf,
+        summed in fp32 and rounded once.  Otherwise event_fc's backward as always, and att_fc's gradient is zero: the flat
+        gradient buffer is overwritten every step and must not keep stale values."""
+        lib, st = self.lib, _stream()
+        dt, m, rows, Wf, C, Cp, dfeat = self._head_operands(p)
+        gw, gb = G["att_fc.weight"], G["att_fc.bias"]
+        if p.att_pending:
+            self._k("sed_att_bwd_pack", lib.sed_att_bwd_pack, L.ptr(p.dpre), L.ptr(p.datt), L.ptr(P["event_fc.weight"]),
+                    L.ptr(P["att_fc.weight"]), L.ptr(p.att_dcat), L.ptr(p.att_wcat), rows, C, self.K, st)
+            self._k("sed_head_bwd", lib.sed_head_bwd, dt, L.ptr(p.att_dcat), L.ptr(m), L.ptr(p.att_wcat), L.ptr(p.att_dw),
+                    L.ptr(p.att_db), L.ptr(dfeat), L.ptr(p.head_ws), p.B, p.t_out, Wf, C, Cp, 2 * self.K, 1, st)
+            self._k("sed_att_bwd_split", lib.sed_att_bwd_split, L.ptr(p.att_dw), L.ptr(p.att_db), L.ptr(G["event_fc.weight"]),
+                    L.ptr(G["event_fc.bias"]), L.ptr(gw), L.ptr(gb), C, self.K, st)
+        else:
+            self._k("sed_head_bwd", lib.sed_head_bwd, dt, L.ptr(src), L.ptr(m), L.ptr(P["event_fc.weight"]),
+                    L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(dfeat), L.ptr(p.head_ws), p.B, p.t_out, Wf,
+                    C, Cp, self.K, ratio, st)
+            gw.zero_()
+            gb.zero_()
+        if on_group_done is not None:
+            on_group_done("att_fc")
+            on_group_done("event_fc")
+
     def _plan_gru(self, B, t, C, dev):
         """Buffers of the recurrent head; R = B*t rows."""
         lib, Hd = self.lib, self.Hd
@@ -487,6 +572,8 @@ class CnnEngine(OptimizerExtMixin):
                 L.ptr(g["hseq"]), L.ptr(g["saved"]) if training else None, B, t, Hd, st)
         self._k("sed_head_fwd", lib.sed_head_fwd, L.SED_F32, L.ptr(g["hseq"]), L.ptr(P["event_fc.weight"]),
                 L.ptr(P["event_fc.bias"]), L.ptr(g["fc_m"]), L.ptr(p.pre), B, t, 1, 2 * Hd, 2 * Hd, self.K, st)
+        if self.attention:
+            self._att_forward(p, P)
         self._tag = ""
 
     def _gru_backward(self, p, P, G, src, ratio, dfeat, on_group_done):
@@ -495,11 +582,14 @@ class CnnEngine(OptimizerExtMixin):
         Cl = self.cfg[-1][0]
         R = g["R"]
         self._tag = "gru"
-        self._k("sed_head_bwd", lib.sed_head_bwd, L.SED_F32, L.ptr(src), L.ptr(g["fc_m"]), L.ptr(P["event_fc.weight"]),
-                L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(g["dhseq"]), L.ptr(p.head_ws), B, t, 1,
-                2 * Hd, 2 * Hd, self.K, ratio, st)
-        if on_group_done is not None:
-            on_group_done("event_fc")
+        if self.attention:
+            self._att_head_backward(p, P, G, src, ratio, on_group_done)
+        else:
+            self._k("sed_head_bwd", lib.sed_head_bwd, L.SED_F32, L.ptr(src), L.ptr(g["fc_m"]), L.ptr(P["event_fc.weight"]),
+                    L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(g["dhseq"]), L.ptr(p.head_ws), B, t, 1,
+                    2 * Hd, 2 * Hd, self.K, ratio, st)
+            if on_group_done is not None:
+                on_group_done("event_fc")
         self._k("sed_gru_seq_bwd", lib.sed_gru_seq_bwd, dt, L.ptr(g["dhseq"]), L.ptr(g["hseq"]), L.ptr(g["saved"]),
                 L.ptr(g["pack_b"]), L.ptr(g["dgi"]), L.ptr(g["dgh"]), B, t, Hd, st)
         ks = max(1, min(g["ksplit"], R // 256))
@@ -579,6 +669,7 @@ class CnnEngine(OptimizerExtMixin):
         p.x_ref = x
         p.trained = training
         p.keep = bool(keep_for_grad)
+        p.att_pending = False
         keep_mask = None
         if p.keep and p.c1_mode:
             if p.c1_mask is None and getattr(p, "c1_mask_keep", None) is None:
@@ -675,6 +766,8 @@ class CnnEngine(OptimizerExtMixin):
             return p
         self._k("sed_head_fwd", self.lib.sed_head_fwd, dt, L.ptr(prev), L.ptr(P["event_fc.weight"]), L.ptr(P["event_fc.bias"]), L.ptr(p.m),
                                  L.ptr(p.pre), B, p.t_out, p.w_out, Cl, pad32(Cl), self.K, st)
+        if self.attention:
+            self._att_forward(p, P)
         return p
 
     def interpolate(self, p: _Plan) -> torch.Tensor:
@@ -683,10 +776,14 @@ class CnnEngine(OptimizerExtMixin):
         return out
 
     def loss_and_grad(self, p: _Plan, target: torch.Tensor, recall_factor: float, need_grad: bool = True,
-                      grad_scale: float = 1.0, weak=None, kind=None, teacher_pre=None, consistency=None) -> torch.Tensor:
+                      grad_scale: float = 1.0, weak=None, kind=None, teacher_pre=None, consistency=None,
+                      teacher_att=None) -> torch.Tensor:
         """WeightedBCE on the virtually interpolated logits; fills plan.dpre; returns plan.loss (1,).
         weak: None, or (mode, weight, only) -- the pooled clip-level loss of csrc/sed_weak.hip, mode one of max / mean / linear /
-        exp, scaled by weight.  only=False: the strong kernel runs as always, then the weak loss of the same (B, T, K) target is
+        exp, scaled by weight -- or "att" on an engine with attention=True, the attention pooling of csrc/sed_attn.hip, which
+        also fills plan.datt; backward() then takes both linear layers (with a teacher, teacher_att is its plan.att, and the clip
+        consistency term pools the teacher with its own attention).
+        only=False: the strong kernel runs as always, then the weak loss of the same (B, T, K) target is
         added on top of plan.loss and plan.dpre.  only=True: the weak loss alone; the target may then be (B, K) clip labels.
         kind: None, or an integer (B,) device tensor, 0 = strongly labelled, 1 = weakly labelled, 2 = unlabelled: the strong term
         then takes the clips with kind == 0 (sed_bce_sel_fwd_bwd) and the weak term those with kind <= 1 (sed_weak_bce_fwd_bwd_ex);
@@ -696,6 +793,7 @@ class CnnEngine(OptimizerExtMixin):
         consistency terms over all clips, added on top: the frame MSE (csrc/sed_semi.hip) and, with a weak pooling, the MSE of
         the pooled clip probabilities.  Their values land in plan.consistency (2,): frame, clip.
         All of them None launches exactly what it always did."""
+        p.att_pending = False       # set below only where datt is written: backward() follows the LAST loss on this plan
         if weak is None and kind is None and teacher_pre is None:
             if not (target.is_cuda and target.dtype == torch.float32 and target.dim() == 3):
                 raise ValueError("target must be a float32 CUDA tensor (B, T, K)")
@@ -706,7 +804,10 @@ class CnnEngine(OptimizerExtMixin):
             raise ValueError("the weak-label loss needs a model with a classification head" if weak is not None else
                              "label kinds and the mean teacher need a model with a classification head")
         mode, weight, only = weak if weak is not None else (None, 0.0, False)
-        mode_id = check_pooling(mode) if weak is not None else None
+        att = weak is not None and mode == ATT_POOLING
+        if att and not self.attention:
+            raise ValueError("the 'att' pooling needs a model with the attention head (attention=True)")
+        mode_id = check_pooling(mode) if weak is not None and not att else None
         if not (target.is_cuda and target.dtype == torch.float32 and target.dim() in ((2, 3) if only else (3,))):
             raise ValueError("target must be a float32 CUDA tensor (B, T, K) or, for the weak loss alone, (B, K) clip labels")
         if target.shape[0] != p.B or target.shape[-1] != self.K:
@@ -724,6 +825,10 @@ class CnnEngine(OptimizerExtMixin):
                 raise ValueError(f"teacher_pre must be a contiguous float32 CUDA tensor {tuple(p.pre.shape)}")
             if consistency is None or not (0.0 <= float(consistency) < float("inf")):
                 raise ValueError(f"teacher_pre needs a finite consistency weight >= 0 (got {consistency!r})")
+            if att and not (teacher_att is not None and teacher_att.is_cuda and teacher_att.dtype == torch.float32
+                            and teacher_att.shape == p.pre.shape and teacher_att.is_contiguous()):
+                raise ValueError("the 'att' pooling with a teacher needs teacher_att, a contiguous float32 CUDA tensor "
+                                 f"{tuple(p.pre.shape)}")
         if kind is not None or teacher_pre is not None:
             self._semi_bufs(p)
         dpre = L.ptr(p.dpre) if need_grad else None
@@ -736,7 +841,13 @@ class CnnEngine(OptimizerExtMixin):
             else:
                 self._k("sed_bce_sel_fwd_bwd", self.lib.sed_bce_sel_fwd_bwd, L.ptr(p.pre), L.ptr(target), L.ptr(sel_strong), L.ptr(p.loss),
                         dpre, 0, *dims, float(recall_factor), 1.0, float(grad_scale), L.ptr(p.semi_ws), _stream())
-        if weak is not None:
+        datt = L.ptr(p.datt) if need_grad and att else None
+        if att:
+            self._k("sed_att_loss_fwd_bwd", self.lib.sed_att_loss_fwd_bwd, L.ptr(p.pre), L.ptr(p.att), L.ptr(target), frames,
+                    L.ptr(sel_weak), L.CRIT_BCE, L.ptr(p.clip_prob), L.ptr(p.loss), dpre, datt, 0 if only else 1, *dims,
+                    float(recall_factor), float(weight), float(grad_scale), L.ptr(p.att_ws), _stream())
+            p.att_pending = bool(need_grad)
+        elif weak is not None:
             self._weak_bufs(p)
             if kind is None:
                 self._k("sed_weak_bce_fwd_bwd", self.lib.sed_weak_bce_fwd_bwd, L.ptr(p.pre), L.ptr(target), frames, L.ptr(p.clip_prob),
@@ -754,7 +865,17 @@ class CnnEngine(OptimizerExtMixin):
         self._k("sed_frame_mse_fwd_bwd", self.lib.sed_frame_mse_fwd_bwd, L.ptr(p.pre), L.ptr(teacher_pre), None, L.ptr(p.consistency),
                 dpre, 1, *dims, cw, float(grad_scale), L.ptr(p.semi_ws), _stream())
         p.loss.add_(p.consistency[0:1])
-        if weak is not None:
+        if att:
+            # the teacher's clip probabilities pooled with its own attention; the student's MSE term against them
+            self._k("sed_att_pool_fwd", self.lib.sed_att_pool_fwd, L.ptr(teacher_pre), L.ptr(teacher_att), L.ptr(p.teacher_clip), *dims,
+                    _stream())
+            self._k("sed_att_loss_fwd_bwd", self.lib.sed_att_loss_fwd_bwd, L.ptr(p.pre), L.ptr(p.att), L.ptr(p.teacher_clip), 0, None,
+                    L.CRIT_MSE, L.ptr(p.clip_prob), L.ptr(p.consistency[1:2]), dpre, L.ptr(p.datt_clip) if need_grad else None, 1,
+                    *dims, float(recall_factor), cw, float(grad_scale), L.ptr(p.att_ws), _stream())
+            if need_grad:
+                p.datt.add_(p.datt_clip)          # (datt is overwritten by every call: one add per element, like the loss terms)
+            p.loss.add_(p.consistency[1:2])
+        elif weak is not None:
             self._k("sed_clip_pool_fwd", self.lib.sed_clip_pool_fwd, L.ptr(teacher_pre), L.ptr(p.teacher_clip), p.B, p.t_out, self.K,
                     self.ratio, Tt, mode_id, _stream())
             self._k("sed_weak_bce_fwd_bwd_ex", self.lib.sed_weak_bce_fwd_bwd_ex, L.ptr(p.pre), L.ptr(p.teacher_clip), 0, None, L.CRIT_MSE,
@@ -785,10 +906,16 @@ class CnnEngine(OptimizerExtMixin):
 
     def clip_probs(self, p: _Plan, mode: str) -> torch.Tensor:
         """(B, K) clip probabilities of the last forward's logits, pooled over all t_out * ratio output frames by `mode` (max /
-        mean / linear / exp).  Returns plan.clip_prob: valid until the next call on this plan."""
-        mode_id = check_pooling(mode)
+        mean / linear / exp, or "att": the attention pooling of an engine with attention=True).  Returns plan.clip_prob: valid
+        until the next call on this plan."""
         if self.head == "none":
+            check_clip_pooling(mode)
             raise ValueError("clip_probs needs a model with a classification head")
+        if check_clip_pooling(mode, self) == ATT_POOLING:
+            self._k("sed_att_pool_fwd", self.lib.sed_att_pool_fwd, L.ptr(p.pre), L.ptr(p.att), L.ptr(p.clip_prob), p.B, p.t_out, self.K,
+                    self.ratio, p.t_out * self.ratio, _stream())
+            return p.clip_prob
+        mode_id = check_pooling(mode)
         self._weak_bufs(p)
         self._k("sed_clip_pool_fwd", self.lib.sed_clip_pool_fwd, L.ptr(p.pre), L.ptr(p.clip_prob), p.B, p.t_out, self.K, self.ratio,
                 p.t_out * self.ratio, mode_id, _stream())
@@ -805,6 +932,9 @@ class CnnEngine(OptimizerExtMixin):
         generic_first path always fills plan.dx).  An eval-mode forward (BatchNorm with running statistics) can be differentiated
         when it ran with keep_for_grad=True; so must a C1-mode training forward whose backward takes need_dx.  Without need_dx, a
         training-mode backward launches exactly what it did before these two kinds existed."""
+        if dlogits is not None and p.att_pending:
+            raise RuntimeError("backward(dlogits=...) after loss_and_grad(weak=('att', ...)): the attention gradient of that loss is "
+                               "pending on this plan (run backward() without dlogits, or a new forward)")
         eval_bwd = not p.trained
         if eval_bwd and not p.keep:
             raise RuntimeError("backward() needs a training-mode forward (batch statistics) or a forward with keep_for_grad=True")
@@ -873,6 +1003,8 @@ class CnnEngine(OptimizerExtMixin):
             pass                      # the caller filled plan.dy[-1] (gradient of the last pooled block output)
         elif self.head == "gru":
             self._gru_backward(p, P, G, src, ratio, p.dy[nb - 1], on_group_done)
+        elif self.attention:
+            self._att_head_backward(p, P, G, src, ratio, on_group_done)
         else:
             self._k("sed_head_bwd", self.lib.sed_head_bwd, dt, L.ptr(src), L.ptr(p.m), L.ptr(P["event_fc.weight"]),
                                      L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(p.dy[nb - 1]),

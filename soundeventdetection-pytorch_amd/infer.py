@@ -46,7 +46,7 @@ def build_parser():
                         "(default: --threshold, plain thresholding)")
     p.add_argument("--max_gap", type=float, default=0.0, help="merge events at most this many seconds apart (default 0 = off)")
     p.add_argument("--min_event", type=float, default=0.0, help="drop events shorter than this many seconds (default 0 = off)")
-    p.add_argument("--clip_pooling", default=None, choices=["max", "mean", "linear", "exp"],
+    p.add_argument("--clip_pooling", default=None, choices=["max", "mean", "linear", "exp", "att"],
                    help="also print and write 'clip_probs' (classes,): the frame probabilities pooled over the recording into one "
                         "clip probability per class, the way the weak-label loss pools them")
     p.add_argument("--teacher", action="store_true",
@@ -102,13 +102,13 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     (n, 3) = (class, onset_s, offset_s) and 'event_frames' (n, 3) int are decoded on the device.  With all four at their defaults
     they are the runs of probabilities > threshold, and 'decisions' / 'onset_frames' are what they always were; otherwise those two
     follow the decoded events.
-    clip_pooling: None, or max / mean / linear / exp: the result gains 'clip_probs' (channels, classes), the frame probabilities
+    clip_pooling: None, or max / mean / linear / exp, or att for a checkpoint with the attention head (att_fc.*): the result gains 'clip_probs' (channels, classes), the frame probabilities
     pooled over the recording on the device (CnnEngine.clip_probs).
     teacher: load the checkpoint's 'teacher' entry (the mean teacher of a --mean_teacher training) in place of 'model'."""
     import dataclasses
     if clip_pooling is not None:
-        from .engine import check_pooling
-        check_pooling(clip_pooling)
+        from .engine import check_clip_pooling
+        check_clip_pooling(clip_pooling)        # ('att' against the checkpoint's keys below)
     from .dataset.dataset_utils import read_multichannel_audio
     from .dataset.spectogram.preprocess import LogMelFrontEnd
     from .dataset.spectogram.spectogram_configs import REF_NATIVE
@@ -133,8 +133,11 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     if "frontend.log_alpha" in weights:       # a --pcen training: the layer is rebuilt from the checkpoint's own keys
         from .models.frontend_layers import PCEN
         frontend = PCEN.from_state_dict(weights, prefix="frontend.")
+    attention = "att_fc.weight" in weights    # an --attention_head training: the head is rebuilt from the checkpoint's own keys
+    if clip_pooling == "att" and not attention:
+        raise ValueError(f"--clip_pooling att needs a checkpoint with the attention head: {ckpt} holds no 'att_fc.weight'")
     model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel,
-                           frontend=frontend).to(dev)
+                           frontend=frontend, attention=attention).to(dev)
     model.set_precision(precision)
     model.load_state_dict(weights)
     model.eval()

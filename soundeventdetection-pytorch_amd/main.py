@@ -107,9 +107,13 @@ def build_weak_parser():
                    help="this build only: train from clip-level labels -- the frame probabilities are pooled over time and the "
                         "loss is taken against the clip label (the maximum of the frame labels); 'both' adds it to the frame-level "
                         "loss, 'only' replaces that loss")
-    p.add_argument("--weak_pooling", default="linear", choices=["max", "mean", "linear", "exp"],
-                   help="--weak_labels: the pooling function (linear = linear softmax, exp = exponential softmax)")
+    p.add_argument("--weak_pooling", default="linear", choices=["max", "mean", "linear", "exp", "att"],
+                   help="--weak_labels: the pooling function (linear = linear softmax, exp = exponential softmax, att = the learned "
+                        "attention pooling of --attention_head)")
     p.add_argument("--weak_weight", type=float, default=1.0, help="--weak_labels: factor on the clip-level loss (> 0)")
+    p.add_argument("--attention_head", action="store_true", default=False,
+                   help="this build only: build the model with the attention pooling head, a second linear layer att_fc beside "
+                        "event_fc whose softmax over time weighs the frame probabilities of a clip (pooling att)")
     return p
 
 
@@ -136,7 +140,7 @@ def build_ranking_parser():
     p.add_argument("--eval_ranking", action="store_true", default=False,
                    help="this build only: the periodic evaluation also logs corpus-level AP, ROC-AUC, d' and the best-F1 threshold "
                         "per class, sorted and scanned on the GPU")
-    p.add_argument("--eval_clip_pooling", default=None, choices=["max", "mean", "linear", "exp"],
+    p.add_argument("--eval_clip_pooling", default=None, choices=["max", "mean", "linear", "exp", "att"],
                    help="--eval_ranking: also rank the recordings by their pooled clip probability against the clip label")
     return p
 
@@ -338,7 +342,8 @@ def get_spectogram_dataset_model_and_criterion(args, device):
                                     preprocessed_mode=args.preprocess_mode, cfg=cfg, device=device,
                                     spec_augment=spec_augment_config(args))
     frontend = build_pcen(args, n_mel, getattr(dataset, "mean", None), getattr(dataset, "std", None))
-    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel, frontend=frontend)
+    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel, frontend=frontend,
+                           attention=bool(getattr(args, "attention_head", False)))
     model.set_precision(args.precision)
     if args.ckpt != "":
         checkpoint = torch.load(args.ckpt, map_location=device)
@@ -409,6 +414,13 @@ def validate_args(args):
                              "(the M5 model has no time axis in its output)")
         from .train import check_weak_options
         check_weak_options(**weak_options(args))
+    att_head = bool(getattr(args, "attention_head", False))
+    if att_head and args.train_features.lower() == "waveform":
+        raise ValueError("--attention_head sits beside the frame-wise head: it needs --train_features Spectogram "
+                         "(the M5 model has no time axis in its output)")
+    for flag, value in (("--weak_pooling", weak_options(args).get("weak_pooling")), ("--eval_clip_pooling", getattr(args, "eval_clip_pooling", None))):
+        if value == "att" and not att_head:
+            raise ValueError(f"{flag} att pools with the attention head: it needs --attention_head")
     semi = semi_options(args)
     kinds = parse_label_kinds(getattr(args, "label_kinds", None))
     if getattr(args, "eval_teacher", False) and not semi:

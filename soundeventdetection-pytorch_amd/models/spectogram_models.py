@@ -2,7 +2,7 @@
 Cnn_AvgPooling :163-230, interpolate :9-22, init_layer/init_bn :25-40) whose arithmetic runs in
 libsed_hip.so on an MI355X.  Same constructor signatures, forward() shapes and state_dict keys
 (`conv_blocks.{i}.conv{1,2}.weight`, `conv_blocks.{i}.bn{1,2}.{weight,bias,running_mean,
-running_var,num_batches_tracked}`, `event_fc.{weight,bias}`), so checkpoints interchange with the
+running_var,num_batches_tracked}`, `event_fc.{weight,bias}`; with attention=True also `att_fc.{weight,bias}`), so checkpoints interchange with the
 reference's `train.py:123-128` / `main.py:37-39`.
 
 There is no CPU path: calling forward() on a CPU module raises.
@@ -204,8 +204,13 @@ class _ModelFunction(torch.autograd.Function):
 
 
 class Cnn_AvgPooling(nn.Module):
-    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, mel_bins=None, frontend=None):
-        '''mel_bins: the declared input width (mel-bin count).  None: the specialised widths only (8 / 16 / 32 / 64 at every
+    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, mel_bins=None, frontend=None,
+                 attention=False):
+        '''attention: True registers att_fc, a second linear layer beside event_fc that scores every frame per class (the
+        attention pooling head, csrc/sed_attn.hip; pooling "att" of FusedTrainer / clip_probs).  forward() is unchanged: it
+        returns the frame logits, and its autograd backward gives att_fc a zero gradient.  False draws no random number and adds
+        no key to the state_dict.
+        mel_bins: the declared input width (mel-bin count).  None: the specialised widths only (8 / 16 / 32 / 64 at every
         block), as before.  An integer F in [1, 256]: inputs of width F only; blocks at other widths run the width-general
         kernels.  The parameters do not depend on it: a checkpoint loads into a model of any declared width.
         frontend: None, or a models.frontend_layers.PCEN applied to the input before the first block (submodule `frontend`,
@@ -213,6 +218,7 @@ class Cnn_AvgPooling(nn.Module):
         state_dict and launches nothing new.'''
         super().__init__()
         self.mel_bins = CnnEngine.check_mel_bins(mel_bins)
+        self.attention = bool(attention)
         self.frontend = self._check_frontend(frontend, self.mel_bins)      # before conv_blocks: first in named_parameters()
         self.model_config = model_config
         self.classes_num = classes_num
@@ -225,6 +231,9 @@ class Cnn_AvgPooling(nn.Module):
         self.conv_blocks = torch.nn.Sequential(*blocks)
         self._build_head(model_config[-1][0], classes_num)
         self.init_weights()
+        if self.attention:          # after event_fc, and after its init: the other parameters draw what they always drew
+            self.att_fc = _LinearParams(self.event_fc.in_features, classes_num)
+            init_layer(self.att_fc)
         self.engine = self._make_engine(self.precision)
         self._fwd_serial = 0
         self._nbt_pending = 0     # training forwards not yet added to the num_batches_tracked buffers
@@ -266,7 +275,8 @@ class Cnn_AvgPooling(nn.Module):
         self.event_fc = _LinearParams(c_last, classes_num)
 
     def _make_engine(self, precision):
-        return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, mel_bins=self.mel_bins)
+        return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, mel_bins=self.mel_bins,
+                         attention=self.attention)
 
     def set_precision(self, precision: str):
         self.precision = precision
@@ -358,9 +368,9 @@ class Crnn_AvgPooling(Cnn_AvgPooling):
     bias_hh_l0_reverse} (loadable into torch.nn.GRU), event_fc.{weight (classes, 2*hidden), bias}."""
 
     def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, gru_hidden=256, mel_bins=None,
-                 frontend=None):
+                 frontend=None, attention=False):
         self.gru_hidden = int(gru_hidden)
-        super().__init__(classes_num, model_config, precision, mel_bins=mel_bins, frontend=frontend)
+        super().__init__(classes_num, model_config, precision, mel_bins=mel_bins, frontend=frontend, attention=attention)
 
     def _build_head(self, c_last, classes_num):
         self.gru = _GruParams(c_last, self.gru_hidden)
@@ -368,4 +378,4 @@ class Crnn_AvgPooling(Cnn_AvgPooling):
 
     def _make_engine(self, precision):
         return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="gru",
-                         gru_hidden=self.gru_hidden, mel_bins=self.mel_bins)
+                         gru_hidden=self.gru_hidden, mel_bins=self.mel_bins, attention=self.attention)

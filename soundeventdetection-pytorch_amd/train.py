@@ -74,8 +74,8 @@ class FlatParams:
         self.buckets = self._merge_buckets(self.groups, n_buckets)
 
     def _make_buckets(self) -> List[tuple]:
-        """(start, end) per top-level group in BACKWARD completion order: event_fc first, then
-        conv_blocks.N-1 ... conv_blocks.0."""
+        """(start, end) per top-level group in BACKWARD completion order: event_fc first (after att_fc on a model with the
+        attention head), then conv_blocks.N-1 ... conv_blocks.0."""
         groups: Dict[str, List[int]] = {}
         order: List[str] = []
         for n in self.names:
@@ -317,8 +317,8 @@ def check_weak_options(weak_pooling=None, weak_weight=1.0, weak_only=False, mode
         if weak_only:
             raise ValueError("weak_only needs a weak_pooling (max, mean, linear or exp)")
         return None
-    from .engine import check_pooling
-    check_pooling(weak_pooling)
+    from .engine import check_clip_pooling
+    check_clip_pooling(weak_pooling, model)           # 'att': the attention pooling, on a model with the attention head
     w = float(weak_weight)
     if not (0.0 < w < float("inf")):
         raise ValueError(f"weak_weight must be finite and > 0 (got {weak_weight!r})")
@@ -412,7 +412,8 @@ class FusedTrainer:
         non-finite norm propagates as in torch (the step is not skipped).  With all four at their defaults the step launches
         what it always did; any option switches to sed_grad_norm / sed_adam_step_ex.
 
-        weak_pooling: None, or max / mean / linear / exp -- train from clip-level labels (csrc/sed_weak.hip): the frame
+        weak_pooling: None, or max / mean / linear / exp -- train from clip-level labels (csrc/sed_weak.hip) -- or att on a model
+        built with attention=True (the learned attention pooling, csrc/sed_attn.hip; it also trains att_fc): the frame
         probabilities are pooled over time and WeightedBCE is taken against the clip label, times weak_weight.  weak_only=False
         adds it to the strong loss, with the clip label taken from the (B, T, K) target on the device; weak_only=True trains on it
         alone, and the target may be (B, K).  None launches nothing new.
@@ -510,13 +511,14 @@ class FusedTrainer:
                 raise RuntimeError("graph=True does not take label kinds (the selections are made by torch comparisons per step)")
             if not hasattr(self.model, "conv_blocks"):
                 raise ValueError(f"label kinds select clips of frame-wise targets: {type(self.model).__name__} has none")
-        teacher_pre = None
+        teacher_pre = teacher_att = None
         if self.teacher is not None:        # first: the teacher's forward, in training mode like the student's
             if not self.teacher_flat.aliased():
                 raise RuntimeError("the teacher's parameters were re-allocated after FusedTrainer was built")
             self.teacher.train()
             xt = x if self.teacher_augment is None else self.teacher_augment(x)
-            teacher_pre = self.teacher.engine.forward(xt, self.teacher_flat.tensor_dict(), training=True).pre
+            tplan = self.teacher.engine.forward(xt, self.teacher_flat.tensor_dict(), training=True)
+            teacher_pre, teacher_att = tplan.pre, tplan.att
             self.teacher._nbt_pending += 1
             self.teacher._fwd_serial += 1
         P = self.flat.tensor_dict()
@@ -535,7 +537,8 @@ class FusedTrainer:
         self.model._fwd_serial += 1
         if kind is not None or teacher_pre is not None:
             cw = None if self.semi is None else consistency_weight_at(self.step_count + 1, self.semi[1], self.semi[2])
-            loss = eng.loss_and_grad(plan, y, self.recall_factor, weak=self.weak, kind=kind, teacher_pre=teacher_pre, consistency=cw)
+            loss = eng.loss_and_grad(plan, y, self.recall_factor, weak=self.weak, kind=kind, teacher_pre=teacher_pre, consistency=cw,
+                                     teacher_att=teacher_att)
             if teacher_pre is not None:
                 self.last_consistency = plan.consistency
         elif self.weak is None:
@@ -817,11 +820,12 @@ def eval_events(model, dataloader, device, *, threshold, low_threshold, median_w
 
 
 def check_ranking_options(clip_pooling=None, model=None):
-    """Validate eval_ranking's clip_pooling (host only): None, or max / mean / linear / exp on a model with a time axis."""
+    """Validate eval_ranking's clip_pooling (host only): None, or max / mean / linear / exp on a model with a time axis, or att
+    on one with the attention head."""
     if clip_pooling is None:
         return None
-    from .engine import check_pooling
-    check_pooling(clip_pooling)
+    from .engine import check_clip_pooling
+    check_clip_pooling(clip_pooling, model)
     if model is not None and not hasattr(model, "conv_blocks"):
         raise ValueError(f"clip pooling pools frame probabilities over time: {type(model).__name__} has no time axis in its "
                          "output (use Cnn_AvgPooling / Crnn_AvgPooling)")
@@ -833,7 +837,7 @@ def eval_ranking(model, dataloader, device, *, clip_pooling=None, limit_val_samp
     eval() does, its frame probabilities -- the sigmoid of sed_metric_counts, the one eval() uses -- and its targets are appended
     ON THE DEVICE to a utils.ranking_utils.RankingAccumulator over the first min(frames) frames, and one sort + scan at the end
     gives per-class AP, ROC-AUC, d' and the best-F1 threshold over all recordings; the host receives 68 bytes per class.
-    clip_pooling (max / mean / linear / exp): a second accumulator takes one element per recording and class, CnnEngine.clip_probs
+    clip_pooling (max / mean / linear / exp, or att on a model with the attention head): a second accumulator takes one element per recording and class, CnnEngine.clip_probs
     of the whole recording against the clip label (the target's maximum over the scored frames); its result sits under 'clip'.
     Returns the JSON-ready dict of metrics_from_rank_counts plus 'n_recordings'."""
     from .utils.metric_utils import metric_counts_device

@@ -93,6 +93,9 @@ class WeakBCE:
 
     def __init__(self, recall_factor, pooling, ratio=1):
         self.recall_factor = float(recall_factor)
+        if pooling == "att":
+            raise ValueError("unknown pooling 'att' for WeakBCE: the criterion sees only the frame logits, not the attention head's "
+                             "(train with FusedTrainer(weak_pooling='att') on a model built with attention=True)")
         self.mode_id = check_pooling(pooling)
         self.pooling = pooling
         self.ratio = int(ratio)
