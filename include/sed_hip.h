@@ -1040,6 +1040,45 @@ int sed_att_bwd_pack(const float* dpre, const float* datt, const float* fc_w, co
 int sed_att_bwd_split(const float* dwcat, const float* dbcat, float* dfc_w, float* dfc_b, float* datt_w,
                       float* datt_b, int C, int K, void* stream);
 
+/* ---- self-attention temporal head (csrc/sed_mhsa.hip) ---------------------------------------
+ * The attention core of torch.nn.MultiheadAttention(C, H, batch_first=True) between its two projections (those are
+ * sed_gemm_nt launches), and the residual LayerNorm behind it.
+ * qkv [B*t][3C] fp32 (q | k | v, head g = columns [g*dh, (g+1)*dh) of each third), C = H*dh, scale = 1/sqrt(dh).  Per clip b and
+ * head g, i and j over the t frames of that clip (no mask, no dropout):
+ *   s_ij = scale * sum_c q_ic k_jc,  lse_i = max_j s_ij + ln sum_j exp(s_ij - max_j s_ij),  p_ij = exp(s_ij - lse_i),
+ *   ctx_ic = sum_j p_ij v_jc                                      ctx [B*t][C], lse [B][H][t] (NULL for inference: same ctx bits)
+ * Backward, D_i = sum_c dctx_ic ctx_ic per head:
+ *   dv_jc = sum_i p_ij dctx_ic,  dp_ij = sum_c dctx_ic v_jc,  ds_ij = p_ij (dp_ij - D_i),
+ *   dq_ic = scale sum_j ds_ij k_jc,  dk_jc = scale sum_i ds_ij q_ic          dqkv [B*t][3C], every element overwritten
+ * Flash form: the t x t scores never reach memory; a wave owns 32 queries (forward, dQ pass) or 32 keys (dK / dV pass) and walks
+ * the other index in tiles of 32 with fp32 running maximum and sum; P is rebuilt from qkv and lse in the backward, which is
+ * three launches (D into the workspace, the key-owner pass, the query-owner pass) in a fixed order: no atomics, the same bits
+ * on every run.
+ * dtype: SED_BF16 rounds q, k, v and dctx to bf16 (nearest even) as MFMA operands, and the probabilities as the operand of P.V
+ * (backward: P for dV, dS for dK and dQ); scores, maximum, sum, lse, D, every accumulator and every stored tensor are fp32, and the
+ * sum that normalises ctx is taken over the fp32 probabilities.  SED_F32: the fp32-input MFMA, exact products.  (The f16x3 / bf16x3
+ * engines pass SED_F32, as they do for the recurrent head.)
+ * Any t >= 1: ragged last tiles are masked, rows past B*t are never read or written.
+ * Refused (non-zero, nothing launched): sizes <= 0, dh outside {32, 64}, a dtype other than those two, a NULL pointer other than
+ * lse in the forward, qkv / ctx / dctx / dqkv not 16-byte aligned, t*3C*4 >= 2^31 bytes (offsets inside a clip are 32-bit; the
+ * clip base is 64-bit, so B is not limited by it) and B*H*ceil(t/128) >= 2^31 workgroups.                                       */
+int    sed_mhsa_fwd(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, void* stream);
+size_t sed_mhsa_bwd_ws_floats(int B, int t, int H, int dh);
+int    sed_mhsa_bwd(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse,
+                    float* dqkv, float* workspace, int B, int t, int H, int dh, void* stream);
+/* y = ((x + a) - mean) * rstd * gamma + beta per row of C: mean, then the centred sum of squares (biased variance), both fp32 in a
+ * fixed order, rstd = 1/sqrt(var + eps); stats [rows][2] = (mean, rstd), NULL for inference (same y bits).
+ * Backward, g = dy * gamma, xhat = ((x + a) - mean) * rstd:  dres = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)) is the
+ * gradient of x and of a alike; dgamma = sum_rows dy * xhat, dbeta = sum_rows dy, through per-workgroup partials (64 rows each) in the
+ * workspace and a fixed-order reduction.  Refused: sizes <= 0, NULL pointers other than stats in the forward, rows > 65535 * 64
+ * in the backward.                                                                                                               */
+int    sed_add_layernorm_fwd(const float* x, const float* a, const float* gamma, const float* beta, float* y,
+                             float* stats, size_t rows, int C, float eps, void* stream);
+size_t sed_add_layernorm_bwd_ws_floats(size_t rows, int C);
+int    sed_add_layernorm_bwd(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
+                             float* dres, float* dgamma, float* dbeta, float* workspace,
+                             size_t rows, int C, void* stream);
+
 /* ---- utilities -----------------------------------------------------------------------------*/
 /* out[i] = sum_{s<nparts} partial[s][i], i < n (fixed order: deterministic)                     */
 int sed_sum_partials(const float* partial, int nparts, size_t n, float* out, void* stream);

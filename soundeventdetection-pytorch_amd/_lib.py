@@ -167,6 +167,12 @@ PROTOTYPES = {
     "sed_att_loss_fwd_bwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
     "sed_att_bwd_pack": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "sed_att_bwd_split": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "sed_mhsa_fwd": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sed_mhsa_bwd_ws_floats": (_Z, [_I, _I, _I, _I]),
+    "sed_mhsa_bwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sed_add_layernorm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _F, _P]),
+    "sed_add_layernorm_bwd_ws_floats": (_Z, [_Z, _I]),
+    "sed_add_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _P]),
     "sed_m5_conv1_len": (_I, [_I]),
     "sed_m5_conv1_nparts": (_I, [_I, _I]),
     "sed_m5_conv1_fwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _P]),

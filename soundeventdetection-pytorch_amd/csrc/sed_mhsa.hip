@@ -1,0 +1,643 @@
+// Self-attention temporal head: the multi-head attention core (forward and backward, flash form, on the matrix pipe) and the
+// residual LayerNorm behind it.  The projections around the core are sed_gemm_nt / sed_gemm_tn launches (sed_gru.hip).
+//
+// Core, for one clip b and head g (dh = 32 or 64 columns [g*dh, (g+1)*dh) of each third of a qkv row), scale = 1/sqrt(dh):
+//   s_ij  = scale * sum_c q_ic k_jc                      i, j over the t frames of the SAME clip, no mask
+//   lse_i = max_j s_ij + ln sum_j exp(s_ij - max_j s_ij)
+//   p_ij  = exp(s_ij - lse_i),   ctx_ic = sum_j p_ij v_jc
+// backward, with D_i = sum_c dctx_ic ctx_ic (per head):
+//   dv_jc = sum_i p_ij dctx_ic          dp_ij = sum_c dctx_ic v_jc          ds_ij = p_ij (dp_ij - D_i)
+//   dq_ic = scale sum_j ds_ij k_jc      dk_jc = scale sum_i ds_ij q_ic
+// (tests/mhsa_formula.py is the same in float64 numpy.)
+//
+// Forward: a workgroup is four waves, each wave owns 32 queries of one (clip, head) and walks the keys in tiles of 32; the t x t
+// scores never reach memory.  The wave computes S^T = K Q^T (32x32 MFMA, key in the accumulator registers, query on the lane), so
+// a lane holds 16 scores of ONE query and the other half-wave's lane the other 16: the running maximum and sum are per-lane fp32
+// scalars plus one exchange with lane ^ 32, and the probabilities are already the B operand of O^T = V^T P^T (an accumulator tile as
+// the next MFMA's operand: P never passes through LDS).  O^T has the query on the lane too, so the rescale by
+// exp(m_old - m_new) and the final 1/sum are per-lane scalars.  ctx = O / sum, lse = m + ln(sum).
+// Where the operands come from: the bf16 forward stages each K / V tile once per workgroup in LDS, rounded to bf16 (mhsa_fwd_lds_kernel
+// below: 0.079 -> 0.063 ms at B 32, t 750, 4 heads of 32 against every wave loading and converting the tiles itself).  The fp32
+// forward and the three backward kernels load their operands straight from global memory into registers (a clip's q, k, v of one head
+// are 3 t dh floats and stay in L2), the next tile's rows while the current tile is computed; their four waves share nothing.
+// Backward: sed_mhsa_bwd is three launches, all in a fixed order (no atomics, the same bits on every run):
+//   1. D_i per (clip, head, frame) into the workspace;
+//   2. waves that own 32 KEYS loop over the query tiles: S = Q K^T and dP = dctx V^T with the key on the lane, P and dS rebuilt in
+//      registers and fed as B operands to dV^T += dctx^T P and dK^T += Q^T dS;
+//   3. waves that own 32 QUERIES loop over the key tiles: S^T and dP^T with the query on the lane (lse_i and D_i are lane scalars),
+//      dQ^T += K^T dS^T.
+// S is recomputed in both passes; dqkv is overwritten, every element of its B*t rows.
+//
+// dtype: SED_BF16 -- q, k, v (and dctx in the backward) are rounded to bf16 (nearest even) as MFMA operands of
+// v_mfma_f32_32x32x16_bf16, and so are the probabilities as the operand of P V (backward: P for dV, dS for dK and dQ); the scores,
+// the maximum, the sum, lse, D, P and dS themselves, every accumulator and every stored tensor are fp32.  The sum that normalises
+// ctx is taken over the fp32 probabilities.  SED_F32 -- the same dataflow on v_mfma_f32_32x32x2_f32 (exact fp32 products).
+//
+// Ragged tiles: any t >= 1.  Loads of rows past the clip are clamped to its last row (always real data of the same clip), their
+// scores are set to -inf (p = 0) or their p / dS to 0, and no row past t is stored: nothing outside the B*t rows is read or written.
+// Addressing: 64-bit clip base + 32-bit offsets inside a clip: t * 3C * 4 bytes must stay below 2^31, and B*H*ceil(t/128) below 2^31
+// workgroups.  qkv, ctx, dctx, dqkv must be 16-byte aligned (rows are read and written with 16-byte accesses).
+//
+// LayerNorm: y = ((x + a) - mean) * rstd * gamma + beta per row, mean and the centred sum of squares in two passes (biased variance,
+// rstd = 1/sqrt(var + eps)), one wave per row, each lane its columns in ascending order and one fixed wave reduction.  Backward with
+// g = dy * gamma, xhat = ((x + a) - mean) * rstd:  dres = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)), the gradient of both x and
+// a; dgamma = sum_rows dy * xhat and dbeta = sum_rows dy through per-workgroup partials (64 rows each) in the workspace and a
+// fixed-order reduction over the workgroups.
+#include "common.h"
+#include <math.h>
+
+#define MHSA_QT 32            // queries (or keys) a wave owns
+#define MHSA_WAVES 4          // waves per workgroup, each with its own tile
+#define LN_ROWS_PER_WG 64     // rows behind one dgamma / dbeta partial
+
+namespace {
+
+// row of the 32x32 accumulator that register i of lane half h holds
+__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+// ---- the fragments of one row-major row (dh head columns) as the operand of a product summed over the columns -----------------
+// bf16: k-step s (16 columns) takes columns 16 s + 8 h + j in element j;  fp32: k-step kk (2 columns) takes column h * dh/2 + kk
+// (both operands of a product use the same map, so the order of the k index inside the sum is free)
+template <typename T, int DH> struct RowFrag;
+template <int DH> struct RowFrag<bf16_t, DH> {
+    static constexpr int N = DH / 16;
+    bf16x8 f[N];
+    __device__ __forceinline__ void load(const float* __restrict__ row, int h) {
+#pragma unroll
+        for (int s = 0; s < N; ++s) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(row + 16 * s + 8 * h);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(row + 16 * s + 8 * h + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { f[s][j] = (bf16_t)a[j]; f[s][4 + j] = (bf16_t)b[j]; }
+        }
+    }
+};
+template <int DH> struct RowFrag<float, DH> {
+    static constexpr int N = DH / 2;
+    float f[N];
+    __device__ __forceinline__ void load(const float* __restrict__ row, int h) {
+#pragma unroll
+        for (int s = 0; s < N / 4; ++s) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(row + h * N + 4 * s);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) f[4 * s + j] = a[j];
+        }
+    }
+};
+
+// acc[row of A][row of B] = sum_c A[.][c] B[.][c]: A's row index lands in the accumulator registers, B's on the lane
+template <typename T, int DH>
+__device__ __forceinline__ f32x16 mm_rows(const RowFrag<T, DH>& a, const RowFrag<T, DH>& b) {
+    f32x16 acc = {};
+#pragma unroll
+    for (int s = 0; s < RowFrag<T, DH>::N; ++s) acc = mfma(a.f[s], b.f[s], acc);
+    return acc;
+}
+
+// One column of a 32-row tile as the A operand of the product below: a[i] = M[row0 + acc_row(i, h)][c], col pointing at column c =
+// this lane's (lane & 31) of row 0 of the clip; rows >= t are read from row t - 1 (their x is 0).  Kept apart from the product so that
+// a kernel can issue these loads a tile ahead, or at the top of the tile, and the wave does not sit out their latency between MFMAs.
+__device__ __forceinline__ void load_col(float (&a)[16], const float* __restrict__ col, int ld, int row0, int t, int h) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        int row = row0 + acc_row(i, h);
+        row = row < t ? row : t - 1;
+        a[i] = col[row * ld];
+    }
+}
+// acc[c][lane] += sum_rows a[row] * x[row][lane], x an accumulator tile (row in the registers)
+template <typename T> struct MmAx;
+template <> struct MmAx<bf16_t> {
+    static __device__ __forceinline__ void run(f32x16& acc, const float (&a)[16], const f32x16& x) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            bf16x8 af, b;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                af[j] = (bf16_t)a[8 * s + j];
+                b[j] = (bf16_t)x[8 * s + j];
+            }
+            acc = mfma(af, b, acc);
+        }
+    }
+};
+template <> struct MmAx<float> {
+    static __device__ __forceinline__ void run(f32x16& acc, const float (&a)[16], const f32x16& x) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float af = a[i], b = x[i];
+            acc = mfma(af, b, acc);
+        }
+    }
+};
+
+__device__ __forceinline__ float xor32(float v) { return __shfl_xor(v, 32, 64); }
+
+struct MhsaParams {
+    const float* qkv;
+    const float* ctx;
+    const float* dctx;
+    const float* lse;
+    float* out;          // ctx (forward) / dqkv (backward)
+    float* lse_out;
+    float* D;            // workspace [B][H][t]
+    int t, H, ntile;     // ntile = ceil(t / 128) workgroups per (clip, head)
+    float scale;
+};
+
+// store the transposed 32 x 32 tile o (column c = acc_row(i, h) in the registers, row on the lane) times f into row `dst` (head columns)
+__device__ __forceinline__ void store_tile_t(float* __restrict__ dst, const f32x16& o, float f, int h) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = o[4 * g + j] * f;
+        *reinterpret_cast<f32x4*>(dst + 8 * g + 4 * h) = v;
+    }
+}
+
+template <typename T, int DH>
+__global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
+    const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
+    const int q0 = (tile * MHSA_WAVES + wave) * MHSA_QT;
+    if (q0 >= t) return;                               // (no barrier in this kernel)
+    const float* __restrict__ base = p.qkv + (size_t)b * t * ld + g * DH;
+    const int qr = q0 + r < t ? q0 + r : t - 1;
+    RowFrag<T, DH> qf;
+    qf.load(base + qr * ld, h);
+    f32x16 o[DH / 32];
+#pragma unroll
+    for (int cb = 0; cb < DH / 32; ++cb) o[cb] = (f32x16){};
+    float m = -INFINITY, l = 0.f;
+    // the next tile's K rows and V columns are loaded while this tile is computed (registers, no LDS)
+    RowFrag<T, DH> kn;
+    float vn[DH / 32][16];
+    kn.load(base + C + (r < t ? r : t - 1) * ld, h);
+#pragma unroll
+    for (int cb = 0; cb < DH / 32; ++cb) load_col(vn[cb], base + 2 * C + cb * 32 + r, ld, 0, t, h);
+    for (int k0 = 0; k0 < t; k0 += 32) {
+        const RowFrag<T, DH> kf = kn;
+        float va[DH / 32][16];
+#pragma unroll
+        for (int cb = 0; cb < DH / 32; ++cb)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) va[cb][i] = vn[cb][i];
+        if (k0 + 32 < t) {
+            const int kr = k0 + 32 + r < t ? k0 + 32 + r : t - 1;
+            kn.load(base + C + kr * ld, h);
+#pragma unroll
+            for (int cb = 0; cb < DH / 32; ++cb) load_col(vn[cb], base + 2 * C + cb * 32 + r, ld, k0 + 32, t, h);
+        }
+        f32x16 s = mm_rows<T, DH>(kf, qf);             // s[key][query]
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            s[i] = k0 + acc_row(i, h) < t ? s[i] * p.scale : -INFINITY;
+            mx = fmaxf(mx, s[i]);
+        }
+        mx = fmaxf(mx, xor32(mx));
+        const float mn = fmaxf(m, mx);                 // finite from the first tile on: key k0 is always inside the clip
+        const float alpha = expf(m - mn);
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { s[i] = expf(s[i] - mn); sum += s[i]; }
+        sum += xor32(sum);
+        l = l * alpha + sum;
+        m = mn;
+#pragma unroll
+        for (int cb = 0; cb < DH / 32; ++cb) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[cb][i] *= alpha;
+            MmAx<T>::run(o[cb], va[cb], s);
+        }
+    }
+    if (q0 + r < t) {
+        const float inv = 1.f / l;
+        float* __restrict__ dst = p.out + ((size_t)b * t + q0 + r) * C + g * DH;
+#pragma unroll
+        for (int cb = 0; cb < DH / 32; ++cb) store_tile_t(dst + cb * 32, o[cb], inv, h);
+        if (p.lse_out != nullptr && h == 0) p.lse_out[(size_t)bh * t + q0 + r] = m + logf(l);
+    }
+}
+
+// The bf16 forward with the K / V tiles staged ONCE per workgroup: the 256 threads load a tile of 32 keys with whole-row 16-byte loads
+// (the next tile's while this one is computed), round it to bf16 and write K row-major (pitch dh + 8: conflict-free 16-byte reads of the
+// A fragments) and V transposed (Vt[c][key], pitch 36: a lane's eight keys of a k-step are two 8-byte reads) into one of two LDS
+// buffers, one barrier per tile.  Same values, same MFMA order and so the same bits as the register-fed kernel above, which the fp32
+// mode keeps; waves whose 32 queries lie past the clip take part in the staging and the barriers only.
+template <int DH>
+__global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParams p) {
+    constexpr int KP = DH + 8, VP = 36, NL = DH / 32, RQ = DH / 4;       // NL 16-byte loads of K and of V per thread and tile
+    __shared__ __attribute__((aligned(16))) bf16_t ks[2][32 * KP];
+    __shared__ __attribute__((aligned(16))) bf16_t vt[2][DH * VP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
+    const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
+    const int q0 = (tile * MHSA_WAVES + wave) * MHSA_QT;
+    const bool active = q0 < t;
+    const float* __restrict__ base = p.qkv + (size_t)b * t * ld + g * DH;
+    const int qr = q0 + r < t ? q0 + r : t - 1;
+    RowFrag<bf16_t, DH> qf;
+    qf.load(base + qr * ld, h);
+    f32x4 kreg[NL], vreg[NL];
+    auto gload = [&](int k0) {
+#pragma unroll
+        for (int n = 0; n < NL; ++n) {
+            const int idx = tid + 256 * n, row = idx / RQ, c4 = (idx % RQ) * 4;
+            const int rr = k0 + row < t ? k0 + row : t - 1;
+            kreg[n] = *reinterpret_cast<const f32x4*>(base + C + rr * ld + c4);
+            vreg[n] = *reinterpret_cast<const f32x4*>(base + 2 * C + rr * ld + c4);
+        }
+    };
+    auto lstore = [&](int buf) {
+#pragma unroll
+        for (int n = 0; n < NL; ++n) {
+            const int idx = tid + 256 * n, row = idx / RQ, c4 = (idx % RQ) * 4;
+            bf16x4 kb;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                kb[i] = (bf16_t)kreg[n][i];
+                vt[buf][(c4 + i) * VP + row] = (bf16_t)vreg[n][i];
+            }
+            *reinterpret_cast<bf16x4*>(&ks[buf][row * KP + c4]) = kb;
+        }
+    };
+    f32x16 o[NL];
+#pragma unroll
+    for (int cb = 0; cb < NL; ++cb) o[cb] = (f32x16){};
+    float m = -INFINITY, l = 0.f;
+    gload(0);
+    lstore(0);
+    __syncthreads();
+    for (int k0 = 0, it = 0; k0 < t; k0 += 32, ++it) {
+        const int cur = it & 1;
+        const bool more = k0 + 32 < t;                 // (the same in every thread: the barrier below is uniform)
+        if (more) gload(k0 + 32);
+        if (active) {
+            RowFrag<bf16_t, DH> kf;
+#pragma unroll
+            for (int s = 0; s < DH / 16; ++s) kf.f[s] = *reinterpret_cast<const bf16x8*>(&ks[cur][r * KP + 16 * s + 8 * h]);
+            f32x16 s = mm_rows<bf16_t, DH>(kf, qf);    // s[key][query]
+            float mx = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                s[i] = k0 + acc_row(i, h) < t ? s[i] * p.scale : -INFINITY;
+                mx = fmaxf(mx, s[i]);
+            }
+            mx = fmaxf(mx, xor32(mx));
+            const float mn = fmaxf(m, mx);
+            const float alpha = expf(m - mn);
+            float sum = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { s[i] = expf(s[i] - mn); sum += s[i]; }
+            sum += xor32(sum);
+            l = l * alpha + sum;
+            m = mn;
+#pragma unroll
+            for (int cb = 0; cb < NL; ++cb) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[cb][i] *= alpha;
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const bf16_t* vrow = &vt[cur][(cb * 32 + r) * VP + 16 * s2 + 4 * h];
+                    const bf16x4 lo = *reinterpret_cast<const bf16x4*>(vrow), hi = *reinterpret_cast<const bf16x4*>(vrow + 8);
+                    bf16x8 af, pb;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { af[j] = lo[j]; af[4 + j] = hi[j]; }
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) pb[j] = (bf16_t)s[8 * s2 + j];
+                    o[cb] = mfma(af, pb, o[cb]);
+                }
+            }
+        }
+        if (more) lstore(cur ^ 1);
+        __syncthreads();
+    }
+    if (active && q0 + r < t) {
+        const float inv = 1.f / l;
+        float* __restrict__ dst = p.out + ((size_t)b * t + q0 + r) * C + g * DH;
+#pragma unroll
+        for (int cb = 0; cb < NL; ++cb) store_tile_t(dst + cb * 32, o[cb], inv, h);
+        if (p.lse_out != nullptr && h == 0) p.lse_out[(size_t)bh * t + q0 + r] = m + logf(l);
+    }
+}
+
+// D[b][g][i] = sum_c dctx[b*t+i][g*dh + c] * ctx[..]: one thread per (row, head), columns ascending
+__global__ __launch_bounds__(256) void mhsa_rowdot_kernel(MhsaParams p, int B, int dh) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t n = (size_t)B * p.t * p.H;
+    if (idx >= n) return;
+    const size_t row = idx / p.H;
+    const int g = (int)(idx % p.H);
+    const size_t b = row / p.t, i = row % p.t;
+    const float* __restrict__ x = p.dctx + row * (size_t)(p.H * dh) + g * dh;
+    const float* __restrict__ y = p.ctx + row * (size_t)(p.H * dh) + g * dh;
+    float acc = 0.f;
+    for (int c = 0; c < dh; c += 4) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(x + c), bb = *reinterpret_cast<const f32x4*>(y + c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = fmaf(a[j], bb[j], acc);
+    }
+    p.D[(b * p.H + g) * p.t + i] = acc;
+}
+
+// pass 2 of the backward: the wave owns 32 keys (on the lane) and loops over the query tiles -> dK, dV
+template <typename T, int DH>
+__global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
+    const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
+    const int k0 = (tile * MHSA_WAVES + wave) * MHSA_QT;
+    if (k0 >= t) return;
+    const float* __restrict__ base = p.qkv + (size_t)b * t * ld + g * DH;
+    const float* __restrict__ dbase = p.dctx + (size_t)b * t * C + g * DH;
+    const float* __restrict__ lse = p.lse + (size_t)bh * t;
+    const float* __restrict__ D = p.D + (size_t)bh * t;
+    const int kr = k0 + r < t ? k0 + r : t - 1;
+    RowFrag<T, DH> kf, vf;
+    kf.load(base + C + kr * ld, h);
+    vf.load(base + 2 * C + kr * ld, h);
+    f32x16 dk[DH / 32], dv[DH / 32];
+#pragma unroll
+    for (int cb = 0; cb < DH / 32; ++cb) { dk[cb] = (f32x16){}; dv[cb] = (f32x16){}; }
+    // the next tile's Q / dctx rows, lse and D are loaded while this tile is computed; this tile's Q / dctx columns at its top
+    RowFrag<T, DH> qn, dn;
+    float ln[16], Dn[16];
+    auto load_rows = [&](int q0) {
+        const int qr = q0 + r < t ? q0 + r : t - 1;
+        qn.load(base + qr * ld, h);
+        dn.load(dbase + qr * C, h);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int q = q0 + acc_row(i, h);
+            const int qc = q < t ? q : t - 1;
+            ln[i] = lse[qc];
+            Dn[i] = D[qc];
+        }
+    };
+    load_rows(0);
+    for (int q0 = 0; q0 < t; q0 += 32) {
+        const RowFrag<T, DH> qf = qn, df = dn;
+        float lc[16], Dc[16], qa[DH / 32][16], da[DH / 32][16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { lc[i] = ln[i]; Dc[i] = Dn[i]; }
+#pragma unroll
+        for (int cb = 0; cb < DH / 32; ++cb) {
+            load_col(da[cb], dbase + cb * 32 + r, C, q0, t, h);
+            load_col(qa[cb], base + cb * 32 + r, ld, q0, t, h);
+        }
+        if (q0 + 32 < t) load_rows(q0 + 32);
+        f32x16 s = mm_rows<T, DH>(qf, kf);             // s[query][key]
+        f32x16 dp = mm_rows<T, DH>(df, vf);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float pr = q0 + acc_row(i, h) < t ? expf(s[i] * p.scale - lc[i]) : 0.f;
+            s[i] = pr;
+            dp[i] = pr * (dp[i] - Dc[i]);
+        }
+#pragma unroll
+        for (int cb = 0; cb < DH / 32; ++cb) {
+            MmAx<T>::run(dv[cb], da[cb], s);
+            MmAx<T>::run(dk[cb], qa[cb], dp);
+        }
+    }
+    if (k0 + r < t) {
+        float* __restrict__ dst = p.out + ((size_t)b * t + k0 + r) * ld + g * DH;
+#pragma unroll
+        for (int cb = 0; cb < DH / 32; ++cb) {
+            store_tile_t(dst + C + cb * 32, dk[cb], p.scale, h);
+            store_tile_t(dst + 2 * C + cb * 32, dv[cb], 1.f, h);
+        }
+    }
+}
+
+// pass 3: the wave owns 32 queries (on the lane) and loops over the key tiles -> dQ
+template <typename T, int DH>
+__global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
+    const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
+    const int q0 = (tile * MHSA_WAVES + wave) * MHSA_QT;
+    if (q0 >= t) return;
+    const float* __restrict__ base = p.qkv + (size_t)b * t * ld + g * DH;
+    const float* __restrict__ dbase = p.dctx + (size_t)b * t * C + g * DH;
+    const int qr = q0 + r < t ? q0 + r : t - 1;
+    const float lse = p.lse[(size_t)bh * t + qr], Dq = p.D[(size_t)bh * t + qr];
+    RowFrag<T, DH> qf, df;
+    qf.load(base + qr * ld, h);
+    df.load(dbase + qr * C, h);
+    f32x16 dq[DH / 32];
+#pragma unroll
+    for (int cb = 0; cb < DH / 32; ++cb) dq[cb] = (f32x16){};
+    // the next tile's K / V rows are loaded while this tile is computed; this tile's K columns at its top
+    RowFrag<T, DH> kn, vn;
+    auto load_rows = [&](int k0) {
+        const int kr = k0 + r < t ? k0 + r : t - 1;
+        kn.load(base + C + kr * ld, h);
+        vn.load(base + 2 * C + kr * ld, h);
+    };
+    load_rows(0);
+    for (int k0 = 0; k0 < t; k0 += 32) {
+        const RowFrag<T, DH> kf = kn, vf = vn;
+        float ka[DH / 32][16];
+#pragma unroll
+        for (int cb = 0; cb < DH / 32; ++cb) load_col(ka[cb], base + C + cb * 32 + r, ld, k0, t, h);
+        if (k0 + 32 < t) load_rows(k0 + 32);
+        f32x16 s = mm_rows<T, DH>(kf, qf);             // s[key][query]
+        f32x16 dp = mm_rows<T, DH>(vf, df);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float pr = k0 + acc_row(i, h) < t ? expf(s[i] * p.scale - lse) : 0.f;
+            dp[i] = pr * (dp[i] - Dq);
+        }
+#pragma unroll
+        for (int cb = 0; cb < DH / 32; ++cb) MmAx<T>::run(dq[cb], ka[cb], dp);
+    }
+    if (q0 + r < t) {
+        float* __restrict__ dst = p.out + ((size_t)b * t + q0 + r) * ld + g * DH;
+#pragma unroll
+        for (int cb = 0; cb < DH / 32; ++cb) store_tile_t(dst + cb * 32, dq[cb], p.scale, h);
+    }
+}
+
+// ---- LayerNorm ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void add_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                         float* __restrict__ y, float* __restrict__ stats, size_t rows, int C, float eps) {
+    const int lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* __restrict__ xr = x + row * C;
+    const float* __restrict__ ar = a + row * C;
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += xr[c] + ar[c];
+    const float mean = wave_sum(s) / (float)C;
+    float ss = 0.f;
+    for (int c = lane; c < C; c += 64) { const float d = (xr[c] + ar[c]) - mean; ss = fmaf(d, d, ss); }
+    const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)C + eps);
+    for (int c = lane; c < C; c += 64) y[row * C + c] = ((xr[c] + ar[c]) - mean) * rstd * gamma[c] + beta[c];
+    if (stats != nullptr && lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
+}
+
+__global__ __launch_bounds__(256) void add_ln_bwd_dres_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                              const float* __restrict__ a, const float* __restrict__ gamma,
+                                                              const float* __restrict__ stats, float* __restrict__ dres, size_t rows, int C) {
+    const int lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* __restrict__ xr = x + row * C;
+    const float* __restrict__ ar = a + row * C;
+    const float* __restrict__ gr = dy + row * C;
+    const float mean = stats[2 * row], rstd = stats[2 * row + 1];
+    float s1 = 0.f, s2 = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        const float g = gr[c] * gamma[c], xh = ((xr[c] + ar[c]) - mean) * rstd;
+        s1 += g;
+        s2 = fmaf(g, xh, s2);
+    }
+    const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+    for (int c = lane; c < C; c += 64) {
+        const float g = gr[c] * gamma[c], xh = ((xr[c] + ar[c]) - mean) * rstd;
+        dres[row * C + c] = rstd * ((g - m1) - xh * m2);
+    }
+}
+
+// partial[chunk][0][c] = sum over the chunk's rows of dy * xhat, partial[chunk][1][c] = sum of dy: 64 columns x 4 row lanes per
+// workgroup, each row lane its rows (stride 4) in ascending order, then the four in a fixed order
+__global__ __launch_bounds__(256) void add_ln_bwd_part_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                              const float* __restrict__ a, const float* __restrict__ stats,
+                                                              float* __restrict__ partial, size_t rows, int C) {
+    __shared__ float sh[2][4][64];
+    const int cl = threadIdx.x & 63, ry = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    const size_t r0 = (size_t)blockIdx.y * LN_ROWS_PER_WG;
+    const size_t r1 = r0 + LN_ROWS_PER_WG < rows ? r0 + LN_ROWS_PER_WG : rows;
+    float sg = 0.f, sb = 0.f;
+    if (c < C)
+        for (size_t row = r0 + ry; row < r1; row += 4) {
+            const float g = dy[row * C + c];
+            const float xh = ((x[row * C + c] + a[row * C + c]) - stats[2 * row]) * stats[2 * row + 1];
+            sg = fmaf(g, xh, sg);
+            sb += g;
+        }
+    sh[0][ry][cl] = sg;
+    sh[1][ry][cl] = sb;
+    __syncthreads();
+    if (ry == 0 && c < C) {
+        partial[((size_t)blockIdx.y * 2 + 0) * C + c] = (sh[0][0][cl] + sh[0][1][cl]) + (sh[0][2][cl] + sh[0][3][cl]);
+        partial[((size_t)blockIdx.y * 2 + 1) * C + c] = (sh[1][0][cl] + sh[1][1][cl]) + (sh[1][2][cl] + sh[1][3][cl]);
+    }
+}
+
+__global__ __launch_bounds__(256) void add_ln_bwd_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dgamma,
+                                                                float* __restrict__ dbeta, int nchunks, int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float sg = 0.f, sb = 0.f;
+    for (int k = 0; k < nchunks; ++k) {
+        sg += partial[((size_t)k * 2 + 0) * C + c];
+        sb += partial[((size_t)k * 2 + 1) * C + c];
+    }
+    dgamma[c] = sg;
+    dbeta[c] = sb;
+}
+
+int mhsa_check(int dtype, int B, int t, int H, int dh, long long* nblocks, int* ntile) {
+    SED_REQUIRE(dtype == SED_F32 || dtype == SED_BF16, "dtype must be SED_F32 or SED_BF16");
+    SED_REQUIRE(B > 0 && t > 0 && H > 0, "sizes must be positive");
+    SED_REQUIRE(dh == 32 || dh == 64, "head width must be 32 or 64");
+    SED_REQUIRE((long long)t * 3 * H * dh * 4 < (1ll << 31), "a clip's qkv rows must stay below 2 GiB (32-bit offsets inside a clip)");
+    *ntile = cdiv(t, MHSA_QT * MHSA_WAVES);
+    *nblocks = (long long)B * H * *ntile;
+    SED_REQUIRE(*nblocks < (1ll << 31), "too many workgroups");
+    return 0;
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int sed_mhsa_fwd(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, void* stream) {
+    long long nb; int ntile;
+    if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
+    SED_REQUIRE(qkv != nullptr && ctx != nullptr, "qkv and ctx are required");
+    SED_REQUIRE(aligned16(qkv) && aligned16(ctx), "qkv and ctx must be 16-byte aligned");
+    MhsaParams p = {};
+    p.qkv = qkv; p.out = ctx; p.lse_out = lse; p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
+    if (dtype == SED_BF16) {
+        if (dh == 32) mhsa_fwd_lds_kernel<32><<<grid, block, 0, st>>>(p);
+        else mhsa_fwd_lds_kernel<64><<<grid, block, 0, st>>>(p);
+    } else {
+        if (dh == 32) mhsa_fwd_kernel<float, 32><<<grid, block, 0, st>>>(p);
+        else mhsa_fwd_kernel<float, 64><<<grid, block, 0, st>>>(p);
+    }
+    SED_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t sed_mhsa_bwd_ws_floats(int B, int t, int H, int dh) {
+    (void)dh;
+    if (B <= 0 || t <= 0 || H <= 0) return 0;
+    return (size_t)B * t * H;
+}
+
+extern "C" int sed_mhsa_bwd(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
+                            float* workspace, int B, int t, int H, int dh, void* stream) {
+    long long nb; int ntile;
+    if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
+    SED_REQUIRE(qkv != nullptr && ctx != nullptr && dctx != nullptr && lse != nullptr && dqkv != nullptr && workspace != nullptr,
+                "qkv, ctx, dctx, lse, dqkv and the workspace are required");
+    SED_REQUIRE(aligned16(qkv) && aligned16(ctx) && aligned16(dctx) && aligned16(dqkv), "qkv, ctx, dctx and dqkv must be 16-byte aligned");
+    MhsaParams p = {};
+    p.qkv = qkv; p.ctx = ctx; p.dctx = dctx; p.lse = lse; p.out = dqkv; p.D = workspace;
+    p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
+    hipStream_t st = (hipStream_t)stream;
+    mhsa_rowdot_kernel<<<(unsigned)cdivz((size_t)B * t * H, 256), 256, 0, st>>>(p, B, dh);
+    SED_LAUNCH_CHECK();
+    const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
+    if (dtype == SED_BF16) {
+        if (dh == 32) { mhsa_bwd_kv_kernel<bf16_t, 32><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 32><<<grid, block, 0, st>>>(p); }
+        else { mhsa_bwd_kv_kernel<bf16_t, 64><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 64><<<grid, block, 0, st>>>(p); }
+    } else {
+        if (dh == 32) { mhsa_bwd_kv_kernel<float, 32><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 32><<<grid, block, 0, st>>>(p); }
+        else { mhsa_bwd_kv_kernel<float, 64><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 64><<<grid, block, 0, st>>>(p); }
+    }
+    SED_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sed_add_layernorm_fwd(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
+                                     size_t rows, int C, float eps, void* stream) {
+    SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
+    SED_REQUIRE(x != nullptr && a != nullptr && gamma != nullptr && beta != nullptr && y != nullptr, "x, a, gamma, beta and y are required");
+    SED_REQUIRE(cdivz(rows, 4) < ((size_t)1 << 31), "too many rows");
+    add_ln_fwd_kernel<<<(unsigned)cdivz(rows, 4), 256, 0, (hipStream_t)stream>>>(x, a, gamma, beta, y, stats, rows, C, eps);
+    SED_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t sed_add_layernorm_bwd_ws_floats(size_t rows, int C) {
+    if (rows == 0 || C <= 0) return 0;
+    return cdivz(rows, LN_ROWS_PER_WG) * 2 * (size_t)C;
+}
+
+extern "C" int sed_add_layernorm_bwd(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
+                                     float* dres, float* dgamma, float* dbeta, float* workspace, size_t rows, int C, void* stream) {
+    SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
+    SED_REQUIRE(dy != nullptr && x != nullptr && a != nullptr && gamma != nullptr && stats != nullptr && dres != nullptr &&
+                dgamma != nullptr && dbeta != nullptr && workspace != nullptr, "every pointer is required");
+    const size_t nchunks = cdivz(rows, LN_ROWS_PER_WG);
+    SED_REQUIRE(nchunks <= 65535, "too many rows (the partial grid takes 65535 * 64)");
+    hipStream_t st = (hipStream_t)stream;
+    add_ln_bwd_dres_kernel<<<(unsigned)cdivz(rows, 4), 256, 0, st>>>(dy, x, a, gamma, stats, dres, rows, C);
+    SED_LAUNCH_CHECK();
+    add_ln_bwd_part_kernel<<<dim3((unsigned)cdiv(C, 64), (unsigned)nchunks), 256, 0, st>>>(dy, x, a, stats, workspace, rows, C);
+    SED_LAUNCH_CHECK();
+    add_ln_bwd_reduce_kernel<<<(unsigned)cdiv(C, 256), 256, 0, st>>>(workspace, dgamma, dbeta, (int)nchunks, C);
+    SED_LAUNCH_CHECK();
+    return 0;
+}

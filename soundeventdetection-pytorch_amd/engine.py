@@ -27,6 +27,7 @@ from . import _lib as L
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
+LN_EPS = 1e-5        # the self-attention head's LayerNorm (torch.nn.LayerNorm's default)
 
 
 def pad32(c: int) -> int:
@@ -138,6 +139,7 @@ class _Plan:
     x_ref: torch.Tensor = None      # the input of the last forward (first layer wgrad re-reads it)
     trained: bool = False
     gru: dict = None                # buffers of the recurrent head (head == 'gru')
+    sa: dict = None                 # buffers of the self-attention head (head == 'sa')
     keep: bool = False              # the last forward ran with keep_for_grad (input-gradient / eval-mode backward possible)
     dx_in: torch.Tensor = None      # (B, 1, T, F) fp32 input gradient of the Cin = 1 model path (the last backward(need_dx=True))
     weak_ws: torch.Tensor = None    # workspace of the weak-label loss (csrc/sed_weak.hip), allocated at its first use
@@ -225,12 +227,13 @@ class OptimizerExtMixin:
 class CnnEngine(OptimizerExtMixin):
     def __init__(self, classes_num: int, model_config: Sequence[Tuple[int, int]], in_channels: int = 1,
                  precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
-                 mel_bins: Optional[int] = None, attention: bool = False):
+                 mel_bins: Optional[int] = None, attention: bool = False, sa_heads: int = 4, pos_encoding: bool = True):
         """attention: a second linear layer att_fc beside event_fc scores every frame per class (csrc/sed_attn.hip): forward()
         also leaves the attention logits in plan.att, loss_and_grad(weak=("att", ...)) pools with them and backward() then takes
         both layers.  False launches exactly what it always did.
-        head: 'fc' (Cnn_AvgPooling), 'gru' (CRNN) or 'none' (a bare stack of ConvBlocks: forward() stops at the last
-        pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
+        head: 'fc' (Cnn_AvgPooling), 'gru' (CRNN), 'sa' (Csa_AvgPooling: a self-attention encoder layer with sa_heads heads between the
+        mel-mean and event_fc, csrc/sed_mhsa.hip; pos_encoding adds the fixed sinusoidal table to the mel-mean rows)
+        or 'none' (a bare stack of ConvBlocks: forward() stops at the last pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
         Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and backward() also produces the input gradient
         plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path keeps the dedicated Cin = 1
         kernels (no input gradient exists there).  mel_bins: None -> every block's width must be one the specialised kernels
@@ -238,11 +241,17 @@ class CnnEngine(OptimizerExtMixin):
         width-general kernels (csrc/sed_conv_anyw.hip; under 'f16x3' / 'bf16x3' those layers take the exact fp32 kernels)."""
         if precision not in ("bf16", "fp32", "bf16x3", "f16x3"):
             raise ValueError("precision must be 'bf16', 'fp32', 'f16x3' or 'bf16x3'")
-        if head not in ("fc", "gru", "none"):
-            raise ValueError("head must be 'fc' (Cnn_AvgPooling), 'gru' (CRNN) or 'none' (ConvBlock stack)")
+        if head not in ("fc", "gru", "sa", "none"):
+            raise ValueError("head must be 'fc' (Cnn_AvgPooling), 'gru' (CRNN), 'sa' (self-attention) or 'none' (ConvBlock stack)")
         if head == "gru" and (gru_hidden % 32 or not 32 <= gru_hidden <= 256):
             raise ValueError("gru_hidden must be a multiple of 32 in [32, 256]")
         self.head, self.Hd = head, int(gru_hidden)
+        self.sa_heads, self.pos_encoding = int(sa_heads), bool(pos_encoding)
+        if head == "sa":
+            Cl = int(list(model_config)[-1][0])
+            if self.sa_heads < 1 or Cl % 4 or Cl % self.sa_heads or Cl // self.sa_heads not in (32, 64):
+                raise ValueError(f"the self-attention head needs channels % 4 == 0 and a head width channels / sa_heads of 32 or 64 "
+                                 f"(channels {Cl}, sa_heads {sa_heads})")
         self.attention = bool(attention)
         if self.attention and head == "none":
             raise ValueError("the attention head sits beside event_fc: it needs a model with a classification head")
@@ -404,6 +413,8 @@ class CnnEngine(OptimizerExtMixin):
             self._plan_att(p, B, H, Cfc, dev)
         if self.head == "gru":
             p.gru = self._plan_gru(B, H, Cl, dev)
+        if self.head == "sa":
+            p.sa = self._plan_sa(B, H, Cl, dev)
         p.wgrad_ws = torch.empty(max(1, max_wgrad_ws), **f32)
         l0 = p.layers[0][0]
         p.c1_ws = torch.empty((lib.sed_conv_c1_nparts(B, T, F), 9, l0.coutp), **f32)
@@ -487,6 +498,9 @@ class CnnEngine(OptimizerExtMixin):
         if self.head == "gru":
             g = p.gru
             return L.SED_F32, g["fc_m"], g["R"], 1, 2 * self.Hd, 2 * self.Hd, g["dhseq"]
+        if self.head == "sa":
+            g, C = p.sa, self.cfg[-1][0]
+            return L.SED_F32, g["fc_m"], g["R"], 1, C, C, g["dh"]
         Cl = self.cfg[-1][0]
         return self.dt, p.m, p.B * p.t_out, p.w_out, Cl, pad32(Cl), p.dy[len(self.cfg) - 1]
 
@@ -616,6 +630,100 @@ class CnnEngine(OptimizerExtMixin):
         self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dgi"]), 6 * Hd, L.ptr(g["wihT"]), 6 * Hd, None, L.ptr(g["dm"]),
                 Cl, R, Cl, 6 * Hd, 1, None, st)
         self._k("sed_mel_mean_bwd", lib.sed_mel_mean_bwd, dt, L.ptr(g["dm"]), L.ptr(dfeat), R, p.w_out, Cl, pad32(Cl), st)
+        self._tag = ""
+
+    def _plan_sa(self, B, t, C, dev):
+        """Buffers of the self-attention head (every one allocated here: a captured step allocates nothing); R = B*t rows."""
+        lib, Hh = self.lib, self.sa_heads
+        f32 = dict(dtype=torch.float32, device=dev)
+        R = B * t
+        g = dict(R=R)
+        for name, cols in (("m", C), ("qkv", 3 * C), ("ctx", C), ("a", C), ("h", C), ("fc_m", C), ("dh", C), ("dres", C), ("dctx", C),
+                           ("dqkv", 3 * C), ("dm", C)):
+            g[name] = torch.empty((R, cols), **f32)
+        g["lse"] = torch.empty((B, Hh, t), **f32)
+        g["stats"] = torch.empty((R, 2), **f32)
+        g["woT"] = torch.empty((C, C), **f32)
+        g["winT"] = torch.empty((C, 3 * C), **f32)
+        g["pe"] = None
+        if self.pos_encoding:
+            # the standard table, built on the host in float64 and rounded once to fp32: pe[i][2j] = sin(i / 10000^(2j/C)), pe[i][2j+1] = cos(.)
+            i = torch.arange(t, dtype=torch.float64)[:, None]
+            j2 = (torch.arange(C) // 2 * 2).to(torch.float64)[None, :]
+            ang = i / torch.pow(torch.tensor(10000.0, dtype=torch.float64), j2 / C)
+            g["pe"] = torch.where((torch.arange(C) % 2 == 0)[None, :], torch.sin(ang), torch.cos(ang)).to(torch.float32).to(dev)
+        g["core_ws"] = torch.empty(max(1, lib.sed_mhsa_bwd_ws_floats(B, t, Hh, C // Hh)), **f32)
+        g["ln_ws"] = torch.empty(max(1, lib.sed_add_layernorm_bwd_ws_floats(R, C)), **f32)
+        # split-K of the two weight-gradient products (K = R rows), as the recurrent head's tail: SED_GRU_KSPLIT, read with the plan
+        g["ksplit"] = max(1, int(_os.environ.get("SED_GRU_KSPLIT", "64")))
+        g["tn_ws"] = torch.empty(max(1, lib.sed_gemm_tn_ws_floats(3 * C, C, g["ksplit"])), **f32)
+        return g
+
+    def _sa_forward(self, p, P, feat, training):
+        lib, dt, st, g, Hh = self.lib, self.dt, _stream(), p.sa, self.sa_heads
+        B, t = p.B, p.t_out
+        C = self.cfg[-1][0]
+        R = g["R"]
+        self._tag = "sa"
+        self._k("sed_mel_mean_fwd", lib.sed_mel_mean_fwd, dt, L.ptr(feat), L.ptr(g["m"]), R, p.w_out, C, pad32(C), st)
+        if g["pe"] is not None:
+            g["m"].view(B, t, C).add_(g["pe"])          # x' = x + pe[frame], in place: the residual and the projections read x'
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["m"]), C, L.ptr(P["attn.in_proj_weight"]), C, L.ptr(P["attn.in_proj_bias"]),
+                L.ptr(g["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
+        self._k("sed_mhsa_fwd", lib.sed_mhsa_fwd, dt, L.ptr(g["qkv"]), L.ptr(g["ctx"]), L.ptr(g["lse"]) if training else None,
+                B, t, Hh, C // Hh, st)
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["ctx"]), C, L.ptr(P["attn.out_proj.weight"]), C,
+                L.ptr(P["attn.out_proj.bias"]), L.ptr(g["a"]), C, R, C, C, 1, None, st)
+        self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(g["m"]), L.ptr(g["a"]), L.ptr(P["attn_norm.weight"]),
+                L.ptr(P["attn_norm.bias"]), L.ptr(g["h"]), L.ptr(g["stats"]) if training else None, R, C, LN_EPS, st)
+        self._k("sed_head_fwd", lib.sed_head_fwd, L.SED_F32, L.ptr(g["h"]), L.ptr(P["event_fc.weight"]), L.ptr(P["event_fc.bias"]),
+                L.ptr(g["fc_m"]), L.ptr(p.pre), B, t, 1, C, C, self.K, st)
+        if self.attention:
+            self._att_forward(p, P)
+        self._tag = ""
+
+    def _sa_backward(self, p, P, G, src, ratio, dfeat, on_group_done):
+        lib, dt, st, g, Hh = self.lib, self.dt, _stream(), p.sa, self.sa_heads
+        B, t = p.B, p.t_out
+        C = self.cfg[-1][0]
+        R = g["R"]
+        self._tag = "sa"
+        if self.attention:
+            self._att_head_backward(p, P, G, src, ratio, on_group_done)
+        else:
+            self._k("sed_head_bwd", lib.sed_head_bwd, L.SED_F32, L.ptr(src), L.ptr(g["fc_m"]), L.ptr(P["event_fc.weight"]),
+                    L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(g["dh"]), L.ptr(p.head_ws), B, t, 1, C, C, self.K,
+                    ratio, st)
+            if on_group_done is not None:
+                on_group_done("event_fc")
+        self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(g["dh"]), L.ptr(g["m"]), L.ptr(g["a"]),
+                L.ptr(P["attn_norm.weight"]), L.ptr(g["stats"]), L.ptr(g["dres"]), L.ptr(G["attn_norm.weight"]),
+                L.ptr(G["attn_norm.bias"]), L.ptr(g["ln_ws"]), R, C, st)
+        if on_group_done is not None:
+            on_group_done("attn_norm")
+        ks = max(1, min(g["ksplit"], R // 256))
+        ws = L.ptr(g["tn_ws"]) if ks > 1 else None
+        # d out_proj.weight = dres^T . ctx, d out_proj.bias = column sums of dres
+        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dres"]), C, L.ptr(g["ctx"]), C, L.ptr(G["attn.out_proj.weight"]), C,
+                L.ptr(G["attn.out_proj.bias"]), C, C, R, t, 0, ks, ws, st)
+        # dctx = dres . out_proj.weight
+        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P["attn.out_proj.weight"]), C, L.ptr(g["woT"]), C, C, C, C, 0, st)
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dres"]), C, L.ptr(g["woT"]), C, None, L.ptr(g["dctx"]), C, R, C, C, 1,
+                None, st)
+        self._k("sed_mhsa_bwd", lib.sed_mhsa_bwd, dt, L.ptr(g["qkv"]), L.ptr(g["ctx"]), L.ptr(g["dctx"]), L.ptr(g["lse"]),
+                L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, st)
+        # d in_proj_weight = dqkv^T . x', d in_proj_bias = column sums of dqkv
+        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dqkv"]), 3 * C, L.ptr(g["m"]), C, L.ptr(G["attn.in_proj_weight"]), C,
+                L.ptr(G["attn.in_proj_bias"]), 3 * C, C, R, t, 0, ks, ws, st)
+        if on_group_done is not None:
+            on_group_done("attn")
+        # dm = dqkv . in_proj_weight + dres (the residual branch), then back through the mel mean
+        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P["attn.in_proj_weight"]), C, L.ptr(g["winT"]), 3 * C, 3 * C, C,
+                3 * C, 0, st)
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dqkv"]), 3 * C, L.ptr(g["winT"]), 3 * C, None, L.ptr(g["dm"]), C, R, C,
+                3 * C, 1, None, st)
+        g["dm"].add_(g["dres"])
+        self._k("sed_mel_mean_bwd", lib.sed_mel_mean_bwd, dt, L.ptr(g["dm"]), L.ptr(dfeat), R, p.w_out, C, pad32(C), st)
         self._tag = ""
 
     # ------------------------------------------------------------------------------------------
@@ -761,6 +869,9 @@ class CnnEngine(OptimizerExtMixin):
         self._tag = ""
         if self.head == "gru":
             self._gru_forward(p, P, prev, training or p.keep)
+            return p
+        if self.head == "sa":
+            self._sa_forward(p, P, prev, training or p.keep)
             return p
         if self.head == "none":
             return p
@@ -1003,6 +1114,8 @@ class CnnEngine(OptimizerExtMixin):
             pass                      # the caller filled plan.dy[-1] (gradient of the last pooled block output)
         elif self.head == "gru":
             self._gru_backward(p, P, G, src, ratio, p.dy[nb - 1], on_group_done)
+        elif self.head == "sa":
+            self._sa_backward(p, P, G, src, ratio, p.dy[nb - 1], on_group_done)
         elif self.attention:
             self._att_head_backward(p, P, G, src, ratio, on_group_done)
         else:

@@ -136,8 +136,15 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     attention = "att_fc.weight" in weights    # an --attention_head training: the head is rebuilt from the checkpoint's own keys
     if clip_pooling == "att" and not attention:
         raise ValueError(f"--clip_pooling att needs a checkpoint with the attention head: {ckpt} holds no 'att_fc.weight'")
-    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel,
-                           frontend=frontend, attention=attention).to(dev)
+    model_config = [(32, 2), (64, 2), (128, 2), (128, 1)]
+    if "attn.in_proj_weight" in weights:      # a --self_attention training: heads and positional flag from the checkpoint's attn_config
+        from .models.spectogram_models import Csa_AvgPooling
+        heads, pos = Csa_AvgPooling.config_from_state_dict(weights)
+        model = Csa_AvgPooling(cfg.classes_num, model_config=model_config, sa_heads=heads, pos_encoding=pos, mel_bins=n_mel,
+                               frontend=frontend, attention=attention).to(dev)
+    else:
+        model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend,
+                               attention=attention).to(dev)
     model.set_precision(precision)
     model.load_state_dict(weights)
     model.eval()

@@ -114,6 +114,12 @@ def build_weak_parser():
     p.add_argument("--attention_head", action="store_true", default=False,
                    help="this build only: build the model with the attention pooling head, a second linear layer att_fc beside "
                         "event_fc whose softmax over time weighs the frame probabilities of a clip (pooling att)")
+    p.add_argument("--self_attention", action="store_true", default=False,
+                   help="this build only: build the model with the self-attention temporal head (Csa_AvgPooling: one multi-head "
+                        "attention encoder layer over the frames of a clip between the mel-mean and event_fc); Spectogram features only")
+    p.add_argument("--sa_heads", type=int, default=4, help="--self_attention: attention heads (the head width 128 / N must be 32 or 64)")
+    p.add_argument("--no_pos_encoding", action="store_true", default=False,
+                   help="--self_attention: leave out the sinusoidal positional table")
     return p
 
 
@@ -342,8 +348,13 @@ def get_spectogram_dataset_model_and_criterion(args, device):
                                     preprocessed_mode=args.preprocess_mode, cfg=cfg, device=device,
                                     spec_augment=spec_augment_config(args))
     frontend = build_pcen(args, n_mel, getattr(dataset, "mean", None), getattr(dataset, "std", None))
-    model = Cnn_AvgPooling(cfg.classes_num, model_config=[(32, 2), (64, 2), (128, 2), (128, 1)], mel_bins=n_mel, frontend=frontend,
-                           attention=bool(getattr(args, "attention_head", False)))
+    model_config, att = [(32, 2), (64, 2), (128, 2), (128, 1)], bool(getattr(args, "attention_head", False))
+    if getattr(args, "self_attention", False):
+        from .models.spectogram_models import Csa_AvgPooling
+        model = Csa_AvgPooling(cfg.classes_num, model_config=model_config, sa_heads=int(args.sa_heads),
+                               pos_encoding=not args.no_pos_encoding, mel_bins=n_mel, frontend=frontend, attention=att)
+    else:
+        model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend, attention=att)
     model.set_precision(args.precision)
     if args.ckpt != "":
         checkpoint = torch.load(args.ckpt, map_location=device)
@@ -418,6 +429,13 @@ def validate_args(args):
     if att_head and args.train_features.lower() == "waveform":
         raise ValueError("--attention_head sits beside the frame-wise head: it needs --train_features Spectogram "
                          "(the M5 model has no time axis in its output)")
+    if getattr(args, "self_attention", False):
+        if args.train_features.lower() == "waveform":
+            raise ValueError("--self_attention attends over the frames of the spectrogram models: it needs --train_features Spectogram")
+        from .models.spectogram_models import check_sa_geometry
+        check_sa_geometry(128, getattr(args, "sa_heads", 4))
+    elif getattr(args, "sa_heads", 4) != 4 or getattr(args, "no_pos_encoding", False):
+        raise ValueError("--sa_heads / --no_pos_encoding configure the self-attention head: they need --self_attention")
     for flag, value in (("--weak_pooling", weak_options(args).get("weak_pooling")), ("--eval_clip_pooling", getattr(args, "eval_clip_pooling", None))):
         if value == "att" and not att_head:
             raise ValueError(f"{flag} att pools with the attention head: it needs --attention_head")

@@ -379,3 +379,86 @@ class Crnn_AvgPooling(Cnn_AvgPooling):
     def _make_engine(self, precision):
         return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="gru",
                          gru_hidden=self.gru_hidden, mel_bins=self.mel_bins, attention=self.attention)
+
+
+class _MhaParams(nn.Module):
+    """Parameter holder with torch.nn.MultiheadAttention(C, heads, batch_first=True)'s names, shapes and initialisation:
+    in_proj_weight (3C, C) xavier-uniform, in_proj_bias (3C,) zeros, out_proj.weight (C, C) nn.Linear's default, out_proj.bias (C,)
+    zeros.  RNG draw order, as that module's constructor: out_proj.weight, out_proj.bias (nn.Linear's draw, then overwritten
+    with zeros), in_proj_weight."""
+
+    def __init__(self, embed_dim, num_heads):
+        super().__init__()
+        self.embed_dim, self.num_heads = embed_dim, num_heads
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        self.in_proj_bias = nn.Parameter(torch.empty(3 * embed_dim))
+        self.out_proj = _LinearParams(embed_dim, embed_dim)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        nn.init.constant_(self.in_proj_bias, 0.0)
+        nn.init.constant_(self.out_proj.bias, 0.0)
+
+
+class _LayerNormParams(nn.Module):
+    """Parameter holder with torch.nn.LayerNorm(C)'s names (eps 1e-5): weight ones, bias zeros, no random draw."""
+
+    def __init__(self, normalized_shape):
+        super().__init__()
+        self.normalized_shape = (normalized_shape,)
+        self.weight = nn.Parameter(torch.ones(normalized_shape))
+        self.bias = nn.Parameter(torch.zeros(normalized_shape))
+
+
+def check_sa_geometry(channels: int, heads: int) -> int:
+    """The head width dh = C / H of the self-attention head, or a ValueError for what the kernels do not cover (host only)."""
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"sa_heads must be a positive integer, got {heads!r}")
+    if channels % 4:
+        raise ValueError(f"the self-attention head needs a channel count that is a multiple of 4, got {channels}")
+    if channels % heads:
+        raise ValueError(f"the last block's {channels} channels do not divide into sa_heads={heads} heads")
+    if channels // heads not in (32, 64):
+        raise ValueError(f"head width {channels // heads} unsupported (channels {channels} / sa_heads {heads}): the attention "
+                         "kernels cover head widths 32 and 64")
+    return channels // heads
+
+
+class Csa_AvgPooling(Cnn_AvgPooling):
+    """The Cnn_AvgPooling feature extractor with a self-attention encoder layer as the temporal head (the conv-Transformer family
+    of the DCASE task-4 systems; csrc/sed_mhsa.hip).  With R = B*t rows and C the last block's channels:
+        x   = mean over mel of the conv features                           [R][C]
+        x'  = x + pe[i]   (pos_encoding; i = frame inside the clip, pe[i][2j] = sin(i / 10000^(2j/C)), pe[i][2j+1] = cos(the same),
+                           built in float64, rounded once to fp32; not a parameter, not in the state_dict)
+        qkv = x' . attn.in_proj_weight^T + attn.in_proj_bias               [R][3C]
+        ctx = multi-head attention: sa_heads heads of dh = C / sa_heads, softmax over the t frames of the same clip, scores
+              scaled by 1/sqrt(dh), no mask, no dropout
+        a   = ctx . attn.out_proj.weight^T + attn.out_proj.bias
+        h   = LayerNorm(x' + a) (attn_norm; eps 1e-5, affine)
+        event_fc(h) (and att_fc(h) with attention=True) -> interpolate as before
+    No feed-forward sub-layer, one layer.  The semantics are torch.nn.MultiheadAttention(C, sa_heads, batch_first=True)'s and
+    torch.nn.LayerNorm(C)'s, and attn.* / attn_norm.* of the state_dict load into those modules.  The float64 buffer attn_config =
+    (sa_heads, pos_encoding) makes the head rebuildable from a state_dict alone (from_state_dict).
+    RNG draw order: conv_blocks as always, then attn.out_proj.weight, attn.out_proj.bias (drawn, then zeroed), attn.in_proj_weight
+    (torch's constructor order), event_fc's draws and its init_layer, then att_fc's with attention=True.
+    Refused: C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0."""
+
+    def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, sa_heads=4, pos_encoding=True,
+                 mel_bins=None, frontend=None, attention=False):
+        check_sa_geometry(int(model_config[-1][0]), sa_heads)
+        self.sa_heads, self.pos_encoding = int(sa_heads), bool(pos_encoding)
+        super().__init__(classes_num, model_config, precision, mel_bins=mel_bins, frontend=frontend, attention=attention)
+
+    def _build_head(self, c_last, classes_num):
+        self.attn = _MhaParams(c_last, self.sa_heads)
+        self.attn_norm = _LayerNormParams(c_last)
+        self.register_buffer("attn_config", torch.tensor([float(self.sa_heads), float(self.pos_encoding)], dtype=torch.float64))
+        self.event_fc = _LinearParams(c_last, classes_num)
+
+    def _make_engine(self, precision):
+        return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="sa", sa_heads=self.sa_heads,
+                         pos_encoding=self.pos_encoding, mel_bins=self.mel_bins, attention=self.attention)
+
+    @staticmethod
+    def config_from_state_dict(weights):
+        """(sa_heads, pos_encoding) from a state_dict's attn_config"""
+        cfg = weights["attn_config"].detach().cpu().double().tolist()
+        return int(round(cfg[0])), bool(round(cfg[1]))
