@@ -1079,7 +1079,30 @@ int    sed_add_layernorm_bwd(const float* dy, const float* x, const float* a, co
                              float* dres, float* dgamma, float* dbeta, float* workspace,
                              size_t rows, int C, void* stream);
 
-/* ---- utilities -----------------------------------------------------------------------------*/
+/* ---- feed-forward sub-layer of the self-attention head (csrc/sed_ffn.hip) ---------------------
+ * The position-wise MLP of torch.nn.TransformerEncoderLayer(C, H, D, dropout=0) between its two LayerNorms (those are
+ * sed_add_layernorm_fwd launches).  x [R][C], w1 [D][C] (linear1.weight), b1 [D], w2 [C][D] (linear2.weight), b2 [C], row-major fp32:
+ *   u = x . w1^T + b1,   a = act(u),   y = a . w2^T + b2                        y [R][C], u [R][D] (NULL for inference: same y bits)
+ *   act: SED_ACT_RELU max(u, 0);  SED_ACT_GELU the erf form 0.5 u (1 + erf(u / sqrt 2)), torch.nn.functional.gelu's default
+ * One launch: a workgroup owns 32 rows, keeps its x tile in LDS and walks D in steps of 128; the hidden tensor a never reaches global
+ * memory, and the fp32 pre-activation u (accumulator plus bias, before any rounding) only when u is given, once, for the backward.
+ * dtype: SED_BF16 rounds x, w1, w2 and a to bf16 (nearest even) as MFMA operands only; both accumulations, the bias adds, the
+ * activation and every stored value are fp32.  SED_F32: the fp32-input MFMA, exact products.  (The f16x3 / bf16x3 engines pass SED_F32.)
+ * No atomics: the same bits on every run.  Rows past R are never read or written.
+ * sed_ffn_act_bwd, elementwise fp32 over n values:  a = act(u),  du = da * act'(u);  ReLU: act' = 1 for u > 0, else 0 (torch's
+ * convention at 0);  GELU: Phi(u) + u phi(u).  a may be u and du may be da (each element is read before it is written); 16-byte
+ * accesses when the four pointers are 16-byte aligned.  The rest of the backward is existing launches: sed_transpose_shift of w2 +
+ * sed_gemm_nt (da = dy . w2), sed_gemm_tn (dw2 = dy^T . a, db2 its column sums), sed_gemm_tn (dw1 = du^T . x, db1), sed_transpose_shift
+ * of w1 + sed_gemm_nt (dx = du . w1).
+ * Refused (non-zero, nothing launched): R <= 0, C or D not a multiple of 32, C > 512, D > 4096, an unknown dtype or act, a NULL
+ * pointer other than u, x / w1 / w2 / y / u not 16-byte aligned; sed_ffn_act_bwd: n <= 0, a NULL pointer, a partly overlapping
+ * (a, u) or (du, da) pair or any other overlap of an output with another buffer.                                                */
+enum { SED_ACT_RELU = 0, SED_ACT_GELU = 1 };
+int sed_ffn_fwd(int dtype, int act, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                float* y, float* u, size_t R, int C, int D, void* stream);
+int sed_ffn_act_bwd(int act, const float* u, const float* da, float* a, float* du, size_t n, void* stream);
+
+/* ---- utilities-----------------------------------------------------------------------------*/
 /* out[i] = sum_{s<nparts} partial[s][i], i < n (fixed order: deterministic)                     */
 int sed_sum_partials(const float* partial, int nparts, size_t n, float* out, void* stream);
 /* fp32 [n] <-> dtype [n] casts (fp32 -> bf16 rounds to nearest even, NaN stays NaN);

@@ -6,6 +6,8 @@ import ctypes as C
 import os
 
 SED_F32, SED_BF16, SED_F32X3, SED_F32H3 = 0, 1, 2, 3
+SED_ACT_RELU, SED_ACT_GELU = 0, 1
+FFN_ACT = {"relu": SED_ACT_RELU, "gelu": SED_ACT_GELU}      # sed_ffn_fwd / sed_ffn_act_bwd
 PRO_NONE, PRO_BNRELU = 0, 1
 EPI_STORE, EPI_STATS, EPI_RELUBWD, EPI_POOLSTATS = 0, 1, 2, 4
 DZ_POOL, DZ_BN = 1, 2
@@ -173,6 +175,8 @@ PROTOTYPES = {
     "sed_add_layernorm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _F, _P]),
     "sed_add_layernorm_bwd_ws_floats": (_Z, [_Z, _I]),
     "sed_add_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _P]),
+    "sed_ffn_fwd": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _P]),
+    "sed_ffn_act_bwd": (_I, [_I, _P, _P, _P, _P, _Z, _P]),
     "sed_m5_conv1_len": (_I, [_I]),
     "sed_m5_conv1_nparts": (_I, [_I, _I]),
     "sed_m5_conv1_fwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _P]),

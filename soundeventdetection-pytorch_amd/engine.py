@@ -227,12 +227,15 @@ class OptimizerExtMixin:
 class CnnEngine(OptimizerExtMixin):
     def __init__(self, classes_num: int, model_config: Sequence[Tuple[int, int]], in_channels: int = 1,
                  precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
-                 mel_bins: Optional[int] = None, attention: bool = False, sa_heads: int = 4, pos_encoding: bool = True):
+                 mel_bins: Optional[int] = None, attention: bool = False, sa_heads: int = 4, pos_encoding: bool = True,
+                 sa_layers: int = 1, sa_ffn: int = 0, sa_activation: str = "relu"):
         """attention: a second linear layer att_fc beside event_fc scores every frame per class (csrc/sed_attn.hip): forward()
         also leaves the attention logits in plan.att, loss_and_grad(weak=("att", ...)) pools with them and backward() then takes
         both layers.  False launches exactly what it always did.
         head: 'fc' (Cnn_AvgPooling), 'gru' (CRNN), 'sa' (Csa_AvgPooling: a self-attention encoder layer with sa_heads heads between the
-        mel-mean and event_fc, csrc/sed_mhsa.hip; pos_encoding adds the fixed sinusoidal table to the mel-mean rows)
+        mel-mean and event_fc, csrc/sed_mhsa.hip; pos_encoding adds the fixed sinusoidal table to the mel-mean rows; sa_layers post-LN
+        encoder layers, each with a feed-forward sub-layer of width sa_ffn > 0 and activation sa_activation behind the attention,
+        csrc/sed_ffn.hip -- torch.nn.TransformerEncoderLayer(C, sa_heads, sa_ffn, dropout=0, norm_first=False) semantics)
         or 'none' (a bare stack of ConvBlocks: forward() stops at the last pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
         Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and backward() also produces the input gradient
         plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path keeps the dedicated Cin = 1
@@ -247,7 +250,17 @@ class CnnEngine(OptimizerExtMixin):
             raise ValueError("gru_hidden must be a multiple of 32 in [32, 256]")
         self.head, self.Hd = head, int(gru_hidden)
         self.sa_heads, self.pos_encoding = int(sa_heads), bool(pos_encoding)
+        self.sa_layers, self.sa_ffn, self.sa_activation = int(sa_layers), int(sa_ffn), sa_activation
         if head == "sa":
+            if self.sa_layers < 1:
+                raise ValueError(f"sa_layers must be at least 1, got {sa_layers!r}")
+            if self.sa_ffn < 0 or self.sa_ffn % 32 or self.sa_ffn > 4096:
+                raise ValueError(f"sa_ffn must be 0 (no feed-forward sub-layer) or a multiple of 32 up to 4096, got {sa_ffn!r}")
+            if sa_activation not in L.FFN_ACT:
+                raise ValueError(f"sa_activation must be 'relu' or 'gelu', got {sa_activation!r}")
+            self.sa_act = L.FFN_ACT[sa_activation]
+            if self.sa_ffn and int(list(model_config)[-1][0]) > 512:
+                raise ValueError("the feed-forward sub-layer takes at most 512 channels")
             Cl = int(list(model_config)[-1][0])
             if self.sa_heads < 1 or Cl % 4 or Cl % self.sa_heads or Cl // self.sa_heads not in (32, 64):
                 raise ValueError(f"the self-attention head needs channels % 4 == 0 and a head width channels / sa_heads of 32 or 64 "
@@ -632,19 +645,36 @@ class CnnEngine(OptimizerExtMixin):
         self._k("sed_mel_mean_bwd", lib.sed_mel_mean_bwd, dt, L.ptr(g["dm"]), L.ptr(dfeat), R, p.w_out, Cl, pad32(Cl), st)
         self._tag = ""
 
+    @staticmethod
+    def sa_layer_names(l):
+        """(attn, attn_norm, ffn, ffn_norm) module names of encoder layer l: layer 0 keeps the one-layer head's names"""
+        sfx = "" if l == 0 else f"_l{l}"
+        return "attn" + sfx, "attn_norm" + sfx, "ffn" + sfx, "ffn_norm" + sfx
+
     def _plan_sa(self, B, t, C, dev):
-        """Buffers of the self-attention head (every one allocated here: a captured step allocates nothing); R = B*t rows."""
-        lib, Hh = self.lib, self.sa_heads
+        """Buffers of the self-attention head (every one allocated here: a captured step allocates nothing); R = B*t rows.  What a
+        layer's backward reads of its forward is kept per layer (g["layers"]); the gradients in flight are shared by the layers."""
+        lib, Hh, D = self.lib, self.sa_heads, self.sa_ffn
         f32 = dict(dtype=torch.float32, device=dev)
         R = B * t
         g = dict(R=R)
-        for name, cols in (("m", C), ("qkv", 3 * C), ("ctx", C), ("a", C), ("h", C), ("fc_m", C), ("dh", C), ("dres", C), ("dctx", C),
-                           ("dqkv", 3 * C), ("dm", C)):
+        for name, cols in (("m", C), ("fc_m", C), ("dh", C), ("dres", C), ("dctx", C), ("dqkv", 3 * C), ("dm", C)):
             g[name] = torch.empty((R, cols), **f32)
-        g["lse"] = torch.empty((B, Hh, t), **f32)
-        g["stats"] = torch.empty((R, 2), **f32)
+        g["layers"] = []
+        for _ in range(self.sa_layers):
+            ly = {name: torch.empty((R, cols), **f32) for name, cols in (("qkv", 3 * C), ("ctx", C), ("a", C), ("h", C), ("stats", 2))}
+            ly["lse"] = torch.empty((B, Hh, t), **f32)
+            if D:
+                ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("u", D), ("f", C), ("h2", C), ("stats2", 2))})
+            g["layers"].append(ly)
+        g["h"] = g["layers"][-1]["h2" if D else "h"]          # what event_fc (and att_fc) read
         g["woT"] = torch.empty((C, C), **f32)
         g["winT"] = torch.empty((C, 3 * C), **f32)
+        if D:
+            # the FFN backward: a and the hidden gradient (da, then du in place), the gradient behind the FFN, the transposed weights
+            g["ffa"], g["fda"] = torch.empty((R, D), **f32), torch.empty((R, D), **f32)
+            g["dh1"] = torch.empty((R, C), **f32)
+            g["w2T"], g["w1T"] = torch.empty((D, C), **f32), torch.empty((C, D), **f32)
         g["pe"] = None
         if self.pos_encoding:
             # the standard table, built on the host in float64 and rounded once to fp32: pe[i][2j] = sin(i / 10000^(2j/C)), pe[i][2j+1] = cos(.)
@@ -654,13 +684,16 @@ class CnnEngine(OptimizerExtMixin):
             g["pe"] = torch.where((torch.arange(C) % 2 == 0)[None, :], torch.sin(ang), torch.cos(ang)).to(torch.float32).to(dev)
         g["core_ws"] = torch.empty(max(1, lib.sed_mhsa_bwd_ws_floats(B, t, Hh, C // Hh)), **f32)
         g["ln_ws"] = torch.empty(max(1, lib.sed_add_layernorm_bwd_ws_floats(R, C)), **f32)
-        # split-K of the two weight-gradient products (K = R rows), as the recurrent head's tail: SED_GRU_KSPLIT, read with the plan
+        # split-K of the weight-gradient products (K = R rows), as the recurrent head's tail: SED_GRU_KSPLIT, read with the plan
         g["ksplit"] = max(1, int(_os.environ.get("SED_GRU_KSPLIT", "64")))
-        g["tn_ws"] = torch.empty(max(1, lib.sed_gemm_tn_ws_floats(3 * C, C, g["ksplit"])), **f32)
+        tn = [lib.sed_gemm_tn_ws_floats(3 * C, C, g["ksplit"])]
+        if D:
+            tn += [lib.sed_gemm_tn_ws_floats(C, D, g["ksplit"]), lib.sed_gemm_tn_ws_floats(D, C, g["ksplit"])]
+        g["tn_ws"] = torch.empty(max(1, max(tn)), **f32)
         return g
 
     def _sa_forward(self, p, P, feat, training):
-        lib, dt, st, g, Hh = self.lib, self.dt, _stream(), p.sa, self.sa_heads
+        lib, dt, st, g, Hh, D = self.lib, self.dt, _stream(), p.sa, self.sa_heads, self.sa_ffn
         B, t = p.B, p.t_out
         C = self.cfg[-1][0]
         R = g["R"]
@@ -668,14 +701,26 @@ class CnnEngine(OptimizerExtMixin):
         self._k("sed_mel_mean_fwd", lib.sed_mel_mean_fwd, dt, L.ptr(feat), L.ptr(g["m"]), R, p.w_out, C, pad32(C), st)
         if g["pe"] is not None:
             g["m"].view(B, t, C).add_(g["pe"])          # x' = x + pe[frame], in place: the residual and the projections read x'
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["m"]), C, L.ptr(P["attn.in_proj_weight"]), C, L.ptr(P["attn.in_proj_bias"]),
-                L.ptr(g["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
-        self._k("sed_mhsa_fwd", lib.sed_mhsa_fwd, dt, L.ptr(g["qkv"]), L.ptr(g["ctx"]), L.ptr(g["lse"]) if training else None,
-                B, t, Hh, C // Hh, st)
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["ctx"]), C, L.ptr(P["attn.out_proj.weight"]), C,
-                L.ptr(P["attn.out_proj.bias"]), L.ptr(g["a"]), C, R, C, C, 1, None, st)
-        self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(g["m"]), L.ptr(g["a"]), L.ptr(P["attn_norm.weight"]),
-                L.ptr(P["attn_norm.bias"]), L.ptr(g["h"]), L.ptr(g["stats"]) if training else None, R, C, LN_EPS, st)
+        xin = g["m"]
+        for l, ly in enumerate(g["layers"]):
+            an, nn_, fn, fnn = self.sa_layer_names(l)
+            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(xin), C, L.ptr(P[an + ".in_proj_weight"]), C, L.ptr(P[an + ".in_proj_bias"]),
+                    L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
+            self._k("sed_mhsa_fwd", lib.sed_mhsa_fwd, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(ly["lse"]) if training else None,
+                    B, t, Hh, C // Hh, st)
+            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["ctx"]), C, L.ptr(P[an + ".out_proj.weight"]), C,
+                    L.ptr(P[an + ".out_proj.bias"]), L.ptr(ly["a"]), C, R, C, C, 1, None, st)
+            self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(xin), L.ptr(ly["a"]), L.ptr(P[nn_ + ".weight"]),
+                    L.ptr(P[nn_ + ".bias"]), L.ptr(ly["h"]), L.ptr(ly["stats"]) if training else None, R, C, LN_EPS, st)
+            xin = ly["h"]
+            if D:
+                # h2 = LayerNorm(h + ffn(h)): both products and the activation in one launch; u only for a backward
+                self._k("sed_ffn_fwd", lib.sed_ffn_fwd, dt, self.sa_act, L.ptr(ly["h"]), L.ptr(P[fn + ".linear1.weight"]),
+                        L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(ly["f"]),
+                        L.ptr(ly["u"]) if training else None, R, C, D, st)
+                self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(ly["h"]), L.ptr(ly["f"]), L.ptr(P[fnn + ".weight"]),
+                        L.ptr(P[fnn + ".bias"]), L.ptr(ly["h2"]), L.ptr(ly["stats2"]) if training else None, R, C, LN_EPS, st)
+                xin = ly["h2"]
         self._k("sed_head_fwd", lib.sed_head_fwd, L.SED_F32, L.ptr(g["h"]), L.ptr(P["event_fc.weight"]), L.ptr(P["event_fc.bias"]),
                 L.ptr(g["fc_m"]), L.ptr(p.pre), B, t, 1, C, C, self.K, st)
         if self.attention:
@@ -683,46 +728,75 @@ class CnnEngine(OptimizerExtMixin):
         self._tag = ""
 
     def _sa_backward(self, p, P, G, src, ratio, dfeat, on_group_done):
-        lib, dt, st, g, Hh = self.lib, self.dt, _stream(), p.sa, self.sa_heads
+        lib, dt, st, g, Hh, D = self.lib, self.dt, _stream(), p.sa, self.sa_heads, self.sa_ffn
         B, t = p.B, p.t_out
         C = self.cfg[-1][0]
         R = g["R"]
         self._tag = "sa"
+        done = on_group_done if on_group_done is not None else (lambda name: None)
         if self.attention:
             self._att_head_backward(p, P, G, src, ratio, on_group_done)
         else:
             self._k("sed_head_bwd", lib.sed_head_bwd, L.SED_F32, L.ptr(src), L.ptr(g["fc_m"]), L.ptr(P["event_fc.weight"]),
                     L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(g["dh"]), L.ptr(p.head_ws), B, t, 1, C, C, self.K,
                     ratio, st)
-            if on_group_done is not None:
-                on_group_done("event_fc")
-        self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(g["dh"]), L.ptr(g["m"]), L.ptr(g["a"]),
-                L.ptr(P["attn_norm.weight"]), L.ptr(g["stats"]), L.ptr(g["dres"]), L.ptr(G["attn_norm.weight"]),
-                L.ptr(G["attn_norm.bias"]), L.ptr(g["ln_ws"]), R, C, st)
-        if on_group_done is not None:
-            on_group_done("attn_norm")
+            done("event_fc")
         ks = max(1, min(g["ksplit"], R // 256))
         ws = L.ptr(g["tn_ws"]) if ks > 1 else None
-        # d out_proj.weight = dres^T . ctx, d out_proj.bias = column sums of dres
-        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dres"]), C, L.ptr(g["ctx"]), C, L.ptr(G["attn.out_proj.weight"]), C,
-                L.ptr(G["attn.out_proj.bias"]), C, C, R, t, 0, ks, ws, st)
-        # dctx = dres . out_proj.weight
-        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P["attn.out_proj.weight"]), C, L.ptr(g["woT"]), C, C, C, C, 0, st)
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dres"]), C, L.ptr(g["woT"]), C, None, L.ptr(g["dctx"]), C, R, C, C, 1,
-                None, st)
-        self._k("sed_mhsa_bwd", lib.sed_mhsa_bwd, dt, L.ptr(g["qkv"]), L.ptr(g["ctx"]), L.ptr(g["dctx"]), L.ptr(g["lse"]),
-                L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, st)
-        # d in_proj_weight = dqkv^T . x', d in_proj_bias = column sums of dqkv
-        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dqkv"]), 3 * C, L.ptr(g["m"]), C, L.ptr(G["attn.in_proj_weight"]), C,
-                L.ptr(G["attn.in_proj_bias"]), 3 * C, C, R, t, 0, ks, ws, st)
-        if on_group_done is not None:
-            on_group_done("attn")
-        # dm = dqkv . in_proj_weight + dres (the residual branch), then back through the mel mean
-        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P["attn.in_proj_weight"]), C, L.ptr(g["winT"]), 3 * C, 3 * C, C,
-                3 * C, 0, st)
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dqkv"]), 3 * C, L.ptr(g["winT"]), 3 * C, None, L.ptr(g["dm"]), C, R, C,
-                3 * C, 1, None, st)
-        g["dm"].add_(g["dres"])
+        gcur = g["dh"]                                   # the gradient of the current layer's output
+        for l in reversed(range(self.sa_layers)):
+            ly = g["layers"][l]
+            xin = g["m"] if l == 0 else g["layers"][l - 1]["h2" if D else "h"]
+            an, nn_, fn, fnn = self.sa_layer_names(l)
+            if D:
+                w1, w2 = fn + ".linear1.weight", fn + ".linear2.weight"
+                self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(gcur), L.ptr(ly["h"]), L.ptr(ly["f"]),
+                        L.ptr(P[fnn + ".weight"]), L.ptr(ly["stats2"]), L.ptr(g["dres"]), L.ptr(G[fnn + ".weight"]),
+                        L.ptr(G[fnn + ".bias"]), L.ptr(g["ln_ws"]), R, C, st)
+                done(fnn)
+                # da = dres . w2, then a = act(u) and du = da act'(u) (du over da)
+                self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w2]), D, L.ptr(g["w2T"]), C, C, D, C, 0, st)
+                self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dres"]), C, L.ptr(g["w2T"]), C, None, L.ptr(g["fda"]), D, R, D, C, 1,
+                        None, st)
+                self._k("sed_ffn_act_bwd", lib.sed_ffn_act_bwd, self.sa_act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
+                        L.ptr(g["fda"]), R * D, st)
+                # d linear2.weight = dres^T . a, d linear1.weight = du^T . h, the biases' gradients their column sums
+                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dres"]), C, L.ptr(g["ffa"]), D, L.ptr(G[w2]), D,
+                        L.ptr(G[fn + ".linear2.bias"]), C, D, R, t, 0, ks, ws, st)
+                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["fda"]), D, L.ptr(ly["h"]), C, L.ptr(G[w1]), C,
+                        L.ptr(G[fn + ".linear1.bias"]), D, C, R, t, 0, ks, ws, st)
+                done(fn)
+                # dh = du . w1 + dres (the residual branch)
+                self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w1]), C, L.ptr(g["w1T"]), D, D, C, D, 0, st)
+                self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["fda"]), D, L.ptr(g["w1T"]), D, None, L.ptr(g["dh1"]), C, R, C, D, 1,
+                        None, st)
+                g["dh1"].add_(g["dres"])
+                gcur = g["dh1"]
+            self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(gcur), L.ptr(xin), L.ptr(ly["a"]),
+                    L.ptr(P[nn_ + ".weight"]), L.ptr(ly["stats"]), L.ptr(g["dres"]), L.ptr(G[nn_ + ".weight"]),
+                    L.ptr(G[nn_ + ".bias"]), L.ptr(g["ln_ws"]), R, C, st)
+            done(nn_)
+            # d out_proj.weight = dres^T . ctx, d out_proj.bias = column sums of dres
+            self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dres"]), C, L.ptr(ly["ctx"]), C, L.ptr(G[an + ".out_proj.weight"]), C,
+                    L.ptr(G[an + ".out_proj.bias"]), C, C, R, t, 0, ks, ws, st)
+            # dctx = dres . out_proj.weight
+            self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[an + ".out_proj.weight"]), C, L.ptr(g["woT"]), C, C, C, C, 0, st)
+            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dres"]), C, L.ptr(g["woT"]), C, None, L.ptr(g["dctx"]), C, R, C, C, 1,
+                    None, st)
+            self._k("sed_mhsa_bwd", lib.sed_mhsa_bwd, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
+                    L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, st)
+            # d in_proj_weight = dqkv^T . x', d in_proj_bias = column sums of dqkv
+            self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dqkv"]), 3 * C, L.ptr(xin), C, L.ptr(G[an + ".in_proj_weight"]), C,
+                    L.ptr(G[an + ".in_proj_bias"]), 3 * C, C, R, t, 0, ks, ws, st)
+            done(an)
+            # dm = dqkv . in_proj_weight + dres (the residual branch): the gradient of the layer's input
+            self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[an + ".in_proj_weight"]), C, L.ptr(g["winT"]), 3 * C, 3 * C, C,
+                    3 * C, 0, st)
+            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dqkv"]), 3 * C, L.ptr(g["winT"]), 3 * C, None, L.ptr(g["dm"]), C, R, C,
+                    3 * C, 1, None, st)
+            g["dm"].add_(g["dres"])
+            gcur = g["dm"]
+        # back through the mel mean
         self._k("sed_mel_mean_bwd", lib.sed_mel_mean_bwd, dt, L.ptr(g["dm"]), L.ptr(dfeat), R, p.w_out, C, pad32(C), st)
         self._tag = ""
 

@@ -140,8 +140,9 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
     if "attn.in_proj_weight" in weights:      # a --self_attention training: heads and positional flag from the checkpoint's attn_config
         from .models.spectogram_models import Csa_AvgPooling
         heads, pos = Csa_AvgPooling.config_from_state_dict(weights)
+        layers, ffn, act = Csa_AvgPooling.encoder_config_from_state_dict(weights)      # (1, 0, relu) for a one-layer checkpoint
         model = Csa_AvgPooling(cfg.classes_num, model_config=model_config, sa_heads=heads, pos_encoding=pos, mel_bins=n_mel,
-                               frontend=frontend, attention=attention).to(dev)
+                               frontend=frontend, attention=attention, sa_layers=layers, sa_ffn=ffn, sa_activation=act).to(dev)
     else:
         model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend,
                                attention=attention).to(dev)

@@ -120,6 +120,11 @@ def build_weak_parser():
     p.add_argument("--sa_heads", type=int, default=4, help="--self_attention: attention heads (the head width 128 / N must be 32 or 64)")
     p.add_argument("--no_pos_encoding", action="store_true", default=False,
                    help="--self_attention: leave out the sinusoidal positional table")
+    p.add_argument("--sa_layers", type=int, default=1, help="--self_attention: encoder layers stacked behind the mel-mean (post-LN)")
+    p.add_argument("--sa_ffn", type=int, default=0,
+                   help="--self_attention: width D of the feed-forward sub-layer of every encoder layer (a multiple of 32 up to 4096, "
+                        "usually 4 x 128 = 512); 0 builds the attention half of a layer only")
+    p.add_argument("--sa_activation", choices=["relu", "gelu"], default="relu", help="--sa_ffn: the activation of the feed-forward sub-layer")
     return p
 
 
@@ -352,7 +357,9 @@ def get_spectogram_dataset_model_and_criterion(args, device):
     if getattr(args, "self_attention", False):
         from .models.spectogram_models import Csa_AvgPooling
         model = Csa_AvgPooling(cfg.classes_num, model_config=model_config, sa_heads=int(args.sa_heads),
-                               pos_encoding=not args.no_pos_encoding, mel_bins=n_mel, frontend=frontend, attention=att)
+                               pos_encoding=not args.no_pos_encoding, mel_bins=n_mel, frontend=frontend, attention=att,
+                               sa_layers=int(getattr(args, "sa_layers", 1)), sa_ffn=int(getattr(args, "sa_ffn", 0)),
+                               sa_activation=getattr(args, "sa_activation", "relu"))
     else:
         model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend, attention=att)
     model.set_precision(args.precision)
@@ -432,10 +439,13 @@ def validate_args(args):
     if getattr(args, "self_attention", False):
         if args.train_features.lower() == "waveform":
             raise ValueError("--self_attention attends over the frames of the spectrogram models: it needs --train_features Spectogram")
-        from .models.spectogram_models import check_sa_geometry
+        from .models.spectogram_models import check_sa_encoder, check_sa_geometry
         check_sa_geometry(128, getattr(args, "sa_heads", 4))
+        check_sa_encoder(128, getattr(args, "sa_layers", 1), getattr(args, "sa_ffn", 0), getattr(args, "sa_activation", "relu"))
     elif getattr(args, "sa_heads", 4) != 4 or getattr(args, "no_pos_encoding", False):
         raise ValueError("--sa_heads / --no_pos_encoding configure the self-attention head: they need --self_attention")
+    elif getattr(args, "sa_layers", 1) != 1 or getattr(args, "sa_ffn", 0) != 0 or getattr(args, "sa_activation", "relu") != "relu":
+        raise ValueError("--sa_layers / --sa_ffn / --sa_activation configure the self-attention head: they need --self_attention")
     for flag, value in (("--weak_pooling", weak_options(args).get("weak_pooling")), ("--eval_clip_pooling", getattr(args, "eval_clip_pooling", None))):
         if value == "att" and not att_head:
             raise ValueError(f"{flag} att pools with the attention head: it needs --attention_head")

@@ -422,6 +422,28 @@ def check_sa_geometry(channels: int, heads: int) -> int:
     return channels // heads
 
 
+class _FfnParams(nn.Module):
+    """Parameter holder of an encoder layer's feed-forward sub-layer with torch.nn.TransformerEncoderLayer's names: linear1 (D, C) and
+    linear2 (C, D), torch.nn.Linear's initial values, drawn in that order (weight, bias each)."""
+
+    def __init__(self, channels, width):
+        super().__init__()
+        self.linear1 = _LinearParams(channels, width)
+        self.linear2 = _LinearParams(width, channels)
+
+
+def check_sa_encoder(channels: int, layers, ffn, activation) -> None:
+    """A ValueError for an encoder stack the kernels do not cover (host only)"""
+    if isinstance(layers, bool) or not isinstance(layers, int) or layers < 1:
+        raise ValueError(f"sa_layers must be a positive integer, got {layers!r}")
+    if isinstance(ffn, bool) or not isinstance(ffn, int) or ffn < 0 or ffn % 32 or ffn > 4096:
+        raise ValueError(f"sa_ffn must be 0 (no feed-forward sub-layer) or a multiple of 32 up to 4096, got {ffn!r}")
+    if ffn and channels > 512:
+        raise ValueError(f"sa_ffn: the feed-forward kernel takes at most 512 channels, the last block has {channels}")
+    if activation not in ("relu", "gelu"):
+        raise ValueError(f"sa_activation must be 'relu' or 'gelu', got {activation!r}")
+
+
 class Csa_AvgPooling(Cnn_AvgPooling):
     """The Cnn_AvgPooling feature extractor with a self-attention encoder layer as the temporal head (the conv-Transformer family
     of the DCASE task-4 systems; csrc/sed_mhsa.hip).  With R = B*t rows and C the last block's channels:
@@ -434,28 +456,75 @@ class Csa_AvgPooling(Cnn_AvgPooling):
         a   = ctx . attn.out_proj.weight^T + attn.out_proj.bias
         h   = LayerNorm(x' + a) (attn_norm; eps 1e-5, affine)
         event_fc(h) (and att_fc(h) with attention=True) -> interpolate as before
-    No feed-forward sub-layer, one layer.  The semantics are torch.nn.MultiheadAttention(C, sa_heads, batch_first=True)'s and
+    By default no feed-forward sub-layer and one layer.  sa_ffn = D > 0 adds the position-wise MLP of an encoder layer behind the
+    attention (csrc/sed_ffn.hip), and sa_layers = N stacks N such layers, the positional table added once before layer 0:
+        f   = act(h . ffn.linear1.weight^T + ffn.linear1.bias) . ffn.linear2.weight^T + ffn.linear2.bias     (act: relu or erf-form gelu)
+        h2  = LayerNorm(h + f) (ffn_norm)                                  -> the next layer's x, or event_fc's input
+    which is torch.nn.TransformerEncoderLayer(C, sa_heads, D, dropout=0.0, activation=act, batch_first=True, norm_first=False);
+    encoder_layer_state(state_dict, l) maps a layer's keys onto that module's.  Layer 0 registers attn, attn_norm, ffn, ffn_norm,
+    layer l >= 1 attn_l{l}, attn_norm_l{l}, ffn_l{l}, ffn_norm_l{l} (the ffn modules only with sa_ffn > 0), event_fc after them.
+    The semantics are torch.nn.MultiheadAttention(C, sa_heads, batch_first=True)'s and
     torch.nn.LayerNorm(C)'s, and attn.* / attn_norm.* of the state_dict load into those modules.  The float64 buffer attn_config =
-    (sa_heads, pos_encoding) makes the head rebuildable from a state_dict alone (from_state_dict).
-    RNG draw order: conv_blocks as always, then attn.out_proj.weight, attn.out_proj.bias (drawn, then zeroed), attn.in_proj_weight
-    (torch's constructor order), event_fc's draws and its init_layer, then att_fc's with attention=True.
-    Refused: C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0."""
+    (sa_heads, pos_encoding) makes the head rebuildable from a state_dict alone (from_state_dict); a second float64 buffer
+    encoder_config = (sa_layers, sa_ffn, activation code: 0 relu, 1 gelu) exists only when sa_layers > 1 or sa_ffn > 0, so a
+    default model's state_dict has the one-layer head's keys.
+    RNG draw order: conv_blocks as always, then per layer attn.out_proj.weight, attn.out_proj.bias (drawn, then zeroed),
+    attn.in_proj_weight (torch's constructor order), then with sa_ffn > 0 ffn.linear1.weight, ffn.linear1.bias, ffn.linear2.weight,
+    ffn.linear2.bias (torch.nn.Linear's initial values; the LayerNorms draw nothing); after the layers event_fc's draws and its
+    init_layer, then att_fc's with attention=True.
+    Refused: C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0, sa_layers < 1, sa_ffn not 0 or a multiple of 32 up to
+    4096 (and C > 512 with it), an activation other than relu / gelu."""
+
+    ACTIVATIONS = ("relu", "gelu")
 
     def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, sa_heads=4, pos_encoding=True,
-                 mel_bins=None, frontend=None, attention=False):
+                 mel_bins=None, frontend=None, attention=False, sa_layers=1, sa_ffn=0, sa_activation="relu"):
         check_sa_geometry(int(model_config[-1][0]), sa_heads)
+        check_sa_encoder(int(model_config[-1][0]), sa_layers, sa_ffn, sa_activation)
         self.sa_heads, self.pos_encoding = int(sa_heads), bool(pos_encoding)
+        self.sa_layers, self.sa_ffn, self.sa_activation = int(sa_layers), int(sa_ffn), sa_activation
         super().__init__(classes_num, model_config, precision, mel_bins=mel_bins, frontend=frontend, attention=attention)
 
     def _build_head(self, c_last, classes_num):
-        self.attn = _MhaParams(c_last, self.sa_heads)
-        self.attn_norm = _LayerNormParams(c_last)
-        self.register_buffer("attn_config", torch.tensor([float(self.sa_heads), float(self.pos_encoding)], dtype=torch.float64))
+        for l in range(self.sa_layers):
+            an, nn_, fn, fnn = CnnEngine.sa_layer_names(l)
+            setattr(self, an, _MhaParams(c_last, self.sa_heads))
+            setattr(self, nn_, _LayerNormParams(c_last))
+            if l == 0:
+                self.register_buffer("attn_config", torch.tensor([float(self.sa_heads), float(self.pos_encoding)], dtype=torch.float64))
+            if self.sa_ffn:
+                setattr(self, fn, _FfnParams(c_last, self.sa_ffn))
+                setattr(self, fnn, _LayerNormParams(c_last))
+        if self.sa_layers > 1 or self.sa_ffn:
+            self.register_buffer("encoder_config", torch.tensor([float(self.sa_layers), float(self.sa_ffn),
+                                                                 float(self.ACTIVATIONS.index(self.sa_activation))], dtype=torch.float64))
         self.event_fc = _LinearParams(c_last, classes_num)
 
     def _make_engine(self, precision):
         return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="sa", sa_heads=self.sa_heads,
-                         pos_encoding=self.pos_encoding, mel_bins=self.mel_bins, attention=self.attention)
+                         pos_encoding=self.pos_encoding, mel_bins=self.mel_bins, attention=self.attention, sa_layers=self.sa_layers,
+                         sa_ffn=self.sa_ffn, sa_activation=self.sa_activation)
+
+    @staticmethod
+    def encoder_config_from_state_dict(weights):
+        """(sa_layers, sa_ffn, sa_activation) from a state_dict's encoder_config; (1, 0, 'relu') when the buffer is absent"""
+        if "encoder_config" not in weights:
+            return 1, 0, "relu"
+        cfg = weights["encoder_config"].detach().cpu().double().tolist()
+        return int(round(cfg[0])), int(round(cfg[1])), Csa_AvgPooling.ACTIVATIONS[int(round(cfg[2]))]
+
+    @staticmethod
+    def encoder_layer_state(weights, layer):
+        """Layer `layer`'s entries of a state_dict under torch.nn.TransformerEncoderLayer's names (self_attn.*, linear1.*, linear2.*,
+        norm1.*, norm2.*; the last three only for a model with an FFN): that torch module on the CPU loads them with load_state_dict (what the tests compare against)."""
+        an, nn_, fn, fnn = CnnEngine.sa_layer_names(layer)
+        out = {}
+        for ours, theirs in ((an, "self_attn"), (nn_, "norm1"), (fn, None), (fnn, "norm2")):
+            for k, v in weights.items():
+                if k.startswith(ours + "."):
+                    rest = k[len(ours) + 1:]
+                    out[rest if theirs is None else theirs + "." + rest] = v
+        return out
 
     @staticmethod
     def config_from_state_dict(weights):
