@@ -39,6 +39,28 @@ reference can shrink it.  mode "f32": every product exact, accumulation in fp32.
             bf16 values are exact in fp32: everything above holds unchanged, plus the two internal operand roundings: P as the
             operand of P.V and of dV costs at most 2^-8 relative per weight (2^-8 sum_j p_ij |v_jc| on ctx, 2^-8 sum_i p_ij |dctx_ic|
             on dv), dS as the operand of dQ and dK costs 2^-8 of its absolute-value form p_ij Abar_ij (added to ES_ij).
+  raw dctx  (mode "bf16", raw_dctx=True)  In the engine dctx comes out of a GEMM and is not bf16-representable: the kernel rounds it
+            to nearest even where it is an MFMA operand.  With eps_ic = round(dctx_ic) - dctx_ic, half an ulp of 8 significant bits
+            is between 2^-9 |dctx_ic| (top of a binade) and 2^-8 |dctx_ic| (bottom); the gate is held to 2^-9, the smaller figure.
+            dctx is an operand in exactly two products, both linear in it, so the shift of the exact result is known:
+              dV = P^T dctx:   dv_jc moves by sum_i p_ij eps_ic,            at most 2^-9 sum_i p_ij |dctx_ic| in absolute values
+              dP = dctx V^T:   dp_ij moves by sum_c eps_ic v_jc and ds_ij = p_ij (dp_ij - D_i) by p_ij times that,
+                                                                            at most 2^-9 p_ij sum_c |dctx_ic| |v_jc|
+            The absolute-value forms alone are too generous: they widen the dk gate by 1.4 and the mutant without D
+            (tests/test_mhsa_host.py), 10.7 gates out under the representable dctx, would pass at 7.6.  The shift itself is a
+            deterministic function of the inputs (nearest-even is what the kernel documents and what the raw-operand test of
+            tests/test_gpu_mhsa.py holds it to, bit for bit), so by the triangle inequality the gate adds |shift| -- the smaller of
+            |sum_i p_ij eps_ic| and the absolute-value form on dv, the smaller of p_ij |sum_c eps_ic v_jc| and the absolute-value
+            form added to ES_ij and so carried into dq and dk -- never more than the 2^-9 forms.  D_i = sum_c dctx_ic ctx_ic is
+            taken from the fp32 dctx (the kernel header says so): its term keeps the raw dctx and does not change.  The reference
+            stays the float64 definition on the raw dctx.
+  teacher-forced  core(..., lse=, ctx=) and core_gates(..., lse=, ctx=): the backward half takes the lse and ctx it is GIVEN (what
+            sed_mhsa_bwd is fed) in place of the definition's own: p_ij = exp(s_ij - lse_i) -- evaluated as p_ij exp(lse_i(own) -
+            lse_i), the same number, so that the definition's own lse reproduces the default path bit for bit -- and
+            D_i = sum_c dctx_ic ctx_ic(given).  The backward derivation above already treats lse and ctx as exact fp32 inputs, so the
+            gates only read |lse| in rho' and |ctx| in Abar from the given values, and p from the rebuilt weights.
+            add_layernorm(..., stats=) / add_layernorm_gates(..., stats=): the backward takes (mean, rstd) per row as given
+            ((rows, 2), what sed_add_layernorm_bwd is fed) in xhat = (z - mean) rstd and in the factor rstd of dres.
   LayerNorm Held to (C + 8) u of its absolute-value expression (C-term sums for the mean and the variance, a handful of roundings
             around them).  With M = mean_c |z_c| and X_c = rstd (|z_c| + M) (the absolute-value form of xhat; the error of the
             difference z_c - mean is relative to |z_c| + M, not to the difference):
@@ -76,9 +98,11 @@ def join_qkv(q, k, v):
     return np.stack([q, k, v], axis=2).reshape(B * t, 3 * H * dh)
 
 
-def core(q, k, v, dctx=None, dtype=np.float64, mutant=None, bf16_operands=False):
+def core(q, k, v, dctx=None, dtype=np.float64, mutant=None, bf16_operands=False, lse=None, ctx=None, round_dctx=False):
     """The definition (dtype float64) or a plain implementation of it in `dtype` arithmetic (float32: what the gates must pass).
     bf16_operands: P and dS are rounded to bf16 where they are operands (the bf16 kernel's internal roundings).
+    round_dctx: dctx is rounded to bf16 where it is an MFMA operand (dp and dv), not in D.
+    lse (B, H, t), ctx (B, t, H, dh): teacher-forced -- the backward half rebuilds p and D from these (module docstring).
     mutant: a deliberately wrong definition (tests/test_mhsa_host.py).  -> dict ctx, lse (B, H, t) and, with dctx, dq, dk, dv."""
     q, k, v = (np.asarray(a, dtype=dtype) for a in (q, k, v))
     B, t, H, dh = q.shape
@@ -99,18 +123,24 @@ def core(q, k, v, dctx=None, dtype=np.float64, mutant=None, bf16_operands=False)
     e = np.exp(s - m).astype(dtype)
     l = e.sum(axis=ax, keepdims=True, dtype=dtype)
     p = (e / l).astype(dtype)
-    lse = (m + np.log(l)).astype(dtype)
+    lse_own = (m + np.log(l)).astype(dtype)
     pv = round_bf16(p).astype(dtype) if bf16_operands else p
-    out = dict(ctx=np.einsum("bhij,bjhc->bihc", pv, vv).astype(dtype), lse=lse[:, :, :, 0] if ax == 3 else lse[:, :, 0, :], p=p, s=s)
+    out = dict(ctx=np.einsum("bhij,bjhc->bihc", pv, vv).astype(dtype), lse=lse_own[:, :, :, 0] if ax == 3 else lse_own[:, :, 0, :], p=p, s=s)
     if dctx is None:
         return out
     dctx = np.asarray(dctx, dtype=dtype)
-    ctx = out["ctx"]
+    if lse is not None:
+        assert ax == 3
+        p = (p * np.exp(out["lse"] - np.asarray(lse, dtype=dtype))[..., None].astype(dtype)).astype(dtype)
+        pv = round_bf16(p).astype(dtype) if bf16_operands else p
+    out["p_bwd"] = p
+    ctx = out["ctx"] if ctx is None else np.asarray(ctx, dtype=dtype)
     D = np.einsum("bihc,bihc->bhi", dctx, ctx).astype(dtype)[:, :, :, None]
-    dp = np.einsum("bihc,bjhc->bhij", dctx, vv).astype(dtype)
+    dop = round_bf16(dctx).astype(dtype) if round_dctx else dctx
+    dp = np.einsum("bihc,bjhc->bhij", dop, vv).astype(dtype)
     ds = (p * dp if mutant == "no_D" else p * (dp - D)).astype(dtype)
     dso = round_bf16(ds).astype(dtype) if bf16_operands else ds
-    out["dv"] = np.einsum("bhij,bihc->bjhc", pv, dctx).astype(dtype)
+    out["dv"] = np.einsum("bhij,bihc->bjhc", pv, dop).astype(dtype)
     out["dq"] = (scale * np.einsum("bhij,bjhc->bihc", dso, kk)).astype(dtype)
     dk = np.einsum("bhij,bihc->bjhc", dso, q).astype(dtype)
     out["dk"] = dk if mutant == "dk_no_scale" else (scale * dk).astype(dtype)
@@ -143,14 +173,15 @@ def core_loops(q, k, v, dctx):
     return out
 
 
-def core_gates(q, k, v, dctx, mode="f32"):
-    """-> dict of per-element gates for ctx, lse, dq, dk, dv (module docstring) from the float64 definition"""
+def core_gates(q, k, v, dctx, mode="f32", raw_dctx=False, lse=None, ctx=None):
+    """-> dict of per-element gates for ctx, lse, dq, dk, dv (module docstring) from the float64 definition.  raw_dctx (bf16): dctx
+    is not bf16-representable and the kernel rounds it.  lse, ctx: the teacher-forced backward (its gates; ctx and lse keep theirs)."""
     assert mode in ("f32", "bf16")
     q, k, v, dctx = (np.asarray(a, dtype=np.float64) for a in (q, k, v, dctx))
     B, t, H, dh = q.shape
     scale = 1.0 / np.sqrt(dh)
-    r = core(q, k, v, dctx)
-    p, s, ctx, lse = r["p"], r["s"], r["ctx"], r["lse"]
+    r = core(q, k, v, dctx, lse=lse, ctx=ctx)
+    p, s, ctx_own, lse_own = r["p"], r["s"], r["ctx"], r["lse"]
     aq, ak, av, ad = np.abs(q), np.abs(k), np.abs(v), np.abs(dctx)
     delta = (dh + 2) * U * scale * np.einsum("bihc,bjhc->bhij", aq, ak).max(axis=3)          # (B, H, t)
     S = np.abs(s).max(axis=3)
@@ -159,12 +190,21 @@ def core_gates(q, k, v, dctx, mode="f32"):
     g = {}
     pav = np.einsum("bhij,bjhc->bihc", p, av)
     g["ctx"] = (rho + (t + 2) * U + pb).transpose(0, 2, 1)[..., None] * pav
-    g["lse"] = rho + 2.0 ** -23 * np.abs(lse)
+    g["lse"] = rho + 2.0 ** -23 * np.abs(lse_own)
+    lse = lse_own if lse is None else np.asarray(lse, dtype=np.float64)
+    ctx = ctx_own if ctx is None else np.asarray(ctx, dtype=np.float64)
+    p = r["p_bwd"]
     rho_b = delta + U * np.abs(lse) + 4.0 * U * S + 8.0 * U
-    Abar = np.einsum("bihc,bjhc->bhij", ad, av) + np.einsum("bihc,bihc->bhi", ad, np.abs(ctx))[..., None]
+    dV = np.einsum("bihc,bjhc->bhij", ad, av)
+    Abar = dV + np.einsum("bihc,bihc->bhi", ad, np.abs(ctx))[..., None]
     pA = p * Abar
     ES = pA * (rho_b[..., None] + (dh + 5) * U + pb)
+    eps = round_bf16(dctx).astype(np.float64) - dctx          # the operand rounding of a raw dctx
+    if raw_dctx and mode == "bf16":
+        ES = ES + p * np.minimum(np.abs(np.einsum("bihc,bjhc->bhij", eps, v)), 2.0 ** -9 * dV)
     g["dv"] = np.einsum("bhij,bihc->bjhc", p * (rho_b[..., None] + (t + 2) * U + pb), ad)
+    if raw_dctx and mode == "bf16":
+        g["dv"] = g["dv"] + np.minimum(np.abs(np.einsum("bhij,bihc->bjhc", p, eps)), 2.0 ** -9 * np.einsum("bhij,bihc->bjhc", p, ad))
     tot = ES + (t + 3) * U * pA
     g["dq"] = scale * np.einsum("bhij,bjhc->bihc", tot, ak)
     g["dk"] = scale * np.einsum("bhij,bihc->bjhc", tot, aq)
@@ -178,8 +218,8 @@ def round_bf16(a):
     return r.view(np.float32).reshape(np.shape(a))
 
 
-def add_layernorm(x, a, gamma, beta, dy=None, eps=EPS, dtype=np.float64, mutant=None):
-    """-> dict y, mean, rstd (rows,) and, with dy, dres, dgamma, dbeta"""
+def add_layernorm(x, a, gamma, beta, dy=None, eps=EPS, dtype=np.float64, mutant=None, stats=None):
+    """-> dict y, mean, rstd (rows,) and, with dy, dres, dgamma, dbeta.  stats (rows, 2): the backward uses these (mean, rstd)."""
     x, a, gamma, beta = (np.asarray(v, dtype=dtype) for v in (x, a, gamma, beta))
     C = x.shape[1]
     z = x + a
@@ -192,6 +232,11 @@ def add_layernorm(x, a, gamma, beta, dy=None, eps=EPS, dtype=np.float64, mutant=
     if dy is None:
         return out
     dy = np.asarray(dy, dtype=dtype)
+    if stats is not None:
+        stats = np.asarray(stats, dtype=dtype)
+        rstd = stats[:, 1:2]
+        xh = (z - stats[:, 0:1]) * rstd
+        out["xhat_bwd"], out["rstd_bwd"] = xh, rstd[:, 0]
     g = dy * gamma
     m1 = g.mean(axis=1, keepdims=True, dtype=dtype)
     m2 = (g * xh).mean(axis=1, keepdims=True, dtype=dtype)
@@ -201,7 +246,7 @@ def add_layernorm(x, a, gamma, beta, dy=None, eps=EPS, dtype=np.float64, mutant=
     return out
 
 
-def add_layernorm_gates(x, a, gamma, beta, dy, eps=EPS):
+def add_layernorm_gates(x, a, gamma, beta, dy, eps=EPS, stats=None):
     x, a, gamma, beta, dy = (np.asarray(v, dtype=np.float64) for v in (x, a, gamma, beta, dy))
     rows, C = x.shape
     r = add_layernorm(x, a, gamma, beta, dy, eps)
@@ -212,8 +257,11 @@ def add_layernorm_gates(x, a, gamma, beta, dy, eps=EPS):
     d = np.abs(z - r["mean"][:, None])
     k = (C + 8) * U
     g = np.abs(dy * gamma)
-    return dict(y=k * (np.abs(gamma) * (X + np.abs(xh) * rstd ** 2 * (d * (az + M)).mean(axis=1, keepdims=True)) + np.abs(beta)),
-                dres=k * rstd * (g + g.mean(axis=1, keepdims=True) + X * (g * X).mean(axis=1, keepdims=True)),
+    y = k * (np.abs(gamma) * (X + np.abs(xh) * rstd ** 2 * (d * (az + M)).mean(axis=1, keepdims=True)) + np.abs(beta))
+    if stats is not None:       # the backward's own rstd (its mean enters only through the absolute-value form |z| + M)
+        rstd = np.asarray(stats, dtype=np.float64)[:, 1:2]
+        X = rstd * (az + M)
+    return dict(y=y, dres=k * rstd * (g + g.mean(axis=1, keepdims=True) + X * (g * X).mean(axis=1, keepdims=True)),
                 dgamma=(rows + 8) * U * (np.abs(dy) * X).sum(axis=0), dbeta=(rows + 8) * U * np.abs(dy).sum(axis=0))
 
 

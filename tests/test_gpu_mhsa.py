@@ -5,7 +5,29 @@ Shapes: B = 2 different clips (leakage between clips shows), t on, under and ove
 queries or keys and walks the other index in tiles of 32; a workgroup is four waves = 128), (H, dh) in {(1, 32), (4, 32), (2, 64)}.
 Every input lies between NaN regions (a read past the B*t rows poisons an output: NaN * 0 is NaN), every output in a NaN-filled
 buffer between canary regions.  The backward is fed lse and ctx as the reference rounded to fp32 (the gates assume that).
-Run with -s for the worst error / gate of every check."""
+
+Beyond those random cases (bf16-representable operands in bf16 mode, as the gates of the "bf16" paragraph assume):
+  many tiles   B = 3 clips, t = 257 and 384: three workgroups per (clip, head) (bh = blockIdx.x / ntile with ntile = 3 and an odd B),
+               nine key tiles with a last tile of one key / twelve through the two LDS buffers
+  ramp         scores +-6 (key tile): the running maximum of an even query rises at every key tile (o and l rescaled by
+               alpha = exp(-6) each time), that of an odd query stays where tile 0 put it
+  raw operands fp32 q, k, v (and dctx) that are not bf16-representable -- what the engine's GEMMs hand the core -- give the bits of the
+               same values rounded to nearest even beforehand, forward and backward (dv alone under a raw dctx: D is taken from the
+               fp32 dctx by design); and a raw dctx against float64 within the raw_dctx gates
+Run with -s for the worst error / gate of every check.  Measured on the MI355X (worst over the shapes of a family; ctx lse dq dk dv):
+  random (test_core_against_formula)    f32 0.016 0.025 0.011 0.009 0.040     bf16 0.61 0.026 0.17 0.15 0.80
+  near one-hot                          f32 0.003 0.011 0.002 0.004 0.017     bf16 0.44 0.011 0.094 0.22 0.85
+  constant scores                       f32 0.004 0.026 0.002 0.004 0.015     bf16 0.000 0.020 0.041 0.070 0.031
+  many tiles                            f32 0.009 0.016 0.006 0.006 0.022     bf16 0.24 0.016 0.20 0.10 0.35
+  ramp                                  f32 0.002 0.009 0.001 0.002 0.009     bf16 0.001 0.009 0.15 0.043 0.40
+  raw dctx (bf16 only)                                                        bf16 0.38 0.021 0.16 0.15 0.52
+  raw operands: bit for bit.  (The ramp's bf16 ctx is nearly exact because the kernel's unnormalised weights exp(s - m) of the
+  dominant tile are exactly 1.)
+Tried against local edits of csrc/sed_mhsa.hip that were not committed: truncation in place of nearest-even where the bf16 forward
+stages K in LDS fails only test_bf16_rounds_its_operands_to_nearest_even (all four cases), and so does truncation of dctx as the
+operand of dP in the dq kernel (at the D = 0 comparison alone: dq differs, dk and dv do not); a third workgroup that takes the second's
+tile fails test_core_many_tiles (all eight) and the ramp at t = 257, and no case with t <= 130; o left without its alpha rescale
+fails every ramp case (and most others with more than four key tiles)."""
 import importlib
 
 import numpy as np
@@ -67,13 +89,14 @@ def ok(got, ref, gate, tag):
     assert good, (tag, worst)
 
 
-def run_core(L, dt, q, k, v, dctx, tag):
-    """forward (with and without lse), backward, each twice; every element against the formula"""
+def run_core(L, dt, q, k, v, dctx, tag, raw_dctx=False):
+    """forward (with and without lse), backward, each twice; every element against the formula.  raw_dctx: dctx is not
+    bf16-representable (the gates then carry its operand rounding)"""
     B, t, H, dh = q.shape
     C = H * dh
     lib, P = L.lib(), L.ptr
     ref = F.core(q, k, v, dctx)
-    gates = F.core_gates(q, k, v, dctx, "bf16" if dt == BF16 else "f32")
+    gates = F.core_gates(q, k, v, dctx, "bf16" if dt == BF16 else "f32", raw_dctx=raw_dctx)
     b = Bufs()
     qkv_h = F.join_qkv(q, k, v)
     qkv = b.inp(qkv_h)
@@ -139,6 +162,116 @@ def test_near_one_hot_rows_and_constant_scores(L, hd, dt):
     q = operands(rng, dt, B, t, H, dh)
     assert np.allclose(F.core(q, k, v)["p"], 1.0 / t, rtol=1e-12)
     run_core(L, dt, q, k, v, d, ("constant", hd, dt))
+
+
+@pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("hd", [(4, 32), (2, 64)], ids=lambda v: f"H{v[0]}dh{v[1]}")
+@pytest.mark.parametrize("t", [257, 384])
+def test_core_many_tiles(L, t, hd, dt):
+    """B = 3 (odd) clips and three workgroups per (clip, head): bh = blockIdx.x / ntile with ntile = 3.  t = 257: nine key tiles,
+    the last of one key (and one query in the third workgroup); t = 384: three full workgroups, twelve key tiles through the two
+    LDS buffers of the bf16 forward"""
+    H, dh = hd
+    assert (t + 127) // 128 == 3 and (t + 31) // 32 in (9, 12)
+    rng = np.random.default_rng(1000 * t + 10 * H + dt)
+    q, k, v, d = (operands(rng, dt, 3, t, H, dh, sigma=s) for s in (1.0, 1.0, 1.0, 0.1))
+    run_core(L, dt, q, k, v, d, ("many tiles", t, hd, dt))
+
+
+RAMP_STEP = 6.0
+
+
+@pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("hd", HEADS, ids=lambda v: f"H{v[0]}dh{v[1]}")
+@pytest.mark.parametrize("t", [130, 257])
+def test_score_ramp_over_the_key_tiles(L, t, hd, dt):
+    """k_j = w (j // 32), q_i = +-(step / sqrt(dh)) w with w a +-1 vector per (clip, head): the scaled score is about +-step (key tile).
+    An even query's running maximum rises by step at EVERY key tile (o and l are rescaled by alpha = exp(-step) each time), an odd
+    query's is fixed from tile 0 on (alpha = 1, every later weight tiny).  step (tiles - 1) <= 80 keeps every exp in fp32's normal
+    range: the gates are relative and do not model underflow."""
+    H, dh = hd
+    B = 2
+    tiles = (t + 31) // 32
+    assert RAMP_STEP * (tiles - 1) <= 80.0
+    rng = np.random.default_rng(50 * t + H + dt)
+    w = np.where(rng.random((B, 1, H, dh)) > 0.5, 1.0, -1.0).astype(np.float32)
+    k = (w * (np.arange(t) // 32).astype(np.float32)[None, :, None, None]).astype(np.float32)
+    sigma = np.where(np.arange(t) % 2 == 0, 1.0, -1.0).astype(np.float32)[None, :, None, None]
+    q = F.round_bf16((sigma * w * np.float32(RAMP_STEP / np.sqrt(dh))).astype(np.float32))
+    assert np.array_equal(F.round_bf16(k), k)
+    v, d = operands(rng, dt, B, t, H, dh), operands(rng, dt, B, t, H, dh, sigma=0.1)
+    r = F.core(q, k, v)
+    s, p = r["s"], r["p"]
+    last = (tiles - 1) * 32
+    assert np.allclose(s[:, :, 0::2, last:], RAMP_STEP * (tiles - 1), rtol=2e-2) and np.allclose(s[:, :, 1::2, last:], -RAMP_STEP * (tiles - 1), rtol=2e-2)
+    assert (p[:, :, 0::2].argmax(axis=3) >= last).all(), "an even query's largest weight is not in the last key tile"
+    assert (p[:, :, 1::2].argmax(axis=3) < 32).all() and (p[:, :, 1::2, :32].sum(axis=3) > 0.99).all()
+    run_core(L, dt, q, k, v, d, ("ramp", t, hd, dt))
+
+
+@pytest.mark.parametrize("hd", [(4, 32), (2, 64)], ids=lambda v: f"H{v[0]}dh{v[1]}")
+@pytest.mark.parametrize("t", [33, 130])
+def test_bf16_rounds_its_operands_to_nearest_even(L, t, hd):
+    """SED_BF16 on fp32 values that are NOT bf16-representable (what the engine's GEMMs hand the core) gives the bits it gives for the
+    same values rounded to nearest even beforehand: the LDS forward's staging, the register-fed fragments of forward and backward
+    and the load_col operands all round the same way.  D is taken from the fp32 dctx by design, so under a raw dctx only dv (which
+    does not depend on D) is compared -- and, with a ctx input of zeros (D = 0 for either dctx), the whole of dqkv."""
+    H, dh = hd
+    B, C = 2, H * dh
+    lib, P = L.lib(), L.ptr
+    rng = np.random.default_rng(900 + t + H)
+    q, k, v = (rng.normal(0.0, 1.0, (B, t, H, dh)).astype(np.float32) for _ in range(3))
+    d_raw = rng.normal(0.0, 0.1, (B, t, H, dh)).astype(np.float32)
+    for a in (q, k, v, d_raw):
+        assert (F.round_bf16(a) != a).mean() > 0.9, "rounding changes too few elements to show anything"
+        trunc = (a.view(np.uint32) & 0xFFFF0000).view(np.float32)
+        assert (F.round_bf16(a) != trunc).mean() > 0.4, "nearest-even and truncation agree too often to tell them apart"
+    qr, kr, vr, d_rnd = (F.round_bf16(a) for a in (q, k, v, d_raw))
+    ref = F.core(qr, kr, vr)
+    b = Bufs()
+    raw, rnd = b.inp(F.join_qkv(q, k, v)), b.inp(F.join_qkv(qr, kr, vr))
+    fwd = {}
+    for name, qkv in (("raw", raw), ("raw again", raw), ("rounded", rnd)):
+        ctx, lse = b.out(B * t, C), b.out(B, H, t)
+        L.check(lib.sed_mhsa_fwd(BF16, P(qkv), P(ctx), P(lse), B, t, H, dh, stream()), "mhsa_fwd")
+        fwd[name] = (ctx, lse)
+    b.intact()
+    for i, what in enumerate(("ctx", "lse")):
+        assert not bool(torch.isnan(fwd["raw"][i]).any()), what
+        assert np.array_equal(bits(fwd["raw"][i]), bits(fwd["raw again"][i])), (what, "two forward runs differ")
+        assert np.array_equal(bits(fwd["raw"][i]), bits(fwd["rounded"][i])), (what, "raw q, k, v are not rounded to nearest even in the forward")
+    ctx_in, lse_in = b.inp(ref["ctx"].reshape(B * t, C)), b.inp(ref["lse"])
+    nws = lib.sed_mhsa_bwd_ws_floats(B, t, H, dh)
+    dd_rnd, dd_raw = b.inp(d_rnd.reshape(B * t, C)), b.inp(d_raw.reshape(B * t, C))
+    bwd = {}
+    zero_ctx = b.inp(np.zeros((B * t, C)))          # D = 0 whatever dctx is: dctx then enters dq and dk through the operand of dP alone
+    for name, qkv, cc, dd in (("raw", raw, ctx_in, dd_rnd), ("raw again", raw, ctx_in, dd_rnd), ("rounded", rnd, ctx_in, dd_rnd),
+                              ("raw dctx", rnd, ctx_in, dd_raw), ("D = 0", rnd, zero_ctx, dd_rnd), ("D = 0, raw dctx", rnd, zero_ctx, dd_raw)):
+        dqkv, ws = b.out(B * t, 3 * C), b.out(nws)
+        L.check(lib.sed_mhsa_bwd(BF16, P(qkv), P(cc), P(dd), P(lse_in), P(dqkv), P(ws), B, t, H, dh, stream()), "mhsa_bwd")
+        bwd[name] = dqkv
+    b.intact()
+    assert not bool(torch.isnan(bwd["raw"]).any())
+    assert np.array_equal(bits(bwd["raw"]), bits(bwd["raw again"])), "two backward runs differ"
+    assert np.array_equal(bits(bwd["raw"]), bits(bwd["rounded"])), "raw q, k, v are not rounded to nearest even in the backward"
+    dv = [F.split_qkv(bits(bwd[n]), B, t, H, dh)[2] for n in ("rounded", "raw dctx")]
+    assert np.array_equal(dv[0], dv[1]), "a raw dctx is not rounded to nearest even as the operand of dV"
+    dq = [F.split_qkv(bits(bwd[n]), B, t, H, dh)[0] for n in ("rounded", "raw dctx")]
+    assert not np.array_equal(dq[0], dq[1]), "D is documented to come from the fp32 dctx: dq should see the raw values"
+    assert not bool(torch.isnan(bwd["D = 0"]).any()) and not np.array_equal(bits(bwd["D = 0"]), bits(bwd["rounded"]))
+    assert np.array_equal(bits(bwd["D = 0"]), bits(bwd["D = 0, raw dctx"])), "a raw dctx is not rounded to nearest even as the operand of dP"
+
+
+@pytest.mark.parametrize("hd", HEADS, ids=lambda v: f"H{v[0]}dh{v[1]}")
+@pytest.mark.parametrize("t", [65, 130])
+def test_bf16_raw_dctx_against_formula(L, t, hd):
+    """representable q, k, v and a raw fp32 dctx (sigma 0.1), against float64 on the raw dctx within the raw_dctx gates"""
+    H, dh = hd
+    rng = np.random.default_rng(77 * t + H)
+    q, k, v = (operands(rng, BF16, 2, t, H, dh) for _ in range(3))
+    d = rng.normal(0.0, 0.1, (2, t, H, dh)).astype(np.float32)
+    assert (F.round_bf16(d) != d).mean() > 0.9
+    run_core(L, BF16, q, k, v, d, ("raw dctx", t, hd), raw_dctx=True)
 
 
 def test_refusals_launch_nothing(L):

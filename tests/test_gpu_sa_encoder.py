@@ -44,7 +44,8 @@ def make_model(sed, K=3, precision="fp32", seed=0, layers=2, ffn=D, act="gelu", 
 
 def oracle(sed, sd, feat, y, heads, layers, ffn, act, pos, ratio):
     """feat (B, t, Wf, C) float64 with requires_grad -> (logits, loss, parameter gradients by state_dict name)"""
-    enc = [torch.nn.TransformerEncoderLayer(C, heads, ffn, dropout=0.0, activation=act, batch_first=True, norm_first=False).double()
+    C = feat.shape[-1]          # (tests/test_gpu_sa_at_size.py calls this at another width than this module's)
+    enc =[torch.nn.TransformerEncoderLayer(C, heads, ffn, dropout=0.0, activation=act, batch_first=True, norm_first=False).double()
            for _ in range(layers)]
     for l, ly in enumerate(enc):
         ly.load_state_dict({k: v.double().cpu() for k, v in sed.Csa_AvgPooling.encoder_layer_state(sd, l).items()})

@@ -1,6 +1,9 @@
 """Host (no GPU): the float64 definition of the self-attention head (tests/mhsa_formula.py) against torch.nn.MultiheadAttention +
 torch.nn.LayerNorm with autograd, the gates of that file against plain fp32 / bf16-operand implementations and against mutants of
-the definition, and Csa_AvgPooling's parameters, state_dict, FlatParams order and refusals."""
+the definition, and Csa_AvgPooling's parameters, state_dict, FlatParams order and refusals.  The raw_dctx gates (a dctx that is not
+bf16-representable) pass the plain implementation that rounds dctx where it is an operand and still reject the backward mutants
+more than 10 gates out; the teacher-forced options (lse=, ctx=, stats=) reproduce the default path bit for bit on the definition's
+own values and pass the plain implementation on values perturbed within the forward gates."""
 import importlib
 
 import numpy as np
@@ -121,6 +124,72 @@ def test_core_gates_reject_mutants(mutant, mode):
             assert not good and worst > 10.0, (mutant, mode, n, worst)
 
 
+def raw_dctx_cases():
+    """cases("bf16") with a dctx that is NOT bf16-representable (what the engine's out_proj GEMM hands the kernel)"""
+    rng = np.random.default_rng(12)
+    out = []
+    for q, k, v, d in cases("bf16"):
+        raw = rng.normal(0, 0.1, d.shape).astype(np.float32)
+        assert (F.round_bf16(raw) != raw).mean() > 0.9
+        out.append((q, k, v, raw))
+    return out
+
+
+def test_raw_dctx_gates_pass_a_plain_implementation():
+    """plain fp32 arithmetic with P, dS and -- where it is an operand, not in D -- dctx rounded to bf16, against float64 on the raw dctx"""
+    for q, k, v, d in raw_dctx_cases():
+        ref, gates = F.core(q, k, v, d), F.core_gates(q, k, v, d, "bf16", raw_dctx=True)
+        tight = F.core_gates(q, k, v, d, "bf16")
+        got = F.core(q, k, v, d, dtype=np.float32, bf16_operands=True, round_dctx=True)
+        for n in CORE_OUT:
+            good, worst = F.check(got[n], ref[n], gates[n], ("raw dctx", q.shape, n))
+            assert good, (q.shape, n, worst)
+            assert (gates[n] >= tight[n]).all() and (gates[n] <= 1.5 * tight[n] + 1e-300).all(), n     # 2^-9 next to 2^-8: at most half as much again
+        for n in ("ctx", "lse"):
+            assert np.array_equal(gates[n], tight[n]), n
+        # f32 mode has no operand rounding: the flag changes nothing there, and the default is today's gate
+        f32 = F.core_gates(q, k, v, d, "f32")
+        assert all(np.array_equal(F.core_gates(q, k, v, d, "f32", raw_dctx=True)[n], f32[n]) for n in CORE_OUT)
+        # rounding dctx in D as well is NOT what the kernel does; the flag of core() leaves D alone
+        plain = F.core(q, k, v, d, dtype=np.float32, bf16_operands=True)
+        assert not np.array_equal(plain["dv"], got["dv"]) and np.array_equal(plain["ctx"], got["ctx"])
+
+
+@pytest.mark.parametrize("mutant", sorted(m for m, outs in MUTANTS.items() if outs[0] not in ("ctx", "lse")))
+def test_raw_dctx_gates_reject_the_backward_mutants(mutant):
+    for q, k, v, d in raw_dctx_cases()[1:3]:
+        ref, gates = F.core(q, k, v, d), F.core_gates(q, k, v, d, "bf16", raw_dctx=True)
+        got = F.core(q, k, v, d, mutant=mutant)
+        for n in MUTANTS[mutant]:
+            good, worst = F.check(got[n], ref[n], gates[n], (mutant, "raw dctx", n))
+            assert not good and worst > 10.0, (mutant, n, worst)
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_teacher_forced_core(mode):
+    """lse= / ctx=: the definition's own values reproduce the default path bit for bit; values perturbed within the forward gates
+    (what a kernel's forward may hand its backward) give a reference that the plain implementation fed the same values still meets"""
+    rng = np.random.default_rng(13)
+    for q, k, v, d in cases(mode):
+        ref, gates = F.core(q, k, v, d), F.core_gates(q, k, v, d, mode)
+        same, gsame = F.core(q, k, v, d, lse=ref["lse"], ctx=ref["ctx"]), F.core_gates(q, k, v, d, mode, lse=ref["lse"], ctx=ref["ctx"])
+        for n in CORE_OUT:
+            assert np.array_equal(same[n], ref[n]) and np.array_equal(gsame[n], gates[n]), n
+        lse = (ref["lse"] + gates["lse"] * rng.uniform(-1, 1, ref["lse"].shape)).astype(np.float32)
+        ctx = (ref["ctx"] + gates["ctx"] * rng.uniform(-1, 1, ref["ctx"].shape)).astype(np.float32)
+        assert not np.array_equal(lse, ref["lse"].astype(np.float32)) and not np.array_equal(ctx, ref["ctx"].astype(np.float32))
+        tf, gtf = F.core(q, k, v, d, lse=lse, ctx=ctx), F.core_gates(q, k, v, d, mode, lse=lse, ctx=ctx)
+        assert np.allclose(tf["p_bwd"], np.exp(tf["s"] - lse.astype(np.float64)[..., None]), rtol=1e-12, atol=0)
+        assert np.array_equal(tf["ctx"], ref["ctx"]) and np.array_equal(tf["lse"], ref["lse"])          # the forward half is not forced
+        got = F.core(q, k, v, d, dtype=np.float32, bf16_operands=mode == "bf16", lse=lse, ctx=ctx)
+        for n in ("dq", "dk", "dv"):
+            good, worst = F.check(got[n], tf[n], gtf[n], (mode, "teacher-forced", q.shape, n))
+            assert good, (mode, q.shape, n, worst)
+        # the forced values matter: a ctx off by far more than its gate moves dq (through D) out of the gate
+        far = F.core(q, k, v, d, lse=lse, ctx=ctx + 0.05)
+        assert not F.check(far["dq"], tf["dq"], gtf["dq"], (mode, "ctx far off, dq"))[0]
+
+
 def ln_case(rows, C, seed=0):
     rng = np.random.default_rng(seed + rows + C)
     return (rng.normal(0.3, 1.0, (rows, C)).astype(np.float32), rng.normal(-0.1, 0.5, (rows, C)).astype(np.float32),
@@ -153,6 +222,34 @@ def test_layernorm_gates(C):
     alone = F.add_layernorm(np.zeros_like(x), a, gamma, beta, dy)
     assert not F.check(alone["y"], ref["y"], gates["y"], (C, "no residual"))[0]
     assert not F.check(alone["dres"], ref["dres"], gates["dres"], (C, "no residual, dres"))[0]
+
+
+@pytest.mark.parametrize("C", [32, 128])
+def test_teacher_forced_layernorm(C):
+    """stats=: the definition's own (mean, rstd) reproduce the default path bit for bit; statistics perturbed within the forward's
+    gates on them (tests/test_gpu_mhsa.py) give a reference the plain fp32 implementation fed the same statistics still meets"""
+    x, a, gamma, beta, dy = ln_case(65, C, seed=1)
+    ref, gates = F.add_layernorm(x, a, gamma, beta, dy), F.add_layernorm_gates(x, a, gamma, beta, dy)
+    own = np.stack([ref["mean"], ref["rstd"]], axis=1)
+    same, gsame = F.add_layernorm(x, a, gamma, beta, dy, stats=own), F.add_layernorm_gates(x, a, gamma, beta, dy, stats=own)
+    for n in ("y", "dres", "dgamma", "dbeta"):
+        assert np.array_equal(same[n], ref[n]) and np.array_equal(gsame[n], gates[n]), n
+    rng = np.random.default_rng(C)
+    z = ref["z"]
+    M = np.abs(z).mean(axis=1)
+    d = np.abs(z - ref["mean"][:, None])
+    k = (C + 8) * F.U
+    g_mean, g_rstd = k * M, k * ref["rstd"] * (1.0 + ref["rstd"] ** 2 * (d * (np.abs(z) + M[:, None])).mean(axis=1))
+    stats = np.stack([ref["mean"] + g_mean * rng.uniform(-1, 1, M.shape), ref["rstd"] + g_rstd * rng.uniform(-1, 1, M.shape)], axis=1).astype(np.float32)
+    tf, gtf = F.add_layernorm(x, a, gamma, beta, dy, stats=stats), F.add_layernorm_gates(x, a, gamma, beta, dy, stats=stats)
+    assert np.array_equal(tf["y"], ref["y"]) and np.array_equal(gtf["y"], gates["y"]) and not np.array_equal(tf["dres"], ref["dres"])
+    got = F.add_layernorm(x, a, gamma, beta, dy, dtype=np.float32, stats=stats)
+    for n in ("dres", "dgamma", "dbeta"):
+        good, worst = F.check(got[n], tf[n], gtf[n], (C, "teacher-forced", n))
+        assert good, (C, n, worst)
+    # the forced statistics matter: an rstd off by 1e-3 relative moves dres out of the gate
+    far = F.add_layernorm(x, a, gamma, beta, dy, stats=stats * np.array([1.0, 1.001]))
+    assert not F.check(far["dres"], tf["dres"], gtf["dres"], (C, "rstd far off, dres"))[0]
 
 
 # ---- the model ---------------------------------------------------------------------------------------------------------------------
