@@ -1102,6 +1102,43 @@ int sed_ffn_fwd(int dtype, int act, const float* x, const float* w1, const float
                 float* y, float* u, size_t R, int C, int D, void* stream);
 int sed_ffn_act_bwd(int act, const float* u, const float* da, float* a, float* du, size_t n, void* stream);
 
+/* ---- Conformer convolution module of the self-attention head (csrc/sed_convmod.hip) ------------
+ * Between the attention and the feed-forward sub-layer: pointwise Conv1d(C, 2C, 1) -> GLU -> depthwise Conv1d(C, C, k, padding
+ * (k-1)/2, groups=C) -> BatchNorm1d(C) -> SiLU -> pointwise Conv1d(C, C, 1).  The pointwise convolutions are sed_gemm_nt launches, the
+ * BatchNorm finalisation is sed_bn_train_finalize / sed_bn_eval_coeffs (forward) and sed_bn_bwd_finalize / sed_bn_eval_stats +
+ * sed_bn_eval_bwd_finalize (backward) with Cp = C.  R = B*t rows, k odd in [3, 31], p = (k-1)/2, everything row-major fp32:
+ *   v[r][c]  = g[r][c] * sigmoid(g[r][C+c])                                    g [R][2C]
+ *   z[b,i,c] = bias[c] + sum_{j<k} w[c][j] * v[b, i+j-p, c]                    w [C][k]; frames outside [0, t) of the SAME clip are 0
+ *   partial [nparts][2][C] = per-workgroup (sum z, sum z^2), nparts = sed_dwconv_nparts(B, t) (sed_dwconv_glu_fwd_ws_floats floats);
+ *            NULL: the eval form, same z bits.  v [R][C] is written only when given (a training forward keeps it: the backward reads
+ *            it for the filter gradient instead of recomputing the GLU with its halo).
+ *   sed_bn_silu_fwd:  s = y * sigmoid(y), y = scale[c] * z + shift[c]          z, s [R][C]
+ *   sed_bn_silu_bwd_reduce:  gz = ds * sigmoid(y) * (1 + y * (1 - sigmoid(y))) (gz may be ds itself);  partial [nparts][2][C] =
+ *            per-workgroup (sum gz, sum gz * (z - mean[c]) * invstd[c]), nparts = sed_bn_silu_bwd_nparts(R) = ceil(R / 128): a workgroup
+ *            owns 128 rows
+ *   sed_dwconv_glu_bwd:  dz = ca[c]*gz + cb[c]*z + cc[c] on load;  dv[b,i,c] = sum_j w[c][j] * dz[b, i-j+p, c];
+ *            dg[r][c] = dv * sigma, dg[r][C+c] = dv * g[r][c] * sigma * (1 - sigma), sigma = sigmoid(g[r][C+c])      dg [R][2C]
+ *            dw[c][j] = sum_{b,i} dz[b,i,c] * v[b, i+j-p, c], dbias[c] = sum_{b,i} dz[b,i,c]: per-workgroup partials in the workspace
+ *            (sed_dwconv_glu_bwd_ws_floats floats), summed in fp64 in a fixed order by the call's second launch.
+ * sigmoid(x) = 1 / (1 + expf(-x)), IEEE division.  All of it is fp32 vector arithmetic whatever the engine's precision; no atomics,
+ * fixed-order sums: the same bits on every run.  A workgroup owns sed_dwconv_tile() frames of one clip and 32 channels; frames of a
+ * neighbouring clip and rows past R are never read; 16-byte accesses along the channel axis.
+ * Refused (non-zero, nothing launched, outputs untouched): sizes <= 0, k even or outside [3, 31], C % 4 != 0, a NULL pointer other
+ * than v and partial of the forward, g / z / v / s / ds / gz / dg / workspace not 16-byte aligned, t*2C*4 >= 2^31 bytes, B > 65535. */
+int    sed_dwconv_tile(void);
+int    sed_dwconv_nparts(int B, int t);
+size_t sed_dwconv_glu_fwd_ws_floats(int B, int t, int C);
+int    sed_dwconv_glu_fwd(const float* g, const float* w, const float* bias, float* z, float* v, float* partial, int B, int t, int C,
+                          int k, void* stream);
+int    sed_bn_silu_fwd(const float* z, const float* scale, const float* shift, float* s, size_t R, int C, void* stream);
+int    sed_bn_silu_bwd_nparts(size_t R);
+int    sed_bn_silu_bwd_reduce(const float* ds, const float* z, const float* scale, const float* shift, const float* mean,
+                              const float* invstd, float* gz, float* partial, size_t R, int C, void* stream);
+size_t sed_dwconv_glu_bwd_ws_floats(int B, int t, int C, int k);
+int    sed_dwconv_glu_bwd(const float* gz, const float* z, const float* ca, const float* cb, const float* cc, const float* v,
+                          const float* g, const float* w, float* dg, float* dw, float* dbias, float* workspace, int B, int t, int C,
+                          int k, void* stream);
+
 /* ---- utilities-----------------------------------------------------------------------------*/
 /* out[i] = sum_{s<nparts} partial[s][i], i < n (fixed order: deterministic)                     */
 int sed_sum_partials(const float* partial, int nparts, size_t n, float* out, void* stream);

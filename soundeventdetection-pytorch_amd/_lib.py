@@ -177,6 +177,15 @@ PROTOTYPES = {
     "sed_add_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _P]),
     "sed_ffn_fwd": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _P]),
     "sed_ffn_act_bwd": (_I, [_I, _P, _P, _P, _P, _Z, _P]),
+    "sed_dwconv_tile": (_I, []),
+    "sed_dwconv_nparts": (_I, [_I, _I]),
+    "sed_dwconv_glu_fwd_ws_floats": (_Z, [_I, _I, _I]),
+    "sed_dwconv_glu_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sed_bn_silu_fwd": (_I, [_P, _P, _P, _P, _Z, _I, _P]),
+    "sed_bn_silu_bwd_nparts": (_I, [_Z]),
+    "sed_bn_silu_bwd_reduce": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _P]),
+    "sed_dwconv_glu_bwd_ws_floats": (_Z, [_I, _I, _I, _I]),
+    "sed_dwconv_glu_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "sed_m5_conv1_len": (_I, [_I]),
     "sed_m5_conv1_nparts": (_I, [_I, _I]),
     "sed_m5_conv1_fwd": (_I, [_I, _P, _P, _P, _P, _I, _I, _P]),

@@ -228,14 +228,16 @@ class CnnEngine(OptimizerExtMixin):
     def __init__(self, classes_num: int, model_config: Sequence[Tuple[int, int]], in_channels: int = 1,
                  precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
                  mel_bins: Optional[int] = None, attention: bool = False, sa_heads: int = 4, pos_encoding: bool = True,
-                 sa_layers: int = 1, sa_ffn: int = 0, sa_activation: str = "relu"):
+                 sa_layers: int = 1, sa_ffn: int = 0, sa_activation: str = "relu", sa_conv_kernel: int = 0):
         """attention: a second linear layer att_fc beside event_fc scores every frame per class (csrc/sed_attn.hip): forward()
         also leaves the attention logits in plan.att, loss_and_grad(weak=("att", ...)) pools with them and backward() then takes
         both layers.  False launches exactly what it always did.
         head: 'fc' (Cnn_AvgPooling), 'gru' (CRNN), 'sa' (Csa_AvgPooling: a self-attention encoder layer with sa_heads heads between the
         mel-mean and event_fc, csrc/sed_mhsa.hip; pos_encoding adds the fixed sinusoidal table to the mel-mean rows; sa_layers post-LN
         encoder layers, each with a feed-forward sub-layer of width sa_ffn > 0 and activation sa_activation behind the attention,
-        csrc/sed_ffn.hip -- torch.nn.TransformerEncoderLayer(C, sa_heads, sa_ffn, dropout=0, norm_first=False) semantics)
+        csrc/sed_ffn.hip -- torch.nn.TransformerEncoderLayer(C, sa_heads, sa_ffn, dropout=0, norm_first=False) semantics; sa_conv_kernel
+        = k > 0, odd in [3, 31], puts the Conformer convolution module -- pointwise conv, GLU, depthwise conv of k taps along time,
+        BatchNorm, SiLU, pointwise conv, residual LayerNorm -- between the two, csrc/sed_convmod.hip)
         or 'none' (a bare stack of ConvBlocks: forward() stops at the last pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
         Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and backward() also produces the input gradient
         plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path keeps the dedicated Cin = 1
@@ -251,7 +253,12 @@ class CnnEngine(OptimizerExtMixin):
         self.head, self.Hd = head, int(gru_hidden)
         self.sa_heads, self.pos_encoding = int(sa_heads), bool(pos_encoding)
         self.sa_layers, self.sa_ffn, self.sa_activation = int(sa_layers), int(sa_ffn), sa_activation
+        self.sa_conv_kernel = int(sa_conv_kernel)
+        if head != "sa" and self.sa_conv_kernel:
+            raise ValueError("sa_conv_kernel belongs to the self-attention head (head='sa')")
         if head == "sa":
+            if self.sa_conv_kernel and (self.sa_conv_kernel < 3 or self.sa_conv_kernel > 31 or self.sa_conv_kernel % 2 == 0):
+                raise ValueError(f"sa_conv_kernel must be 0 (no convolution module) or an odd integer in [3, 31], got {sa_conv_kernel!r}")
             if self.sa_layers < 1:
                 raise ValueError(f"sa_layers must be at least 1, got {sa_layers!r}")
             if self.sa_ffn < 0 or self.sa_ffn % 32 or self.sa_ffn > 4096:
@@ -651,10 +658,16 @@ class CnnEngine(OptimizerExtMixin):
         sfx = "" if l == 0 else f"_l{l}"
         return "attn" + sfx, "attn_norm" + sfx, "ffn" + sfx, "ffn_norm" + sfx
 
+    @staticmethod
+    def sa_conv_names(l):
+        """(convm, conv_norm) module names of encoder layer l's convolution module (between attn_norm* and ffn* of sa_layer_names)"""
+        sfx = "" if l == 0 else f"_l{l}"
+        return "convm" + sfx, "conv_norm" + sfx
+
     def _plan_sa(self, B, t, C, dev):
         """Buffers of the self-attention head (every one allocated here: a captured step allocates nothing); R = B*t rows.  What a
         layer's backward reads of its forward is kept per layer (g["layers"]); the gradients in flight are shared by the layers."""
-        lib, Hh, D = self.lib, self.sa_heads, self.sa_ffn
+        lib, Hh, D, kc = self.lib, self.sa_heads, self.sa_ffn, self.sa_conv_kernel
         f32 = dict(dtype=torch.float32, device=dev)
         R = B * t
         g = dict(R=R)
@@ -666,8 +679,14 @@ class CnnEngine(OptimizerExtMixin):
             ly["lse"] = torch.empty((B, Hh, t), **f32)
             if D:
                 ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("u", D), ("f", C), ("h2", C), ("stats2", 2))})
+            if kc:
+                # the convolution module: the GLU's input and output, the depthwise output, the activation, the module's output, the
+                # residual LayerNorm's output and statistics, and the BatchNorm's per-channel vectors (Cp = C)
+                ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("cg", 2 * C), ("cv", C), ("cz", C), ("cs", C), ("co", C),
+                                                                                 ("hc", C), ("stats3", 2))})
+                ly.update({name: torch.empty(C, **f32) for name in ("cscale", "cshift", "cmean", "cinvstd")})
             g["layers"].append(ly)
-        g["h"] = g["layers"][-1]["h2" if D else "h"]          # what event_fc (and att_fc) read
+        g["h"] = self._sa_layer_out(g["layers"][-1])          # what event_fc (and att_fc) read
         g["woT"] = torch.empty((C, C), **f32)
         g["winT"] = torch.empty((C, 3 * C), **f32)
         if D:
@@ -675,6 +694,15 @@ class CnnEngine(OptimizerExtMixin):
             g["ffa"], g["fda"] = torch.empty((R, D), **f32), torch.empty((R, D), **f32)
             g["dh1"] = torch.empty((R, C), **f32)
             g["w2T"], g["w1T"] = torch.empty((D, C), **f32), torch.empty((C, D), **f32)
+        if kc:
+            # shared by the layers: the statistics partials of the forward and the backward, the BatchNorm backward's coefficients, the
+            # gradients of the activation (ds, then gz in place) and of g, the filter-gradient workspace, the transposed pointwise weights
+            g["cpart"] = torch.empty(max(1, lib.sed_dwconv_glu_fwd_ws_floats(B, t, C)), **f32)
+            g["cbpart"] = torch.empty((max(1, lib.sed_bn_silu_bwd_nparts(R)), 2, C), **f32)
+            g["ccoef"] = torch.empty((3, C), **f32)
+            g["cds"], g["cdg"], g["dhc"] = torch.empty((R, C), **f32), torch.empty((R, 2 * C), **f32), torch.empty((R, C), **f32)
+            g["cw_ws"] = torch.empty(max(1, lib.sed_dwconv_glu_bwd_ws_floats(B, t, C, kc)), **f32)
+            g["cw2T"], g["cw1T"] = torch.empty((C, C), **f32), torch.empty((2 * C, C), **f32)
         g["pe"] = None
         if self.pos_encoding:
             # the standard table, built on the host in float64 and rounded once to fp32: pe[i][2j] = sin(i / 10000^(2j/C)), pe[i][2j+1] = cos(.)
@@ -689,10 +717,86 @@ class CnnEngine(OptimizerExtMixin):
         tn = [lib.sed_gemm_tn_ws_floats(3 * C, C, g["ksplit"])]
         if D:
             tn += [lib.sed_gemm_tn_ws_floats(C, D, g["ksplit"]), lib.sed_gemm_tn_ws_floats(D, C, g["ksplit"])]
+        if kc:
+            tn += [lib.sed_gemm_tn_ws_floats(2 * C, C, g["ksplit"])]
         g["tn_ws"] = torch.empty(max(1, max(tn)), **f32)
         return g
 
-    def _sa_forward(self, p, P, feat, training):
+    def _sa_layer_out(self, ly):
+        return ly["h2"] if self.sa_ffn else ly["hc"] if self.sa_conv_kernel else ly["h"]
+
+    def _sa_conv_forward(self, p, P, l, ly, training, bn_training, update_running_stats):
+        """The convolution module of layer l behind attn_norm: ly["h"] -> ly["hc"].  training: keep what a backward reads;
+        bn_training: batch statistics (and the running update) instead of the running statistics."""
+        lib, dt, st, g, kc = self.lib, self.dt, _stream(), p.sa, self.sa_conv_kernel
+        B, t, C, R = p.B, p.t_out, self.cfg[-1][0], p.sa["R"]
+        cm, cn = self.sa_conv_names(l)
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["h"]), C, L.ptr(P[cm + ".pointwise1.weight"]), C,
+                L.ptr(P[cm + ".pointwise1.bias"]), L.ptr(ly["cg"]), 2 * C, R, 2 * C, C, 1, None, st)
+        self._k("sed_dwconv_glu_fwd", lib.sed_dwconv_glu_fwd, L.ptr(ly["cg"]), L.ptr(P[cm + ".depthwise.weight"]),
+                L.ptr(P[cm + ".depthwise.bias"]), L.ptr(ly["cz"]), L.ptr(ly["cv"]) if training else None,
+                L.ptr(g["cpart"]) if bn_training else None, B, t, C, kc, st)
+        if bn_training:
+            rm = P[cm + ".bn.running_mean"] if update_running_stats else None
+            rv = P[cm + ".bn.running_var"] if update_running_stats else None
+            self._k("sed_bn_train_finalize", lib.sed_bn_train_finalize, L.ptr(g["cpart"]), lib.sed_dwconv_nparts(B, t), float(R),
+                    L.ptr(P[cm + ".bn.weight"]), L.ptr(P[cm + ".bn.bias"]), L.ptr(rm), L.ptr(rv), BN_MOMENTUM, BN_EPS,
+                    L.ptr(ly["cscale"]), L.ptr(ly["cshift"]), L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), C, C, st)
+        else:
+            self._k("sed_bn_eval_coeffs", lib.sed_bn_eval_coeffs, L.ptr(P[cm + ".bn.weight"]), L.ptr(P[cm + ".bn.bias"]),
+                    L.ptr(P[cm + ".bn.running_mean"]), L.ptr(P[cm + ".bn.running_var"]), BN_EPS, L.ptr(ly["cscale"]),
+                    L.ptr(ly["cshift"]), C, C, st)
+        self._k("sed_bn_silu_fwd", lib.sed_bn_silu_fwd, L.ptr(ly["cz"]), L.ptr(ly["cscale"]), L.ptr(ly["cshift"]), L.ptr(ly["cs"]), R, C, st)
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["cs"]), C, L.ptr(P[cm + ".pointwise2.weight"]), C,
+                L.ptr(P[cm + ".pointwise2.bias"]), L.ptr(ly["co"]), C, R, C, C, 1, None, st)
+        self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(ly["h"]), L.ptr(ly["co"]), L.ptr(P[cn + ".weight"]),
+                L.ptr(P[cn + ".bias"]), L.ptr(ly["hc"]), L.ptr(ly["stats3"]) if training else None, R, C, LN_EPS, st)
+
+    def _sa_conv_backward(self, p, P, G, l, ly, gcur, eval_bwd, ks, ws, done):
+        """Backward of layer l's convolution module: gcur = the gradient of ly["hc"]; returns the gradient of ly["h"] (g["dhc"])."""
+        lib, dt, st, g, kc = self.lib, self.dt, _stream(), p.sa, self.sa_conv_kernel
+        B, t, C, R = p.B, p.t_out, self.cfg[-1][0], p.sa["R"]
+        cm, cn = self.sa_conv_names(l)
+        w1, w2 = cm + ".pointwise1.weight", cm + ".pointwise2.weight"
+        self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(gcur), L.ptr(ly["h"]), L.ptr(ly["co"]),
+                L.ptr(P[cn + ".weight"]), L.ptr(ly["stats3"]), L.ptr(g["dres"]), L.ptr(G[cn + ".weight"]), L.ptr(G[cn + ".bias"]),
+                L.ptr(g["ln_ws"]), R, C, st)
+        done(cn)
+        # ds = dres . pointwise2.weight;  d pointwise2.weight = dres^T . s, its bias gradient the column sums of dres
+        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w2]), C, L.ptr(g["cw2T"]), C, C, C, C, 0, st)
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dres"]), C, L.ptr(g["cw2T"]), C, None, L.ptr(g["cds"]), C, R, C, C, 1, None, st)
+        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dres"]), C, L.ptr(ly["cs"]), C, L.ptr(G[w2]), C,
+                L.ptr(G[cm + ".pointwise2.bias"]), C, C, R, t, 0, ks, ws, st)
+        # through the SiLU (gz over ds) and the BatchNorm: statistics, the finalisation, then dz = ca gz + cb z + cc on load
+        if eval_bwd:
+            self._k("sed_bn_eval_stats", lib.sed_bn_eval_stats, L.ptr(P[cm + ".bn.running_mean"]), L.ptr(P[cm + ".bn.running_var"]), BN_EPS,
+                    L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), C, C, st)
+        nparts = lib.sed_bn_silu_bwd_nparts(R)
+        self._k("sed_bn_silu_bwd_reduce", lib.sed_bn_silu_bwd_reduce, L.ptr(g["cds"]), L.ptr(ly["cz"]), L.ptr(ly["cscale"]),
+                L.ptr(ly["cshift"]), L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), L.ptr(g["cds"]), L.ptr(g["cbpart"]), R, C, st)
+        ca, cb, cc = g["ccoef"][0], g["ccoef"][1], g["ccoef"][2]
+        if eval_bwd:
+            self._k("sed_bn_eval_bwd_finalize", lib.sed_bn_eval_bwd_finalize, L.ptr(g["cbpart"]), nparts, L.ptr(P[cm + ".bn.weight"]),
+                    L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), L.ptr(G[cm + ".bn.weight"]), L.ptr(G[cm + ".bn.bias"]), L.ptr(ca), L.ptr(cb),
+                    L.ptr(cc), C, C, st)
+        else:
+            self._k("sed_bn_bwd_finalize", lib.sed_bn_bwd_finalize, L.ptr(g["cbpart"]), nparts, float(R), L.ptr(P[cm + ".bn.weight"]),
+                    L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), L.ptr(G[cm + ".bn.weight"]), L.ptr(G[cm + ".bn.bias"]), L.ptr(ca), L.ptr(cb),
+                    L.ptr(cc), C, C, st)
+        self._k("sed_dwconv_glu_bwd", lib.sed_dwconv_glu_bwd, L.ptr(g["cds"]), L.ptr(ly["cz"]), L.ptr(ca), L.ptr(cb), L.ptr(cc),
+                L.ptr(ly["cv"]), L.ptr(ly["cg"]), L.ptr(P[cm + ".depthwise.weight"]), L.ptr(g["cdg"]), L.ptr(G[cm + ".depthwise.weight"]),
+                L.ptr(G[cm + ".depthwise.bias"]), L.ptr(g["cw_ws"]), B, t, C, kc, st)
+        # d pointwise1.weight = dg^T . h, its bias gradient the column sums of dg;  dh = dg . pointwise1.weight + dres (the residual)
+        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["cdg"]), 2 * C, L.ptr(ly["h"]), C, L.ptr(G[w1]), C,
+                L.ptr(G[cm + ".pointwise1.bias"]), 2 * C, C, R, t, 0, ks, ws, st)
+        done(cm)
+        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w1]), C, L.ptr(g["cw1T"]), 2 * C, 2 * C, C, 2 * C, 0, st)
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["cdg"]), 2 * C, L.ptr(g["cw1T"]), 2 * C, None, L.ptr(g["dhc"]), C, R, C, 2 * C, 1,
+                None, st)
+        g["dhc"].add_(g["dres"])
+        return g["dhc"]
+
+    def _sa_forward(self, p, P, feat, training, bn_training=False, update_running_stats=True):
         lib, dt, st, g, Hh, D = self.lib, self.dt, _stream(), p.sa, self.sa_heads, self.sa_ffn
         B, t = p.B, p.t_out
         C = self.cfg[-1][0]
@@ -713,12 +817,15 @@ class CnnEngine(OptimizerExtMixin):
             self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(xin), L.ptr(ly["a"]), L.ptr(P[nn_ + ".weight"]),
                     L.ptr(P[nn_ + ".bias"]), L.ptr(ly["h"]), L.ptr(ly["stats"]) if training else None, R, C, LN_EPS, st)
             xin = ly["h"]
+            if self.sa_conv_kernel:
+                self._sa_conv_forward(p, P, l, ly, training, bn_training, update_running_stats)
+                xin = ly["hc"]
             if D:
                 # h2 = LayerNorm(h + ffn(h)): both products and the activation in one launch; u only for a backward
-                self._k("sed_ffn_fwd", lib.sed_ffn_fwd, dt, self.sa_act, L.ptr(ly["h"]), L.ptr(P[fn + ".linear1.weight"]),
+                self._k("sed_ffn_fwd", lib.sed_ffn_fwd, dt, self.sa_act, L.ptr(xin), L.ptr(P[fn + ".linear1.weight"]),
                         L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(ly["f"]),
                         L.ptr(ly["u"]) if training else None, R, C, D, st)
-                self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(ly["h"]), L.ptr(ly["f"]), L.ptr(P[fnn + ".weight"]),
+                self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(xin), L.ptr(ly["f"]), L.ptr(P[fnn + ".weight"]),
                         L.ptr(P[fnn + ".bias"]), L.ptr(ly["h2"]), L.ptr(ly["stats2"]) if training else None, R, C, LN_EPS, st)
                 xin = ly["h2"]
         self._k("sed_head_fwd", lib.sed_head_fwd, L.SED_F32, L.ptr(g["h"]), L.ptr(P["event_fc.weight"]), L.ptr(P["event_fc.bias"]),
@@ -746,11 +853,12 @@ class CnnEngine(OptimizerExtMixin):
         gcur = g["dh"]                                   # the gradient of the current layer's output
         for l in reversed(range(self.sa_layers)):
             ly = g["layers"][l]
-            xin = g["m"] if l == 0 else g["layers"][l - 1]["h2" if D else "h"]
+            xin = g["m"] if l == 0 else self._sa_layer_out(g["layers"][l - 1])
             an, nn_, fn, fnn = self.sa_layer_names(l)
+            fin = ly["hc"] if self.sa_conv_kernel else ly["h"]        # the FFN sub-layer's input
             if D:
                 w1, w2 = fn + ".linear1.weight", fn + ".linear2.weight"
-                self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(gcur), L.ptr(ly["h"]), L.ptr(ly["f"]),
+                self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(gcur), L.ptr(fin), L.ptr(ly["f"]),
                         L.ptr(P[fnn + ".weight"]), L.ptr(ly["stats2"]), L.ptr(g["dres"]), L.ptr(G[fnn + ".weight"]),
                         L.ptr(G[fnn + ".bias"]), L.ptr(g["ln_ws"]), R, C, st)
                 done(fnn)
@@ -763,7 +871,7 @@ class CnnEngine(OptimizerExtMixin):
                 # d linear2.weight = dres^T . a, d linear1.weight = du^T . h, the biases' gradients their column sums
                 self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dres"]), C, L.ptr(g["ffa"]), D, L.ptr(G[w2]), D,
                         L.ptr(G[fn + ".linear2.bias"]), C, D, R, t, 0, ks, ws, st)
-                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["fda"]), D, L.ptr(ly["h"]), C, L.ptr(G[w1]), C,
+                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["fda"]), D, L.ptr(fin), C, L.ptr(G[w1]), C,
                         L.ptr(G[fn + ".linear1.bias"]), D, C, R, t, 0, ks, ws, st)
                 done(fn)
                 # dh = du . w1 + dres (the residual branch)
@@ -772,6 +880,8 @@ class CnnEngine(OptimizerExtMixin):
                         None, st)
                 g["dh1"].add_(g["dres"])
                 gcur = g["dh1"]
+            if self.sa_conv_kernel:
+                gcur = self._sa_conv_backward(p, P, G, l, ly, gcur, not p.trained, ks, ws, done)
             self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(gcur), L.ptr(xin), L.ptr(ly["a"]),
                     L.ptr(P[nn_ + ".weight"]), L.ptr(ly["stats"]), L.ptr(g["dres"]), L.ptr(G[nn_ + ".weight"]),
                     L.ptr(G[nn_ + ".bias"]), L.ptr(g["ln_ws"]), R, C, st)
@@ -945,7 +1055,7 @@ class CnnEngine(OptimizerExtMixin):
             self._gru_forward(p, P, prev, training or p.keep)
             return p
         if self.head == "sa":
-            self._sa_forward(p, P, prev, training or p.keep)
+            self._sa_forward(p, P, prev, training or p.keep, training, update_running_stats)
             return p
         if self.head == "none":
             return p

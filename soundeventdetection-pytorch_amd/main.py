@@ -125,6 +125,9 @@ def build_weak_parser():
                    help="--self_attention: width D of the feed-forward sub-layer of every encoder layer (a multiple of 32 up to 4096, "
                         "usually 4 x 128 = 512); 0 builds the attention half of a layer only")
     p.add_argument("--sa_activation", choices=["relu", "gelu"], default="relu", help="--sa_ffn: the activation of the feed-forward sub-layer")
+    p.add_argument("--sa_conv_kernel", type=int, default=0,
+                   help="--self_attention: taps k of the depthwise filter of a Conformer convolution module between the attention and the "
+                        "feed-forward sub-layer of every encoder layer (odd, 3 to 31); 0 builds no convolution module")
     return p
 
 
@@ -359,7 +362,8 @@ def get_spectogram_dataset_model_and_criterion(args, device):
         model = Csa_AvgPooling(cfg.classes_num, model_config=model_config, sa_heads=int(args.sa_heads),
                                pos_encoding=not args.no_pos_encoding, mel_bins=n_mel, frontend=frontend, attention=att,
                                sa_layers=int(getattr(args, "sa_layers", 1)), sa_ffn=int(getattr(args, "sa_ffn", 0)),
-                               sa_activation=getattr(args, "sa_activation", "relu"))
+                               sa_activation=getattr(args, "sa_activation", "relu"),
+                               sa_conv_kernel=int(getattr(args, "sa_conv_kernel", 0)))
     else:
         model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend, attention=att)
     model.set_precision(args.precision)
@@ -439,13 +443,16 @@ def validate_args(args):
     if getattr(args, "self_attention", False):
         if args.train_features.lower() == "waveform":
             raise ValueError("--self_attention attends over the frames of the spectrogram models: it needs --train_features Spectogram")
-        from .models.spectogram_models import check_sa_encoder, check_sa_geometry
+        from .models.spectogram_models import check_sa_conv_kernel, check_sa_encoder, check_sa_geometry
         check_sa_geometry(128, getattr(args, "sa_heads", 4))
+        check_sa_conv_kernel(getattr(args, "sa_conv_kernel", 0))
         check_sa_encoder(128, getattr(args, "sa_layers", 1), getattr(args, "sa_ffn", 0), getattr(args, "sa_activation", "relu"))
     elif getattr(args, "sa_heads", 4) != 4 or getattr(args, "no_pos_encoding", False):
         raise ValueError("--sa_heads / --no_pos_encoding configure the self-attention head: they need --self_attention")
     elif getattr(args, "sa_layers", 1) != 1 or getattr(args, "sa_ffn", 0) != 0 or getattr(args, "sa_activation", "relu") != "relu":
         raise ValueError("--sa_layers / --sa_ffn / --sa_activation configure the self-attention head: they need --self_attention")
+    elif getattr(args, "sa_conv_kernel", 0) != 0:
+        raise ValueError("--sa_conv_kernel configures the self-attention head: it needs --self_attention")
     for flag, value in (("--weak_pooling", weak_options(args).get("weak_pooling")), ("--eval_clip_pooling", getattr(args, "eval_clip_pooling", None))):
         if value == "att" and not att_head:
             raise ValueError(f"{flag} att pools with the attention head: it needs --attention_head")

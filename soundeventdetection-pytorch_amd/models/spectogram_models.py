@@ -444,6 +444,40 @@ def check_sa_encoder(channels: int, layers, ffn, activation) -> None:
         raise ValueError(f"sa_activation must be 'relu' or 'gelu', got {activation!r}")
 
 
+class _Conv1dParams(nn.Module):
+    """Parameter holder with torch.nn.Conv1d(in, out, k, groups=groups)'s names, shapes (weight (out, in / groups, k), bias (out,)) and
+    initial values, drawn in that module's order (weight, then bias)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, groups=1):
+        super().__init__()
+        self.in_channels, self.out_channels, self.kernel_size, self.groups = in_channels, out_channels, kernel_size, groups
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels // groups, kernel_size))
+        self.bias = nn.Parameter(torch.empty(out_channels))
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))   # same RNG draws as nn.Conv1d.__init__
+        bound = 1 / math.sqrt(in_channels // groups * kernel_size)
+        nn.init.uniform_(self.bias, -bound, bound)
+
+
+class _ConvModuleParams(nn.Module):
+    """Parameter holder of an encoder layer's Conformer convolution module: pointwise1 Conv1d(C, 2C, 1), depthwise Conv1d(C, C, k,
+    padding=(k-1)/2, groups=C), bn BatchNorm1d(C), pointwise2 Conv1d(C, C, 1), with torch's names and shapes; drawn in the order
+    pointwise1, depthwise, pointwise2 (the BatchNorm draws nothing)."""
+
+    def __init__(self, channels, kernel_size):
+        super().__init__()
+        self.pointwise1 = _Conv1dParams(channels, 2 * channels, 1)
+        self.depthwise = _Conv1dParams(channels, channels, kernel_size, groups=channels)
+        self.bn = _BatchNormParams(channels)
+        self.pointwise2 = _Conv1dParams(channels, channels, 1)
+
+
+def check_sa_conv_kernel(k) -> int:
+    """The tap count of the convolution module's depthwise filter: 0 (no module) or an odd integer in [3, 31]; a ValueError otherwise"""
+    if isinstance(k, bool) or not isinstance(k, int) or (k != 0 and (k < 3 or k > 31 or k % 2 == 0)):
+        raise ValueError(f"sa_conv_kernel must be 0 (no convolution module) or an odd integer in [3, 31], got {k!r}")
+    return k
+
+
 class Csa_AvgPooling(Cnn_AvgPooling):
     """The Cnn_AvgPooling feature extractor with a self-attention encoder layer as the temporal head (the conv-Transformer family
     of the DCASE task-4 systems; csrc/sed_mhsa.hip).  With R = B*t rows and C the last block's channels:
@@ -472,15 +506,31 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     attn.in_proj_weight (torch's constructor order), then with sa_ffn > 0 ffn.linear1.weight, ffn.linear1.bias, ffn.linear2.weight,
     ffn.linear2.bias (torch.nn.Linear's initial values; the LayerNorms draw nothing); after the layers event_fc's draws and its
     init_layer, then att_fc's with attention=True.
+    sa_conv_kernel = k > 0 (odd, 3..31) puts the Conformer convolution module between the attention and the feed-forward sub-layer of
+    every layer (csrc/sed_convmod.hip), post-LN like the other two, p = (k - 1) / 2:
+        g   = h . convm.pointwise1.weight^T + convm.pointwise1.bias                 [R][2C]  (Conv1d(C, 2C, 1))
+        v   = g[:, :C] * sigmoid(g[:, C:])                                          (F.glu over the channels)
+        z[b,i,c] = convm.depthwise.bias[c] + sum_{j<k} convm.depthwise.weight[c][0][j] * v[b, i + j - p, c]
+                                                    (Conv1d(C, C, k, padding=p, groups=C); frames outside the clip are zero)
+        y   = convm.bn(z)     BatchNorm1d(C) over the R rows (eps 1e-5, momentum 0.1; batch statistics and the running update in
+                              training, the running statistics in eval)
+        o   = silu(y) . convm.pointwise2.weight^T + convm.pointwise2.bias           (Conv1d(C, C, 1))
+        h_c = LayerNorm(h + o) (conv_norm)                     -> the FFN sub-layer's input, or the layer's output without an FFN
+    Layer 0 registers convm and conv_norm, layer l >= 1 convm_l{l} and conv_norm_l{l}, between that layer's attn_norm* and ffn*;
+    conv_module_state(state_dict, l) returns a layer's entries under the names above.  A third float64 buffer conv_config = (k,)
+    exists only when k > 0.  Per layer the draws are: the attention's, then convm.pointwise1.{weight, bias}, convm.depthwise.{weight,
+    bias}, convm.pointwise2.{weight, bias} (torch.nn.Conv1d's initial values; bn and conv_norm draw nothing), then the FFN's.  With
+    k = 0 the draws, the state_dict keys and the launches are those of a model without the argument.
     Refused: C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0, sa_layers < 1, sa_ffn not 0 or a multiple of 32 up to
-    4096 (and C > 512 with it), an activation other than relu / gelu."""
+    4096 (and C > 512 with it), an activation other than relu / gelu, sa_conv_kernel even, below 3 or above 31 (before any draw)."""
 
     ACTIVATIONS = ("relu", "gelu")
 
     def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, sa_heads=4, pos_encoding=True,
-                 mel_bins=None, frontend=None, attention=False, sa_layers=1, sa_ffn=0, sa_activation="relu"):
+                 mel_bins=None, frontend=None, attention=False, sa_layers=1, sa_ffn=0, sa_activation="relu", sa_conv_kernel=0):
         check_sa_geometry(int(model_config[-1][0]), sa_heads)
         check_sa_encoder(int(model_config[-1][0]), sa_layers, sa_ffn, sa_activation)
+        self.sa_conv_kernel = check_sa_conv_kernel(sa_conv_kernel)
         self.sa_heads, self.pos_encoding = int(sa_heads), bool(pos_encoding)
         self.sa_layers, self.sa_ffn, self.sa_activation = int(sa_layers), int(sa_ffn), sa_activation
         super().__init__(classes_num, model_config, precision, mel_bins=mel_bins, frontend=frontend, attention=attention)
@@ -492,9 +542,15 @@ class Csa_AvgPooling(Cnn_AvgPooling):
             setattr(self, nn_, _LayerNormParams(c_last))
             if l == 0:
                 self.register_buffer("attn_config", torch.tensor([float(self.sa_heads), float(self.pos_encoding)], dtype=torch.float64))
+            if self.sa_conv_kernel:
+                cm, cn = CnnEngine.sa_conv_names(l)
+                setattr(self, cm, _ConvModuleParams(c_last, self.sa_conv_kernel))
+                setattr(self, cn, _LayerNormParams(c_last))
             if self.sa_ffn:
                 setattr(self, fn, _FfnParams(c_last, self.sa_ffn))
                 setattr(self, fnn, _LayerNormParams(c_last))
+        if self.sa_conv_kernel:
+            self.register_buffer("conv_config", torch.tensor([float(self.sa_conv_kernel)], dtype=torch.float64))
         if self.sa_layers > 1 or self.sa_ffn:
             self.register_buffer("encoder_config", torch.tensor([float(self.sa_layers), float(self.sa_ffn),
                                                                  float(self.ACTIVATIONS.index(self.sa_activation))], dtype=torch.float64))
@@ -503,7 +559,35 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     def _make_engine(self, precision):
         return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="sa", sa_heads=self.sa_heads,
                          pos_encoding=self.pos_encoding, mel_bins=self.mel_bins, attention=self.attention, sa_layers=self.sa_layers,
-                         sa_ffn=self.sa_ffn, sa_activation=self.sa_activation)
+                         sa_ffn=self.sa_ffn, sa_activation=self.sa_activation, sa_conv_kernel=self.sa_conv_kernel)
+
+    def _flush_counters(self):
+        """The convolution modules' BatchNorm counters follow the conv blocks': counted on the host, folded in when looked at."""
+        n = self._nbt_pending
+        super()._flush_counters()
+        if n and self.sa_conv_kernel:
+            for l in range(self.sa_layers):
+                getattr(self, CnnEngine.sa_conv_names(l)[0]).bn.num_batches_tracked += n
+
+    @staticmethod
+    def conv_config_from_state_dict(weights):
+        """sa_conv_kernel from a state_dict's conv_config; 0 when the buffer is absent"""
+        if "conv_config" not in weights:
+            return 0
+        return int(round(weights["conv_config"].detach().cpu().double().tolist()[0]))
+
+    @staticmethod
+    def conv_module_state(weights, layer):
+        """Layer `layer`'s convolution-module entries of a state_dict without the module prefix: pointwise1.*, depthwise.*, bn.*,
+        pointwise2.* (they load into torch.nn.Conv1d / BatchNorm1d modules of those names) and, as conv_norm.*, the LayerNorm's."""
+        cm, cn = CnnEngine.sa_conv_names(layer)
+        out = {}
+        for k, v in weights.items():
+            if k.startswith(cm + "."):
+                out[k[len(cm) + 1:]] = v
+            elif k.startswith(cn + "."):
+                out["conv_norm." + k[len(cn) + 1:]] = v
+        return out
 
     @staticmethod
     def encoder_config_from_state_dict(weights):

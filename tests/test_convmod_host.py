@@ -1,0 +1,377 @@
+"""Host (no GPU): the float64 definition of the Conformer convolution module and the encoder layer around it (tests/convmod_formula.py)
+against torch.nn.Conv1d / F.glu / BatchNorm1d / F.silu / LayerNorm / TransformerEncoderLayer with autograd, the gates of that file
+against a plain fp32 implementation and against mutants of the definition, and Csa_AvgPooling's new parameters, buffers, state_dict,
+FlatParams order, draw order, refusals and command-line flag."""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as TF
+
+import convmod_formula as V
+import ffn_formula as F
+
+PKG = "soundeventdetection-pytorch_amd"
+CFG = [(32, 2), (64, 2)]
+C = 64
+TILE = 64          # a chain length for the host checks of the gates (the GPU test asks the library for the kernel's own)
+OLD_KEYS = ["attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "attn.out_proj.bias", "attn_norm.weight", "attn_norm.bias",
+            "attn_config", "event_fc.weight", "event_fc.bias"]
+CONV_KEYS = ["pointwise1.weight", "pointwise1.bias", "depthwise.weight", "depthwise.bias", "bn.weight", "bn.bias", "bn.running_mean",
+             "bn.running_var", "bn.num_batches_tracked", "pointwise2.weight", "pointwise2.bias"]
+
+
+@pytest.fixture(scope="module")
+def sed():
+    return importlib.import_module(PKG)
+
+
+def rel(a, b):
+    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1e-300, np.abs(np.asarray(b)).max()))
+
+
+def randomized(sed, layers, ffn, k, heads=2, seed=0):
+    """a model on the CPU whose encoder parameters and running statistics are all away from their initial values"""
+    torch.manual_seed(seed)
+    m = sed.Csa_AvgPooling(3, CFG, precision="fp32", sa_heads=heads, sa_layers=layers, sa_ffn=ffn, sa_activation="gelu", mel_bins=8,
+                           sa_conv_kernel=k)
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if n.startswith(("attn", "ffn", "conv")) and not n.startswith("conv_blocks"):
+                p.normal_(1.0 if ("norm" in n or ".bn." in n) and n.endswith("weight") else 0.0, 0.2)
+        for n, b in m.named_buffers():
+            if n.endswith("bn.running_mean") and n.startswith("convm"):
+                b.normal_(0.0, 0.3)
+            if n.endswith("bn.running_var") and n.startswith("convm"):
+                b.uniform_(0.5, 1.5)
+    return m
+
+
+class TorchConvModule(torch.nn.Module):
+    """the issue's chain in torch primitives"""
+
+    def __init__(self, Cc, k):
+        super().__init__()
+        self.pointwise1 = torch.nn.Conv1d(Cc, 2 * Cc, 1)
+        self.depthwise = torch.nn.Conv1d(Cc, Cc, k, padding=(k - 1) // 2, groups=Cc)
+        self.bn = torch.nn.BatchNorm1d(Cc)
+        self.pointwise2 = torch.nn.Conv1d(Cc, Cc, 1)
+        self.conv_norm = torch.nn.LayerNorm(Cc)
+
+    def forward(self, h):                   # (B, t, C)
+        x = TF.glu(self.pointwise1(h.transpose(1, 2)), dim=1)
+        x = self.pointwise2(TF.silu(self.bn(self.depthwise(x))))
+        return self.conv_norm(h + x.transpose(1, 2))
+
+
+class TorchLayer(torch.nn.Module):
+    def __init__(self, Cc, H, D, k):
+        super().__init__()
+        self.enc = torch.nn.TransformerEncoderLayer(Cc, H, max(D, 1), dropout=0.0, activation="gelu", batch_first=True, norm_first=False)
+        self.conv = TorchConvModule(Cc, k)
+        self.D = D
+
+    def forward(self, x):
+        e = self.enc
+        h = e.norm1(x + e.self_attn(x, x, x, need_weights=False)[0])
+        h = self.conv(h)
+        if self.D:
+            h = e.norm2(h + e.linear2(TF.gelu(e.linear1(h))))
+        return h
+
+
+@pytest.mark.parametrize("k", [3, 7, 31])
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("layers,D", [(1, 0), (2, 96)])
+def test_definition_against_torch(sed, k, training, layers, D):
+    B, t, H = 2, 9, 2
+    m = randomized(sed, layers, D, k, H, seed=k + layers)
+    sd = {n: (v.double() if v.is_floating_point() else v.clone()) for n, v in m.state_dict().items()}
+    rng = np.random.default_rng(k)
+    x, dh_out = rng.normal(0, 1, (B * t, C)), rng.normal(0, 1, (B * t, C))
+    W = {n: v.numpy() for n, v in sd.items() if n.startswith(("attn", "ffn", "convm", "conv_norm")) and "config" not in n}
+    ref = V.encoder(x, W, B, t, H, layers, D, "gelu", pos_encoding=True, training=training, dh_out=dh_out)
+    stack = []
+    for l in range(layers):
+        ly = TorchLayer(C, H, D, k).double()
+        enc = sed.Csa_AvgPooling.encoder_layer_state(sd, l)
+        ly.enc.load_state_dict(enc, strict=False)
+        assert set(enc) == {n for n, _ in ly.enc.named_parameters() if D or not n.startswith(("linear", "norm2"))}
+        ly.conv.load_state_dict(sed.Csa_AvgPooling.conv_module_state(sd, l))        # strict: the names and shapes are torch's
+        ly.train(training)
+        stack.append(ly)
+    xt = torch.from_numpy(x).view(B, t, C).clone().requires_grad_(True)
+    h = xt + torch.from_numpy(F.M.positional_table(t, C))
+    for ly in stack:
+        h = ly(h)
+    h.backward(torch.from_numpy(dh_out).view(B, t, C))
+    assert rel(ref["h"], h.detach().numpy().reshape(B * t, C)) < 1e-12
+    assert rel(ref["dx"], xt.grad.numpy().reshape(B * t, C)) < 1e-12
+    seen = 0
+    for l, ly in enumerate(stack):
+        an, nn_, fn, fnn = F.layer_names(l)
+        cm, cn = V.conv_names(l)
+        back = {"self_attn": an, "norm1": nn_, "linear1": fn + ".linear1", "linear2": fn + ".linear2", "norm2": fnn}
+        for n, p in ly.enc.named_parameters():
+            top, rest = n.split(".", 1)
+            if not D and top in ("linear1", "linear2", "norm2"):
+                continue
+            assert rel(ref[f"d_{back[top]}.{rest}"], p.grad.numpy()) < 1e-12, (l, n)
+            seen += 1
+        for n, p in ly.conv.named_parameters():
+            ours = (cn + n[len("conv_norm"):]) if n.startswith("conv_norm") else cm + "." + n
+            seen += 1
+            if training and n == "depthwise.bias":
+                # batch statistics remove a per-channel constant: this gradient is zero but for rounding (1e-12 of the other bias's)
+                tol = 1e-12 * np.abs(ref["d_" + cm + ".pointwise2.bias"]).max()
+                assert np.abs(ref["d_" + ours]).max() < tol and np.abs(p.grad.numpy()).max() < tol
+                continue
+            assert rel(ref["d_" + ours], p.grad.numpy()) < 1e-12, (l, n)
+        if training:
+            assert rel(ref[cm + ".bn.running_mean"], ly.conv.bn.running_mean.numpy()) < 1e-12
+            assert rel(ref[cm + ".bn.running_var"], ly.conv.bn.running_var.numpy()) < 1e-12
+    assert seen == (16 + (6 if D else 0)) * layers == len([n for n in ref if n.startswith("d_") and n != "dx"])
+
+
+def stages(case, B, t, k, dtype, mutant=None, training=True):
+    """Every launch's result in `dtype` arithmetic, each fed the reference's values rounded to fp32 (as the gates assume and the GPU
+    test feeds them).  -> (ref, got, gates)"""
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    g, w, bias = case["g"], case["w"], case["bias"]
+    R = B * t
+    ref, got, gates = {}, {}, {}
+    ref["v"] = V.glu(g)
+    ref["z"] = V.dwconv(ref["v"], w, bias, B, t)
+    got["v"] = V.glu(g, dtype, mutant)
+    got["z"] = V.dwconv(got["v"], w, bias, B, t, dtype, mutant)
+    fg = V.fwd_gates(g, w, bias, B, t, TILE)
+    gates.update(v=fg["v"], z=fg["z"])
+    z32 = f32(ref["z"])
+    bn = V.bn_coeffs(z32, case["gamma"], case["beta"], case["rmean"], case["rvar"], training)
+    bg = V.bn_coeffs(z32, case["gamma"], case["beta"], case["rmean"], case["rvar"], training, dtype, mutant)
+    fin = V.finalize_gates(z32, np.zeros_like(ref["z"]), case["gamma"], case["beta"], case["rmean"], case["rvar"], TILE)
+    for n in ("scale", "shift") + (("running_mean", "running_var") if training else ()):
+        ref[n], got[n], gates[n] = bn[n], bg[n], fin[n]
+    sc, sh, mu, inv = f32(bn["scale"]), f32(bn["shift"]), f32(bn["mean"]), f32(bn["invstd"])
+    ref["s"] = V.bn_silu(z32, sc, sh)[1]
+    got["s"] = V.bn_silu(z32, sc, sh, dtype)[1]
+    gates["s"] = V.bn_silu_gates(z32, sc, sh)["s"]
+    ref["gz"], ref["sum"], ref["sumx"] = V.bn_silu_bwd(case["ds"], z32, sc, sh, mu, inv)
+    got["gz"], got["sum"], got["sumx"] = V.bn_silu_bwd(case["ds"], z32, sc, sh, mu, inv, dtype, mutant)
+    gates.update(V.bn_silu_bwd_gates(case["ds"], z32, sc, sh, mu, inv, TILE))
+    ca, cb, cc = (f32(a) for a in V.bn_bwd_coeffs(ref["sum"], ref["sumx"], R, case["gamma"], mu, inv, training))
+    gz32, v32 = f32(ref["gz"]), f32(ref["v"])
+    dz = ca.astype(np.float64) * gz32 + cb.astype(np.float64) * z32 + cc.astype(np.float64)
+    dv, ref["dw"], ref["dbias"] = V.dwconv_bwd(dz, v32, w, B, t)
+    ref["dg"] = V.glu_bwd(dv, g)
+    dzg = (ca * gz32 + (cb * z32 + cc)).astype(dtype)
+    dvg, got["dw"], got["dbias"] = V.dwconv_bwd(dzg, v32, w, B, t, dtype)
+    got["dg"] = V.glu_bwd(dvg, g, dtype)
+    gates.update(V.bwd_gates(gz32, z32, ca, cb, cc, v32, g, w, B, t, TILE))
+    return ref, got, gates
+
+
+STAGE_KEYS = ("v", "z", "scale", "shift", "running_mean", "running_var", "s", "gz", "sum", "sumx", "dg", "dw", "dbias")
+
+
+@pytest.mark.parametrize("k", [3, 7, 31])
+def test_plain_fp32_implementation_passes_every_gate(k):
+    B, t, Cc = 3, 37, 32
+    case = V.gaussian_case(np.random.default_rng(k), B, t, Cc, k)
+    ref, got, gates = stages(case, B, t, k, np.float32)
+    for n in STAGE_KEYS:
+        ok, worst = V.check(got[n], ref[n], gates[n], ("f32", k, n))
+        assert ok, (n, worst)
+    # the family keeps |mean| within the standard deviation per channel, so that q / n - mean^2 does not cancel in the reference
+    z = ref["z"]
+    assert (np.abs(z.mean(axis=0)) <= 2.0 * z.std(axis=0)).all()
+
+
+def test_eval_form_passes_the_gates():
+    B, t, Cc, k = 2, 21, 16, 7
+    case = V.gaussian_case(np.random.default_rng(5), B, t, Cc, k)
+    ref, got, gates = stages(case, B, t, k, np.float32, training=False)
+    for n in ("scale", "shift", "s", "gz", "dg", "dw", "dbias"):
+        assert V.check(got[n], ref[n], gates[n], ("eval", n))[0], n
+
+
+@pytest.mark.parametrize("mutant,key", [("halo_neighbour", "z"), ("flipped", "z"), ("tap_offset", "z"), ("glu_swapped", "v"),
+                                        ("unbiased_norm", "scale"), ("silu_grad_at_z", "gz"), ("no_dw_bias", "z"),
+                                        ("filters_swapped", "z")])
+def test_mutants_fail_the_fp32_gate(mutant, key):
+    B, t, Cc, k = 3, 37, 32, 7
+    case = V.gaussian_case(np.random.default_rng(9), B, t, Cc, k)
+    ref, got, gates = stages(case, B, t, k, np.float32)
+    assert V.check(got[key], ref[key], gates[key], ("plain", key))[0]
+    _, bad, _ = stages(case, B, t, k, np.float32, mutant=mutant)
+    assert not V.check(bad[key], ref[key], gates[key], (mutant, key))[0]
+
+
+def test_missing_residual_fails_the_gate(sed):
+    B, t, k = 2, 9, 7
+    m = randomized(sed, 1, 0, k, seed=3)
+    Wc = V.conv_state({n: v.double().numpy() for n, v in m.state_dict().items() if n.startswith(("convm", "conv_norm"))}, 0)
+    Wn = (Wc["conv_norm.weight"], Wc["conv_norm.bias"])
+    h = np.random.default_rng(4).normal(0, 1, (B * t, C))
+    ref = V.sublayer(h, Wc, Wn, B, t)["hc"]
+    gate = F.stack_gate(ref, 1, C, 2 * C, t)          # the layer-level gate of the stack: a sub-layer is fewer stages than a layer
+    assert V.check(V.sublayer(h, Wc, Wn, B, t, dtype=np.float32)["hc"], ref, gate, "plain fp32 sub-layer")[0]
+    assert not V.check(V.sublayer(h, Wc, Wn, B, t, mutant="no_residual")["hc"], ref, gate, "no_residual")[0]
+
+
+def test_exact_integer_condition_of_the_gpu_cases():
+    """tests/test_gpu_convmod.py's exact family: fp32 arithmetic reproduces float64 bit for bit, in z, dv and the filter gradients"""
+    for (B, t, Cc, k) in [(2, 5, 4, 3), (3, 67, 32, 7), (2, 131, 96, 31)]:
+        case = V.exact_case(np.random.default_rng(B + t + k), B, t, Cc, k)
+        v = V.glu(case["g"])
+        assert np.array_equal(v, case["g"][:, :Cc]) and np.array_equal(V.glu(case["g"], np.float32), v)
+        z = V.dwconv(v, case["w"], case["bias"], B, t)
+        assert np.array_equal(z, np.round(z)) and np.array_equal(V.dwconv(v, case["w"], case["bias"], B, t, np.float32), z)
+        assert np.count_nonzero(z) > 0
+        dz = case["ca"].astype(np.float64) * case["gz"] + case["cb"].astype(np.float64) * case["z"] + case["cc"]
+        ref = V.dwconv_bwd(dz, case["v"], case["w"], B, t)
+        got = V.dwconv_bwd(dz.astype(np.float32), case["v"], case["w"], B, t, np.float32)
+        for a, b in zip(ref, got):
+            assert np.array_equal(a, b) and np.abs(a).max() < 2 ** 24
+        dg = V.glu_bwd(ref[0], case["g"])
+        assert np.array_equal(dg[:, :Cc], ref[0]) and not dg[:, Cc:].any()
+
+
+def test_state_dict_keys_and_config(sed):
+    torch.manual_seed(0)
+    default = sed.Csa_AvgPooling(3, CFG, precision="fp32", sa_heads=2, mel_bins=8, sa_conv_kernel=0)
+    head = [k for k in default.state_dict() if not k.startswith("conv_blocks.")]
+    assert sorted(head) == sorted(OLD_KEYS), "a k = 0 model's state_dict is not today's"
+    assert sed.Csa_AvgPooling.conv_config_from_state_dict(default.state_dict()) == 0
+    assert sed.Csa_AvgPooling.conv_module_state(default.state_dict(), 0) == {}
+    full = sed.Csa_AvgPooling(3, CFG, precision="fp32", sa_heads=2, mel_bins=8, sa_layers=2, sa_ffn=96, sa_conv_kernel=7)
+    sd = full.state_dict()
+    shapes = {"pointwise1.weight": (2 * C, C, 1), "pointwise1.bias": (2 * C,), "depthwise.weight": (C, 1, 7), "depthwise.bias": (C,),
+              "bn.weight": (C,), "bn.bias": (C,), "bn.running_mean": (C,), "bn.running_var": (C,), "bn.num_batches_tracked": (),
+              "pointwise2.weight": (C, C, 1), "pointwise2.bias": (C,)}
+    assert list(shapes) == CONV_KEYS
+    for l in range(2):
+        cm, cn = V.conv_names(l)
+        st = sed.Csa_AvgPooling.conv_module_state(sd, l)
+        assert list(st) == CONV_KEYS + ["conv_norm.weight", "conv_norm.bias"]
+        for n, shp in shapes.items():
+            assert tuple(sd[f"{cm}.{n}"].shape) == shp and st[n] is sd[f"{cm}.{n}"]
+        assert bool((sd[cn + ".weight"] == 1).all()) and not sd[cn + ".bias"].any()
+        assert bool((sd[cm + ".bn.weight"] == 1).all()) and not sd[cm + ".bn.bias"].any()
+        assert not sd[cm + ".bn.running_mean"].any() and bool((sd[cm + ".bn.running_var"] == 1).all())
+    assert sd["conv_config"].dtype == torch.float64 and sd["conv_config"].tolist() == [7.0]
+    assert sd["encoder_config"].tolist() == [2.0, 96.0, 0.0] and sd["attn_config"].tolist() == [2.0, 1.0]
+    assert sed.Csa_AvgPooling.conv_config_from_state_dict(sd) == 7
+    # the order of the modules: attn, attn_norm, convm, conv_norm, ffn, ffn_norm per layer
+    tops = []
+    for n, _ in full.named_parameters():
+        top = n.split(".")[0]
+        if top != "conv_blocks" and (not tops or tops[-1] != top):
+            tops.append(top)
+    assert tops == ["attn", "attn_norm", "convm", "conv_norm", "ffn", "ffn_norm", "attn_l1", "attn_norm_l1", "convm_l1", "conv_norm_l1",
+                    "ffn_l1", "ffn_norm_l1", "event_fc"]
+    twin = sed.Csa_AvgPooling(3, CFG, precision="fp32", sa_heads=2, mel_bins=8, sa_layers=2, sa_ffn=96, sa_conv_kernel=7)
+    twin.load_state_dict(sd)
+    clone = full.clone_without_engines()
+    assert clone.engine.sa_conv_kernel == 7 and clone.engine is not full.engine
+    assert clone.convm.bn.running_var is not full.convm.bn.running_var and torch.equal(clone.convm.bn.running_var, full.convm.bn.running_var)
+    # the BatchNorm counters follow the conv blocks': pending forwards are folded in when the state_dict is looked at
+    full._nbt_pending = 3
+    sd = full.state_dict()
+    assert int(sd["convm.bn.num_batches_tracked"]) == 3 == int(sd["convm_l1.bn.num_batches_tracked"]) == int(sd["conv_blocks.0.bn1.num_batches_tracked"])
+    assert sed.CnnEngine.sa_layer_names(1) == ("attn_l1", "attn_norm_l1", "ffn_l1", "ffn_norm_l1")
+    assert sed.CnnEngine.sa_conv_names(0) == ("convm", "conv_norm") and sed.CnnEngine.sa_conv_names(2) == ("convm_l2", "conv_norm_l2")
+
+
+def replay(sed, seed, K, heads, layers, ffn, k):
+    """the documented draw order, by hand: conv blocks, then per layer the attention draws, pointwise1, depthwise, pointwise2 and
+    linear1, linear2; event_fc last"""
+    sm = sed.models.spectogram_models
+    torch.manual_seed(seed)
+    out = {}
+    cin = 1
+    for i, (c, pool) in enumerate(CFG):
+        blk = sed.ConvBlock(in_channels=cin, out_channels=c, pool_size=pool)
+        out.update({f"conv_blocks.{i}.{n}": p for n, p in blk.named_parameters()})
+        cin = c
+    for l in range(layers):
+        an, _, fn, _ = F.layer_names(l)
+        cm, _ = V.conv_names(l)
+        out.update({f"{an}.{n}": p for n, p in sm._MhaParams(cin, heads).named_parameters()})
+        if k:
+            for name, mod in (("pointwise1", torch.nn.Conv1d(cin, 2 * cin, 1)), ("depthwise", torch.nn.Conv1d(cin, cin, k, padding=k // 2, groups=cin)),
+                              ("pointwise2", torch.nn.Conv1d(cin, cin, 1))):
+                out.update({f"{cm}.{name}.{n}": p for n, p in mod.named_parameters()})
+        if ffn:
+            l1 = sm._LinearParams(cin, ffn)
+            l2 = sm._LinearParams(ffn, cin)
+            out.update({f"{fn}.linear1.{n}": p for n, p in l1.named_parameters()})
+            out.update({f"{fn}.linear2.{n}": p for n, p in l2.named_parameters()})
+    fc = sm._LinearParams(cin, K)
+    sed.init_layer(fc)
+    out.update({f"event_fc.{n}": p for n, p in fc.named_parameters()})
+    return out
+
+
+@pytest.mark.parametrize("layers,ffn,k", [(1, 0, 3), (2, 96, 7), (2, 96, 0), (1, 0, 0)])
+def test_initial_values_follow_the_documented_draw_order(sed, layers, ffn, k):
+    """bit for bit; the convolutions' initial values are torch.nn.Conv1d's own (the replay builds those modules)"""
+    torch.manual_seed(11)
+    m = sed.Csa_AvgPooling(3, CFG, precision="fp32", sa_heads=2, sa_layers=layers, sa_ffn=ffn, sa_conv_kernel=k)
+    want = replay(sed, 11, 3, 2, layers, ffn, k)
+    got = dict(m.named_parameters())
+    assert set(want) == {n for n in got if "norm" not in n and ".bn." not in n}
+    for n, p in want.items():
+        assert torch.equal(p, got[n]), n
+    if not k:           # k = 0 is the model without the argument, draw for draw
+        torch.manual_seed(11)
+        old = sed.Csa_AvgPooling(3, CFG, precision="fp32", sa_heads=2, sa_layers=layers, sa_ffn=ffn)
+        assert list(old.state_dict()) == list(m.state_dict())
+        for n, v in old.state_dict().items():
+            assert torch.equal(v, m.state_dict()[n]), n
+
+
+def test_flat_params_group_order(sed):
+    """backward completion order: event_fc, then per layer from the last to the first ffn_norm, ffn, conv_norm, convm, attn_norm, attn"""
+    m = sed.Csa_AvgPooling(3, CFG, precision="fp32", sa_heads=2, sa_layers=2, sa_ffn=96, attention=True, sa_conv_kernel=7)
+    flat = sed.train.FlatParams(m, n_buckets=0)
+    keys = [k for k, _, _ in flat.groups]
+    assert keys == ["att_fc", "event_fc", "ffn_norm_l1", "ffn_l1", "conv_norm_l1", "convm_l1", "attn_norm_l1", "attn_l1", "ffn_norm", "ffn",
+                    "conv_norm", "convm", "attn_norm", "attn", "conv_blocks.1", "conv_blocks.0"]
+    spans = sorted((s, e) for _, s, e in flat.groups)
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), "the groups are not disjoint contiguous slices"
+    m = sed.Csa_AvgPooling(3, CFG, precision="fp32", sa_heads=2, sa_conv_kernel=31)
+    keys = [k for k, _, _ in sed.train.FlatParams(m, n_buckets=0).groups]
+    assert keys == ["event_fc", "conv_norm", "convm", "attn_norm", "attn", "conv_blocks.1", "conv_blocks.0"]
+
+
+def test_refusals(sed):
+    for k in (1, 2, 4, 30, 33, -3, 7.0, True, None, "7"):
+        state = torch.random.get_rng_state()
+        with pytest.raises(ValueError, match="sa_conv_kernel"):
+            sed.Csa_AvgPooling(3, CFG, sa_heads=2, sa_conv_kernel=k)
+        assert torch.equal(state, torch.random.get_rng_state()), "a refused model drew random numbers"
+    for k in (1, 4, 33):
+        with pytest.raises(ValueError, match="sa_conv_kernel"):
+            sed.CnnEngine(3, CFG, head="sa", sa_heads=2, sa_conv_kernel=k)
+    with pytest.raises(ValueError, match="sa_conv_kernel"):
+        sed.CnnEngine(3, CFG, head="fc", sa_conv_kernel=7)
+    for ok in (3, 17, 31):
+        assert sed.Csa_AvgPooling(3, CFG, sa_heads=2, sa_conv_kernel=ok).engine.sa_conv_kernel == ok
+
+
+def test_command_line_flag(sed):
+    main = importlib.import_module(PKG + ".main")
+    full = main.build_full_parser()
+    base = ["--train_features", "Spectogram", "--dataset_name", "synthetic"]
+    args = full.parse_args(base + ["--self_attention", "--sa_conv_kernel", "7"])
+    assert args.sa_conv_kernel == 7
+    main.validate_args(args)
+    assert full.parse_args(base).sa_conv_kernel == 0
+    main.validate_args(full.parse_args(base))
+    for bad in ("4", "1", "33"):
+        with pytest.raises(ValueError, match="sa_conv_kernel"):
+            main.validate_args(full.parse_args(base + ["--self_attention", "--sa_conv_kernel", bad]))
+    with pytest.raises(ValueError, match="--self_attention"):
+        main.validate_args(full.parse_args(base + ["--sa_conv_kernel", "7"]))
