@@ -40,6 +40,9 @@ carries its own terms only; TILE is the chain length of a per-workgroup fp32 sum
           d_sigma = C_SIG u sigma, d_(1 - sigma) = d_sigma + u (1 - sigma), d_P = d_sigma (1 - sigma) + sigma d_(1 - sigma) + u P,
           so |a| P gate_dv + |dv a| d_P + 2 u |dv a| P
   dw, db  (TILE + 2) u sum |dz||v| + sum gate_dz |v|  and  (TILE + 2) u sum |dz| + sum gate_dz  (fp32 per workgroup, fp64 across)
+Inside the engine (tests/test_gpu_sa_at_size.py) a launch is fed the engine's own values instead, whose gate is then zero; what that
+needs beyond the above is composed, not modelled anew, at the end of the gates section: gz behind the GEMM whose ds it overwrites
+(gz_through_ds), the BatchNorm backward finalisations on given partial rows (bn_bwd_finalize) and the eval-mode coefficients (bn_eval).
 C_SIG and C_DSILU are the accuracy of the device expf / sigmoid as the kernels use it.  The ROCm installation carries no table for
 it, so both were measured once on the MI355X against float64 (tools/convmod_time.py --csig: v = a sigmoid(x) and silu'(x) over the
 dense grid x in [-30, 30], step 2^-10, and x = 40) and doubled: the measured worst errors were 23.59 u |v| for the GLU (at x = -23.07),
@@ -47,6 +50,8 @@ dense grid x in [-30, 30], step 2^-10, and x = 40) and doubled: the measured wor
 x << 0; over |x| <= 8, where the tests' Gaussian operands lie, the tool reports the smaller figures of its second grid.  C_SIG covers
 the GLU and the SiLU.
 """
+import math
+
 import numpy as np
 
 import ffn_formula as F
@@ -392,6 +397,65 @@ def bwd_gates(gz, z, ca, cb, cc, v, g, w, B, t, tile):
         sv = np.abs(shift_frames(v, j - p, B, t))
         gdw[:, j] = (tile + 2) * U * (np.abs(dz) * sv).sum(axis=0) + (gdz * sv).sum(axis=0)
     return dict(dg=np.concatenate([gval, ggate], axis=1), dw=gdw, dbias=(tile + 2) * U * np.abs(dz).sum(axis=0) + gdz.sum(axis=0))
+
+
+# ---- the module inside the engine (tests/test_gpu_sa_at_size.py): compositions of the gates above with those of the launches around
+# them.  Nothing new is modelled: the GEMM's gate comes from the caller (tests/test_gpu_crnn_exact_oracle.py's form), the BatchNorm
+# finalisations' are the forms of tests/test_gpu_ops_exact_oracle.py (test_bn_bwd_finalize, test_bn_eval_coeffs) in numpy.
+U64 = 2.0 ** -53
+SAFE = 4.0                   # that file's safety factor over the operation count
+
+
+def exact_colsum(part):
+    """float64 column sums of partial rows [nparts][...] holding fp32 values, exact to the last float64 rounding"""
+    a = np.asarray(part)
+    if np.finfo(np.longdouble).nmant >= 63:
+        return a.astype(np.longdouble).sum(axis=0).astype(np.float64)
+    flat = a.reshape(a.shape[0], -1).astype(np.float64)
+    return np.array([math.fsum(col) for col in flat.T]).reshape(a.shape[1:])
+
+
+def gz_through_ds(ds_ref, e_ds, z, scale, shift, mean, invstd, tile):
+    """sed_bn_silu_bwd_reduce writing gz over the ds a sed_gemm_nt has just produced: ds is seen only through gz = ds silu'(y).
+    ds_ref: the product in float64, e_ds: its gate.  -> ((gz, sum gz, sum gz xhat) from ds_ref, their gates): the GEMM's error passed
+    on, e_ds A(y) with A the absolute-value form of silu' (and its column sums, with X for the second), plus the launch's own gates
+    taken at the largest |ds| the GEMM's gate allows, |ds_ref| + e_ds."""
+    ds_ref, e_ds, z, scale, shift, mean, invstd = (np.asarray(a, dtype=np.float64) for a in (ds_ref, e_ds, z, scale, shift, mean, invstd))
+    y, _ = bn_silu(z, scale, shift)
+    own = bn_silu_bwd_gates(np.abs(ds_ref) + e_ds, z, scale, shift, mean, invstd, tile)
+    passed = e_ds * silu_grad_abs(y)
+    X = (np.abs(z) + np.abs(mean)) * np.abs(invstd)
+    return bn_silu_bwd(ds_ref, z, scale, shift, mean, invstd), dict(gz=own["gz"] + passed, sum=own["sum"] + passed.sum(axis=0),
+                                                                     sumx=own["sumx"] + (passed * X).sum(axis=0))
+
+
+def bn_bwd_finalize(part, n, gamma, mean, invstd, training=True):
+    """sed_bn_bwd_finalize (training) / sed_bn_eval_bwd_finalize on the partial rows part [nparts][2][C] = (sum gz, sum gz xhat) it is
+    given.  -> (dbeta, dgamma, ca, cb, cc in float64 from the exact column sums, their gates): one rounding of a float64 value each
+    (SAFE u), and the kernel's fp64 sum of nparts rows charged (ceil(nparts / 256) + 12) 2^-53 of the sum of magnitudes, passed on to
+    cb and cc.  Eval: cb and cc are exactly 0 (gate 0)."""
+    part, gm, mu, is_ = (np.asarray(a, dtype=np.float64) for a in (part, gamma, mean, invstd))
+    nparts = part.shape[0]
+    (s, q), (sa, qa) = exact_colsum(part), exact_colsum(np.abs(part))
+    c64 = (-(-nparts // 256) + 12) * U64
+    ca, cb, cc = bn_bwd_coeffs(s, q, n, gm, mu, is_, training)
+    gates = dict(dbeta=SAFE * U * np.abs(s) + c64 * sa, dgamma=SAFE * U * np.abs(q) + c64 * qa, ca=SAFE * U * np.abs(ca),
+                 cb=np.zeros_like(ca), cc=np.zeros_like(ca))
+    if training:
+        Sc = np.abs(gm * is_) * (np.abs(s) / n + np.abs(mu * is_ * q) / n)
+        gates["cb"] = SAFE * U * np.abs(cb) + np.abs(gm * is_ * is_) * c64 * qa / n
+        gates["cc"] = SAFE * U * Sc + np.abs(gm * is_) * c64 * (sa + np.abs(mu * is_) * qa) / n + 4.0 * U64 * Sc
+    return dict(dbeta=s, dgamma=q, ca=ca, cb=cb, cc=cc), gates
+
+
+def bn_eval(gamma, beta, rmean, rvar, eps=EPS):
+    """sed_bn_eval_coeffs and sed_bn_eval_stats.  -> (scale, shift, mean, invstd in float64, their gates): invstd = 1 / sqrtf(rvar + eps)
+    is 4 roundings, scale 5, shift 7 of |beta| + |mean scale| (test_bn_eval_coeffs); mean is the running mean's own bits (gate 0)."""
+    gamma, beta, rmean, rvar = (np.asarray(a, dtype=np.float64) for a in (gamma, beta, rmean, rvar))
+    r = bn_coeffs(np.zeros((1, gamma.shape[0])), gamma, beta, rmean, rvar, False, eps=eps)
+    ref = {n: r[n] for n in ("scale", "shift", "mean", "invstd")}
+    return ref, dict(scale=SAFE * 5 * U * np.abs(r["scale"]), shift=SAFE * 7 * U * (np.abs(beta) + np.abs(rmean * r["scale"])),
+                     mean=np.zeros_like(rmean), invstd=SAFE * 4 * U * r["invstd"])
 
 
 # ---- operand families ---------------------------------------------------------------------------------------------------------------

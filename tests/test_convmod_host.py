@@ -1,6 +1,7 @@
 """Host (no GPU): the float64 definition of the Conformer convolution module and the encoder layer around it (tests/convmod_formula.py)
 against torch.nn.Conv1d / F.glu / BatchNorm1d / F.silu / LayerNorm / TransformerEncoderLayer with autograd, the gates of that file
-against a plain fp32 implementation and against mutants of the definition, and Csa_AvgPooling's new parameters, buffers, state_dict,
+against a plain fp32 implementation and against mutants of the definition (also at the geometry of tests/test_gpu_sa_at_size.py, with the
+gate compositions that file adds), and Csa_AvgPooling's new parameters, buffers, state_dict,
 FlatParams order, draw order, refusals and command-line flag."""
 import importlib
 
@@ -175,9 +176,10 @@ def stages(case, B, t, k, dtype, mutant=None, training=True):
 STAGE_KEYS = ("v", "z", "scale", "shift", "running_mean", "running_var", "s", "gz", "sum", "sumx", "dg", "dw", "dbias")
 
 
-@pytest.mark.parametrize("k", [3, 7, 31])
-def test_plain_fp32_implementation_passes_every_gate(k):
-    B, t, Cc = 3, 37, 32
+AT_SIZE = (4, 130, 128)     # (B, t, C) of tests/test_gpu_sa_at_size.py: three frame tiles per clip, R = 520
+
+
+def plain_fp32_passes_every_gate(B, t, Cc, k):
     case = V.gaussian_case(np.random.default_rng(k), B, t, Cc, k)
     ref, got, gates = stages(case, B, t, k, np.float32)
     for n in STAGE_KEYS:
@@ -188,6 +190,16 @@ def test_plain_fp32_implementation_passes_every_gate(k):
     assert (np.abs(z.mean(axis=0)) <= 2.0 * z.std(axis=0)).all()
 
 
+@pytest.mark.parametrize("k", [3, 7, 31])
+def test_plain_fp32_implementation_passes_every_gate(k):
+    plain_fp32_passes_every_gate(3, 37, 32, k)
+
+
+@pytest.mark.parametrize("k", [7, 31])
+def test_plain_fp32_implementation_passes_every_gate_at_size(k):
+    plain_fp32_passes_every_gate(*AT_SIZE, k)
+
+
 def test_eval_form_passes_the_gates():
     B, t, Cc, k = 2, 21, 16, 7
     case = V.gaussian_case(np.random.default_rng(5), B, t, Cc, k)
@@ -196,16 +208,109 @@ def test_eval_form_passes_the_gates():
         assert V.check(got[n], ref[n], gates[n], ("eval", n))[0], n
 
 
-@pytest.mark.parametrize("mutant,key", [("halo_neighbour", "z"), ("flipped", "z"), ("tap_offset", "z"), ("glu_swapped", "v"),
-                                        ("unbiased_norm", "scale"), ("silu_grad_at_z", "gz"), ("no_dw_bias", "z"),
-                                        ("filters_swapped", "z")])
-def test_mutants_fail_the_fp32_gate(mutant, key):
-    B, t, Cc, k = 3, 37, 32, 7
+MUTANTS = [("halo_neighbour", "z"), ("flipped", "z"), ("tap_offset", "z"), ("glu_swapped", "v"), ("unbiased_norm", "scale"),
+           ("silu_grad_at_z", "gz"), ("no_dw_bias", "z"), ("filters_swapped", "z")]
+
+
+def mutant_fails_the_fp32_gate(mutant, key, B, t, Cc, k):
     case = V.gaussian_case(np.random.default_rng(9), B, t, Cc, k)
     ref, got, gates = stages(case, B, t, k, np.float32)
     assert V.check(got[key], ref[key], gates[key], ("plain", key))[0]
     _, bad, _ = stages(case, B, t, k, np.float32, mutant=mutant)
     assert not V.check(bad[key], ref[key], gates[key], (mutant, key))[0]
+
+
+@pytest.mark.parametrize("mutant,key", MUTANTS)
+def test_mutants_fail_the_fp32_gate(mutant, key):
+    mutant_fails_the_fp32_gate(mutant, key, 3, 37, 32, 7)
+
+
+@pytest.mark.parametrize("k", [7, 31])
+@pytest.mark.parametrize("mutant,key", MUTANTS)
+def test_mutants_fail_the_fp32_gate_at_size(mutant, key, k):
+    """at R = 520 the unbiased variance differs from the biased one by 1 / 519 only: the narrowest of the eight"""
+    mutant_fails_the_fp32_gate(mutant, key, *AT_SIZE, k)
+
+
+# ---- the compositions tests/test_gpu_sa_at_size.py adds for the module inside the engine (convmod_formula: gz_through_ds,
+# bn_bwd_finalize, bn_eval): a plain fp32 evaluation passes, a mutant fails
+def _through_ds_case(B=2, t=70, Cc=32, k=7, seed=12):
+    rng = np.random.default_rng(seed)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)
+    case = V.gaussian_case(rng, B, t, Cc, k)
+    z32 = f32(V.dwconv(V.glu(case["g"]), case["w"], case["bias"], B, t))
+    bn = V.bn_coeffs(z32, case["gamma"], case["beta"], case["rmean"], case["rvar"], True)
+    co = tuple(f32(bn[n]) for n in ("scale", "shift", "mean", "invstd"))
+    dres, w2 = f32(rng.standard_normal((B * t, Cc))), f32(rng.uniform(-1, 1, (Cc, Cc)) / np.sqrt(Cc))
+    a, b = dres.astype(np.float64), w2.T.astype(np.float64)
+    return case, z32, co, dres, w2, a @ b.T, 4.0 * (Cc + 1) * V.U * (np.abs(a) @ np.abs(b).T)
+
+
+def test_gz_through_an_in_place_ds_passes_and_mutants_fail():
+    case, z32, co, dres, w2, ds_ref, e_ds = _through_ds_case()
+    ref, gates = V.gz_through_ds(ds_ref, e_ds, z32, *co, TILE)
+    # e_ds = 0 and the product rounded to fp32 is the gate a launch fed the reference's ds has
+    own = V.bn_silu_bwd_gates(ds_ref, z32, *co, TILE)
+    assert all((gates[n] >= own[n]).all() for n in ("gz", "sum", "sumx"))
+    for w, good in ((w2, True), (w2.T.copy(), False)):          # the mutant: pointwise2.weight not transposed in the product
+        ds32 = dres @ w
+        got = V.bn_silu_bwd(ds32, z32, *co, dtype=np.float32)
+        for n, a, r in zip(("gz", "sum", "sumx"), got, ref):
+            assert V.check(a, r, gates[n], ("through ds", good, n))[0] == good, (good, n)
+    bad = V.bn_silu_bwd(dres @ w2, z32, *co, dtype=np.float32, mutant="silu_grad_at_z")
+    assert not V.check(bad[0], ref[0], gates["gz"], "silu' at z through ds")[0]
+    # a ds that is off by a few of ITS gates fails gz: the passed-on term is the GEMM's gate, not a loosening of it
+    off = (ds_ref + 3.0 * e_ds).astype(np.float32)
+    assert not V.check(V.bn_silu_bwd(off, z32, *co, dtype=np.float32)[0], ref[0], gates["gz"], "ds three gates off")[0]
+
+
+@pytest.mark.parametrize("training", [True, False])
+def test_bn_bwd_finalize_reference_and_gates(training):
+    case, z32, co, dres, w2, ds_ref, _ = _through_ds_case()
+    sc, sh, mu, inv = co
+    R, Cc = z32.shape
+    gz = V.bn_silu_bwd(ds_ref, z32, sc, sh, mu, inv)[0].astype(np.float32)
+    xh = (z32.astype(np.float64) - mu) * inv
+    rows = [slice(i, min(i + 64, R)) for i in range(0, R, 64)]
+    part = np.stack([np.stack([gz[r].sum(axis=0, dtype=np.float32), (gz[r] * xh[r]).sum(axis=0).astype(np.float32)]) for r in rows])
+    assert part.shape == (3, 2, Cc)
+    ref, gates = V.bn_bwd_finalize(part, R, case["gamma"], mu, inv, training)
+
+    def plain(p, n, train):         # the kernel's arithmetic: float64 sums and coefficients, each result rounded once to fp32
+        s, q = p.astype(np.float64).sum(axis=0)
+        ca, cb, cc = V.bn_bwd_coeffs(s, q, n, case["gamma"], mu, inv, train)
+        return {n_: np.asarray(a, dtype=np.float32) for n_, a in (("dbeta", s), ("dgamma", q), ("ca", ca), ("cb", cb), ("cc", cc))}
+
+    fails = lambda got: {n for n in ref if not V.check(got[n], ref[n], gates[n], ("finalize", training, n))[0]}
+    assert not fails(plain(part, R, training))
+    assert fails(plain(part[:-1], R, training)) >= {"dbeta", "dgamma"} | ({"cb", "cc"} if training else set())     # a part count one short
+    assert fails(plain(part, R - 1, training)) == ({"cb", "cc"} if training else set())             # a wrong row count
+    assert fails(plain(part, R, not training)) == {"cb", "cc"}                                      # the other mode's form
+    if not training:
+        assert not ref["cb"].any() and not ref["cc"].any() and not gates["cb"].any() and not gates["cc"].any()
+
+
+def test_bn_eval_reference_and_gates():
+    case = V.gaussian_case(np.random.default_rng(2), 2, 9, 32, 7)
+    gamma, beta, rm, rv = (case[n] for n in ("gamma", "beta", "rmean", "rvar"))
+    ref, gates = V.bn_eval(gamma, beta, rm, rv)
+    eps = np.float32(V.EPS)
+
+    def plain(e):                   # sed_bn_eval_stats / sed_bn_eval_coeffs in fp32
+        invstd = np.float32(1) / np.sqrt(rv + e)
+        scale = gamma * invstd
+        return dict(mean=rm, invstd=invstd, scale=scale, shift=beta - rm * scale)
+
+    got = plain(eps)
+    assert all(a.dtype == np.float32 for a in got.values())
+    for n in ref:
+        assert V.check(got[n], ref[n], gates[n], ("eval", n))[0], n
+    assert not gates["mean"].any()
+    bad = plain(np.float32(0))      # eps left out: 5e-6 / var relative
+    for n in ("invstd", "scale"):
+        assert not V.check(bad[n], ref[n], gates[n], ("eval without eps", n))[0], n
+    biased = V.bn_coeffs(np.zeros((1, 32)), gamma, beta, rm, rv * (519.0 / 520.0), False)        # the variance of another convention
+    assert not V.check(biased["scale"], ref["scale"], gates["scale"], "eval, variance 519 / 520")[0]
 
 
 def test_missing_residual_fails_the_gate(sed):

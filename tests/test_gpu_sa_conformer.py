@@ -10,7 +10,8 @@ gradient 3e-3 relative L2.  Two things that bound does not define are set here b
     its relative error means nothing: both the oracle's and the model's must stay below 3e-3 of the L2 norm of the depthwise.weight
     gradient, which is formed from the same dz;
   - the running statistics after a step are means over R = 20 rows of an fp32 chain of a 32-term product and a k-term filter, a
-    relative error of the order of 50 u = 3e-6: held to 1e-4 relative L2 against the oracle's BatchNorm buffers."""
+    relative error of the order of 50 u = 3e-6: held to 1e-4 relative L2 against the oracle's BatchNorm buffers.
+tests/test_gpu_sa_at_size.py calls compare and oracle at its own geometry (C = 128, t = 130, R = 520), with the same bounds."""
 import importlib
 
 import numpy as np
@@ -71,14 +72,25 @@ class ConvModule(torch.nn.Module):
         return self.conv_norm(h + x.transpose(1, 2))
 
 
-def oracle(sed, sd, feat, y, heads, layers, ffn, k, ratio, training=True):
-    """feat (B, t, Wf, C) float64 with requires_grad -> (logits, loss, parameter gradients by state_dict name, BatchNorm buffers)"""
+def oracle(sed, sd, feat, y, heads, layers, ffn, k, ratio, training=True, pos=True, act="gelu", plain_attention=False):
+    """feat (B, t, Wf, C) float64 with requires_grad -> (logits, loss, parameter gradients by state_dict name, BatchNorm buffers).
+    pos: the positional table; act: the FFN's activation; plain_attention (no FFN): the attention half from torch.nn.MultiheadAttention
+    + LayerNorm as tests/test_gpu_sa_model.py's oracle_head builds it, not from a TransformerEncoderLayer with an unused FFN."""
     Cc = feat.shape[-1]
     cpu = lambda d: {n: (v.double() if v.is_floating_point() else v).cpu() for n, v in d.items()}
     enc, conv = [], []
     for l in range(layers):
-        e = torch.nn.TransformerEncoderLayer(Cc, heads, max(ffn, 1), dropout=0.0, activation="gelu", batch_first=True, norm_first=False).double()
-        e.load_state_dict(cpu(sed.Csa_AvgPooling.encoder_layer_state(sd, l)), strict=False)
+        if plain_attention:
+            assert not ffn
+            an, nn_ = F.layer_names(l)[:2]
+            e = torch.nn.Module()
+            e.self_attn, e.norm1 = torch.nn.MultiheadAttention(Cc, heads, batch_first=True), torch.nn.LayerNorm(Cc)
+            e.double()
+            for mod, name in ((e.self_attn, an), (e.norm1, nn_)):
+                mod.load_state_dict(cpu({n[len(name) + 1:]: v for n, v in sd.items() if n.startswith(name + ".")}))
+        else:
+            e = torch.nn.TransformerEncoderLayer(Cc, heads, max(ffn, 1), dropout=0.0, activation=act, batch_first=True, norm_first=False).double()
+            e.load_state_dict(cpu(sed.Csa_AvgPooling.encoder_layer_state(sd, l)), strict=False)
         c = ConvModule(Cc, k).double()
         c.load_state_dict(cpu(sed.Csa_AvgPooling.conv_module_state(sd, l)))
         enc.append(e.train(training))
@@ -86,12 +98,12 @@ def oracle(sed, sd, feat, y, heads, layers, ffn, k, ratio, training=True):
     fc = torch.nn.Linear(Cc, sd["event_fc.weight"].shape[0]).double()
     fc.load_state_dict({n[len("event_fc."):]: v.double().cpu() for n, v in sd.items() if n.startswith("event_fc.")})
     m = feat.mean(dim=2)
-    h = m + torch.from_numpy(M.positional_table(m.shape[1], Cc)).float().double()       # the table as rounded to fp32
+    h = m + torch.from_numpy(M.positional_table(m.shape[1], Cc)).float().double() if pos else m      # the table as rounded to fp32
     for e, c in zip(enc, conv):
         h = e.norm1(h + e.self_attn(h, h, h, need_weights=False)[0])
         h = c(h)
         if ffn:
-            h = e.norm2(h + e.linear2(TF.gelu(e.linear1(h))))
+            h = e.norm2(h + e.linear2(getattr(TF, act)(e.linear1(h))))
     out = fc(h).repeat_interleave(ratio, dim=1)
     N = min(out.shape[1], y.shape[1])
     loss = TF.binary_cross_entropy_with_logits(out[:, :N], y[:, :N], pos_weight=torch.tensor(W, dtype=torch.float64))
@@ -112,9 +124,10 @@ def oracle(sed, sd, feat, y, heads, layers, ffn, k, ratio, training=True):
     return out.detach(), loss.detach(), grads, bufs
 
 
-def compare(sed, model, x, y, layers, ffn, k, training, tag):
-    """one forward + backward of the model against the oracle fed by a head='none' engine; -> (the bare plan, feat, P)"""
-    K = y.shape[-1]
+def compare(sed, model, x, y, layers, ffn, k, training, tag, cfg=CFG, mel=MEL, heads=1, **oracle_kw):
+    """one forward + backward of the model against the oracle fed by a head='none' engine; -> (the bare engine, its plan, feat, P).
+    cfg, mel, heads, oracle_kw: another geometry than this module's (tests/test_gpu_sa_at_size.py)"""
+    K, C = y.shape[-1], cfg[-1][0]
     sd0 = {n: v.clone() for n, v in model.state_dict().items()}
     model.train(training)
     model.zero_grad()
@@ -124,12 +137,12 @@ def compare(sed, model, x, y, layers, ffn, k, training, tag):
     plan = the_plan(model)
     assert plan.sa is not None and len(plan.sa["layers"]) == layers and "cz" in plan.sa["layers"][0]
     P = model._tensor_dict()
-    bare = sed.CnnEngine(K, CFG, 1, "fp32", head="none", mel_bins=MEL)
+    bare = sed.CnnEngine(K, cfg, 1, "fp32", head="none", mel_bins=mel)
     P0 = {n: v.cuda() for n, v in sd0.items()}
     bp = bare.forward(x, P0, training=training, update_running_stats=False, keep_for_grad=not training)
     assert torch.equal(bp.y[-1], plan.y[-1])
     feat = bp.y[-1][..., :C].double().cpu().requires_grad_(True)
-    out_t, loss_t, grads, bufs = oracle(sed, sd0, feat, y.double().cpu(), 1, layers, ffn, k, model.engine.ratio, training)
+    out_t, loss_t, grads, bufs = oracle(sed, sd0, feat, y.double().cpu(), heads, layers, ffn, k, model.engine.ratio, training, **oracle_kw)
     err = float((out.detach().cpu().double() - out_t).abs().max())
     print(f"{tag}: logits max error {err:.3e}, loss error {abs(loss.item() - float(loss_t)):.3e}")
     assert err < 1e-3 and abs(loss.item() - float(loss_t)) < 1e-4
@@ -147,14 +160,14 @@ def compare(sed, model, x, y, layers, ffn, k, training, tag):
         assert l2 < 3e-3, (n, l2)
     sd1 = model.state_dict()
     for n, b in bufs.items():
+        nbt = n.replace("running_mean", "num_batches_tracked").replace("running_var", "num_batches_tracked")
         if training:
             l2 = rel_l2(sd1[n], b)
             print(f"  {n}: relative L2 {l2:.3e}")
             assert l2 < 1e-4, (n, l2)
-            assert int(sd1[n.replace("running_mean", "num_batches_tracked").replace("running_var", "num_batches_tracked")]) == \
-                int(sd0[n.replace("running_mean", "num_batches_tracked").replace("running_var", "num_batches_tracked")]) + 1
+            assert int(sd1[nbt]) == int(sd0[nbt]) + 1
         else:
-            assert torch.equal(sd1[n], sd0[n]), (n, "an eval forward changed a running statistic")
+            assert torch.equal(sd1[n], sd0[n]) and torch.equal(sd1[nbt], sd0[nbt]), (n, "an eval forward changed a running statistic")
     return bare, bp, feat, P0
 
 
