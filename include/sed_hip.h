@@ -1102,6 +1102,51 @@ int sed_ffn_fwd(int dtype, int act, const float* x, const float* w1, const float
                 float* y, float* u, size_t R, int C, int D, void* stream);
 int sed_ffn_act_bwd(int act, const float* u, const float* da, float* a, float* du, size_t n, void* stream);
 
+/* ---- dropout of the self-attention head (csrc/philox.h, sed_dropout.hip, the _drop twins in sed_mhsa.hip / sed_ffn.hip) ---------
+ * Masks are generated inside the fused kernels, forward and backward, from a counter-based generator (Philox4x32-10: multipliers
+ * 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds), never stored:
+ *   state  rng: four uint32 in DEVICE memory (seed_lo, seed_hi, step, 0); the kernels load it (a captured graph replays with the
+ *          step word its own add advanced)
+ *   key    (seed_lo, seed_hi ^ stream_id), stream_id = 8 * layer + site; sites: 0 attention probabilities, 1 attention output
+ *          before its residual add, 2 convolution module output before its residual add, 3 FFN hidden activation, 4 FFN output
+ *          before its residual add
+ *   rows   [R][N], element (r, c): counter (c >> 2, r mod 2^32, r >> 32, step), output word c & 3
+ *   attn   clip b, head g, query i, key j: counter (j >> 2, i, b*H + g, step), output word j & 3
+ *   keep   m = 1 iff word >= thr, thr = min(2^32 - 1, floor(p * 2^32 + 1/2)) in double from the float p; kept values are
+ *          multiplied in fp32 by s = (float)(1 / (1 - (double)p)).  p = 0: every cell kept, s = 1, the plain twin's bits.
+ * Each twin takes its plain entry's arguments plus (float p, const uint32_t* rng, uint32_t stream_id):
+ *   sed_mhsa_fwd_drop:  lse_i and p_ij as sed_mhsa_fwd (all keys, no renormalisation);  p~_ij = m_ij s p_ij,  ctx_ic = sum_j p~_ij v_jc
+ *     (running form: exp(s_ij - m_run) times m_ij s in fp32 for the P V operand only -- SED_BF16: the operand is bf16(p m s) -- the
+ *     normalising sum over the undropped fp32 probabilities)
+ *   sed_mhsa_bwd_drop:  dv_jc = sum_i p~_ij dctx_ic,  dp_ij = m_ij s sum_c dctx_ic v_jc,  ds_ij = p_ij (dp_ij - D_i),  D_i = sum_c dctx_ic
+ *     ctx_ic with the dropped ctx (launch 1 unchanged); dq, dk from ds as sed_mhsa_bwd
+ *   sed_add_layernorm_fwd_drop:  y = LayerNorm(x + m s a)
+ *   sed_add_layernorm_bwd_drop:  dres (the gradient of x) as sed_add_layernorm_bwd with xhat of the dropped sum, and the extra output
+ *     da [rows][C] = m s dres (the gradient of a); dgamma / dbeta use xhat of the dropped sum
+ *   sed_ffn_fwd_drop:  a = m s act(u) as the operand of the second product; u is stored undropped
+ *   sed_ffn_act_bwd_drop:  u, da, a, du are [R][D] (D a multiple of 4):  a = m s act(u),  du = da m s act'(u)
+ * sed_dropout_mask writes the 0 / 1 keep bytes themselves: kind SED_DROP_ROWS keep[n0][n1] (t ignored), kind SED_DROP_ATTN
+ * keep[n0 = B][n1 = H][t][t] -- exactly the cells the fused kernels drop.
+ * A twin called with thr = 0 (p = 0) launches its plain twin's kernels (sed_add_layernorm_bwd_drop then copies dres into da).
+ * Refused (non-zero, nothing launched, outputs untouched): whatever the plain twin refuses; p < 0, p >= 1, NaN; rng NULL; da NULL;
+ * sed_dropout_mask: an unknown kind, keep NULL, a size <= 0.                                                                      */
+enum { SED_DROP_ROWS = 0, SED_DROP_ATTN = 1 };
+int sed_mhsa_fwd_drop(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, float p,
+                      const uint32_t* rng, uint32_t stream_id, void* stream);
+int sed_mhsa_bwd_drop(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
+                      float* workspace, int B, int t, int H, int dh, float p, const uint32_t* rng, uint32_t stream_id, void* stream);
+int sed_add_layernorm_fwd_drop(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
+                               size_t rows, int C, float eps, float p, const uint32_t* rng, uint32_t stream_id, void* stream);
+int sed_add_layernorm_bwd_drop(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
+                               float* dres, float* da, float* dgamma, float* dbeta, float* workspace, size_t rows, int C, float p,
+                               const uint32_t* rng, uint32_t stream_id, void* stream);
+int sed_ffn_fwd_drop(int dtype, int act, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                     float* y, float* u, size_t R, int C, int D, float p, const uint32_t* rng, uint32_t stream_id, void* stream);
+int sed_ffn_act_bwd_drop(int act, const float* u, const float* da, float* a, float* du, size_t R, int D, float p,
+                         const uint32_t* rng, uint32_t stream_id, void* stream);
+int sed_dropout_mask(unsigned char* keep, int kind, size_t n0, int n1, int t, float p, const uint32_t* rng, uint32_t stream_id,
+                     void* stream);
+
 /* ---- Conformer convolution module of the self-attention head (csrc/sed_convmod.hip) ------------
  * Between the attention and the feed-forward sub-layer: pointwise Conv1d(C, 2C, 1) -> GLU -> depthwise Conv1d(C, C, k, padding
  * (k-1)/2, groups=C) -> BatchNorm1d(C) -> SiLU -> pointwise Conv1d(C, C, 1).  The pointwise convolutions are sed_gemm_nt launches, the

@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsed_hip.so")
 
 _P, _I, _Z, _F, _D = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_double
+_U32 = C.c_uint32
 
 
 
@@ -177,6 +178,14 @@ PROTOTYPES = {
     "sed_add_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _P]),
     "sed_ffn_fwd": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _P]),
     "sed_ffn_act_bwd": (_I, [_I, _P, _P, _P, _P, _Z, _P]),
+    # the dropout twins: the plain entry's arguments + (float p, const uint32_t* rng, uint32_t stream_id)
+    "sed_mhsa_fwd_drop": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _F, _P, _U32, _P]),
+    "sed_mhsa_bwd_drop": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _U32, _P]),
+    "sed_add_layernorm_fwd_drop": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _F, _F, _P, _U32, _P]),
+    "sed_add_layernorm_bwd_drop": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _F, _P, _U32, _P]),
+    "sed_ffn_fwd_drop": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _F, _P, _U32, _P]),
+    "sed_ffn_act_bwd_drop": (_I, [_I, _P, _P, _P, _P, _Z, _I, _F, _P, _U32, _P]),
+    "sed_dropout_mask": (_I, [_P, _I, _Z, _I, _I, _F, _P, _U32, _P]),
     "sed_dwconv_tile": (_I, []),
     "sed_dwconv_nparts": (_I, [_I, _I]),
     "sed_dwconv_glu_fwd_ws_floats": (_Z, [_I, _I, _I]),

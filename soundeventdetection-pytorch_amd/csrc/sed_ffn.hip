@@ -24,7 +24,13 @@
 // No atomics, every sum in a fixed order: the same bits on every run.
 //
 // Ragged last tile: loads of rows past R are clamped to row R - 1 (real data), their results are never stored.
+//
+// Dropout (the DROP instantiations behind sed_ffn_fwd_drop / sed_ffn_act_bwd_drop; mask m of element (row, hidden unit) and scale
+// s = 1 / (1 - p) from philox.h, generated in registers):  a = m s act(u) before it becomes the operand of the second product, u stored
+// undropped;  backward  a = m s act(u) (for dw2),  du = da m s act'(u).  A register group of the forward and a 16-byte access of the
+// backward are four consecutive hidden units of one row: one Philox call each.  thr = 0 (p = 0) launches the plain instantiation.
 #include "common.h"
+#include "philox.h"
 #include <math.h>
 
 #define FFN_ROWS 32           // rows a workgroup owns
@@ -110,6 +116,7 @@ struct FfnParams {
     float* u;
     size_t R;
     int C, D;
+    DropArgs drop;       // the DROP instantiations only
 };
 
 template <typename T> constexpr int ffn_pad() { return 16 / (int)sizeof(T); }       // 16 bytes: the 16-byte fragment reads of the 32 rows spread over the banks
@@ -118,7 +125,9 @@ template <typename T> static inline size_t ffn_lds_bytes(int C) {
 }
 
 // TPW: output tiles (32 columns each) per wave = ceil(C / 128)
-template <typename T, int ACT, int TPW>
+// DROP: a = m s act(u) with the mask of element (row, hidden unit) (philox.h: a register group is four consecutive hidden units of one
+// row, one call); u is stored undropped
+template <typename T, int ACT, int TPW, bool DROP>
 __global__ __launch_bounds__(64 * FFN_WAVES) void ffn_fwd_kernel(FfnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int AP = FFN_DSTEP + ffn_pad<T>();
@@ -136,6 +145,7 @@ __global__ __launch_bounds__(64 * FFN_WAVES) void ffn_fwd_kernel(FfnParams p) {
     }
     __syncthreads();
     const bool live = row0 + r < p.R;
+    const DropKey key = drop_key<DROP>(p.drop);
     f32x16 acc[TPW];
 #pragma unroll
     for (int tt = 0; tt < TPW; ++tt) acc[tt] = (f32x16){};
@@ -163,6 +173,11 @@ __global__ __launch_bounds__(64 * FFN_WAVES) void ffn_fwd_kernel(FfnParams p) {
                 for (int j = 0; j < 4; ++j) {
                     uv[j] = ut[4 * g + j] + p.b1[d0 + hl + j];
                     av[j] = act_fwd<ACT>(uv[j]);
+                }
+                if (DROP) {
+                    const PhiloxWords w = drop_row_words(key, row0 + r, (uint32_t)(d0 + hl) >> 2);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) av[j] *= drop_ms(w.w[j], p.drop);
                 }
                 if (p.u != nullptr && live) *reinterpret_cast<f32x4*>(p.u + (row0 + r) * D + d0 + hl) = uv;
                 put4(ab + r * AP + hl, av);
@@ -205,9 +220,12 @@ __global__ __launch_bounds__(64 * FFN_WAVES) void ffn_fwd_kernel(FfnParams p) {
 }
 
 // a = act(u), du = da * act'(u): every element read before it is written (a may be u, du may be da)
-template <int ACT, bool VEC>
-__global__ __launch_bounds__(256) void ffn_act_bwd_kernel(const float* u, const float* da, float* a, float* du, size_t n) {
+// DROP (the tensors are [R][D], D a multiple of 4, so n % 4 = 0 and four consecutive elements share a row and a call):
+// a = m s act(u), du = da m s act'(u)
+template <int ACT, bool VEC, bool DROP>
+__global__ __launch_bounds__(256) void ffn_act_bwd_kernel(const float* u, const float* da, float* a, float* du, size_t n, int D, DropArgs drop) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const DropKey key = drop_key<DROP>(drop);
     if (VEC) {
         const size_t n4 = n / 4;
         if (i < n4) {
@@ -215,6 +233,12 @@ __global__ __launch_bounds__(256) void ffn_act_bwd_kernel(const float* u, const 
             f32x4 av, gv;
 #pragma unroll
             for (int j = 0; j < 4; ++j) { av[j] = act_fwd<ACT>(uv[j]); gv[j] = dv[j] * act_grad<ACT>(uv[j]); }
+            if (DROP) {
+                const size_t e = 4 * i;
+                const PhiloxWords w = drop_row_words(key, e / (size_t)D, (uint32_t)(e % (size_t)D) >> 2);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { const float ms = drop_ms(w.w[j], drop); av[j] *= ms; gv[j] *= ms; }
+            }
             reinterpret_cast<f32x4*>(a)[i] = av;
             reinterpret_cast<f32x4*>(du)[i] = gv;
         } else if (i - n4 < n % 4) {                               // the tail, one element per thread
@@ -225,8 +249,14 @@ __global__ __launch_bounds__(256) void ffn_act_bwd_kernel(const float* u, const 
         }
     } else if (i < n) {
         const float uv = u[i], dv = da[i];
-        a[i] = act_fwd<ACT>(uv);
-        du[i] = dv * act_grad<ACT>(uv);
+        if (DROP) {
+            const float ms = drop_row_ms(key, drop, i / (size_t)D, (int)(i % (size_t)D));
+            a[i] = act_fwd<ACT>(uv) * ms;
+            du[i] = dv * act_grad<ACT>(uv) * ms;
+        } else {
+            a[i] = act_fwd<ACT>(uv);
+            du[i] = dv * act_grad<ACT>(uv);
+        }
     }
 }
 
@@ -241,28 +271,27 @@ inline bool any_overlap(const void* a, const void* b, size_t bytes) {
     return x < y + bytes && y < x + bytes;
 }
 
-template <typename T, int ACT, int TPW>
+template <typename T, int ACT, int TPW, bool DROP>
 int ffn_launch(const FfnParams& p, hipStream_t st) {
     const size_t lds = ffn_lds_bytes<T>(p.C);
     if (lds > 48 * 1024)
-        if (int rc = sed_set_max_lds<ffn_fwd_kernel<T, ACT, TPW>>(lds)) return rc;
-    ffn_fwd_kernel<T, ACT, TPW><<<(unsigned)cdivz(p.R, FFN_ROWS), 64 * FFN_WAVES, lds, st>>>(p);
+        if (int rc = sed_set_max_lds<ffn_fwd_kernel<T, ACT, TPW, DROP>>(lds)) return rc;
+    ffn_fwd_kernel<T, ACT, TPW, DROP><<<(unsigned)cdivz(p.R, FFN_ROWS), 64 * FFN_WAVES, lds, st>>>(p);
     return 0;
 }
-template <typename T, int ACT>
+template <typename T, int ACT, bool DROP>
 int ffn_launch_tpw(const FfnParams& p, hipStream_t st) {
     switch (cdiv(p.C / 32, FFN_WAVES)) {
-        case 1: return ffn_launch<T, ACT, 1>(p, st);
-        case 2: return ffn_launch<T, ACT, 2>(p, st);
-        case 3: return ffn_launch<T, ACT, 3>(p, st);
-        default: return ffn_launch<T, ACT, 4>(p, st);
+        case 1: return ffn_launch<T, ACT, 1, DROP>(p, st);
+        case 2: return ffn_launch<T, ACT, 2, DROP>(p, st);
+        case 3: return ffn_launch<T, ACT, 3, DROP>(p, st);
+        default: return ffn_launch<T, ACT, 4, DROP>(p, st);
     }
 }
 
-}  // namespace
-
-extern "C" int sed_ffn_fwd(int dtype, int act, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                           float* y, float* u, size_t R, int C, int D, void* stream) {
+template <bool DROP>
+int ffn_fwd_entry(int dtype, int act, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                  float* y, float* u, size_t R, int C, int D, const DropArgs& drop, void* stream) {
     SED_REQUIRE(dtype == SED_F32 || dtype == SED_BF16, "dtype must be SED_F32 or SED_BF16");
     SED_REQUIRE(act == SED_ACT_RELU || act == SED_ACT_GELU, "act must be SED_ACT_RELU or SED_ACT_GELU");
     SED_REQUIRE(R > 0 && cdivz(R, FFN_ROWS) < ((size_t)1 << 31), "R must be positive (and below 2^31 tiles of 32 rows)");
@@ -271,17 +300,20 @@ extern "C" int sed_ffn_fwd(int dtype, int act, const float* x, const float* w1, 
     SED_REQUIRE(x != nullptr && w1 != nullptr && b1 != nullptr && w2 != nullptr && b2 != nullptr && y != nullptr,
                 "x, w1, b1, w2, b2 and y are required");
     SED_REQUIRE(aligned16(x) && aligned16(w1) && aligned16(w2) && aligned16(y) && aligned16(u), "x, w1, w2, y and u must be 16-byte aligned");
-    FfnParams p = {x, w1, b1, w2, b2, y, u, R, C, D};
+    FfnParams p = {x, w1, b1, w2, b2, y, u, R, C, D, drop};
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if (dtype == SED_BF16) rc = act == SED_ACT_RELU ? ffn_launch_tpw<bf16_t, SED_ACT_RELU>(p, st) : ffn_launch_tpw<bf16_t, SED_ACT_GELU>(p, st);
-    else rc = act == SED_ACT_RELU ? ffn_launch_tpw<float, SED_ACT_RELU>(p, st) : ffn_launch_tpw<float, SED_ACT_GELU>(p, st);
+    if (dtype == SED_BF16)
+        rc = act == SED_ACT_RELU ? ffn_launch_tpw<bf16_t, SED_ACT_RELU, DROP>(p, st) : ffn_launch_tpw<bf16_t, SED_ACT_GELU, DROP>(p, st);
+    else
+        rc = act == SED_ACT_RELU ? ffn_launch_tpw<float, SED_ACT_RELU, DROP>(p, st) : ffn_launch_tpw<float, SED_ACT_GELU, DROP>(p, st);
     if (rc) return rc;
     SED_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int sed_ffn_act_bwd(int act, const float* u, const float* da, float* a, float* du, size_t n, void* stream) {
+template <bool DROP>
+int ffn_act_bwd_entry(int act, const float* u, const float* da, float* a, float* du, size_t n, int D, const DropArgs& drop, void* stream) {
     SED_REQUIRE(act == SED_ACT_RELU || act == SED_ACT_GELU, "act must be SED_ACT_RELU or SED_ACT_GELU");
     SED_REQUIRE(n > 0 && n < ((size_t)1 << 38), "n must be positive (and below 2^38)");
     SED_REQUIRE(u != nullptr && da != nullptr && a != nullptr && du != nullptr, "every pointer is required");
@@ -293,13 +325,47 @@ extern "C" int sed_ffn_act_bwd(int act, const float* u, const float* da, float* 
     const bool vec = aligned16(u) && aligned16(da) && aligned16(a) && aligned16(du) && n >= 4;
     if (vec) {
         const unsigned grid = (unsigned)cdivz(n / 4 + n % 4, 256);
-        if (act == SED_ACT_RELU) ffn_act_bwd_kernel<SED_ACT_RELU, true><<<grid, 256, 0, st>>>(u, da, a, du, n);
-        else ffn_act_bwd_kernel<SED_ACT_GELU, true><<<grid, 256, 0, st>>>(u, da, a, du, n);
+        if (act == SED_ACT_RELU) ffn_act_bwd_kernel<SED_ACT_RELU, true, DROP><<<grid, 256, 0, st>>>(u, da, a, du, n, D, drop);
+        else ffn_act_bwd_kernel<SED_ACT_GELU, true, DROP><<<grid, 256, 0, st>>>(u, da, a, du, n, D, drop);
     } else {
         const unsigned grid = (unsigned)cdivz(n, 256);
-        if (act == SED_ACT_RELU) ffn_act_bwd_kernel<SED_ACT_RELU, false><<<grid, 256, 0, st>>>(u, da, a, du, n);
-        else ffn_act_bwd_kernel<SED_ACT_GELU, false><<<grid, 256, 0, st>>>(u, da, a, du, n);
+        if (act == SED_ACT_RELU) ffn_act_bwd_kernel<SED_ACT_RELU, false, DROP><<<grid, 256, 0, st>>>(u, da, a, du, n, D, drop);
+        else ffn_act_bwd_kernel<SED_ACT_GELU, false, DROP><<<grid, 256, 0, st>>>(u, da, a, du, n, D, drop);
     }
     SED_LAUNCH_CHECK();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int sed_ffn_fwd(int dtype, int act, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                           float* y, float* u, size_t R, int C, int D, void* stream) {
+    return ffn_fwd_entry<false>(dtype, act, x, w1, b1, w2, b2, y, u, R, C, D, DropArgs{}, stream);
+}
+
+extern "C" int sed_ffn_act_bwd(int act, const float* u, const float* da, float* a, float* du, size_t n, void* stream) {
+    return ffn_act_bwd_entry<false>(act, u, da, a, du, n, 4, DropArgs{}, stream);
+}
+
+// the dropout twins (philox.h): the plain entry's checks, then p in [0, 1) and the state
+extern "C" int sed_ffn_fwd_drop(int dtype, int act, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                                float* y, float* u, size_t R, int C, int D, float p, const uint32_t* rng, uint32_t stream_id,
+                                void* stream) {
+    SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
+    DropArgs d;
+    SED_REQUIRE(drop_host_args(p, rng, stream_id, &d), "the dropout probability must lie in [0, 1)");
+    if (d.thr == 0) return ffn_fwd_entry<false>(dtype, act, x, w1, b1, w2, b2, y, u, R, C, D, d, stream);      // (no dropout: sed_mhsa.hip)
+    return ffn_fwd_entry<true>(dtype, act, x, w1, b1, w2, b2, y, u, R, C, D, d, stream);
+}
+
+// u, da, a, du are [R][D]; D a multiple of 4
+extern "C" int sed_ffn_act_bwd_drop(int act, const float* u, const float* da, float* a, float* du, size_t R, int D, float p,
+                                    const uint32_t* rng, uint32_t stream_id, void* stream) {
+    SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
+    DropArgs d;
+    SED_REQUIRE(drop_host_args(p, rng, stream_id, &d), "the dropout probability must lie in [0, 1)");
+    SED_REQUIRE(R > 0 && D > 0 && D % 4 == 0, "R and D must be positive, D a multiple of 4");
+    SED_REQUIRE(R < ((size_t)1 << 38) / (size_t)D, "R * D must stay below 2^38");
+    if (d.thr == 0) return ffn_act_bwd_entry<false>(act, u, da, a, du, R * (size_t)D, D, d, stream);
+    return ffn_act_bwd_entry<true>(act, u, da, a, du, R * (size_t)D, D, d, stream);
 }

@@ -43,7 +43,23 @@
 // g = dy * gamma, xhat = ((x + a) - mean) * rstd:  dres = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)), the gradient of both x and
 // a; dgamma = sum_rows dy * xhat and dbeta = sum_rows dy through per-workgroup partials (64 rows each) in the workspace and a
 // fixed-order reduction over the workgroups.
+//
+// Dropout (the DROP instantiations behind sed_mhsa_fwd_drop / sed_mhsa_bwd_drop / sed_add_layernorm_fwd_drop / _bwd_drop; masks m and
+// scale s = 1 / (1 - p) from philox.h, generated in registers in the forward and again in the backward, never stored):
+//   core       lse_i and p_ij as above, over all keys (no renormalisation);  p~_ij = m_ij s p_ij,  ctx_ic = sum_j p~_ij v_jc.  In the
+//              running form exp(s_ij - m_run) is multiplied by m_ij s in fp32 for the P V operand only (SED_BF16: the operand is
+//              bf16(p m s)); the normalising sum is still taken over the undropped fp32 probabilities.
+//              dv_jc = sum_i p~_ij dctx_ic,  dp_ij = m_ij s sum_c dctx_ic v_jc,  ds_ij = p_ij (dp_ij - D_i);  D_i = sum_c dctx_ic ctx_ic
+//              holds with the dropped ctx, so launch 1 is unchanged.
+//   LayerNorm  y = LayerNorm(x + m s a) (one fma per element);  dres (the gradient of x) as above with xhat of the dropped sum, and a
+//              second output da = m s dres (the gradient of a);  dgamma / dbeta with xhat of the dropped sum.
+// A lane of the forward and of the dQ pass holds four consecutive keys of one query in registers 4 n ... 4 n + 3: one Philox call per
+// four scores.  Where four consecutive keys / columns sit on the four lanes of a quad (the dK / dV pass, the LayerNorm kernels) the
+// quad shares the counter: every lane makes the call of another query / column step / row step and the words change places inside
+// the quad with DPP quad permutes.  The plain instantiations (DROP = false) are the code they were; a twin called with thr = 0
+// (p = 0) launches the plain instantiation.
 #include "common.h"
+#include "philox.h"
 #include <math.h>
 
 #define MHSA_QT 32            // queries (or keys) a wave owns
@@ -143,6 +159,7 @@ struct MhsaParams {
     float* D;            // workspace [B][H][t]
     int t, H, ntile;     // ntile = ceil(t / 128) workgroups per (clip, head)
     float scale;
+    DropArgs drop;       // the DROP instantiations only
 };
 
 // store the transposed 32 x 32 tile o (column c = acc_row(i, h) in the registers, row on the lane) times f into row `dst` (head columns)
@@ -156,7 +173,48 @@ __device__ __forceinline__ void store_tile_t(float* __restrict__ dst, const f32x
     }
 }
 
-template <typename T, int DH>
+// ---- dropout on the probabilities (philox.h): m_ij s per score of a 32 x 32 tile ------------------------------------------------------
+// query on the lane (the forward and the dQ pass): registers 4 n ... 4 n + 3 are four consecutive keys k0 + 8 n + 4 h + (0 ... 3) of
+// query i, so one call gives the four words of a register group
+__device__ __forceinline__ void drop_factors_t(float (&ms)[16], const DropArgs& d, int k0, int i, int bh, int h) {
+    const DropKey key(d);
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const PhiloxWords w = drop_attn_words(key, (uint32_t)(k0 >> 2) + 2 * n + h, (uint32_t)i, (uint32_t)bh);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ms[4 * n + j] = drop_ms(w.w[j], d);
+    }
+}
+__device__ __forceinline__ void drop_scores_t(f32x16& s, const DropArgs& d, int k0, int i, int bh, int h) {
+    float ms[16];
+    drop_factors_t(ms, d, k0, i, bh, h);
+#pragma unroll
+    for (int n = 0; n < 16; ++n) s[n] *= ms[n];
+}
+template <int J> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {      // lane J of the quad to its four lanes
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, J * 0x55, 0xF, 0xF, true);
+}
+template <int J> __device__ __forceinline__ uint32_t quad_word(const PhiloxWords& w, int word) {
+    const PhiloxWords b = {{quad_bcast<J>(w.w[0]), quad_bcast<J>(w.w[1]), quad_bcast<J>(w.w[2]), quad_bcast<J>(w.w[3])}};
+    return philox_pick(b, word);
+}
+// key on the lane (the dK / dV pass): registers 4 n ... 4 n + 3 are four consecutive queries q0 + 8 n + 4 h + (0 ... 3) of key j = k0 + r,
+// and the four lanes of a quad share j >> 2: lane L of the quad makes the call of query q0 + 8 n + 4 h + L, and lane j & 3 takes word
+// j & 3 of each of the quad's four calls (quad permutes; every lane of the wave is live here)
+__device__ __forceinline__ void drop_factors_k(float (&ms)[16], const DropArgs& d, int j, int q0, int bh, int h) {
+    const DropKey key(d);
+    const int L = j & 3;                               // (k0 is a multiple of 32: j & 3 is the lane's place in its quad)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const PhiloxWords w = drop_attn_words(key, (uint32_t)j >> 2, (uint32_t)(q0 + 8 * n + 4 * h + L), (uint32_t)bh);
+        ms[4 * n + 0] = drop_ms(quad_word<0>(w, L), d);
+        ms[4 * n + 1] = drop_ms(quad_word<1>(w, L), d);
+        ms[4 * n + 2] = drop_ms(quad_word<2>(w, L), d);
+        ms[4 * n + 3] = drop_ms(quad_word<3>(w, L), d);
+    }
+}
+
+template <typename T, int DH, bool DROP>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
@@ -206,6 +264,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
         sum += xor32(sum);
         l = l * alpha + sum;
         m = mn;
+        if (DROP) drop_scores_t(s, p.drop, k0, q0 + r, bh, h);
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) {
 #pragma unroll
@@ -227,7 +286,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
 // A fragments) and V transposed (Vt[c][key], pitch 36: a lane's eight keys of a k-step are two 8-byte reads) into one of two LDS
 // buffers, one barrier per tile.  Same values, same MFMA order and so the same bits as the register-fed kernel above, which the fp32
 // mode keeps; waves whose 32 queries lie past the clip take part in the staging and the barriers only.
-template <int DH>
+template <int DH, bool DROP>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParams p) {
     constexpr int KP = DH + 8, VP = 36, NL = DH / 32, RQ = DH / 4;       // NL 16-byte loads of K and of V per thread and tile
     __shared__ __attribute__((aligned(16))) bf16_t ks[2][32 * KP];
@@ -295,6 +354,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParam
             sum += xor32(sum);
             l = l * alpha + sum;
             m = mn;
+            if (DROP) drop_scores_t(s, p.drop, k0, q0 + r, bh, h);
 #pragma unroll
             for (int cb = 0; cb < NL; ++cb) {
 #pragma unroll
@@ -344,7 +404,7 @@ __global__ __launch_bounds__(256) void mhsa_rowdot_kernel(MhsaParams p, int B, i
 }
 
 // pass 2 of the backward: the wave owns 32 keys (on the lane) and loops over the query tiles -> dK, dV
-template <typename T, int DH>
+template <typename T, int DH, bool DROP>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
@@ -391,11 +451,22 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
         if (q0 + 32 < t) load_rows(q0 + 32);
         f32x16 s = mm_rows<T, DH>(qf, kf);             // s[query][key]
         f32x16 dp = mm_rows<T, DH>(df, vf);
+        if (DROP) {
+            float ms[16];
+            drop_factors_k(ms, p.drop, k0 + r, q0, bh, h);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float pr = q0 + acc_row(i, h) < t ? expf(s[i] * p.scale - lc[i]) : 0.f;
-            s[i] = pr;
-            dp[i] = pr * (dp[i] - Dc[i]);
+            for (int i = 0; i < 16; ++i) {
+                const float pr = q0 + acc_row(i, h) < t ? expf(s[i] * p.scale - lc[i]) : 0.f;
+                s[i] = pr * ms[i];                       // p~ for dV
+                dp[i] = pr * (dp[i] * ms[i] - Dc[i]);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float pr = q0 + acc_row(i, h) < t ? expf(s[i] * p.scale - lc[i]) : 0.f;
+                s[i] = pr;
+                dp[i] = pr * (dp[i] - Dc[i]);
+            }
         }
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) {
@@ -414,7 +485,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
 }
 
 // pass 3: the wave owns 32 queries (on the lane) and loops over the key tiles -> dQ
-template <typename T, int DH>
+template <typename T, int DH, bool DROP>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
@@ -447,6 +518,12 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
         if (k0 + 32 < t) load_rows(k0 + 32);
         f32x16 s = mm_rows<T, DH>(kf, qf);             // s[key][query]
         f32x16 dp = mm_rows<T, DH>(vf, df);
+        if (DROP) {
+            float ms[16];
+            drop_factors_t(ms, p.drop, k0, q0 + r, bh, h);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) dp[i] *= ms[i];
+        }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const float pr = k0 + acc_row(i, h) < t ? expf(s[i] * p.scale - lse) : 0.f;
@@ -463,14 +540,63 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
 }
 
 // ---- LayerNorm ---------------------------------------------------------------------------------------------------------------
+// m s of a lane's columns lane + 64 k of one row, k < LN_MSK, made once per row and kept in registers over the passes: the four lanes
+// of a quad own four consecutive columns, which share their counter, so lane L of the quad makes the call of step k0 + L and the words
+// change places inside the quad (quad_word): one call per lane and four steps = 256 columns.  Columns from 64 LN_MSK on take a call each.
+#define LN_MSK 8
+struct LnMask {
+    float ms[LN_MSK];
+    __device__ __forceinline__ LnMask(const DropKey& key, const DropArgs& d, size_t row, int C, int lane) {
+        const int L = lane & 3;
+#pragma unroll
+        for (int k0 = 0; k0 < LN_MSK; k0 += 4) {
+            if (64 * k0 < C) {                         // (uniform: every lane of the wave takes part in the permutes)
+                const PhiloxWords w = drop_row_words(key, row, (uint32_t)((lane >> 2) + 16 * (k0 + L)));
+                ms[k0 + 0] = drop_ms(quad_word<0>(w, L), d);
+                ms[k0 + 1] = drop_ms(quad_word<1>(w, L), d);
+                ms[k0 + 2] = drop_ms(quad_word<2>(w, L), d);
+                ms[k0 + 3] = drop_ms(quad_word<3>(w, L), d);
+            } else {
+                ms[k0 + 0] = ms[k0 + 1] = ms[k0 + 2] = ms[k0 + 3] = 0.f;
+            }
+        }
+    }
+    // f(c, m s) for this lane's columns in ascending order
+    template <typename Fn>
+    __device__ __forceinline__ void each(const DropKey& key, const DropArgs& d, size_t row, int C, int lane, Fn f) const {
+#pragma unroll
+        for (int k = 0; k < LN_MSK; ++k) {
+            const int c = lane + 64 * k;
+            if (c < C) f(c, ms[k]);
+        }
+        for (int c = lane + 64 * LN_MSK; c < C; c += 64) f(c, drop_row_ms(key, d, row, c));
+    }
+};
+
+template <bool DROP>
 __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float* __restrict__ y, float* __restrict__ stats, size_t rows, int C, float eps) {
+                                                         float* __restrict__ y, float* __restrict__ stats, size_t rows, int C, float eps,
+                                                         DropArgs drop) {
     const int lane = threadIdx.x & 63;
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* __restrict__ xr = x + row * C;
     const float* __restrict__ ar = a + row * C;
+    if (DROP) {                                        // the same sums in the same order over x + m s a (one fma per element)
+        const DropKey key(drop);
+        const LnMask mk(key, drop, row, C, lane);
+        float s = 0.f;
+        mk.each(key, drop, row, C, lane, [&](int c, float ms) { s += fmaf(ar[c], ms, xr[c]); });
+        const float mean = wave_sum(s) / (float)C;
+        float ss = 0.f;
+        mk.each(key, drop, row, C, lane, [&](int c, float ms) { const float d = fmaf(ar[c], ms, xr[c]) - mean; ss = fmaf(d, d, ss); });
+        const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)C + eps);
+        mk.each(key, drop, row, C, lane,
+                [&](int c, float ms) { y[row * C + c] = (fmaf(ar[c], ms, xr[c]) - mean) * rstd * gamma[c] + beta[c]; });
+        if (stats != nullptr && lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
+        return;
+    }
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += xr[c] + ar[c];
     const float mean = wave_sum(s) / (float)C;
@@ -481,9 +607,12 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const float* __restrict
     if (stats != nullptr && lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
 }
 
+// DROP: xhat of x + m s a, and the second output da = m s dres (the gradient of a; dres stays the gradient of x)
+template <bool DROP>
 __global__ __launch_bounds__(256) void add_ln_bwd_dres_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                               const float* __restrict__ a, const float* __restrict__ gamma,
-                                                              const float* __restrict__ stats, float* __restrict__ dres, size_t rows, int C) {
+                                                              const float* __restrict__ stats, float* __restrict__ dres,
+                                                              float* __restrict__ da, size_t rows, int C, DropArgs drop) {
     const int lane = threadIdx.x & 63;
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -491,6 +620,24 @@ __global__ __launch_bounds__(256) void add_ln_bwd_dres_kernel(const float* __res
     const float* __restrict__ ar = a + row * C;
     const float* __restrict__ gr = dy + row * C;
     const float mean = stats[2 * row], rstd = stats[2 * row + 1];
+    if (DROP) {
+        const DropKey key(drop);
+        const LnMask mk(key, drop, row, C, lane);
+        float s1 = 0.f, s2 = 0.f;
+        mk.each(key, drop, row, C, lane, [&](int c, float ms) {
+            const float g = gr[c] * gamma[c], xh = (fmaf(ar[c], ms, xr[c]) - mean) * rstd;
+            s1 += g;
+            s2 = fmaf(g, xh, s2);
+        });
+        const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+        mk.each(key, drop, row, C, lane, [&](int c, float ms) {
+            const float g = gr[c] * gamma[c], xh = (fmaf(ar[c], ms, xr[c]) - mean) * rstd;
+            const float d = rstd * ((g - m1) - xh * m2);
+            dres[row * C + c] = d;
+            da[row * C + c] = d * ms;
+        });
+        return;
+    }
     float s1 = 0.f, s2 = 0.f;
     for (int c = lane; c < C; c += 64) {
         const float g = gr[c] * gamma[c], xh = ((xr[c] + ar[c]) - mean) * rstd;
@@ -506,16 +653,37 @@ __global__ __launch_bounds__(256) void add_ln_bwd_dres_kernel(const float* __res
 
 // partial[chunk][0][c] = sum over the chunk's rows of dy * xhat, partial[chunk][1][c] = sum of dy: 64 columns x 4 row lanes per
 // workgroup, each row lane its rows (stride 4) in ascending order, then the four in a fixed order
+template <bool DROP>
 __global__ __launch_bounds__(256) void add_ln_bwd_part_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                               const float* __restrict__ a, const float* __restrict__ stats,
-                                                              float* __restrict__ partial, size_t rows, int C) {
+                                                              float* __restrict__ partial, size_t rows, int C, DropArgs drop) {
     __shared__ float sh[2][4][64];
     const int cl = threadIdx.x & 63, ry = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cl;
     const size_t r0 = (size_t)blockIdx.y * LN_ROWS_PER_WG;
     const size_t r1 = r0 + LN_ROWS_PER_WG < rows ? r0 + LN_ROWS_PER_WG : rows;
     float sg = 0.f, sb = 0.f;
-    if (c < C)
+    if (DROP) {
+        // a quad's four columns share the counter of a row: lane L of the quad makes the call of row step it0 + L and the words change
+        // places inside the quad; every thread takes part in the permutes, whatever its column and rows
+        const DropKey key(drop);
+        const int L = cl & 3;
+        for (int it0 = 0; it0 < LN_ROWS_PER_WG / 4; it0 += 4) {
+            const PhiloxWords w = drop_row_words(key, r0 + ry + 4 * (size_t)(it0 + L), (uint32_t)c >> 2);
+            const float ms4[4] = {drop_ms(quad_word<0>(w, L), drop), drop_ms(quad_word<1>(w, L), drop), drop_ms(quad_word<2>(w, L), drop),
+                                  drop_ms(quad_word<3>(w, L), drop)};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const size_t row = r0 + ry + 4 * (size_t)(it0 + j);
+                if (c < C && row < r1) {
+                    const float g = dy[row * C + c];
+                    const float xh = (fmaf(a[row * C + c], ms4[j], x[row * C + c]) - stats[2 * row]) * stats[2 * row + 1];
+                    sg = fmaf(g, xh, sg);
+                    sb += g;
+                }
+            }
+        }
+    } else if (c < C)
         for (size_t row = r0 + ry; row < r1; row += 4) {
             const float g = dy[row * C + c];
             const float xh = ((x[row * C + c] + a[row * C + c]) - stats[2 * row]) * stats[2 * row + 1];
@@ -559,24 +727,47 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-extern "C" int sed_mhsa_fwd(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, void* stream) {
+namespace {
+template <bool DROP>
+int mhsa_fwd_launch(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, const DropArgs& drop, void* stream) {
     long long nb; int ntile;
     if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
     SED_REQUIRE(qkv != nullptr && ctx != nullptr, "qkv and ctx are required");
     SED_REQUIRE(aligned16(qkv) && aligned16(ctx), "qkv and ctx must be 16-byte aligned");
     MhsaParams p = {};
     p.qkv = qkv; p.out = ctx; p.lse_out = lse; p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
+    p.drop = drop;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
     if (dtype == SED_BF16) {
-        if (dh == 32) mhsa_fwd_lds_kernel<32><<<grid, block, 0, st>>>(p);
-        else mhsa_fwd_lds_kernel<64><<<grid, block, 0, st>>>(p);
+        if (dh == 32) mhsa_fwd_lds_kernel<32, DROP><<<grid, block, 0, st>>>(p);
+        else mhsa_fwd_lds_kernel<64, DROP><<<grid, block, 0, st>>>(p);
     } else {
-        if (dh == 32) mhsa_fwd_kernel<float, 32><<<grid, block, 0, st>>>(p);
-        else mhsa_fwd_kernel<float, 64><<<grid, block, 0, st>>>(p);
+        if (dh == 32) mhsa_fwd_kernel<float, 32, DROP><<<grid, block, 0, st>>>(p);
+        else mhsa_fwd_kernel<float, 64, DROP><<<grid, block, 0, st>>>(p);
     }
     SED_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace
+
+extern "C" int sed_mhsa_fwd(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, void* stream) {
+    return mhsa_fwd_launch<false>(dtype, qkv, ctx, lse, B, t, H, dh, DropArgs{}, stream);
+}
+
+// the dropout twins: the plain entry's checks, then p in [0, 1) and the state.  thr = 0 (p below 2^-33: every cell kept, s = 1 exactly)
+// is no dropout by definition and takes the plain instantiation, so p = 0 gives the plain entry's bits whatever the compiler
+// contracts where
+#define SED_DROP_ARGS(p, rng, stream_id, out)                                                                     \
+    SED_REQUIRE((rng) != nullptr, "the dropout state rng is required");                                           \
+    SED_REQUIRE(drop_host_args((p), (rng), (stream_id), &(out)), "the dropout probability must lie in [0, 1)")
+
+extern "C" int sed_mhsa_fwd_drop(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, float p,
+                                 const uint32_t* rng, uint32_t stream_id, void* stream) {
+    DropArgs d;
+    SED_DROP_ARGS(p, rng, stream_id, d);
+    if (d.thr == 0) return mhsa_fwd_launch<false>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream);
+    return mhsa_fwd_launch<true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream);
 }
 
 extern "C" size_t sed_mhsa_bwd_ws_floats(int B, int t, int H, int dh) {
@@ -585,8 +776,10 @@ extern "C" size_t sed_mhsa_bwd_ws_floats(int B, int t, int H, int dh) {
     return (size_t)B * t * H;
 }
 
-extern "C" int sed_mhsa_bwd(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
-                            float* workspace, int B, int t, int H, int dh, void* stream) {
+namespace {
+template <bool DROP>
+int mhsa_bwd_launch(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
+                    float* workspace, int B, int t, int H, int dh, const DropArgs& drop, void* stream) {
     long long nb; int ntile;
     if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
     SED_REQUIRE(qkv != nullptr && ctx != nullptr && dctx != nullptr && lse != nullptr && dqkv != nullptr && workspace != nullptr,
@@ -595,29 +788,61 @@ extern "C" int sed_mhsa_bwd(int dtype, const float* qkv, const float* ctx, const
     MhsaParams p = {};
     p.qkv = qkv; p.ctx = ctx; p.dctx = dctx; p.lse = lse; p.out = dqkv; p.D = workspace;
     p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
+    p.drop = drop;
     hipStream_t st = (hipStream_t)stream;
     mhsa_rowdot_kernel<<<(unsigned)cdivz((size_t)B * t * H, 256), 256, 0, st>>>(p, B, dh);
     SED_LAUNCH_CHECK();
     const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
     if (dtype == SED_BF16) {
-        if (dh == 32) { mhsa_bwd_kv_kernel<bf16_t, 32><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 32><<<grid, block, 0, st>>>(p); }
-        else { mhsa_bwd_kv_kernel<bf16_t, 64><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 64><<<grid, block, 0, st>>>(p); }
+        if (dh == 32) { mhsa_bwd_kv_kernel<bf16_t, 32, DROP><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 32, DROP><<<grid, block, 0, st>>>(p); }
+        else { mhsa_bwd_kv_kernel<bf16_t, 64, DROP><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 64, DROP><<<grid, block, 0, st>>>(p); }
     } else {
-        if (dh == 32) { mhsa_bwd_kv_kernel<float, 32><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 32><<<grid, block, 0, st>>>(p); }
-        else { mhsa_bwd_kv_kernel<float, 64><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 64><<<grid, block, 0, st>>>(p); }
+        if (dh == 32) { mhsa_bwd_kv_kernel<float, 32, DROP><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 32, DROP><<<grid, block, 0, st>>>(p); }
+        else { mhsa_bwd_kv_kernel<float, 64, DROP><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 64, DROP><<<grid, block, 0, st>>>(p); }
     }
     SED_LAUNCH_CHECK();
     return 0;
 }
+}  // namespace
 
-extern "C" int sed_add_layernorm_fwd(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
-                                     size_t rows, int C, float eps, void* stream) {
+extern "C" int sed_mhsa_bwd(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
+                            float* workspace, int B, int t, int H, int dh, void* stream) {
+    return mhsa_bwd_launch<false>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, DropArgs{}, stream);
+}
+
+extern "C" int sed_mhsa_bwd_drop(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
+                                 float* workspace, int B, int t, int H, int dh, float p, const uint32_t* rng, uint32_t stream_id,
+                                 void* stream) {
+    DropArgs d;
+    SED_DROP_ARGS(p, rng, stream_id, d);
+    if (d.thr == 0) return mhsa_bwd_launch<false>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
+    return mhsa_bwd_launch<true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
+}
+
+namespace {
+template <bool DROP>
+int add_ln_fwd_launch(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
+                      size_t rows, int C, float eps, const DropArgs& drop, void* stream) {
     SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
     SED_REQUIRE(x != nullptr && a != nullptr && gamma != nullptr && beta != nullptr && y != nullptr, "x, a, gamma, beta and y are required");
     SED_REQUIRE(cdivz(rows, 4) < ((size_t)1 << 31), "too many rows");
-    add_ln_fwd_kernel<<<(unsigned)cdivz(rows, 4), 256, 0, (hipStream_t)stream>>>(x, a, gamma, beta, y, stats, rows, C, eps);
+    add_ln_fwd_kernel<DROP><<<(unsigned)cdivz(rows, 4), 256, 0, (hipStream_t)stream>>>(x, a, gamma, beta, y, stats, rows, C, eps, drop);
     SED_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace
+
+extern "C" int sed_add_layernorm_fwd(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
+                                     size_t rows, int C, float eps, void* stream) {
+    return add_ln_fwd_launch<false>(x, a, gamma, beta, y, stats, rows, C, eps, DropArgs{}, stream);
+}
+
+extern "C" int sed_add_layernorm_fwd_drop(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
+                                          size_t rows, int C, float eps, float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
+    DropArgs d;
+    SED_DROP_ARGS(p, rng, stream_id, d);
+    if (d.thr == 0) return add_ln_fwd_launch<false>(x, a, gamma, beta, y, stats, rows, C, eps, d, stream);
+    return add_ln_fwd_launch<true>(x, a, gamma, beta, y, stats, rows, C, eps, d, stream);
 }
 
 extern "C" size_t sed_add_layernorm_bwd_ws_floats(size_t rows, int C) {
@@ -625,19 +850,44 @@ extern "C" size_t sed_add_layernorm_bwd_ws_floats(size_t rows, int C) {
     return cdivz(rows, LN_ROWS_PER_WG) * 2 * (size_t)C;
 }
 
-extern "C" int sed_add_layernorm_bwd(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
-                                     float* dres, float* dgamma, float* dbeta, float* workspace, size_t rows, int C, void* stream) {
+namespace {
+template <bool DROP>
+int add_ln_bwd_launch(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
+                      float* dres, float* da, float* dgamma, float* dbeta, float* workspace, size_t rows, int C, const DropArgs& drop,
+                      void* stream) {
     SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
     SED_REQUIRE(dy != nullptr && x != nullptr && a != nullptr && gamma != nullptr && stats != nullptr && dres != nullptr &&
                 dgamma != nullptr && dbeta != nullptr && workspace != nullptr, "every pointer is required");
+    SED_REQUIRE(!DROP || da != nullptr, "da is required");
     const size_t nchunks = cdivz(rows, LN_ROWS_PER_WG);
     SED_REQUIRE(nchunks <= 65535, "too many rows (the partial grid takes 65535 * 64)");
     hipStream_t st = (hipStream_t)stream;
-    add_ln_bwd_dres_kernel<<<(unsigned)cdivz(rows, 4), 256, 0, st>>>(dy, x, a, gamma, stats, dres, rows, C);
+    add_ln_bwd_dres_kernel<DROP><<<(unsigned)cdivz(rows, 4), 256, 0, st>>>(dy, x, a, gamma, stats, dres, da, rows, C, drop);
     SED_LAUNCH_CHECK();
-    add_ln_bwd_part_kernel<<<dim3((unsigned)cdiv(C, 64), (unsigned)nchunks), 256, 0, st>>>(dy, x, a, stats, workspace, rows, C);
+    add_ln_bwd_part_kernel<DROP><<<dim3((unsigned)cdiv(C, 64), (unsigned)nchunks), 256, 0, st>>>(dy, x, a, stats, workspace, rows, C, drop);
     SED_LAUNCH_CHECK();
     add_ln_bwd_reduce_kernel<<<(unsigned)cdiv(C, 256), 256, 0, st>>>(workspace, dgamma, dbeta, (int)nchunks, C);
     SED_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace
+
+extern "C" int sed_add_layernorm_bwd(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
+                                     float* dres, float* dgamma, float* dbeta, float* workspace, size_t rows, int C, void* stream) {
+    return add_ln_bwd_launch<false>(dy, x, a, gamma, stats, dres, nullptr, dgamma, dbeta, workspace, rows, C, DropArgs{}, stream);
+}
+
+extern "C" int sed_add_layernorm_bwd_drop(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
+                                          float* dres, float* da, float* dgamma, float* dbeta, float* workspace, size_t rows, int C,
+                                          float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
+    DropArgs d;
+    SED_DROP_ARGS(p, rng, stream_id, d);
+    SED_REQUIRE(da != nullptr, "da is required");
+    if (d.thr == 0) {                                  // da = dres
+        if (int rc = add_ln_bwd_launch<false>(dy, x, a, gamma, stats, dres, da, dgamma, dbeta, workspace, rows, C, d, stream)) return rc;
+        const hipError_t e = hipMemcpyAsync(da, dres, rows * (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        SED_REQUIRE(e == hipSuccess, "the copy of dres into da failed");
+        return 0;
+    }
+    return add_ln_bwd_launch<true>(dy, x, a, gamma, stats, dres, da, dgamma, dbeta, workspace, rows, C, d, stream);
 }

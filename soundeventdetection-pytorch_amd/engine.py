@@ -228,7 +228,8 @@ class CnnEngine(OptimizerExtMixin):
     def __init__(self, classes_num: int, model_config: Sequence[Tuple[int, int]], in_channels: int = 1,
                  precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
                  mel_bins: Optional[int] = None, attention: bool = False, sa_heads: int = 4, pos_encoding: bool = True,
-                 sa_layers: int = 1, sa_ffn: int = 0, sa_activation: str = "relu", sa_conv_kernel: int = 0):
+                 sa_layers: int = 1, sa_ffn: int = 0, sa_activation: str = "relu", sa_conv_kernel: int = 0,
+                 sa_dropout: float = 0.0, sa_dropout_seed: Optional[int] = None):
         """attention: a second linear layer att_fc beside event_fc scores every frame per class (csrc/sed_attn.hip): forward()
         also leaves the attention logits in plan.att, loss_and_grad(weak=("att", ...)) pools with them and backward() then takes
         both layers.  False launches exactly what it always did.
@@ -238,6 +239,10 @@ class CnnEngine(OptimizerExtMixin):
         csrc/sed_ffn.hip -- torch.nn.TransformerEncoderLayer(C, sa_heads, sa_ffn, dropout=0, norm_first=False) semantics; sa_conv_kernel
         = k > 0, odd in [3, 31], puts the Conformer convolution module -- pointwise conv, GLU, depthwise conv of k taps along time,
         BatchNorm, SiLU, pointwise conv, residual LayerNorm -- between the two, csrc/sed_convmod.hip)
+        sa_dropout = p in [0, 1): torch.nn.TransformerEncoderLayer(dropout=p)'s placement in TRAINING forwards and their backwards --
+        the attention probabilities, each sub-layer's output before its residual add, the FFN hidden activation -- with masks generated
+        inside the kernels from the counter-based state drop_state = (seed_lo, seed_hi, step, 0) (csrc/philox.h); sa_dropout_seed:
+        the 64-bit seed, None -> torch.initial_seed() (no random number is drawn).  p = 0 launches what it always did.
         or 'none' (a bare stack of ConvBlocks: forward() stops at the last pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
         Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and backward() also produces the input gradient
         plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path keeps the dedicated Cin = 1
@@ -256,6 +261,13 @@ class CnnEngine(OptimizerExtMixin):
         self.sa_conv_kernel = int(sa_conv_kernel)
         if head != "sa" and self.sa_conv_kernel:
             raise ValueError("sa_conv_kernel belongs to the self-attention head (head='sa')")
+        self.sa_dropout = self.check_sa_dropout(sa_dropout)
+        if head != "sa" and (self.sa_dropout or sa_dropout_seed is not None):
+            raise ValueError("sa_dropout / sa_dropout_seed belong to the self-attention head (head='sa')")
+        self.sa_dropout_seed = (torch.initial_seed() if sa_dropout_seed is None else int(sa_dropout_seed)) & 0xFFFFFFFFFFFFFFFF
+        self._drop_state = None              # (4,) int32 on the device holding the uint32 words, made with the first plan (on its device)
+        self._drop_dev = "cuda"
+        self._drop_host = [self.sa_dropout_seed & 0xFFFFFFFF, self.sa_dropout_seed >> 32, 0, 0]
         if head == "sa":
             if self.sa_conv_kernel and (self.sa_conv_kernel < 3 or self.sa_conv_kernel > 31 or self.sa_conv_kernel % 2 == 0):
                 raise ValueError(f"sa_conv_kernel must be 0 (no convolution module) or an odd integer in [3, 31], got {sa_conv_kernel!r}")
@@ -304,6 +316,37 @@ class CnnEngine(OptimizerExtMixin):
         # sums are reduced to one row per rank, summed over the ranks, and finalized with count * world.
         self.bn_sync = None
         self._e_shift = 0                    # f16x3 pre-scale shift of the running backward (_grad_dtype; 0 outside the new backward kinds)
+
+    @staticmethod
+    def check_sa_dropout(p) -> float:
+        """a probability in [0, 1) (NaN refused)"""
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) < 1.0:
+            raise ValueError(f"sa_dropout must be a probability in [0, 1), got {p!r}")
+        return float(p)
+
+    # ---- the dropout state: (seed_lo, seed_hi, step, 0), uint32 words in an int32 device tensor ---------------------------------
+    @property
+    def drop_state(self) -> torch.Tensor:
+        """The (4,) device tensor the NEXT training forward's masks come from (that forward ends by adding 1 to the step word)."""
+        if self._drop_state is None:
+            words = [w - (1 << 32) if w >= (1 << 31) else w for w in self._drop_host]
+            self._drop_state = torch.tensor(words, dtype=torch.int32, device=self._drop_dev)
+        return self._drop_state
+
+    def drop_state_words(self):
+        """the four uint32 words as Python ints (synchronises)"""
+        if self._drop_state is None:
+            return list(self._drop_host)
+        return [int(v) & 0xFFFFFFFF for v in self._drop_state.cpu().tolist()]
+
+    def set_drop_state(self, words) -> None:
+        """overwrite the state in place (a captured graph keeps reading the same tensor)"""
+        words = [int(w) & 0xFFFFFFFF for w in words]
+        if len(words) != 4:
+            raise ValueError("the dropout state is four uint32 words (seed_lo, seed_hi, step, 0)")
+        self._drop_host = words
+        if self._drop_state is not None:
+            self._drop_state.copy_(torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=torch.int32))
 
     @staticmethod
     def check_mel_bins(mel_bins):
@@ -703,6 +746,14 @@ class CnnEngine(OptimizerExtMixin):
             g["cds"], g["cdg"], g["dhc"] = torch.empty((R, C), **f32), torch.empty((R, 2 * C), **f32), torch.empty((R, C), **f32)
             g["cw_ws"] = torch.empty(max(1, lib.sed_dwconv_glu_bwd_ws_floats(B, t, C, kc)), **f32)
             g["cw2T"], g["cw1T"] = torch.empty((C, C), **f32), torch.empty((2 * C, C), **f32)
+        if self.sa_dropout:
+            if self._drop_state is None:
+                self._drop_dev = dev
+            _ = self.drop_state                      # made here, never inside a captured step
+            # the gradient of a sub-layer's output a (da = m s dres) and the state the plan's last training forward drew its masks from
+            # (what its backward regenerates them from)
+            g["da"] = torch.empty((R, C), **f32)
+            g["rng"] = torch.zeros(4, dtype=torch.int32, device=dev)
         g["pe"] = None
         if self.pos_encoding:
             # the standard table, built on the host in float64 and rounded once to fp32: pe[i][2j] = sin(i / 10000^(2j/C)), pe[i][2j+1] = cos(.)
@@ -724,6 +775,29 @@ class CnnEngine(OptimizerExtMixin):
 
     def _sa_layer_out(self, ly):
         return ly["h2"] if self.sa_ffn else ly["hc"] if self.sa_conv_kernel else ly["h"]
+
+    def _add_ln_fwd(self, g, x, a, gamma, beta, y, stats, R, C, sid):
+        """y = LayerNorm(x + a); sid: the dropout stream of a, None = no dropout (the plain launch)"""
+        lib, st = self.lib, _stream()
+        if sid is None:
+            self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(x), L.ptr(a), L.ptr(gamma), L.ptr(beta), L.ptr(y),
+                    L.ptr(stats), R, C, LN_EPS, st)
+        else:
+            self._k("sed_add_layernorm_fwd_drop", lib.sed_add_layernorm_fwd_drop, L.ptr(x), L.ptr(a), L.ptr(gamma), L.ptr(beta), L.ptr(y),
+                    L.ptr(stats), R, C, LN_EPS, self.sa_dropout, L.ptr(g["rng"]), sid, st)
+
+    def _add_ln_bwd(self, g, dy, x, a, gamma, stats, dgamma, dbeta, R, C, sid):
+        """the residual LayerNorm's backward: g["dres"] = the gradient of x; returns the gradient of a (g["dres"], or g["da"] = m s dres
+        under dropout stream sid)"""
+        lib, st = self.lib, _stream()
+        if sid is None:
+            self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(dy), L.ptr(x), L.ptr(a), L.ptr(gamma), L.ptr(stats),
+                    L.ptr(g["dres"]), L.ptr(dgamma), L.ptr(dbeta), L.ptr(g["ln_ws"]), R, C, st)
+            return g["dres"]
+        self._k("sed_add_layernorm_bwd_drop", lib.sed_add_layernorm_bwd_drop, L.ptr(dy), L.ptr(x), L.ptr(a), L.ptr(gamma), L.ptr(stats),
+                L.ptr(g["dres"]), L.ptr(g["da"]), L.ptr(dgamma), L.ptr(dbeta), L.ptr(g["ln_ws"]), R, C, self.sa_dropout, L.ptr(g["rng"]),
+                sid, st)
+        return g["da"]
 
     def _sa_conv_forward(self, p, P, l, ly, training, bn_training, update_running_stats):
         """The convolution module of layer l behind attn_norm: ly["h"] -> ly["hc"].  training: keep what a backward reads;
@@ -749,8 +823,8 @@ class CnnEngine(OptimizerExtMixin):
         self._k("sed_bn_silu_fwd", lib.sed_bn_silu_fwd, L.ptr(ly["cz"]), L.ptr(ly["cscale"]), L.ptr(ly["cshift"]), L.ptr(ly["cs"]), R, C, st)
         self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["cs"]), C, L.ptr(P[cm + ".pointwise2.weight"]), C,
                 L.ptr(P[cm + ".pointwise2.bias"]), L.ptr(ly["co"]), C, R, C, C, 1, None, st)
-        self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(ly["h"]), L.ptr(ly["co"]), L.ptr(P[cn + ".weight"]),
-                L.ptr(P[cn + ".bias"]), L.ptr(ly["hc"]), L.ptr(ly["stats3"]) if training else None, R, C, LN_EPS, st)
+        self._add_ln_fwd(g, ly["h"], ly["co"], P[cn + ".weight"], P[cn + ".bias"], ly["hc"], ly["stats3"] if training else None, R, C,
+                         8 * l + 2 if bn_training and self.sa_dropout else None)
 
     def _sa_conv_backward(self, p, P, G, l, ly, gcur, eval_bwd, ks, ws, done):
         """Backward of layer l's convolution module: gcur = the gradient of ly["hc"]; returns the gradient of ly["h"] (g["dhc"])."""
@@ -758,14 +832,14 @@ class CnnEngine(OptimizerExtMixin):
         B, t, C, R = p.B, p.t_out, self.cfg[-1][0], p.sa["R"]
         cm, cn = self.sa_conv_names(l)
         w1, w2 = cm + ".pointwise1.weight", cm + ".pointwise2.weight"
-        self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(gcur), L.ptr(ly["h"]), L.ptr(ly["co"]),
-                L.ptr(P[cn + ".weight"]), L.ptr(ly["stats3"]), L.ptr(g["dres"]), L.ptr(G[cn + ".weight"]), L.ptr(G[cn + ".bias"]),
-                L.ptr(g["ln_ws"]), R, C, st)
+        ga = self._add_ln_bwd(g, gcur, ly["h"], ly["co"], P[cn + ".weight"], ly["stats3"], G[cn + ".weight"], G[cn + ".bias"], R, C,
+                              8 * l + 2 if p.trained and self.sa_dropout else None)
         done(cn)
-        # ds = dres . pointwise2.weight;  d pointwise2.weight = dres^T . s, its bias gradient the column sums of dres
+        # ds = ga . pointwise2.weight;  d pointwise2.weight = ga^T . s, its bias gradient the column sums of ga (ga = dres, or m s dres
+        # under dropout: the gradient of the module's output)
         self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w2]), C, L.ptr(g["cw2T"]), C, C, C, C, 0, st)
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dres"]), C, L.ptr(g["cw2T"]), C, None, L.ptr(g["cds"]), C, R, C, C, 1, None, st)
-        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dres"]), C, L.ptr(ly["cs"]), C, L.ptr(G[w2]), C,
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ga), C, L.ptr(g["cw2T"]), C, None, L.ptr(g["cds"]), C, R, C, C, 1, None, st)
+        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(ga), C, L.ptr(ly["cs"]), C, L.ptr(G[w2]), C,
                 L.ptr(G[cm + ".pointwise2.bias"]), C, C, R, t, 0, ks, ws, st)
         # through the SiLU (gz over ds) and the BatchNorm: statistics, the finalisation, then dz = ca gz + cb z + cc on load
         if eval_bwd:
@@ -802,6 +876,9 @@ class CnnEngine(OptimizerExtMixin):
         C = self.cfg[-1][0]
         R = g["R"]
         self._tag = "sa"
+        drop = self.sa_dropout if bn_training else 0.0       # training-mode forwards only (a kept eval forward never drops)
+        if drop:
+            g["rng"].copy_(self.drop_state)                  # this forward's masks, and its backward's
         self._k("sed_mel_mean_fwd", lib.sed_mel_mean_fwd, dt, L.ptr(feat), L.ptr(g["m"]), R, p.w_out, C, pad32(C), st)
         if g["pe"] is not None:
             g["m"].view(B, t, C).add_(g["pe"])          # x' = x + pe[frame], in place: the residual and the projections read x'
@@ -810,28 +887,39 @@ class CnnEngine(OptimizerExtMixin):
             an, nn_, fn, fnn = self.sa_layer_names(l)
             self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(xin), C, L.ptr(P[an + ".in_proj_weight"]), C, L.ptr(P[an + ".in_proj_bias"]),
                     L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
-            self._k("sed_mhsa_fwd", lib.sed_mhsa_fwd, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(ly["lse"]) if training else None,
-                    B, t, Hh, C // Hh, st)
+            if drop:
+                self._k("sed_mhsa_fwd_drop", lib.sed_mhsa_fwd_drop, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(ly["lse"]),
+                        B, t, Hh, C // Hh, drop, L.ptr(g["rng"]), 8 * l + 0, st)
+            else:
+                self._k("sed_mhsa_fwd", lib.sed_mhsa_fwd, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(ly["lse"]) if training else None,
+                        B, t, Hh, C // Hh, st)
             self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["ctx"]), C, L.ptr(P[an + ".out_proj.weight"]), C,
                     L.ptr(P[an + ".out_proj.bias"]), L.ptr(ly["a"]), C, R, C, C, 1, None, st)
-            self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(xin), L.ptr(ly["a"]), L.ptr(P[nn_ + ".weight"]),
-                    L.ptr(P[nn_ + ".bias"]), L.ptr(ly["h"]), L.ptr(ly["stats"]) if training else None, R, C, LN_EPS, st)
+            self._add_ln_fwd(g, xin, ly["a"], P[nn_ + ".weight"], P[nn_ + ".bias"], ly["h"], ly["stats"] if training else None, R, C,
+                             8 * l + 1 if drop else None)
             xin = ly["h"]
             if self.sa_conv_kernel:
                 self._sa_conv_forward(p, P, l, ly, training, bn_training, update_running_stats)
                 xin = ly["hc"]
             if D:
                 # h2 = LayerNorm(h + ffn(h)): both products and the activation in one launch; u only for a backward
-                self._k("sed_ffn_fwd", lib.sed_ffn_fwd, dt, self.sa_act, L.ptr(xin), L.ptr(P[fn + ".linear1.weight"]),
-                        L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(ly["f"]),
-                        L.ptr(ly["u"]) if training else None, R, C, D, st)
-                self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(xin), L.ptr(ly["f"]), L.ptr(P[fnn + ".weight"]),
-                        L.ptr(P[fnn + ".bias"]), L.ptr(ly["h2"]), L.ptr(ly["stats2"]) if training else None, R, C, LN_EPS, st)
+                if drop:
+                    self._k("sed_ffn_fwd_drop", lib.sed_ffn_fwd_drop, dt, self.sa_act, L.ptr(xin), L.ptr(P[fn + ".linear1.weight"]),
+                            L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(ly["f"]),
+                            L.ptr(ly["u"]), R, C, D, drop, L.ptr(g["rng"]), 8 * l + 3, st)
+                else:
+                    self._k("sed_ffn_fwd", lib.sed_ffn_fwd, dt, self.sa_act, L.ptr(xin), L.ptr(P[fn + ".linear1.weight"]),
+                            L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(ly["f"]),
+                            L.ptr(ly["u"]) if training else None, R, C, D, st)
+                self._add_ln_fwd(g, xin, ly["f"], P[fnn + ".weight"], P[fnn + ".bias"], ly["h2"], ly["stats2"] if training else None, R, C,
+                                 8 * l + 4 if drop else None)
                 xin = ly["h2"]
         self._k("sed_head_fwd", lib.sed_head_fwd, L.SED_F32, L.ptr(g["h"]), L.ptr(P["event_fc.weight"]), L.ptr(P["event_fc.bias"]),
                 L.ptr(g["fc_m"]), L.ptr(p.pre), B, t, 1, C, C, self.K, st)
         if self.attention:
             self._att_forward(p, P)
+        if drop:
+            self.drop_state[2:3].add_(1)                     # the next training forward draws new masks (captured with the step)
         self._tag = ""
 
     def _sa_backward(self, p, P, G, src, ratio, dfeat, on_group_done):
@@ -851,6 +939,7 @@ class CnnEngine(OptimizerExtMixin):
         ks = max(1, min(g["ksplit"], R // 256))
         ws = L.ptr(g["tn_ws"]) if ks > 1 else None
         gcur = g["dh"]                                   # the gradient of the current layer's output
+        drop = self.sa_dropout if p.trained else 0.0     # the masks of the forward this backward belongs to (g["rng"])
         for l in reversed(range(self.sa_layers)):
             ly = g["layers"][l]
             xin = g["m"] if l == 0 else self._sa_layer_out(g["layers"][l - 1])
@@ -858,18 +947,22 @@ class CnnEngine(OptimizerExtMixin):
             fin = ly["hc"] if self.sa_conv_kernel else ly["h"]        # the FFN sub-layer's input
             if D:
                 w1, w2 = fn + ".linear1.weight", fn + ".linear2.weight"
-                self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(gcur), L.ptr(fin), L.ptr(ly["f"]),
-                        L.ptr(P[fnn + ".weight"]), L.ptr(ly["stats2"]), L.ptr(g["dres"]), L.ptr(G[fnn + ".weight"]),
-                        L.ptr(G[fnn + ".bias"]), L.ptr(g["ln_ws"]), R, C, st)
+                ga = self._add_ln_bwd(g, gcur, fin, ly["f"], P[fnn + ".weight"], ly["stats2"], G[fnn + ".weight"], G[fnn + ".bias"], R, C,
+                                      8 * l + 4 if drop else None)
                 done(fnn)
-                # da = dres . w2, then a = act(u) and du = da act'(u) (du over da)
+                # da = ga . w2 (ga: the gradient of the FFN's output -- dres, or m s dres under dropout), then a = act(u) and
+                # du = da act'(u) (du over da; under dropout a = m s act(u), du = da m s act'(u))
                 self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w2]), D, L.ptr(g["w2T"]), C, C, D, C, 0, st)
-                self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dres"]), C, L.ptr(g["w2T"]), C, None, L.ptr(g["fda"]), D, R, D, C, 1,
+                self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ga), C, L.ptr(g["w2T"]), C, None, L.ptr(g["fda"]), D, R, D, C, 1,
                         None, st)
-                self._k("sed_ffn_act_bwd", lib.sed_ffn_act_bwd, self.sa_act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
-                        L.ptr(g["fda"]), R * D, st)
-                # d linear2.weight = dres^T . a, d linear1.weight = du^T . h, the biases' gradients their column sums
-                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dres"]), C, L.ptr(g["ffa"]), D, L.ptr(G[w2]), D,
+                if drop:
+                    self._k("sed_ffn_act_bwd_drop", lib.sed_ffn_act_bwd_drop, self.sa_act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
+                            L.ptr(g["fda"]), R, D, drop, L.ptr(g["rng"]), 8 * l + 3, st)
+                else:
+                    self._k("sed_ffn_act_bwd", lib.sed_ffn_act_bwd, self.sa_act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
+                            L.ptr(g["fda"]), R * D, st)
+                # d linear2.weight = ga^T . a, d linear1.weight = du^T . h, the biases' gradients their column sums
+                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(ga), C, L.ptr(g["ffa"]), D, L.ptr(G[w2]), D,
                         L.ptr(G[fn + ".linear2.bias"]), C, D, R, t, 0, ks, ws, st)
                 self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["fda"]), D, L.ptr(fin), C, L.ptr(G[w1]), C,
                         L.ptr(G[fn + ".linear1.bias"]), D, C, R, t, 0, ks, ws, st)
@@ -882,19 +975,22 @@ class CnnEngine(OptimizerExtMixin):
                 gcur = g["dh1"]
             if self.sa_conv_kernel:
                 gcur = self._sa_conv_backward(p, P, G, l, ly, gcur, not p.trained, ks, ws, done)
-            self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(gcur), L.ptr(xin), L.ptr(ly["a"]),
-                    L.ptr(P[nn_ + ".weight"]), L.ptr(ly["stats"]), L.ptr(g["dres"]), L.ptr(G[nn_ + ".weight"]),
-                    L.ptr(G[nn_ + ".bias"]), L.ptr(g["ln_ws"]), R, C, st)
+            ga = self._add_ln_bwd(g, gcur, xin, ly["a"], P[nn_ + ".weight"], ly["stats"], G[nn_ + ".weight"], G[nn_ + ".bias"], R, C,
+                                  8 * l + 1 if drop else None)
             done(nn_)
-            # d out_proj.weight = dres^T . ctx, d out_proj.bias = column sums of dres
-            self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dres"]), C, L.ptr(ly["ctx"]), C, L.ptr(G[an + ".out_proj.weight"]), C,
+            # d out_proj.weight = ga^T . ctx, d out_proj.bias = column sums of ga (ga: the gradient of a -- dres, or m s dres under dropout)
+            self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(ga), C, L.ptr(ly["ctx"]), C, L.ptr(G[an + ".out_proj.weight"]), C,
                     L.ptr(G[an + ".out_proj.bias"]), C, C, R, t, 0, ks, ws, st)
-            # dctx = dres . out_proj.weight
+            # dctx = ga . out_proj.weight
             self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[an + ".out_proj.weight"]), C, L.ptr(g["woT"]), C, C, C, C, 0, st)
-            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dres"]), C, L.ptr(g["woT"]), C, None, L.ptr(g["dctx"]), C, R, C, C, 1,
+            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ga), C, L.ptr(g["woT"]), C, None, L.ptr(g["dctx"]), C, R, C, C, 1,
                     None, st)
-            self._k("sed_mhsa_bwd", lib.sed_mhsa_bwd, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
-                    L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, st)
+            if drop:
+                self._k("sed_mhsa_bwd_drop", lib.sed_mhsa_bwd_drop, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
+                        L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, drop, L.ptr(g["rng"]), 8 * l + 0, st)
+            else:
+                self._k("sed_mhsa_bwd", lib.sed_mhsa_bwd, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
+                        L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, st)
             # d in_proj_weight = dqkv^T . x', d in_proj_bias = column sums of dqkv
             self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dqkv"]), 3 * C, L.ptr(xin), C, L.ptr(G[an + ".in_proj_weight"]), C,
                     L.ptr(G[an + ".in_proj_bias"]), 3 * C, C, R, t, 0, ks, ws, st)

@@ -128,6 +128,11 @@ def build_weak_parser():
     p.add_argument("--sa_conv_kernel", type=int, default=0,
                    help="--self_attention: taps k of the depthwise filter of a Conformer convolution module between the attention and the "
                         "feed-forward sub-layer of every encoder layer (odd, 3 to 31); 0 builds no convolution module")
+    p.add_argument("--sa_dropout", type=float, default=0.0,
+                   help="--self_attention: dropout probability P in [0, 1) of the encoder layers in training (the attention probabilities, "
+                        "every sub-layer's output before its residual add, the FFN hidden activation); 0 drops nothing")
+    p.add_argument("--sa_dropout_seed", type=int, default=None,
+                   help="--sa_dropout: the 64-bit seed of the counter-based masks (default: torch's initial seed)")
     return p
 
 
@@ -363,7 +368,8 @@ def get_spectogram_dataset_model_and_criterion(args, device):
                                pos_encoding=not args.no_pos_encoding, mel_bins=n_mel, frontend=frontend, attention=att,
                                sa_layers=int(getattr(args, "sa_layers", 1)), sa_ffn=int(getattr(args, "sa_ffn", 0)),
                                sa_activation=getattr(args, "sa_activation", "relu"),
-                               sa_conv_kernel=int(getattr(args, "sa_conv_kernel", 0)))
+                               sa_conv_kernel=int(getattr(args, "sa_conv_kernel", 0)),
+                               sa_dropout=float(getattr(args, "sa_dropout", 0.0)), sa_dropout_seed=getattr(args, "sa_dropout_seed", None))
     else:
         model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend, attention=att)
     model.set_precision(args.precision)
@@ -447,12 +453,16 @@ def validate_args(args):
         check_sa_geometry(128, getattr(args, "sa_heads", 4))
         check_sa_conv_kernel(getattr(args, "sa_conv_kernel", 0))
         check_sa_encoder(128, getattr(args, "sa_layers", 1), getattr(args, "sa_ffn", 0), getattr(args, "sa_activation", "relu"))
+        from .engine import CnnEngine
+        CnnEngine.check_sa_dropout(getattr(args, "sa_dropout", 0.0))
     elif getattr(args, "sa_heads", 4) != 4 or getattr(args, "no_pos_encoding", False):
         raise ValueError("--sa_heads / --no_pos_encoding configure the self-attention head: they need --self_attention")
     elif getattr(args, "sa_layers", 1) != 1 or getattr(args, "sa_ffn", 0) != 0 or getattr(args, "sa_activation", "relu") != "relu":
         raise ValueError("--sa_layers / --sa_ffn / --sa_activation configure the self-attention head: they need --self_attention")
     elif getattr(args, "sa_conv_kernel", 0) != 0:
         raise ValueError("--sa_conv_kernel configures the self-attention head: it needs --self_attention")
+    elif getattr(args, "sa_dropout", 0.0) != 0.0 or getattr(args, "sa_dropout_seed", None) is not None:
+        raise ValueError("--sa_dropout / --sa_dropout_seed configure the self-attention head: they need --self_attention")
     for flag, value in (("--weak_pooling", weak_options(args).get("weak_pooling")), ("--eval_clip_pooling", getattr(args, "eval_clip_pooling", None))):
         if value == "att" and not att_head:
             raise ValueError(f"{flag} att pools with the attention head: it needs --attention_head")

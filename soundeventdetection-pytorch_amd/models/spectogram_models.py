@@ -521,13 +521,23 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     exists only when k > 0.  Per layer the draws are: the attention's, then convm.pointwise1.{weight, bias}, convm.depthwise.{weight,
     bias}, convm.pointwise2.{weight, bias} (torch.nn.Conv1d's initial values; bn and conv_norm draw nothing), then the FFN's.  With
     k = 0 the draws, the state_dict keys and the launches are those of a model without the argument.
-    Refused: C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0, sa_layers < 1, sa_ffn not 0 or a multiple of 32 up to
+    sa_dropout = p in [0, 1) and sa_dropout_seed: torch.nn.TransformerEncoderLayer(dropout=p)'s placement with one probability for
+    every site, in training mode only -- the attention probabilities (p~_ij = m_ij s p_ij, no renormalisation), each sub-layer's output
+    before its residual add (attention, convolution module, FFN: LayerNorm(x + m s a)) and the FFN hidden activation (m s act(u)),
+    s = 1 / (1 - p).  The masks are generated inside the kernels, forward and backward, from the engine's counter-based state
+    engine.drop_state = (seed_lo, seed_hi, step, 0) (csrc/philox.h; tests/dropout_formula.py reproduces every cell); every training
+    forward advances the step word by one.  The seed is sa_dropout_seed, or torch.initial_seed() when None: no random number is
+    drawn, no parameter or buffer is added, and eval-mode forwards and backwards never drop.  p = 0 (the default) changes nothing.
+    Refused: sa_dropout outside [0, 1), C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0, sa_layers < 1, sa_ffn not 0 or a multiple of 32 up to
     4096 (and C > 512 with it), an activation other than relu / gelu, sa_conv_kernel even, below 3 or above 31 (before any draw)."""
 
     ACTIVATIONS = ("relu", "gelu")
 
     def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, sa_heads=4, pos_encoding=True,
-                 mel_bins=None, frontend=None, attention=False, sa_layers=1, sa_ffn=0, sa_activation="relu", sa_conv_kernel=0):
+                 mel_bins=None, frontend=None, attention=False, sa_layers=1, sa_ffn=0, sa_activation="relu", sa_conv_kernel=0,
+                 sa_dropout=0.0, sa_dropout_seed=None):
+        self.sa_dropout = CnnEngine.check_sa_dropout(sa_dropout)          # (before any draw)
+        self.sa_dropout_seed = None if sa_dropout_seed is None else int(sa_dropout_seed)
         check_sa_geometry(int(model_config[-1][0]), sa_heads)
         check_sa_encoder(int(model_config[-1][0]), sa_layers, sa_ffn, sa_activation)
         self.sa_conv_kernel = check_sa_conv_kernel(sa_conv_kernel)
@@ -559,7 +569,8 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     def _make_engine(self, precision):
         return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="sa", sa_heads=self.sa_heads,
                          pos_encoding=self.pos_encoding, mel_bins=self.mel_bins, attention=self.attention, sa_layers=self.sa_layers,
-                         sa_ffn=self.sa_ffn, sa_activation=self.sa_activation, sa_conv_kernel=self.sa_conv_kernel)
+                         sa_ffn=self.sa_ffn, sa_activation=self.sa_activation, sa_conv_kernel=self.sa_conv_kernel,
+                         sa_dropout=self.sa_dropout, sa_dropout_seed=self.sa_dropout_seed)
 
     def _flush_counters(self):
         """The convolution modules' BatchNorm counters follow the conv blocks': counted on the host, folded in when looked at."""

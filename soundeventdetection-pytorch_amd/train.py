@@ -391,6 +391,17 @@ def check_state_amsgrad(group, amsgrad: bool):
                          "build it with amsgrad=True to resume from this state")
 
 
+# The mean teacher's dropout seed is the student's XOR this constant (the 64-bit golden-ratio constant): its training-mode forward
+# draws masks of its own.  With a process group, rank r uses seed + r.
+TEACHER_DROPOUT_SEED_XOR = 0x9E3779B97F4A7C15
+
+
+def _dropout_engine(model):
+    """the model's engine when it drops (Csa_AvgPooling with sa_dropout > 0), else None"""
+    eng = getattr(model, "engine", None)
+    return eng if eng is not None and getattr(eng, "sa_dropout", 0.0) > 0.0 else None
+
+
 class FusedTrainer:
     """Owns the flat buffers, the Adam state and the step counter for one model."""
 
@@ -474,6 +485,15 @@ class FusedTrainer:
         self.reducer = GradAllReducer(self.flat.g, self.flat.buckets, group)
         if self.teacher is not None:
             self.teacher_flat = FlatParams(self.teacher, grads=False)
+        deng = _dropout_engine(model)
+        if deng is not None:
+            seed = deng.sa_dropout_seed
+            if self.reducer.enabled:        # every rank its own masks
+                seed = (seed + self.reducer.rank) & 0xFFFFFFFFFFFFFFFF
+                deng.set_drop_state([seed & 0xFFFFFFFF, seed >> 32] + deng.drop_state_words()[2:])
+            if self.teacher is not None:
+                ts = seed ^ TEACHER_DROPOUT_SEED_XOR
+                self.teacher.engine.set_drop_state([ts & 0xFFFFFFFF, ts >> 32, 0, 0])
         self.sync_bn = bool(sync_bn) and self.reducer.enabled
         if self.reducer.enabled:
             # replicas start from rank 0's parameters and BatchNorm buffers (the DDP constructor's broadcast): identical
@@ -659,6 +679,11 @@ class FusedTrainer:
         sd = {"state": state, "param_groups": [group]}
         if self.teacher is not None:        # the mean teacher's parameters and BatchNorm buffers
             sd["teacher"] = {k: v.clone() for k, v in self.teacher.state_dict().items()}
+        deng = _dropout_engine(self.model)
+        if deng is not None:                # the four uint32 words (seed_lo, seed_hi, step, 0) the next training forward draws from
+            sd["dropout_state"] = torch.tensor(deng.drop_state_words(), dtype=torch.int64)
+            if self.teacher is not None:
+                sd["teacher_dropout_state"] = torch.tensor(self.teacher.engine.drop_state_words(), dtype=torch.int64)
         return sd
 
     def load_state_dict(self, sd, teacher=None):
@@ -693,6 +718,13 @@ class FusedTrainer:
                 self.teacher.load_state_dict(teacher if teacher is not None else sd["teacher"])
             else:                           # a checkpoint from before the teacher: it starts as a copy of the student
                 self.teacher.load_state_dict(self.model.state_dict())
+        deng = _dropout_engine(self.model)
+        if deng is not None:                # a state without it starts at step 0 with the seed the engine has
+            for eng, key in ((deng, "dropout_state"), (self.teacher.engine if self.teacher is not None else None, "teacher_dropout_state")):
+                if eng is None:
+                    continue
+                words = [int(v) for v in sd[key].tolist()] if key in sd else eng.drop_state_words()[:2] + [0, 0]
+                eng.set_drop_state(words)
         if self.use_graph:
             self.hyper[0] = self.lr
             self.step_dev.fill_(step)

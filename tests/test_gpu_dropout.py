@@ -1,0 +1,457 @@
+"""GPU: the dropout twins of the self-attention head through the C ABI (csrc/philox.h, sed_dropout.hip, the DROP instantiations of
+sed_mhsa.hip / sed_ffn.hip), per element against the float64 definitions of tests/dropout_formula.py within the gates derived in
+that file's docstring, at p in {0.1, 0.5}, SED_F32 and SED_BF16.
+
+  mask       sed_dropout_mask equals the numpy masks cell for cell (rows and attention), and a probe reads the mask out of the fused
+             attention forward itself: q = k = 0 (uniform weights 1/t), V = the first t rows of the identity, so ctx[i][j] = m_ij s / t
+  attention  ctx, lse, dq, dk, dv at B = 2, t on, under and over the tile edges (130: two workgroups per (clip, head), a 2-key last tile)
+  LayerNorm  y, stats, dres, da, dgamma, dbeta
+  FFN        the exact-integer family at p = 0.5 (s = 2: every value an integer) bit for bit, the Gaussian family inside the gates,
+             sed_ffn_act_bwd_drop per element
+  everywhere p = 0 gives the plain twin's bits, repeats give the same bits, another step word another result, lse = NULL / u = NULL
+             the same output bits, inputs between NaN regions and outputs between canaries, refusals leave the outputs untouched.
+Run with -s for the worst error / gate of every check.  Measured on the MI355X (worst over the cases of a family): attention 0.84 in
+bf16 (dv at t = 5: the 2^-8 operand term of p~ dominates there) and 0.04 in fp32, LayerNorm 0.17, activation backward 0.25, FFN 0.06."""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+import dropout_formula as DF
+import ffn_formula as FF
+import mhsa_formula as MF
+
+pytestmark = pytest.mark.gpu
+
+PKG = "soundeventdetection-pytorch_amd"
+GUARD = 1024
+CANARY = -1024.0
+F32, BF16 = 0, 1
+SEED = (0x5EDD0001, 0x00C0FFEE)          # tests/test_dropout_host.py: the kept fractions of these cases lie within 5 sigma
+STEP = 3
+PS = [0.1, 0.5]
+HEADS = [(1, 32), (4, 32), (2, 64)]
+T_SIZES = [1, 5, 33, 64, 65, 130]
+ROWS_MASK = [(1, 32), (65, 160), (130, 512)]
+ATTN_MASK = [(1, 5), (4, 33), (2, 130)]
+LN_SHAPES = [(r, c) for r in (1, 65, 130) for c in (32, 160)]
+FFN_SHAPES = [(1, 32, 32), (33, 64, 160), (130, 128, 512)]
+
+
+@pytest.fixture(scope="module")
+def L():
+    assert torch.cuda.is_available(), "GPU tests need the MI355X"
+    return importlib.import_module(PKG)._lib
+
+
+def stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def state(step=STEP, seed=SEED):
+    return np.array([seed[0], seed[1], step, 0], dtype=np.uint32)
+
+
+def dev_state(st):
+    return torch.from_numpy(np.asarray(st, dtype=np.uint32).view(np.int32).copy()).cuda()
+
+
+class Bufs:
+    def __init__(self):
+        self.outs = []
+
+    def out(self, *shape, dtype=torch.float32):
+        n = int(np.prod(shape))
+        fill = CANARY if dtype == torch.float32 else 0x5A
+        buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device="cuda")
+        buf[GUARD:GUARD + n] = float("nan") if dtype == torch.float32 else 0x77
+        self.outs.append((buf, n, fill))
+        return buf[GUARD:GUARD + n].view(shape)
+
+    @staticmethod
+    def inp(a):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        buf = torch.full((a.size + 2 * GUARD,), float("nan"), dtype=torch.float32, device="cuda")
+        buf[GUARD:GUARD + a.size] = torch.from_numpy(a.reshape(-1)).cuda()
+        return buf[GUARD:GUARD + a.size].view(a.shape)
+
+    def intact(self):
+        torch.cuda.synchronize()
+        for buf, n, fill in self.outs:
+            assert bool((buf[:GUARD] == fill).all()) and bool((buf[GUARD + n:] == fill).all()), "write outside an output buffer"
+
+
+def bits(t):
+    return t.detach().cpu().numpy().view(np.uint32)
+
+
+def untouched(*tensors):
+    torch.cuda.synchronize()
+    return all(bool(torch.isnan(t).all()) for t in tensors)
+
+
+def ok(got, ref, gate, tag):
+    good, worst = DF.check(got, ref, gate, tag)
+    assert good, (tag, worst)
+
+
+def operands(rng, dt, *shape, sigma=1.0):
+    a = rng.normal(0.0, sigma, shape).astype(np.float32)
+    return MF.round_bf16(a) if dt == BF16 else a
+
+
+# ---- the mask ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("p", PS)
+@pytest.mark.parametrize("shape", ROWS_MASK, ids=lambda v: f"R{v[0]}N{v[1]}")
+def test_mask_rows(L, shape, p):
+    R, N = shape
+    lib, P = L.lib(), L.ptr
+    b = Bufs()
+    st = state()
+    keep = b.out(R, N, dtype=torch.uint8)
+    L.check(lib.sed_dropout_mask(P(keep), 0, R, N, 0, p, P(dev_state(st)), DF.stream_id(1, 4), stream()), "dropout_mask")
+    b.intact()
+    assert np.array_equal(keep.cpu().numpy(), DF.keep_rows(st, DF.stream_id(1, 4), R, N, p))
+
+
+@pytest.mark.parametrize("p", PS)
+@pytest.mark.parametrize("shape", ATTN_MASK, ids=lambda v: f"H{v[0]}t{v[1]}")
+def test_mask_attention(L, shape, p):
+    H, t = shape
+    B = 2
+    lib, P = L.lib(), L.ptr
+    b = Bufs()
+    st = state()
+    keep = b.out(B, H, t, t, dtype=torch.uint8)
+    L.check(lib.sed_dropout_mask(P(keep), 1, B, H, t, p, P(dev_state(st)), DF.stream_id(2, 0), stream()), "dropout_mask")
+    b.intact()
+    assert np.array_equal(keep.cpu().numpy(), DF.keep_attn(st, DF.stream_id(2, 0), B, H, t, p))
+
+
+@pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("p", PS)
+@pytest.mark.parametrize("hd_t", [((1, 32), 5), ((4, 32), 32), ((2, 64), 33), ((2, 64), 64)], ids=str)
+def test_mask_read_out_of_the_fused_forward(L, hd_t, p, dt):
+    """q = k = 0: p_ij = 1/t; V = the first t rows of the identity (t <= dh): ctx[i][j] = m_ij s / t for j < t, 0 beyond"""
+    (H, dh), t = hd_t
+    B, C = 2, H * dh
+    lib, P = L.lib(), L.ptr
+    q = np.zeros((B, t, H, dh), dtype=np.float32)
+    v = np.zeros((B, t, H, dh), dtype=np.float32)
+    for j in range(t):
+        v[:, j, :, j] = 1.0
+    st = state(step=11)
+    sid = DF.stream_id(0, 0)
+    b = Bufs()
+    qkv, ctx = b.inp(MF.join_qkv(q, q, v)), b.out(B * t, C)
+    L.check(lib.sed_mhsa_fwd_drop(dt, P(qkv), P(ctx), None, B, t, H, dh, p, P(dev_state(st)), sid, stream()), "mhsa_fwd_drop")
+    b.intact()
+    got = ctx.cpu().numpy().reshape(B, t, H, dh).transpose(0, 2, 1, 3)           # [b][g][i][column]
+    keep = DF.keep_attn(st, sid, B, H, t, p)
+    assert np.array_equal(got[..., :t] != 0, keep != 0), "the fused forward drops other cells than sed_dropout_mask names"
+    assert not got[..., t:].any()
+    s = float(DF.thr_scale(p)[1])
+    assert np.allclose(got[..., :t], keep * (s / t), rtol=2.0 ** -7, atol=0)
+
+
+# ---- attention ----------------------------------------------------------------------------------------------------------------------
+def run_core_drop(L, dt, q, k, v, dctx, p, st, sid, tag):
+    B, t, H, dh = q.shape
+    C = H * dh
+    lib, P = L.lib(), L.ptr
+    keep, s = DF.keep_attn(st, sid, B, H, t, p), DF.thr_scale(p)[1]
+    ref = DF.core(q, k, v, keep, s, dctx)
+    mode = "bf16" if dt == BF16 else "f32"
+    b = Bufs()
+    rng_d = dev_state(st)
+    qkv = b.inp(MF.join_qkv(q, k, v))
+    ctx, lse, ctx2 = b.out(B * t, C), b.out(B, H, t), b.out(B * t, C)
+    L.check(lib.sed_mhsa_fwd_drop(dt, P(qkv), P(ctx), P(lse), B, t, H, dh, p, P(rng_d), sid, stream()), "mhsa_fwd_drop")
+    L.check(lib.sed_mhsa_fwd_drop(dt, P(qkv), P(ctx2), None, B, t, H, dh, p, P(rng_d), sid, stream()), "mhsa_fwd_drop")
+    b.intact()
+    gates = DF.core_gates(q, k, v, keep, s, dctx, mode)
+    ok(ctx.cpu().numpy().reshape(B, t, H, dh), ref["ctx"], gates["ctx"], (tag, "ctx"))
+    ok(lse.cpu().numpy(), ref["lse"], gates["lse"], (tag, "lse"))
+    assert np.array_equal(bits(ctx), bits(ctx2)), (tag, "lse = NULL changed ctx")
+    ctx_in, lse_in, dctx_in = b.inp(ref["ctx"].reshape(B * t, C)), b.inp(ref["lse"]), b.inp(dctx.reshape(B * t, C))
+    ctx32 = ctx_in.cpu().numpy().reshape(B, t, H, dh)
+    lse32 = lse_in.cpu().numpy()
+    refb = DF.core(q, k, v, keep, s, dctx, lse=lse32, ctx=ctx32)
+    gb = DF.core_gates(q, k, v, keep, s, dctx, mode, lse=lse32, ctx=ctx32)
+    nws = lib.sed_mhsa_bwd_ws_floats(B, t, H, dh)
+    outs = []
+    for _ in range(2):
+        dqkv, ws = b.out(B * t, 3 * C), b.out(nws)
+        L.check(lib.sed_mhsa_bwd_drop(dt, P(qkv), P(ctx_in), P(dctx_in), P(lse_in), P(dqkv), P(ws), B, t, H, dh, p, P(rng_d), sid,
+                                      stream()), "mhsa_bwd_drop")
+        outs.append(dqkv)
+    b.intact()
+    assert np.array_equal(bits(outs[0]), bits(outs[1])), (tag, "two backward runs differ")
+    dq, dk, dv = MF.split_qkv(outs[0].cpu().numpy(), B, t, H, dh)
+    for name, got in (("dq", dq), ("dk", dk), ("dv", dv)):
+        ok(got, refb[name], gb[name], (tag, name))
+    return ctx, outs[0]
+
+
+@pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("p", PS)
+@pytest.mark.parametrize("hd", HEADS, ids=lambda v: f"H{v[0]}dh{v[1]}")
+@pytest.mark.parametrize("t", T_SIZES)
+def test_core_against_formula(L, t, hd, p, dt):
+    H, dh = hd
+    rng = np.random.default_rng(1000 * t + 10 * H + dt)
+    q, k, v, d = (operands(rng, dt, 2, t, H, dh, sigma=s) for s in (1.0, 1.0, 1.0, 0.1))
+    run_core_drop(L, dt, q, k, v, d, p, state(), DF.stream_id(1, 0), ("core", t, H, dh, p, dt))
+
+
+@pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
+def test_core_p0_is_the_plain_twin_and_the_step_matters(L, dt):
+    B, t, H, dh = 2, 65, 2, 64
+    C = H * dh
+    lib, P = L.lib(), L.ptr
+    rng = np.random.default_rng(5)
+    q, k, v, d = (operands(rng, dt, B, t, H, dh, sigma=s) for s in (1.0, 1.0, 1.0, 0.1))
+    b = Bufs()
+    qkv, dctx = b.inp(MF.join_qkv(q, k, v)), b.inp(d.reshape(B * t, C))
+    nws = lib.sed_mhsa_bwd_ws_floats(B, t, H, dh)
+
+    def run(p, st):
+        ctx, lse, dqkv, ws = b.out(B * t, C), b.out(B, H, t), b.out(B * t, 3 * C), b.out(nws)
+        if p is None:
+            L.check(lib.sed_mhsa_fwd(dt, P(qkv), P(ctx), P(lse), B, t, H, dh, stream()), "fwd")
+            L.check(lib.sed_mhsa_bwd(dt, P(qkv), P(ctx), P(dctx), P(lse), P(dqkv), P(ws), B, t, H, dh, stream()), "bwd")
+        else:
+            r = dev_state(st)
+            L.check(lib.sed_mhsa_fwd_drop(dt, P(qkv), P(ctx), P(lse), B, t, H, dh, p, P(r), 0, stream()), "fwd")
+            L.check(lib.sed_mhsa_bwd_drop(dt, P(qkv), P(ctx), P(dctx), P(lse), P(dqkv), P(ws), B, t, H, dh, p, P(r), 0, stream()), "bwd")
+        return [bits(x) for x in (ctx, lse, dqkv)]
+
+    plain, zero = run(None, None), run(0.0, state())
+    assert all(np.array_equal(a, c) for a, c in zip(plain, zero)), "p = 0 must give the plain twin's bits"
+    a, a2, c = run(0.5, state(3)), run(0.5, state(3)), run(0.5, state(4))
+    assert all(np.array_equal(x, y) for x, y in zip(a, a2))
+    assert np.array_equal(a[1], plain[1]), "lse does not see the mask"
+    assert not np.array_equal(a[0], c[0]) and not np.array_equal(a[2], c[2]), "another step word must give another mask"
+    b.intact()
+
+
+# ---- LayerNorm ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("p", PS)
+@pytest.mark.parametrize("shape", LN_SHAPES, ids=lambda v: f"R{v[0]}C{v[1]}")
+def test_add_layernorm_against_formula(L, shape, p):
+    R, C = shape
+    lib, P = L.lib(), L.ptr
+    rng = np.random.default_rng(100 * R + C)
+    x, a, dy = (rng.normal(0, s, (R, C)).astype(np.float32) for s in (1.0, 1.0, 0.1))
+    gamma, beta = rng.normal(1, 0.2, C).astype(np.float32), rng.normal(0, 0.2, C).astype(np.float32)
+    st, sid = state(), DF.stream_id(0, 1)
+    keep, s = DF.keep_rows(st, sid, R, C, p), DF.thr_scale(p)[1]
+    ref = DF.add_layernorm(x, a, keep, s, gamma, beta, dy)
+    b = Bufs()
+    r = dev_state(st)
+    xd, ad, gd, bd, dyd = (b.inp(v) for v in (x, a, gamma, beta, dy))
+    y, stats, y2 = b.out(R, C), b.out(R, 2), b.out(R, C)
+    L.check(lib.sed_add_layernorm_fwd_drop(P(xd), P(ad), P(gd), P(bd), P(y), P(stats), R, C, MF.EPS, p, P(r), sid, stream()), "ln_fwd_drop")
+    L.check(lib.sed_add_layernorm_fwd_drop(P(xd), P(ad), P(gd), P(bd), P(y2), None, R, C, MF.EPS, p, P(r), sid, stream()), "ln_fwd_drop")
+    b.intact()
+    assert np.array_equal(bits(y), bits(y2))
+    st32 = np.stack([ref["mean"], ref["rstd"]], axis=1).astype(np.float32)
+    g = DF.add_layernorm_gates(x, a, keep, s, gamma, beta, dy, stats=st32)
+    ok(y.cpu().numpy(), ref["y"], g["y"], ("ln", R, C, p, "y"))
+    got = stats.cpu().numpy()
+    az = np.abs(ref["z"])
+    assert (np.abs(got[:, 0] - ref["mean"]) <= (C + 9) * DF.U * az.mean(axis=1)).all()
+    assert (np.abs(got[:, 1] - ref["rstd"]) <= (C + 9) * DF.U * ref["rstd"] * 2).all()
+    refb = DF.add_layernorm(x, a, keep, s, gamma, beta, dy, stats=st32)
+    sd = b.inp(st32)
+    nws = lib.sed_add_layernorm_bwd_ws_floats(R, C)
+    outs = []
+    for _ in range(2):
+        dres, da, dg, db, ws = b.out(R, C), b.out(R, C), b.out(C), b.out(C), b.out(nws)
+        L.check(lib.sed_add_layernorm_bwd_drop(P(dyd), P(xd), P(ad), P(gd), P(sd), P(dres), P(da), P(dg), P(db), P(ws), R, C, p, P(r), sid,
+                                               stream()), "ln_bwd_drop")
+        outs.append((dres, da, dg, db))
+    b.intact()
+    for u_, w_ in zip(*outs):
+        assert np.array_equal(bits(u_), bits(w_))
+    for name, got in zip(("dres", "da", "dgamma", "dbeta"), outs[0]):
+        ok(got.cpu().numpy(), refb[name], g[name], ("ln", R, C, p, name))
+
+
+def test_add_layernorm_p0_is_the_plain_twin_and_the_step_matters(L):
+    R, C = 65, 160
+    lib, P = L.lib(), L.ptr
+    rng = np.random.default_rng(9)
+    x, a, dy = (rng.normal(0, 1, (R, C)).astype(np.float32) for _ in range(3))
+    gamma, beta = rng.normal(1, 0.2, C).astype(np.float32), rng.normal(0, 0.2, C).astype(np.float32)
+    b = Bufs()
+    xd, ad, gd, bd, dyd = (b.inp(v) for v in (x, a, gamma, beta, dy))
+    nws = lib.sed_add_layernorm_bwd_ws_floats(R, C)
+
+    def run(p, st):
+        y, stats, dres, da, dg, db, ws = b.out(R, C), b.out(R, 2), b.out(R, C), b.out(R, C), b.out(C), b.out(C), b.out(nws)
+        if p is None:
+            L.check(lib.sed_add_layernorm_fwd(P(xd), P(ad), P(gd), P(bd), P(y), P(stats), R, C, MF.EPS, stream()), "f")
+            L.check(lib.sed_add_layernorm_bwd(P(dyd), P(xd), P(ad), P(gd), P(stats), P(dres), P(dg), P(db), P(ws), R, C, stream()), "b")
+            da = dres
+        else:
+            r = dev_state(st)
+            L.check(lib.sed_add_layernorm_fwd_drop(P(xd), P(ad), P(gd), P(bd), P(y), P(stats), R, C, MF.EPS, p, P(r), 2, stream()), "f")
+            L.check(lib.sed_add_layernorm_bwd_drop(P(dyd), P(xd), P(ad), P(gd), P(stats), P(dres), P(da), P(dg), P(db), P(ws), R, C, p,
+                                                   P(r), 2, stream()), "b")
+        return [bits(v) for v in (y, stats, dres, da, dg, db)]
+
+    plain, zero = run(None, None), run(0.0, state())
+    assert all(np.array_equal(u_, w_) for u_, w_ in zip(plain, zero)), "p = 0 must give the plain twin's bits (da = dres)"
+    u1, u2 = run(0.5, state(3)), run(0.5, state(4))
+    assert not np.array_equal(u1[0], u2[0]) and not np.array_equal(u1[3], u2[3])
+    b.intact()
+
+
+# ---- FFN ------------------------------------------------------------------------------------------------------------------------------
+def run_ffn(L, dt, act, x, w1, b1, w2, b2, p, st, sid, with_u=True):
+    lib, P = L.lib(), L.ptr
+    R, C = x.shape
+    D = w1.shape[0]
+    b = Bufs()
+    r = dev_state(st)
+    xd, w1d, b1d, w2d, b2d = (b.inp(v) for v in (x, w1, b1, w2, b2))
+    y, u = b.out(R, C), b.out(R, D)
+    L.check(lib.sed_ffn_fwd_drop(dt, FF.ACT_CODE[act], P(xd), P(w1d), P(b1d), P(w2d), P(b2d), P(y), P(u) if with_u else None, R, C, D, p,
+                                 P(r), sid, stream()), "ffn_fwd_drop")
+    b.intact()
+    return y, u
+
+
+@pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("shape", FFN_SHAPES, ids=lambda v: "R%dC%dD%d" % v)
+def test_ffn_exact_integers_at_one_half(L, shape, dt):
+    """the exact-integer family of tests/test_gpu_ffn.py (ReLU) at p = 0.5: s = 2 exactly and every value stays an integer, so float64,
+    fp32 and bf16 operands agree bit for bit"""
+    R, C, D = shape
+    act = "relu"
+    x, w1, b1, w2, b2 = FF.exact_case(np.random.default_rng(R + C + D), R, C, D)
+    st, sid = state(), DF.stream_id(0, 3)
+    keep, s = DF.keep_rows(st, sid, R, D, 0.5), DF.thr_scale(0.5)[1]
+    assert float(s) == 2.0
+    ref = DF.ffn(x, w1, b1, w2, b2, act, keep, s)
+    y, u = run_ffn(L, dt, act, x, w1, b1, w2, b2, 0.5, st, sid)
+    y2, _ = run_ffn(L, dt, act, x, w1, b1, w2, b2, 0.5, st, sid, with_u=False)
+    assert np.array_equal(u.cpu().numpy().astype(np.float64), ref["u"]), "u is stored undropped, exactly"
+    assert np.array_equal(bits(y), bits(y2)), "u = NULL changed y"
+    assert np.abs(ref["a"]).max() <= 256 and np.array_equal(ref["a"], np.round(ref["a"]))
+    assert np.array_equal(y.cpu().numpy().astype(np.float64), ref["y"]), "y is not exact: the hidden mask or its scale is off"
+
+
+@pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("p", PS)
+@pytest.mark.parametrize("act", ["relu", "gelu"])
+@pytest.mark.parametrize("shape", FFN_SHAPES, ids=lambda v: "R%dC%dD%d" % v)
+def test_ffn_gaussian_against_formula(L, shape, act, p, dt):
+    R, C, D = shape
+    rng = np.random.default_rng(7 * R + C + D)
+    x, w1, w2 = operands(rng, dt, R, C), operands(rng, dt, D, C, sigma=C ** -0.5), operands(rng, dt, C, D, sigma=D ** -0.5)
+    b1, b2 = rng.normal(0, 0.1, D).astype(np.float32), rng.normal(0, 0.1, C).astype(np.float32)
+    st, sid = state(), DF.stream_id(1, 3)
+    keep, s = DF.keep_rows(st, sid, R, D, p), DF.thr_scale(p)[1]
+    ref = DF.ffn(x, w1, b1, w2, b2, act, keep, s)
+    g = DF.ffn_gates(x, w1, b1, w2, b2, act, keep, s, "bf16" if dt == BF16 else "f32")
+    y, u = run_ffn(L, dt, act, x, w1, b1, w2, b2, p, st, sid)
+    y2, _ = run_ffn(L, dt, act, x, w1, b1, w2, b2, p, st, sid, with_u=False)
+    ok(u.cpu().numpy(), ref["u"], g["u"], ("ffn", shape, act, p, dt, "u"))
+    ok(y.cpu().numpy(), ref["y"], g["y"], ("ffn", shape, act, p, dt, "y"))
+    assert np.array_equal(bits(y), bits(y2)), "u = NULL changed y"
+    y3, _ = run_ffn(L, dt, act, x, w1, b1, w2, b2, p, state(STEP + 1), sid)
+    assert not np.array_equal(bits(y), bits(y3)), "another step word must give another mask"
+
+
+@pytest.mark.parametrize("p", PS)
+@pytest.mark.parametrize("act", ["relu", "gelu"])
+@pytest.mark.parametrize("shape", [(1, 32), (33, 160), (130, 512)], ids=lambda v: "R%dD%d" % v)
+def test_ffn_act_bwd_drop_per_element(L, shape, act, p):
+    R, D = shape
+    lib, P = L.lib(), L.ptr
+    rng = np.random.default_rng(R + D)
+    u, da = rng.normal(0, 2, (R, D)).astype(np.float32), rng.normal(0, 1, (R, D)).astype(np.float32)
+    st, sid = state(), DF.stream_id(0, 3)
+    keep, s = DF.keep_rows(st, sid, R, D, p), DF.thr_scale(p)[1]
+    ms = keep * float(s)
+    b = Bufs()
+    ud, dad, r = b.inp(u), b.inp(da), dev_state(st)
+    outs = []
+    for _ in range(2):
+        a, du = b.out(R, D), b.out(R, D)
+        L.check(lib.sed_ffn_act_bwd_drop(FF.ACT_CODE[act], P(ud), P(dad), P(a), P(du), R, D, p, P(r), sid, stream()), "act_bwd_drop")
+        outs.append((a, du))
+    b.intact()
+    assert np.array_equal(bits(outs[0][0]), bits(outs[1][0])) and np.array_equal(bits(outs[0][1]), bits(outs[1][1]))
+    g = DF.act_bwd_gates(u, da, act, keep, s)
+    u64, da64 = u.astype(np.float64), da.astype(np.float64)
+    ok(outs[0][0].cpu().numpy(), ms * FF.act_fwd(u64, act), g["a"], ("act_bwd", shape, act, p, "a"))
+    ok(outs[0][1].cpu().numpy(), da64 * ms * FF.act_grad(u64, act), g["du"], ("act_bwd", shape, act, p, "du"))
+
+
+@pytest.mark.parametrize("dt", [F32, BF16], ids=["f32", "bf16"])
+def test_ffn_p0_is_the_plain_twin(L, dt):
+    R, C, D = 33, 64, 160
+    lib, P = L.lib(), L.ptr
+    rng = np.random.default_rng(3)
+    x, w1, w2 = operands(rng, dt, R, C), operands(rng, dt, D, C, sigma=0.1), operands(rng, dt, C, D, sigma=0.1)
+    b1, b2 = rng.normal(0, 0.1, D).astype(np.float32), rng.normal(0, 0.1, C).astype(np.float32)
+    b = Bufs()
+    xd, w1d, b1d, w2d, b2d = (b.inp(v) for v in (x, w1, b1, w2, b2))
+    da = b.inp(rng.normal(0, 1, (R, D)))
+    y, u, a, du = b.out(R, C), b.out(R, D), b.out(R, D), b.out(R, D)
+    L.check(lib.sed_ffn_fwd(dt, 1, P(xd), P(w1d), P(b1d), P(w2d), P(b2d), P(y), P(u), R, C, D, stream()), "ffn")
+    L.check(lib.sed_ffn_act_bwd(1, P(u), P(da), P(a), P(du), R * D, stream()), "act")
+    r = dev_state(state())
+    y0, u0, a0, du0 = b.out(R, C), b.out(R, D), b.out(R, D), b.out(R, D)
+    L.check(lib.sed_ffn_fwd_drop(dt, 1, P(xd), P(w1d), P(b1d), P(w2d), P(b2d), P(y0), P(u0), R, C, D, 0.0, P(r), 3, stream()), "ffn")
+    L.check(lib.sed_ffn_act_bwd_drop(1, P(u0), P(da), P(a0), P(du0), R, D, 0.0, P(r), 3, stream()), "act")
+    b.intact()
+    for m, n in ((y, y0), (u, u0), (a, a0), (du, du0)):
+        assert np.array_equal(bits(m), bits(n)), "p = 0 must give the plain twin's bits"
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------
+def test_refusals_leave_the_outputs_untouched(L):
+    lib, P = L.lib(), L.ptr
+    B, t, H, dh, C, D = 1, 5, 1, 32, 32, 32
+    R = B * t
+    b = Bufs()
+    rng = np.random.default_rng(0)
+    qkv, ctxi, dctx, lsei = b.inp(rng.normal(0, 1, (R, 3 * C))), b.inp(rng.normal(0, 1, (R, C))), b.inp(rng.normal(0, 1, (R, C))), b.inp(np.zeros((B, H, t)))
+    x, a, gam, bet, stats = b.inp(rng.normal(0, 1, (R, C))), b.inp(rng.normal(0, 1, (R, C))), b.inp(np.ones(C)), b.inp(np.zeros(C)), b.inp(np.ones((R, 2)))
+    w1, b1, w2, b2, u = b.inp(rng.normal(0, 1, (D, C))), b.inp(np.zeros(D)), b.inp(rng.normal(0, 1, (C, D))), b.inp(np.zeros(C)), b.inp(rng.normal(0, 1, (R, D)))
+    da_in = b.inp(rng.normal(0, 1, (R, D)))
+    r = dev_state(state())
+    ctx, lse, dqkv, ws = b.out(R, C), b.out(B, H, t), b.out(R, 3 * C), b.out(64)
+    y, st_o, dres, da, dg, db, lws = b.out(R, C), b.out(R, 2), b.out(R, C), b.out(R, C), b.out(C), b.out(C), b.out(2 * C)
+    fy, fu, fa, fdu = b.out(R, C), b.out(R, D), b.out(R, D), b.out(R, D)
+    keep = b.out(R, C, dtype=torch.uint8)
+    s = stream()
+    bad = [(-0.1, P(r)), (1.0, P(r)), (1.5, P(r)), (float("nan"), P(r)), (0.1, None)]
+    for p, rp in bad:
+        assert lib.sed_mhsa_fwd_drop(F32, P(qkv), P(ctx), P(lse), B, t, H, dh, p, rp, 0, s) != 0
+        assert lib.sed_mhsa_bwd_drop(F32, P(qkv), P(ctxi), P(dctx), P(lsei), P(dqkv), P(ws), B, t, H, dh, p, rp, 0, s) != 0
+        assert lib.sed_add_layernorm_fwd_drop(P(x), P(a), P(gam), P(bet), P(y), P(st_o), R, C, MF.EPS, p, rp, 1, s) != 0
+        assert lib.sed_add_layernorm_bwd_drop(P(dctx), P(x), P(a), P(gam), P(stats), P(dres), P(da), P(dg), P(db), P(lws), R, C, p, rp, 1, s) != 0
+        assert lib.sed_ffn_fwd_drop(F32, 0, P(x), P(w1), P(b1), P(w2), P(b2), P(fy), P(fu), R, C, D, p, rp, 3, s) != 0
+        assert lib.sed_ffn_act_bwd_drop(0, P(u), P(da_in), P(fa), P(fdu), R, D, p, rp, 3, s) != 0
+        assert lib.sed_dropout_mask(P(keep), 0, R, C, 0, p, rp, 0, s) != 0
+    # what the plain twins refuse, and the twins' own arguments
+    assert lib.sed_mhsa_fwd_drop(F32, P(qkv), P(ctx), P(lse), B, t, H, 48, 0.1, P(r), 0, s) != 0
+    assert lib.sed_mhsa_fwd_drop(7, P(qkv), P(ctx), P(lse), B, t, H, dh, 0.1, P(r), 0, s) != 0
+    assert lib.sed_mhsa_bwd_drop(F32, P(qkv), P(ctxi), P(dctx), None, P(dqkv), P(ws), B, t, H, dh, 0.1, P(r), 0, s) != 0
+    assert lib.sed_add_layernorm_fwd_drop(P(x), None, P(gam), P(bet), P(y), P(st_o), R, C, MF.EPS, 0.1, P(r), 1, s) != 0
+    assert lib.sed_add_layernorm_bwd_drop(P(dctx), P(x), P(a), P(gam), P(stats), P(dres), None, P(dg), P(db), P(lws), R, C, 0.1, P(r), 1, s) != 0
+    assert lib.sed_ffn_fwd_drop(F32, 0, P(x), P(w1), P(b1), P(w2), P(b2), P(fy), P(fu), R, C, 48, 0.1, P(r), 3, s) != 0
+    assert lib.sed_ffn_act_bwd_drop(0, P(u), P(da_in), P(fa), P(fdu), R, 30, 0.1, P(r), 3, s) != 0
+    assert lib.sed_ffn_act_bwd_drop(5, P(u), P(da_in), P(fa), P(fdu), R, D, 0.1, P(r), 3, s) != 0
+    assert lib.sed_dropout_mask(P(keep), 2, R, C, 0, 0.1, P(r), 0, s) != 0
+    assert lib.sed_dropout_mask(None, 0, R, C, 0, 0.1, P(r), 0, s) != 0
+    assert lib.sed_dropout_mask(P(keep), 1, 1, 1, 0, 0.1, P(r), 0, s) != 0
+    assert untouched(ctx, lse, dqkv, ws, y, st_o, dres, da, dg, db, lws, fy, fu, fa, fdu)
+    assert bool((keep == 0x77).all())
+    b.intact()
