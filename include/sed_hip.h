@@ -1147,6 +1147,31 @@ int sed_ffn_act_bwd_drop(int act, const float* u, const float* da, float* a, flo
 int sed_dropout_mask(unsigned char* keep, int kind, size_t n0, int n1, int t, float p, const uint32_t* rng, uint32_t stream_id,
                      void* stream);
 
+/* ---- local attention window of the self-attention head (the WIN instantiations in csrc/sed_mhsa.hip) ---------------------------
+ * Two integers for every head: key j of the same clip takes part for query i iff i - left <= j <= i + right (torch: attn_mask
+ * M[i][j] = True where j < i - left or j > i + right).  In sed_mhsa_fwd's definitions lse_i, p_ij and ctx_i run over the in-window
+ * keys only and p_ij = 0 outside; in the backward ds_ij = 0 outside, and dv, dq, dk and D_i are built from those.  The diagonal is
+ * always inside, so no row is empty.  A side >= t - 1 is unbounded (SED_WIN_UNBOUNDED for short); right = 0 is causal attention
+ * with a look-back of left.  Dropout composes: p~_ij = m_ij s p_ij with p over the window, the counters indexed by the absolute
+ * (b H + g, i, j, step), so the dropped cells are the ones sed_dropout_mask reports.
+ * A wave that owns queries [q0, q0 + 31] walks only the key tiles that meet [q0 - left, q0 + 31 + right] (the dK / dV pass: keys
+ * [k0, k0 + 31], query tiles that meet [k0 - right, k0 + 31 + left]); inside a visited tile cells outside the window are masked by
+ * select (score -inf; backward p = dS = 0 without taking the exponential).  Fixed order, no atomics, the same bits on every run.
+ * One pair of entries: p = 0 is no dropout and allowed with rng NULL, p > 0 needs rng as the _drop twins do.  The workspace is
+ * sed_mhsa_bwd_ws_floats.  Both sides unbounded (after clamping to t - 1) launches the kernels of sed_mhsa_fwd / _bwd (p = 0) or of
+ * the _drop twins (p > 0): their bits by construction.
+ * sed_mhsa_win_tiles: per (clip, head), the number of 32 x 32 tiles on which a wave of the pass (0 forward, 1 dK / dV, 2 dQ) issues
+ * MFMAs -- the loop bounds the kernels use, from the same helper; a host function, nothing is launched.  All t x t: ceil(t/32)^2.
+ * Refused (non-zero, nothing launched, outputs untouched): whatever sed_mhsa_fwd / _bwd refuse; left < 0, right < 0; p < 0, p >= 1,
+ * NaN; p > 0 with rng NULL.  sed_mhsa_win_tiles returns -1 for t <= 0, a negative side or an unknown pass.                         */
+#define SED_WIN_UNBOUNDED 0x7fffffff
+int sed_mhsa_fwd_win(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, int left, int right, float p,
+                     const uint32_t* rng, uint32_t stream_id, void* stream);
+int sed_mhsa_bwd_win(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
+                     float* workspace, int B, int t, int H, int dh, int left, int right, float p, const uint32_t* rng,
+                     uint32_t stream_id, void* stream);
+long long sed_mhsa_win_tiles(int t, int left, int right, int pass);
+
 /* ---- Conformer convolution module of the self-attention head (csrc/sed_convmod.hip) ------------
  * Between the attention and the feed-forward sub-layer: pointwise Conv1d(C, 2C, 1) -> GLU -> depthwise Conv1d(C, C, k, padding
  * (k-1)/2, groups=C) -> BatchNorm1d(C) -> SiLU -> pointwise Conv1d(C, C, 1).  The pointwise convolutions are sed_gemm_nt launches, the

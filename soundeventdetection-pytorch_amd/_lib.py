@@ -15,6 +15,7 @@ PCM_I16, PCM_I32, PCM_F32 = 0, 1, 2
 POOL_MAX, POOL_MEAN, POOL_LINEAR, POOL_EXP = 0, 1, 2, 3
 POOL_MODES = {"max": POOL_MAX, "mean": POOL_MEAN, "linear": POOL_LINEAR, "exp": POOL_EXP}
 CRIT_BCE, CRIT_MSE = 0, 1
+WIN_UNBOUNDED = 0x7FFFFFFF          # SED_WIN_UNBOUNDED: a side of sed_mhsa_fwd_win / _bwd_win that reaches the clip's end
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsed_hip.so")
@@ -186,6 +187,10 @@ PROTOTYPES = {
     "sed_ffn_fwd_drop": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _F, _P, _U32, _P]),
     "sed_ffn_act_bwd_drop": (_I, [_I, _P, _P, _P, _P, _Z, _I, _F, _P, _U32, _P]),
     "sed_dropout_mask": (_I, [_P, _I, _Z, _I, _I, _F, _P, _U32, _P]),
+    # the local attention window: the plain entry's arguments + (int left, int right, float p, const uint32_t* rng, uint32_t stream_id)
+    "sed_mhsa_fwd_win": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _U32, _P]),
+    "sed_mhsa_bwd_win": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _U32, _P]),
+    "sed_mhsa_win_tiles": (C.c_longlong, [_I, _I, _I, _I]),
     "sed_dwconv_tile": (_I, []),
     "sed_dwconv_nparts": (_I, [_I, _I]),
     "sed_dwconv_glu_fwd_ws_floats": (_Z, [_I, _I, _I]),

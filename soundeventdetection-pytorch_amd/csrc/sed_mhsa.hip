@@ -58,6 +58,24 @@
 // quad shares the counter: every lane makes the call of another query / column step / row step and the words change places inside
 // the quad with DPP quad permutes.  The plain instantiations (DROP = false) are the code they were; a twin called with thr = 0
 // (p = 0) launches the plain instantiation.
+//
+// Local window (the WIN instantiations behind sed_mhsa_fwd_win / sed_mhsa_bwd_win; left, right >= 0, the same for every head): key j
+// takes part for query i iff i - left <= j <= i + right.  lse_i, p_ij and ctx_i run over the in-window keys only, p_ij = 0 outside; in the
+// backward ds_ij = 0 outside, and dv, dq, dk, D_i are built from those.  The diagonal is always inside: no row is empty.  Dropout composes
+// (p~_ij = m_ij s p_ij with p over the window; the counters are indexed by the absolute (b H + g, i, j, step), the same cells dropped).
+//   tiles      mhsa_win_range, one __host__ __device__ helper for the kernels and for sed_mhsa_win_tiles: a wave that owns queries
+//              [q0, q0 + 31] walks the key tiles that meet [q0 - left, q0 + 31 + right] and [0, t); a wave that owns keys [k0, k0 + 31]
+//              (the dK / dV pass) the query tiles that meet [k0 - right, k0 + 31 + left].  The prefetch a tile ahead starts at the first
+//              visited tile.  mhsa_fwd_lds_kernel stages the union of its four waves' ranges (loop bounds and `more` the same in every
+//              thread: the barrier is uniform); a wave computes on the tiles of its own range and stages and waits on the others.
+//   mask       inside a visited tile, by select: forward score -inf; backward p = dS = 0 without taking exp(s - lse) of an out-of-window
+//              cell (lse covers the window only, so that exponential can overflow).
+//   maximum    a query's first visited tiles can lie wholly outside its window (left = 3: queries 32 ... 63 start at key tile 0, where
+//              query 40 has no key); while its running maximum is -inf the reference point of the tile is 0, so alpha and every
+//              probability are exp(-inf) = 0 instead of exp(-inf + inf).
+// The host clamps left and right to t - 1 (nothing overflows; a side that reaches the clip's end from every query is unbounded); both
+// sides unbounded launches the WIN = false instantiation, plain or DROP, which is the code it was.  Ragged tiles, clamped loads, the 2^31
+// limits, no atomics, a fixed order and the same bits on every run as above.
 #include "common.h"
 #include "philox.h"
 #include <math.h>
@@ -160,7 +178,22 @@ struct MhsaParams {
     int t, H, ntile;     // ntile = ceil(t / 128) workgroups per (clip, head)
     float scale;
     DropArgs drop;       // the DROP instantiations only
+    int wl, wr;          // the WIN instantiations only: left and right, clamped to t - 1 by the host
 };
+
+// ---- the local window: the tiles a wave walks --------------------------------------------------------------------------------------
+// A wave (span 32) or a workgroup (span 128) that owns rows [a0, a0 + span - 1], a0 < t, of one index walks the tiles of 32 of the
+// OTHER index that intersect [a0 - before, a0 + span - 1 + after] with [0, t): tile starts lo, lo + 32, ... < hi.  Queries own keys
+// with (before, after) = (left, right), keys own queries with (right, left).  Rows past t widen nothing: the last real row t - 1
+// already reaches t - 1 + after >= t - 1.  before, after <= t - 1 (the host clamps them), so nothing here overflows.
+struct TileRange { int lo, hi; };
+__host__ __device__ inline TileRange mhsa_win_range(int a0, int span, int t, int before, int after) {
+    const int first = a0 - before > 0 ? a0 - before : 0;
+    const int last = a0 + span - 1 + after < t - 1 ? a0 + span - 1 + after : t - 1;
+    return {first & ~(MHSA_QT - 1), last + 1};
+}
+// key j takes part for query i (both inside the clip is the caller's business)
+__device__ __forceinline__ bool in_window(int i, int j, int wl, int wr) { return j >= i - wl && j <= i + wr; }
 
 // store the transposed 32 x 32 tile o (column c = acc_row(i, h) in the registers, row on the lane) times f into row `dst` (head columns)
 __device__ __forceinline__ void store_tile_t(float* __restrict__ dst, const f32x16& o, float f, int h) {
@@ -214,7 +247,7 @@ __device__ __forceinline__ void drop_factors_k(float (&ms)[16], const DropArgs& 
     }
 }
 
-template <typename T, int DH, bool DROP>
+template <typename T, int DH, bool DROP, bool WIN>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
@@ -232,17 +265,18 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
     // the next tile's K rows and V columns are loaded while this tile is computed (registers, no LDS)
     RowFrag<T, DH> kn;
     float vn[DH / 32][16];
-    kn.load(base + C + (r < t ? r : t - 1) * ld, h);
+    const TileRange kt = WIN ? mhsa_win_range(q0, MHSA_QT, t, p.wl, p.wr) : TileRange{0, t};
+    kn.load(base + C + (kt.lo + r < t ? kt.lo + r : t - 1) * ld, h);
 #pragma unroll
-    for (int cb = 0; cb < DH / 32; ++cb) load_col(vn[cb], base + 2 * C + cb * 32 + r, ld, 0, t, h);
-    for (int k0 = 0; k0 < t; k0 += 32) {
+    for (int cb = 0; cb < DH / 32; ++cb) load_col(vn[cb], base + 2 * C + cb * 32 + r, ld, kt.lo, t, h);
+    for (int k0 = kt.lo; k0 < kt.hi; k0 += 32) {
         const RowFrag<T, DH> kf = kn;
         float va[DH / 32][16];
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb)
 #pragma unroll
             for (int i = 0; i < 16; ++i) va[cb][i] = vn[cb][i];
-        if (k0 + 32 < t) {
+        if (k0 + 32 < kt.hi) {
             const int kr = k0 + 32 + r < t ? k0 + 32 + r : t - 1;
             kn.load(base + C + kr * ld, h);
 #pragma unroll
@@ -252,18 +286,23 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
         float mx = -INFINITY;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            s[i] = k0 + acc_row(i, h) < t ? s[i] * p.scale : -INFINITY;
+            const int j = k0 + acc_row(i, h);
+            s[i] = j < t && (!WIN || in_window(q0 + r, j, p.wl, p.wr)) ? s[i] * p.scale : -INFINITY;
             mx = fmaxf(mx, s[i]);
         }
         mx = fmaxf(mx, xor32(mx));
-        const float mn = fmaxf(m, mx);                 // finite from the first tile on: key k0 is always inside the clip
+        // plain: finite from the first tile on (key k0 is always inside the clip).  WIN: a query's first visited tiles can lie wholly
+        // left of its window (left = 3, queries 32 ... 63 start at key tile 0, where query 40 has no key): the maximum is still -inf
+        // there, and the reference point 0 makes alpha and every probability exp(-inf) = 0 instead of exp(-inf + inf)
+        const float mx2 = fmaxf(m, mx);
+        const float mn = WIN && mx2 == -INFINITY ? 0.f : mx2;
         const float alpha = expf(m - mn);
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) { s[i] = expf(s[i] - mn); sum += s[i]; }
         sum += xor32(sum);
         l = l * alpha + sum;
-        m = mn;
+        m = WIN ? mx2 : mn;
         if (DROP) drop_scores_t(s, p.drop, k0, q0 + r, bh, h);
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) {
@@ -286,7 +325,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
 // A fragments) and V transposed (Vt[c][key], pitch 36: a lane's eight keys of a k-step are two 8-byte reads) into one of two LDS
 // buffers, one barrier per tile.  Same values, same MFMA order and so the same bits as the register-fed kernel above, which the fp32
 // mode keeps; waves whose 32 queries lie past the clip take part in the staging and the barriers only.
-template <int DH, bool DROP>
+template <int DH, bool DROP, bool WIN>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParams p) {
     constexpr int KP = DH + 8, VP = 36, NL = DH / 32, RQ = DH / 4;       // NL 16-byte loads of K and of V per thread and tile
     __shared__ __attribute__((aligned(16))) bf16_t ks[2][32 * KP];
@@ -327,14 +366,18 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParam
 #pragma unroll
     for (int cb = 0; cb < NL; ++cb) o[cb] = (f32x16){};
     float m = -INFINITY, l = 0.f;
-    gload(0);
+    // WIN: the workgroup stages the union of its waves' ranges (the range of its 128 queries: wg, the same in every thread); a wave
+    // computes on the tiles of its own range (mine) and only stages and waits on the others
+    const TileRange wg = WIN ? mhsa_win_range(tile * MHSA_WAVES * MHSA_QT, MHSA_WAVES * MHSA_QT, t, p.wl, p.wr) : TileRange{0, t};
+    const TileRange mine = WIN && active ? mhsa_win_range(q0, MHSA_QT, t, p.wl, p.wr) : TileRange{0, t};
+    gload(wg.lo);
     lstore(0);
     __syncthreads();
-    for (int k0 = 0, it = 0; k0 < t; k0 += 32, ++it) {
+    for (int k0 = wg.lo, it = 0; k0 < wg.hi; k0 += 32, ++it) {
         const int cur = it & 1;
-        const bool more = k0 + 32 < t;                 // (the same in every thread: the barrier below is uniform)
+        const bool more = k0 + 32 < wg.hi;             // (the same in every thread: the barrier below is uniform)
         if (more) gload(k0 + 32);
-        if (active) {
+        if (active && (!WIN || (k0 >= mine.lo && k0 < mine.hi))) {
             RowFrag<bf16_t, DH> kf;
 #pragma unroll
             for (int s = 0; s < DH / 16; ++s) kf.f[s] = *reinterpret_cast<const bf16x8*>(&ks[cur][r * KP + 16 * s + 8 * h]);
@@ -342,18 +385,20 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParam
             float mx = -INFINITY;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                s[i] = k0 + acc_row(i, h) < t ? s[i] * p.scale : -INFINITY;
+                const int j = k0 + acc_row(i, h);
+                s[i] = j < t && (!WIN || in_window(q0 + r, j, p.wl, p.wr)) ? s[i] * p.scale : -INFINITY;
                 mx = fmaxf(mx, s[i]);
             }
             mx = fmaxf(mx, xor32(mx));
-            const float mn = fmaxf(m, mx);
+            const float mx2 = fmaxf(m, mx);
+            const float mn = WIN && mx2 == -INFINITY ? 0.f : mx2;      // (as in mhsa_fwd_kernel: no key of this query yet)
             const float alpha = expf(m - mn);
             float sum = 0.f;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { s[i] = expf(s[i] - mn); sum += s[i]; }
             sum += xor32(sum);
             l = l * alpha + sum;
-            m = mn;
+            m = WIN ? mx2 : mn;
             if (DROP) drop_scores_t(s, p.drop, k0, q0 + r, bh, h);
 #pragma unroll
             for (int cb = 0; cb < NL; ++cb) {
@@ -404,7 +449,7 @@ __global__ __launch_bounds__(256) void mhsa_rowdot_kernel(MhsaParams p, int B, i
 }
 
 // pass 2 of the backward: the wave owns 32 keys (on the lane) and loops over the query tiles -> dK, dV
-template <typename T, int DH, bool DROP>
+template <typename T, int DH, bool DROP, bool WIN>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
@@ -437,8 +482,12 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
             Dn[i] = D[qc];
         }
     };
-    load_rows(0);
-    for (int q0 = 0; q0 < t; q0 += 32) {
+    const TileRange qt = WIN ? mhsa_win_range(k0, MHSA_QT, t, p.wr, p.wl) : TileRange{0, t};
+    // WIN: p and dS of a cell outside the window (or the clip) are 0 by select; exp(s - lse) is not taken there (lse covers the window
+    // only, so it can overflow)
+    auto live = [&](int q) { return q < t && (!WIN || (k0 + r < t && in_window(q, k0 + r, p.wl, p.wr))); };
+    load_rows(qt.lo);
+    for (int q0 = qt.lo; q0 < qt.hi; q0 += 32) {
         const RowFrag<T, DH> qf = qn, df = dn;
         float lc[16], Dc[16], qa[DH / 32][16], da[DH / 32][16];
 #pragma unroll
@@ -448,7 +497,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
             load_col(da[cb], dbase + cb * 32 + r, C, q0, t, h);
             load_col(qa[cb], base + cb * 32 + r, ld, q0, t, h);
         }
-        if (q0 + 32 < t) load_rows(q0 + 32);
+        if (q0 + 32 < qt.hi) load_rows(q0 + 32);
         f32x16 s = mm_rows<T, DH>(qf, kf);             // s[query][key]
         f32x16 dp = mm_rows<T, DH>(df, vf);
         if (DROP) {
@@ -456,16 +505,18 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
             drop_factors_k(ms, p.drop, k0 + r, q0, bh, h);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const float pr = q0 + acc_row(i, h) < t ? expf(s[i] * p.scale - lc[i]) : 0.f;
+                const bool in = live(q0 + acc_row(i, h));
+                const float pr = in ? expf(s[i] * p.scale - lc[i]) : 0.f;
                 s[i] = pr * ms[i];                       // p~ for dV
-                dp[i] = pr * (dp[i] * ms[i] - Dc[i]);
+                dp[i] = !WIN || in ? pr * (dp[i] * ms[i] - Dc[i]) : 0.f;
             }
         } else {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const float pr = q0 + acc_row(i, h) < t ? expf(s[i] * p.scale - lc[i]) : 0.f;
+                const bool in = live(q0 + acc_row(i, h));
+                const float pr = in ? expf(s[i] * p.scale - lc[i]) : 0.f;
                 s[i] = pr;
-                dp[i] = pr * (dp[i] - Dc[i]);
+                dp[i] = !WIN || in ? pr * (dp[i] - Dc[i]) : 0.f;
             }
         }
 #pragma unroll
@@ -485,7 +536,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
 }
 
 // pass 3: the wave owns 32 queries (on the lane) and loops over the key tiles -> dQ
-template <typename T, int DH, bool DROP>
+template <typename T, int DH, bool DROP, bool WIN>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
@@ -509,13 +560,14 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
         kn.load(base + C + kr * ld, h);
         vn.load(base + 2 * C + kr * ld, h);
     };
-    load_rows(0);
-    for (int k0 = 0; k0 < t; k0 += 32) {
+    const TileRange kt = WIN ? mhsa_win_range(q0, MHSA_QT, t, p.wl, p.wr) : TileRange{0, t};
+    load_rows(kt.lo);
+    for (int k0 = kt.lo; k0 < kt.hi; k0 += 32) {
         const RowFrag<T, DH> kf = kn, vf = vn;
         float ka[DH / 32][16];
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) load_col(ka[cb], base + C + cb * 32 + r, ld, k0, t, h);
-        if (k0 + 32 < t) load_rows(k0 + 32);
+        if (k0 + 32 < kt.hi) load_rows(k0 + 32);
         f32x16 s = mm_rows<T, DH>(kf, qf);             // s[key][query]
         f32x16 dp = mm_rows<T, DH>(vf, df);
         if (DROP) {
@@ -526,8 +578,10 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const float pr = k0 + acc_row(i, h) < t ? expf(s[i] * p.scale - lse) : 0.f;
-            dp[i] = pr * (dp[i] - Dq);
+            const int j = k0 + acc_row(i, h);
+            const bool in = j < t && (!WIN || (q0 + r < t && in_window(q0 + r, j, p.wl, p.wr)));   // (select: see mhsa_bwd_kv_kernel)
+            const float pr = in ? expf(s[i] * p.scale - lse) : 0.f;
+            dp[i] = !WIN || in ? pr * (dp[i] - Dq) : 0.f;
         }
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) MmAx<T>::run(dq[cb], ka[cb], dp);
@@ -728,8 +782,10 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
 namespace {
-template <bool DROP>
-int mhsa_fwd_launch(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, const DropArgs& drop, void* stream) {
+// wl, wr: the window, already clamped to [0, t - 1] (WIN only)
+template <bool DROP, bool WIN = false>
+int mhsa_fwd_launch(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, const DropArgs& drop, void* stream,
+                    int wl = 0, int wr = 0) {
     long long nb; int ntile;
     if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
     SED_REQUIRE(qkv != nullptr && ctx != nullptr, "qkv and ctx are required");
@@ -737,14 +793,15 @@ int mhsa_fwd_launch(int dtype, const float* qkv, float* ctx, float* lse, int B, 
     MhsaParams p = {};
     p.qkv = qkv; p.out = ctx; p.lse_out = lse; p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
     p.drop = drop;
+    p.wl = wl; p.wr = wr;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
     if (dtype == SED_BF16) {
-        if (dh == 32) mhsa_fwd_lds_kernel<32, DROP><<<grid, block, 0, st>>>(p);
-        else mhsa_fwd_lds_kernel<64, DROP><<<grid, block, 0, st>>>(p);
+        if (dh == 32) mhsa_fwd_lds_kernel<32, DROP, WIN><<<grid, block, 0, st>>>(p);
+        else mhsa_fwd_lds_kernel<64, DROP, WIN><<<grid, block, 0, st>>>(p);
     } else {
-        if (dh == 32) mhsa_fwd_kernel<float, 32, DROP><<<grid, block, 0, st>>>(p);
-        else mhsa_fwd_kernel<float, 64, DROP><<<grid, block, 0, st>>>(p);
+        if (dh == 32) mhsa_fwd_kernel<float, 32, DROP, WIN><<<grid, block, 0, st>>>(p);
+        else mhsa_fwd_kernel<float, 64, DROP, WIN><<<grid, block, 0, st>>>(p);
     }
     SED_LAUNCH_CHECK();
     return 0;
@@ -770,6 +827,38 @@ extern "C" int sed_mhsa_fwd_drop(int dtype, const float* qkv, float* ctx, float*
     return mhsa_fwd_launch<true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream);
 }
 
+// the windowed entry: one for plain and dropout (p = 0: no dropout, rng may be NULL).  The sides are clamped to t - 1 (a side that
+// reaches the clip's end from every query is unbounded); both unbounded is the attention above and launches its instantiation
+#define SED_WIN_ARGS(left, right, p, rng, stream_id, out)                                                        \
+    SED_REQUIRE((left) >= 0 && (right) >= 0, "the window sides left and right must be >= 0");                    \
+    SED_REQUIRE(drop_host_args((p), (rng), (stream_id), &(out)), "the dropout probability must lie in [0, 1)");  \
+    SED_REQUIRE((out).thr == 0 || (rng) != nullptr, "the dropout state rng is required when p > 0")
+
+extern "C" int sed_mhsa_fwd_win(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, int left, int right,
+                                float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
+    DropArgs d;
+    SED_WIN_ARGS(left, right, p, rng, stream_id, d);
+    const int cap = t > 0 ? t - 1 : 0, wl = left < cap ? left : cap, wr = right < cap ? right : cap;
+    if (wl == cap && wr == cap) {
+        if (d.thr == 0) return mhsa_fwd_launch<false>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream);
+        return mhsa_fwd_launch<true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream);
+    }
+    if (d.thr == 0) return mhsa_fwd_launch<false, true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream, wl, wr);
+    return mhsa_fwd_launch<true, true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream, wl, wr);
+}
+
+// tiles of 32 x 32 per (clip, head) on which a wave of the pass issues MFMAs: the sum of mhsa_win_range over the waves
+extern "C" long long sed_mhsa_win_tiles(int t, int left, int right, int pass) {
+    if (t <= 0 || left < 0 || right < 0 || pass < 0 || pass > 2) return -1;
+    const int wl = left < t - 1 ? left : t - 1, wr = right < t - 1 ? right : t - 1;
+    long long n = 0;
+    for (int a0 = 0; a0 < t; a0 += MHSA_QT) {
+        const TileRange rg = pass == 1 ? mhsa_win_range(a0, MHSA_QT, t, wr, wl) : mhsa_win_range(a0, MHSA_QT, t, wl, wr);
+        n += (rg.hi - rg.lo + MHSA_QT - 1) / MHSA_QT;
+    }
+    return n;
+}
+
 extern "C" size_t sed_mhsa_bwd_ws_floats(int B, int t, int H, int dh) {
     (void)dh;
     if (B <= 0 || t <= 0 || H <= 0) return 0;
@@ -777,9 +866,9 @@ extern "C" size_t sed_mhsa_bwd_ws_floats(int B, int t, int H, int dh) {
 }
 
 namespace {
-template <bool DROP>
+template <bool DROP, bool WIN = false>
 int mhsa_bwd_launch(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
-                    float* workspace, int B, int t, int H, int dh, const DropArgs& drop, void* stream) {
+                    float* workspace, int B, int t, int H, int dh, const DropArgs& drop, void* stream, int wl = 0, int wr = 0) {
     long long nb; int ntile;
     if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
     SED_REQUIRE(qkv != nullptr && ctx != nullptr && dctx != nullptr && lse != nullptr && dqkv != nullptr && workspace != nullptr,
@@ -789,16 +878,17 @@ int mhsa_bwd_launch(int dtype, const float* qkv, const float* ctx, const float* 
     p.qkv = qkv; p.ctx = ctx; p.dctx = dctx; p.lse = lse; p.out = dqkv; p.D = workspace;
     p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
     p.drop = drop;
+    p.wl = wl; p.wr = wr;
     hipStream_t st = (hipStream_t)stream;
     mhsa_rowdot_kernel<<<(unsigned)cdivz((size_t)B * t * H, 256), 256, 0, st>>>(p, B, dh);
     SED_LAUNCH_CHECK();
     const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
     if (dtype == SED_BF16) {
-        if (dh == 32) { mhsa_bwd_kv_kernel<bf16_t, 32, DROP><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 32, DROP><<<grid, block, 0, st>>>(p); }
-        else { mhsa_bwd_kv_kernel<bf16_t, 64, DROP><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 64, DROP><<<grid, block, 0, st>>>(p); }
+        if (dh == 32) { mhsa_bwd_kv_kernel<bf16_t, 32, DROP, WIN><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 32, DROP, WIN><<<grid, block, 0, st>>>(p); }
+        else { mhsa_bwd_kv_kernel<bf16_t, 64, DROP, WIN><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 64, DROP, WIN><<<grid, block, 0, st>>>(p); }
     } else {
-        if (dh == 32) { mhsa_bwd_kv_kernel<float, 32, DROP><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 32, DROP><<<grid, block, 0, st>>>(p); }
-        else { mhsa_bwd_kv_kernel<float, 64, DROP><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 64, DROP><<<grid, block, 0, st>>>(p); }
+        if (dh == 32) { mhsa_bwd_kv_kernel<float, 32, DROP, WIN><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 32, DROP, WIN><<<grid, block, 0, st>>>(p); }
+        else { mhsa_bwd_kv_kernel<float, 64, DROP, WIN><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 64, DROP, WIN><<<grid, block, 0, st>>>(p); }
     }
     SED_LAUNCH_CHECK();
     return 0;
@@ -817,6 +907,20 @@ extern "C" int sed_mhsa_bwd_drop(int dtype, const float* qkv, const float* ctx, 
     SED_DROP_ARGS(p, rng, stream_id, d);
     if (d.thr == 0) return mhsa_bwd_launch<false>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
     return mhsa_bwd_launch<true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
+}
+
+extern "C" int sed_mhsa_bwd_win(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
+                                float* workspace, int B, int t, int H, int dh, int left, int right, float p, const uint32_t* rng,
+                                uint32_t stream_id, void* stream) {
+    DropArgs d;
+    SED_WIN_ARGS(left, right, p, rng, stream_id, d);
+    const int cap = t > 0 ? t - 1 : 0, wl = left < cap ? left : cap, wr = right < cap ? right : cap;
+    if (wl == cap && wr == cap) {
+        if (d.thr == 0) return mhsa_bwd_launch<false>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
+        return mhsa_bwd_launch<true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
+    }
+    if (d.thr == 0) return mhsa_bwd_launch<false, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr);
+    return mhsa_bwd_launch<true, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr);
 }
 
 namespace {

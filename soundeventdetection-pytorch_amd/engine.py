@@ -229,7 +229,7 @@ class CnnEngine(OptimizerExtMixin):
                  precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
                  mel_bins: Optional[int] = None, attention: bool = False, sa_heads: int = 4, pos_encoding: bool = True,
                  sa_layers: int = 1, sa_ffn: int = 0, sa_activation: str = "relu", sa_conv_kernel: int = 0,
-                 sa_dropout: float = 0.0, sa_dropout_seed: Optional[int] = None):
+                 sa_dropout: float = 0.0, sa_dropout_seed: Optional[int] = None, sa_window=None):
         """attention: a second linear layer att_fc beside event_fc scores every frame per class (csrc/sed_attn.hip): forward()
         also leaves the attention logits in plan.att, loss_and_grad(weak=("att", ...)) pools with them and backward() then takes
         both layers.  False launches exactly what it always did.
@@ -243,6 +243,10 @@ class CnnEngine(OptimizerExtMixin):
         the attention probabilities, each sub-layer's output before its residual add, the FFN hidden activation -- with masks generated
         inside the kernels from the counter-based state drop_state = (seed_lo, seed_hi, step, 0) (csrc/philox.h); sa_dropout_seed:
         the 64-bit seed, None -> torch.initial_seed() (no random number is drawn).  p = 0 launches what it always did.
+        sa_window = None, an int w or a pair (left, right), None on a side for unbounded: the local attention window of every head of
+        every layer (key j takes part for query i iff i - left <= j <= i + right; torch's src_mask), in every forward and backward --
+        sed_mhsa_fwd_win / sed_mhsa_bwd_win in the places of the plain / _drop core launches, no new buffers.  None launches what it
+        always did.
         or 'none' (a bare stack of ConvBlocks: forward() stops at the last pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
         Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and backward() also produces the input gradient
         plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path keeps the dedicated Cin = 1
@@ -265,6 +269,11 @@ class CnnEngine(OptimizerExtMixin):
         if head != "sa" and (self.sa_dropout or sa_dropout_seed is not None):
             raise ValueError("sa_dropout / sa_dropout_seed belong to the self-attention head (head='sa')")
         self.sa_dropout_seed = (torch.initial_seed() if sa_dropout_seed is None else int(sa_dropout_seed)) & 0xFFFFFFFFFFFFFFFF
+        self.sa_window = self.check_sa_window(sa_window)
+        if head != "sa" and self.sa_window is not None:
+            raise ValueError("sa_window belongs to the self-attention head (head='sa')")
+        # the sides as the C entries take them
+        self._win = None if self.sa_window is None else tuple(L.WIN_UNBOUNDED if v is None else min(v, L.WIN_UNBOUNDED) for v in self.sa_window)
         self._drop_state = None              # (4,) int32 on the device holding the uint32 words, made with the first plan (on its device)
         self._drop_dev = "cuda"
         self._drop_host = [self.sa_dropout_seed & 0xFFFFFFFF, self.sa_dropout_seed >> 32, 0, 0]
@@ -323,6 +332,25 @@ class CnnEngine(OptimizerExtMixin):
         if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) < 1.0:
             raise ValueError(f"sa_dropout must be a probability in [0, 1), got {p!r}")
         return float(p)
+
+    @staticmethod
+    def check_sa_window(w):
+        """None, an int w >= 0 (left = right = w) or a pair (left, right) of ints >= 0 / None (unbounded) -> None or the pair"""
+        def side(v):
+            if v is None:
+                return None
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"a side of sa_window must be None (unbounded) or an integer >= 0, got {v!r}")
+            return v
+        if w is None:
+            return None
+        if isinstance(w, (tuple, list)):
+            if len(w) != 2:
+                raise ValueError(f"sa_window must be None, an integer or a pair (left, right), got {w!r}")
+            return side(w[0]), side(w[1])
+        if isinstance(w, bool) or not isinstance(w, int):
+            raise ValueError(f"sa_window must be None, an integer or a pair (left, right), got {w!r}")
+        return side(w), side(w)
 
     # ---- the dropout state: (seed_lo, seed_hi, step, 0), uint32 words in an int32 device tensor ---------------------------------
     @property
@@ -887,7 +915,11 @@ class CnnEngine(OptimizerExtMixin):
             an, nn_, fn, fnn = self.sa_layer_names(l)
             self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(xin), C, L.ptr(P[an + ".in_proj_weight"]), C, L.ptr(P[an + ".in_proj_bias"]),
                     L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
-            if drop:
+            if self._win is not None:
+                self._k("sed_mhsa_fwd_win", lib.sed_mhsa_fwd_win, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]),
+                        L.ptr(ly["lse"]) if training or drop else None, B, t, Hh, C // Hh, self._win[0], self._win[1], drop,
+                        L.ptr(g["rng"]) if drop else None, 8 * l + 0, st)
+            elif drop:
                 self._k("sed_mhsa_fwd_drop", lib.sed_mhsa_fwd_drop, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(ly["lse"]),
                         B, t, Hh, C // Hh, drop, L.ptr(g["rng"]), 8 * l + 0, st)
             else:
@@ -985,7 +1017,11 @@ class CnnEngine(OptimizerExtMixin):
             self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[an + ".out_proj.weight"]), C, L.ptr(g["woT"]), C, C, C, C, 0, st)
             self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ga), C, L.ptr(g["woT"]), C, None, L.ptr(g["dctx"]), C, R, C, C, 1,
                     None, st)
-            if drop:
+            if self._win is not None:
+                self._k("sed_mhsa_bwd_win", lib.sed_mhsa_bwd_win, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
+                        L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, self._win[0], self._win[1], drop,
+                        L.ptr(g["rng"]) if drop else None, 8 * l + 0, st)
+            elif drop:
                 self._k("sed_mhsa_bwd_drop", lib.sed_mhsa_bwd_drop, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
                         L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, drop, L.ptr(g["rng"]), 8 * l + 0, st)
             else:

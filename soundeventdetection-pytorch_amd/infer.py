@@ -143,7 +143,8 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
         layers, ffn, act = Csa_AvgPooling.encoder_config_from_state_dict(weights)      # (1, 0, relu) for a one-layer checkpoint
         model = Csa_AvgPooling(cfg.classes_num, model_config=model_config, sa_heads=heads, pos_encoding=pos, mel_bins=n_mel,
                                frontend=frontend, attention=attention, sa_layers=layers, sa_ffn=ffn, sa_activation=act,
-                               sa_conv_kernel=Csa_AvgPooling.conv_config_from_state_dict(weights)).to(dev)      # (0: no conv_config)
+                               sa_conv_kernel=Csa_AvgPooling.conv_config_from_state_dict(weights),      # (0: no conv_config)
+                               sa_window=Csa_AvgPooling.window_config_from_state_dict(weights)).to(dev)  # (None: no window_config)
     else:
         model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend,
                                attention=attention).to(dev)

@@ -133,7 +133,28 @@ def build_weak_parser():
                         "every sub-layer's output before its residual add, the FFN hidden activation); 0 drops nothing")
     p.add_argument("--sa_dropout_seed", type=int, default=None,
                    help="--sa_dropout: the 64-bit seed of the counter-based masks (default: torch's initial seed)")
+    p.add_argument("--sa_window", type=str, default=None, metavar="L[:R]",
+                   help="--self_attention: local attention window of every encoder layer -- a frame attends to the L frames before it and "
+                        "the R frames after it (one number: L = R; inf: that side unbounded; 64:0 is causal attention with a look-back "
+                        "of 64 frames); default: every frame attends to every frame")
     return p
+
+
+def parse_sa_window(text):
+    """--sa_window L[:R] -> None or (left, right), None for a side given as inf; a ValueError for anything else"""
+    if text is None:
+        return None
+    def side(v):
+        v = v.strip().lower()
+        if v == "inf":
+            return None
+        if not v.isdigit():
+            raise ValueError(f"--sa_window takes L or L:R with non-negative integers or inf, got {text!r}")
+        return int(v)
+    parts = str(text).split(":")
+    if len(parts) > 2:
+        raise ValueError(f"--sa_window takes L or L:R with non-negative integers or inf, got {text!r}")
+    return side(parts[0]), side(parts[-1])
 
 
 def build_semi_parser():
@@ -369,7 +390,8 @@ def get_spectogram_dataset_model_and_criterion(args, device):
                                sa_layers=int(getattr(args, "sa_layers", 1)), sa_ffn=int(getattr(args, "sa_ffn", 0)),
                                sa_activation=getattr(args, "sa_activation", "relu"),
                                sa_conv_kernel=int(getattr(args, "sa_conv_kernel", 0)),
-                               sa_dropout=float(getattr(args, "sa_dropout", 0.0)), sa_dropout_seed=getattr(args, "sa_dropout_seed", None))
+                               sa_dropout=float(getattr(args, "sa_dropout", 0.0)), sa_dropout_seed=getattr(args, "sa_dropout_seed", None),
+                               sa_window=parse_sa_window(getattr(args, "sa_window", None)))
     else:
         model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend, attention=att)
     model.set_precision(args.precision)
@@ -455,6 +477,7 @@ def validate_args(args):
         check_sa_encoder(128, getattr(args, "sa_layers", 1), getattr(args, "sa_ffn", 0), getattr(args, "sa_activation", "relu"))
         from .engine import CnnEngine
         CnnEngine.check_sa_dropout(getattr(args, "sa_dropout", 0.0))
+        parse_sa_window(getattr(args, "sa_window", None))
     elif getattr(args, "sa_heads", 4) != 4 or getattr(args, "no_pos_encoding", False):
         raise ValueError("--sa_heads / --no_pos_encoding configure the self-attention head: they need --self_attention")
     elif getattr(args, "sa_layers", 1) != 1 or getattr(args, "sa_ffn", 0) != 0 or getattr(args, "sa_activation", "relu") != "relu":
@@ -463,6 +486,8 @@ def validate_args(args):
         raise ValueError("--sa_conv_kernel configures the self-attention head: it needs --self_attention")
     elif getattr(args, "sa_dropout", 0.0) != 0.0 or getattr(args, "sa_dropout_seed", None) is not None:
         raise ValueError("--sa_dropout / --sa_dropout_seed configure the self-attention head: they need --self_attention")
+    elif getattr(args, "sa_window", None) is not None:
+        raise ValueError("--sa_window configures the self-attention head: it needs --self_attention")
     for flag, value in (("--weak_pooling", weak_options(args).get("weak_pooling")), ("--eval_clip_pooling", getattr(args, "eval_clip_pooling", None))):
         if value == "att" and not att_head:
             raise ValueError(f"{flag} att pools with the attention head: it needs --attention_head")

@@ -528,15 +528,26 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     engine.drop_state = (seed_lo, seed_hi, step, 0) (csrc/philox.h; tests/dropout_formula.py reproduces every cell); every training
     forward advances the step word by one.  The seed is sa_dropout_seed, or torch.initial_seed() when None: no random number is
     drawn, no parameter or buffer is added, and eval-mode forwards and backwards never drop.  p = 0 (the default) changes nothing.
-    Refused: sa_dropout outside [0, 1), C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0, sa_layers < 1, sa_ffn not 0 or a multiple of 32 up to
+    sa_window = None, an int w (left = right = w) or a pair (left, right) with None for an unbounded side: the local attention window
+    of every head of every layer -- key j of the same clip takes part for query i iff i - left <= j <= i + right, which is
+    torch.nn.TransformerEncoderLayer(src, src_mask=M) with M[i][j] = True where j < i - left or j > i + right; (left, 0) is causal
+    attention with a look-back of left.  The softmax runs over the in-window keys only (the diagonal is always inside: no empty row)
+    and the kernels skip the key tiles outside it (sed_mhsa_fwd_win / sed_mhsa_bwd_win, csrc/sed_mhsa.hip).  The window is
+    architecture, not regularisation: it holds in training and eval forwards and in every backward, and dropout composes with it
+    (the same cells dropped, p over the window).  Only the attention is windowed: the convolution module and the CNN keep their
+    receptive fields.  A float64 buffer window_config = (left, right), -1 for an unbounded side, exists only when a window is set
+    (window_config_from_state_dict returns None without it); with sa_window = None the draws, the state_dict keys, the launches and
+    the output bits are those of a model without the argument.
+    Refused: a negative or non-integer sa_window side, sa_dropout outside [0, 1), C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0, sa_layers < 1, sa_ffn not 0 or a multiple of 32 up to
     4096 (and C > 512 with it), an activation other than relu / gelu, sa_conv_kernel even, below 3 or above 31 (before any draw)."""
 
     ACTIVATIONS = ("relu", "gelu")
 
     def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, sa_heads=4, pos_encoding=True,
                  mel_bins=None, frontend=None, attention=False, sa_layers=1, sa_ffn=0, sa_activation="relu", sa_conv_kernel=0,
-                 sa_dropout=0.0, sa_dropout_seed=None):
+                 sa_dropout=0.0, sa_dropout_seed=None, sa_window=None):
         self.sa_dropout = CnnEngine.check_sa_dropout(sa_dropout)          # (before any draw)
+        self.sa_window = CnnEngine.check_sa_window(sa_window)
         self.sa_dropout_seed = None if sa_dropout_seed is None else int(sa_dropout_seed)
         check_sa_geometry(int(model_config[-1][0]), sa_heads)
         check_sa_encoder(int(model_config[-1][0]), sa_layers, sa_ffn, sa_activation)
@@ -564,13 +575,15 @@ class Csa_AvgPooling(Cnn_AvgPooling):
         if self.sa_layers > 1 or self.sa_ffn:
             self.register_buffer("encoder_config", torch.tensor([float(self.sa_layers), float(self.sa_ffn),
                                                                  float(self.ACTIVATIONS.index(self.sa_activation))], dtype=torch.float64))
+        if self.sa_window is not None:
+            self.register_buffer("window_config", torch.tensor([-1.0 if v is None else float(v) for v in self.sa_window], dtype=torch.float64))
         self.event_fc = _LinearParams(c_last, classes_num)
 
     def _make_engine(self, precision):
         return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="sa", sa_heads=self.sa_heads,
                          pos_encoding=self.pos_encoding, mel_bins=self.mel_bins, attention=self.attention, sa_layers=self.sa_layers,
                          sa_ffn=self.sa_ffn, sa_activation=self.sa_activation, sa_conv_kernel=self.sa_conv_kernel,
-                         sa_dropout=self.sa_dropout, sa_dropout_seed=self.sa_dropout_seed)
+                         sa_dropout=self.sa_dropout, sa_dropout_seed=self.sa_dropout_seed, sa_window=self.sa_window)
 
     def _flush_counters(self):
         """The convolution modules' BatchNorm counters follow the conv blocks': counted on the host, folded in when looked at."""
@@ -586,6 +599,14 @@ class Csa_AvgPooling(Cnn_AvgPooling):
         if "conv_config" not in weights:
             return 0
         return int(round(weights["conv_config"].detach().cpu().double().tolist()[0]))
+
+    @staticmethod
+    def window_config_from_state_dict(weights):
+        """sa_window = (left, right), None for an unbounded side, from a state_dict's window_config; None when the buffer is absent"""
+        if "window_config" not in weights:
+            return None
+        cfg = weights["window_config"].detach().cpu().double().tolist()
+        return tuple(None if v < 0 else int(round(v)) for v in cfg[:2])
 
     @staticmethod
     def conv_module_state(weights, layer):
