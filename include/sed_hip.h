@@ -1172,6 +1172,39 @@ int sed_mhsa_bwd_win(int dtype, const float* qkv, const float* ctx, const float*
                      uint32_t stream_id, void* stream);
 long long sed_mhsa_win_tiles(int t, int left, int right, int pass);
 
+/* ---- learned relative-position bias of the self-attention head (the REL instantiations in csrc/sed_mhsa.hip) ---------------------
+ * Per head g a table over the distance d = j - i (key minus query, frames of the same clip), rel[g][d + t - 1], d in [-(t-1), t-1],
+ * fp32, [H][2t - 1]:
+ *     s_ij = scale * q_i . k_j + rel[g][(j - i) + t - 1]
+ * and everything downstream as in the windowed entries: lse, p and ctx over the in-window keys, dropout on p, cells outside the
+ * window -inf / 0 by select.  Backward: ds_ij is the gradient of the biased score (as before), dq and dk carry `scale`, and
+ *     drel[g][d + t - 1] = sum_b sum_{(i, j) in the window, j - i = d} ds_ij              (no `scale`)
+ * The kernels never see buckets.  sed_relpos_expand builds the table from a learned w[H][nb] and an int32 map over the 2t - 1
+ * distances (rel[g][x] = w[g][map[x]], a bit copy, one small launch), sed_relpos_fold folds the table's gradient back:
+ * dw[g][n] = sum_{x: map[x] = n} drel[g][x] in fp64, ascending x, rounded once; a bucket no distance maps to gets exact 0.
+ * sed_mhsa_fwd_rel / _bwd_rel: the argument lists of the _win entries and, before the stream, `const float* rel` (and `float* drel`).
+ * They always launch the windowed kernels (both sides unbounded is a valid window; p = 0 is no dropout).  A wave stages the slice
+ * of its head's table that its tile walk can reach in LDS -- (visited keys + 31) floats, 256 visited rows (8 tiles) at a time, one
+ * coalesced load of 5 floats per lane and chunk instead of 16 scattered loads per lane and tile -- and adds it after the scaling in the forward and in both backward passes.  drel: the dQ pass reduces every visited
+ * 32 x 32 tile of ds along its 63 diagonals with lane exchanges in a fixed order, carries the upper half of the diagonals to the
+ * next tile in a register and stores per-wave partials; a last launch sums them over the waves and clips in fp64 in a fixed order
+ * and rounds once.  No atomics, the same bits on every run.  Cells outside the window, the clip or t contribute exact 0 and no
+ * exponential is taken there.  A zero table gives the _win kernels' ctx, lse and dqkv bits.
+ * The backward's workspace is sed_mhsa_bwd_rel_ws_floats(B, t, H, dh, left, right) floats (0 for sizes the entries refuse).
+ * sed_relpos_map_check(map on the HOST, nb, t): 0 iff every one of the 2t - 1 entries lies in [0, nb) -- to be called when the map
+ * is built; the kernels do not validate it (the expand kernel clamps its read, so a bad map cannot read outside w).
+ * Refused (non-zero, nothing launched, outputs untouched): whatever sed_mhsa_fwd_win / _bwd_win refuse; rel or drel NULL or not
+ * 4-byte aligned; expand / fold: a NULL or misaligned pointer, H outside [1, 65535], nb outside [1, 4096], t outside [1, 2^30).  */
+int sed_mhsa_fwd_rel(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, int left, int right, float p,
+                     const uint32_t* rng, uint32_t stream_id, const float* rel, void* stream);
+size_t sed_mhsa_bwd_rel_ws_floats(int B, int t, int H, int dh, int left, int right);
+int sed_mhsa_bwd_rel(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
+                     float* workspace, int B, int t, int H, int dh, int left, int right, float p, const uint32_t* rng,
+                     uint32_t stream_id, const float* rel, float* drel, void* stream);
+int sed_relpos_map_check(const int* map_host, int nb, int t);
+int sed_relpos_expand(const float* w, const int* map, float* rel, int H, int nb, int t, void* stream);
+int sed_relpos_fold(const float* drel, const int* map, float* dw, int H, int nb, int t, void* stream);
+
 /* ---- Conformer convolution module of the self-attention head (csrc/sed_convmod.hip) ------------
  * Between the attention and the feed-forward sub-layer: pointwise Conv1d(C, 2C, 1) -> GLU -> depthwise Conv1d(C, C, k, padding
  * (k-1)/2, groups=C) -> BatchNorm1d(C) -> SiLU -> pointwise Conv1d(C, C, 1).  The pointwise convolutions are sed_gemm_nt launches, the

@@ -191,6 +191,13 @@ PROTOTYPES = {
     "sed_mhsa_fwd_win": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _U32, _P]),
     "sed_mhsa_bwd_win": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _U32, _P]),
     "sed_mhsa_win_tiles": (C.c_longlong, [_I, _I, _I, _I]),
+    # the relative-position bias: the windowed entry's arguments + (const float* rel[, float* drel]) before the stream
+    "sed_mhsa_fwd_rel": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _U32, _P, _P]),
+    "sed_mhsa_bwd_rel_ws_floats": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "sed_mhsa_bwd_rel": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _U32, _P, _P, _P]),
+    "sed_relpos_map_check": (_I, [_P, _I, _I]),
+    "sed_relpos_expand": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "sed_relpos_fold": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "sed_dwconv_tile": (_I, []),
     "sed_dwconv_nparts": (_I, [_I, _I]),
     "sed_dwconv_glu_fwd_ws_floats": (_Z, [_I, _I, _I]),

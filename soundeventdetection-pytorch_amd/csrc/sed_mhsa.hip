@@ -76,6 +76,20 @@
 // The host clamps left and right to t - 1 (nothing overflows; a side that reaches the clip's end from every query is unbounded); both
 // sides unbounded launches the WIN = false instantiation, plain or DROP, which is the code it was.  Ragged tiles, clamped loads, the 2^31
 // limits, no atomics, a fixed order and the same bits on every run as above.
+//
+// Relative-position bias (the REL instantiations behind sed_mhsa_fwd_rel / sed_mhsa_bwd_rel, always with WIN = true: both sides unbounded is
+// a valid window; rel[H][2t - 1] fp32, one row per head, index d + t - 1 for the distance d = j - i, key minus query):
+//   s_ij = scale * sum_c q_ic k_jc + rel[g][(j - i) + t - 1]         lse, p, p~, ctx, D, dv, dp, ds, dq, dk as above with this s
+//   drel[g][d + t - 1] = sum_b sum_{(i, j) in the window, j - i = d} ds_ij                  (no scale: it enters dq and dk only)
+//   stage      a wave keeps the slice of its head's row that its walk can reach in LDS of its own (rel_stage below), 256 walked rows at a
+//              time; the forward and the dQ pass read slot (key - chunk start) + 31 - (lane & 31), the dK / dV pass the mirrored slice
+//   backward   the exponent is written scale s - (lse - rel): the shape of the other instantiations, so a zero table gives their bits
+//   drel       the dQ pass holds dS of a tile with the key in the register and the query on the lane: lane X gathers diagonal
+//              X = key row - query lane + 31 of the tile from the two half-waves (32 lane reads, fixed order), stores the 32 diagonals no
+//              later tile meets into the wave's workspace row and carries the other 31 down 32 lanes; mhsa_rel_reduce_kernel sums the rows
+//              over waves and clips in fp64 in a fixed order and rounds once.  Masked cells are exact zeros (select), no exp is taken there.
+// sed_relpos_expand: rel[g][x] = w[g][map[x]] (bit copy); sed_relpos_fold: dw[g][n] = sum_{x: map[x] = n} drel[g][x], fp64, ascending x,
+// rounded once, 0 for an empty bucket.  The bucket map is the host's (sed_relpos_map_check); the hot kernels never see it.
 #include "common.h"
 #include "philox.h"
 #include <math.h>
@@ -179,6 +193,9 @@ struct MhsaParams {
     float scale;
     DropArgs drop;       // the DROP instantiations only
     int wl, wr;          // the WIN instantiations only: left and right, clamped to t - 1 by the host
+    const float* rel;    // the REL instantiations only: the per-distance table [H][2t - 1]
+    float* relws;        // dQ pass: per-wave diagonal partials [B][H][ntile * MHSA_WAVES][relspan]
+    int relspan;
 };
 
 // ---- the local window: the tiles a wave walks --------------------------------------------------------------------------------------
@@ -194,6 +211,35 @@ __host__ __device__ inline TileRange mhsa_win_range(int a0, int span, int t, int
 }
 // key j takes part for query i (both inside the clip is the caller's business)
 __device__ __forceinline__ bool in_window(int i, int j, int wl, int wr) { return j >= i - wl && j <= i + wr; }
+
+// ---- the relative-position bias: a wave's slice of its head's table in LDS -----------------------------------------------------------
+// A wave that owns 32 rows of one index and walks tiles of the other meets, over REL_CHUNK walked rows (8 tiles), REL_CHUNK + 62
+// distances in a row: it stages them once per chunk with five coalesced loads per lane in its own REL_PITCH floats (5 KiB per
+// workgroup whatever t is; the whole walk of t = 750 would be 17 KiB and no faster: measured), slot x = (walked row - chunk
+// start) + 31 - (lane & 31), and a cell reads slot x + (its row inside the tile).  Queries own keys: slot x holds
+// rel[(kc - q0 - 31 + x) + t - 1] (dir +1); keys own queries: rel[(k0 + 31 - qc - x) + t - 1] (dir -1).  Slots whose distance lies
+// outside [-(t - 1), t - 1] belong to rows past the clip only (masked cells) and are read from the clamped end.  The slice is private to
+// the wave: no workgroup barrier, only the wave's own program order.
+#define REL_CHUNK 256
+#define REL_PITCH (REL_CHUNK + 64)
+__device__ __forceinline__ void wave_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ void rel_stage(float* relw, const float* __restrict__ rel_g, int base, int dir, int n, int t, int lane) {
+    wave_lds_order();
+    for (int x = lane; x < n; x += 64) {
+        int idx = base + dir * x;
+        idx = idx < 0 ? 0 : idx > 2 * t - 2 ? 2 * t - 2 : idx;
+        relw[x] = rel_g[idx];
+    }
+    wave_lds_order();
+}
+// slots a chunk that starts at walked row c0 of a walk that ends at hi needs
+__device__ __forceinline__ int rel_slots(int c0, int hi) {
+    const int rows = ((hi - c0 + MHSA_QT - 1) & ~(MHSA_QT - 1)) < REL_CHUNK ? ((hi - c0 + MHSA_QT - 1) & ~(MHSA_QT - 1)) : REL_CHUNK;
+    return rows + 31;
+}
 
 // store the transposed 32 x 32 tile o (column c = acc_row(i, h) in the registers, row on the lane) times f into row `dst` (head columns)
 __device__ __forceinline__ void store_tile_t(float* __restrict__ dst, const f32x16& o, float f, int h) {
@@ -247,8 +293,9 @@ __device__ __forceinline__ void drop_factors_k(float (&ms)[16], const DropArgs& 
     }
 }
 
-template <typename T, int DH, bool DROP, bool WIN>
+template <typename T, int DH, bool DROP, bool WIN, bool REL = false>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p) {
+    static_assert(WIN || !REL, "REL is instantiated with WIN only");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
     const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
@@ -269,7 +316,19 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
     kn.load(base + C + (kt.lo + r < t ? kt.lo + r : t - 1) * ld, h);
 #pragma unroll
     for (int cb = 0; cb < DH / 32; ++cb) load_col(vn[cb], base + 2 * C + cb * 32 + r, ld, kt.lo, t, h);
+    float* relw = nullptr;
+    if constexpr (REL) {
+        __shared__ float relsm[MHSA_WAVES * REL_PITCH];
+        relw = relsm + wave * REL_PITCH;
+    }
+    int kc = kt.lo;                                    // REL: the start of the staged chunk
     for (int k0 = kt.lo; k0 < kt.hi; k0 += 32) {
+        if constexpr (REL) {
+            if (((k0 - kt.lo) & (REL_CHUNK - 1)) == 0) {
+                kc = k0;
+                rel_stage(relw, p.rel + (size_t)g * (2 * t - 1), kc - q0 - 31 + t - 1, 1, rel_slots(kc, kt.hi), t, lane);
+            }
+        }
         const RowFrag<T, DH> kf = kn;
         float va[DH / 32][16];
 #pragma unroll
@@ -287,7 +346,10 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int j = k0 + acc_row(i, h);
-            s[i] = j < t && (!WIN || in_window(q0 + r, j, p.wl, p.wr)) ? s[i] * p.scale : -INFINITY;
+            if constexpr (REL)
+                s[i] = j < t && in_window(q0 + r, j, p.wl, p.wr) ? s[i] * p.scale + relw[(k0 - kc) + acc_row(i, h) + 31 - r] : -INFINITY;
+            else
+                s[i] = j < t && (!WIN || in_window(q0 + r, j, p.wl, p.wr)) ? s[i] * p.scale : -INFINITY;
             mx = fmaxf(mx, s[i]);
         }
         mx = fmaxf(mx, xor32(mx));
@@ -325,8 +387,9 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
 // A fragments) and V transposed (Vt[c][key], pitch 36: a lane's eight keys of a k-step are two 8-byte reads) into one of two LDS
 // buffers, one barrier per tile.  Same values, same MFMA order and so the same bits as the register-fed kernel above, which the fp32
 // mode keeps; waves whose 32 queries lie past the clip take part in the staging and the barriers only.
-template <int DH, bool DROP, bool WIN>
+template <int DH, bool DROP, bool WIN, bool REL = false>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParams p) {
+    static_assert(WIN || !REL, "REL is instantiated with WIN only");
     constexpr int KP = DH + 8, VP = 36, NL = DH / 32, RQ = DH / 4;       // NL 16-byte loads of K and of V per thread and tile
     __shared__ __attribute__((aligned(16))) bf16_t ks[2][32 * KP];
     __shared__ __attribute__((aligned(16))) bf16_t vt[2][DH * VP];
@@ -373,11 +436,23 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParam
     gload(wg.lo);
     lstore(0);
     __syncthreads();
+    float* relw = nullptr;
+    if constexpr (REL) {
+        __shared__ float relsm[MHSA_WAVES * REL_PITCH];
+        relw = relsm + wave * REL_PITCH;
+    }
+    int kc = mine.lo;                                  // REL: the start of the wave's staged chunk
     for (int k0 = wg.lo, it = 0; k0 < wg.hi; k0 += 32, ++it) {
         const int cur = it & 1;
         const bool more = k0 + 32 < wg.hi;             // (the same in every thread: the barrier below is uniform)
         if (more) gload(k0 + 32);
         if (active && (!WIN || (k0 >= mine.lo && k0 < mine.hi))) {
+            if constexpr (REL) {
+                if (((k0 - mine.lo) & (REL_CHUNK - 1)) == 0) {
+                    kc = k0;
+                    rel_stage(relw, p.rel + (size_t)g * (2 * t - 1), kc - q0 - 31 + t - 1, 1, rel_slots(kc, mine.hi), t, lane);
+                }
+            }
             RowFrag<bf16_t, DH> kf;
 #pragma unroll
             for (int s = 0; s < DH / 16; ++s) kf.f[s] = *reinterpret_cast<const bf16x8*>(&ks[cur][r * KP + 16 * s + 8 * h]);
@@ -386,7 +461,10 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParam
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int j = k0 + acc_row(i, h);
-                s[i] = j < t && (!WIN || in_window(q0 + r, j, p.wl, p.wr)) ? s[i] * p.scale : -INFINITY;
+                if constexpr (REL)
+                    s[i] = j < t && in_window(q0 + r, j, p.wl, p.wr) ? s[i] * p.scale + relw[(k0 - kc) + acc_row(i, h) + 31 - r] : -INFINITY;
+                else
+                    s[i] = j < t && (!WIN || in_window(q0 + r, j, p.wl, p.wr)) ? s[i] * p.scale : -INFINITY;
                 mx = fmaxf(mx, s[i]);
             }
             mx = fmaxf(mx, xor32(mx));
@@ -449,8 +527,9 @@ __global__ __launch_bounds__(256) void mhsa_rowdot_kernel(MhsaParams p, int B, i
 }
 
 // pass 2 of the backward: the wave owns 32 keys (on the lane) and loops over the query tiles -> dK, dV
-template <typename T, int DH, bool DROP, bool WIN>
+template <typename T, int DH, bool DROP, bool WIN, bool REL = false>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams p) {
+    static_assert(WIN || !REL, "REL is instantiated with WIN only");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
     const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
@@ -487,7 +566,25 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
     // only, so it can overflow)
     auto live = [&](int q) { return q < t && (!WIN || (k0 + r < t && in_window(q, k0 + r, p.wl, p.wr))); };
     load_rows(qt.lo);
+    float* relw = nullptr;
+    if constexpr (REL) {
+        __shared__ float relsm[MHSA_WAVES * REL_PITCH];
+        relw = relsm + wave * REL_PITCH;
+    }
+    int qc = qt.lo;                                    // REL: the start of the staged chunk
+    // what the scaled product of cell (query q0 + acc_row(i, h), key k0 + r) is reduced by under the exponential: lse_i, REL: lse_i - rel
+    // (the expression keeps the shape scale * s - c of the other instantiations: a zero table gives their bits whatever is contracted)
+    auto under = [&](float l, int q0, int i) {
+        if constexpr (REL) return l - relw[(q0 - qc) + acc_row(i, h) + 31 - r];
+        else return l;
+    };
     for (int q0 = qt.lo; q0 < qt.hi; q0 += 32) {
+        if constexpr (REL) {
+            if (((q0 - qt.lo) & (REL_CHUNK - 1)) == 0) {
+                qc = q0;
+                rel_stage(relw, p.rel + (size_t)g * (2 * t - 1), k0 + 31 - qc + t - 1, -1, rel_slots(qc, qt.hi), t, lane);
+            }
+        }
         const RowFrag<T, DH> qf = qn, df = dn;
         float lc[16], Dc[16], qa[DH / 32][16], da[DH / 32][16];
 #pragma unroll
@@ -506,7 +603,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const bool in = live(q0 + acc_row(i, h));
-                const float pr = in ? expf(s[i] * p.scale - lc[i]) : 0.f;
+                const float pr = in ? expf(s[i] * p.scale - under(lc[i], q0, i)) : 0.f;
                 s[i] = pr * ms[i];                       // p~ for dV
                 dp[i] = !WIN || in ? pr * (dp[i] * ms[i] - Dc[i]) : 0.f;
             }
@@ -514,7 +611,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const bool in = live(q0 + acc_row(i, h));
-                const float pr = in ? expf(s[i] * p.scale - lc[i]) : 0.f;
+                const float pr = in ? expf(s[i] * p.scale - under(lc[i], q0, i)) : 0.f;
                 s[i] = pr;
                 dp[i] = !WIN || in ? pr * (dp[i] - Dc[i]) : 0.f;
             }
@@ -536,8 +633,9 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
 }
 
 // pass 3: the wave owns 32 queries (on the lane) and loops over the key tiles -> dQ
-template <typename T, int DH, bool DROP, bool WIN>
+template <typename T, int DH, bool DROP, bool WIN, bool REL = false>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams p) {
+    static_assert(WIN || !REL, "REL is instantiated with WIN only");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
     const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
@@ -562,7 +660,25 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
     };
     const TileRange kt = WIN ? mhsa_win_range(q0, MHSA_QT, t, p.wl, p.wr) : TileRange{0, t};
     load_rows(kt.lo);
+    float* relw = nullptr;
+    if constexpr (REL) {
+        __shared__ float relsm[MHSA_WAVES * REL_PITCH];
+        relw = relsm + wave * REL_PITCH;
+    }
+    int kc = kt.lo;                                    // REL: the start of the staged chunk
+    // REL: the wave's partial of drel.  Slot x of its workspace row is distance (kt.lo - q0 - 31) + x; a tile at k0 meets slots
+    // (k0 - kt.lo) + 0 ... 62, lane X of `carry` holding slot (k0 - kt.lo) + X: the lower 32 are complete after this tile and are
+    // stored, the upper 31 move down to meet the next tile; the row ends with the last tile's upper half.
+    float carry = 0.f;
+    float* __restrict__ wsrow = nullptr;
+    if constexpr (REL) wsrow = p.relws + ((size_t)blockIdx.x * MHSA_WAVES + wave) * p.relspan;
     for (int k0 = kt.lo; k0 < kt.hi; k0 += 32) {
+        if constexpr (REL) {
+            if (((k0 - kt.lo) & (REL_CHUNK - 1)) == 0) {
+                kc = k0;
+                rel_stage(relw, p.rel + (size_t)g * (2 * t - 1), kc - q0 - 31 + t - 1, 1, rel_slots(kc, kt.hi), t, lane);
+            }
+        }
         const RowFrag<T, DH> kf = kn, vf = vn;
         float ka[DH / 32][16];
 #pragma unroll
@@ -580,17 +696,125 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
         for (int i = 0; i < 16; ++i) {
             const int j = k0 + acc_row(i, h);
             const bool in = j < t && (!WIN || (q0 + r < t && in_window(q0 + r, j, p.wl, p.wr)));   // (select: see mhsa_bwd_kv_kernel)
-            const float pr = in ? expf(s[i] * p.scale - lse) : 0.f;
+            float lr = lse;                             // REL: lse - rel, the expression's shape kept (see mhsa_bwd_kv_kernel)
+            if constexpr (REL) lr = lse - relw[(k0 - kc) + acc_row(i, h) + 31 - r];
+            const float pr = in ? expf(s[i] * p.scale - lr) : 0.f;
             dp[i] = !WIN || in ? pr * (dp[i] - Dq) : 0.f;
+        }
+        if constexpr (REL) {
+            // the tile's 63 diagonal sums of dS, diagonal X = (key row) - (query lane) + 31 on lane X: register i holds key rows
+            // b and b + 4 (the two half-waves), so lane X takes it from lane b + 31 - X of the lower and b + 35 - X of the upper
+            // half where those exist; 32 reads in a fixed order, no two lanes ever add into one place
+            float v = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int bi = (i & 3) + 8 * (i >> 2);
+                const int r0 = bi + 31 - lane, r1 = bi + 35 - lane;
+                const float a0 = __shfl(dp[i], r0 & 31, 64), a1 = __shfl(dp[i], 32 + (r1 & 31), 64);
+                v += r0 >= 0 && r0 < 32 ? a0 : 0.f;
+                v += r1 >= 0 && r1 < 32 ? a1 : 0.f;
+            }
+            const float up = __shfl(carry, (lane + 32) & 63, 64);
+            carry = lane < 32 ? v + up : v;
+            if (lane < 32) wsrow[(k0 - kt.lo) + lane] = carry;
         }
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) MmAx<T>::run(dq[cb], ka[cb], dp);
+    }
+    if constexpr (REL) {
+        if (lane >= 32) wsrow[((kt.hi - kt.lo + MHSA_QT - 1) & ~(MHSA_QT - 1)) + lane - 32] = carry;
     }
     if (q0 + r < t) {
         float* __restrict__ dst = p.out + ((size_t)b * t + q0 + r) * ld + g * DH;
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) store_tile_t(dst + cb * 32, dq[cb], p.scale, h);
     }
+}
+
+// ---- relative-position bias: the workspace rows of the dQ pass and their reduction ---------------------------------------------------
+// floats of a wave's row: 32 per visited tile and 32 for the last tile's upper half, the largest over the waves of a clip
+inline int rel_span(int t, int wl, int wr) {
+    int span = 0;
+    for (int q0 = 0; q0 < t; q0 += MHSA_QT) {
+        const TileRange kt = mhsa_win_range(q0, MHSA_QT, t, wl, wr);
+        const int n = ((kt.hi - kt.lo + MHSA_QT - 1) & ~(MHSA_QT - 1)) + MHSA_QT;
+        span = n > span ? n : span;
+    }
+    return span;
+}
+
+// drel[g][d + t - 1] = sum over the clips and the waves of their partials of distance d, in fp64: 64 distances x REL_RED_LANES clip lanes
+// per workgroup, each clip lane its clips (stride REL_RED_LANES) and their waves in ascending order, then the lanes in a fixed tree,
+// rounded once
+#define REL_RED_LANES 16
+__global__ __launch_bounds__(64 * REL_RED_LANES) void mhsa_rel_reduce_kernel(const float* __restrict__ ws, float* __restrict__ drel, int B, int t, int H,
+                                                              int ntile, int relspan, int wl, int wr) {
+    __shared__ double sh[REL_RED_LANES][64];
+    const int cl = threadIdx.x & 63, ry = threadIdx.x >> 6;
+    const int di = blockIdx.x * 64 + cl, g = blockIdx.y, d = di - (t - 1);
+    double s = 0.0;
+    if (di < 2 * t - 1)
+        for (int b = ry; b < B; b += REL_RED_LANES)
+            for (int w = 0; w * MHSA_QT < t; ++w) {
+                const int q0 = w * MHSA_QT;
+                const TileRange kt = mhsa_win_range(q0, MHSA_QT, t, wl, wr);
+                const int slot = d - (kt.lo - q0 - 31);
+                const int n = ((kt.hi - kt.lo + MHSA_QT - 1) & ~(MHSA_QT - 1)) + MHSA_QT;
+                if (slot >= 0 && slot < n) s += (double)ws[(((size_t)b * H + g) * ((size_t)ntile * MHSA_WAVES) + w) * relspan + slot];
+            }
+    sh[ry][cl] = s;
+    __syncthreads();
+#pragma unroll
+    for (int n = REL_RED_LANES / 2; n >= 1; n >>= 1) {          // lane ry += lane ry + n: the same tree on every run
+        if (ry < n) sh[ry][cl] += sh[ry + n][cl];
+        __syncthreads();
+    }
+    if (ry == 0 && di < 2 * t - 1) drel[(size_t)g * (2 * t - 1) + di] = (float)sh[0][cl];
+}
+
+// rel[g][x] = w[g][map[x]], x = d + t - 1 (a bit copy; the map was checked on the host: sed_relpos_map_check)
+__global__ __launch_bounds__(256) void relpos_expand_kernel(const float* __restrict__ w, const int* __restrict__ map, float* __restrict__ rel,
+                                                            int nb, int n) {
+    const int x = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
+    if (x >= n) return;
+    int m = map[x];
+    m = m < 0 ? 0 : m >= nb ? nb - 1 : m;              // (never taken for a checked map: no read outside w whatever the map holds)
+    rel[(size_t)g * n + x] = w[(size_t)g * nb + m];
+}
+
+// dw[g][b] = sum over the distances x with map[x] = b of drel[g][x], in fp64, ascending x, rounded once; 0 for an empty bucket
+__global__ __launch_bounds__(256) void relpos_fold_kernel(const float* __restrict__ drel, const int* __restrict__ map, float* __restrict__ dw,
+                                                          int nb, int n) {
+    // the workgroup stages 1024 distances at a time in LDS (coalesced loads, the tail padded with bucket -1); every thread scans them for
+    // its bucket in ascending order, 16 at a time through 16-byte LDS reads issued together
+    __shared__ __attribute__((aligned(16))) int ms[1024];
+    __shared__ __attribute__((aligned(16))) float ds[1024];
+    const int b = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
+    double s = 0.0;
+    for (int x0 = 0; x0 < n; x0 += 1024) {
+        for (int x = threadIdx.x; x < 1024; x += 256) {
+            const bool in = x0 + x < n;
+            ms[x] = in ? map[x0 + x] : -1;
+            ds[x] = in ? drel[(size_t)g * n + x0 + x] : 0.f;
+        }
+        __syncthreads();
+        const int m = n - x0 < 1024 ? n - x0 : 1024;
+        for (int x = 0; x < m; x += 16) {
+            int4 mm[4];
+            f32x4 dd[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { mm[k] = *reinterpret_cast<const int4*>(&ms[x + 4 * k]); dd[k] = *reinterpret_cast<const f32x4*>(&ds[x + 4 * k]); }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                s += mm[k].x == b ? (double)dd[k][0] : 0.0;
+                s += mm[k].y == b ? (double)dd[k][1] : 0.0;
+                s += mm[k].z == b ? (double)dd[k][2] : 0.0;
+                s += mm[k].w == b ? (double)dd[k][3] : 0.0;
+            }
+        }
+        __syncthreads();
+    }
+    if (b < nb) dw[(size_t)g * nb + b] = (float)s;
 }
 
 // ---- LayerNorm ---------------------------------------------------------------------------------------------------------------
@@ -783,9 +1007,9 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 namespace {
 // wl, wr: the window, already clamped to [0, t - 1] (WIN only)
-template <bool DROP, bool WIN = false>
+template <bool DROP, bool WIN = false, bool REL = false>
 int mhsa_fwd_launch(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, const DropArgs& drop, void* stream,
-                    int wl = 0, int wr = 0) {
+                    int wl = 0, int wr = 0, const float* rel = nullptr) {
     long long nb; int ntile;
     if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
     SED_REQUIRE(qkv != nullptr && ctx != nullptr, "qkv and ctx are required");
@@ -794,14 +1018,15 @@ int mhsa_fwd_launch(int dtype, const float* qkv, float* ctx, float* lse, int B, 
     p.qkv = qkv; p.out = ctx; p.lse_out = lse; p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
     p.drop = drop;
     p.wl = wl; p.wr = wr;
+    p.rel = rel;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
     if (dtype == SED_BF16) {
-        if (dh == 32) mhsa_fwd_lds_kernel<32, DROP, WIN><<<grid, block, 0, st>>>(p);
-        else mhsa_fwd_lds_kernel<64, DROP, WIN><<<grid, block, 0, st>>>(p);
+        if (dh == 32) mhsa_fwd_lds_kernel<32, DROP, WIN, REL><<<grid, block, 0, st>>>(p);
+        else mhsa_fwd_lds_kernel<64, DROP, WIN, REL><<<grid, block, 0, st>>>(p);
     } else {
-        if (dh == 32) mhsa_fwd_kernel<float, 32, DROP, WIN><<<grid, block, 0, st>>>(p);
-        else mhsa_fwd_kernel<float, 64, DROP, WIN><<<grid, block, 0, st>>>(p);
+        if (dh == 32) mhsa_fwd_kernel<float, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p);
+        else mhsa_fwd_kernel<float, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p);
     }
     SED_LAUNCH_CHECK();
     return 0;
@@ -866,9 +1091,10 @@ extern "C" size_t sed_mhsa_bwd_ws_floats(int B, int t, int H, int dh) {
 }
 
 namespace {
-template <bool DROP, bool WIN = false>
+template <bool DROP, bool WIN = false, bool REL = false>
 int mhsa_bwd_launch(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
-                    float* workspace, int B, int t, int H, int dh, const DropArgs& drop, void* stream, int wl = 0, int wr = 0) {
+                    float* workspace, int B, int t, int H, int dh, const DropArgs& drop, void* stream, int wl = 0, int wr = 0,
+                    const float* rel = nullptr, float* drel = nullptr) {
     long long nb; int ntile;
     if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
     SED_REQUIRE(qkv != nullptr && ctx != nullptr && dctx != nullptr && lse != nullptr && dqkv != nullptr && workspace != nullptr,
@@ -879,18 +1105,27 @@ int mhsa_bwd_launch(int dtype, const float* qkv, const float* ctx, const float* 
     p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
     p.drop = drop;
     p.wl = wl; p.wr = wr;
+    if (REL) {
+        p.rel = rel;
+        p.relws = workspace + (size_t)B * t * H;
+        p.relspan = rel_span(t, wl, wr);
+    }
     hipStream_t st = (hipStream_t)stream;
     mhsa_rowdot_kernel<<<(unsigned)cdivz((size_t)B * t * H, 256), 256, 0, st>>>(p, B, dh);
     SED_LAUNCH_CHECK();
     const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
     if (dtype == SED_BF16) {
-        if (dh == 32) { mhsa_bwd_kv_kernel<bf16_t, 32, DROP, WIN><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 32, DROP, WIN><<<grid, block, 0, st>>>(p); }
-        else { mhsa_bwd_kv_kernel<bf16_t, 64, DROP, WIN><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 64, DROP, WIN><<<grid, block, 0, st>>>(p); }
+        if (dh == 32) { mhsa_bwd_kv_kernel<bf16_t, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p); }
+        else { mhsa_bwd_kv_kernel<bf16_t, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p); }
     } else {
-        if (dh == 32) { mhsa_bwd_kv_kernel<float, 32, DROP, WIN><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 32, DROP, WIN><<<grid, block, 0, st>>>(p); }
-        else { mhsa_bwd_kv_kernel<float, 64, DROP, WIN><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 64, DROP, WIN><<<grid, block, 0, st>>>(p); }
+        if (dh == 32) { mhsa_bwd_kv_kernel<float, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p); }
+        else { mhsa_bwd_kv_kernel<float, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p); }
     }
     SED_LAUNCH_CHECK();
+    if (REL) {
+        mhsa_rel_reduce_kernel<<<dim3((unsigned)cdiv(2 * t - 1, 64), (unsigned)H), 64 * REL_RED_LANES, 0, st>>>(p.relws, drel, B, t, H, ntile, p.relspan, wl, wr);
+        SED_LAUNCH_CHECK();
+    }
     return 0;
 }
 }  // namespace
@@ -921,6 +1156,79 @@ extern "C" int sed_mhsa_bwd_win(int dtype, const float* qkv, const float* ctx, c
     }
     if (d.thr == 0) return mhsa_bwd_launch<false, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr);
     return mhsa_bwd_launch<true, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr);
+}
+
+// ---- the relative-position entries: the windowed entries' arguments and the per-distance table(s).  Always the WIN = true kernels
+// (both sides unbounded is a valid window: every tile is visited and the select never masks), DROP by thr as above
+inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
+extern "C" int sed_mhsa_fwd_rel(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, int left, int right,
+                                float p, const uint32_t* rng, uint32_t stream_id, const float* rel, void* stream) {
+    DropArgs d;
+    SED_WIN_ARGS(left, right, p, rng, stream_id, d);
+    SED_REQUIRE(rel != nullptr, "the distance table rel is required");
+    SED_REQUIRE(aligned4(rel), "rel must be 4-byte aligned");
+    const int cap = t > 0 ? t - 1 : 0, wl = left < cap ? left : cap, wr = right < cap ? right : cap;
+    if (d.thr == 0) return mhsa_fwd_launch<false, true, true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream, wl, wr, rel);
+    return mhsa_fwd_launch<true, true, true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream, wl, wr, rel);
+}
+
+extern "C" size_t sed_mhsa_bwd_rel_ws_floats(int B, int t, int H, int dh, int left, int right) {
+    long long nb; int ntile;
+    if (left < 0 || right < 0 || B <= 0 || t <= 0 || H <= 0 || (dh != 32 && dh != 64)) return 0;
+    if ((long long)t * 3 * H * dh * 4 >= (1ll << 31)) return 0;
+    ntile = cdiv(t, MHSA_QT * MHSA_WAVES);
+    nb = (long long)B * H * ntile;
+    const int wl = left < t - 1 ? left : t - 1, wr = right < t - 1 ? right : t - 1;
+    return (size_t)B * t * H + (size_t)nb * MHSA_WAVES * rel_span(t, wl, wr);
+}
+
+extern "C" int sed_mhsa_bwd_rel(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
+                                float* workspace, int B, int t, int H, int dh, int left, int right, float p, const uint32_t* rng,
+                                uint32_t stream_id, const float* rel, float* drel, void* stream) {
+    DropArgs d;
+    SED_WIN_ARGS(left, right, p, rng, stream_id, d);
+    SED_REQUIRE(rel != nullptr && drel != nullptr, "the distance tables rel and drel are required");
+    SED_REQUIRE(aligned4(rel) && aligned4(drel), "rel and drel must be 4-byte aligned");
+    const int cap = t > 0 ? t - 1 : 0, wl = left < cap ? left : cap, wr = right < cap ? right : cap;
+    if (d.thr == 0)
+        return mhsa_bwd_launch<false, true, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr, rel, drel);
+    return mhsa_bwd_launch<true, true, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr, rel, drel);
+}
+
+#define SED_RELPOS_MAX_BUCKETS 4096
+extern "C" int sed_relpos_map_check(const int* map_host, int nb, int t) {
+    SED_REQUIRE(map_host != nullptr, "the bucket map is required");
+    SED_REQUIRE(nb >= 1 && nb <= SED_RELPOS_MAX_BUCKETS, "the bucket count must lie in [1, 4096]");
+    SED_REQUIRE(t >= 1 && t < (1 << 30), "t must lie in [1, 2^30)");
+    for (int x = 0; x < 2 * t - 1; ++x) SED_REQUIRE(map_host[x] >= 0 && map_host[x] < nb, "a bucket map entry lies outside [0, nb)");
+    return 0;
+}
+
+namespace {
+int relpos_check(const void* a, const void* map, const void* b, int H, int nb, int t) {
+    SED_REQUIRE(a != nullptr && map != nullptr && b != nullptr, "the table, the map and the output are required");
+    SED_REQUIRE(aligned4(a) && aligned4(map) && aligned4(b), "the table, the map and the output must be 4-byte aligned");
+    SED_REQUIRE(H >= 1 && H <= 65535, "H must lie in [1, 65535]");
+    SED_REQUIRE(nb >= 1 && nb <= SED_RELPOS_MAX_BUCKETS, "the bucket count must lie in [1, 4096]");
+    SED_REQUIRE(t >= 1 && t < (1 << 30), "t must lie in [1, 2^30)");
+    return 0;
+}
+}  // namespace
+
+extern "C" int sed_relpos_expand(const float* w, const int* map, float* rel, int H, int nb, int t, void* stream) {
+    if (int rc = relpos_check(w, map, rel, H, nb, t)) return rc;
+    const int n = 2 * t - 1;
+    relpos_expand_kernel<<<dim3((unsigned)cdiv(n, 256), (unsigned)H), 256, 0, (hipStream_t)stream>>>(w, map, rel, nb, n);
+    SED_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sed_relpos_fold(const float* drel, const int* map, float* dw, int H, int nb, int t, void* stream) {
+    if (int rc = relpos_check(drel, map, dw, H, nb, t)) return rc;
+    relpos_fold_kernel<<<dim3((unsigned)cdiv(nb, 256), (unsigned)H), 256, 0, (hipStream_t)stream>>>(drel, map, dw, nb, 2 * t - 1);
+    SED_LAUNCH_CHECK();
+    return 0;
 }
 
 namespace {

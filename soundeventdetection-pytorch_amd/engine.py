@@ -20,7 +20,7 @@ import os as _os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
-
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -229,7 +229,7 @@ class CnnEngine(OptimizerExtMixin):
                  precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
                  mel_bins: Optional[int] = None, attention: bool = False, sa_heads: int = 4, pos_encoding: bool = True,
                  sa_layers: int = 1, sa_ffn: int = 0, sa_activation: str = "relu", sa_conv_kernel: int = 0,
-                 sa_dropout: float = 0.0, sa_dropout_seed: Optional[int] = None, sa_window=None):
+                 sa_dropout: float = 0.0, sa_dropout_seed: Optional[int] = None, sa_window=None, sa_rel_pos=None):
         """attention: a second linear layer att_fc beside event_fc scores every frame per class (csrc/sed_attn.hip): forward()
         also leaves the attention logits in plan.att, loss_and_grad(weak=("att", ...)) pools with them and backward() then takes
         both layers.  False launches exactly what it always did.
@@ -247,6 +247,11 @@ class CnnEngine(OptimizerExtMixin):
         every layer (key j takes part for query i iff i - left <= j <= i + right; torch's src_mask), in every forward and backward --
         sed_mhsa_fwd_win / sed_mhsa_bwd_win in the places of the plain / _drop core launches, no new buffers.  None launches what it
         always did.
+        sa_rel_pos = None, an int L >= 1 (clipped distances, 2L + 1 buckets) or a pair (num_buckets, max_distance) (T5's bidirectional
+        log buckets): a learned bias per head and bucket of the distance j - i on every score of every layer, P["rel_pos*.weight"]
+        (H, num_buckets) -- sed_relpos_expand + sed_mhsa_fwd_rel in the place of the core launch, sed_mhsa_bwd_rel + sed_relpos_fold
+        into G["rel_pos*.weight"] in the backward; the map, the per-layer distance tables and the workspace belong to the plan.  It
+        composes with sa_window and sa_dropout.  None launches what it always did.
         or 'none' (a bare stack of ConvBlocks: forward() stops at the last pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
         Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and backward() also produces the input gradient
         plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path keeps the dedicated Cin = 1
@@ -274,6 +279,9 @@ class CnnEngine(OptimizerExtMixin):
             raise ValueError("sa_window belongs to the self-attention head (head='sa')")
         # the sides as the C entries take them
         self._win = None if self.sa_window is None else tuple(L.WIN_UNBOUNDED if v is None else min(v, L.WIN_UNBOUNDED) for v in self.sa_window)
+        self.sa_rel_pos = self.check_sa_rel_pos(sa_rel_pos)
+        if head != "sa" and self.sa_rel_pos is not None:
+            raise ValueError("sa_rel_pos belongs to the self-attention head (head='sa')")
         self._drop_state = None              # (4,) int32 on the device holding the uint32 words, made with the first plan (on its device)
         self._drop_dev = "cuda"
         self._drop_host = [self.sa_dropout_seed & 0xFFFFFFFF, self.sa_dropout_seed >> 32, 0, 0]
@@ -351,6 +359,58 @@ class CnnEngine(OptimizerExtMixin):
         if isinstance(w, bool) or not isinstance(w, int):
             raise ValueError(f"sa_window must be None, an integer or a pair (left, right), got {w!r}")
         return side(w), side(w)
+
+    RELPOS_MAX_BUCKETS = 4096
+
+    @staticmethod
+    def check_sa_rel_pos(v):
+        """None, an int L >= 1 or a pair (num_buckets even >= 4, max_distance > num_buckets / 4) -> None, ("clip", L) or
+        ("log", num_buckets, max_distance); at most RELPOS_MAX_BUCKETS buckets"""
+        def integer(x):
+            return isinstance(x, int) and not isinstance(x, bool)
+        if v is None:
+            return None
+        if isinstance(v, (tuple, list)):
+            if len(v) == 2 and v[0] == "clip":         # (what this function returned)
+                v = v[1]
+            elif len(v) == 3 and v[0] == "log":
+                v = v[1:]
+        if isinstance(v, (tuple, list)):
+            if len(v) != 2 or not integer(v[0]) or not integer(v[1]):
+                raise ValueError(f"sa_rel_pos must be None, an integer L >= 1 or a pair of integers (num_buckets, max_distance), got {v!r}")
+            nb, maxd = v
+            if nb < 4 or nb % 2:
+                raise ValueError(f"sa_rel_pos: num_buckets must be even and >= 4, got {nb}")
+            if 4 * maxd <= nb:
+                raise ValueError(f"sa_rel_pos: max_distance must exceed num_buckets / 4, got {maxd} with {nb} buckets")
+            if nb > CnnEngine.RELPOS_MAX_BUCKETS:
+                raise ValueError(f"sa_rel_pos: at most {CnnEngine.RELPOS_MAX_BUCKETS} buckets, got {nb}")
+            return "log", nb, maxd
+        if not integer(v) or v < 1:
+            raise ValueError(f"sa_rel_pos must be None, an integer L >= 1 or a pair of integers (num_buckets, max_distance), got {v!r}")
+        if 2 * v + 1 > CnnEngine.RELPOS_MAX_BUCKETS:
+            raise ValueError(f"sa_rel_pos: at most {CnnEngine.RELPOS_MAX_BUCKETS} buckets, L = {v} gives {2 * v + 1}")
+        return "clip", v
+
+    @staticmethod
+    def rel_pos_buckets(cfg):
+        """the number of buckets of a checked sa_rel_pos"""
+        return 2 * cfg[1] + 1 if cfg[0] == "clip" else cfg[1]
+
+    @staticmethod
+    def rel_pos_map(cfg, t):
+        """int32 (2t - 1,): the bucket of distance d = j - i at index d + t - 1.  clip: clamp(d, -L, L) + L.  log (T5, bidirectional),
+        n = nb / 2, a = |d|, m = n / 2: (n if d > 0 else 0) + (a if a < m else min(n - 1, m + floor(ln(a / m) / ln(maxd / m) * (n - m)))),
+        evaluated in float64 as written"""
+        d = np.arange(-(t - 1), t, dtype=np.int64)
+        if cfg[0] == "clip":
+            return (np.clip(d, -cfg[1], cfg[1]) + cfg[1]).astype(np.int32)
+        nb, maxd = cfg[1], cfg[2]
+        n = nb // 2
+        m = n // 2
+        a = np.abs(d)
+        big = m + np.floor(np.log(np.maximum(a, 1).astype(np.float64) / m) / np.log(float(maxd) / m) * (n - m)).astype(np.int64)
+        return (np.where(d > 0, n, 0) + np.where(a < m, a, np.minimum(n - 1, big))).astype(np.int32)
 
     # ---- the dropout state: (seed_lo, seed_hi, step, 0), uint32 words in an int32 device tensor ---------------------------------
     @property
@@ -735,6 +795,11 @@ class CnnEngine(OptimizerExtMixin):
         sfx = "" if l == 0 else f"_l{l}"
         return "convm" + sfx, "conv_norm" + sfx
 
+    @staticmethod
+    def sa_rel_name(l):
+        """module name of encoder layer l's relative-position table (between attn* and attn_norm* of sa_layer_names)"""
+        return "rel_pos" if l == 0 else f"rel_pos_l{l}"
+
     def _plan_sa(self, B, t, C, dev):
         """Buffers of the self-attention head (every one allocated here: a captured step allocates nothing); R = B*t rows.  What a
         layer's backward reads of its forward is kept per layer (g["layers"]); the gradients in flight are shared by the layers."""
@@ -790,6 +855,16 @@ class CnnEngine(OptimizerExtMixin):
             ang = i / torch.pow(torch.tensor(10000.0, dtype=torch.float64), j2 / C)
             g["pe"] = torch.where((torch.arange(C) % 2 == 0)[None, :], torch.sin(ang), torch.cos(ang)).to(torch.float32).to(dev)
         g["core_ws"] = torch.empty(max(1, lib.sed_mhsa_bwd_ws_floats(B, t, Hh, C // Hh)), **f32)
+        if self.sa_rel_pos is not None:
+            # the bucket map over the 2t - 1 distances (checked here, on the host: the kernels do not), a distance table and its gradient
+            # per layer, and the core backward's workspace with the per-wave diagonal partials behind D
+            m = np.ascontiguousarray(self.rel_pos_map(self.sa_rel_pos, t))
+            L.check(lib.sed_relpos_map_check(m.ctypes.data, self.rel_pos_buckets(self.sa_rel_pos), t), "sed_relpos_map_check")
+            g["rel_map"] = torch.from_numpy(m).to(dev)
+            for ly in g["layers"]:
+                ly["rel"], ly["drel"] = torch.empty((Hh, 2 * t - 1), **f32), torch.empty((Hh, 2 * t - 1), **f32)
+            wl, wr = self._win if self._win is not None else (L.WIN_UNBOUNDED, L.WIN_UNBOUNDED)
+            g["core_ws"] = torch.empty(max(1, lib.sed_mhsa_bwd_rel_ws_floats(B, t, Hh, C // Hh, wl, wr)), **f32)
         g["ln_ws"] = torch.empty(max(1, lib.sed_add_layernorm_bwd_ws_floats(R, C)), **f32)
         # split-K of the weight-gradient products (K = R rows), as the recurrent head's tail: SED_GRU_KSPLIT, read with the plan
         g["ksplit"] = max(1, int(_os.environ.get("SED_GRU_KSPLIT", "64")))
@@ -915,7 +990,14 @@ class CnnEngine(OptimizerExtMixin):
             an, nn_, fn, fnn = self.sa_layer_names(l)
             self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(xin), C, L.ptr(P[an + ".in_proj_weight"]), C, L.ptr(P[an + ".in_proj_bias"]),
                     L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
-            if self._win is not None:
+            if self.sa_rel_pos is not None:
+                wl, wr = self._win if self._win is not None else (L.WIN_UNBOUNDED, L.WIN_UNBOUNDED)
+                self._k("sed_relpos_expand", lib.sed_relpos_expand, L.ptr(P[self.sa_rel_name(l) + ".weight"]), L.ptr(g["rel_map"]),
+                        L.ptr(ly["rel"]), Hh, self.rel_pos_buckets(self.sa_rel_pos), t, st)
+                self._k("sed_mhsa_fwd_rel", lib.sed_mhsa_fwd_rel, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]),
+                        L.ptr(ly["lse"]) if training or drop else None, B, t, Hh, C // Hh, wl, wr, drop,
+                        L.ptr(g["rng"]) if drop else None, 8 * l + 0, L.ptr(ly["rel"]), st)
+            elif self._win is not None:
                 self._k("sed_mhsa_fwd_win", lib.sed_mhsa_fwd_win, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]),
                         L.ptr(ly["lse"]) if training or drop else None, B, t, Hh, C // Hh, self._win[0], self._win[1], drop,
                         L.ptr(g["rng"]) if drop else None, 8 * l + 0, st)
@@ -1017,7 +1099,17 @@ class CnnEngine(OptimizerExtMixin):
             self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[an + ".out_proj.weight"]), C, L.ptr(g["woT"]), C, C, C, C, 0, st)
             self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ga), C, L.ptr(g["woT"]), C, None, L.ptr(g["dctx"]), C, R, C, C, 1,
                     None, st)
-            if self._win is not None:
+            if self.sa_rel_pos is not None:
+                # ly["rel"] is the table this layer's forward read (the weights do not change between a step's forward and backward)
+                wl, wr = self._win if self._win is not None else (L.WIN_UNBOUNDED, L.WIN_UNBOUNDED)
+                rn = self.sa_rel_name(l)
+                self._k("sed_mhsa_bwd_rel", lib.sed_mhsa_bwd_rel, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
+                        L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, wl, wr, drop,
+                        L.ptr(g["rng"]) if drop else None, 8 * l + 0, L.ptr(ly["rel"]), L.ptr(ly["drel"]), st)
+                self._k("sed_relpos_fold", lib.sed_relpos_fold, L.ptr(ly["drel"]), L.ptr(g["rel_map"]), L.ptr(G[rn + ".weight"]), Hh,
+                        self.rel_pos_buckets(self.sa_rel_pos), t, st)
+                done(rn)
+            elif self._win is not None:
                 self._k("sed_mhsa_bwd_win", lib.sed_mhsa_bwd_win, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
                         L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, self._win[0], self._win[1], drop,
                         L.ptr(g["rng"]) if drop else None, 8 * l + 0, st)

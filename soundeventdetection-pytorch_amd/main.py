@@ -137,7 +137,21 @@ def build_weak_parser():
                    help="--self_attention: local attention window of every encoder layer -- a frame attends to the L frames before it and "
                         "the R frames after it (one number: L = R; inf: that side unbounded; 64:0 is causal attention with a look-back "
                         "of 64 frames); default: every frame attends to every frame")
+    p.add_argument("--sa_rel_pos", type=str, default=None, metavar="L|NB:MAXD",
+                   help="--self_attention: learned relative-position bias per layer, head and bucket of the distance between two frames -- "
+                        "L: distances clipped to [-L, L] (2L + 1 buckets); NB:MAXD: T5's bidirectional log buckets (NB even >= 4, "
+                        "MAXD > NB / 4); usually with --no_pos_encoding; default: none")
     return p
+
+
+def parse_sa_rel_pos(text):
+    """--sa_rel_pos L | NB:MAXD -> None, L or (NB, MAXD); a ValueError for anything else (the ranges are the model's to check)"""
+    if text is None:
+        return None
+    parts = [v.strip() for v in str(text).split(":")]
+    if len(parts) > 2 or not all(v.isdigit() for v in parts):
+        raise ValueError(f"--sa_rel_pos takes L or NB:MAXD with positive integers, got {text!r}")
+    return int(parts[0]) if len(parts) == 1 else (int(parts[0]), int(parts[1]))
 
 
 def parse_sa_window(text):
@@ -391,7 +405,8 @@ def get_spectogram_dataset_model_and_criterion(args, device):
                                sa_activation=getattr(args, "sa_activation", "relu"),
                                sa_conv_kernel=int(getattr(args, "sa_conv_kernel", 0)),
                                sa_dropout=float(getattr(args, "sa_dropout", 0.0)), sa_dropout_seed=getattr(args, "sa_dropout_seed", None),
-                               sa_window=parse_sa_window(getattr(args, "sa_window", None)))
+                               sa_window=parse_sa_window(getattr(args, "sa_window", None)),
+                               sa_rel_pos=parse_sa_rel_pos(getattr(args, "sa_rel_pos", None)))
     else:
         model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend, attention=att)
     model.set_precision(args.precision)
@@ -478,6 +493,7 @@ def validate_args(args):
         from .engine import CnnEngine
         CnnEngine.check_sa_dropout(getattr(args, "sa_dropout", 0.0))
         parse_sa_window(getattr(args, "sa_window", None))
+        CnnEngine.check_sa_rel_pos(parse_sa_rel_pos(getattr(args, "sa_rel_pos", None)))
     elif getattr(args, "sa_heads", 4) != 4 or getattr(args, "no_pos_encoding", False):
         raise ValueError("--sa_heads / --no_pos_encoding configure the self-attention head: they need --self_attention")
     elif getattr(args, "sa_layers", 1) != 1 or getattr(args, "sa_ffn", 0) != 0 or getattr(args, "sa_activation", "relu") != "relu":
@@ -488,6 +504,8 @@ def validate_args(args):
         raise ValueError("--sa_dropout / --sa_dropout_seed configure the self-attention head: they need --self_attention")
     elif getattr(args, "sa_window", None) is not None:
         raise ValueError("--sa_window configures the self-attention head: it needs --self_attention")
+    elif getattr(args, "sa_rel_pos", None) is not None:
+        raise ValueError("--sa_rel_pos configures the self-attention head: it needs --self_attention")
     for flag, value in (("--weak_pooling", weak_options(args).get("weak_pooling")), ("--eval_clip_pooling", getattr(args, "eval_clip_pooling", None))):
         if value == "att" and not att_head:
             raise ValueError(f"{flag} att pools with the attention head: it needs --attention_head")

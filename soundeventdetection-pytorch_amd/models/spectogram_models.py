@@ -478,6 +478,15 @@ def check_sa_conv_kernel(k) -> int:
     return k
 
 
+class _RelPosParams(nn.Module):
+    """Parameter holder of one layer's relative-position table: weight (heads, num_buckets) fp32, zeros (nothing is drawn)"""
+
+    def __init__(self, heads, num_buckets):
+        super().__init__()
+        self.heads, self.num_buckets = heads, num_buckets
+        self.weight = nn.Parameter(torch.zeros(heads, num_buckets))
+
+
 class Csa_AvgPooling(Cnn_AvgPooling):
     """The Cnn_AvgPooling feature extractor with a self-attention encoder layer as the temporal head (the conv-Transformer family
     of the DCASE task-4 systems; csrc/sed_mhsa.hip).  With R = B*t rows and C the last block's channels:
@@ -538,16 +547,35 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     receptive fields.  A float64 buffer window_config = (left, right), -1 for an unbounded side, exists only when a window is set
     (window_config_from_state_dict returns None without it); with sa_window = None the draws, the state_dict keys, the launches and
     the output bits are those of a model without the argument.
-    Refused: a negative or non-integer sa_window side, sa_dropout outside [0, 1), C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0, sa_layers < 1, sa_ffn not 0 or a multiple of 32 up to
+    sa_rel_pos = None, an int L >= 1 or a pair (num_buckets, max_distance): a learned relative-position bias per layer, head and bucket,
+    as T5 / WavLM / BEATs use it -- with d = j - i (key minus query, frames of the same clip)
+        s_ij = scale q_i . k_j + rel_pos.weight[g][bucket(d)]
+    which is torch's float attn_mask / src_mask (rel_pos_bias(state_dict, l, t) returns it, (H, t, t)); lse, p and ctx run over the
+    in-window keys, dropout and the window compose as before.  L: bucket(d) = clamp(d, -L, L) + L, 2L + 1 buckets.  (nb, maxd): T5's
+    bidirectional log buckets, nb even >= 4, maxd > nb / 4; n = nb / 2, a = |d|, m = n / 2: bucket = (n if d > 0 else 0) + (a if a < m
+    else min(n - 1, m + floor(ln(a / m) / ln(maxd / m) (n - m)))), in float64 (CnnEngine.rel_pos_map).  Every layer has its own table:
+    one module with a single fp32 parameter weight (sa_heads, num_buckets), initialised to zeros (no random number is drawn, every other
+    parameter keeps its initial value), registered BETWEEN that layer's attn* and attn_norm* -- layer 0 rel_pos, layer l >= 1
+    rel_pos_l{l} -- so the parameter order per layer is attn, rel_pos, attn_norm, convm, conv_norm, ffn, ffn_norm and the backward
+    completes the groups in exactly the reverse order (the table's gradient is ready right after the attention core's backward, before
+    in_proj's).  The kernels read a per-distance table built from the weights by one small launch per layer and forward
+    (sed_relpos_expand, sed_mhsa_fwd_rel / _bwd_rel, sed_relpos_fold; csrc/sed_mhsa.hip); the t x t bias and its gradient never
+    exist.  A float64 buffer rel_pos_config = (mode, a, b) -- (0, L, 0) or (1, nb, maxd) -- exists only when the option is set
+    (rel_pos_config_from_state_dict returns None without it); encoder_layer_state still returns TransformerEncoderLayer's keys only.
+    pos_encoding is an independent switch (the expected use is pos_encoding=False with sa_rel_pos).  With sa_rel_pos = None the
+    draws, the state_dict keys, the launches and the output bits are those of a model without the argument.
+    Refused: sa_rel_pos a non-integer or L < 1, num_buckets odd or < 4, max_distance <= num_buckets / 4, more than 4096 buckets,
+    a negative or non-integer sa_window side, sa_dropout outside [0, 1), C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0, sa_layers < 1, sa_ffn not 0 or a multiple of 32 up to
     4096 (and C > 512 with it), an activation other than relu / gelu, sa_conv_kernel even, below 3 or above 31 (before any draw)."""
 
     ACTIVATIONS = ("relu", "gelu")
 
     def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, sa_heads=4, pos_encoding=True,
                  mel_bins=None, frontend=None, attention=False, sa_layers=1, sa_ffn=0, sa_activation="relu", sa_conv_kernel=0,
-                 sa_dropout=0.0, sa_dropout_seed=None, sa_window=None):
+                 sa_dropout=0.0, sa_dropout_seed=None, sa_window=None, sa_rel_pos=None):
         self.sa_dropout = CnnEngine.check_sa_dropout(sa_dropout)          # (before any draw)
         self.sa_window = CnnEngine.check_sa_window(sa_window)
+        self.sa_rel_pos = CnnEngine.check_sa_rel_pos(sa_rel_pos)
         self.sa_dropout_seed = None if sa_dropout_seed is None else int(sa_dropout_seed)
         check_sa_geometry(int(model_config[-1][0]), sa_heads)
         check_sa_encoder(int(model_config[-1][0]), sa_layers, sa_ffn, sa_activation)
@@ -560,6 +588,8 @@ class Csa_AvgPooling(Cnn_AvgPooling):
         for l in range(self.sa_layers):
             an, nn_, fn, fnn = CnnEngine.sa_layer_names(l)
             setattr(self, an, _MhaParams(c_last, self.sa_heads))
+            if self.sa_rel_pos is not None:
+                setattr(self, CnnEngine.sa_rel_name(l), _RelPosParams(self.sa_heads, CnnEngine.rel_pos_buckets(self.sa_rel_pos)))
             setattr(self, nn_, _LayerNormParams(c_last))
             if l == 0:
                 self.register_buffer("attn_config", torch.tensor([float(self.sa_heads), float(self.pos_encoding)], dtype=torch.float64))
@@ -577,13 +607,18 @@ class Csa_AvgPooling(Cnn_AvgPooling):
                                                                  float(self.ACTIVATIONS.index(self.sa_activation))], dtype=torch.float64))
         if self.sa_window is not None:
             self.register_buffer("window_config", torch.tensor([-1.0 if v is None else float(v) for v in self.sa_window], dtype=torch.float64))
+        if self.sa_rel_pos is not None:
+            mode = self.sa_rel_pos[0] == "log"
+            self.register_buffer("rel_pos_config", torch.tensor([float(mode), float(self.sa_rel_pos[1]),
+                                                                 float(self.sa_rel_pos[2]) if mode else 0.0], dtype=torch.float64))
         self.event_fc = _LinearParams(c_last, classes_num)
 
     def _make_engine(self, precision):
         return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="sa", sa_heads=self.sa_heads,
                          pos_encoding=self.pos_encoding, mel_bins=self.mel_bins, attention=self.attention, sa_layers=self.sa_layers,
                          sa_ffn=self.sa_ffn, sa_activation=self.sa_activation, sa_conv_kernel=self.sa_conv_kernel,
-                         sa_dropout=self.sa_dropout, sa_dropout_seed=self.sa_dropout_seed, sa_window=self.sa_window)
+                         sa_dropout=self.sa_dropout, sa_dropout_seed=self.sa_dropout_seed, sa_window=self.sa_window,
+                         sa_rel_pos=self.sa_rel_pos)
 
     def _flush_counters(self):
         """The convolution modules' BatchNorm counters follow the conv blocks': counted on the host, folded in when looked at."""
@@ -607,6 +642,26 @@ class Csa_AvgPooling(Cnn_AvgPooling):
             return None
         cfg = weights["window_config"].detach().cpu().double().tolist()
         return tuple(None if v < 0 else int(round(v)) for v in cfg[:2])
+
+    @staticmethod
+    def rel_pos_config_from_state_dict(weights):
+        """sa_rel_pos = L or (num_buckets, max_distance) from a state_dict's rel_pos_config; None when the buffer is absent"""
+        if "rel_pos_config" not in weights:
+            return None
+        mode, a, b = (int(round(v)) for v in weights["rel_pos_config"].detach().cpu().double().tolist()[:3])
+        return (a, b) if mode else a
+
+    @staticmethod
+    def rel_pos_bias(weights, layer, t):
+        """(H, t, t) float tensor: layer `layer`'s bias bias[g][i][j] = weight[g][bucket(j - i)] as torch's additive attn_mask / src_mask
+        (repeat it over the clips for a 3-D mask), in the weight's dtype on the CPU"""
+        cfg = CnnEngine.check_sa_rel_pos(Csa_AvgPooling.rel_pos_config_from_state_dict(weights))
+        if cfg is None:
+            raise ValueError("the state_dict has no rel_pos_config: the model was built without sa_rel_pos")
+        w = weights[CnnEngine.sa_rel_name(layer) + ".weight"].detach().cpu()
+        m = torch.from_numpy(CnnEngine.rel_pos_map(cfg, t).astype("int64"))
+        i = torch.arange(t)
+        return w[:, m[(i[None, :] - i[:, None]) + t - 1]]
 
     @staticmethod
     def conv_module_state(weights, layer):
