@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "common.h"
 
 struct PhiloxWords { uint32_t w[4]; };
 
@@ -87,4 +88,9 @@ static inline bool drop_host_args(float p, const uint32_t* rng, uint32_t stream_
     out->thr = (uint32_t)f;
     out->scale = (float)(1.0 / (1.0 - (double)p));
     return true;
+}
+// the same behind an entry: the refusal and its error code
+static inline int drop_require_args(float p, const uint32_t* rng, uint32_t stream_id, DropArgs* out) {
+    SED_REQUIRE(drop_host_args(p, rng, stream_id, out), "the dropout probability must lie in [0, 1)");
+    return 0;
 }

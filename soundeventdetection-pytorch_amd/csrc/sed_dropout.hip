@@ -34,7 +34,7 @@ extern "C" int sed_dropout_mask(unsigned char* keep, int kind, size_t n0, int n1
     SED_REQUIRE(keep != nullptr && rng != nullptr, "keep and the dropout state rng are required");
     SED_REQUIRE(n0 > 0 && n1 > 0 && (kind == SED_DROP_ROWS || t > 0), "sizes must be positive");
     DropArgs d;
-    SED_REQUIRE(drop_host_args(p, rng, stream_id, &d), "the dropout probability must lie in [0, 1)");
+    if (int rc = drop_require_args(p, rng, stream_id, &d)) return rc;
     const bool attn = kind == SED_DROP_ATTN;
     SED_REQUIRE(!attn || n0 * (size_t)n1 < ((size_t)1 << 32), "B * H must stay below 2^32");
     const size_t rows = attn ? n0 * (size_t)n1 * (size_t)t : n0;

@@ -353,7 +353,7 @@ extern "C" int sed_ffn_fwd_drop(int dtype, int act, const float* x, const float*
                                 void* stream) {
     SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
     DropArgs d;
-    SED_REQUIRE(drop_host_args(p, rng, stream_id, &d), "the dropout probability must lie in [0, 1)");
+    if (int rc = drop_require_args(p, rng, stream_id, &d)) return rc;
     if (d.thr == 0) return ffn_fwd_entry<false>(dtype, act, x, w1, b1, w2, b2, y, u, R, C, D, d, stream);      // (no dropout: sed_mhsa.hip)
     return ffn_fwd_entry<true>(dtype, act, x, w1, b1, w2, b2, y, u, R, C, D, d, stream);
 }
@@ -363,7 +363,7 @@ extern "C" int sed_ffn_act_bwd_drop(int act, const float* u, const float* da, fl
                                     const uint32_t* rng, uint32_t stream_id, void* stream) {
     SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
     DropArgs d;
-    SED_REQUIRE(drop_host_args(p, rng, stream_id, &d), "the dropout probability must lie in [0, 1)");
+    if (int rc = drop_require_args(p, rng, stream_id, &d)) return rc;
     SED_REQUIRE(R > 0 && D > 0 && D % 4 == 0, "R and D must be positive, D a multiple of 4");
     SED_REQUIRE(R < ((size_t)1 << 38) / (size_t)D, "R * D must stay below 2^38");
     if (d.thr == 0) return ffn_act_bwd_entry<false>(act, u, da, a, du, R * (size_t)D, D, d, stream);

@@ -93,6 +93,7 @@
 #include "common.h"
 #include "philox.h"
 #include <math.h>
+#include <type_traits>
 
 #define MHSA_QT 32            // queries (or keys) a wave owns
 #define MHSA_WAVES 4          // waves per workgroup, each with its own tile
@@ -198,6 +199,15 @@ struct MhsaParams {
     int relspan;
 };
 
+// A thread's place in a core launch: workgroup blockIdx.x is tile `tile` (128 rows) of clip b and head g, its wave `wave` owns the 32 rows
+// from row0 (queries, or keys in the dK / dV pass); r = the lane's row or column inside a 32 x 32 tile, h = its half-wave
+template <int DH> struct WaveTile {
+    int lane, wave, r, h, bh, tile, b, g, C, ld, row0;
+    __device__ __forceinline__ explicit WaveTile(const MhsaParams& p)
+        : lane(threadIdx.x & 63), wave(threadIdx.x >> 6), r(lane & 31), h(lane >> 5), bh(blockIdx.x / p.ntile), tile(blockIdx.x % p.ntile),
+          b(bh / p.H), g(bh % p.H), C(p.H * DH), ld(3 * C), row0((tile * MHSA_WAVES + wave) * MHSA_QT) {}
+};
+
 // ---- the local window: the tiles a wave walks --------------------------------------------------------------------------------------
 // A wave (span 32) or a workgroup (span 128) that owns rows [a0, a0 + span - 1], a0 < t, of one index walks the tiles of 32 of the
 // OTHER index that intersect [a0 - before, a0 + span - 1 + after] with [0, t): tile starts lo, lo + 32, ... < hi.  Queries own keys
@@ -240,6 +250,28 @@ __device__ __forceinline__ int rel_slots(int c0, int hi) {
     const int rows = ((hi - c0 + MHSA_QT - 1) & ~(MHSA_QT - 1)) < REL_CHUNK ? ((hi - c0 + MHSA_QT - 1) & ~(MHSA_QT - 1)) : REL_CHUNK;
     return rows + 31;
 }
+// A wave's slice over its walk from row lo: the slice (REL only: the other instantiations hold no LDS for it) and the start c0 of the
+// staged chunk.  tile() at the top of the tile at walked row x0 restages where a chunk starts (own0: the wave's first own row, hi: the
+// walk's end, dir as above); at() is the bias of the cell in register i of the tile at x0.
+template <bool REL> struct RelWalk {
+    float* relw = nullptr;
+    int lo, c0;
+    __device__ __forceinline__ RelWalk(int wave, int lo_) : lo(lo_), c0(lo_) {
+        if constexpr (REL) {
+            __shared__ float relsm[MHSA_WAVES * REL_PITCH];
+            relw = relsm + wave * REL_PITCH;
+        }
+    }
+    __device__ __forceinline__ void tile(const MhsaParams& p, int g, int own0, int x0, int hi, int dir, int lane) {
+        if constexpr (REL) {
+            if (((x0 - lo) & (REL_CHUNK - 1)) == 0) {
+                c0 = x0;
+                rel_stage(relw, p.rel + (size_t)g * (2 * p.t - 1), dir * (c0 - own0 - 31) + p.t - 1, dir, rel_slots(c0, hi), p.t, lane);
+            }
+        }
+    }
+    __device__ __forceinline__ float at(int x0, int i, int h, int r) const { return relw[(x0 - c0) + acc_row(i, h) + 31 - r]; }
+};
 
 // store the transposed 32 x 32 tile o (column c = acc_row(i, h) in the registers, row on the lane) times f into row `dst` (head columns)
 __device__ __forceinline__ void store_tile_t(float* __restrict__ dst, const f32x16& o, float f, int h) {
@@ -270,6 +302,40 @@ __device__ __forceinline__ void drop_scores_t(f32x16& s, const DropArgs& d, int 
 #pragma unroll
     for (int n = 0; n < 16; ++n) s[n] *= ms[n];
 }
+
+// One tile of the forward's running softmax, both forward kernels': s holds the products of the keys k0 + acc_row(i, h) with the lane's
+// query w.row0 + w.r and leaves as the P V operand, exp(s - m_run) (DROP: times m s); m and l are the query's running maximum and sum
+// (of the undropped probabilities).  Returns alpha = exp(m_old - m_new), what the query's O so far is rescaled by.
+template <bool DROP, bool WIN, bool REL, int DH>
+__device__ __forceinline__ float softmax_tile(f32x16& s, float& m, float& l, const MhsaParams& p, const WaveTile<DH>& w, int k0,
+                                              const RelWalk<REL>& rw) {
+    const int t = p.t, q0 = w.row0, r = w.r, h = w.h;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int j = k0 + acc_row(i, h);
+        if constexpr (REL)
+            s[i] = j < t && in_window(q0 + r, j, p.wl, p.wr) ? s[i] * p.scale + rw.at(k0, i, h, r) : -INFINITY;
+        else
+            s[i] = j < t && (!WIN || in_window(q0 + r, j, p.wl, p.wr)) ? s[i] * p.scale : -INFINITY;
+        mx = fmaxf(mx, s[i]);
+    }
+    mx = fmaxf(mx, xor32(mx));
+    // plain: finite from the first tile on (key k0 is always inside the clip).  WIN: a query's first visited tiles can lie wholly
+    // left of its window (left = 3, queries 32 ... 63 start at key tile 0, where query 40 has no key): the maximum is still -inf
+    // there, and the reference point 0 makes alpha and every probability exp(-inf) = 0 instead of exp(-inf + inf)
+    const float mx2 = fmaxf(m, mx);
+    const float mn = WIN && mx2 == -INFINITY ? 0.f : mx2;
+    const float alpha = expf(m - mn);
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { s[i] = expf(s[i] - mn); sum += s[i]; }
+    sum += xor32(sum);
+    l = l * alpha + sum;
+    m = WIN ? mx2 : mn;
+    if (DROP) drop_scores_t(s, p.drop, k0, q0 + r, w.bh, h);
+    return alpha;
+}
 template <int J> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {      // lane J of the quad to its four lanes
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, J * 0x55, 0xF, 0xF, true);
 }
@@ -296,12 +362,10 @@ __device__ __forceinline__ void drop_factors_k(float (&ms)[16], const DropArgs& 
 template <typename T, int DH, bool DROP, bool WIN, bool REL = false>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p) {
     static_assert(WIN || !REL, "REL is instantiated with WIN only");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
-    const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
-    const int q0 = (tile * MHSA_WAVES + wave) * MHSA_QT;
+    const WaveTile<DH> w(p);
+    const int t = p.t, q0 = w.row0, r = w.r, h = w.h, C = w.C, ld = w.ld;
     if (q0 >= t) return;                               // (no barrier in this kernel)
-    const float* __restrict__ base = p.qkv + (size_t)b * t * ld + g * DH;
+    const float* __restrict__ base = p.qkv + (size_t)w.b * t * ld + w.g * DH;
     const int qr = q0 + r < t ? q0 + r : t - 1;
     RowFrag<T, DH> qf;
     qf.load(base + qr * ld, h);
@@ -316,19 +380,9 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
     kn.load(base + C + (kt.lo + r < t ? kt.lo + r : t - 1) * ld, h);
 #pragma unroll
     for (int cb = 0; cb < DH / 32; ++cb) load_col(vn[cb], base + 2 * C + cb * 32 + r, ld, kt.lo, t, h);
-    float* relw = nullptr;
-    if constexpr (REL) {
-        __shared__ float relsm[MHSA_WAVES * REL_PITCH];
-        relw = relsm + wave * REL_PITCH;
-    }
-    int kc = kt.lo;                                    // REL: the start of the staged chunk
+    RelWalk<REL> rw(w.wave, kt.lo);
     for (int k0 = kt.lo; k0 < kt.hi; k0 += 32) {
-        if constexpr (REL) {
-            if (((k0 - kt.lo) & (REL_CHUNK - 1)) == 0) {
-                kc = k0;
-                rel_stage(relw, p.rel + (size_t)g * (2 * t - 1), kc - q0 - 31 + t - 1, 1, rel_slots(kc, kt.hi), t, lane);
-            }
-        }
+        rw.tile(p, w.g, q0, k0, kt.hi, 1, w.lane);
         const RowFrag<T, DH> kf = kn;
         float va[DH / 32][16];
 #pragma unroll
@@ -342,30 +396,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
             for (int cb = 0; cb < DH / 32; ++cb) load_col(vn[cb], base + 2 * C + cb * 32 + r, ld, k0 + 32, t, h);
         }
         f32x16 s = mm_rows<T, DH>(kf, qf);             // s[key][query]
-        float mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int j = k0 + acc_row(i, h);
-            if constexpr (REL)
-                s[i] = j < t && in_window(q0 + r, j, p.wl, p.wr) ? s[i] * p.scale + relw[(k0 - kc) + acc_row(i, h) + 31 - r] : -INFINITY;
-            else
-                s[i] = j < t && (!WIN || in_window(q0 + r, j, p.wl, p.wr)) ? s[i] * p.scale : -INFINITY;
-            mx = fmaxf(mx, s[i]);
-        }
-        mx = fmaxf(mx, xor32(mx));
-        // plain: finite from the first tile on (key k0 is always inside the clip).  WIN: a query's first visited tiles can lie wholly
-        // left of its window (left = 3, queries 32 ... 63 start at key tile 0, where query 40 has no key): the maximum is still -inf
-        // there, and the reference point 0 makes alpha and every probability exp(-inf) = 0 instead of exp(-inf + inf)
-        const float mx2 = fmaxf(m, mx);
-        const float mn = WIN && mx2 == -INFINITY ? 0.f : mx2;
-        const float alpha = expf(m - mn);
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { s[i] = expf(s[i] - mn); sum += s[i]; }
-        sum += xor32(sum);
-        l = l * alpha + sum;
-        m = WIN ? mx2 : mn;
-        if (DROP) drop_scores_t(s, p.drop, k0, q0 + r, bh, h);
+        const float alpha = softmax_tile<DROP, WIN, REL>(s, m, l, p, w, k0, rw);
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) {
 #pragma unroll
@@ -375,10 +406,10 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_kernel(MhsaParams p)
     }
     if (q0 + r < t) {
         const float inv = 1.f / l;
-        float* __restrict__ dst = p.out + ((size_t)b * t + q0 + r) * C + g * DH;
+        float* __restrict__ dst = p.out + ((size_t)w.b * t + q0 + r) * C + w.g * DH;
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) store_tile_t(dst + cb * 32, o[cb], inv, h);
-        if (p.lse_out != nullptr && h == 0) p.lse_out[(size_t)bh * t + q0 + r] = m + logf(l);
+        if (p.lse_out != nullptr && h == 0) p.lse_out[(size_t)w.bh * t + q0 + r] = m + logf(l);
     }
 }
 
@@ -393,12 +424,10 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParam
     constexpr int KP = DH + 8, VP = 36, NL = DH / 32, RQ = DH / 4;       // NL 16-byte loads of K and of V per thread and tile
     __shared__ __attribute__((aligned(16))) bf16_t ks[2][32 * KP];
     __shared__ __attribute__((aligned(16))) bf16_t vt[2][DH * VP];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
-    const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
-    const int q0 = (tile * MHSA_WAVES + wave) * MHSA_QT;
+    const WaveTile<DH> w(p);
+    const int tid = threadIdx.x, t = p.t, q0 = w.row0, r = w.r, h = w.h, C = w.C, ld = w.ld;
     const bool active = q0 < t;
-    const float* __restrict__ base = p.qkv + (size_t)b * t * ld + g * DH;
+    const float* __restrict__ base = p.qkv + (size_t)w.b * t * ld + w.g * DH;
     const int qr = q0 + r < t ? q0 + r : t - 1;
     RowFrag<bf16_t, DH> qf;
     qf.load(base + qr * ld, h);
@@ -431,53 +460,23 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParam
     float m = -INFINITY, l = 0.f;
     // WIN: the workgroup stages the union of its waves' ranges (the range of its 128 queries: wg, the same in every thread); a wave
     // computes on the tiles of its own range (mine) and only stages and waits on the others
-    const TileRange wg = WIN ? mhsa_win_range(tile * MHSA_WAVES * MHSA_QT, MHSA_WAVES * MHSA_QT, t, p.wl, p.wr) : TileRange{0, t};
+    const TileRange wg = WIN ? mhsa_win_range(w.tile * MHSA_WAVES * MHSA_QT, MHSA_WAVES * MHSA_QT, t, p.wl, p.wr) : TileRange{0, t};
     const TileRange mine = WIN && active ? mhsa_win_range(q0, MHSA_QT, t, p.wl, p.wr) : TileRange{0, t};
     gload(wg.lo);
     lstore(0);
     __syncthreads();
-    float* relw = nullptr;
-    if constexpr (REL) {
-        __shared__ float relsm[MHSA_WAVES * REL_PITCH];
-        relw = relsm + wave * REL_PITCH;
-    }
-    int kc = mine.lo;                                  // REL: the start of the wave's staged chunk
+    RelWalk<REL> rw(w.wave, mine.lo);                  // (the wave's own walk)
     for (int k0 = wg.lo, it = 0; k0 < wg.hi; k0 += 32, ++it) {
         const int cur = it & 1;
         const bool more = k0 + 32 < wg.hi;             // (the same in every thread: the barrier below is uniform)
         if (more) gload(k0 + 32);
         if (active && (!WIN || (k0 >= mine.lo && k0 < mine.hi))) {
-            if constexpr (REL) {
-                if (((k0 - mine.lo) & (REL_CHUNK - 1)) == 0) {
-                    kc = k0;
-                    rel_stage(relw, p.rel + (size_t)g * (2 * t - 1), kc - q0 - 31 + t - 1, 1, rel_slots(kc, mine.hi), t, lane);
-                }
-            }
+            rw.tile(p, w.g, q0, k0, mine.hi, 1, w.lane);
             RowFrag<bf16_t, DH> kf;
 #pragma unroll
             for (int s = 0; s < DH / 16; ++s) kf.f[s] = *reinterpret_cast<const bf16x8*>(&ks[cur][r * KP + 16 * s + 8 * h]);
             f32x16 s = mm_rows<bf16_t, DH>(kf, qf);    // s[key][query]
-            float mx = -INFINITY;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int j = k0 + acc_row(i, h);
-                if constexpr (REL)
-                    s[i] = j < t && in_window(q0 + r, j, p.wl, p.wr) ? s[i] * p.scale + relw[(k0 - kc) + acc_row(i, h) + 31 - r] : -INFINITY;
-                else
-                    s[i] = j < t && (!WIN || in_window(q0 + r, j, p.wl, p.wr)) ? s[i] * p.scale : -INFINITY;
-                mx = fmaxf(mx, s[i]);
-            }
-            mx = fmaxf(mx, xor32(mx));
-            const float mx2 = fmaxf(m, mx);
-            const float mn = WIN && mx2 == -INFINITY ? 0.f : mx2;      // (as in mhsa_fwd_kernel: no key of this query yet)
-            const float alpha = expf(m - mn);
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { s[i] = expf(s[i] - mn); sum += s[i]; }
-            sum += xor32(sum);
-            l = l * alpha + sum;
-            m = WIN ? mx2 : mn;
-            if (DROP) drop_scores_t(s, p.drop, k0, q0 + r, bh, h);
+            const float alpha = softmax_tile<DROP, WIN, REL>(s, m, l, p, w, k0, rw);
 #pragma unroll
             for (int cb = 0; cb < NL; ++cb) {
 #pragma unroll
@@ -500,10 +499,10 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_fwd_lds_kernel(MhsaParam
     }
     if (active && q0 + r < t) {
         const float inv = 1.f / l;
-        float* __restrict__ dst = p.out + ((size_t)b * t + q0 + r) * C + g * DH;
+        float* __restrict__ dst = p.out + ((size_t)w.b * t + q0 + r) * C + w.g * DH;
 #pragma unroll
         for (int cb = 0; cb < NL; ++cb) store_tile_t(dst + cb * 32, o[cb], inv, h);
-        if (p.lse_out != nullptr && h == 0) p.lse_out[(size_t)bh * t + q0 + r] = m + logf(l);
+        if (p.lse_out != nullptr && h == 0) p.lse_out[(size_t)w.bh * t + q0 + r] = m + logf(l);
     }
 }
 
@@ -530,15 +529,13 @@ __global__ __launch_bounds__(256) void mhsa_rowdot_kernel(MhsaParams p, int B, i
 template <typename T, int DH, bool DROP, bool WIN, bool REL = false>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams p) {
     static_assert(WIN || !REL, "REL is instantiated with WIN only");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
-    const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
-    const int k0 = (tile * MHSA_WAVES + wave) * MHSA_QT;
+    const WaveTile<DH> w(p);
+    const int t = p.t, k0 = w.row0, r = w.r, h = w.h, C = w.C, ld = w.ld;
     if (k0 >= t) return;
-    const float* __restrict__ base = p.qkv + (size_t)b * t * ld + g * DH;
-    const float* __restrict__ dbase = p.dctx + (size_t)b * t * C + g * DH;
-    const float* __restrict__ lse = p.lse + (size_t)bh * t;
-    const float* __restrict__ D = p.D + (size_t)bh * t;
+    const float* __restrict__ base = p.qkv + (size_t)w.b * t * ld + w.g * DH;
+    const float* __restrict__ dbase = p.dctx + (size_t)w.b * t * C + w.g * DH;
+    const float* __restrict__ lse = p.lse + (size_t)w.bh * t;
+    const float* __restrict__ D = p.D + (size_t)w.bh * t;
     const int kr = k0 + r < t ? k0 + r : t - 1;
     RowFrag<T, DH> kf, vf;
     kf.load(base + C + kr * ld, h);
@@ -566,25 +563,15 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
     // only, so it can overflow)
     auto live = [&](int q) { return q < t && (!WIN || (k0 + r < t && in_window(q, k0 + r, p.wl, p.wr))); };
     load_rows(qt.lo);
-    float* relw = nullptr;
-    if constexpr (REL) {
-        __shared__ float relsm[MHSA_WAVES * REL_PITCH];
-        relw = relsm + wave * REL_PITCH;
-    }
-    int qc = qt.lo;                                    // REL: the start of the staged chunk
+    RelWalk<REL> rw(w.wave, qt.lo);
     // what the scaled product of cell (query q0 + acc_row(i, h), key k0 + r) is reduced by under the exponential: lse_i, REL: lse_i - rel
     // (the expression keeps the shape scale * s - c of the other instantiations: a zero table gives their bits whatever is contracted)
     auto under = [&](float l, int q0, int i) {
-        if constexpr (REL) return l - relw[(q0 - qc) + acc_row(i, h) + 31 - r];
+        if constexpr (REL) return l - rw.at(q0, i, h, r);
         else return l;
     };
     for (int q0 = qt.lo; q0 < qt.hi; q0 += 32) {
-        if constexpr (REL) {
-            if (((q0 - qt.lo) & (REL_CHUNK - 1)) == 0) {
-                qc = q0;
-                rel_stage(relw, p.rel + (size_t)g * (2 * t - 1), k0 + 31 - qc + t - 1, -1, rel_slots(qc, qt.hi), t, lane);
-            }
-        }
+        rw.tile(p, w.g, k0, q0, qt.hi, -1, w.lane);
         const RowFrag<T, DH> qf = qn, df = dn;
         float lc[16], Dc[16], qa[DH / 32][16], da[DH / 32][16];
 #pragma unroll
@@ -597,21 +584,16 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
         if (q0 + 32 < qt.hi) load_rows(q0 + 32);
         f32x16 s = mm_rows<T, DH>(qf, kf);             // s[query][key]
         f32x16 dp = mm_rows<T, DH>(df, vf);
-        if (DROP) {
-            float ms[16];
-            drop_factors_k(ms, p.drop, k0 + r, q0, bh, h);
+        float ms[16];
+        if constexpr (DROP) drop_factors_k(ms, p.drop, k0 + r, q0, w.bh, h);
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const bool in = live(q0 + acc_row(i, h));
-                const float pr = in ? expf(s[i] * p.scale - under(lc[i], q0, i)) : 0.f;
+        for (int i = 0; i < 16; ++i) {
+            const bool in = live(q0 + acc_row(i, h));
+            const float pr = in ? expf(s[i] * p.scale - under(lc[i], q0, i)) : 0.f;
+            if constexpr (DROP) {
                 s[i] = pr * ms[i];                       // p~ for dV
                 dp[i] = !WIN || in ? pr * (dp[i] * ms[i] - Dc[i]) : 0.f;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const bool in = live(q0 + acc_row(i, h));
-                const float pr = in ? expf(s[i] * p.scale - under(lc[i], q0, i)) : 0.f;
+            } else {
                 s[i] = pr;
                 dp[i] = !WIN || in ? pr * (dp[i] - Dc[i]) : 0.f;
             }
@@ -623,7 +605,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
         }
     }
     if (k0 + r < t) {
-        float* __restrict__ dst = p.out + ((size_t)b * t + k0 + r) * ld + g * DH;
+        float* __restrict__ dst = p.out + ((size_t)w.b * t + k0 + r) * ld + w.g * DH;
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) {
             store_tile_t(dst + C + cb * 32, dk[cb], p.scale, h);
@@ -636,15 +618,13 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_kv_kernel(MhsaParams
 template <typename T, int DH, bool DROP, bool WIN, bool REL = false>
 __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams p) {
     static_assert(WIN || !REL, "REL is instantiated with WIN only");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int bh = blockIdx.x / p.ntile, tile = blockIdx.x % p.ntile;
-    const int b = bh / p.H, g = bh % p.H, t = p.t, C = p.H * DH, ld = 3 * C;
-    const int q0 = (tile * MHSA_WAVES + wave) * MHSA_QT;
+    const WaveTile<DH> w(p);
+    const int t = p.t, q0 = w.row0, lane = w.lane, r = w.r, h = w.h, C = w.C, ld = w.ld;
     if (q0 >= t) return;
-    const float* __restrict__ base = p.qkv + (size_t)b * t * ld + g * DH;
-    const float* __restrict__ dbase = p.dctx + (size_t)b * t * C + g * DH;
+    const float* __restrict__ base = p.qkv + (size_t)w.b * t * ld + w.g * DH;
+    const float* __restrict__ dbase = p.dctx + (size_t)w.b * t * C + w.g * DH;
     const int qr = q0 + r < t ? q0 + r : t - 1;
-    const float lse = p.lse[(size_t)bh * t + qr], Dq = p.D[(size_t)bh * t + qr];
+    const float lse = p.lse[(size_t)w.bh * t + qr], Dq = p.D[(size_t)w.bh * t + qr];
     RowFrag<T, DH> qf, df;
     qf.load(base + qr * ld, h);
     df.load(dbase + qr * C, h);
@@ -660,25 +640,15 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
     };
     const TileRange kt = WIN ? mhsa_win_range(q0, MHSA_QT, t, p.wl, p.wr) : TileRange{0, t};
     load_rows(kt.lo);
-    float* relw = nullptr;
-    if constexpr (REL) {
-        __shared__ float relsm[MHSA_WAVES * REL_PITCH];
-        relw = relsm + wave * REL_PITCH;
-    }
-    int kc = kt.lo;                                    // REL: the start of the staged chunk
+    RelWalk<REL> rw(w.wave, kt.lo);
     // REL: the wave's partial of drel.  Slot x of its workspace row is distance (kt.lo - q0 - 31) + x; a tile at k0 meets slots
     // (k0 - kt.lo) + 0 ... 62, lane X of `carry` holding slot (k0 - kt.lo) + X: the lower 32 are complete after this tile and are
     // stored, the upper 31 move down to meet the next tile; the row ends with the last tile's upper half.
     float carry = 0.f;
     float* __restrict__ wsrow = nullptr;
-    if constexpr (REL) wsrow = p.relws + ((size_t)blockIdx.x * MHSA_WAVES + wave) * p.relspan;
+    if constexpr (REL) wsrow = p.relws + ((size_t)blockIdx.x * MHSA_WAVES + w.wave) * p.relspan;
     for (int k0 = kt.lo; k0 < kt.hi; k0 += 32) {
-        if constexpr (REL) {
-            if (((k0 - kt.lo) & (REL_CHUNK - 1)) == 0) {
-                kc = k0;
-                rel_stage(relw, p.rel + (size_t)g * (2 * t - 1), kc - q0 - 31 + t - 1, 1, rel_slots(kc, kt.hi), t, lane);
-            }
-        }
+        rw.tile(p, w.g, q0, k0, kt.hi, 1, lane);
         const RowFrag<T, DH> kf = kn, vf = vn;
         float ka[DH / 32][16];
 #pragma unroll
@@ -688,7 +658,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
         f32x16 dp = mm_rows<T, DH>(vf, df);
         if (DROP) {
             float ms[16];
-            drop_factors_t(ms, p.drop, k0, q0 + r, bh, h);
+            drop_factors_t(ms, p.drop, k0, q0 + r, w.bh, h);
 #pragma unroll
             for (int i = 0; i < 16; ++i) dp[i] *= ms[i];
         }
@@ -697,7 +667,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
             const int j = k0 + acc_row(i, h);
             const bool in = j < t && (!WIN || (q0 + r < t && in_window(q0 + r, j, p.wl, p.wr)));   // (select: see mhsa_bwd_kv_kernel)
             float lr = lse;                             // REL: lse - rel, the expression's shape kept (see mhsa_bwd_kv_kernel)
-            if constexpr (REL) lr = lse - relw[(k0 - kc) + acc_row(i, h) + 31 - r];
+            if constexpr (REL) lr = lse - rw.at(k0, i, h, r);
             const float pr = in ? expf(s[i] * p.scale - lr) : 0.f;
             dp[i] = !WIN || in ? pr * (dp[i] - Dq) : 0.f;
         }
@@ -725,7 +695,7 @@ __global__ __launch_bounds__(64 * MHSA_WAVES) void mhsa_bwd_q_kernel(MhsaParams 
         if (lane >= 32) wsrow[((kt.hi - kt.lo + MHSA_QT - 1) & ~(MHSA_QT - 1)) + lane - 32] = carry;
     }
     if (q0 + r < t) {
-        float* __restrict__ dst = p.out + ((size_t)b * t + q0 + r) * ld + g * DH;
+        float* __restrict__ dst = p.out + ((size_t)w.b * t + q0 + r) * ld + w.g * DH;
 #pragma unroll
         for (int cb = 0; cb < DH / 32; ++cb) store_tile_t(dst + cb * 32, dq[cb], p.scale, h);
     }
@@ -1002,80 +972,114 @@ int mhsa_check(int dtype, int B, int t, int H, int dh, long long* nblocks, int* 
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 
-}  // namespace
+// ---- the options of a core launch: dropout, window and table, as every entry hands them to the two launchers ------------------------
+// drop.thr = 0 (p below 2^-33: every cell kept, s = 1 exactly) is no dropout by definition and takes the DROP = false instantiation, so
+// p = 0 gives the plain entry's bits whatever the compiler contracts where.  win: a bounded side, or a table (both sides unbounded is a
+// valid window for the REL kernels: every tile is visited and the select never masks); without either the launch is the WIN = false
+// instantiation, plain or DROP.
+struct MhsaOpts {
+    DropArgs drop;
+    bool win;
+    int wl, wr;          // the sides, clamped to t - 1
+    const float* rel;
+    float* drel;
+};
 
-namespace {
-// wl, wr: the window, already clamped to [0, t - 1] (WIN only)
-template <bool DROP, bool WIN = false, bool REL = false>
-int mhsa_fwd_launch(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, const DropArgs& drop, void* stream,
-                    int wl = 0, int wr = 0, const float* rel = nullptr) {
+// a side clamped to t - 1: one that reaches the clip's end from every query is unbounded
+inline int mhsa_win_side(int side, int t) {
+    const int cap = t > 0 ? t - 1 : 0;
+    return side < cap ? side : cap;
+}
+
+// p = 0: no dropout, rng may be NULL
+int mhsa_opts(MhsaOpts* o, int t, int left, int right, float p, const uint32_t* rng, uint32_t stream_id, const float* rel, float* drel) {
+    SED_REQUIRE(left >= 0 && right >= 0, "the window sides left and right must be >= 0");
+    if (int rc = drop_require_args(p, rng, stream_id, &o->drop)) return rc;
+    SED_REQUIRE(o->drop.thr == 0 || rng != nullptr, "the dropout state rng is required when p > 0");
+    o->wl = mhsa_win_side(left, t);
+    o->wr = mhsa_win_side(right, t);
+    const int cap = mhsa_win_side(SED_WIN_UNBOUNDED, t);
+    o->win = rel != nullptr || o->wl != cap || o->wr != cap;
+    o->rel = rel;
+    o->drel = drel;
+    return 0;
+}
+
+// f(MhsaKernel<T, DH, DROP, WIN, REL>{}) for the instantiation of (dtype, dh) and the options; REL comes with WIN only
+template <typename T_, int DH, bool DROP, bool WIN, bool REL> struct MhsaKernel {
+    using T = T_;
+    static constexpr int dh = DH;
+    static constexpr bool drop = DROP, win = WIN, rel = REL;
+};
+template <typename F> void mhsa_dispatch(int dtype, int dh, const MhsaOpts& o, F f) {
+    auto by_size = [&](auto drop, auto win, auto rel) {
+        constexpr bool D = decltype(drop)::value, W = decltype(win)::value, R = decltype(rel)::value;
+        if (dtype == SED_BF16) {
+            if (dh == 32) f(MhsaKernel<bf16_t, 32, D, W, R>{});
+            else f(MhsaKernel<bf16_t, 64, D, W, R>{});
+        } else {
+            if (dh == 32) f(MhsaKernel<float, 32, D, W, R>{});
+            else f(MhsaKernel<float, 64, D, W, R>{});
+        }
+    };
+    auto by_drop = [&](auto win, auto rel) {
+        if (o.drop.thr != 0) by_size(std::true_type{}, win, rel);
+        else by_size(std::false_type{}, win, rel);
+    };
+    if (o.rel != nullptr) by_drop(std::true_type{}, std::true_type{});
+    else if (o.win) by_drop(std::true_type{}, std::false_type{});
+    else by_drop(std::false_type{}, std::false_type{});
+}
+
+int mhsa_fwd_launch(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, const MhsaOpts& o, void* stream) {
     long long nb; int ntile;
     if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
     SED_REQUIRE(qkv != nullptr && ctx != nullptr, "qkv and ctx are required");
     SED_REQUIRE(aligned16(qkv) && aligned16(ctx), "qkv and ctx must be 16-byte aligned");
     MhsaParams p = {};
     p.qkv = qkv; p.out = ctx; p.lse_out = lse; p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
-    p.drop = drop;
-    p.wl = wl; p.wr = wr;
-    p.rel = rel;
+    p.drop = o.drop;
+    p.wl = o.wl; p.wr = o.wr;
+    p.rel = o.rel;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
-    if (dtype == SED_BF16) {
-        if (dh == 32) mhsa_fwd_lds_kernel<32, DROP, WIN, REL><<<grid, block, 0, st>>>(p);
-        else mhsa_fwd_lds_kernel<64, DROP, WIN, REL><<<grid, block, 0, st>>>(p);
-    } else {
-        if (dh == 32) mhsa_fwd_kernel<float, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p);
-        else mhsa_fwd_kernel<float, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p);
-    }
+    mhsa_dispatch(dtype, dh, o, [&](auto k) {
+        using K = decltype(k);
+        if constexpr (std::is_same_v<typename K::T, bf16_t>) mhsa_fwd_lds_kernel<K::dh, K::drop, K::win, K::rel><<<grid, block, 0, st>>>(p);
+        else mhsa_fwd_kernel<float, K::dh, K::drop, K::win, K::rel><<<grid, block, 0, st>>>(p);
+    });
     SED_LAUNCH_CHECK();
     return 0;
 }
 }  // namespace
 
 extern "C" int sed_mhsa_fwd(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, void* stream) {
-    return mhsa_fwd_launch<false>(dtype, qkv, ctx, lse, B, t, H, dh, DropArgs{}, stream);
+    return mhsa_fwd_launch(dtype, qkv, ctx, lse, B, t, H, dh, MhsaOpts{}, stream);
 }
 
-// the dropout twins: the plain entry's checks, then p in [0, 1) and the state.  thr = 0 (p below 2^-33: every cell kept, s = 1 exactly)
-// is no dropout by definition and takes the plain instantiation, so p = 0 gives the plain entry's bits whatever the compiler
-// contracts where
-#define SED_DROP_ARGS(p, rng, stream_id, out)                                                                     \
-    SED_REQUIRE((rng) != nullptr, "the dropout state rng is required");                                           \
-    SED_REQUIRE(drop_host_args((p), (rng), (stream_id), &(out)), "the dropout probability must lie in [0, 1)")
-
+// the dropout twins: p in [0, 1) and the state (required whatever p is), then the plain entry's checks
 extern "C" int sed_mhsa_fwd_drop(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, float p,
                                  const uint32_t* rng, uint32_t stream_id, void* stream) {
-    DropArgs d;
-    SED_DROP_ARGS(p, rng, stream_id, d);
-    if (d.thr == 0) return mhsa_fwd_launch<false>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream);
-    return mhsa_fwd_launch<true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream);
+    SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
+    MhsaOpts o;
+    if (int rc = mhsa_opts(&o, t, SED_WIN_UNBOUNDED, SED_WIN_UNBOUNDED, p, rng, stream_id, nullptr, nullptr)) return rc;
+    return mhsa_fwd_launch(dtype, qkv, ctx, lse, B, t, H, dh, o, stream);
 }
 
-// the windowed entry: one for plain and dropout (p = 0: no dropout, rng may be NULL).  The sides are clamped to t - 1 (a side that
-// reaches the clip's end from every query is unbounded); both unbounded is the attention above and launches its instantiation
-#define SED_WIN_ARGS(left, right, p, rng, stream_id, out)                                                        \
-    SED_REQUIRE((left) >= 0 && (right) >= 0, "the window sides left and right must be >= 0");                    \
-    SED_REQUIRE(drop_host_args((p), (rng), (stream_id), &(out)), "the dropout probability must lie in [0, 1)");  \
-    SED_REQUIRE((out).thr == 0 || (rng) != nullptr, "the dropout state rng is required when p > 0")
-
+// the windowed entry: one for plain and dropout; both sides unbounded is the attention above and launches its instantiation
 extern "C" int sed_mhsa_fwd_win(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, int left, int right,
                                 float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
-    DropArgs d;
-    SED_WIN_ARGS(left, right, p, rng, stream_id, d);
-    const int cap = t > 0 ? t - 1 : 0, wl = left < cap ? left : cap, wr = right < cap ? right : cap;
-    if (wl == cap && wr == cap) {
-        if (d.thr == 0) return mhsa_fwd_launch<false>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream);
-        return mhsa_fwd_launch<true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream);
-    }
-    if (d.thr == 0) return mhsa_fwd_launch<false, true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream, wl, wr);
-    return mhsa_fwd_launch<true, true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream, wl, wr);
+    MhsaOpts o;
+    if (int rc = mhsa_opts(&o, t, left, right, p, rng, stream_id, nullptr, nullptr)) return rc;
+    return mhsa_fwd_launch(dtype, qkv, ctx, lse, B, t, H, dh, o, stream);
 }
 
 // tiles of 32 x 32 per (clip, head) on which a wave of the pass issues MFMAs: the sum of mhsa_win_range over the waves
 extern "C" long long sed_mhsa_win_tiles(int t, int left, int right, int pass) {
     if (t <= 0 || left < 0 || right < 0 || pass < 0 || pass > 2) return -1;
-    const int wl = left < t - 1 ? left : t - 1, wr = right < t - 1 ? right : t - 1;
+    const int wl = mhsa_win_side(left, t), wr = mhsa_win_side(right, t);
     long long n = 0;
     for (int a0 = 0; a0 < t; a0 += MHSA_QT) {
         const TileRange rg = pass == 1 ? mhsa_win_range(a0, MHSA_QT, t, wr, wl) : mhsa_win_range(a0, MHSA_QT, t, wl, wr);
@@ -1091,10 +1095,8 @@ extern "C" size_t sed_mhsa_bwd_ws_floats(int B, int t, int H, int dh) {
 }
 
 namespace {
-template <bool DROP, bool WIN = false, bool REL = false>
 int mhsa_bwd_launch(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
-                    float* workspace, int B, int t, int H, int dh, const DropArgs& drop, void* stream, int wl = 0, int wr = 0,
-                    const float* rel = nullptr, float* drel = nullptr) {
+                    float* workspace, int B, int t, int H, int dh, const MhsaOpts& o, void* stream) {
     long long nb; int ntile;
     if (int rc = mhsa_check(dtype, B, t, H, dh, &nb, &ntile)) return rc;
     SED_REQUIRE(qkv != nullptr && ctx != nullptr && dctx != nullptr && lse != nullptr && dqkv != nullptr && workspace != nullptr,
@@ -1103,27 +1105,25 @@ int mhsa_bwd_launch(int dtype, const float* qkv, const float* ctx, const float* 
     MhsaParams p = {};
     p.qkv = qkv; p.ctx = ctx; p.dctx = dctx; p.lse = lse; p.out = dqkv; p.D = workspace;
     p.t = t; p.H = H; p.ntile = ntile; p.scale = 1.f / sqrtf((float)dh);
-    p.drop = drop;
-    p.wl = wl; p.wr = wr;
-    if (REL) {
-        p.rel = rel;
+    p.drop = o.drop;
+    p.wl = o.wl; p.wr = o.wr;
+    if (o.rel != nullptr) {
+        p.rel = o.rel;
         p.relws = workspace + (size_t)B * t * H;
-        p.relspan = rel_span(t, wl, wr);
+        p.relspan = rel_span(t, o.wl, o.wr);
     }
     hipStream_t st = (hipStream_t)stream;
     mhsa_rowdot_kernel<<<(unsigned)cdivz((size_t)B * t * H, 256), 256, 0, st>>>(p, B, dh);
     SED_LAUNCH_CHECK();
     const dim3 grid((unsigned)nb), block(64 * MHSA_WAVES);
-    if (dtype == SED_BF16) {
-        if (dh == 32) { mhsa_bwd_kv_kernel<bf16_t, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p); }
-        else { mhsa_bwd_kv_kernel<bf16_t, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<bf16_t, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p); }
-    } else {
-        if (dh == 32) { mhsa_bwd_kv_kernel<float, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 32, DROP, WIN, REL><<<grid, block, 0, st>>>(p); }
-        else { mhsa_bwd_kv_kernel<float, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p); mhsa_bwd_q_kernel<float, 64, DROP, WIN, REL><<<grid, block, 0, st>>>(p); }
-    }
+    mhsa_dispatch(dtype, dh, o, [&](auto k) {
+        using K = decltype(k);
+        mhsa_bwd_kv_kernel<typename K::T, K::dh, K::drop, K::win, K::rel><<<grid, block, 0, st>>>(p);
+        mhsa_bwd_q_kernel<typename K::T, K::dh, K::drop, K::win, K::rel><<<grid, block, 0, st>>>(p);
+    });
     SED_LAUNCH_CHECK();
-    if (REL) {
-        mhsa_rel_reduce_kernel<<<dim3((unsigned)cdiv(2 * t - 1, 64), (unsigned)H), 64 * REL_RED_LANES, 0, st>>>(p.relws, drel, B, t, H, ntile, p.relspan, wl, wr);
+    if (o.rel != nullptr) {
+        mhsa_rel_reduce_kernel<<<dim3((unsigned)cdiv(2 * t - 1, 64), (unsigned)H), 64 * REL_RED_LANES, 0, st>>>(p.relws, o.drel, B, t, H, ntile, p.relspan, o.wl, o.wr);
         SED_LAUNCH_CHECK();
     }
     return 0;
@@ -1132,68 +1132,51 @@ int mhsa_bwd_launch(int dtype, const float* qkv, const float* ctx, const float* 
 
 extern "C" int sed_mhsa_bwd(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
                             float* workspace, int B, int t, int H, int dh, void* stream) {
-    return mhsa_bwd_launch<false>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, DropArgs{}, stream);
+    return mhsa_bwd_launch(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, MhsaOpts{}, stream);
 }
 
 extern "C" int sed_mhsa_bwd_drop(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
                                  float* workspace, int B, int t, int H, int dh, float p, const uint32_t* rng, uint32_t stream_id,
                                  void* stream) {
-    DropArgs d;
-    SED_DROP_ARGS(p, rng, stream_id, d);
-    if (d.thr == 0) return mhsa_bwd_launch<false>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
-    return mhsa_bwd_launch<true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
+    SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
+    MhsaOpts o;
+    if (int rc = mhsa_opts(&o, t, SED_WIN_UNBOUNDED, SED_WIN_UNBOUNDED, p, rng, stream_id, nullptr, nullptr)) return rc;
+    return mhsa_bwd_launch(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, o, stream);
 }
 
 extern "C" int sed_mhsa_bwd_win(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
                                 float* workspace, int B, int t, int H, int dh, int left, int right, float p, const uint32_t* rng,
                                 uint32_t stream_id, void* stream) {
-    DropArgs d;
-    SED_WIN_ARGS(left, right, p, rng, stream_id, d);
-    const int cap = t > 0 ? t - 1 : 0, wl = left < cap ? left : cap, wr = right < cap ? right : cap;
-    if (wl == cap && wr == cap) {
-        if (d.thr == 0) return mhsa_bwd_launch<false>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
-        return mhsa_bwd_launch<true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream);
-    }
-    if (d.thr == 0) return mhsa_bwd_launch<false, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr);
-    return mhsa_bwd_launch<true, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr);
+    MhsaOpts o;
+    if (int rc = mhsa_opts(&o, t, left, right, p, rng, stream_id, nullptr, nullptr)) return rc;
+    return mhsa_bwd_launch(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, o, stream);
 }
 
-// ---- the relative-position entries: the windowed entries' arguments and the per-distance table(s).  Always the WIN = true kernels
-// (both sides unbounded is a valid window: every tile is visited and the select never masks), DROP by thr as above
-inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
+// ---- the relative-position entries: the windowed entries' arguments and the per-distance table(s).  Always the WIN = true kernels,
+// DROP by thr as above
 extern "C" int sed_mhsa_fwd_rel(int dtype, const float* qkv, float* ctx, float* lse, int B, int t, int H, int dh, int left, int right,
                                 float p, const uint32_t* rng, uint32_t stream_id, const float* rel, void* stream) {
-    DropArgs d;
-    SED_WIN_ARGS(left, right, p, rng, stream_id, d);
+    MhsaOpts o;
+    if (int rc = mhsa_opts(&o, t, left, right, p, rng, stream_id, rel, nullptr)) return rc;
     SED_REQUIRE(rel != nullptr, "the distance table rel is required");
     SED_REQUIRE(aligned4(rel), "rel must be 4-byte aligned");
-    const int cap = t > 0 ? t - 1 : 0, wl = left < cap ? left : cap, wr = right < cap ? right : cap;
-    if (d.thr == 0) return mhsa_fwd_launch<false, true, true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream, wl, wr, rel);
-    return mhsa_fwd_launch<true, true, true>(dtype, qkv, ctx, lse, B, t, H, dh, d, stream, wl, wr, rel);
+    return mhsa_fwd_launch(dtype, qkv, ctx, lse, B, t, H, dh, o, stream);
 }
 
 extern "C" size_t sed_mhsa_bwd_rel_ws_floats(int B, int t, int H, int dh, int left, int right) {
     long long nb; int ntile;
-    if (left < 0 || right < 0 || B <= 0 || t <= 0 || H <= 0 || (dh != 32 && dh != 64)) return 0;
-    if ((long long)t * 3 * H * dh * 4 >= (1ll << 31)) return 0;
-    ntile = cdiv(t, MHSA_QT * MHSA_WAVES);
-    nb = (long long)B * H * ntile;
-    const int wl = left < t - 1 ? left : t - 1, wr = right < t - 1 ? right : t - 1;
-    return (size_t)B * t * H + (size_t)nb * MHSA_WAVES * rel_span(t, wl, wr);
+    if (left < 0 || right < 0 || mhsa_check(SED_F32, B, t, H, dh, &nb, &ntile) != 0) return 0;
+    return (size_t)B * t * H + (size_t)nb * MHSA_WAVES * rel_span(t, mhsa_win_side(left, t), mhsa_win_side(right, t));
 }
 
 extern "C" int sed_mhsa_bwd_rel(int dtype, const float* qkv, const float* ctx, const float* dctx, const float* lse, float* dqkv,
                                 float* workspace, int B, int t, int H, int dh, int left, int right, float p, const uint32_t* rng,
                                 uint32_t stream_id, const float* rel, float* drel, void* stream) {
-    DropArgs d;
-    SED_WIN_ARGS(left, right, p, rng, stream_id, d);
+    MhsaOpts o;
+    if (int rc = mhsa_opts(&o, t, left, right, p, rng, stream_id, rel, drel)) return rc;
     SED_REQUIRE(rel != nullptr && drel != nullptr, "the distance tables rel and drel are required");
     SED_REQUIRE(aligned4(rel) && aligned4(drel), "rel and drel must be 4-byte aligned");
-    const int cap = t > 0 ? t - 1 : 0, wl = left < cap ? left : cap, wr = right < cap ? right : cap;
-    if (d.thr == 0)
-        return mhsa_bwd_launch<false, true, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr, rel, drel);
-    return mhsa_bwd_launch<true, true, true>(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, d, stream, wl, wr, rel, drel);
+    return mhsa_bwd_launch(dtype, qkv, ctx, dctx, lse, dqkv, workspace, B, t, H, dh, o, stream);
 }
 
 #define SED_RELPOS_MAX_BUCKETS 4096
@@ -1251,8 +1234,9 @@ extern "C" int sed_add_layernorm_fwd(const float* x, const float* a, const float
 
 extern "C" int sed_add_layernorm_fwd_drop(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
                                           size_t rows, int C, float eps, float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
+    SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
     DropArgs d;
-    SED_DROP_ARGS(p, rng, stream_id, d);
+    if (int rc = drop_require_args(p, rng, stream_id, &d)) return rc;
     if (d.thr == 0) return add_ln_fwd_launch<false>(x, a, gamma, beta, y, stats, rows, C, eps, d, stream);
     return add_ln_fwd_launch<true>(x, a, gamma, beta, y, stats, rows, C, eps, d, stream);
 }
@@ -1292,8 +1276,9 @@ extern "C" int sed_add_layernorm_bwd(const float* dy, const float* x, const floa
 extern "C" int sed_add_layernorm_bwd_drop(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
                                           float* dres, float* da, float* dgamma, float* dbeta, float* workspace, size_t rows, int C,
                                           float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
+    SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
     DropArgs d;
-    SED_DROP_ARGS(p, rng, stream_id, d);
+    if (int rc = drop_require_args(p, rng, stream_id, &d)) return rc;
     SED_REQUIRE(da != nullptr, "da is required");
     if (d.thr == 0) {                                  // da = dres
         if (int rc = add_ln_bwd_launch<false>(dy, x, a, gamma, stats, dres, da, dgamma, dbeta, workspace, rows, C, d, stream)) return rc;

@@ -279,6 +279,8 @@ class CnnEngine(OptimizerExtMixin):
             raise ValueError("sa_window belongs to the self-attention head (head='sa')")
         # the sides as the C entries take them
         self._win = None if self.sa_window is None else tuple(L.WIN_UNBOUNDED if v is None else min(v, L.WIN_UNBOUNDED) for v in self.sa_window)
+        # the effective (left, right): what the relative-position entries take where no window is set
+        self._win_sides = self._win if self._win is not None else (L.WIN_UNBOUNDED, L.WIN_UNBOUNDED)
         self.sa_rel_pos = self.check_sa_rel_pos(sa_rel_pos)
         if head != "sa" and self.sa_rel_pos is not None:
             raise ValueError("sa_rel_pos belongs to the self-attention head (head='sa')")
@@ -863,8 +865,7 @@ class CnnEngine(OptimizerExtMixin):
             g["rel_map"] = torch.from_numpy(m).to(dev)
             for ly in g["layers"]:
                 ly["rel"], ly["drel"] = torch.empty((Hh, 2 * t - 1), **f32), torch.empty((Hh, 2 * t - 1), **f32)
-            wl, wr = self._win if self._win is not None else (L.WIN_UNBOUNDED, L.WIN_UNBOUNDED)
-            g["core_ws"] = torch.empty(max(1, lib.sed_mhsa_bwd_rel_ws_floats(B, t, Hh, C // Hh, wl, wr)), **f32)
+            g["core_ws"] = torch.empty(max(1, lib.sed_mhsa_bwd_rel_ws_floats(B, t, Hh, C // Hh, *self._win_sides)), **f32)
         g["ln_ws"] = torch.empty(max(1, lib.sed_add_layernorm_bwd_ws_floats(R, C)), **f32)
         # split-K of the weight-gradient products (K = R rows), as the recurrent head's tail: SED_GRU_KSPLIT, read with the plan
         g["ksplit"] = max(1, int(_os.environ.get("SED_GRU_KSPLIT", "64")))
@@ -901,6 +902,47 @@ class CnnEngine(OptimizerExtMixin):
                 L.ptr(g["dres"]), L.ptr(g["da"]), L.ptr(dgamma), L.ptr(dbeta), L.ptr(g["ln_ws"]), R, C, self.sa_dropout, L.ptr(g["rng"]),
                 sid, st)
         return g["da"]
+
+    def _lin_dx(self, dy, W, wT, dx, rows, n_out, n_in):
+        """dx[rows][n_in] = dy[rows][n_out] . W[n_out][n_in], through W's transpose in wT[n_in][n_out]"""
+        lib, st = self.lib, _stream()
+        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(W), n_in, L.ptr(wT), n_out, n_out, n_in, n_out, 0, st)
+        self._k("sed_gemm_nt", lib.sed_gemm_nt, self.dt, L.ptr(dy), n_out, L.ptr(wT), n_out, None, L.ptr(dx), n_in, rows, n_in, n_out, 1,
+                None, st)
+
+    def _lin_dw(self, dy, x, dW, db, rows, n_out, n_in, t, ks, ws):
+        """dW[n_out][n_in] = dy^T . x over the rows, db = the column sums of dy (split-K ks with the workspace ws)"""
+        self._k("sed_gemm_tn", self.lib.sed_gemm_tn, self.dt, L.ptr(dy), n_out, L.ptr(x), n_in, L.ptr(dW), n_in, L.ptr(db), n_out, n_in,
+                rows, t, 0, ks, ws, _stream())
+
+    def _mhsa_opts(self, g, ly, l, drop):
+        """The core entry of layer l, the same for the forward and the backward: its suffix and its arguments between the sizes and
+        the tables' gradient / the stream.  A table takes _rel (with the window, or both sides unbounded), else a window _win, else
+        dropout _drop, else the plain entry."""
+        rng = L.ptr(g["rng"]) if drop else None
+        if self.sa_rel_pos is not None:
+            return "_rel", (*self._win_sides, drop, rng, 8 * l + 0, L.ptr(ly["rel"]))
+        if self._win is not None:
+            return "_win", (*self._win, drop, rng, 8 * l + 0)
+        if drop:
+            return "_drop", (drop, rng, 8 * l + 0)
+        return "", ()
+
+    def _mhsa_fwd(self, g, ly, l, training, drop):
+        """ly["qkv"] -> ly["ctx"]; lse is kept for a backward (training) and wherever the masks are drawn"""
+        (B, Hh, t), C = ly["lse"].shape, ly["ctx"].shape[1]
+        sfx, opts = self._mhsa_opts(g, ly, l, drop)
+        self._k("sed_mhsa_fwd" + sfx, getattr(self.lib, "sed_mhsa_fwd" + sfx), self.dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]),
+                L.ptr(ly["lse"]) if training or drop else None, B, t, Hh, C // Hh, *opts, _stream())
+
+    def _mhsa_bwd(self, g, ly, l, drop):
+        """g["dctx"] -> g["dqkv"] (and ly["drel"] where there is a table)"""
+        (B, Hh, t), C = ly["lse"].shape, ly["ctx"].shape[1]
+        sfx, opts = self._mhsa_opts(g, ly, l, drop)
+        if sfx == "_rel":
+            opts += (L.ptr(ly["drel"]),)
+        self._k("sed_mhsa_bwd" + sfx, getattr(self.lib, "sed_mhsa_bwd" + sfx), self.dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]),
+                L.ptr(ly["lse"]), L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, *opts, _stream())
 
     def _sa_conv_forward(self, p, P, l, ly, training, bn_training, update_running_stats):
         """The convolution module of layer l behind attn_norm: ly["h"] -> ly["hc"].  training: keep what a backward reads;
@@ -940,10 +982,8 @@ class CnnEngine(OptimizerExtMixin):
         done(cn)
         # ds = ga . pointwise2.weight;  d pointwise2.weight = ga^T . s, its bias gradient the column sums of ga (ga = dres, or m s dres
         # under dropout: the gradient of the module's output)
-        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w2]), C, L.ptr(g["cw2T"]), C, C, C, C, 0, st)
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ga), C, L.ptr(g["cw2T"]), C, None, L.ptr(g["cds"]), C, R, C, C, 1, None, st)
-        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(ga), C, L.ptr(ly["cs"]), C, L.ptr(G[w2]), C,
-                L.ptr(G[cm + ".pointwise2.bias"]), C, C, R, t, 0, ks, ws, st)
+        self._lin_dx(ga, P[w2], g["cw2T"], g["cds"], R, C, C)
+        self._lin_dw(ga, ly["cs"], G[w2], G[cm + ".pointwise2.bias"], R, C, C, t, ks, ws)
         # through the SiLU (gz over ds) and the BatchNorm: statistics, the finalisation, then dz = ca gz + cb z + cc on load
         if eval_bwd:
             self._k("sed_bn_eval_stats", lib.sed_bn_eval_stats, L.ptr(P[cm + ".bn.running_mean"]), L.ptr(P[cm + ".bn.running_var"]), BN_EPS,
@@ -964,12 +1004,9 @@ class CnnEngine(OptimizerExtMixin):
                 L.ptr(ly["cv"]), L.ptr(ly["cg"]), L.ptr(P[cm + ".depthwise.weight"]), L.ptr(g["cdg"]), L.ptr(G[cm + ".depthwise.weight"]),
                 L.ptr(G[cm + ".depthwise.bias"]), L.ptr(g["cw_ws"]), B, t, C, kc, st)
         # d pointwise1.weight = dg^T . h, its bias gradient the column sums of dg;  dh = dg . pointwise1.weight + dres (the residual)
-        self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["cdg"]), 2 * C, L.ptr(ly["h"]), C, L.ptr(G[w1]), C,
-                L.ptr(G[cm + ".pointwise1.bias"]), 2 * C, C, R, t, 0, ks, ws, st)
+        self._lin_dw(g["cdg"], ly["h"], G[w1], G[cm + ".pointwise1.bias"], R, 2 * C, C, t, ks, ws)
         done(cm)
-        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w1]), C, L.ptr(g["cw1T"]), 2 * C, 2 * C, C, 2 * C, 0, st)
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["cdg"]), 2 * C, L.ptr(g["cw1T"]), 2 * C, None, L.ptr(g["dhc"]), C, R, C, 2 * C, 1,
-                None, st)
+        self._lin_dx(g["cdg"], P[w1], g["cw1T"], g["dhc"], R, 2 * C, C)
         g["dhc"].add_(g["dres"])
         return g["dhc"]
 
@@ -991,22 +1028,9 @@ class CnnEngine(OptimizerExtMixin):
             self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(xin), C, L.ptr(P[an + ".in_proj_weight"]), C, L.ptr(P[an + ".in_proj_bias"]),
                     L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
             if self.sa_rel_pos is not None:
-                wl, wr = self._win if self._win is not None else (L.WIN_UNBOUNDED, L.WIN_UNBOUNDED)
                 self._k("sed_relpos_expand", lib.sed_relpos_expand, L.ptr(P[self.sa_rel_name(l) + ".weight"]), L.ptr(g["rel_map"]),
                         L.ptr(ly["rel"]), Hh, self.rel_pos_buckets(self.sa_rel_pos), t, st)
-                self._k("sed_mhsa_fwd_rel", lib.sed_mhsa_fwd_rel, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]),
-                        L.ptr(ly["lse"]) if training or drop else None, B, t, Hh, C // Hh, wl, wr, drop,
-                        L.ptr(g["rng"]) if drop else None, 8 * l + 0, L.ptr(ly["rel"]), st)
-            elif self._win is not None:
-                self._k("sed_mhsa_fwd_win", lib.sed_mhsa_fwd_win, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]),
-                        L.ptr(ly["lse"]) if training or drop else None, B, t, Hh, C // Hh, self._win[0], self._win[1], drop,
-                        L.ptr(g["rng"]) if drop else None, 8 * l + 0, st)
-            elif drop:
-                self._k("sed_mhsa_fwd_drop", lib.sed_mhsa_fwd_drop, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(ly["lse"]),
-                        B, t, Hh, C // Hh, drop, L.ptr(g["rng"]), 8 * l + 0, st)
-            else:
-                self._k("sed_mhsa_fwd", lib.sed_mhsa_fwd, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(ly["lse"]) if training else None,
-                        B, t, Hh, C // Hh, st)
+            self._mhsa_fwd(g, ly, l, training, drop)
             self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["ctx"]), C, L.ptr(P[an + ".out_proj.weight"]), C,
                     L.ptr(P[an + ".out_proj.bias"]), L.ptr(ly["a"]), C, R, C, C, 1, None, st)
             self._add_ln_fwd(g, xin, ly["a"], P[nn_ + ".weight"], P[nn_ + ".bias"], ly["h"], ly["stats"] if training else None, R, C,
@@ -1066,9 +1090,7 @@ class CnnEngine(OptimizerExtMixin):
                 done(fnn)
                 # da = ga . w2 (ga: the gradient of the FFN's output -- dres, or m s dres under dropout), then a = act(u) and
                 # du = da act'(u) (du over da; under dropout a = m s act(u), du = da m s act'(u))
-                self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w2]), D, L.ptr(g["w2T"]), C, C, D, C, 0, st)
-                self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ga), C, L.ptr(g["w2T"]), C, None, L.ptr(g["fda"]), D, R, D, C, 1,
-                        None, st)
+                self._lin_dx(ga, P[w2], g["w2T"], g["fda"], R, C, D)
                 if drop:
                     self._k("sed_ffn_act_bwd_drop", lib.sed_ffn_act_bwd_drop, self.sa_act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
                             L.ptr(g["fda"]), R, D, drop, L.ptr(g["rng"]), 8 * l + 3, st)
@@ -1076,15 +1098,11 @@ class CnnEngine(OptimizerExtMixin):
                     self._k("sed_ffn_act_bwd", lib.sed_ffn_act_bwd, self.sa_act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
                             L.ptr(g["fda"]), R * D, st)
                 # d linear2.weight = ga^T . a, d linear1.weight = du^T . h, the biases' gradients their column sums
-                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(ga), C, L.ptr(g["ffa"]), D, L.ptr(G[w2]), D,
-                        L.ptr(G[fn + ".linear2.bias"]), C, D, R, t, 0, ks, ws, st)
-                self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["fda"]), D, L.ptr(fin), C, L.ptr(G[w1]), C,
-                        L.ptr(G[fn + ".linear1.bias"]), D, C, R, t, 0, ks, ws, st)
+                self._lin_dw(ga, g["ffa"], G[w2], G[fn + ".linear2.bias"], R, C, D, t, ks, ws)
+                self._lin_dw(g["fda"], fin, G[w1], G[fn + ".linear1.bias"], R, D, C, t, ks, ws)
                 done(fn)
                 # dh = du . w1 + dres (the residual branch)
-                self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[w1]), C, L.ptr(g["w1T"]), D, D, C, D, 0, st)
-                self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["fda"]), D, L.ptr(g["w1T"]), D, None, L.ptr(g["dh1"]), C, R, C, D, 1,
-                        None, st)
+                self._lin_dx(g["fda"], P[w1], g["w1T"], g["dh1"], R, D, C)
                 g["dh1"].add_(g["dres"])
                 gcur = g["dh1"]
             if self.sa_conv_kernel:
@@ -1093,41 +1111,21 @@ class CnnEngine(OptimizerExtMixin):
                                   8 * l + 1 if drop else None)
             done(nn_)
             # d out_proj.weight = ga^T . ctx, d out_proj.bias = column sums of ga (ga: the gradient of a -- dres, or m s dres under dropout)
-            self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(ga), C, L.ptr(ly["ctx"]), C, L.ptr(G[an + ".out_proj.weight"]), C,
-                    L.ptr(G[an + ".out_proj.bias"]), C, C, R, t, 0, ks, ws, st)
+            self._lin_dw(ga, ly["ctx"], G[an + ".out_proj.weight"], G[an + ".out_proj.bias"], R, C, C, t, ks, ws)
             # dctx = ga . out_proj.weight
-            self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[an + ".out_proj.weight"]), C, L.ptr(g["woT"]), C, C, C, C, 0, st)
-            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ga), C, L.ptr(g["woT"]), C, None, L.ptr(g["dctx"]), C, R, C, C, 1,
-                    None, st)
+            self._lin_dx(ga, P[an + ".out_proj.weight"], g["woT"], g["dctx"], R, C, C)
+            self._mhsa_bwd(g, ly, l, drop)
             if self.sa_rel_pos is not None:
                 # ly["rel"] is the table this layer's forward read (the weights do not change between a step's forward and backward)
-                wl, wr = self._win if self._win is not None else (L.WIN_UNBOUNDED, L.WIN_UNBOUNDED)
                 rn = self.sa_rel_name(l)
-                self._k("sed_mhsa_bwd_rel", lib.sed_mhsa_bwd_rel, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
-                        L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, wl, wr, drop,
-                        L.ptr(g["rng"]) if drop else None, 8 * l + 0, L.ptr(ly["rel"]), L.ptr(ly["drel"]), st)
                 self._k("sed_relpos_fold", lib.sed_relpos_fold, L.ptr(ly["drel"]), L.ptr(g["rel_map"]), L.ptr(G[rn + ".weight"]), Hh,
                         self.rel_pos_buckets(self.sa_rel_pos), t, st)
                 done(rn)
-            elif self._win is not None:
-                self._k("sed_mhsa_bwd_win", lib.sed_mhsa_bwd_win, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
-                        L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, self._win[0], self._win[1], drop,
-                        L.ptr(g["rng"]) if drop else None, 8 * l + 0, st)
-            elif drop:
-                self._k("sed_mhsa_bwd_drop", lib.sed_mhsa_bwd_drop, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
-                        L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, drop, L.ptr(g["rng"]), 8 * l + 0, st)
-            else:
-                self._k("sed_mhsa_bwd", lib.sed_mhsa_bwd, dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]), L.ptr(ly["lse"]),
-                        L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, st)
             # d in_proj_weight = dqkv^T . x', d in_proj_bias = column sums of dqkv
-            self._k("sed_gemm_tn", lib.sed_gemm_tn, dt, L.ptr(g["dqkv"]), 3 * C, L.ptr(xin), C, L.ptr(G[an + ".in_proj_weight"]), C,
-                    L.ptr(G[an + ".in_proj_bias"]), 3 * C, C, R, t, 0, ks, ws, st)
+            self._lin_dw(g["dqkv"], xin, G[an + ".in_proj_weight"], G[an + ".in_proj_bias"], R, 3 * C, C, t, ks, ws)
             done(an)
             # dm = dqkv . in_proj_weight + dres (the residual branch): the gradient of the layer's input
-            self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P[an + ".in_proj_weight"]), C, L.ptr(g["winT"]), 3 * C, 3 * C, C,
-                    3 * C, 0, st)
-            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dqkv"]), 3 * C, L.ptr(g["winT"]), 3 * C, None, L.ptr(g["dm"]), C, R, C,
-                    3 * C, 1, None, st)
+            self._lin_dx(g["dqkv"], P[an + ".in_proj_weight"], g["winT"], g["dm"], R, 3 * C, C)
             g["dm"].add_(g["dres"])
             gcur = g["dm"]
         # back through the mel mean
