@@ -43,13 +43,35 @@ Gate, per element; u = 2^-24 (one fp32 rounding), derived, not fitted:
     c = C_ABS2 + (hi - lo) / 4 + 2 + the same dB terms: sqrt(x^2 + y^2) squared (2 u under the root halves to u, the root u, the square
     doubles: 5 u), four lanes with a quarter of the band each and two adds.
   sed_logmel_crops.  Bit-equal to bank[start + t] without mean / std; with them (v - mean) / std within C_Z * u * |v - mean| / std.
+  sed_complex_augment_logmel (complex_augment_logmel_kernel: gather + mean of nmix crops + real noise + complex z-score + |.|^2 + mel
+    + log; reference: mix_logmel_reference, gate: mix_ratio).  |p_got - p_ref| <= S_m + c * u * p_ref with sed_complex_to_logmel's c
+    (the kernel squares and sums exactly as that one does) and S_m = sum_k W[m,k] * (2 |v_k| E_k + E_k^2), v_k the complex value the
+    kernel squares and E_k = hypot(E_re, E_im) the bound on its error.  Per component (x = re or im of the float64 value at each step,
+    E the bound carried so far; every new rounding is taken of |x| + E, the largest the computed value can be):
+      sum     the nmix - 1 adds of w_1 .. w_nmix: every partial sum is <= A = sum_j |w_j|, one rounding each     E1 = (nmix - 1) u A
+      mean    inv = fl(1 / nmix) and the product, applied only for nmix > 1; both are exact for nmix 2 and 4 (a power of two),
+              two roundings for nmix 3                                                                            E2 = E1 / nmix + c_inv u (|x| + E1 / nmix), c_inv = 2 (nmix 3), 0 (else)
+      noise   re only, only where nstd > 0: fma(nstd, z, x), one rounding; the product nstd * z of the two fp32
+              inputs is exact in the reference.  Generator noise: the device's z is within C_GEN u of the float64
+              Box-Muller value of the same 24-bit uniforms (below)                                                E3 = E2 [+ nstd C_GEN u] + u (|x| + ..)
+      z-score x - mean: one rounding                                                                              E4 = E3 + u (|x| + E3)
+              is = fl(1 / std) (correctly rounded division: u) and the product (u)                                E5 = (E4 + 2 u (|x| + E4)) / std
+    C_GEN (absolute: |z| < R = sqrt(-2 ln 2^-24) = sqrt(48 ln 2) = 5.77): u1, u2 are exact in fp32 (24-bit integers times 2^-24).
+      The argument fl(fl(2 pi) u2) carries the rounded constant and the product: 2 u * 2 pi = 4 pi u, and |d cos| <= |d arg|.
+      cosf: <= 4 ulp, logf: <= 3 ulp (the limits of OpenCL's full profile, which the device library is written to);
+      ulp(y) <= 2 u |y|: 8 u on the cosine; 6 u relative under the root, which halves it, plus the root's own u: 4 u on the radius;
+      the final product: u.  |dz| <= R (4 pi + 8 + 4 + 1) u = 147.5 u.
+    A band whose reference power is exactly 0 (an empty band, an all-zero bank without noise and z-score) must give exactly -100.
 
 Measured on the MI355X (tests/test_gpu_frontend_exact_oracle.py holds the table): the largest err / bound is 0.23 for the STFT
 (margin 4.4), 0.26 for the log-mel routes (3.9, through the single-bin bands of a Slaney bank, i.e. the STFT bound again), 0.60 and 0.62
-for sed_complex_to_logmel on bands of 1 .. 5 bins and for the crops' z-score, whose bounds are worst-case counts of a few roundings.
+for sed_complex_to_logmel on bands of 1 .. 5 bins and for the crops' z-score, whose bounds are worst-case counts of a few roundings;
+0.58 for sed_complex_augment_logmel (margin 1.7, on the same short bands; tests/test_gpu_complex_augment_exact_oracle.py holds its table)
+and 0.18 for the generator's draws read out one by one.
 """
 import numpy as np
 
+from oracle import dataset_oracle as DO
 from oracle import frontend_oracle as FO
 
 U = 2.0 ** -24
@@ -354,5 +376,293 @@ def emulate_f32(waves, window, nfft, hop, W=None, lo=None, hi=None, mean=None, s
         out[..., m] = f32(10.0) * log10_f32(np.maximum(f32(AMIN), acc))
     if mean is not None:
         out = (out - np.asarray(mean, f32)) / np.asarray(std, f32)
+    assert out.dtype == f32
+    return out
+
+
+# ---- sed_complex_augment_logmel: reference, gate, mutated references, inputs, fp32 emulation ------------------------------------------
+R_GEN = float(np.sqrt(48.0 * np.log(2.0)))                        # the largest Box-Muller radius of a 24-bit uniform
+C_GEN = R_GEN * (4.0 * np.pi + 8.0 + 4.0 + 1.0)                   # |z_device - z_float64| <= C_GEN * u (derivation: the docstring)
+INT_MAX = 2 ** 31 - 1
+
+# name -> what a case must have for the mutation to change the result (mix_mutations_for)
+MIX_MUTATIONS = {
+    "div_nmix_plus_1": "any",            # divide by nmix + 1
+    "no_division": "mix",                # the sum, not the mean
+    "max_not_mean": "mix",               # component-wise maximum in place of the mean
+    "noise_on_imag": "noise",            # the noise also on the imaginary part
+    "noise_after_zscore": "noise+z",     # z-score first, then the noise
+    "counter_no_frame": "gen",           # generator counter k in place of frame * bins + k
+    "counter_n_mels": "gen",             # generator counter frame * n_mels + k
+    "conj_mean": "z",                    # the conjugated mean
+    "mul_cstd": "z",                     # times std in place of divided by it
+    "row_plus_1": "any",                 # bank row start + 1 + t
+    "slot0_for_all": "mix",              # every mixed crop read from slot 0
+}
+
+
+def counter_normal64(seed, counters):
+    """the generator's draw in float64 from the same two 24-bit uniforms (oracle.dataset_oracle.counter_normal rounds this to fp32)"""
+    h = DO.counter_bits(seed, counters)
+    u1 = (((h >> np.uint64(40)) & np.uint64(0xFFFFFF)).astype(np.float64) + 1.0) / 16777216.0
+    u2 = ((h >> np.uint64(8)) & np.uint64(0xFFFFFF)).astype(np.float64) / 16777216.0
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def _counters(B, crop, bins, stride=None, frame_term=True):
+    frame = np.arange(B * crop, dtype=np.uint64).reshape(B, crop, 1) * np.uint64(bins if stride is None else stride)
+    k = np.arange(bins, dtype=np.uint64)[None, None, :]
+    return frame + k if frame_term else np.broadcast_to(k, (B, crop, bins)).copy()
+
+
+class MixReference:
+    """V (B, crop, bins) complex128: the value the kernel squares; E its error bound; p, S, v (B, crop, n_mels) as in MelReference."""
+
+    def __init__(self, bank, starts, nmix, nstd, z, cmean, cstd, W, lo, hi, mutation=None, crop=None, seed=None):
+        assert mutation is None or mutation in MIX_MUTATIONS, mutation
+        bank = np.asarray(bank, np.complex64).astype(np.complex128)
+        frames, bins = bank.shape
+        starts, nmix = np.asarray(starts).reshape(-1, 4).astype(np.int64), np.asarray(nmix).astype(np.int64)
+        B = len(nmix)
+        if z is not None:
+            z = np.asarray(z, np.float32).astype(np.float64)
+            crop = z.shape[1] if crop is None else crop
+            assert z.shape == (B, crop, bins)
+        assert crop is not None
+        generator = z is None and nstd is not None and seed is not None
+        if generator:
+            z = counter_normal64(seed, _counters(B, crop, bins, W.shape[0] if mutation == "counter_n_mels" else None,
+                                                 mutation != "counter_no_frame"))
+        nstd = np.zeros(B) if nstd is None else np.asarray(nstd, np.float32).astype(np.float64)
+        assert z is not None or not (nstd > 0).any(), "noise asked for without draws or a seed"
+        zscore = cmean is not None
+        if zscore:
+            mu = np.asarray(cmean, np.complex64).astype(np.complex128)
+            sd = np.asarray(cstd, np.float32).astype(np.float64)
+            if mutation == "conj_mean":
+                mu = mu.conj()
+        t = np.arange(crop)
+        self.V = np.empty((B, crop, bins), np.complex128)
+        self.E = np.empty((B, crop, bins), np.float64)
+        for b in range(B):
+            nm = int(nmix[b])
+            assert 1 <= nm <= 4
+            rows = [starts[b, 0 if mutation == "slot0_for_all" else j] + t + (1 if mutation == "row_plus_1" else 0) for j in range(nm)]
+            w = np.stack([bank[r % frames] for r in rows])                       # (nm, crop, bins); unused slots are never read
+            if mutation == "max_not_mean":
+                v = w.real.max(0) + 1j * w.imag.max(0)
+            else:
+                v = w.sum(0) / {"div_nmix_plus_1": nm + 1.0, "no_division": 1.0}.get(mutation, float(nm))
+            c_inv = 2.0 if nm == 3 else 0.0
+            ns = nstd[b]
+            noise = ns * z[b] if ns > 0 else None
+            comp = []
+            for part, x in (("re", v.real.copy()), ("im", v.imag.copy())):
+                A = np.abs(w.real if part == "re" else w.imag).sum(0)
+                e = (nm - 1) * U * A / nm
+                e = e + c_inv * U * (np.abs(x) + e)
+                if noise is not None and mutation != "noise_after_zscore" and (part == "re" or mutation == "noise_on_imag"):
+                    x = x + noise
+                    e = e + (ns * C_GEN * U if generator else 0.0)
+                    e = e + U * (np.abs(x) + e)
+                if zscore:
+                    x = x - (mu.real if part == "re" else mu.imag)
+                    e = e + U * (np.abs(x) + e)
+                    if mutation == "mul_cstd":
+                        x, e = x * sd, (e + 2.0 * U * (np.abs(x) + e)) * sd
+                    else:
+                        x, e = x / sd, (e + 2.0 * U * (np.abs(x) + e)) / sd
+                if noise is not None and mutation == "noise_after_zscore" and part == "re":
+                    x = x + noise
+                comp.append((x, e))
+            self.V[b] = comp[0][0] + 1j * comp[1][0]
+            self.E[b] = np.hypot(comp[0][1], comp[1][1])
+        W = np.asarray(W, np.float32).astype(np.float64).copy()
+        lo, hi = np.asarray(lo).astype(np.int64), np.asarray(hi).astype(np.int64)
+        k = np.arange(bins)[None, :]
+        W *= (k >= lo[:, None]) & (k < hi[:, None])
+        A = np.abs(self.V)
+        self.n = (hi - lo).astype(np.float64)
+        self.p = (A * A) @ W.T
+        self.S = (2.0 * A * self.E + self.E * self.E) @ W.T
+        self.v = 10.0 * np.log10(np.maximum(AMIN, self.p))
+        self.mean = self.std = None
+        self.z = self.v
+
+
+def mix_logmel_reference(bank, starts, nmix, nstd, z, cmean, cstd, W, lo, hi, mutation=None, crop=None, seed=None):
+    """float64 reference of sed_complex_augment_logmel on its fp32 inputs.  bank (frames, bins) complex64; starts (B, 4), only the
+    first nmix[b] slots of a row are read; nstd (B,) or None (no noise); z (B, crop, bins) explicit draws, or None with `seed` for the
+    in-kernel generator (then `crop` is needed too); cmean / cstd (bins,) or None."""
+    return MixReference(bank, starts, nmix, nstd, z, cmean, cstd, W, lo, hi, mutation, crop, seed)
+
+
+def mix_ratio(got, ref):
+    """got: the kernel's output (B, crop, n_mels); err / bound per element"""
+    return _power_ratio(got, ref, ref.S + (C_ABS2 + ref.n / 4.0 + 2.0 + _db_terms(ref)) * U * ref.p)
+
+
+def _mc(bins, n_mels, crop, bank, nmix, noise=None, nstd=None, zscore=False, kind="noise", frames=40, width=None):
+    return dict(bins=bins, n_mels=n_mels, crop=crop, bank=bank, nmix=tuple(nmix), noise=noise, nstd=nstd, zscore=zscore, kind=kind,
+                frames=frames, width=width)
+
+
+# the cases of tests/test_gpu_complex_augment_exact_oracle.py (the host file runs the fp32 emulation through the same list).
+# noise: None (noise_std NULL), "off" (a table of zeros), "explicit", "gen"; kind: "noise" (amplitude 5), "amps" (rows of amplitude 30,
+# then rows of 1e-3; the last clip lies in the quiet rows), "zero" (an all-zero bank).  The n_mels loop wraps above 64 (65, 130);
+# bins 16385 is four bytes over the 64 KB of LDS a launch gets without asking, 32769 the largest the launch accepts.  Noise of 0.004
+# on a band of a hundred bins of amplitude 30 moves its power by less than the band's own rounding bound: the cases whose bands are all
+# that wide carry louder noise, so that every noise mutation shows in every case it is listed for.
+MIX_CASES = [
+    _mc(33, 1, 1, "random", [1]),
+    _mc(257, 17, 9, "lengths", [1, 1]),
+    _mc(513, 64, 9, "empty", [1, 2], kind="zero"),
+    _mc(513, 64, 9, "slaney", [1, 2, 3, 4, 1]),
+    _mc(257, 65, 9, "lengths", [4, 3, 2, 1], kind="amps"),
+    _mc(513, 130, 1, "lengths", [3, 2], noise="off"),
+    _mc(513, 64, 9, "slaney", [1, 2, 3, 4, 1], "explicit", (0.0, 0.004, 0.0, 0.0065, 0.006), zscore=True),
+    _mc(257, 130, 9, "lengths", [1, 2, 3, 4], "explicit", (0.7, 0.0, 0.004, 0.05), kind="amps"),
+    _mc(33, 17, 1, "dense", [2, 1, 3], "explicit", (0.5, 0.004, 0.0), zscore=True),
+    _mc(513, 64, 9, "slaney", [1, 2, 3, 4, 1], "gen", (0.0, 0.004, 0.0, 0.0065, 0.006), zscore=True),
+    _mc(257, 65, 9, "lengths", [1, 3], "gen", (0.3, 0.004)),
+    _mc(513, 17, 1, "empty", [2, 4, 1], "gen", (0.004, 0.3, 0.0), zscore=True, kind="amps"),
+    _mc(257, 64, 9, "dense", [1, 1, 2], zscore=True),
+    _mc(513, 130, 9, "lengths", [1, 3], zscore=True, kind="amps"),
+    _mc(33, 17, 1, "random", [1], zscore=True, kind="zero"),
+    _mc(16385, 17, 1, "lengths", [3, 1], "explicit", (0.004, 0.0), zscore=True, frames=6),
+    _mc(16385, 5, 2, "random", [2], "gen", (0.3,), frames=6, width=48),
+    _mc(32769, 5, 2, "random", [4], "gen", (0.05,), zscore=True, frames=6, width=48),
+    _mc(32769, 1, 1, "random", [1], frames=4),
+]
+
+
+def mix_id(c):
+    s = f"b{c['bins']}-m{c['n_mels']}-c{c['crop']}-{c['bank']}-mix{''.join(map(str, c['nmix']))}"
+    s += f"-{c['noise']}" if c["noise"] else ""
+    s += "-z" if c["zscore"] else ""
+    return s + (f"-{c['kind']}" if c["kind"] != "noise" else "")
+
+
+def mix_group(c):
+    """the row of the measured table a case is recorded under"""
+    if c["bins"] > 16384:
+        return "wide bins"
+    if c["noise"] in ("gen", "explicit"):
+        return "generator" if c["noise"] == "gen" else "explicit noise"
+    return "z-score" if c["zscore"] else "mixed" if max(c["nmix"]) > 1 else "plain"
+
+
+def mix_mutations_for(c):
+    """the mutations that change this case's result (the cases each mutation is listed for)"""
+    if c["kind"] == "zero":              # (nothing to mix or shift, and |-mean / std|^2 does not see the conjugate)
+        return []
+    B, has = len(c["nmix"]), {"any"}
+    if max(c["nmix"]) > 1:
+        has.add("mix")
+    if c["noise"] in ("explicit", "gen"):
+        has.add("noise")
+        if c["zscore"]:
+            has.add("noise+z")
+    if c["noise"] == "gen" and B * c["crop"] > 1:
+        has.add("gen")
+    if c["zscore"]:
+        has.add("z")
+    return [m for m, need in MIX_MUTATIONS.items() if need in has]
+
+
+def make_mix_inputs(c, seed=0):
+    """one case's host arrays: bank (frames, bins) complex64, starts (B, 4) int32 with -1 / INT_MAX in the unused slots, nmix, nstd and
+    z (or None), seed, cmean / cstd (or None), W, lo, hi.  Clip 0 starts at row 0, the last clip's last crop at frames - crop (the last
+    legal start); a clip of three or four crops holds one start twice."""
+    bins, n_mels, crop, frames = c["bins"], c["n_mels"], c["crop"], c["frames"]
+    B = len(c["nmix"])
+    rng = np.random.default_rng(1000 * seed + bins + 7 * n_mels + crop)
+    amp = np.full(frames, 5.0)
+    if c["kind"] == "amps":
+        amp[:frames // 2], amp[frames // 2:] = 30.0, 1e-3
+    bank = ((rng.standard_normal((frames, bins)) + 1j * rng.standard_normal((frames, bins))) * 10.0 ** rng.uniform(-1.5, 1.5, (frames, bins))
+            * amp[:, None]).astype(np.complex64)
+    if c["kind"] == "zero":
+        bank[:] = 0
+    last = frames - crop
+    assert last >= 1 and (c["kind"] != "amps" or crop <= frames // 2)
+    nmix = np.array(c["nmix"], np.int32)
+    starts = rng.integers(0, last + 1, (B, 4)).astype(np.int32)
+    if c["kind"] == "amps":
+        starts[:-1] = rng.integers(0, frames // 2 - crop + 1, (B - 1, 4))         # loud clips from the loud rows,
+        starts[-1] = rng.integers(frames // 2, last + 1, 4)                       # the last clip from the quiet ones
+    starts[0, 0] = 0
+    for b in range(B):
+        if nmix[b] >= 3:
+            starts[b, 1] = starts[b, 0]
+        if b == B - 1:
+            starts[b, nmix[b] - 1] = last
+        starts[b, nmix[b]:] = [-1, INT_MAX, -1][:4 - nmix[b]]
+    d = dict(c, B=B, bank=bank, starts=starts, nmix=nmix, nstd=None, z=None, seed=0, cmean=None, cstd=None)
+    if c["noise"] == "off":
+        d["nstd"] = np.zeros(B, np.float32)
+    elif c["noise"]:
+        d["nstd"] = np.array(c["nstd"], np.float32)
+        assert len(d["nstd"]) == B
+        if c["noise"] == "explicit":
+            d["z"] = rng.standard_normal((B, crop, bins)).astype(np.float32)
+        else:
+            d["seed"] = 0x9E3779B97F4A7C15 ^ (bins * 1000003 + n_mels)            # all 64 bits in use
+    if c["zscore"]:
+        d["cmean"] = (0.3 * (rng.standard_normal(bins) + 1j * rng.standard_normal(bins))).astype(np.complex64)
+        d["cstd"] = (1.0 + rng.random(bins)).astype(np.float32)
+    d["W"], d["lo"], d["hi"] = make_bank(c["bank"], n_mels, bins, seed, c["width"])
+    return d
+
+
+def mix_reference_of(d, mutation=None):
+    return mix_logmel_reference(d["bank"], d["starts"], d["nmix"], d["nstd"], d["z"], d["cmean"], d["cstd"], d["W"], d["lo"], d["hi"],
+                                mutation, d["crop"], d["seed"] if d["noise"] == "gen" else None)
+
+
+def emulate_mix_f32(bank, starts, nmix, nstd, z, cmean, cstd, W, lo, hi, crop, seed=None, order="lanes"):
+    """Plain float32 numpy of the same operation (no fma: every product and every add rounds).  order "lanes": the band sum as four
+    interleaved chains k = lo + q, lo + q + 4, .. added as (0 + 1) + (2 + 3), the kernel's order; "plain": one chain over the band."""
+    f32 = np.float32
+    bank = np.asarray(bank, np.complex64)
+    re, im = np.ascontiguousarray(bank.real), np.ascontiguousarray(bank.imag)
+    bins, B = bank.shape[1], len(nmix)
+    t = np.arange(crop)
+    P = np.empty((B, crop, bins), f32)
+    if z is None and nstd is not None and seed is not None:
+        h = DO.counter_bits(seed, _counters(B, crop, bins))
+        u1 = (((h >> np.uint64(40)) & np.uint64(0xFFFFFF)).astype(f32) + f32(1)) * f32(1 / 16777216)
+        u2 = ((h >> np.uint64(8)) & np.uint64(0xFFFFFF)).astype(f32) * f32(1 / 16777216)
+        z = np.sqrt(f32(-2) * np.log(u1)) * np.cos(f32(2 * np.pi) * u2)
+        assert z.dtype == f32
+    for b in range(B):
+        nm = int(nmix[b])
+        x, y = re[starts[b, 0] + t], im[starts[b, 0] + t]
+        for j in range(1, nm):
+            x, y = x + re[starts[b, j] + t], y + im[starts[b, j] + t]
+        if nm > 1:
+            inv = f32(1) / f32(nm)
+            x, y = x * inv, y * inv
+        if nstd is not None and nstd[b] > 0:
+            x = x + f32(nstd[b]) * np.asarray(z[b], f32)
+        if cmean is not None:
+            mu = np.asarray(cmean, np.complex64)
+            inv = f32(1) / np.asarray(cstd, f32)
+            x, y = (x - mu.real) * inv, (y - mu.imag) * inv
+        a = np.sqrt(x * x + y * y)
+        P[b] = a * a
+        assert P.dtype == f32 and a.dtype == f32
+    W = np.asarray(W, f32)
+    out = np.empty((B, crop, W.shape[0]), f32)
+    for m in range(W.shape[0]):
+        chains = [range(int(lo[m]) + q, int(hi[m]), 4) for q in range(4)] if order == "lanes" else [range(int(lo[m]), int(hi[m]))]
+        acc = []
+        for ch in chains:
+            a = np.zeros((B, crop), f32)
+            for j in ch:
+                a = a + W[m, j] * P[..., j]
+            acc.append(a)
+        s = (acc[0] + acc[1]) + (acc[2] + acc[3]) if order == "lanes" else acc[0]
+        out[..., m] = np.maximum(f32(-100.0), f32(10.0) * log10_f32(np.maximum(f32(AMIN), s)))
     assert out.dtype == f32
     return out

@@ -2,11 +2,17 @@
 the reference agrees with oracle/frontend_oracle.py (precision="f64") to float64 rounding; the gate accepts an independent plain
 float32 emulation (radix-2 FFT with a float32 twiddle table, fp32 power and band sums) on every input family of the GPU file; and
 every mutated reference -- and the old tolerance's worth of error -- is rejected on the inputs of the sensitivity cases.  A gate that
-is too loose, or too tight for a correct fp32 implementation, is found here, before a GPU is involved."""
+is too loose, or too tight for a correct fp32 implementation, is found here, before a GPU is involved.
+
+The same for the Complex-mode batch kernel (tests/test_gpu_complex_augment_exact_oracle.py): at every case of that file's list a plain
+fp32 numpy emulation passes mix_ratio with the band sums in the kernel's lane order and in plain order, every mutated reference fails
+it at the cases it is listed for, and mix_logmel_reference agrees with oracle/dataset_oracle.py's mix_samples / add_noise /
+transform_complex run in double precision."""
 import numpy as np
 import pytest
 
 import frontend_formula as FF
+from oracle import dataset_oracle as DO
 from oracle import frontend_oracle as FO
 
 
@@ -124,3 +130,93 @@ def test_complex_and_crop_gates():
     assert FF.crops_ratio((crops - mean) / std, bank, starts, 8, mean, std).max() <= 1.0
     assert FF.crops_ratio(np.nextafter(crops, f32(np.inf)), bank, starts, 8).max() == np.inf
     assert FF.crops_ratio((crops - np.roll(mean, 1)) / std, bank, starts, 8, mean, std).max() > 1.0
+
+
+# ---- sed_complex_augment_logmel --------------------------------------------------------------------------------------------------------
+def _emulate(d, order):
+    return FF.emulate_mix_f32(d["bank"], d["starts"], d["nmix"], d["nstd"], d["z"], d["cmean"], d["cstd"], d["W"], d["lo"], d["hi"], d["crop"],
+                              d["seed"] if d["noise"] == "gen" else None, order)
+
+
+def test_mix_case_list_covers_what_it_promises():
+    C = FF.MIX_CASES
+    assert {c["bins"] for c in C} == {33, 257, 513, 16385, 32769} and {c["n_mels"] for c in C} >= {1, 17, 64, 65, 130}
+    assert {c["crop"] for c in C} >= {1, 9} and max(len(c["nmix"]) for c in C) <= 5
+    assert {c["bank"] for c in C} >= {"slaney", "lengths", "empty", "dense"} and {c["kind"] for c in C} == {"noise", "amps", "zero"}
+    assert {(c["noise"], c["zscore"]) for c in C} >= {(n, z) for n in (None, "explicit", "gen") for z in (False, True)} | {("off", False)}
+    assert any(set(c["nmix"]) == {1, 2, 3, 4} for c in C)
+    assert all(len(c["nmix"]) * c["crop"] <= 2 and c["n_mels"] <= 17 for c in C if c["bins"] > 16384)
+    assert any(0.0 in c["nstd"] and max(c["nstd"]) > 0 for c in C if c["nstd"])
+    listed = {m for c in C for m in FF.mix_mutations_for(c)}
+    assert listed == set(FF.MIX_MUTATIONS)
+    for c in C:
+        d = FF.make_mix_inputs(c)
+        st, nm, last = d["starts"], d["nmix"], c["frames"] - c["crop"]
+        assert (st[0, 0] == 0 or (d["B"], nm[0]) == (1, 1)) and st[-1, nm[-1] - 1] == last      # (one clip of one crop: the last start)
+        used = [st[b, :nm[b]] for b in range(d["B"])]
+        assert all(((u >= 0) & (u <= last)).all() for u in used)
+        assert all(set(st[b, nm[b]:]) <= {-1, FF.INT_MAX} for b in range(d["B"]))
+        assert all(len(set(u)) < len(u) for u in used if len(u) >= 3)           # a start held twice
+
+
+@pytest.mark.parametrize("c", FF.MIX_CASES, ids=FF.mix_id)
+def test_mix_gate_accepts_fp32_and_rejects_every_mutation(c):
+    d = FF.make_mix_inputs(c)
+    ref = FF.mix_reference_of(d)
+    got = {order: _emulate(d, order) for order in ("lanes", "plain")}
+    r = {order: FF.mix_ratio(g, ref).max() for order, g in got.items()}
+    print(f"\n{FF.mix_id(c)}: fp32 emulation max err/bound  lanes {r['lanes']:.3f}  plain {r['plain']:.3f}", end="")
+    assert r["lanes"] <= 1.0 and r["plain"] <= 1.0
+    if c["kind"] == "zero" and not c["zscore"]:
+        assert (got["lanes"] == -100.0).all() and (ref.p == 0).all()
+    for m in range(c["n_mels"]):                                                # an empty band is exactly -100
+        if d["hi"][m] == d["lo"][m]:
+            assert (got["lanes"][..., m] == -100.0).all() and (ref.p[..., m] == 0).all()
+    for mut in FF.mix_mutations_for(c):
+        rm = FF.mix_ratio(got["lanes"], FF.mix_reference_of(d, mut)).max()
+        print(f"  {mut} {rm:.3g}", end="")
+        assert rm > 1.0, mut
+
+
+def test_mix_gate_is_not_slack():
+    """one ulp-scale error that the flat 2e-3 dB tolerance let through by a factor of hundreds: a loud single-bin band 1e-4 dB off"""
+    c = FF.MIX_CASES[1]
+    d = FF.make_mix_inputs(c)
+    ref = FF.mix_reference_of(d)
+    got = _emulate(d, "lanes")
+    one = np.flatnonzero(d["hi"] - d["lo"] == 1)[0]
+    bad = got.copy()
+    bad[0, 0, one] += np.float32(1e-4)
+    assert FF.mix_ratio(got, ref).max() <= 1.0 < FF.mix_ratio(bad, ref)[0, 0, one]
+    bad = got.copy()
+    bad[0, 0, np.flatnonzero(d["hi"] == d["lo"])[0]] = np.float32(-100.00001)   # silence has to be exact
+    assert FF.mix_ratio(bad, ref).max() == np.inf
+
+
+def test_mix_reference_agrees_with_the_dataset_oracle():
+    for c in (FF.MIX_CASES[6], FF.MIX_CASES[7], FF.MIX_CASES[3]):               # noise + z-score; noise alone; neither
+        d = FF.make_mix_inputs(c)
+        ref = FF.mix_reference_of(d)
+        bank = d["bank"].astype(np.complex128)[None]
+        mel = d["W"].astype(np.float64).T
+        for b in range(d["B"]):
+            f, _ = DO.mix_samples(bank, np.zeros((c["frames"], 1)), list(d["starts"][b, :d["nmix"][b]]), c["crop"])
+            if d["nstd"] is not None and d["nstd"][b] > 0:
+                f = DO.add_noise(f, float(d["nstd"][b]), d["z"][b][None].astype(np.float64))
+            if c["zscore"]:
+                f = (f - d["cmean"].astype(np.complex128)) / d["cstd"].astype(np.float64)
+            np.testing.assert_allclose(f[0], ref.V[b], rtol=0, atol=1e-13 * np.abs(ref.V[b]).max())
+            p = np.abs(f[0]) ** 2 @ mel
+            np.testing.assert_allclose(p, ref.p[b], rtol=1e-13, atol=0)
+            if c["zscore"]:                                                     # the oracle's own last step (it returns float32)
+                lm = DO.transform_complex(f - 0, 0.0, 1.0, mel)[0]
+                np.testing.assert_allclose(lm, ref.v[b], rtol=0, atol=2.0 ** -24 * np.abs(ref.v[b]).max())
+    # the generator: the float64 draw rounds to the oracle's fp32 one, and the bound C_GEN holds for a plain fp32 Box-Muller
+    ctr = np.arange(100000, dtype=np.uint64)
+    z64 = FF.counter_normal64(77, ctr)
+    assert np.array_equal(z64.astype(np.float32), DO.counter_normal(77, ctr)) and np.abs(z64).max() <= FF.R_GEN
+    h = DO.counter_bits(77, ctr)
+    u1 = (((h >> np.uint64(40)) & np.uint64(0xFFFFFF)).astype(np.float32) + np.float32(1)) * np.float32(1 / 16777216)
+    u2 = ((h >> np.uint64(8)) & np.uint64(0xFFFFFF)).astype(np.float32) * np.float32(1 / 16777216)
+    z32 = np.sqrt(np.float32(-2) * np.log(u1)) * np.cos(np.float32(2 * np.pi) * u2)
+    assert z32.dtype == np.float32 and 0 < np.abs(z32 - z64).max() <= FF.C_GEN * FF.U

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import frontend_formula as FF
 from oracle import dataset_oracle as DO
 from oracle import frontend_oracle as FO
 
@@ -194,9 +195,35 @@ def test_spectogram_dataset_end_to_end(env, tmp_path, mode):
     if mode == "Complex":
         np.random.seed(1)
         aug = dsm.SpectogramDataset(d, ms, val_descriptor="rec3", augment_data=True, preprocessed_mode=mode, cfg=cfg)
+        state = np.random.get_state()                      # seed 1 and the constructor's three shuffles
         xa, ya = aug.device_batch(list(range(64)))
         assert torch.isfinite(xa).all() and xa.shape == (64, 1, 30, 64)
         assert ya.shape == (64, 30, 1) and float(ya.max()) <= 1.0
+        # the same draws on the host, in _draw's order (choice of the number of extra crops, a randint per extra crop, rand for the
+        # noise), then every element of the batch against the float64 reference with the generator's noise restated in numpy
+        np.random.set_state(state)
+        tsi = aug.train_start_indices
+        starts = np.zeros((64, 4), np.int32)
+        nmix, nstd = np.ones(64, np.int32), np.zeros(64, np.float32)
+        for b in range(64):
+            st = [int(tsi[b])]
+            for _ in range(int(np.random.choice([0, 1, 2, 3], 1, p=[0.6, 0.25, 0.1, 0.05])[0])):
+                st.append(int(tsi[np.random.randint(len(tsi))]))
+            starts[b, :len(st)], nmix[b], nstd[b] = st, len(st), DO.noise_std_of(np.random.rand())
+        assert set(nmix) >= {1, 2, 3} and (nstd == 0).any() and (nstd > 0).any()
+        assert aug._noise_calls == 1
+        seed = (aug.noise_seed * 0x9E3779B1 + aug._noise_calls) & 0xFFFFFFFFFFFFFFFF
+        fe = aug.fe
+        mref = FF.mix_logmel_reference(feats[0].astype(np.complex64), starts, nmix, nstd, None,
+                                       np.broadcast_to(msd["mean"], (cfg.bins,)).astype(np.complex64),
+                                       np.broadcast_to(msd["std"], (cfg.bins,)).astype(np.float32), fe.melT.cpu().numpy(),
+                                       fe.mel_lo.cpu().numpy(), fe.mel_hi.cpu().numpy(), crop=30, seed=seed)
+        ratio = FF.mix_ratio(xa[:, 0].cpu().numpy(), mref)
+        print(f"\ndevice_batch, 64 augmented clips: max err/bound {ratio.max():.3f}", end="")
+        assert ratio.max() <= 1.0, (np.unravel_index(ratio.argmax(), ratio.shape), ratio.max())
+        ev = aug.train_event_matrix
+        want = np.stack([np.max([ev[s:s + 30] for s in starts[b, :nmix[b]]], axis=0) for b in range(64)])
+        assert np.array_equal(ya.cpu().numpy(), want)
     # train() + device-side eval() run on it
     tr = importlib.import_module(PKG + ".train")
     sed = importlib.import_module(PKG)
