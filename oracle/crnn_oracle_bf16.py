@@ -6,7 +6,7 @@ Same mathematics as oracle/crnn_oracle.py (ConvBlock stack of /root/reference/mo
 torch.nn.GRU's published equations -- the reference itself has no recurrent model, SURVEY D2 --, Linear, x8 interpolate,
 WeightedBCE /root/reference/utils/common.py:16-30, autograd backward /root/reference/train.py:102) in float64, with every
 operand the MI355X engine feeds to the matrix pipe in bf16, or stores in bf16, rounded where the engine rounds it
-(csrc/sed_gru.hip, engine._gru_forward / _gru_backward):
+(csrc/sed_gru.hip, heads.GruHead._forward / _backward):
 
   * the ConvBlock stack: oracle/cnn_oracle_bf16.py (blocks_forward_bf16 / blocks_backward_bf16);
   * m = mean over mel of the bf16 block output, kept in fp32;

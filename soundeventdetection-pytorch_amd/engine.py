@@ -15,23 +15,15 @@ happens in the HIP kernels.  There is no CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as _C
+import math
 import os as _os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 
 from . import _lib as L
-
-BN_EPS = 1e-5
-BN_MOMENTUM = 0.1
-LN_EPS = 1e-5        # the self-attention head's LayerNorm (torch.nn.LayerNorm's default)
-
-
-def pad32(c: int) -> int:
-    return (c + 31) // 32 * 32
+from .heads import BN_EPS, BN_MOMENTUM, FcHead, GruHead, SaConfig, SaHead, _stream, pad32
 
 
 def num_pools_of(model_config) -> int:
@@ -67,10 +59,6 @@ def block0_route(lib, precision: str, mel_bins: int, channels: int, pool: int, g
             lib.sed_conv3x3_bwd_fused_c1_supported(dt, mel_bins, channels, pool):
         return "c1_fused"
     return "c1_stats"
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 def check_pooling(mode) -> int:
@@ -230,34 +218,15 @@ class CnnEngine(OptimizerExtMixin):
                  mel_bins: Optional[int] = None, attention: bool = False, sa_heads: int = 4, pos_encoding: bool = True,
                  sa_layers: int = 1, sa_ffn: int = 0, sa_activation: str = "relu", sa_conv_kernel: int = 0,
                  sa_dropout: float = 0.0, sa_dropout_seed: Optional[int] = None, sa_window=None, sa_rel_pos=None):
-        """attention: a second linear layer att_fc beside event_fc scores every frame per class (csrc/sed_attn.hip): forward()
-        also leaves the attention logits in plan.att, loss_and_grad(weak=("att", ...)) pools with them and backward() then takes
-        both layers.  False launches exactly what it always did.
-        head: 'fc' (Cnn_AvgPooling), 'gru' (CRNN), 'sa' (Csa_AvgPooling: a self-attention encoder layer with sa_heads heads between the
-        mel-mean and event_fc, csrc/sed_mhsa.hip; pos_encoding adds the fixed sinusoidal table to the mel-mean rows; sa_layers post-LN
-        encoder layers, each with a feed-forward sub-layer of width sa_ffn > 0 and activation sa_activation behind the attention,
-        csrc/sed_ffn.hip -- torch.nn.TransformerEncoderLayer(C, sa_heads, sa_ffn, dropout=0, norm_first=False) semantics; sa_conv_kernel
-        = k > 0, odd in [3, 31], puts the Conformer convolution module -- pointwise conv, GLU, depthwise conv of k taps along time,
-        BatchNorm, SiLU, pointwise conv, residual LayerNorm -- between the two, csrc/sed_convmod.hip)
-        sa_dropout = p in [0, 1): torch.nn.TransformerEncoderLayer(dropout=p)'s placement in TRAINING forwards and their backwards --
-        the attention probabilities, each sub-layer's output before its residual add, the FFN hidden activation -- with masks generated
-        inside the kernels from the counter-based state drop_state = (seed_lo, seed_hi, step, 0) (csrc/philox.h); sa_dropout_seed:
-        the 64-bit seed, None -> torch.initial_seed() (no random number is drawn).  p = 0 launches what it always did.
-        sa_window = None, an int w or a pair (left, right), None on a side for unbounded: the local attention window of every head of
-        every layer (key j takes part for query i iff i - left <= j <= i + right; torch's src_mask), in every forward and backward --
-        sed_mhsa_fwd_win / sed_mhsa_bwd_win in the places of the plain / _drop core launches, no new buffers.  None launches what it
-        always did.
-        sa_rel_pos = None, an int L >= 1 (clipped distances, 2L + 1 buckets) or a pair (num_buckets, max_distance) (T5's bidirectional
-        log buckets): a learned bias per head and bucket of the distance j - i on every score of every layer, P["rel_pos*.weight"]
-        (H, num_buckets) -- sed_relpos_expand + sed_mhsa_fwd_rel in the place of the core launch, sed_mhsa_bwd_rel + sed_relpos_fold
-        into G["rel_pos*.weight"] in the backward; the map, the per-layer distance tables and the workspace belong to the plan.  It
-        composes with sa_window and sa_dropout.  None launches what it always did.
-        or 'none' (a bare stack of ConvBlocks: forward() stops at the last pooled output plan.y[-1], backward() takes its gradient).  generic_first: the first conv runs through the general
-        Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and backward() also produces the input gradient
-        plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path keeps the dedicated Cin = 1
-        kernels (no input gradient exists there).  mel_bins: None -> every block's width must be one the specialised kernels
-        are built for (8 / 16 / 32 / 64); an integer F -> inputs must be F wide (1 <= F <= 256) and blocks at other widths run the
-        width-general kernels (csrc/sed_conv_anyw.hip; under 'f16x3' / 'bf16x3' those layers take the exact fp32 kernels)."""
+        """head: 'fc' (Cnn_AvgPooling: heads.FcHead), 'gru' (CRNN: heads.GruHead, gru_hidden units), 'sa' (Csa_AvgPooling: heads.SaHead;
+        pos_encoding and the sa_* options are heads.SaConfig's fields, described and checked there, and belong to this head alone)
+        or 'none' (a bare stack of ConvBlocks: forward() stops at the last pooled output plan.y[-1], backward() takes its gradient).
+        attention: the attention pooling beside event_fc (heads._Head); False launches exactly what it always did.
+        generic_first: the first conv runs through the general Cin >= 1 kernels on an NHWC copy of the (B, Cin, T, F) input and
+        backward() also produces the input gradient plan.dx -- the standalone ConvBlock of spectogram_models.py:128-160; the model path
+        keeps the dedicated Cin = 1 kernels (no input gradient exists there).  mel_bins: None -> every block's width must be one the
+        specialised kernels are built for (8 / 16 / 32 / 64); an integer F -> inputs must be F wide (1 <= F <= 256) and blocks at other
+        widths run the width-general kernels (csrc/sed_conv_anyw.hip; under 'f16x3' / 'bf16x3' those layers take the exact fp32 kernels)."""
         if precision not in ("bf16", "fp32", "bf16x3", "f16x3"):
             raise ValueError("precision must be 'bf16', 'fp32', 'f16x3' or 'bf16x3'")
         if head not in ("fc", "gru", "sa", "none"):
@@ -265,44 +234,10 @@ class CnnEngine(OptimizerExtMixin):
         if head == "gru" and (gru_hidden % 32 or not 32 <= gru_hidden <= 256):
             raise ValueError("gru_hidden must be a multiple of 32 in [32, 256]")
         self.head, self.Hd = head, int(gru_hidden)
-        self.sa_heads, self.pos_encoding = int(sa_heads), bool(pos_encoding)
-        self.sa_layers, self.sa_ffn, self.sa_activation = int(sa_layers), int(sa_ffn), sa_activation
-        self.sa_conv_kernel = int(sa_conv_kernel)
-        if head != "sa" and self.sa_conv_kernel:
-            raise ValueError("sa_conv_kernel belongs to the self-attention head (head='sa')")
-        self.sa_dropout = self.check_sa_dropout(sa_dropout)
-        if head != "sa" and (self.sa_dropout or sa_dropout_seed is not None):
-            raise ValueError("sa_dropout / sa_dropout_seed belong to the self-attention head (head='sa')")
-        self.sa_dropout_seed = (torch.initial_seed() if sa_dropout_seed is None else int(sa_dropout_seed)) & 0xFFFFFFFFFFFFFFFF
-        self.sa_window = self.check_sa_window(sa_window)
-        if head != "sa" and self.sa_window is not None:
-            raise ValueError("sa_window belongs to the self-attention head (head='sa')")
-        # the sides as the C entries take them
-        self._win = None if self.sa_window is None else tuple(L.WIN_UNBOUNDED if v is None else min(v, L.WIN_UNBOUNDED) for v in self.sa_window)
-        # the effective (left, right): what the relative-position entries take where no window is set
-        self._win_sides = self._win if self._win is not None else (L.WIN_UNBOUNDED, L.WIN_UNBOUNDED)
-        self.sa_rel_pos = self.check_sa_rel_pos(sa_rel_pos)
-        if head != "sa" and self.sa_rel_pos is not None:
-            raise ValueError("sa_rel_pos belongs to the self-attention head (head='sa')")
-        self._drop_state = None              # (4,) int32 on the device holding the uint32 words, made with the first plan (on its device)
-        self._drop_dev = "cuda"
-        self._drop_host = [self.sa_dropout_seed & 0xFFFFFFFF, self.sa_dropout_seed >> 32, 0, 0]
-        if head == "sa":
-            if self.sa_conv_kernel and (self.sa_conv_kernel < 3 or self.sa_conv_kernel > 31 or self.sa_conv_kernel % 2 == 0):
-                raise ValueError(f"sa_conv_kernel must be 0 (no convolution module) or an odd integer in [3, 31], got {sa_conv_kernel!r}")
-            if self.sa_layers < 1:
-                raise ValueError(f"sa_layers must be at least 1, got {sa_layers!r}")
-            if self.sa_ffn < 0 or self.sa_ffn % 32 or self.sa_ffn > 4096:
-                raise ValueError(f"sa_ffn must be 0 (no feed-forward sub-layer) or a multiple of 32 up to 4096, got {sa_ffn!r}")
-            if sa_activation not in L.FFN_ACT:
-                raise ValueError(f"sa_activation must be 'relu' or 'gelu', got {sa_activation!r}")
-            self.sa_act = L.FFN_ACT[sa_activation]
-            if self.sa_ffn and int(list(model_config)[-1][0]) > 512:
-                raise ValueError("the feed-forward sub-layer takes at most 512 channels")
-            Cl = int(list(model_config)[-1][0])
-            if self.sa_heads < 1 or Cl % 4 or Cl % self.sa_heads or Cl // self.sa_heads not in (32, 64):
-                raise ValueError(f"the self-attention head needs channels % 4 == 0 and a head width channels / sa_heads of 32 or 64 "
-                                 f"(channels {Cl}, sa_heads {sa_heads})")
+        sa = (sa_heads, pos_encoding, sa_layers, sa_ffn, sa_activation, sa_conv_kernel, sa_dropout, sa_dropout_seed, sa_window, sa_rel_pos)
+        self.sa_config = SaConfig(int(list(model_config)[-1][0]), *sa) if head == "sa" else None
+        for kw, v in (self.sa_config.keywords() if head == "sa" else SaConfig.absent(*sa)).items():
+            setattr(self, kw, v)            # engine.sa_heads, engine.sa_dropout, ...: the checked options (the defaults without the head)
         self.attention = bool(attention)
         if self.attention and head == "none":
             raise ValueError("the attention head sits beside event_fc: it needs a model with a classification head")
@@ -335,108 +270,28 @@ class CnnEngine(OptimizerExtMixin):
         # sums are reduced to one row per rank, summed over the ranks, and finalized with count * world.
         self.bn_sync = None
         self._e_shift = 0                    # f16x3 pre-scale shift of the running backward (_grad_dtype; 0 outside the new backward kinds)
+        self.head_impl = None               # the head's launches and buffers (heads.py); None for head == 'none'
+        if head == "fc":
+            self.head_impl = FcHead(self)
+        elif head == "gru":
+            self.head_impl = GruHead(self)
+        elif head == "sa":
+            self.head_impl = SaHead(self, self.sa_config)
+            self.sa_dropout_seed = self.head_impl.seed      # (None resolved to torch.initial_seed())
 
-    @staticmethod
-    def check_sa_dropout(p) -> float:
-        """a probability in [0, 1) (NaN refused)"""
-        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= float(p) < 1.0:
-            raise ValueError(f"sa_dropout must be a probability in [0, 1), got {p!r}")
-        return float(p)
-
-    @staticmethod
-    def check_sa_window(w):
-        """None, an int w >= 0 (left = right = w) or a pair (left, right) of ints >= 0 / None (unbounded) -> None or the pair"""
-        def side(v):
-            if v is None:
-                return None
-            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
-                raise ValueError(f"a side of sa_window must be None (unbounded) or an integer >= 0, got {v!r}")
-            return v
-        if w is None:
-            return None
-        if isinstance(w, (tuple, list)):
-            if len(w) != 2:
-                raise ValueError(f"sa_window must be None, an integer or a pair (left, right), got {w!r}")
-            return side(w[0]), side(w[1])
-        if isinstance(w, bool) or not isinstance(w, int):
-            raise ValueError(f"sa_window must be None, an integer or a pair (left, right), got {w!r}")
-        return side(w), side(w)
-
-    RELPOS_MAX_BUCKETS = 4096
-
-    @staticmethod
-    def check_sa_rel_pos(v):
-        """None, an int L >= 1 or a pair (num_buckets even >= 4, max_distance > num_buckets / 4) -> None, ("clip", L) or
-        ("log", num_buckets, max_distance); at most RELPOS_MAX_BUCKETS buckets"""
-        def integer(x):
-            return isinstance(x, int) and not isinstance(x, bool)
-        if v is None:
-            return None
-        if isinstance(v, (tuple, list)):
-            if len(v) == 2 and v[0] == "clip":         # (what this function returned)
-                v = v[1]
-            elif len(v) == 3 and v[0] == "log":
-                v = v[1:]
-        if isinstance(v, (tuple, list)):
-            if len(v) != 2 or not integer(v[0]) or not integer(v[1]):
-                raise ValueError(f"sa_rel_pos must be None, an integer L >= 1 or a pair of integers (num_buckets, max_distance), got {v!r}")
-            nb, maxd = v
-            if nb < 4 or nb % 2:
-                raise ValueError(f"sa_rel_pos: num_buckets must be even and >= 4, got {nb}")
-            if 4 * maxd <= nb:
-                raise ValueError(f"sa_rel_pos: max_distance must exceed num_buckets / 4, got {maxd} with {nb} buckets")
-            if nb > CnnEngine.RELPOS_MAX_BUCKETS:
-                raise ValueError(f"sa_rel_pos: at most {CnnEngine.RELPOS_MAX_BUCKETS} buckets, got {nb}")
-            return "log", nb, maxd
-        if not integer(v) or v < 1:
-            raise ValueError(f"sa_rel_pos must be None, an integer L >= 1 or a pair of integers (num_buckets, max_distance), got {v!r}")
-        if 2 * v + 1 > CnnEngine.RELPOS_MAX_BUCKETS:
-            raise ValueError(f"sa_rel_pos: at most {CnnEngine.RELPOS_MAX_BUCKETS} buckets, L = {v} gives {2 * v + 1}")
-        return "clip", v
-
-    @staticmethod
-    def rel_pos_buckets(cfg):
-        """the number of buckets of a checked sa_rel_pos"""
-        return 2 * cfg[1] + 1 if cfg[0] == "clip" else cfg[1]
-
-    @staticmethod
-    def rel_pos_map(cfg, t):
-        """int32 (2t - 1,): the bucket of distance d = j - i at index d + t - 1.  clip: clamp(d, -L, L) + L.  log (T5, bidirectional),
-        n = nb / 2, a = |d|, m = n / 2: (n if d > 0 else 0) + (a if a < m else min(n - 1, m + floor(ln(a / m) / ln(maxd / m) * (n - m)))),
-        evaluated in float64 as written"""
-        d = np.arange(-(t - 1), t, dtype=np.int64)
-        if cfg[0] == "clip":
-            return (np.clip(d, -cfg[1], cfg[1]) + cfg[1]).astype(np.int32)
-        nb, maxd = cfg[1], cfg[2]
-        n = nb // 2
-        m = n // 2
-        a = np.abs(d)
-        big = m + np.floor(np.log(np.maximum(a, 1).astype(np.float64) / m) / np.log(float(maxd) / m) * (n - m)).astype(np.int64)
-        return (np.where(d > 0, n, 0) + np.where(a < m, a, np.minimum(n - 1, big))).astype(np.int32)
-
-    # ---- the dropout state: (seed_lo, seed_hi, step, 0), uint32 words in an int32 device tensor ---------------------------------
-    @property
-    def drop_state(self) -> torch.Tensor:
-        """The (4,) device tensor the NEXT training forward's masks come from (that forward ends by adding 1 to the step word)."""
-        if self._drop_state is None:
-            words = [w - (1 << 32) if w >= (1 << 31) else w for w in self._drop_host]
-            self._drop_state = torch.tensor(words, dtype=torch.int32, device=self._drop_dev)
-        return self._drop_state
+    # names of the self-attention head that tools, tests and the models reach through the engine (heads.SaConfig / heads.SaHead)
+    RELPOS_MAX_BUCKETS = SaConfig.RELPOS_MAX_BUCKETS
+    check_sa_dropout, check_sa_window, check_sa_rel_pos, rel_pos_buckets, rel_pos_map, sa_layer_names, sa_conv_names, sa_rel_name = map(
+        staticmethod, (SaConfig.check_dropout, SaConfig.check_window, SaConfig.check_rel_pos, SaConfig.rel_pos_buckets,
+                       SaConfig.rel_pos_map, SaConfig.layer_names, SaConfig.conv_names, SaConfig.rel_name))
+    drop_state = property(lambda self: self.head_impl.drop_state)
+    _sa_layer_out = lambda self, ly: self.head_impl.layer_out(ly)     # (tests/test_gpu_sa_at_size.py reads a layer's output through it)
 
     def drop_state_words(self):
-        """the four uint32 words as Python ints (synchronises)"""
-        if self._drop_state is None:
-            return list(self._drop_host)
-        return [int(v) & 0xFFFFFFFF for v in self._drop_state.cpu().tolist()]
+        return self.head_impl.drop_state_words()
 
     def set_drop_state(self, words) -> None:
-        """overwrite the state in place (a captured graph keeps reading the same tensor)"""
-        words = [int(w) & 0xFFFFFFFF for w in words]
-        if len(words) != 4:
-            raise ValueError("the dropout state is four uint32 words (seed_lo, seed_hi, step, 0)")
-        self._drop_host = words
-        if self._drop_state is not None:
-            self._drop_state.copy_(torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=torch.int32))
+        self.head_impl.set_drop_state(words)
 
     @staticmethod
     def check_mel_bins(mel_bins):
@@ -470,7 +325,6 @@ class CnnEngine(OptimizerExtMixin):
             return self.dt           # width-general kernels: exact fp32 under the split-operand modes, no pre-scale exponent
         if self.dt_mm != L.SED_F32H3:
             return self.dt_mm
-        import math
         e = max(-100, min(100, int(round(math.log2(max(1, B * H * W)))) + 2 - self._e_shift))
         return L.SED_F32H3 | ((e & 0xff) << 8)
 
@@ -478,7 +332,6 @@ class CnnEngine(OptimizerExtMixin):
         """Binades between the upstream gradient's largest magnitude and what the mean-reduced loss gives at this shape
         (~1/n_ref per element): the f16x3 pre-scale of an input-gradient or eval-mode backward is shifted by it, so that a
         sum-reduced or one-hot upstream gradient does not saturate the fp16 pieces.  0 when the gradient is all zeros."""
-        import math
         if getattr(p, "amax", None) is None:
             p.amax = torch.empty(1, dtype=torch.float32, device=src.device)
         self._k("sed_absmax", self.lib.sed_absmax, L.ptr(src), src.numel(), L.ptr(p.amax), _stream())
@@ -554,20 +407,13 @@ class CnnEngine(OptimizerExtMixin):
         if H < 1:
             raise ValueError("input too short for the pooling stack")
         p.t_out, p.w_out = H, W
-        Cl, Clp = cin, pad32(cin)
-        p.m = torch.empty((B, H, Clp), **f32)
+        p.m = torch.empty((B, H, pad32(cin)), **f32)
         p.pre = torch.empty((B, H, self.K), **f32)
         p.dpre = torch.empty((B, H, self.K), **f32)
         p.loss = torch.zeros(1, **f32)
         p.loss_partial = torch.empty(max(1, (B * H * self.ratio * self.K + 255) // 256), **f32)
-        Cfc = 2 * self.Hd if self.head == "gru" else Cl
-        p.head_ws = torch.empty(max(1, lib.sed_head_bwd_ws_floats(B, H, Cfc, max(1, self.K) * (2 if self.attention else 1))), **f32)
-        if self.attention:
-            self._plan_att(p, B, H, Cfc, dev)
-        if self.head == "gru":
-            p.gru = self._plan_gru(B, H, Cl, dev)
-        if self.head == "sa":
-            p.sa = self._plan_sa(B, H, Cl, dev)
+        if self.head_impl is not None:
+            self.head_impl.plan(p, B, H, cin, dev)
         p.wgrad_ws = torch.empty(max(1, max_wgrad_ws), **f32)
         l0 = p.layers[0][0]
         p.c1_ws = torch.empty((lib.sed_conv_c1_nparts(B, T, F), 9, l0.coutp), **f32)
@@ -628,509 +474,6 @@ class CnnEngine(OptimizerExtMixin):
         p.scratch = [torch.empty(maxact, dtype=self.tdtype, device=dev) for _ in range(2)]
         self._plans[key] = p
         return p
-
-
-    def _plan_att(self, p, B, t, C, dev):
-        """Buffers of the attention head, allocated with the plan (a captured step allocates nothing): the logits and their
-        gradients, the loss workspace, and the packed operands / results of the two layers' backward through sed_head_bwd."""
-        f32 = dict(dtype=torch.float32, device=dev)
-        K = self.K
-        p.att = torch.empty((B, t, K), **f32)
-        p.datt = torch.empty((B, t, K), **f32)
-        p.datt_clip = torch.empty((B, t, K), **f32)      # the clip consistency term's, added to datt
-        p.att_ws = torch.empty(max(1, self.lib.sed_att_loss_ws_bytes(B, t, K) // 8), dtype=torch.float64, device=dev)
-        p.att_dcat = torch.empty((B * t, 2 * K), **f32)
-        p.att_wcat = torch.empty((2 * K, C), **f32)
-        p.att_dw = torch.empty((2 * K, C), **f32)
-        p.att_db = torch.empty(2 * K, **f32)
-        p.clip_prob = torch.empty((B, K), **f32)
-        p.weak_ws = torch.empty(max(1, self.lib.sed_weak_bce_ws_bytes(B, t, K) // 8), dtype=torch.float64, device=dev)
-
-    def _head_operands(self, p):
-        """(dtype, m, rows, Wf, C, Cp, feature gradient) of the linear layer(s) on top: the mel-mean the head forward left behind"""
-        if self.head == "gru":
-            g = p.gru
-            return L.SED_F32, g["fc_m"], g["R"], 1, 2 * self.Hd, 2 * self.Hd, g["dhseq"]
-        if self.head == "sa":
-            g, C = p.sa, self.cfg[-1][0]
-            return L.SED_F32, g["fc_m"], g["R"], 1, C, C, g["dh"]
-        Cl = self.cfg[-1][0]
-        return self.dt, p.m, p.B * p.t_out, p.w_out, Cl, pad32(Cl), p.dy[len(self.cfg) - 1]
-
-    def _att_forward(self, p, P):
-        _, m, rows, _, C, Cp, _ = self._head_operands(p)
-        self._k("sed_att_logits_fwd", self.lib.sed_att_logits_fwd, L.ptr(m), L.ptr(P["att_fc.weight"]), L.ptr(P["att_fc.bias"]),
-                L.ptr(p.att), rows, C, Cp, self.K, _stream())
-
-    def _att_head_backward(self, p, P, G, src, ratio, on_group_done):
-        """The head backward of an engine with attention.  After loss_and_grad(weak=("att", ...)): both layers through ONE
-        sed_head_bwd on the packed [rows][2K] gradients and [2K][C] weight -- the feature gradient is (dpre@fc_w + datt@att_w)/Wf,
-        summed in fp32 and rounded once.  Otherwise event_fc's backward as always, and att_fc's gradient is zero: the flat
-        gradient buffer is overwritten every step and must not keep stale values."""
-        lib, st = self.lib, _stream()
-        dt, m, rows, Wf, C, Cp, dfeat = self._head_operands(p)
-        gw, gb = G["att_fc.weight"], G["att_fc.bias"]
-        if p.att_pending:
-            self._k("sed_att_bwd_pack", lib.sed_att_bwd_pack, L.ptr(p.dpre), L.ptr(p.datt), L.ptr(P["event_fc.weight"]),
-                    L.ptr(P["att_fc.weight"]), L.ptr(p.att_dcat), L.ptr(p.att_wcat), rows, C, self.K, st)
-            self._k("sed_head_bwd", lib.sed_head_bwd, dt, L.ptr(p.att_dcat), L.ptr(m), L.ptr(p.att_wcat), L.ptr(p.att_dw),
-                    L.ptr(p.att_db), L.ptr(dfeat), L.ptr(p.head_ws), p.B, p.t_out, Wf, C, Cp, 2 * self.K, 1, st)
-            self._k("sed_att_bwd_split", lib.sed_att_bwd_split, L.ptr(p.att_dw), L.ptr(p.att_db), L.ptr(G["event_fc.weight"]),
-                    L.ptr(G["event_fc.bias"]), L.ptr(gw), L.ptr(gb), C, self.K, st)
-        else:
-            self._k("sed_head_bwd", lib.sed_head_bwd, dt, L.ptr(src), L.ptr(m), L.ptr(P["event_fc.weight"]),
-                    L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(dfeat), L.ptr(p.head_ws), p.B, p.t_out, Wf,
-                    C, Cp, self.K, ratio, st)
-            gw.zero_()
-            gb.zero_()
-        if on_group_done is not None:
-            on_group_done("att_fc")
-            on_group_done("event_fc")
-
-    def _plan_gru(self, B, t, C, dev):
-        """Buffers of the recurrent head; R = B*t rows."""
-        lib, Hd = self.lib, self.Hd
-        if C % 4:
-            raise ValueError("the GRU head needs a channel count that is a multiple of 4")
-        f32 = dict(dtype=torch.float32, device=dev)
-        R = B * t
-        g = dict(R=R)
-        g["m"] = torch.empty((R, C), **f32)
-        g["gi"] = torch.empty((R, 6 * Hd), **f32)
-        g["hseq"] = torch.empty((R, 2 * Hd), **f32)
-        g["saved"] = torch.empty((R, 8 * Hd), **f32)
-        g["fc_m"] = torch.empty((R, 2 * Hd), **f32)
-        g["dhseq"] = torch.empty((R, 2 * Hd), **f32)
-        g["dgi"] = torch.empty((R, 6 * Hd), **f32)
-        g["dgh"] = torch.empty((R, 6 * Hd), **f32)
-        g["wihT"] = torch.empty((C, 6 * Hd), **f32)
-        g["dm"] = torch.empty((R, C), **f32)
-        g["bhh"] = torch.empty((2, 3 * Hd), **f32)
-        n = lib.sed_gru_pack_elems(Hd)
-        g["pack_f"] = torch.empty(n, dtype=self.tdtype, device=dev)
-        g["pack_b"] = torch.empty(n, dtype=self.tdtype, device=dev)
-        # split-K of the weight-gradient GEMMs (K = B*t rows): SED_GRU_KSPLIT, read here -- when the plan is built, like the other engine-side
-        # SED_* knobs (INTEGRATION.md section 5) -- and kept with the plan, because the workspace below is sized for it
-        g["ksplit"] = max(1, int(_os.environ.get("SED_GRU_KSPLIT", "64")))
-        ws = max(lib.sed_gemm_nt_ws_floats(3 * Hd, C, g["ksplit"]), lib.sed_gemm_nt_ws_floats(3 * Hd, Hd, g["ksplit"]),
-                 lib.sed_gemm_tn_ws_floats(3 * Hd, C, g["ksplit"]), lib.sed_gemm_tn_ws_floats(3 * Hd, Hd, g["ksplit"]))
-        # the BPTT tail's weight / bias gradients come straight from the row-major gate gradients, all four products in one launch
-        # (sed_gemm_tn_batch: reduction index on the rows, shifted hidden-state rows, column sums as a by-product): a workspace each
-        g["ws4"] = [torch.empty(max(1, ws), **f32) for _ in range(4)]
-        g["tn_desc"] = (L.GemmTnDesc * 4)()
-        return g
-
-    GRU_DIRS = ("", "_reverse")
-
-    def _gru_forward(self, p, P, feat, training):
-        lib, dt, st, Hd, g = self.lib, self.dt, _stream(), self.Hd, p.gru
-        B, t = p.B, p.t_out
-        Cl = self.cfg[-1][0]
-        R = g["R"]
-        self._tag = "gru"
-        self._k("sed_mel_mean_fwd", lib.sed_mel_mean_fwd, dt, L.ptr(feat), L.ptr(g["m"]), R, p.w_out, Cl, pad32(Cl), st)
-        for d, sfx in enumerate(self.GRU_DIRS):
-            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["m"]), Cl, L.ptr(P["gru.weight_ih_l0" + sfx]), Cl,
-                    L.ptr(P["gru.bias_ih_l0" + sfx]), g["gi"].data_ptr() + 4 * d * 3 * Hd, 6 * Hd, R, 3 * Hd, Cl, 1, None, st)
-            g["bhh"][d].copy_(P["gru.bias_hh_l0" + sfx])
-        self._k("sed_gru_pack_weights", lib.sed_gru_pack_weights, dt, L.ptr(P["gru.weight_hh_l0"]),
-                L.ptr(P["gru.weight_hh_l0_reverse"]), L.ptr(g["pack_f"]), L.ptr(g["pack_b"]), Hd, st)
-        self._k("sed_gru_seq_fwd", lib.sed_gru_seq_fwd, dt, L.ptr(g["gi"]), L.ptr(g["bhh"]), L.ptr(g["pack_f"]),
-                L.ptr(g["hseq"]), L.ptr(g["saved"]) if training else None, B, t, Hd, st)
-        self._k("sed_head_fwd", lib.sed_head_fwd, L.SED_F32, L.ptr(g["hseq"]), L.ptr(P["event_fc.weight"]),
-                L.ptr(P["event_fc.bias"]), L.ptr(g["fc_m"]), L.ptr(p.pre), B, t, 1, 2 * Hd, 2 * Hd, self.K, st)
-        if self.attention:
-            self._att_forward(p, P)
-        self._tag = ""
-
-    def _gru_backward(self, p, P, G, src, ratio, dfeat, on_group_done):
-        lib, dt, st, Hd, g = self.lib, self.dt, _stream(), self.Hd, p.gru
-        B, t = p.B, p.t_out
-        Cl = self.cfg[-1][0]
-        R = g["R"]
-        self._tag = "gru"
-        if self.attention:
-            self._att_head_backward(p, P, G, src, ratio, on_group_done)
-        else:
-            self._k("sed_head_bwd", lib.sed_head_bwd, L.SED_F32, L.ptr(src), L.ptr(g["fc_m"]), L.ptr(P["event_fc.weight"]),
-                    L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(g["dhseq"]), L.ptr(p.head_ws), B, t, 1,
-                    2 * Hd, 2 * Hd, self.K, ratio, st)
-            if on_group_done is not None:
-                on_group_done("event_fc")
-        self._k("sed_gru_seq_bwd", lib.sed_gru_seq_bwd, dt, L.ptr(g["dhseq"]), L.ptr(g["hseq"]), L.ptr(g["saved"]),
-                L.ptr(g["pack_b"]), L.ptr(g["dgi"]), L.ptr(g["dgh"]), B, t, Hd, st)
-        ks = max(1, min(g["ksplit"], R // 256))
-        # dW_ih = dgi_d^T . m (+ db_ih = column sums of dgi_d);  dW_hh = dgh_d^T . h_prev (+ db_hh), both directions: ONE product
-        # launch and ONE reduction launch.  h_prev = hseq shifted by one step inside each clip's sequence (the forward direction looks
-        # one step back, the reverse one step ahead)
-        ds = g["tn_desc"]
-        for d, sfx in enumerate(self.GRU_DIRS):
-            for j, (a, b, ldb, wname, bname, n, shift) in enumerate((
-                    (g["dgi"].data_ptr() + 4 * d * 3 * Hd, L.ptr(g["m"]), Cl, "gru.weight_ih_l0", "gru.bias_ih_l0", Cl, 0),
-                    (g["dgh"].data_ptr() + 4 * d * 3 * Hd, g["hseq"].data_ptr() + 4 * d * Hd, 2 * Hd, "gru.weight_hh_l0", "gru.bias_hh_l0", Hd,
-                     1 if d == 0 else -1))):
-                e = ds[2 * d + j]
-                e.A, e.B, e.C, e.colsum = a, b, L.ptr(G[wname + sfx]), L.ptr(G[bname + sfx])
-                e.workspace = L.ptr(g["ws4"][2 * d + j]) if ks > 1 else None
-                e.lda, e.ldb, e.ldc, e.M, e.N, e.K, e.seq, e.shift, e.ksplit = 6 * Hd, ldb, n, 3 * Hd, n, R, t, shift, ks
-        self._k("sed_gemm_tn_batch", lib.sed_gemm_tn_batch, dt, _C.cast(ds, _C.c_void_p), 4, st)
-        for d, sfx in enumerate(self.GRU_DIRS):
-            self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(P["gru.weight_ih_l0" + sfx]), Cl,
-                    g["wihT"].data_ptr() + 4 * d * 3 * Hd, 6 * Hd, 3 * Hd, Cl, 3 * Hd, 0, st)
-        if on_group_done is not None:
-            on_group_done("gru")
-        # dm = dgi . [W_ih ; W_ih_reverse]  (both directions in one K = 6*Hd product), then back through the mel mean
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(g["dgi"]), 6 * Hd, L.ptr(g["wihT"]), 6 * Hd, None, L.ptr(g["dm"]),
-                Cl, R, Cl, 6 * Hd, 1, None, st)
-        self._k("sed_mel_mean_bwd", lib.sed_mel_mean_bwd, dt, L.ptr(g["dm"]), L.ptr(dfeat), R, p.w_out, Cl, pad32(Cl), st)
-        self._tag = ""
-
-    @staticmethod
-    def sa_layer_names(l):
-        """(attn, attn_norm, ffn, ffn_norm) module names of encoder layer l: layer 0 keeps the one-layer head's names"""
-        sfx = "" if l == 0 else f"_l{l}"
-        return "attn" + sfx, "attn_norm" + sfx, "ffn" + sfx, "ffn_norm" + sfx
-
-    @staticmethod
-    def sa_conv_names(l):
-        """(convm, conv_norm) module names of encoder layer l's convolution module (between attn_norm* and ffn* of sa_layer_names)"""
-        sfx = "" if l == 0 else f"_l{l}"
-        return "convm" + sfx, "conv_norm" + sfx
-
-    @staticmethod
-    def sa_rel_name(l):
-        """module name of encoder layer l's relative-position table (between attn* and attn_norm* of sa_layer_names)"""
-        return "rel_pos" if l == 0 else f"rel_pos_l{l}"
-
-    def _plan_sa(self, B, t, C, dev):
-        """Buffers of the self-attention head (every one allocated here: a captured step allocates nothing); R = B*t rows.  What a
-        layer's backward reads of its forward is kept per layer (g["layers"]); the gradients in flight are shared by the layers."""
-        lib, Hh, D, kc = self.lib, self.sa_heads, self.sa_ffn, self.sa_conv_kernel
-        f32 = dict(dtype=torch.float32, device=dev)
-        R = B * t
-        g = dict(R=R)
-        for name, cols in (("m", C), ("fc_m", C), ("dh", C), ("dres", C), ("dctx", C), ("dqkv", 3 * C), ("dm", C)):
-            g[name] = torch.empty((R, cols), **f32)
-        g["layers"] = []
-        for _ in range(self.sa_layers):
-            ly = {name: torch.empty((R, cols), **f32) for name, cols in (("qkv", 3 * C), ("ctx", C), ("a", C), ("h", C), ("stats", 2))}
-            ly["lse"] = torch.empty((B, Hh, t), **f32)
-            if D:
-                ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("u", D), ("f", C), ("h2", C), ("stats2", 2))})
-            if kc:
-                # the convolution module: the GLU's input and output, the depthwise output, the activation, the module's output, the
-                # residual LayerNorm's output and statistics, and the BatchNorm's per-channel vectors (Cp = C)
-                ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("cg", 2 * C), ("cv", C), ("cz", C), ("cs", C), ("co", C),
-                                                                                 ("hc", C), ("stats3", 2))})
-                ly.update({name: torch.empty(C, **f32) for name in ("cscale", "cshift", "cmean", "cinvstd")})
-            g["layers"].append(ly)
-        g["h"] = self._sa_layer_out(g["layers"][-1])          # what event_fc (and att_fc) read
-        g["woT"] = torch.empty((C, C), **f32)
-        g["winT"] = torch.empty((C, 3 * C), **f32)
-        if D:
-            # the FFN backward: a and the hidden gradient (da, then du in place), the gradient behind the FFN, the transposed weights
-            g["ffa"], g["fda"] = torch.empty((R, D), **f32), torch.empty((R, D), **f32)
-            g["dh1"] = torch.empty((R, C), **f32)
-            g["w2T"], g["w1T"] = torch.empty((D, C), **f32), torch.empty((C, D), **f32)
-        if kc:
-            # shared by the layers: the statistics partials of the forward and the backward, the BatchNorm backward's coefficients, the
-            # gradients of the activation (ds, then gz in place) and of g, the filter-gradient workspace, the transposed pointwise weights
-            g["cpart"] = torch.empty(max(1, lib.sed_dwconv_glu_fwd_ws_floats(B, t, C)), **f32)
-            g["cbpart"] = torch.empty((max(1, lib.sed_bn_silu_bwd_nparts(R)), 2, C), **f32)
-            g["ccoef"] = torch.empty((3, C), **f32)
-            g["cds"], g["cdg"], g["dhc"] = torch.empty((R, C), **f32), torch.empty((R, 2 * C), **f32), torch.empty((R, C), **f32)
-            g["cw_ws"] = torch.empty(max(1, lib.sed_dwconv_glu_bwd_ws_floats(B, t, C, kc)), **f32)
-            g["cw2T"], g["cw1T"] = torch.empty((C, C), **f32), torch.empty((2 * C, C), **f32)
-        if self.sa_dropout:
-            if self._drop_state is None:
-                self._drop_dev = dev
-            _ = self.drop_state                      # made here, never inside a captured step
-            # the gradient of a sub-layer's output a (da = m s dres) and the state the plan's last training forward drew its masks from
-            # (what its backward regenerates them from)
-            g["da"] = torch.empty((R, C), **f32)
-            g["rng"] = torch.zeros(4, dtype=torch.int32, device=dev)
-        g["pe"] = None
-        if self.pos_encoding:
-            # the standard table, built on the host in float64 and rounded once to fp32: pe[i][2j] = sin(i / 10000^(2j/C)), pe[i][2j+1] = cos(.)
-            i = torch.arange(t, dtype=torch.float64)[:, None]
-            j2 = (torch.arange(C) // 2 * 2).to(torch.float64)[None, :]
-            ang = i / torch.pow(torch.tensor(10000.0, dtype=torch.float64), j2 / C)
-            g["pe"] = torch.where((torch.arange(C) % 2 == 0)[None, :], torch.sin(ang), torch.cos(ang)).to(torch.float32).to(dev)
-        g["core_ws"] = torch.empty(max(1, lib.sed_mhsa_bwd_ws_floats(B, t, Hh, C // Hh)), **f32)
-        if self.sa_rel_pos is not None:
-            # the bucket map over the 2t - 1 distances (checked here, on the host: the kernels do not), a distance table and its gradient
-            # per layer, and the core backward's workspace with the per-wave diagonal partials behind D
-            m = np.ascontiguousarray(self.rel_pos_map(self.sa_rel_pos, t))
-            L.check(lib.sed_relpos_map_check(m.ctypes.data, self.rel_pos_buckets(self.sa_rel_pos), t), "sed_relpos_map_check")
-            g["rel_map"] = torch.from_numpy(m).to(dev)
-            for ly in g["layers"]:
-                ly["rel"], ly["drel"] = torch.empty((Hh, 2 * t - 1), **f32), torch.empty((Hh, 2 * t - 1), **f32)
-            g["core_ws"] = torch.empty(max(1, lib.sed_mhsa_bwd_rel_ws_floats(B, t, Hh, C // Hh, *self._win_sides)), **f32)
-        g["ln_ws"] = torch.empty(max(1, lib.sed_add_layernorm_bwd_ws_floats(R, C)), **f32)
-        # split-K of the weight-gradient products (K = R rows), as the recurrent head's tail: SED_GRU_KSPLIT, read with the plan
-        g["ksplit"] = max(1, int(_os.environ.get("SED_GRU_KSPLIT", "64")))
-        tn = [lib.sed_gemm_tn_ws_floats(3 * C, C, g["ksplit"])]
-        if D:
-            tn += [lib.sed_gemm_tn_ws_floats(C, D, g["ksplit"]), lib.sed_gemm_tn_ws_floats(D, C, g["ksplit"])]
-        if kc:
-            tn += [lib.sed_gemm_tn_ws_floats(2 * C, C, g["ksplit"])]
-        g["tn_ws"] = torch.empty(max(1, max(tn)), **f32)
-        return g
-
-    def _sa_layer_out(self, ly):
-        return ly["h2"] if self.sa_ffn else ly["hc"] if self.sa_conv_kernel else ly["h"]
-
-    def _add_ln_fwd(self, g, x, a, gamma, beta, y, stats, R, C, sid):
-        """y = LayerNorm(x + a); sid: the dropout stream of a, None = no dropout (the plain launch)"""
-        lib, st = self.lib, _stream()
-        if sid is None:
-            self._k("sed_add_layernorm_fwd", lib.sed_add_layernorm_fwd, L.ptr(x), L.ptr(a), L.ptr(gamma), L.ptr(beta), L.ptr(y),
-                    L.ptr(stats), R, C, LN_EPS, st)
-        else:
-            self._k("sed_add_layernorm_fwd_drop", lib.sed_add_layernorm_fwd_drop, L.ptr(x), L.ptr(a), L.ptr(gamma), L.ptr(beta), L.ptr(y),
-                    L.ptr(stats), R, C, LN_EPS, self.sa_dropout, L.ptr(g["rng"]), sid, st)
-
-    def _add_ln_bwd(self, g, dy, x, a, gamma, stats, dgamma, dbeta, R, C, sid):
-        """the residual LayerNorm's backward: g["dres"] = the gradient of x; returns the gradient of a (g["dres"], or g["da"] = m s dres
-        under dropout stream sid)"""
-        lib, st = self.lib, _stream()
-        if sid is None:
-            self._k("sed_add_layernorm_bwd", lib.sed_add_layernorm_bwd, L.ptr(dy), L.ptr(x), L.ptr(a), L.ptr(gamma), L.ptr(stats),
-                    L.ptr(g["dres"]), L.ptr(dgamma), L.ptr(dbeta), L.ptr(g["ln_ws"]), R, C, st)
-            return g["dres"]
-        self._k("sed_add_layernorm_bwd_drop", lib.sed_add_layernorm_bwd_drop, L.ptr(dy), L.ptr(x), L.ptr(a), L.ptr(gamma), L.ptr(stats),
-                L.ptr(g["dres"]), L.ptr(g["da"]), L.ptr(dgamma), L.ptr(dbeta), L.ptr(g["ln_ws"]), R, C, self.sa_dropout, L.ptr(g["rng"]),
-                sid, st)
-        return g["da"]
-
-    def _lin_dx(self, dy, W, wT, dx, rows, n_out, n_in):
-        """dx[rows][n_in] = dy[rows][n_out] . W[n_out][n_in], through W's transpose in wT[n_in][n_out]"""
-        lib, st = self.lib, _stream()
-        self._k("sed_transpose_shift", lib.sed_transpose_shift, L.ptr(W), n_in, L.ptr(wT), n_out, n_out, n_in, n_out, 0, st)
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, self.dt, L.ptr(dy), n_out, L.ptr(wT), n_out, None, L.ptr(dx), n_in, rows, n_in, n_out, 1,
-                None, st)
-
-    def _lin_dw(self, dy, x, dW, db, rows, n_out, n_in, t, ks, ws):
-        """dW[n_out][n_in] = dy^T . x over the rows, db = the column sums of dy (split-K ks with the workspace ws)"""
-        self._k("sed_gemm_tn", self.lib.sed_gemm_tn, self.dt, L.ptr(dy), n_out, L.ptr(x), n_in, L.ptr(dW), n_in, L.ptr(db), n_out, n_in,
-                rows, t, 0, ks, ws, _stream())
-
-    def _mhsa_opts(self, g, ly, l, drop):
-        """The core entry of layer l, the same for the forward and the backward: its suffix and its arguments between the sizes and
-        the tables' gradient / the stream.  A table takes _rel (with the window, or both sides unbounded), else a window _win, else
-        dropout _drop, else the plain entry."""
-        rng = L.ptr(g["rng"]) if drop else None
-        if self.sa_rel_pos is not None:
-            return "_rel", (*self._win_sides, drop, rng, 8 * l + 0, L.ptr(ly["rel"]))
-        if self._win is not None:
-            return "_win", (*self._win, drop, rng, 8 * l + 0)
-        if drop:
-            return "_drop", (drop, rng, 8 * l + 0)
-        return "", ()
-
-    def _mhsa_fwd(self, g, ly, l, training, drop):
-        """ly["qkv"] -> ly["ctx"]; lse is kept for a backward (training) and wherever the masks are drawn"""
-        (B, Hh, t), C = ly["lse"].shape, ly["ctx"].shape[1]
-        sfx, opts = self._mhsa_opts(g, ly, l, drop)
-        self._k("sed_mhsa_fwd" + sfx, getattr(self.lib, "sed_mhsa_fwd" + sfx), self.dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]),
-                L.ptr(ly["lse"]) if training or drop else None, B, t, Hh, C // Hh, *opts, _stream())
-
-    def _mhsa_bwd(self, g, ly, l, drop):
-        """g["dctx"] -> g["dqkv"] (and ly["drel"] where there is a table)"""
-        (B, Hh, t), C = ly["lse"].shape, ly["ctx"].shape[1]
-        sfx, opts = self._mhsa_opts(g, ly, l, drop)
-        if sfx == "_rel":
-            opts += (L.ptr(ly["drel"]),)
-        self._k("sed_mhsa_bwd" + sfx, getattr(self.lib, "sed_mhsa_bwd" + sfx), self.dt, L.ptr(ly["qkv"]), L.ptr(ly["ctx"]), L.ptr(g["dctx"]),
-                L.ptr(ly["lse"]), L.ptr(g["dqkv"]), L.ptr(g["core_ws"]), B, t, Hh, C // Hh, *opts, _stream())
-
-    def _sa_conv_forward(self, p, P, l, ly, training, bn_training, update_running_stats):
-        """The convolution module of layer l behind attn_norm: ly["h"] -> ly["hc"].  training: keep what a backward reads;
-        bn_training: batch statistics (and the running update) instead of the running statistics."""
-        lib, dt, st, g, kc = self.lib, self.dt, _stream(), p.sa, self.sa_conv_kernel
-        B, t, C, R = p.B, p.t_out, self.cfg[-1][0], p.sa["R"]
-        cm, cn = self.sa_conv_names(l)
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["h"]), C, L.ptr(P[cm + ".pointwise1.weight"]), C,
-                L.ptr(P[cm + ".pointwise1.bias"]), L.ptr(ly["cg"]), 2 * C, R, 2 * C, C, 1, None, st)
-        self._k("sed_dwconv_glu_fwd", lib.sed_dwconv_glu_fwd, L.ptr(ly["cg"]), L.ptr(P[cm + ".depthwise.weight"]),
-                L.ptr(P[cm + ".depthwise.bias"]), L.ptr(ly["cz"]), L.ptr(ly["cv"]) if training else None,
-                L.ptr(g["cpart"]) if bn_training else None, B, t, C, kc, st)
-        if bn_training:
-            rm = P[cm + ".bn.running_mean"] if update_running_stats else None
-            rv = P[cm + ".bn.running_var"] if update_running_stats else None
-            self._k("sed_bn_train_finalize", lib.sed_bn_train_finalize, L.ptr(g["cpart"]), lib.sed_dwconv_nparts(B, t), float(R),
-                    L.ptr(P[cm + ".bn.weight"]), L.ptr(P[cm + ".bn.bias"]), L.ptr(rm), L.ptr(rv), BN_MOMENTUM, BN_EPS,
-                    L.ptr(ly["cscale"]), L.ptr(ly["cshift"]), L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), C, C, st)
-        else:
-            self._k("sed_bn_eval_coeffs", lib.sed_bn_eval_coeffs, L.ptr(P[cm + ".bn.weight"]), L.ptr(P[cm + ".bn.bias"]),
-                    L.ptr(P[cm + ".bn.running_mean"]), L.ptr(P[cm + ".bn.running_var"]), BN_EPS, L.ptr(ly["cscale"]),
-                    L.ptr(ly["cshift"]), C, C, st)
-        self._k("sed_bn_silu_fwd", lib.sed_bn_silu_fwd, L.ptr(ly["cz"]), L.ptr(ly["cscale"]), L.ptr(ly["cshift"]), L.ptr(ly["cs"]), R, C, st)
-        self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["cs"]), C, L.ptr(P[cm + ".pointwise2.weight"]), C,
-                L.ptr(P[cm + ".pointwise2.bias"]), L.ptr(ly["co"]), C, R, C, C, 1, None, st)
-        self._add_ln_fwd(g, ly["h"], ly["co"], P[cn + ".weight"], P[cn + ".bias"], ly["hc"], ly["stats3"] if training else None, R, C,
-                         8 * l + 2 if bn_training and self.sa_dropout else None)
-
-    def _sa_conv_backward(self, p, P, G, l, ly, gcur, eval_bwd, ks, ws, done):
-        """Backward of layer l's convolution module: gcur = the gradient of ly["hc"]; returns the gradient of ly["h"] (g["dhc"])."""
-        lib, dt, st, g, kc = self.lib, self.dt, _stream(), p.sa, self.sa_conv_kernel
-        B, t, C, R = p.B, p.t_out, self.cfg[-1][0], p.sa["R"]
-        cm, cn = self.sa_conv_names(l)
-        w1, w2 = cm + ".pointwise1.weight", cm + ".pointwise2.weight"
-        ga = self._add_ln_bwd(g, gcur, ly["h"], ly["co"], P[cn + ".weight"], ly["stats3"], G[cn + ".weight"], G[cn + ".bias"], R, C,
-                              8 * l + 2 if p.trained and self.sa_dropout else None)
-        done(cn)
-        # ds = ga . pointwise2.weight;  d pointwise2.weight = ga^T . s, its bias gradient the column sums of ga (ga = dres, or m s dres
-        # under dropout: the gradient of the module's output)
-        self._lin_dx(ga, P[w2], g["cw2T"], g["cds"], R, C, C)
-        self._lin_dw(ga, ly["cs"], G[w2], G[cm + ".pointwise2.bias"], R, C, C, t, ks, ws)
-        # through the SiLU (gz over ds) and the BatchNorm: statistics, the finalisation, then dz = ca gz + cb z + cc on load
-        if eval_bwd:
-            self._k("sed_bn_eval_stats", lib.sed_bn_eval_stats, L.ptr(P[cm + ".bn.running_mean"]), L.ptr(P[cm + ".bn.running_var"]), BN_EPS,
-                    L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), C, C, st)
-        nparts = lib.sed_bn_silu_bwd_nparts(R)
-        self._k("sed_bn_silu_bwd_reduce", lib.sed_bn_silu_bwd_reduce, L.ptr(g["cds"]), L.ptr(ly["cz"]), L.ptr(ly["cscale"]),
-                L.ptr(ly["cshift"]), L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), L.ptr(g["cds"]), L.ptr(g["cbpart"]), R, C, st)
-        ca, cb, cc = g["ccoef"][0], g["ccoef"][1], g["ccoef"][2]
-        if eval_bwd:
-            self._k("sed_bn_eval_bwd_finalize", lib.sed_bn_eval_bwd_finalize, L.ptr(g["cbpart"]), nparts, L.ptr(P[cm + ".bn.weight"]),
-                    L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), L.ptr(G[cm + ".bn.weight"]), L.ptr(G[cm + ".bn.bias"]), L.ptr(ca), L.ptr(cb),
-                    L.ptr(cc), C, C, st)
-        else:
-            self._k("sed_bn_bwd_finalize", lib.sed_bn_bwd_finalize, L.ptr(g["cbpart"]), nparts, float(R), L.ptr(P[cm + ".bn.weight"]),
-                    L.ptr(ly["cmean"]), L.ptr(ly["cinvstd"]), L.ptr(G[cm + ".bn.weight"]), L.ptr(G[cm + ".bn.bias"]), L.ptr(ca), L.ptr(cb),
-                    L.ptr(cc), C, C, st)
-        self._k("sed_dwconv_glu_bwd", lib.sed_dwconv_glu_bwd, L.ptr(g["cds"]), L.ptr(ly["cz"]), L.ptr(ca), L.ptr(cb), L.ptr(cc),
-                L.ptr(ly["cv"]), L.ptr(ly["cg"]), L.ptr(P[cm + ".depthwise.weight"]), L.ptr(g["cdg"]), L.ptr(G[cm + ".depthwise.weight"]),
-                L.ptr(G[cm + ".depthwise.bias"]), L.ptr(g["cw_ws"]), B, t, C, kc, st)
-        # d pointwise1.weight = dg^T . h, its bias gradient the column sums of dg;  dh = dg . pointwise1.weight + dres (the residual)
-        self._lin_dw(g["cdg"], ly["h"], G[w1], G[cm + ".pointwise1.bias"], R, 2 * C, C, t, ks, ws)
-        done(cm)
-        self._lin_dx(g["cdg"], P[w1], g["cw1T"], g["dhc"], R, 2 * C, C)
-        g["dhc"].add_(g["dres"])
-        return g["dhc"]
-
-    def _sa_forward(self, p, P, feat, training, bn_training=False, update_running_stats=True):
-        lib, dt, st, g, Hh, D = self.lib, self.dt, _stream(), p.sa, self.sa_heads, self.sa_ffn
-        B, t = p.B, p.t_out
-        C = self.cfg[-1][0]
-        R = g["R"]
-        self._tag = "sa"
-        drop = self.sa_dropout if bn_training else 0.0       # training-mode forwards only (a kept eval forward never drops)
-        if drop:
-            g["rng"].copy_(self.drop_state)                  # this forward's masks, and its backward's
-        self._k("sed_mel_mean_fwd", lib.sed_mel_mean_fwd, dt, L.ptr(feat), L.ptr(g["m"]), R, p.w_out, C, pad32(C), st)
-        if g["pe"] is not None:
-            g["m"].view(B, t, C).add_(g["pe"])          # x' = x + pe[frame], in place: the residual and the projections read x'
-        xin = g["m"]
-        for l, ly in enumerate(g["layers"]):
-            an, nn_, fn, fnn = self.sa_layer_names(l)
-            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(xin), C, L.ptr(P[an + ".in_proj_weight"]), C, L.ptr(P[an + ".in_proj_bias"]),
-                    L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
-            if self.sa_rel_pos is not None:
-                self._k("sed_relpos_expand", lib.sed_relpos_expand, L.ptr(P[self.sa_rel_name(l) + ".weight"]), L.ptr(g["rel_map"]),
-                        L.ptr(ly["rel"]), Hh, self.rel_pos_buckets(self.sa_rel_pos), t, st)
-            self._mhsa_fwd(g, ly, l, training, drop)
-            self._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["ctx"]), C, L.ptr(P[an + ".out_proj.weight"]), C,
-                    L.ptr(P[an + ".out_proj.bias"]), L.ptr(ly["a"]), C, R, C, C, 1, None, st)
-            self._add_ln_fwd(g, xin, ly["a"], P[nn_ + ".weight"], P[nn_ + ".bias"], ly["h"], ly["stats"] if training else None, R, C,
-                             8 * l + 1 if drop else None)
-            xin = ly["h"]
-            if self.sa_conv_kernel:
-                self._sa_conv_forward(p, P, l, ly, training, bn_training, update_running_stats)
-                xin = ly["hc"]
-            if D:
-                # h2 = LayerNorm(h + ffn(h)): both products and the activation in one launch; u only for a backward
-                if drop:
-                    self._k("sed_ffn_fwd_drop", lib.sed_ffn_fwd_drop, dt, self.sa_act, L.ptr(xin), L.ptr(P[fn + ".linear1.weight"]),
-                            L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(ly["f"]),
-                            L.ptr(ly["u"]), R, C, D, drop, L.ptr(g["rng"]), 8 * l + 3, st)
-                else:
-                    self._k("sed_ffn_fwd", lib.sed_ffn_fwd, dt, self.sa_act, L.ptr(xin), L.ptr(P[fn + ".linear1.weight"]),
-                            L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(ly["f"]),
-                            L.ptr(ly["u"]) if training else None, R, C, D, st)
-                self._add_ln_fwd(g, xin, ly["f"], P[fnn + ".weight"], P[fnn + ".bias"], ly["h2"], ly["stats2"] if training else None, R, C,
-                                 8 * l + 4 if drop else None)
-                xin = ly["h2"]
-        self._k("sed_head_fwd", lib.sed_head_fwd, L.SED_F32, L.ptr(g["h"]), L.ptr(P["event_fc.weight"]), L.ptr(P["event_fc.bias"]),
-                L.ptr(g["fc_m"]), L.ptr(p.pre), B, t, 1, C, C, self.K, st)
-        if self.attention:
-            self._att_forward(p, P)
-        if drop:
-            self.drop_state[2:3].add_(1)                     # the next training forward draws new masks (captured with the step)
-        self._tag = ""
-
-    def _sa_backward(self, p, P, G, src, ratio, dfeat, on_group_done):
-        lib, dt, st, g, Hh, D = self.lib, self.dt, _stream(), p.sa, self.sa_heads, self.sa_ffn
-        B, t = p.B, p.t_out
-        C = self.cfg[-1][0]
-        R = g["R"]
-        self._tag = "sa"
-        done = on_group_done if on_group_done is not None else (lambda name: None)
-        if self.attention:
-            self._att_head_backward(p, P, G, src, ratio, on_group_done)
-        else:
-            self._k("sed_head_bwd", lib.sed_head_bwd, L.SED_F32, L.ptr(src), L.ptr(g["fc_m"]), L.ptr(P["event_fc.weight"]),
-                    L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(g["dh"]), L.ptr(p.head_ws), B, t, 1, C, C, self.K,
-                    ratio, st)
-            done("event_fc")
-        ks = max(1, min(g["ksplit"], R // 256))
-        ws = L.ptr(g["tn_ws"]) if ks > 1 else None
-        gcur = g["dh"]                                   # the gradient of the current layer's output
-        drop = self.sa_dropout if p.trained else 0.0     # the masks of the forward this backward belongs to (g["rng"])
-        for l in reversed(range(self.sa_layers)):
-            ly = g["layers"][l]
-            xin = g["m"] if l == 0 else self._sa_layer_out(g["layers"][l - 1])
-            an, nn_, fn, fnn = self.sa_layer_names(l)
-            fin = ly["hc"] if self.sa_conv_kernel else ly["h"]        # the FFN sub-layer's input
-            if D:
-                w1, w2 = fn + ".linear1.weight", fn + ".linear2.weight"
-                ga = self._add_ln_bwd(g, gcur, fin, ly["f"], P[fnn + ".weight"], ly["stats2"], G[fnn + ".weight"], G[fnn + ".bias"], R, C,
-                                      8 * l + 4 if drop else None)
-                done(fnn)
-                # da = ga . w2 (ga: the gradient of the FFN's output -- dres, or m s dres under dropout), then a = act(u) and
-                # du = da act'(u) (du over da; under dropout a = m s act(u), du = da m s act'(u))
-                self._lin_dx(ga, P[w2], g["w2T"], g["fda"], R, C, D)
-                if drop:
-                    self._k("sed_ffn_act_bwd_drop", lib.sed_ffn_act_bwd_drop, self.sa_act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
-                            L.ptr(g["fda"]), R, D, drop, L.ptr(g["rng"]), 8 * l + 3, st)
-                else:
-                    self._k("sed_ffn_act_bwd", lib.sed_ffn_act_bwd, self.sa_act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
-                            L.ptr(g["fda"]), R * D, st)
-                # d linear2.weight = ga^T . a, d linear1.weight = du^T . h, the biases' gradients their column sums
-                self._lin_dw(ga, g["ffa"], G[w2], G[fn + ".linear2.bias"], R, C, D, t, ks, ws)
-                self._lin_dw(g["fda"], fin, G[w1], G[fn + ".linear1.bias"], R, D, C, t, ks, ws)
-                done(fn)
-                # dh = du . w1 + dres (the residual branch)
-                self._lin_dx(g["fda"], P[w1], g["w1T"], g["dh1"], R, D, C)
-                g["dh1"].add_(g["dres"])
-                gcur = g["dh1"]
-            if self.sa_conv_kernel:
-                gcur = self._sa_conv_backward(p, P, G, l, ly, gcur, not p.trained, ks, ws, done)
-            ga = self._add_ln_bwd(g, gcur, xin, ly["a"], P[nn_ + ".weight"], ly["stats"], G[nn_ + ".weight"], G[nn_ + ".bias"], R, C,
-                                  8 * l + 1 if drop else None)
-            done(nn_)
-            # d out_proj.weight = ga^T . ctx, d out_proj.bias = column sums of ga (ga: the gradient of a -- dres, or m s dres under dropout)
-            self._lin_dw(ga, ly["ctx"], G[an + ".out_proj.weight"], G[an + ".out_proj.bias"], R, C, C, t, ks, ws)
-            # dctx = ga . out_proj.weight
-            self._lin_dx(ga, P[an + ".out_proj.weight"], g["woT"], g["dctx"], R, C, C)
-            self._mhsa_bwd(g, ly, l, drop)
-            if self.sa_rel_pos is not None:
-                # ly["rel"] is the table this layer's forward read (the weights do not change between a step's forward and backward)
-                rn = self.sa_rel_name(l)
-                self._k("sed_relpos_fold", lib.sed_relpos_fold, L.ptr(ly["drel"]), L.ptr(g["rel_map"]), L.ptr(G[rn + ".weight"]), Hh,
-                        self.rel_pos_buckets(self.sa_rel_pos), t, st)
-                done(rn)
-            # d in_proj_weight = dqkv^T . x', d in_proj_bias = column sums of dqkv
-            self._lin_dw(g["dqkv"], xin, G[an + ".in_proj_weight"], G[an + ".in_proj_bias"], R, 3 * C, C, t, ks, ws)
-            done(an)
-            # dm = dqkv . in_proj_weight + dres (the residual branch): the gradient of the layer's input
-            self._lin_dx(g["dqkv"], P[an + ".in_proj_weight"], g["winT"], g["dm"], R, 3 * C, C)
-            g["dm"].add_(g["dres"])
-            gcur = g["dm"]
-        # back through the mel mean
-        self._k("sed_mel_mean_bwd", lib.sed_mel_mean_bwd, dt, L.ptr(g["dm"]), L.ptr(dfeat), R, p.w_out, C, pad32(C), st)
-        self._tag = ""
 
     # ------------------------------------------------------------------------------------------
     def _bn_names(self, bi, j):
@@ -1271,20 +614,9 @@ class CnnEngine(OptimizerExtMixin):
                 self._k("sed_bn_relu_pool_fwd", self.lib.sed_bn_relu_pool_fwd, dt, L.ptr(l2.z), L.ptr(l2.scale), L.ptr(l2.shift), L.ptr(p.y[bi]), B,
                                                  l2.H, l2.W, l2.coutp, pool, st)
             prev = p.y[bi]
-        Cl = self.cfg[-1][0]
         self._tag = ""
-        if self.head == "gru":
-            self._gru_forward(p, P, prev, training or p.keep)
-            return p
-        if self.head == "sa":
-            self._sa_forward(p, P, prev, training or p.keep, training, update_running_stats)
-            return p
-        if self.head == "none":
-            return p
-        self._k("sed_head_fwd", self.lib.sed_head_fwd, dt, L.ptr(prev), L.ptr(P["event_fc.weight"]), L.ptr(P["event_fc.bias"]), L.ptr(p.m),
-                                 L.ptr(p.pre), B, p.t_out, p.w_out, Cl, pad32(Cl), self.K, st)
-        if self.attention:
-            self._att_forward(p, P)
+        if self.head_impl is not None:
+            self.head_impl.forward(p, P, prev, training or p.keep, training, update_running_stats)
         return p
 
     def interpolate(self, p: _Plan) -> torch.Tensor:
@@ -1464,7 +796,6 @@ class CnnEngine(OptimizerExtMixin):
         c1_plain = new_kind and p.c1_mode     # C1 mode: the unfused block-0 route, which writes g1 and takes the forward's mask
         lib, dt, st = self.lib, self.dt, _stream()
         B = p.B
-        Cl = self.cfg[-1][0]
         if self.head == "none":
             src, ratio = None, 1
         elif dlogits is None:
@@ -1489,7 +820,7 @@ class CnnEngine(OptimizerExtMixin):
         # an eval forward keeps no pooled-tensor statistics (active-pixel counts): the per-pixel pass everywhere
         pool_fused = [False] * nb if eval_bwd else p.pool_fused
         try:
-            self._backward_blocks(p, P, G, src, ratio, debug, on_group_done, eval_bwd, pool_fused, c1_plain)
+            self._backward_blocks(p, P, G, src, ratio, debug, on_group_done or (lambda name: None), eval_bwd, pool_fused, c1_plain)
         finally:
             self._e_shift = 0
         if need_dx:
@@ -1511,25 +842,12 @@ class CnnEngine(OptimizerExtMixin):
         self._k("sed_bn_bwd_finalize", self.lib.sed_bn_bwd_finalize, L.ptr(bpart), nparts, count, L.ptr(gamma), L.ptr(ly.mean),
                 L.ptr(ly.invstd), L.ptr(dg), L.ptr(db), L.ptr(ca), L.ptr(cb), L.ptr(cc), ly.cout, ly.coutp, _stream())
 
-    def _backward_blocks(self, p, P, G, src, ratio, debug, on_group_done, eval_bwd, pool_fused, c1_plain):
+    def _backward_blocks(self, p, P, G, src, ratio, debug, done, eval_bwd, pool_fused, c1_plain):
         lib, dt, st = self.lib, self.dt, _stream()
         B = p.B
-        Cl = self.cfg[-1][0]
         nb = len(self.cfg)
-        if self.head == "none":
-            pass                      # the caller filled plan.dy[-1] (gradient of the last pooled block output)
-        elif self.head == "gru":
-            self._gru_backward(p, P, G, src, ratio, p.dy[nb - 1], on_group_done)
-        elif self.head == "sa":
-            self._sa_backward(p, P, G, src, ratio, p.dy[nb - 1], on_group_done)
-        elif self.attention:
-            self._att_head_backward(p, P, G, src, ratio, on_group_done)
-        else:
-            self._k("sed_head_bwd", self.lib.sed_head_bwd, dt, L.ptr(src), L.ptr(p.m), L.ptr(P["event_fc.weight"]),
-                                     L.ptr(G["event_fc.weight"]), L.ptr(G["event_fc.bias"]), L.ptr(p.dy[nb - 1]),
-                                     L.ptr(p.head_ws), B, p.t_out, p.w_out, Cl, pad32(Cl), self.K, ratio, st)
-            if on_group_done is not None:
-                on_group_done("event_fc")
+        if self.head_impl is not None:        # (without a head the caller filled plan.dy[-1], the gradient of the last pooled block output)
+            self.head_impl.backward(p, P, G, src, ratio, p.dy[nb - 1], done)
         dzA, dzB = p.scratch
         if any(pool_fused):
             p.pool_flag.zero_()
@@ -1580,8 +898,7 @@ class CnnEngine(OptimizerExtMixin):
                 if debug is not None:
                     raise RuntimeError("stage snapshots need conv1's output in memory: set SED_C1_MODE=0 (or use precision='fp32')")
                 self._backward_block0_c1(p, P, G, eval_bwd, c1_plain, gcount)
-                if on_group_done is not None:
-                    on_group_done("conv_blocks.0")
+                done("conv_blocks.0")
                 continue
             fused2 = p.bwd_fused[bi][1] and debug is None
             if fused2:
@@ -1652,8 +969,7 @@ class CnnEngine(OptimizerExtMixin):
                             L.ptr(q2.mean) if pst else None, L.ptr(q2.invstd) if pst else None, L.ptr(p.bwd_part) if pst else None,
                             p.pool_nparts[bi - 1] if pst else 0, L.ptr(p.pool_flag[bi - 1:]) if pst else None, L.ptr(l1.dwpack), L.ptr(p.wgrad_ws),
                             B, H, W, l1.cinp, l1.coutp, L.ptr(G[w1n]), l1.cout, l1.cin, st)
-                    if on_group_done is not None:
-                        on_group_done(f"conv_blocks.{bi}")
+                    done(f"conv_blocks.{bi}")
                     continue
                 self._k("sed_conv3x3_wgrad_fused", self.lib.sed_conv3x3_wgrad_fused_u, dtg, L.PRO_NONE, L.ptr(xin),
                         None, None, L.DZ_BN, L.ptr(dzB), L.ptr(l1.z), None, None, L.ptr(ca), L.ptr(cb), L.ptr(cc), 1,
@@ -1672,8 +988,7 @@ class CnnEngine(OptimizerExtMixin):
                             l1.cinp, st)
                 if debug is not None and bi > 0:
                     debug[f"dy{bi - 1}"] = p.dy[bi - 1].float().clone()
-            if on_group_done is not None:
-                on_group_done(f"conv_blocks.{bi}")
+            done(f"conv_blocks.{bi}")
         self._tag = ""
 
     def _backward_block0_c1(self, p, P, G, eval_bwd, plain, gcount):

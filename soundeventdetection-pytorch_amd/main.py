@@ -486,26 +486,15 @@ def validate_args(args):
     if getattr(args, "self_attention", False):
         if args.train_features.lower() == "waveform":
             raise ValueError("--self_attention attends over the frames of the spectrogram models: it needs --train_features Spectogram")
-        from .models.spectogram_models import check_sa_conv_kernel, check_sa_encoder, check_sa_geometry
-        check_sa_geometry(128, getattr(args, "sa_heads", 4))
-        check_sa_conv_kernel(getattr(args, "sa_conv_kernel", 0))
-        check_sa_encoder(128, getattr(args, "sa_layers", 1), getattr(args, "sa_ffn", 0), getattr(args, "sa_activation", "relu"))
-        from .engine import CnnEngine
-        CnnEngine.check_sa_dropout(getattr(args, "sa_dropout", 0.0))
-        parse_sa_window(getattr(args, "sa_window", None))
-        CnnEngine.check_sa_rel_pos(parse_sa_rel_pos(getattr(args, "sa_rel_pos", None)))
-    elif getattr(args, "sa_heads", 4) != 4 or getattr(args, "no_pos_encoding", False):
-        raise ValueError("--sa_heads / --no_pos_encoding configure the self-attention head: they need --self_attention")
-    elif getattr(args, "sa_layers", 1) != 1 or getattr(args, "sa_ffn", 0) != 0 or getattr(args, "sa_activation", "relu") != "relu":
-        raise ValueError("--sa_layers / --sa_ffn / --sa_activation configure the self-attention head: they need --self_attention")
-    elif getattr(args, "sa_conv_kernel", 0) != 0:
-        raise ValueError("--sa_conv_kernel configures the self-attention head: it needs --self_attention")
-    elif getattr(args, "sa_dropout", 0.0) != 0.0 or getattr(args, "sa_dropout_seed", None) is not None:
-        raise ValueError("--sa_dropout / --sa_dropout_seed configure the self-attention head: they need --self_attention")
-    elif getattr(args, "sa_window", None) is not None:
-        raise ValueError("--sa_window configures the self-attention head: it needs --self_attention")
-    elif getattr(args, "sa_rel_pos", None) is not None:
-        raise ValueError("--sa_rel_pos configures the self-attention head: it needs --self_attention")
+        from .heads import SaConfig
+        SaConfig(128, getattr(args, "sa_heads", 4), True, getattr(args, "sa_layers", 1), getattr(args, "sa_ffn", 0),
+                 getattr(args, "sa_activation", "relu"), getattr(args, "sa_conv_kernel", 0), getattr(args, "sa_dropout", 0.0), None,
+                 parse_sa_window(getattr(args, "sa_window", None)), parse_sa_rel_pos(getattr(args, "sa_rel_pos", None)))
+    else:
+        for name, default in (("sa_heads", 4), ("no_pos_encoding", False), ("sa_layers", 1), ("sa_ffn", 0), ("sa_activation", "relu"),
+                              ("sa_conv_kernel", 0), ("sa_dropout", 0.0), ("sa_dropout_seed", None), ("sa_window", None), ("sa_rel_pos", None)):
+            if getattr(args, name, default) != default:
+                raise ValueError(f"--{name} configures the self-attention head: it needs --self_attention")
     for flag, value in (("--weak_pooling", weak_options(args).get("weak_pooling")), ("--eval_clip_pooling", getattr(args, "eval_clip_pooling", None))):
         if value == "att" and not att_head:
             raise ValueError(f"{flag} att pools with the attention head: it needs --attention_head")

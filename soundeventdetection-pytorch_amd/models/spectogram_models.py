@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
-from ..engine import CnnEngine, num_pools_of, pad32, _stream
+from ..engine import CnnEngine, SaConfig, num_pools_of, pad32, _stream
 
 DEFAULT_CHANNEL_AND_POOL = [(64, 2), (128, 2), (256, 2), (512, 1)]   # spectogram_models.py:7
 AUDIO_CHANNELS = 1      # dataset/common_config.py:6
@@ -408,20 +408,6 @@ class _LayerNormParams(nn.Module):
         self.bias = nn.Parameter(torch.zeros(normalized_shape))
 
 
-def check_sa_geometry(channels: int, heads: int) -> int:
-    """The head width dh = C / H of the self-attention head, or a ValueError for what the kernels do not cover (host only)."""
-    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
-        raise ValueError(f"sa_heads must be a positive integer, got {heads!r}")
-    if channels % 4:
-        raise ValueError(f"the self-attention head needs a channel count that is a multiple of 4, got {channels}")
-    if channels % heads:
-        raise ValueError(f"the last block's {channels} channels do not divide into sa_heads={heads} heads")
-    if channels // heads not in (32, 64):
-        raise ValueError(f"head width {channels // heads} unsupported (channels {channels} / sa_heads {heads}): the attention "
-                         "kernels cover head widths 32 and 64")
-    return channels // heads
-
-
 class _FfnParams(nn.Module):
     """Parameter holder of an encoder layer's feed-forward sub-layer with torch.nn.TransformerEncoderLayer's names: linear1 (D, C) and
     linear2 (C, D), torch.nn.Linear's initial values, drawn in that order (weight, bias each)."""
@@ -430,18 +416,6 @@ class _FfnParams(nn.Module):
         super().__init__()
         self.linear1 = _LinearParams(channels, width)
         self.linear2 = _LinearParams(width, channels)
-
-
-def check_sa_encoder(channels: int, layers, ffn, activation) -> None:
-    """A ValueError for an encoder stack the kernels do not cover (host only)"""
-    if isinstance(layers, bool) or not isinstance(layers, int) or layers < 1:
-        raise ValueError(f"sa_layers must be a positive integer, got {layers!r}")
-    if isinstance(ffn, bool) or not isinstance(ffn, int) or ffn < 0 or ffn % 32 or ffn > 4096:
-        raise ValueError(f"sa_ffn must be 0 (no feed-forward sub-layer) or a multiple of 32 up to 4096, got {ffn!r}")
-    if ffn and channels > 512:
-        raise ValueError(f"sa_ffn: the feed-forward kernel takes at most 512 channels, the last block has {channels}")
-    if activation not in ("relu", "gelu"):
-        raise ValueError(f"sa_activation must be 'relu' or 'gelu', got {activation!r}")
 
 
 class _Conv1dParams(nn.Module):
@@ -469,13 +443,6 @@ class _ConvModuleParams(nn.Module):
         self.depthwise = _Conv1dParams(channels, channels, kernel_size, groups=channels)
         self.bn = _BatchNormParams(channels)
         self.pointwise2 = _Conv1dParams(channels, channels, 1)
-
-
-def check_sa_conv_kernel(k) -> int:
-    """The tap count of the convolution module's depthwise filter: 0 (no module) or an odd integer in [3, 31]; a ValueError otherwise"""
-    if isinstance(k, bool) or not isinstance(k, int) or (k != 0 and (k < 3 or k > 31 or k % 2 == 0)):
-        raise ValueError(f"sa_conv_kernel must be 0 (no convolution module) or an odd integer in [3, 31], got {k!r}")
-    return k
 
 
 class _RelPosParams(nn.Module):
@@ -553,7 +520,7 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     which is torch's float attn_mask / src_mask (rel_pos_bias(state_dict, l, t) returns it, (H, t, t)); lse, p and ctx run over the
     in-window keys, dropout and the window compose as before.  L: bucket(d) = clamp(d, -L, L) + L, 2L + 1 buckets.  (nb, maxd): T5's
     bidirectional log buckets, nb even >= 4, maxd > nb / 4; n = nb / 2, a = |d|, m = n / 2: bucket = (n if d > 0 else 0) + (a if a < m
-    else min(n - 1, m + floor(ln(a / m) / ln(maxd / m) (n - m)))), in float64 (CnnEngine.rel_pos_map).  Every layer has its own table:
+    else min(n - 1, m + floor(ln(a / m) / ln(maxd / m) (n - m)))), in float64 (heads.SaConfig.rel_pos_map).  Every layer has its own table:
     one module with a single fp32 parameter weight (sa_heads, num_buckets), initialised to zeros (no random number is drawn, every other
     parameter keeps its initial value), registered BETWEEN that layer's attn* and attn_norm* -- layer 0 rel_pos, layer l >= 1
     rel_pos_l{l} -- so the parameter order per layer is attn, rel_pos, attn_norm, convm, conv_norm, ffn, ffn_norm and the backward
@@ -573,15 +540,10 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, sa_heads=4, pos_encoding=True,
                  mel_bins=None, frontend=None, attention=False, sa_layers=1, sa_ffn=0, sa_activation="relu", sa_conv_kernel=0,
                  sa_dropout=0.0, sa_dropout_seed=None, sa_window=None, sa_rel_pos=None):
-        self.sa_dropout = CnnEngine.check_sa_dropout(sa_dropout)          # (before any draw)
-        self.sa_window = CnnEngine.check_sa_window(sa_window)
-        self.sa_rel_pos = CnnEngine.check_sa_rel_pos(sa_rel_pos)
-        self.sa_dropout_seed = None if sa_dropout_seed is None else int(sa_dropout_seed)
-        check_sa_geometry(int(model_config[-1][0]), sa_heads)
-        check_sa_encoder(int(model_config[-1][0]), sa_layers, sa_ffn, sa_activation)
-        self.sa_conv_kernel = check_sa_conv_kernel(sa_conv_kernel)
-        self.sa_heads, self.pos_encoding = int(sa_heads), bool(pos_encoding)
-        self.sa_layers, self.sa_ffn, self.sa_activation = int(sa_layers), int(sa_ffn), sa_activation
+        self.sa_config = SaConfig(int(model_config[-1][0]), sa_heads, pos_encoding, sa_layers, sa_ffn, sa_activation, sa_conv_kernel,
+                                  sa_dropout, sa_dropout_seed, sa_window, sa_rel_pos)          # (checked before any draw)
+        for kw, v in self.sa_config.keywords().items():
+            setattr(self, kw, v)            # model.sa_heads, model.sa_dropout, ...: the checked options
         super().__init__(classes_num, model_config, precision, mel_bins=mel_bins, frontend=frontend, attention=attention)
 
     def _build_head(self, c_last, classes_num):
@@ -614,11 +576,8 @@ class Csa_AvgPooling(Cnn_AvgPooling):
         self.event_fc = _LinearParams(c_last, classes_num)
 
     def _make_engine(self, precision):
-        return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="sa", sa_heads=self.sa_heads,
-                         pos_encoding=self.pos_encoding, mel_bins=self.mel_bins, attention=self.attention, sa_layers=self.sa_layers,
-                         sa_ffn=self.sa_ffn, sa_activation=self.sa_activation, sa_conv_kernel=self.sa_conv_kernel,
-                         sa_dropout=self.sa_dropout, sa_dropout_seed=self.sa_dropout_seed, sa_window=self.sa_window,
-                         sa_rel_pos=self.sa_rel_pos)
+        return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="sa", mel_bins=self.mel_bins,
+                         attention=self.attention, **self.sa_config.keywords())
 
     def _flush_counters(self):
         """The convolution modules' BatchNorm counters follow the conv blocks': counted on the host, folded in when looked at."""

@@ -1,4 +1,4 @@
-"""GPU: the self-attention head (csrc/sed_mhsa.hip, csrc/sed_ffn.hip, CnnEngine._plan_sa / _sa_forward / _sa_backward) through the
+"""GPU: the self-attention head (csrc/sed_mhsa.hip, csrc/sed_ffn.hip, heads.SaHead's plan / forward / backward) through the
 engine at a multi-head, multi-tile size, end to end against torch in float64 and launch by launch against float64.
 
 Geometry: CFG = [(32, 2), (64, 2), (128, 2), (128, 1)], 8 mel bins, B = 4 clips of T = 1040 frames, 3 classes, recall weight 5:
@@ -52,7 +52,7 @@ out-projection reading ctx with a row stride of C / 2 (over K = C / 2, to stay i
 at "a" (1.5e4 gates out); g["tn_ws"] sized for one slab fails the workspace assertion before any backward launch.  (A leading
 dimension below K is refused by sed_gemm_nt itself.)
 
-The Conformer convolution module (csrc/sed_convmod.hip, CnnEngine._sa_conv_forward / _sa_conv_backward) at the same geometry:
+The Conformer convolution module (csrc/sed_convmod.hip, heads.SaHead._conv_forward / _conv_backward) at the same geometry:
   AC  A plus sa_conv_kernel 7        BC  B plus sa_conv_kernel 31
 Biases, the LayerNorm and BatchNorm affine parameters and the running statistics are randomised (tests/test_gpu_sa_conformer.py:
 make_model).  What this size makes happen, asserted from the library (conv_geometry) or the engine (Step): three frame tiles of 64 per

@@ -16,8 +16,8 @@ Core, at (B, t, C, H) = (32, 750, 128, 4) and (16, 750, 512, 8), SED_F32 and SED
                           (bench.measure_peaks, this process; the fp32-input MFMA runs at 1/16 of the bf16 rate), plus B H t^2
                           exponentials (backward: 2 B H t^2) at the vector rate of v_exp_f32, 8 results per clock per SIMD x 4 SIMDs x
                           256 CUs x 2.4 GHz = 1.97e13 / s
-Head, at the bench shape's rows (B = 32, t = 750, C = 128): CnnEngine._sa_forward + _sa_backward (4 heads) against
-  CnnEngine._gru_forward + _gru_backward (hidden 256), each on its own model's plan after one train step, bf16 engines.
+Head, at the bench shape's rows (B = 32, t = 750, C = 128): heads.SaHead's forward + backward (4 heads) against
+  heads.GruHead's (hidden 256), each on its own model's plan (engine.head_impl) after one train step, bf16 engines.
 Train step: eager bf16 FusedTrainer.train_step, B = 32, T = 6001 frames of 64 mel bins, one class: Cnn_AvgPooling, Csa_AvgPooling and
   Crnn_AvgPooling.  predicted_ratio = 1 + (sa head forward + backward) / plain step, an upper bound (the plain head's two launches,
   which the new head replaces, are not subtracted), computed before the steps are timed.
@@ -163,13 +163,13 @@ def heads_and_steps(B, T, reps, warmup, seed):
         trainers[name].train_step(x, y)
     torch.cuda.synchronize()
     hv = {}
-    for name, fwd, bwd in (("csa", "_sa_forward", "_sa_backward"), ("crnn", "_gru_forward", "_gru_backward")):
+    for name in ("csa", "crnn"):
         tr = trainers[name]
-        eng, flat = tr.engine, tr.flat
-        p = list(eng._plans.values())[0]
+        head, flat = tr.engine.head_impl, tr.flat
+        p = list(tr.engine._plans.values())[0]
         Pd = flat.tensor_dict()
-        hv[name + "_head_fwd"] = (lambda eng=eng, p=p, Pd=Pd, fwd=fwd: getattr(eng, fwd)(p, Pd, p.y[-1], True))
-        hv[name + "_head_bwd"] = (lambda eng=eng, p=p, Pd=Pd, flat=flat, bwd=bwd: getattr(eng, bwd)(p, Pd, flat.G, p.dpre, 1, p.dy[-1], None))
+        hv[name + "_head_fwd"] = (lambda head=head, p=p, Pd=Pd: head.forward(p, Pd, p.y[-1], True, False, True))
+        hv[name + "_head_bwd"] = (lambda head=head, p=p, Pd=Pd, flat=flat: head.backward(p, Pd, flat.G, p.dpre, 1, p.dy[-1], lambda name: None))
     head = interleaved(hv, reps, warmup, 5)
     sa_ms = head["csa_head_fwd"]["median_ms"] + head["csa_head_bwd"]["median_ms"]
     gru_ms = head["crnn_head_fwd"]["median_ms"] + head["crnn_head_bwd"]["median_ms"]
