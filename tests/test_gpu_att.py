@@ -22,6 +22,7 @@ import pytest
 import torch
 
 from att_formula import att_loop, att_vectorised, feature_grad, gate, linear_bwd, linear_fwd
+from test_gpu_weak import MANY_CLASSES, events_reach_the_last_slice_and_pass, label_slices
 from weak_formula import frame_counts
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +30,10 @@ pytestmark = pytest.mark.gpu
 PKG = "soundeventdetection-pytorch_amd"
 GUARD = 1024
 FILL = {torch.float32: (float("nan"), -1024.0), torch.float64: (float("nan"), -4096.0), torch.bfloat16: (float("nan"), -1024.0)}
-SHAPES = [(1, 1, 1), (2, 5, 3), (3, 63, 1), (3, 64, 14), (2, 65, 17), (2, 257, 2), (1, 1025, 1)]
+# the last two: many classes, where att_label_slice (the maxima of a strong target, the twin of label_slice in csrc/sed_weak.hip) takes
+# several passes of 256 classes, the slice count is capped at ATT_MAX_SLICES (the first) or clamped to the frames N (the second):
+# the cuts of test_gpu_weak.test_shapes_reach_the_label_slice_branches, which the two files share constant for constant
+SHAPES = [(1, 1, 1), (2, 5, 3), (3, 63, 1), (3, 64, 14), (2, 65, 17), (2, 257, 2), (1, 1025, 1), (2, 125, 527), (1, 3, 8200)]
 W = 5.0                     # recall factor
 U = 2.0 ** -24
 F32, BF16 = 0, 1
@@ -199,6 +203,19 @@ def selections(B):
     return [np.zeros(B, dtype=np.uint8), one, np.full(B, 3, dtype=np.uint8)]
 
 
+def test_shapes_reach_the_label_slice_branches():
+    """att_label_slice through test_att_loss_against_formula.  (2, 125, 527): three passes over the classes, the last with 15 live
+    classes, in 4 to 63 slices; with ratio 8 and Tt around 1000 more than 64 slices are asked for and the count is capped.
+    (1, 3, 8200): 33 passes, and more slices asked for than frames, so the count is clamped to N.  SHAPES before them: one pass."""
+    B, t, K = MANY_CLASSES
+    assert MANY_CLASSES in SHAPES and SHAPES[-1] == (1, 3, 8200) and K - 2 * 256 == 15
+    assert [label_slices(min(t * r, Tt), K) for r in (1, 8) for Tt in frame_totals(t, r)] == \
+        [(4, 4, 16, 3), (8, 8, 16, 3), (9, 9, 14, 3), (32, 31, 16, 3), (65, 63, 16, 3), (65, 63, 16, 3)]
+    assert [label_slices(min(3 * r, Tt), 8200) for r in (1, 8) for Tt in frame_totals(3, r)] == \
+        [(4, 3, 1, 33), (4, 3, 1, 33), (22, 21, 1, 33), (25, 24, 1, 33)]
+    assert all(label_slices(min(s[1] * r, Tt), s[2])[3] == 1 for s in SHAPES[:-2] for r in (1, 8) for Tt in frame_totals(s[1], r))
+
+
 @pytest.mark.parametrize("ratio", [1, 8])
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_att_loss_against_formula(L, shape, ratio):
@@ -214,7 +231,9 @@ def test_att_loss_against_formula(L, shape, ratio):
         for sigma in (1.0, 30.0):
             att = rng.normal(0.0, sigma, shape).astype(np.float32)
             tgts = targets(rng, B, K, Tt)
-            for _ in range(8):          # 8 of the 32 combinations per (Tt, sigma), the next 8 for the next pair
+            if shape == MANY_CLASSES:
+                events_reach_the_last_slice_and_pass(tgts[1], min(t * ratio, Tt))
+            for _ in range(8):         # 8 of the 32 combinations per (Tt, sigma), the next 8 for the next pair
                 form, crit, s, acc = next(combos)
                 sel = None if s is None else selections(B)[s]
                 tag = (shape, ratio, Tt, sigma, form, crit, None if sel is None else int((sel != 0).sum()), acc)
@@ -266,8 +285,14 @@ def test_attention_spread_above_800_underflows_to_exact_zero_weights(L, ratio):
 
 # ---- the linear layer ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rows", [1, 15, 16, 17, 63, 64, 65, 257])
-@pytest.mark.parametrize("geom", [(128, 128, 1), (128, 100, 2), (512, 512, 17), (96, 80, 33), (32, 1, 1)], ids=lambda g: "x".join(map(str, g)))
+@pytest.mark.parametrize("geom", [(128, 128, 1), (128, 100, 2), (512, 512, 17), (96, 80, 33), (32, 1, 1), (128, 128, 527),
+                                  (516, 513, 30), (2048, 2048, 7), (1028, 1025, 3)], ids=lambda g: "x".join(map(str, g)))
 def test_att_logits_against_formula(L, geom, rows):
+    """the last four geoms: more classes than one LDS weight chunk holds, kch = ATT_LDS_FLOATS / (64 NV) = 12288 / (64 NV), so the
+    weights are restaged per chunk between two barriers and the last chunk is partial -- (128, 128, 527): NV = 2, kch = 96, 6
+    chunks, the last of 47 classes; (516, 513, 30): NV = 16, kch = 12, 3 chunks, the last of 6; (2048, 2048, 7): NV = 32, kch = 6,
+    2 chunks, the last of 1 -- and the NV = 16 and NV = 32 instantiations (C > 512, one row per group of 16 lanes), of which
+    (1028, 1025, 3) is the single-chunk case"""
     Cp, C, K = geom
     rng = np.random.default_rng(Cp + 3 * C + 5 * K + rows)
     m = rng.normal(0.0, 1.0, (rows, Cp)).astype(np.float32)
@@ -285,6 +310,42 @@ def test_att_logits_against_formula(L, geom, rows):
     bound_check(got, ref, (C + 2) * U * scale, ("att_logits", geom, rows))
     again = g.new(torch.float32, rows, K)
     L.check(L.lib().sed_att_logits_fwd(L.ptr(d_m), L.ptr(d_w), L.ptr(d_b), L.ptr(again), rows, C, Cp, K, stream()), "att_logits_fwd")
+    assert same_bits(again.cpu().numpy(), got)
+
+
+@pytest.mark.parametrize("case", [(32, 32, 32, 3), (32, 128, 128, 100), (16, 516, 513, 13)], ids=lambda c: "x".join(map(str, c)))
+def test_att_logits_more_rows_than_one_grid_pass(L, case):
+    """att_logits_kernel's loop over `it`: rows = 768 * per_wg + 5, so iters = 2 and the second pass holds 5 rows, in workgroup 0.
+    (32, 32, 32, 3): one chunk -- the weights staged at it == 0 serve it == 1 (the branch `nch > 1 || it == 0` not taken).
+    (32, 128, 128, 100): kch = 96, two chunks per iteration, restaged in both.  (16, 516, 513, 13): NV = 16, one row per group, kch
+    = 12, two chunks."""
+    per_wg, Cp, C, K = case
+    GRID_CAP = 768                      # launch_att_logits in csrc/sed_attn.hip: `if (grid > 768) grid = 768`
+    ROWS_PER_WG = {2: 32, 1: 16}        # 4 waves * ATT_GPW (4 groups of 16 lanes) * RG rows; RG = 2 for C <= 512 (NV <= 8), else 1
+    assert per_wg == ROWS_PER_WG[2 if C <= 512 else 1]
+    edge = GRID_CAP * per_wg            # the first row of the second iteration
+    rows = edge + 5
+    rng = np.random.default_rng(Cp + 3 * C + 5 * K + rows)
+    m = rng.normal(0.0, 1.0, (rows, Cp)).astype(np.float32)
+    m[:, C:] = np.nan                                # the padding holds garbage: it must not be read
+    w, b = rng.normal(0.0, 0.2, (K, C)).astype(np.float32), rng.normal(0.0, 1.0, K).astype(np.float32)
+    g = Guards()
+    d_m, d_w, d_b = dev(m), dev(w), dev(b)
+    att = g.new(torch.float32, rows, K)
+    L.check(L.lib().sed_att_logits_fwd(L.ptr(d_m), L.ptr(d_w), L.ptr(d_b), L.ptr(att), rows, C, Cp, K, stream()), "att_logits_fwd")
+    g.intact()
+    for d, h in ((d_m, m), (d_w, w), (d_b, b)):
+        assert np.array_equal(d.cpu().numpy(), h, equal_nan=True), "an input was modified"
+    ref, scale = linear_fwd(np.nan_to_num(m), w, b)
+    got = att.cpu().numpy()
+    bound = (C + 2) * U * scale
+    for name, sl in (("the last row of the first iteration", slice(edge - 1, edge)), ("the first row of the second", slice(edge, edge + 1)),
+                     ("the last 5 rows", slice(rows - 5, rows))):
+        bound_check(got[sl], ref[sl], bound[sl], ("att_logits", case, name))
+    bound_check(got, ref, bound, ("att_logits", case, rows))
+    again = g.new(torch.float32, rows, K)
+    L.check(L.lib().sed_att_logits_fwd(L.ptr(d_m), L.ptr(d_w), L.ptr(d_b), L.ptr(again), rows, C, Cp, K, stream()), "att_logits_fwd")
+    g.intact()
     assert same_bits(again.cpu().numpy(), got)
 
 

@@ -8,7 +8,9 @@ integers or selections: np.array_equal, no tolerance.  AP is a sum of G non-nega
 math.fsum, G the number of tie groups.  Every output buffer starts filled with a sentinel and lies between two guard regions that
 must be untouched afterwards.
 
-Sizes: 1, 2, around the 64-lane ballot word, around the tile (sed_rank_tile) and several tiles plus a remainder."""
+Sizes: 1, 2, around the 64-lane ballot word, around the tile (sed_rank_tile) and several tiles plus a remainder (SIZES); and the
+corpus sizes of train.eval_ranking, 5, 37 and 258 tiles (CORPUS_SIZES), at which the per-row loops over tiles of the table scan,
+the row scan and the finishing kernel take more than one step and the 64-bit integers need their upper halves."""
 import functools
 import importlib
 import json
@@ -27,6 +29,7 @@ GUARD = 1024
 FILL = {torch.float32: (float("nan"), -1024.0), torch.float64: (float("nan"), -1024.0), torch.int32: (-77, 0x5A5A5A5A),
         torch.uint8: (0x77, 0xA5), torch.int64: (-77, 0x5A5A5A5A5A5A)}
 SIZES = [1, 2, 63, 64, 65, 2047, 2048, 2049, 6161]
+CORPUS_SIZES = [8193, 73828, 526353]     # 5, 37 and 258 tiles: test_corpus_sizes_cover_the_tile_loops
 WORST = {"ratio": 0.0}                   # worst |AP - ref| / (2^-53 * ref) seen by this module, in units of the (G + 8) bound
 
 
@@ -87,6 +90,27 @@ def test_sizes_cover_the_tile(L):
     assert set(SIZES) == {1, 2, 63, 64, 65, tile - 1, tile, tile + 1, 3 * tile + 17}
 
 
+def test_corpus_sizes_cover_the_tile_loops(L):
+    """what each of CORPUS_SIZES is for, from the constants of csrc/sed_rank.hip: 4 scan groups (RK_SCAN_GROUPS), an unroll of 8 in
+    rank_scan_kernel, 256 threads over the tiles of a row in rank_rowscan_kernel and rank_finish_kernel"""
+    tile = L.lib().sed_rank_tile()
+    assert CORPUS_SIZES == [4 * tile + 1, 36 * tile + 100, 257 * tile + 17]
+
+    def groups(tiles):                   # rank_scan_kernel: tiles per scan group
+        per = -(-tiles // 4)
+        return [min(g * per + per, tiles) - min(g * per, tiles) for g in range(4)]
+
+    tiles = [-(-n // tile) for n in CORPUS_SIZES]
+    assert tiles == [5, 37, 258]
+    assert groups(5) == [2, 2, 1, 0]                        # in-group loops run twice, a carry between groups, an empty group
+    assert groups(37) == [10, 10, 10, 7]                    # the unrolled body (8) and its remainder (2, and 7 alone)
+    assert max(groups(-(-n // tile)) for n in SIZES) == [1, 1, 1, 1], "SIZES never reach any of this"
+    per = -(-258 // 256)                                    # rank_rowscan_kernel: tiles per thread
+    assert per == 2 and [t for t in range(256) if min(t * per, 258) < 258][-1] == 128      # threads 129..255 own nothing
+    assert [t for t in range(256) if t + 256 < 258] == [0, 1]                               # rank_finish_kernel: a second step
+    assert CORPUS_SIZES[-1] ** 2 // 8 > 2 ** 32 > SIZES[-1] ** 2           # n^2 / 8, the scale of auc2 at 30 % positives
+
+
 # ---- pack --------------------------------------------------------------------------------------------------------------------------
 def pack_inputs(rows_s, rows_t, K, seed):
     rng = np.random.default_rng(seed)
@@ -116,8 +140,9 @@ def run_pack(L, keys_dev, invalid_dev, score, target, K, capacity, offset):
                                   L.ptr(invalid_dev), stream()), "rank_pack")
 
 
-@pytest.mark.parametrize("K", [1, 3, 14, 40])
+@pytest.mark.parametrize("K", [1, 3, 14, 40, 527])
 def test_pack_is_the_numpy_packing(L, K):
+    """K = 527: 17 column blocks of PK_COLS = 32 classes in rank_pack_kernel, the last one 15 wide (blockIdx.y up to 16)"""
     for rows_s, rows_t, offset, extra in ((1, 1, 0, 0), (255, 300, 7, 5), (256, 256, 0, 1), (700, 513, 300, 64), (257, 257, 1, 0)):
         score, target = pack_inputs(rows_s, rows_t, K, seed=K * 1000 + rows_s)
         n = min(rows_s, rows_t)
@@ -131,7 +156,7 @@ def test_pack_is_the_numpy_packing(L, K):
         want, winv = packed_by_numpy(score, target)
         got = u32(keys)
         assert np.array_equal(got[:, offset:offset + n], want), (K, rows_s, rows_t, offset)
-        if n <= 300:
+        if n <= 300 and n * K <= 300 * 40:                                    # the loop form, where it is quick
             assert np.array_equal(want, pack_formula(score, target)[0])
         sentinel = np.uint32(FILL[torch.int32][0] & 0xFFFFFFFF)
         assert bool((got[:, :offset] == sentinel).all()) and bool((got[:, offset + n:] == sentinel).all()), "columns outside"
@@ -206,6 +231,20 @@ def test_sort_is_np_sort(L, n):
     assert np.array_equal(one[:, :n], np.sort(keys[4:5, :n], axis=1))
     part = run_sort(L, keys, n // 2)                                          # n < capacity by a lot: the rest is left alone
     assert np.array_equal(part[:, :n // 2], np.sort(keys[:, :n // 2], axis=1)) and np.array_equal(part[:, n // 2:], keys[:, n // 2:])
+
+
+@pytest.mark.parametrize("n", CORPUS_SIZES)
+def test_sort_is_np_sort_at_corpus_size(L, n):
+    """rank_scan_kernel with more than one tile per scan group: 5 tiles (groups of 2, 2, 1, 0: the in-group loops twice, the
+    gsum carry, an empty group), 37 tiles (10, 10, 10, 7: the unrolled body and its remainder), 258 tiles.  The rows 'equal' and
+    'two' put one digit in every tile, so every tile's base is a carry over all the tiles before it, and the order of equal digits
+    across tiles (the stability the LSD passes rest on) is decided by this scan alone."""
+    keys = np.concatenate([sort_key_sets(n, n), np.full((5, 37), 0xDEADBEEF, dtype=np.uint32)], axis=1)
+    got = run_sort(L, keys, n)
+    assert np.array_equal(got[:, :n], np.sort(keys[:, :n], axis=1)), n
+    assert np.array_equal(got[:, n:], keys[:, n:]), "the tail of a row was touched"
+    one = run_sort(L, keys[4:5], n)                                           # K = 1
+    assert np.array_equal(one[:, :n], np.sort(keys[4:5, :n], axis=1)) and np.array_equal(one[:, n:], keys[4:5, n:])
 
 
 # ---- curve -------------------------------------------------------------------------------------------------------------------------
@@ -292,6 +331,53 @@ def test_curve_is_the_formula(L, n):
     print(f"worst AP error so far: {WORST['ratio']:.4f} of the (G + 8) * 2^-53 * ref bound")
 
 
+EQUAL_SCORE = np.float32(0.375)
+
+
+@functools.lru_cache(maxsize=None)
+def corpus_case(n):
+    """curve_case(n) and an eighth row, 'all equal': every score EQUAL_SCORE, mixed labels -- one tie group over the whole row.
+    (sorted keys (8, n), the formula's per-row results): computed once per size, shared, never modified"""
+    keys7, refs7 = curve_case(n)
+    labels = (np.random.default_rng(1000 + n).uniform(size=n) < 0.3).astype(np.uint32)
+    row = np.sort((np.uint32(EQUAL_SCORE.view(np.uint32)) << np.uint32(1)) | labels)
+    keys = np.concatenate([keys7, row[None]], axis=0)
+    keys.setflags(write=False)
+    return keys, refs7 + (curve_formula(row),)
+
+
+@pytest.mark.parametrize("n", CORPUS_SIZES)
+def test_curve_is_the_formula_at_corpus_size(L, n):
+    """the suffix scan over many tiles: rank_rowscan_kernel with per = 2 tiles per thread and threads 129..255 empty, and
+    rank_finish_kernel's strided loop taking a second step in threads 0 and 1 (both at 258 tiles, the largest size); tie groups
+    that span hundreds of tiles ('one group over tiles', 'all equal'); and, at the largest size, 64-bit products that need their
+    upper halves: auc2 = sum fp_g (2 S(i') + tp_g) and better_point's tp (npred + P) pass 2^32, which the reference rows are
+    asserted to do below (tests/test_ranking_host.py takes the same rows through 32-bit products: auc2 changes on every row with
+    many negatives in a group, the best point on 'saturated' and 'f1 tie')."""
+    tile = L.lib().sed_rank_tile()
+    keys, refs = corpus_case(n)
+    assert len(refs) == len(CURVE_ROWS) + 1
+    # the eighth row: 1 group, so AP is the single term (P / P) * (P / n), auc2 the single product fp * tp, the best point the whole row
+    e = refs[7]
+    P = e["P"]
+    assert 0 < P < n and counts_row(e) == [P, n, P * (n - P), P, n, 1] and e["best_score"] == EQUAL_SCORE
+    assert e["AP"] == P / n
+    assert refs[3]["P"] == 0 and refs[4]["P"] == n and refs[2]["groups"] == n and refs[1]["groups"] < n // 5
+    assert counts_row(refs[6])[3:5] == [n // 5, n // 5] and refs[6]["best_score"] == np.float32(0.9), "the tie case ties"
+    if n == CORPUS_SIZES[-1]:
+        assert e["auc2"] > 2 ** 32, "one term of auc2 above 2^32"
+        for r in (refs[0], refs[2], refs[5], refs[6]):                        # '8 levels', 'distinct', 'saturated', 'f1 tie'
+            assert r["auc2"] > 2 ** 32 and r["best_tp"] * (r["best_npred"] + r["P"]) > 2 ** 32
+        half = np.uint32(np.float32(0.5).view(np.uint32))
+        assert int(((keys[1] >> np.uint32(1)) == half).sum()) > 200 * tile, "'one group over tiles': a tie group over 200 tiles"
+    check_curve(run_curve(L, keys, n), refs, f"n = {n}")
+    # rows longer than n (capacity > n) and a single row
+    wide = np.concatenate([keys, np.full((8, 19), 0xFFFFFFFF, dtype=np.uint32)], axis=1)
+    check_curve(run_curve(L, wide, n), refs, f"n = {n}, capacity = n + 19")
+    check_curve(run_curve(L, np.ascontiguousarray(keys[1:2]), n), refs[1:2], f"n = {n}, K = 1")
+    print(f"worst AP error so far: {WORST['ratio']:.4f} of the (G + 8) * 2^-53 * ref bound")
+
+
 def test_curve_of_nothing(L):
     ap, counts, best = run_curve(L, np.zeros((3, 0), dtype=np.uint32), 0)
     assert np.isnan(ap).all() and counts.tolist() == [[0] * 6] * 3 and best.tolist() == [1.0] * 3
@@ -319,9 +405,10 @@ def test_pack_sort_curve_together(L):
 
 
 # ---- determinism ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [65, 2049, 6161])
+@pytest.mark.parametrize("n", [65, 2049, 6161, CORPUS_SIZES[-1]])
 def test_two_runs_give_the_same_bits(L, n):
-    keys, _ = curve_case(n)
+    """at the largest size: 258 tiles, every loop over tiles with more than one step"""
+    keys, _ = corpus_case(n) if n in CORPUS_SIZES else curve_case(n)
     shuffled = np.ascontiguousarray(np.random.default_rng(n).permuted(keys, axis=1))
     a, b = run_sort(L, shuffled, n), run_sort(L, shuffled, n)
     assert np.array_equal(a, b) and np.array_equal(a, keys)
@@ -368,6 +455,40 @@ def test_accumulator_grows_and_equals_the_one_shot_call(ru):
     assert json.dumps(acc.compute()) == json.dumps(ru.ranking_metrics_device(s[:700], t[:700]))
     empty = ru.RankingAccumulator(K, "cuda").compute()
     assert empty["classes_scored"] == 0 and math.isnan(empty["mAP"]) and empty["per_class"][0]["n"] == 0
+
+
+def test_accumulator_at_corpus_size(L, ru):
+    """pack, sort and curve through RankingAccumulator(K = 2, capacity = 0) at 257 * tile + 17 elements per class (258 tiles: the
+    multi-step loops of rank_scan_kernel, rank_rowscan_kernel and rank_finish_kernel, integers above 2^32), fed in uneven batches
+    whose ends are multiples neither of rank_pack_kernel's 256 rows nor of the tile, so that the key buffer grows (with its copy)
+    seven times and most appends start in the middle of a pack block"""
+    tile = L.lib().sed_rank_tile()
+    K, n = 2, 257 * tile + 17
+    assert n == CORPUS_SIZES[-1]
+    score, target = pack_inputs(n, n, K, seed=31)
+    score[:, 1] = np.round(score[:, 1] * 64) / 64                             # 65 tie groups beside a nearly distinct column
+    cuts = [0, 1, 700, 4097, 9001, 20003, 70001, 150001, 300003, n]
+    assert all(c % 256 and c % tile for c in cuts[1:])
+    s, t = torch.from_numpy(score).cuda(), torch.from_numpy(target).cuda()
+    acc = ru.RankingAccumulator(K, "cuda", capacity=0)
+    grown = 0
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        before = acc.capacity
+        acc.update(s[a:b], t[a:b])
+        grown += acc.capacity != before
+    assert acc.n == n and acc.capacity >= n and grown >= 7
+    keys, invalid = packed_by_numpy(score, target)                            # (pack_formula is a Python loop over every element)
+    assert int(invalid.sum()) == 0 and np.array_equal(u32(acc.keys[:, :n]), keys), "the appended keys"
+    first = acc.compute_raw()
+    shot = ru.RankingAccumulator(K, "cuda", capacity=n)
+    shot.update(s, t)
+    assert same_raw(first, shot.compute_raw()), "uneven appends and one append give different bits"
+    assert np.array_equal(s.cpu().numpy(), score) and np.array_equal(t.cpu().numpy(), target), "an input was modified"
+    refs = [curve_formula(row) for row in keys]
+    assert all(r["auc2"] > 2 ** 32 and r["best_tp"] * (r["best_npred"] + r["P"]) > 2 ** 32 for r in refs)
+    assert refs[1]["groups"] == 65 and refs[0]["groups"] > n // 2
+    check_curve(first[:3], refs, f"accumulator, {n}")
+    assert first[3].tolist() == [0, 0]
 
 
 def test_accumulator_reports_invalid_scores(ru):

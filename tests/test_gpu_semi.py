@@ -27,13 +27,15 @@ import torch
 
 from semi_formula import bce_sel, ema, frame_mse, weak_ex
 from test_gpu_ops_exact_oracle import SAFE, TINY, U
-from test_gpu_weak import K_CLASSES, W, Guards, batch, dev, frame_totals, make_model, stream, targets, the_plan, within
+from test_gpu_weak import K_CLASSES, W, Guards, batch, dev, frame_totals, label_slices, make_model, stream, targets, the_plan, within
 from weak_formula import MODES, frame_counts
 
 pytestmark = pytest.mark.gpu
 
 PKG = "soundeventdetection-pytorch_amd"
-SHAPES = [(1, 1, 1), (3, 5, 2), (3, 63, 1), (4, 65, 3), (2, 257, 14), (2, 64, 17)]
+# (2, 125, 300): more than 256 classes, so label_slice of csrc/sed_weak.hip (the maxima of a strong target) takes a second pass over
+# the classes, with 44 of its 256 threads live -- under every selection of SELS through sed_weak_bce_fwd_bwd_ex
+SHAPES = [(1, 1, 1), (3, 5, 2), (3, 63, 1), (4, 65, 3), (2, 257, 14), (2, 64, 17), (2, 125, 300)]
 SELS = ["null", "all", "none", "first", "alternating"]
 ids = lambda s: "x".join(map(str, s))           # noqa: E731
 
@@ -147,6 +149,14 @@ def check_accumulate(L, entry, alone, pre, other, sel, ratio, Tt, rng, tag, **kw
 
 def same_bits(a, b):
     return all((x is None and y is None) or np.array_equal(bits(x), bits(y)) for x, y in zip(a, b))
+
+
+def test_shapes_reach_the_second_class_pass():
+    """the last of SHAPES: two passes over the classes in label_slice, the second with 44 live classes, in 5 to 37 slices"""
+    B, t, K = SHAPES[-1]
+    cuts = [label_slices(min(t * r, Tt), K) for r in (1, 8) for Tt in frame_totals(t, r) if Tt >= r]
+    assert all(c[3] == 2 for c in cuts) and K - 256 == 44 and (min(c[1] for c in cuts), max(c[1] for c in cuts)) == (5, 37)
+    assert all(label_slices(min(s[1] * r, Tt), s[2])[3] == 1 for s in SHAPES[:-1] for r in (1, 8) for Tt in frame_totals(s[1], r))
 
 
 # ---- the kernels against the formula ---------------------------------------------------------------------------------------------

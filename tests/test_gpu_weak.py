@@ -22,7 +22,10 @@ pytestmark = pytest.mark.gpu
 PKG = "soundeventdetection-pytorch_amd"
 GUARD = 1024
 FILL = {torch.float32: (float("nan"), -1024.0), torch.float64: (float("nan"), -4096.0)}
-SHAPES = [(2, 5, 3), (1, 1, 1), (3, 63, 1), (3, 64, 14), (2, 65, 17), (2, 257, 2), (1, 1025, 1), (4, 750, 14)]
+# the last two: many classes, where label_slice (the maxima of a strong target) takes several passes of 256 classes (MANY_CLASSES below)
+SHAPES = [(2, 5, 3), (1, 1, 1), (3, 63, 1), (3, 64, 14), (2, 65, 17), (2, 257, 2), (1, 1025, 1), (4, 750, 14), (2, 125, 527),
+          (1, 3, 8200)]
+MANY_CLASSES = (2, 125, 527)
 W = 5.0                     # recall factor
 
 
@@ -153,6 +156,40 @@ def frame_totals(t, ratio):
     return sorted({Tt for Tt in (t * ratio, t * ratio - 3, t * ratio + 5, ratio - 5) if Tt > 0})
 
 
+def label_slices(N, K):
+    """how sed_weak_bce_fwd_bwd_ex (and its twin sed_att_loss_fwd_bwd) cuts the first N frames of a strong target for label_slice,
+    from the documented constants: about 8192 target values per slice (WEAK_SLICE_VALUES), at most 64 slices per clip
+    (WEAK_MAX_SLICES), never more slices than frames, 256 classes per pass
+    -> (slices asked for before either limit, slices, frames per slice, passes over the classes)"""
+    asked = -(-N * K // 8192)
+    frames = -(-N // min(asked, 64, N))
+    return asked, -(-N // frames), frames, -(-K // 256)
+
+
+def events_reach_the_last_slice_and_pass(strong, N):
+    """a strong target of MANY_CLASSES: events in the frames of the last slice in every pass over the classes (the second and the
+    partial third among them), and in classes >= 256 in the first slice"""
+    _, slices, frames, passes = label_slices(N, strong.shape[2])
+    first, last = strong[:, :frames], strong[:, (slices - 1) * frames:N]
+    assert passes == 3 and last.shape[1] > 0
+    assert last[:, :, :256].any() and last[:, :, 256:512].any() and last[:, :, 512:].any() and first[:, :, 256:].any()
+
+
+def test_shapes_reach_the_label_slice_branches():
+    """(2, 125, 527) with ratio 8: N * K > 64 * 8192, so the slice count is capped at 64, and k0 takes three passes, the last with
+    15 live classes; with ratio 1: 9 slices.  (1, 3, 8200): more slices asked for than frames, so the count is clamped to N, and
+    33 passes, the last with 8 live classes.  SHAPES before them: K <= 17, at most 11 slices."""
+    B, t, K = MANY_CLASSES
+    assert MANY_CLASSES in SHAPES and (1, 3, 8200) in SHAPES
+    assert [label_slices(min(t * 8, Tt), K) for Tt in frame_totals(t, 8)] == \
+        [(1, 1, 3, 3), (65, 63, 16, 3), (65, 63, 16, 3), (65, 63, 16, 3)]
+    assert min(t * 8, frame_totals(t, 8)[1]) * K > 64 * 8192 and K - 2 * 256 == 15
+    assert [label_slices(min(t, Tt), K)[:2] for Tt in frame_totals(t, 1)] == [(8, 8), (9, 9), (9, 9)]
+    assert [label_slices(min(3 * r, Tt), 8200) for r in (1, 8) for Tt in frame_totals(3, r)] == \
+        [(4, 3, 1, 33), (4, 3, 1, 33), (4, 3, 1, 33), (22, 21, 1, 33), (25, 24, 1, 33), (25, 24, 1, 33)]
+    assert max(label_slices(min(s[1] * r, Tt), s[2])[0] for s in SHAPES[:-2] for r in (1, 8) for Tt in frame_totals(s[1], r)) == 11
+
+
 # ---- the kernels against the formula ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("ratio", [1, 8])
@@ -165,6 +202,8 @@ def test_weak_loss_against_formula(L, shape, ratio, mode):
     assert len(totals) == (4 if ratio == 8 else 3 if t > 3 else 2)
     for Tt in totals:
         clip_t, strong_t = targets(rng, B, K, Tt)
+        if shape == MANY_CLASSES:
+            events_reach_the_last_slice_and_pass(strong_t, min(t * ratio, Tt))
         for target in (clip_t, strong_t):
             tag = (shape, ratio, Tt, mode, target.ndim)
             ref = weak_vectorised(pre, target, ratio, Tt, mode, W, 0.75, 0.5)

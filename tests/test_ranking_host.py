@@ -124,6 +124,54 @@ def test_formula_against_sklearn(seed, n, levels):
     assert 2 * res["best_tp"] / (res["best_npred"] + P) == pytest.approx(f1.max(), rel=1e-12)
 
 
+# ---- the GPU tests' data at corpus size: would a 32-bit product be noticed? -------------------------------------------------------
+def walk_with_products_modulo(keys_sorted, bits):
+    """(auc2, best_tp, best_npred) of an ascending row of keys by curve_formula's walk, with every integer PRODUCT taken modulo
+    2^bits before it is added or compared -- bits = 32 is a kernel that lost a (u64) cast, bits = 64 the formula itself"""
+    mask = (1 << bits) - 1
+    k = np.asarray(keys_sorted, dtype=np.uint32)[::-1]
+    start = np.flatnonzero(np.r_[True, (k[1:] >> np.uint32(1)) != (k[:-1] >> np.uint32(1))])
+    size = np.diff(np.r_[start, k.size]).tolist()
+    tp = np.add.reduceat((k & np.uint32(1)).astype(np.int64), start).tolist()
+    P = sum(tp)
+    auc2, TP, seen, best = 0, 0, 0, (0, 0)
+    for tp_g, n_g in zip(tp, size):
+        auc2 += ((n_g - tp_g) * (2 * TP + tp_g)) & mask
+        TP += tp_g
+        seen += n_g
+        if best == (0, 0) or (TP * (best[1] + P)) & mask > (best[0] * (seen + P)) & mask:
+            best = (TP, seen)
+    return auc2, best[0], best[1]
+
+
+def test_the_largest_gpu_size_would_notice_a_32_bit_product():
+    """tests/test_gpu_ranking.py asserts that its reference rows pass 2^32 at CORPUS_SIZES[-1]; here the same rows go through the walk
+    with 32-bit products, and the counts the GPU tests compare exactly come out different -- while at the largest of SIZES they
+    come out the same, so the tests at those sizes could not tell.  Which rows tell: auc2 on every row with a group that holds
+    many negatives ('distinct' has fp_g <= 1, so its products stay small and only its 64-bit SUM is at stake); the best-F1 point on
+    'saturated' and 'f1 tie', whose candidates lie far apart -- on '8 levels' and 'distinct' the winner is next to 'predict
+    everything', both sides of a comparison wrap alike, and the walk's choice survives."""
+    gpu = importlib.import_module("test_gpu_ranking")
+    big, small = gpu.CORPUS_SIZES[-1], gpu.SIZES[-1]
+    keys, refs = gpu.corpus_case(big)
+    assert gpu.CURVE_ROWS[5:7] == ("saturated", "f1 tie") and gpu.CURVE_ROWS[2] == "distinct"
+    for row in range(len(refs)):
+        want = tuple(counts_row(refs[row])[2:5])
+        if refs[row]["P"]:
+            assert walk_with_products_modulo(keys[row], 64) == want, "the walk is the formula's"
+        lost = walk_with_products_modulo(keys[row], 32)
+        if row in (0, 1, 5, 6, 7):
+            assert lost[0] != want[0], (row, "auc2 survives 32-bit products")
+        if row in (5, 6):
+            assert lost[1:] != want[1:], (row, "the best-F1 point survives 32-bit products")
+        if row in (0, 1, 2, 5, 6, 7):
+            assert want[0] > 2 ** 32, (row, "auc2 survives a 32-bit sum")
+    keys, refs = gpu.curve_case(small)
+    for row in range(len(refs)):
+        if refs[row]["P"]:
+            assert walk_with_products_modulo(keys[row], 32) == tuple(counts_row(refs[row])[2:5]), (row, small)
+
+
 # ---- host arithmetic of the package ------------------------------------------------------------------------------------------------
 def test_metrics_from_rank_counts(ru):
     from scipy.stats import norm
