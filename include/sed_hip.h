@@ -1147,6 +1147,33 @@ int sed_ffn_act_bwd_drop(int act, const float* u, const float* da, float* a, flo
 int sed_dropout_mask(unsigned char* keep, int kind, size_t n0, int n1, int t, float p, const uint32_t* rng, uint32_t stream_id,
                      void* stream);
 
+/* ---- pre-LN residual LayerNorm of the self-attention head (csrc/sed_mhsa.hip) ---------------------------------------------------
+ * The residual add of one sub-layer and the LayerNorm in front of the next in one launch, row-major fp32, one wave per row:
+ *   forward   xsum = fma(a, s m sd, x)   (the product s * (m sd) is taken in fp32 first; m sd is sed_add_layernorm_fwd_drop's row
+ *             keep factor of stream stream_id, 1 for p = 0),   y = (xsum - mean) * rstd * gamma + beta,   stats [rows][2] = (mean, rstd),
+ *             NULL for inference (same y bits).  mean, then the centred sum of squares, in sed_add_layernorm_fwd's order: with s = 1
+ *             the bits of y and stats are that entry's (p = 0) or its _drop twin's (p > 0), and xsum is the IEEE fp32 sum.
+ *             a == NULL: y = LayerNorm(x) gamma + beta; xsum is not written and s, p, rng, stream_id are ignored.
+ *             xsum must not overlap x or a.
+ *   backward  g = dy gamma, xhat = (xsum - mean) rstd from the STORED xsum (neither x nor a is read again):
+ *             dxsum = dres_in + rstd (g - mean_c(g) - xhat mean_c(g xhat))    the gradient of the residual stream in front of the add
+ *             da    = s m sd dxsum                                            the gradient of the sub-layer output that was added
+ *             dres_in NULL: no gradient arrives on the stream (with s = 1 the bits of dxsum, dgamma, dbeta are
+ *             sed_add_layernorm_bwd's on (xsum, zeros)); dxsum may alias dres_in; da NULL: not written, and s, p, rng, stream_id are
+ *             ignored.  dgamma = sum_rows dy xhat, dbeta = sum_rows dy through 64-row partials in the workspace
+ *             (sed_resid_layernorm_bwd_ws_floats floats) and a fixed-order reduction.  No atomics: the same bits on every run.
+ * p = 0 is allowed with rng == NULL (one entry, no _drop twin).  Nothing outside the rows * C elements is read or written.
+ * Refused (non-zero, nothing launched, outputs untouched): sizes <= 0; a NULL x, gamma, beta, y (forward), dy, xsum, gamma, stats,
+ * dxsum, dgamma, dbeta, workspace (backward); rows > 65535 * 64 in the backward; and where a / da is given: a non-finite s, xsum NULL,
+ * p < 0, p >= 1 or NaN, p > 0 with rng NULL.                                                                                       */
+int    sed_resid_layernorm_fwd(const float* x, const float* a, float s, const float* gamma, const float* beta, float* xsum, float* y,
+                               float* stats, size_t rows, int C, float eps, float p, const uint32_t* rng, uint32_t stream_id,
+                               void* stream);
+size_t sed_resid_layernorm_bwd_ws_floats(size_t rows, int C);
+int    sed_resid_layernorm_bwd(const float* dy, const float* dres_in, const float* xsum, const float* gamma, const float* stats,
+                               float s, float* dxsum, float* da, float* dgamma, float* dbeta, float* workspace, size_t rows, int C,
+                               float p, const uint32_t* rng, uint32_t stream_id, void* stream);
+
 /* ---- local attention window of the self-attention head (the WIN instantiations in csrc/sed_mhsa.hip) ---------------------------
  * Two integers for every head: key j of the same clip takes part for query i iff i - left <= j <= i + right (torch: attn_mask
  * M[i][j] = True where j < i - left or j > i + right).  In sed_mhsa_fwd's definitions lse_i, p_ij and ctx_i run over the in-window

@@ -198,6 +198,11 @@ PROTOTYPES = {
     "sed_relpos_map_check": (_I, [_P, _I, _I]),
     "sed_relpos_expand": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "sed_relpos_fold": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    # the pre-LN pair: (x, a, s, gamma, beta, xsum, y, stats, rows, C, eps, p, rng, stream_id) and
+    # (dy, dres_in, xsum, gamma, stats, s, dxsum, da, dgamma, dbeta, workspace, rows, C, p, rng, stream_id)
+    "sed_resid_layernorm_fwd": (_I, [_P, _P, _F, _P, _P, _P, _P, _P, _Z, _I, _F, _F, _P, _U32, _P]),
+    "sed_resid_layernorm_bwd_ws_floats": (_Z, [_Z, _I]),
+    "sed_resid_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _Z, _I, _F, _P, _U32, _P]),
     "sed_dwconv_tile": (_I, []),
     "sed_dwconv_nparts": (_I, [_I, _I]),
     "sed_dwconv_glu_fwd_ws_floats": (_Z, [_I, _I, _I]),

@@ -1288,3 +1288,184 @@ extern "C" int sed_add_layernorm_bwd_drop(const float* dy, const float* x, const
     }
     return add_ln_bwd_launch<true>(dy, x, a, gamma, stats, dres, da, dgamma, dbeta, workspace, rows, C, d, stream);
 }
+
+// ---- pre-LN: the residual add of one sub-layer and the LayerNorm in front of the next, one launch each way -----------------------------
+// forward   xsum = fma(a, s m sd, x) (s m sd multiplied in fp32 first; m sd = 1 without dropout), y = LayerNorm(xsum) gamma + beta,
+//           stats = (mean, rstd); a == NULL: y = LayerNorm(x) and nothing else.  The sums, their order and the expressions are
+//           add_ln_fwd_kernel's: with s = 1 the bits of y and stats are that kernel's, plain or DROP.
+// backward  dxsum = dres_in + rstd (g - mean_c(g) - xhat mean_c(g xhat)), g = dy gamma, xhat from the STORED xsum (neither x nor a is
+//           read); da = s m sd dxsum.  A thread reads an element of dres_in before it writes the same element of dxsum: they may alias.
+//           dgamma / dbeta: partials over LN_ROWS_PER_WG rows from (dy, xsum, stats) and add_ln_bwd_reduce_kernel.
+namespace {
+template <typename Each>
+__device__ __forceinline__ void resid_ln_row(Each each, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                             float* __restrict__ yr, float* __restrict__ stats, size_t row, int C, float eps, int lane) {
+    float s = 0.f;
+    each([&](int c, float v) { s += v; });
+    const float mean = wave_sum(s) / (float)C;
+    float ss = 0.f;
+    each([&](int c, float v) { const float d = v - mean; ss = fmaf(d, d, ss); });
+    const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)C + eps);
+    each([&](int c, float v) { yr[c] = (v - mean) * rstd * gamma[c] + beta[c]; });
+    if (stats != nullptr && lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
+}
+
+template <bool HAS_A, bool DROP>
+__global__ __launch_bounds__(256) void resid_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a, float s,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float* __restrict__ xsum, float* __restrict__ y, float* __restrict__ stats,
+                                                           size_t rows, int C, float eps, DropArgs drop) {
+    const int lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* __restrict__ xr = x + row * C;
+    float* __restrict__ yr = y + row * C;
+    if (!HAS_A) {
+        resid_ln_row([&](auto f) { for (int c = lane; c < C; c += 64) f(c, xr[c]); }, gamma, beta, yr, stats, row, C, eps, lane);
+        return;
+    }
+    const float* __restrict__ ar = a + row * C;
+    float* __restrict__ sr = xsum + row * C;
+    if (DROP) {
+        const DropKey key(drop);
+        const LnMask mk(key, drop, row, C, lane);
+        auto each = [&](auto f) { mk.each(key, drop, row, C, lane, [&](int c, float ms) { f(c, fmaf(ar[c], s * ms, xr[c])); }); };
+        each([&](int c, float v) { sr[c] = v; });
+        resid_ln_row(each, gamma, beta, yr, stats, row, C, eps, lane);
+        return;
+    }
+    auto each = [&](auto f) { for (int c = lane; c < C; c += 64) f(c, fmaf(ar[c], s, xr[c])); };
+    each([&](int c, float v) { sr[c] = v; });
+    resid_ln_row(each, gamma, beta, yr, stats, row, C, eps, lane);
+}
+
+// dres_in and dxsum carry no __restrict__: they may be the same buffer
+template <bool HAS_RES, bool HAS_DA, bool DROP>
+__global__ __launch_bounds__(256) void resid_ln_bwd_row_kernel(const float* __restrict__ dy, const float* dres_in,
+                                                               const float* __restrict__ xsum, const float* __restrict__ gamma,
+                                                               const float* __restrict__ stats, float s, float* dxsum,
+                                                               float* __restrict__ da, size_t rows, int C, DropArgs drop) {
+    const int lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* __restrict__ xr = xsum + row * C;
+    const float* __restrict__ gr = dy + row * C;
+    const float mean = stats[2 * row], rstd = stats[2 * row + 1];
+    float s1 = 0.f, s2 = 0.f;
+    for (int c = lane; c < C; c += 64) {
+        const float g = gr[c] * gamma[c], xh = (xr[c] - mean) * rstd;
+        s1 += g;
+        s2 = fmaf(g, xh, s2);
+    }
+    const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+    auto out = [&](int c, float f) {
+        const float g = gr[c] * gamma[c], xh = (xr[c] - mean) * rstd;
+        // (the add of dres_in as an explicit fma: every instantiation rounds it the same way, whatever the compiler contracts)
+        const float in = (g - m1) - xh * m2;
+        const float d = HAS_RES ? fmaf(rstd, in, dres_in[row * C + c]) : rstd * in;
+        dxsum[row * C + c] = d;
+        if (HAS_DA) da[row * C + c] = d * f;
+    };
+    if (DROP) {
+        const DropKey key(drop);
+        const LnMask mk(key, drop, row, C, lane);
+        mk.each(key, drop, row, C, lane, [&](int c, float ms) { out(c, s * ms); });
+        return;
+    }
+    for (int c = lane; c < C; c += 64) out(c, s);
+}
+
+// add_ln_bwd_part_kernel's plain branch with xhat from the stored sum: the same partial layout, the same order
+__global__ __launch_bounds__(256) void resid_ln_bwd_part_kernel(const float* __restrict__ dy, const float* __restrict__ xsum,
+                                                                const float* __restrict__ stats, float* __restrict__ partial,
+                                                                size_t rows, int C) {
+    __shared__ float sh[2][4][64];
+    const int cl = threadIdx.x & 63, ry = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    const size_t r0 = (size_t)blockIdx.y * LN_ROWS_PER_WG;
+    const size_t r1 = r0 + LN_ROWS_PER_WG < rows ? r0 + LN_ROWS_PER_WG : rows;
+    float sg = 0.f, sb = 0.f;
+    if (c < C)
+        for (size_t row = r0 + ry; row < r1; row += 4) {
+            const float g = dy[row * C + c];
+            const float xh = (xsum[row * C + c] - stats[2 * row]) * stats[2 * row + 1];
+            sg = fmaf(g, xh, sg);
+            sb += g;
+        }
+    sh[0][ry][cl] = sg;
+    sh[1][ry][cl] = sb;
+    __syncthreads();
+    if (ry == 0 && c < C) {
+        partial[((size_t)blockIdx.y * 2 + 0) * C + c] = (sh[0][0][cl] + sh[0][1][cl]) + (sh[0][2][cl] + sh[0][3][cl]);
+        partial[((size_t)blockIdx.y * 2 + 1) * C + c] = (sh[1][0][cl] + sh[1][1][cl]) + (sh[1][2][cl] + sh[1][3][cl]);
+    }
+}
+
+// the scale and dropout arguments of an entry whose added tensor is present: s finite, p in [0, 1), rng required only for p > 0
+int resid_scale_args(float s, float p, const uint32_t* rng, uint32_t stream_id, DropArgs* d) {
+    SED_REQUIRE(isfinite(s), "the residual scale s must be finite");
+    if (int rc = drop_require_args(p, rng, stream_id, d)) return rc;
+    SED_REQUIRE(p == 0.f || rng != nullptr, "the dropout state rng is required for p > 0");
+    return 0;
+}
+}  // namespace
+
+extern "C" int sed_resid_layernorm_fwd(const float* x, const float* a, float s, const float* gamma, const float* beta, float* xsum,
+                                       float* y, float* stats, size_t rows, int C, float eps, float p, const uint32_t* rng,
+                                       uint32_t stream_id, void* stream) {
+    SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
+    SED_REQUIRE(x != nullptr && gamma != nullptr && beta != nullptr && y != nullptr, "x, gamma, beta and y are required");
+    SED_REQUIRE(cdivz(rows, 4) < ((size_t)1 << 31), "too many rows");
+    const unsigned grid = (unsigned)cdivz(rows, 4);
+    hipStream_t st = (hipStream_t)stream;
+    if (a == nullptr) {
+        resid_ln_fwd_kernel<false, false><<<grid, 256, 0, st>>>(x, nullptr, 1.f, gamma, beta, nullptr, y, stats, rows, C, eps, DropArgs{});
+    } else {
+        SED_REQUIRE(xsum != nullptr, "xsum is required with a");
+        DropArgs d;
+        if (int rc = resid_scale_args(s, p, rng, stream_id, &d)) return rc;
+        if (d.thr == 0)
+            resid_ln_fwd_kernel<true, false><<<grid, 256, 0, st>>>(x, a, s * d.scale, gamma, beta, xsum, y, stats, rows, C, eps, d);
+        else
+            resid_ln_fwd_kernel<true, true><<<grid, 256, 0, st>>>(x, a, s, gamma, beta, xsum, y, stats, rows, C, eps, d);
+    }
+    SED_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t sed_resid_layernorm_bwd_ws_floats(size_t rows, int C) { return sed_add_layernorm_bwd_ws_floats(rows, C); }
+
+extern "C" int sed_resid_layernorm_bwd(const float* dy, const float* dres_in, const float* xsum, const float* gamma, const float* stats,
+                                       float s, float* dxsum, float* da, float* dgamma, float* dbeta, float* workspace, size_t rows,
+                                       int C, float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
+    SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
+    SED_REQUIRE(dy != nullptr && xsum != nullptr && gamma != nullptr && stats != nullptr && dxsum != nullptr && dgamma != nullptr &&
+                dbeta != nullptr && workspace != nullptr, "every pointer but dres_in and da is required");
+    const size_t nchunks = cdivz(rows, LN_ROWS_PER_WG);
+    SED_REQUIRE(nchunks <= 65535, "too many rows (the partial grid takes 65535 * 64)");
+    DropArgs d{};
+    if (da != nullptr)
+        if (int rc = resid_scale_args(s, p, rng, stream_id, &d)) return rc;
+    const bool drop = da != nullptr && d.thr != 0;
+    const float f = da != nullptr && !drop ? s * d.scale : s;
+    const unsigned grid = (unsigned)cdivz(rows, 4);
+    hipStream_t st = (hipStream_t)stream;
+#define SED_RESID_BWD(RES, DA, DROP) \
+    resid_ln_bwd_row_kernel<RES, DA, DROP><<<grid, 256, 0, st>>>(dy, dres_in, xsum, gamma, stats, f, dxsum, da, rows, C, d)
+    if (dres_in != nullptr) {
+        if (drop) SED_RESID_BWD(true, true, true);
+        else if (da != nullptr) SED_RESID_BWD(true, true, false);
+        else SED_RESID_BWD(true, false, false);
+    } else {
+        if (drop) SED_RESID_BWD(false, true, true);
+        else if (da != nullptr) SED_RESID_BWD(false, true, false);
+        else SED_RESID_BWD(false, false, false);
+    }
+#undef SED_RESID_BWD
+    SED_LAUNCH_CHECK();
+    resid_ln_bwd_part_kernel<<<dim3((unsigned)cdiv(C, 64), (unsigned)nchunks), 256, 0, st>>>(dy, xsum, stats, workspace, rows, C);
+    SED_LAUNCH_CHECK();
+    add_ln_bwd_reduce_kernel<<<(unsigned)cdiv(C, 256), 256, 0, st>>>(workspace, dgamma, dbeta, (int)nchunks, C);
+    SED_LAUNCH_CHECK();
+    return 0;
+}

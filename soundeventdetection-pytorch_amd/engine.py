@@ -217,7 +217,8 @@ class CnnEngine(OptimizerExtMixin):
                  precision: str = "bf16", head: str = "fc", gru_hidden: int = 256, generic_first: bool = False,
                  mel_bins: Optional[int] = None, attention: bool = False, sa_heads: int = 4, pos_encoding: bool = True,
                  sa_layers: int = 1, sa_ffn: int = 0, sa_activation: str = "relu", sa_conv_kernel: int = 0,
-                 sa_dropout: float = 0.0, sa_dropout_seed: Optional[int] = None, sa_window=None, sa_rel_pos=None):
+                 sa_dropout: float = 0.0, sa_dropout_seed: Optional[int] = None, sa_window=None, sa_rel_pos=None,
+                 sa_norm_first: bool = False, sa_macaron: bool = False):
         """head: 'fc' (Cnn_AvgPooling: heads.FcHead), 'gru' (CRNN: heads.GruHead, gru_hidden units), 'sa' (Csa_AvgPooling: heads.SaHead;
         pos_encoding and the sa_* options are heads.SaConfig's fields, described and checked there, and belong to this head alone)
         or 'none' (a bare stack of ConvBlocks: forward() stops at the last pooled output plan.y[-1], backward() takes its gradient).
@@ -234,9 +235,10 @@ class CnnEngine(OptimizerExtMixin):
         if head == "gru" and (gru_hidden % 32 or not 32 <= gru_hidden <= 256):
             raise ValueError("gru_hidden must be a multiple of 32 in [32, 256]")
         self.head, self.Hd = head, int(gru_hidden)
-        sa = (sa_heads, pos_encoding, sa_layers, sa_ffn, sa_activation, sa_conv_kernel, sa_dropout, sa_dropout_seed, sa_window, sa_rel_pos)
+        sa = (sa_heads, pos_encoding, sa_layers, sa_ffn, sa_activation, sa_conv_kernel, sa_dropout, sa_dropout_seed, sa_window, sa_rel_pos,
+              sa_norm_first, sa_macaron)
         self.sa_config = SaConfig(int(list(model_config)[-1][0]), *sa) if head == "sa" else None
-        for kw, v in (self.sa_config.keywords() if head == "sa" else SaConfig.absent(*sa)).items():
+        for kw, v in (self.sa_config.keywords(every=True) if head == "sa" else SaConfig.absent(*sa)).items():
             setattr(self, kw, v)            # engine.sa_heads, engine.sa_dropout, ...: the checked options (the defaults without the head)
         self.attention = bool(attention)
         if self.attention and head == "none":

@@ -50,6 +50,12 @@ class SaConfig:
     rel_pos = None, an int L >= 1 (clipped distances, 2L + 1 buckets) or a pair (num_buckets, max_distance) (T5's bidirectional log
     buckets): a learned bias per head and bucket of the distance j - i on every score of every layer, P["rel_pos*.weight"]
     (H, num_buckets).  It composes with window and dropout.
+    norm_first: pre-LN layers -- every sub-layer is x <- x + f(LayerNorm(x)) on a residual stream (its norm attn_norm* / conv_norm* /
+    ffn_norm* in FRONT of it), and the last layer ends with a closing LayerNorm out_norm*, which event_fc reads:
+    torch.nn.TransformerEncoder(TransformerEncoderLayer(norm_first=True), N, norm=LayerNorm(C)).  One launch adds sub-layer j's
+    output and normalises for sub-layer j + 1 (sed_resid_layernorm_fwd / _bwd, csrc/sed_mhsa.hip).
+    macaron (needs norm_first and ffn > 0): the Conformer block -- a second FFN ffn_mac* behind ffn_mac_norm* in front of the
+    attention, both FFNs added with the weight 1/2, and a closing norm on EVERY layer.
     Every option at its default launches what the one-layer head always did."""
     channels: int
     heads: int = 4
@@ -62,6 +68,8 @@ class SaConfig:
     dropout_seed: Optional[int] = None
     window: object = None
     rel_pos: object = None
+    norm_first: bool = False
+    macaron: bool = False
 
     RELPOS_MAX_BUCKETS = 4096
 
@@ -88,15 +96,24 @@ class SaConfig:
             raise ValueError(f"sa_activation must be 'relu' or 'gelu', got {self.activation!r}")
         if not _integer(k) or (k != 0 and (k < 3 or k > 31 or k % 2 == 0)):
             raise ValueError(f"sa_conv_kernel must be 0 (no convolution module) or an odd integer in [3, 31], got {k!r}")
+        self.norm_first, self.macaron = bool(self.norm_first), bool(self.macaron)
+        if self.macaron and not self.norm_first:
+            raise ValueError("sa_macaron needs sa_norm_first: the macaron half-step FFNs belong to the pre-LN block")
+        if self.macaron and not D:
+            raise ValueError("sa_macaron needs a feed-forward sub-layer (sa_ffn > 0)")
 
     @staticmethod
     def keyword(name: str) -> str:
         """the keyword of CnnEngine / Csa_AvgPooling (and the attribute they keep) for the field `name`"""
         return name if name == "pos_encoding" else "sa_" + name
 
-    def keywords(self) -> dict:
-        """the options under the keywords of CnnEngine / Csa_AvgPooling, in their checked form"""
-        return {self.keyword(f.name): getattr(self, f.name) for f in fields(self)[1:]}
+    BLOCK_SWITCHES = ("norm_first", "macaron")
+
+    def keywords(self, every: bool = False) -> dict:
+        """the options under the keywords of CnnEngine / Csa_AvgPooling, in their checked form; the block switches norm_first and
+        macaron only where one is set (a post-LN configuration has the keywords it always had), or with every=True"""
+        skip = () if every or self.norm_first else self.BLOCK_SWITCHES
+        return {self.keyword(f.name): getattr(self, f.name) for f in fields(self)[1:] if f.name not in skip}
 
     @classmethod
     def absent(cls, *options) -> dict:
@@ -194,6 +211,58 @@ class SaConfig:
         """(convm, conv_norm) module names of encoder layer l's convolution module (between attn_norm* and ffn* of layer_names)"""
         sfx = "" if l == 0 else f"_l{l}"
         return "convm" + sfx, "conv_norm" + sfx
+
+    @staticmethod
+    def macaron_names(l):
+        """(ffn_mac, ffn_mac_norm) module names of encoder layer l's macaron FFN (norm_first + macaron: in front of attn_norm*)"""
+        sfx = "" if l == 0 else f"_l{l}"
+        return "ffn_mac" + sfx, "ffn_mac_norm" + sfx
+
+    @staticmethod
+    def out_name(l):
+        """module name of encoder layer l's closing LayerNorm (norm_first: every layer with macaron, else the last layer)"""
+        return "out_norm" if l == 0 else f"out_norm_l{l}"
+
+    def has_out_norm(self, l) -> bool:
+        """whether layer l ends with a closing LayerNorm"""
+        return self.norm_first and (self.macaron or l == self.layers - 1)
+
+    def sublayers(self, l):
+        """norm_first: layer l's sub-layers in forward order as (kind, module, norm module, residual weight, dropout site of the
+        output before its add); kind 'mac' / 'attn' / 'conv' / 'ffn'"""
+        an, nn_, fn, fnn = self.layer_names(l)
+        out = []
+        if self.macaron:
+            mn, mnn = self.macaron_names(l)
+            out.append(("mac", mn, mnn, 0.5, 6))
+        out.append(("attn", an, nn_, 1.0, 1))
+        if self.conv_kernel:
+            cm, cn = self.conv_names(l)
+            out.append(("conv", cm, cn, 1.0, 2))
+        if self.ffn:
+            out.append(("ffn", fn, fnn, 0.5 if self.macaron else 1.0, 4))
+        return out
+
+    def module_order(self):
+        """the head's parameter modules in registration order (event_fc / att_fc excluded): post-LN attn, rel_pos, attn_norm, convm,
+        conv_norm, ffn, ffn_norm per layer; norm_first ffn_mac_norm, ffn_mac, attn_norm, attn, rel_pos, conv_norm, convm, ffn_norm,
+        ffn, out_norm -- each norm before its sub-layer, because its gradient completes after the sub-layer's"""
+        names = []
+        for l in range(self.layers):
+            an, nn_, fn, fnn = self.layer_names(l)
+            rel = [self.rel_name(l)] if self.rel_pos is not None else []
+            if self.norm_first:
+                for kind, mod, norm, _, _ in self.sublayers(l):
+                    names += [norm, mod] + (rel if kind == "attn" else [])
+                if self.has_out_norm(l):
+                    names.append(self.out_name(l))
+            else:
+                names += [an] + rel + [nn_]
+                if self.conv_kernel:
+                    names += list(self.conv_names(l))
+                if self.ffn:
+                    names += [fn, fnn]
+        return names
 
     @staticmethod
     def rel_name(l):
@@ -381,7 +450,9 @@ class SaHead(_Head):
     options).  Per option, what replaces the default launches: dropout the _drop entries; a window sed_mhsa_fwd_win / sed_mhsa_bwd_win in
     the places of the plain / _drop core launches, no new buffers; rel_pos sed_relpos_expand + sed_mhsa_fwd_rel in the place of the
     core launch, sed_mhsa_bwd_rel + sed_relpos_fold into G["rel_pos*.weight"] in the backward -- the map, the per-layer distance tables
-    and the workspace belong to the plan."""
+    and the workspace belong to the plan.  cfg.norm_first: the pre-LN chain (_plan_chain, _forward_pre, _backward_pre) -- one
+    sed_resid_layernorm_fwd / _bwd per LayerNorm, each doing the previous sub-layer's residual add (forward) or adding its input gradient to
+    the running stream gradient in place (backward), around the same sub-layer launches; no torch add on that path."""
     tag = "sa"
 
     def __init__(self, eng, cfg: SaConfig):
@@ -437,19 +508,25 @@ class SaHead(_Head):
         for name, cols in (("m", C), ("fc_m", C), ("dh", C), ("dres", C), ("dctx", C), ("dqkv", 3 * C), ("dm", C)):
             g[name] = torch.empty((R, cols), **f32)
         g["layers"] = []
+        pre = c.norm_first
         for _ in range(c.layers):
-            ly = {name: torch.empty((R, cols), **f32) for name, cols in (("qkv", 3 * C), ("ctx", C), ("a", C), ("h", C), ("stats", 2))}
+            ly = {name: torch.empty((R, cols), **f32) for name, cols in (("qkv", 3 * C), ("ctx", C), ("a", C))
+                  + (() if pre else (("h", C), ("stats", 2)))}
             ly["lse"] = torch.empty((B, Hh, t), **f32)
             if D:
-                ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("u", D), ("f", C), ("h2", C), ("stats2", 2))})
+                ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("u", D), ("f", C)) + (() if pre else (("h2", C), ("stats2", 2)))})
+            if c.macaron:
+                ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("mu", D), ("mf", C))})
             if kc:
                 # the convolution module: the GLU's input and output, the depthwise output, the activation, the module's output, the
                 # residual LayerNorm's output and statistics, and the BatchNorm's per-channel vectors (Cp = C)
-                ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("cg", 2 * C), ("cv", C), ("cz", C), ("cs", C), ("co", C),
-                                                                                 ("hc", C), ("stats3", 2))})
+                ly.update({name: torch.empty((R, cols), **f32) for name, cols in (("cg", 2 * C), ("cv", C), ("cz", C), ("cs", C), ("co", C))
+                           + (() if pre else (("hc", C), ("stats3", 2)))})
                 ly.update({name: torch.empty(C, **f32) for name in ("cscale", "cshift", "cmean", "cinvstd")})
             g["layers"].append(ly)
-        g["h"] = self.layer_out(g["layers"][-1])          # what event_fc (and att_fc) read
+        if pre:
+            self._plan_chain(g, R, C, f32)
+        g["h"] = g["chain"][-1]["y"] if pre else self.layer_out(g["layers"][-1])          # what event_fc (and att_fc) read
         g["woT"] = torch.empty((C, C), **f32)
         g["winT"] = torch.empty((C, 3 * C), **f32)
         if D:
@@ -470,9 +547,11 @@ class SaHead(_Head):
             if self._drop_state is None:
                 self._drop_dev = dev
             _ = self.drop_state                      # made here, never inside a captured step
-            # the gradient of a sub-layer's output a (da = m s dres) and the state the plan's last training forward drew its masks from
-            # (what its backward regenerates them from)
+        if c.dropout or c.macaron:
+            # the gradient of a sub-layer's output a (da = s m sd dres: dropout, or a residual weight other than 1)
             g["da"] = torch.empty((R, C), **f32)
+        if c.dropout:
+            # the state the plan's last training forward drew its masks from (what its backward regenerates them from)
             g["rng"] = torch.zeros(4, dtype=torch.int32, device=dev)
         g["pe"] = None
         if c.pos_encoding:
@@ -491,7 +570,7 @@ class SaHead(_Head):
             for ly in g["layers"]:
                 ly["rel"], ly["drel"] = torch.empty((Hh, 2 * t - 1), **f32), torch.empty((Hh, 2 * t - 1), **f32)
             g["core_ws"] = torch.empty(max(1, lib.sed_mhsa_bwd_rel_ws_floats(B, t, Hh, C // Hh, *self._win_sides)), **f32)
-        g["ln_ws"] = torch.empty(max(1, lib.sed_add_layernorm_bwd_ws_floats(R, C)), **f32)
+        g["ln_ws"] = torch.empty(max(1, (lib.sed_resid_layernorm_bwd_ws_floats if pre else lib.sed_add_layernorm_bwd_ws_floats)(R, C)), **f32)
         # split-K of the weight-gradient products (K = R rows), as the recurrent head's tail: SED_GRU_KSPLIT, read with the plan
         g["ksplit"] = max(1, int(_os.environ.get("SED_GRU_KSPLIT", "64")))
         tn = [lib.sed_gemm_tn_ws_floats(3 * C, C, g["ksplit"])]
@@ -502,8 +581,44 @@ class SaHead(_Head):
         g["tn_ws"] = torch.empty(max(1, max(tn)), **f32)
 
     def layer_out(self, ly):
-        """the output of a layer, given its buffers: the next layer's input, or what event_fc reads"""
+        """the output of a layer, given its buffers: the next layer's input, or what event_fc reads (norm_first: the closing norm's
+        output, or the residual stream behind the layer's last add)"""
+        if self.cfg.norm_first:
+            return ly["out"]
         return ly["h2"] if self.cfg.ffn else ly["hc"] if self.cfg.conv_kernel else ly["h"]
+
+    def _plan_chain(self, g, R, C, f32):
+        """norm_first: the chain of LayerNorm launches, one node per launch in forward order.  A node normalises the residual stream
+        node["x"]: with node["add"] = (a, s, site, l) it first forms x = src + s m sd a in its own buffer (the previous sub-layer's add,
+        across a layer boundary where there is no closing norm), else x is src itself -- the mel-mean rows, or a closing norm's
+        output.  node["y"], node["stats"]: the LayerNorm's output (the sub-layer's input) and statistics; node["sub"] = (kind, module,
+        layer, buffers) of the sub-layer that reads y, None for a closing norm; node["new"]: x is a new stream (no gradient arrives
+        on it from later adds other than through this node)."""
+        c = self.cfg
+        chain, src, add = [], g["m"], None
+        new = lambda cols: torch.empty((R, cols), **f32)
+        def node(norm, sub):
+            nonlocal src, add
+            n = dict(norm=norm, src=src, add=add, x=new(C) if add is not None else src, y=new(C), stats=new(2), sub=sub)
+            chain.append(n)
+            src, add = n["x"], None
+            return n
+        for l, ly in enumerate(g["layers"]):
+            for kind, mod, norm, s, site in c.sublayers(l):
+                node(norm, (kind, mod, l, ly))
+                add = (ly[{"mac": "mf", "attn": "a", "conv": "co", "ffn": "f"}[kind]], s, site, l)
+            if c.has_out_norm(l):
+                n = node(c.out_name(l), None)
+                src = ly["out"] = n["y"]
+            else:
+                ly["out"] = None                       # (the stream behind the layer: the next node's x, set below)
+        for i, n in enumerate(chain):
+            if n["sub"] is not None and n["sub"][0] == ("mac" if c.macaron else "attn") and n["sub"][2] > 0:
+                prev = g["layers"][n["sub"][2] - 1]
+                if prev["out"] is None:
+                    prev["out"] = n["x"]
+        g["chain"] = chain
+        g["dn"], g["ds"] = new(C), [new(C), new(C)]     # the gradient of a node's y; the stream gradient (two: a closing norm's dy and dx)
 
     def _add_ln_fwd(self, g, x, a, gamma, beta, y, stats, R, C, sid):
         """y = LayerNorm(x + a); sid: the dropout stream of a, None = no dropout (the plain launch)"""
@@ -568,10 +683,19 @@ class SaHead(_Head):
     def _conv_forward(self, p, P, l, ly, keep, training, update_running_stats):
         """The convolution module of layer l behind attn_norm: ly["h"] -> ly["hc"].  keep: keep what a backward reads;
         training: batch statistics (and the running update) instead of the running statistics."""
+        g, C, R = p.sa, self.eng.cfg[-1][0], p.sa["R"]
+        cn = self.cfg.conv_names(l)[1]
+        self._conv_inner_forward(p, P, l, ly, ly["h"], keep, training, update_running_stats)
+        self._add_ln_fwd(g, ly["h"], ly["co"], P[cn + ".weight"], P[cn + ".bias"], ly["hc"], ly["stats3"] if keep else None, R, C,
+                         8 * l + 2 if training and self.cfg.dropout else None)
+
+    def _conv_inner_forward(self, p, P, l, ly, xin, keep, training, update_running_stats):
+        """The inner convolution module of layer l between given buffers: xin -> ly["co"] (pointwise conv, GLU + depthwise conv,
+        BatchNorm, SiLU, pointwise conv)."""
         eng, lib, dt, st, g, kc = self.eng, self.eng.lib, self.eng.dt, _stream(), p.sa, self.cfg.conv_kernel
         B, t, C, R = p.B, p.t_out, eng.cfg[-1][0], p.sa["R"]
         cm, cn = self.cfg.conv_names(l)
-        eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["h"]), C, L.ptr(P[cm + ".pointwise1.weight"]), C,
+        eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(xin), C, L.ptr(P[cm + ".pointwise1.weight"]), C,
                L.ptr(P[cm + ".pointwise1.bias"]), L.ptr(ly["cg"]), 2 * C, R, 2 * C, C, 1, None, st)
         eng._k("sed_dwconv_glu_fwd", lib.sed_dwconv_glu_fwd, L.ptr(ly["cg"]), L.ptr(P[cm + ".depthwise.weight"]),
                L.ptr(P[cm + ".depthwise.bias"]), L.ptr(ly["cz"]), L.ptr(ly["cv"]) if keep else None,
@@ -589,18 +713,26 @@ class SaHead(_Head):
         eng._k("sed_bn_silu_fwd", lib.sed_bn_silu_fwd, L.ptr(ly["cz"]), L.ptr(ly["cscale"]), L.ptr(ly["cshift"]), L.ptr(ly["cs"]), R, C, st)
         eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["cs"]), C, L.ptr(P[cm + ".pointwise2.weight"]), C,
                L.ptr(P[cm + ".pointwise2.bias"]), L.ptr(ly["co"]), C, R, C, C, 1, None, st)
-        self._add_ln_fwd(g, ly["h"], ly["co"], P[cn + ".weight"], P[cn + ".bias"], ly["hc"], ly["stats3"] if keep else None, R, C,
-                         8 * l + 2 if training and self.cfg.dropout else None)
 
     def _conv_backward(self, p, P, G, l, ly, gcur, eval_bwd, ks, ws, done):
         """Backward of layer l's convolution module: gcur = the gradient of ly["hc"]; returns the gradient of ly["h"] (g["dhc"])."""
         eng, lib, st, g, kc = self.eng, self.eng.lib, _stream(), p.sa, self.cfg.conv_kernel
         B, t, C, R = p.B, p.t_out, eng.cfg[-1][0], p.sa["R"]
         cm, cn = self.cfg.conv_names(l)
-        w1, w2 = cm + ".pointwise1.weight", cm + ".pointwise2.weight"
         ga = self._add_ln_bwd(g, gcur, ly["h"], ly["co"], P[cn + ".weight"], ly["stats3"], G[cn + ".weight"], G[cn + ".bias"], R, C,
                               8 * l + 2 if p.trained and self.cfg.dropout else None)
         done(cn)
+        self._conv_inner_backward(p, P, G, l, ly, ga, ly["h"], g["dhc"], eval_bwd, ks, ws, done)
+        g["dhc"].add_(g["dres"])
+        return g["dhc"]
+
+    def _conv_inner_backward(self, p, P, G, l, ly, ga, xin, dxin, eval_bwd, ks, ws, done):
+        """Backward of layer l's inner convolution module: ga = the gradient of ly["co"], xin the module's input -> its parameters'
+        gradients and dxin, the gradient of xin through the module (no residual)."""
+        eng, lib, st, g, kc = self.eng, self.eng.lib, _stream(), p.sa, self.cfg.conv_kernel
+        B, t, C, R = p.B, p.t_out, eng.cfg[-1][0], p.sa["R"]
+        cm, cn = self.cfg.conv_names(l)
+        w1, w2 = cm + ".pointwise1.weight", cm + ".pointwise2.weight"
         # ds = ga . pointwise2.weight;  d pointwise2.weight = ga^T . s, its bias gradient the column sums of ga (ga = dres, or m s dres
         # under dropout: the gradient of the module's output)
         self._lin_dx(ga, P[w2], g["cw2T"], g["cds"], R, C, C)
@@ -625,11 +757,9 @@ class SaHead(_Head):
                L.ptr(ly["cv"]), L.ptr(ly["cg"]), L.ptr(P[cm + ".depthwise.weight"]), L.ptr(g["cdg"]), L.ptr(G[cm + ".depthwise.weight"]),
                L.ptr(G[cm + ".depthwise.bias"]), L.ptr(g["cw_ws"]), B, t, C, kc, st)
         # d pointwise1.weight = dg^T . h, its bias gradient the column sums of dg;  dh = dg . pointwise1.weight + dres (the residual)
-        self._lin_dw(g["cdg"], ly["h"], G[w1], G[cm + ".pointwise1.bias"], R, 2 * C, C, t, ks, ws)
+        self._lin_dw(g["cdg"], xin, G[w1], G[cm + ".pointwise1.bias"], R, 2 * C, C, t, ks, ws)
         done(cm)
-        self._lin_dx(g["cdg"], P[w1], g["cw1T"], g["dhc"], R, 2 * C, C)
-        g["dhc"].add_(g["dres"])
-        return g["dhc"]
+        self._lin_dx(g["cdg"], P[w1], g["cw1T"], dxin, R, 2 * C, C)
 
     def _forward(self, p, P, feat, keep, training, update_running_stats):
         c, eng, lib, dt, st, g = self.cfg, self.eng, self.eng.lib, self.eng.dt, _stream(), p.sa
@@ -643,6 +773,8 @@ class SaHead(_Head):
         eng._k("sed_mel_mean_fwd", lib.sed_mel_mean_fwd, dt, L.ptr(feat), L.ptr(g["m"]), R, p.w_out, C, pad32(C), st)
         if g["pe"] is not None:
             g["m"].view(B, t, C).add_(g["pe"])          # x' = x + pe[frame], in place: the residual and the projections read x'
+        if c.norm_first:
+            return self._forward_pre(p, P, keep, training, update_running_stats, drop)
         xin = g["m"]
         for l, ly in enumerate(g["layers"]):
             an, nn_, fn, fnn = c.layer_names(l)
@@ -683,6 +815,8 @@ class SaHead(_Head):
         ws = L.ptr(g["tn_ws"]) if ks > 1 else None
         gcur = g["dh"]                                   # the gradient of the current layer's output
         drop = c.dropout if p.trained else 0.0           # the masks of the forward this backward belongs to (g["rng"])
+        if c.norm_first:
+            return self._backward_pre(p, P, G, dfeat, done, drop, ks, ws)
         for l in reversed(range(c.layers)):
             ly = g["layers"][l]
             xin = g["m"] if l == 0 else self.layer_out(g["layers"][l - 1])
@@ -735,3 +869,105 @@ class SaHead(_Head):
             gcur = g["dm"]
         # back through the mel mean
         eng._k("sed_mel_mean_bwd", lib.sed_mel_mean_bwd, eng.dt, L.ptr(g["dm"]), L.ptr(dfeat), R, p.w_out, C, pad32(C), st)
+
+    # ---- norm_first: the pre-LN chain (plan: _plan_chain) ------------------------------------------------------------------------------
+    def _ffn_fwd(self, g, P, fn, x, f, u, keep, drop, sid, R, C, D):
+        """f = ffn(x) of module fn; u for a backward (and wherever the hidden mask is drawn); sid: the hidden activation's stream"""
+        eng, lib = self.eng, self.eng.lib
+        sfx, opts = ("_drop", (drop, L.ptr(g["rng"]), sid)) if drop else ("", ())
+        eng._k("sed_ffn_fwd" + sfx, getattr(lib, "sed_ffn_fwd" + sfx), eng.dt, self.act, L.ptr(x), L.ptr(P[fn + ".linear1.weight"]),
+               L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(f),
+               L.ptr(u) if keep or drop else None, R, C, D, *opts, _stream())
+
+    def _forward_pre(self, p, P, keep, training, update_running_stats, drop):
+        c, eng, lib, dt, st, g = self.cfg, self.eng, self.eng.lib, self.eng.dt, _stream(), p.sa
+        Hh, D, t, C, R = c.heads, c.ffn, p.t_out, self.eng.cfg[-1][0], p.sa["R"]
+        rng = L.ptr(g["rng"]) if drop else None
+        for n in g["chain"]:
+            # the previous sub-layer's add (where there is one) and this node's LayerNorm
+            a, s, site, la = n["add"] if n["add"] is not None else (None, 1.0, 0, 0)
+            eng._k("sed_resid_layernorm_fwd", lib.sed_resid_layernorm_fwd, L.ptr(n["src"]), L.ptr(a), s, L.ptr(P[n["norm"] + ".weight"]),
+                   L.ptr(P[n["norm"] + ".bias"]), L.ptr(n["x"]) if a is not None else None, L.ptr(n["y"]),
+                   L.ptr(n["stats"]) if keep else None, R, C, LN_EPS, drop if a is not None else 0.0, rng, 8 * la + site, st)
+            if n["sub"] is None:
+                continue
+            kind, mod, l, ly = n["sub"]
+            if kind == "attn":
+                eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(n["y"]), C, L.ptr(P[mod + ".in_proj_weight"]), C,
+                       L.ptr(P[mod + ".in_proj_bias"]), L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
+                if c.rel_pos is not None:
+                    eng._k("sed_relpos_expand", lib.sed_relpos_expand, L.ptr(P[c.rel_name(l) + ".weight"]), L.ptr(g["rel_map"]),
+                           L.ptr(ly["rel"]), Hh, c.rel_pos_buckets(c.rel_pos), t, st)
+                self._mhsa_fwd(g, ly, l, keep, drop)
+                eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["ctx"]), C, L.ptr(P[mod + ".out_proj.weight"]), C,
+                       L.ptr(P[mod + ".out_proj.bias"]), L.ptr(ly["a"]), C, R, C, C, 1, None, st)
+            elif kind == "conv":
+                self._conv_inner_forward(p, P, l, ly, n["y"], keep, training, update_running_stats)
+            elif kind == "ffn":
+                self._ffn_fwd(g, P, mod, n["y"], ly["f"], ly["u"], keep, drop, 8 * l + 3, R, C, D)
+            else:
+                self._ffn_fwd(g, P, mod, n["y"], ly["mf"], ly["mu"], keep, drop, 8 * l + 5, R, C, D)
+        if drop:
+            self.drop_state[2:3].add_(1)                     # the next training forward draws new masks (captured with the step)
+        return g["h"]
+
+    def _backward_pre(self, p, P, G, dfeat, done, drop, ks, ws):
+        """The chain in reverse.  gs: the running gradient of the residual stream (None while nothing has arrived on the current
+        stream); gy: the gradient of the current node's LayerNorm output.  A node's launch adds its LayerNorm's input gradient to gs
+        in place (dxsum aliases dres_in) and leaves the gradient of the sub-layer output that was added in front of it (ga)."""
+        c, eng, lib, st, g = self.cfg, self.eng, self.eng.lib, _stream(), p.sa
+        Hh, D, t, C, R = c.heads, c.ffn, p.t_out, self.eng.cfg[-1][0], p.sa["R"]
+        rng = L.ptr(g["rng"]) if drop else None
+        gy, gs, flip = g["dh"], None, 0
+        for n in reversed(g["chain"]):
+            if n["sub"] is not None:
+                # the sub-layer behind this node: ga (the gradient of its output) -> its parameters' gradients and gy = g["dn"]
+                kind, mod, l, ly = n["sub"]
+                if kind == "attn":
+                    self._lin_dw(ga, ly["ctx"], G[mod + ".out_proj.weight"], G[mod + ".out_proj.bias"], R, C, C, t, ks, ws)
+                    self._lin_dx(ga, P[mod + ".out_proj.weight"], g["woT"], g["dctx"], R, C, C)
+                    self._mhsa_bwd(g, ly, l, drop)
+                    if c.rel_pos is not None:
+                        rn = c.rel_name(l)
+                        eng._k("sed_relpos_fold", lib.sed_relpos_fold, L.ptr(ly["drel"]), L.ptr(g["rel_map"]), L.ptr(G[rn + ".weight"]), Hh,
+                               c.rel_pos_buckets(c.rel_pos), t, st)
+                        done(rn)
+                    self._lin_dw(g["dqkv"], n["y"], G[mod + ".in_proj_weight"], G[mod + ".in_proj_bias"], R, 3 * C, C, t, ks, ws)
+                    done(mod)
+                    self._lin_dx(g["dqkv"], P[mod + ".in_proj_weight"], g["winT"], g["dn"], R, 3 * C, C)
+                elif kind == "conv":
+                    self._conv_inner_backward(p, P, G, l, ly, ga, n["y"], g["dn"], not p.trained, ks, ws, done)
+                else:
+                    u, hid = (ly["u"], 8 * l + 3) if kind == "ffn" else (ly["mu"], 8 * l + 5)
+                    w1, w2 = mod + ".linear1.weight", mod + ".linear2.weight"
+                    self._lin_dx(ga, P[w2], g["w2T"], g["fda"], R, C, D)
+                    if drop:
+                        eng._k("sed_ffn_act_bwd_drop", lib.sed_ffn_act_bwd_drop, self.act, L.ptr(u), L.ptr(g["fda"]), L.ptr(g["ffa"]),
+                               L.ptr(g["fda"]), R, D, drop, rng, hid, st)
+                    else:
+                        eng._k("sed_ffn_act_bwd", lib.sed_ffn_act_bwd, self.act, L.ptr(u), L.ptr(g["fda"]), L.ptr(g["ffa"]),
+                               L.ptr(g["fda"]), R * D, st)
+                    self._lin_dw(ga, g["ffa"], G[w2], G[mod + ".linear2.bias"], R, C, D, t, ks, ws)
+                    self._lin_dw(g["fda"], n["y"], G[w1], G[mod + ".linear1.bias"], R, D, C, t, ks, ws)
+                    done(mod)
+                    self._lin_dx(g["fda"], P[w1], g["w1T"], g["dn"], R, D, C)
+                gy = g["dn"]
+            else:
+                # a closing norm: its output is a new stream, whose gradient is what has arrived on it (the head's for the last one)
+                gy, gs = (gs if gs is not None else gy), None
+            if gs is None:
+                flip ^= 1
+                dx = g["ds"][flip]                      # (never the buffer gy may be)
+            else:
+                dx = gs
+            a, s, site, la = n["add"] if n["add"] is not None else (None, 1.0, 0, 0)
+            # the gradient of a is dx itself where s m sd = 1
+            da = g["da"] if a is not None and (drop or s != 1.0) else None
+            eng._k("sed_resid_layernorm_bwd", lib.sed_resid_layernorm_bwd, L.ptr(gy), L.ptr(gs), L.ptr(n["x"]), L.ptr(P[n["norm"] + ".weight"]),
+                   L.ptr(n["stats"]), s, L.ptr(dx), L.ptr(da), L.ptr(G[n["norm"] + ".weight"]), L.ptr(G[n["norm"] + ".bias"]),
+                   L.ptr(g["ln_ws"]), R, C, drop if da is not None else 0.0, rng, 8 * la + site, st)
+            done(n["norm"])
+            gs = dx
+            ga = da if da is not None else dx
+        # back through the mel mean
+        eng._k("sed_mel_mean_bwd", lib.sed_mel_mean_bwd, eng.dt, L.ptr(gs), L.ptr(dfeat), R, p.w_out, C, pad32(C), st)

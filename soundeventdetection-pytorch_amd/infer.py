@@ -141,11 +141,13 @@ def infer_file(audio_file, ckpt, device="cuda:0", mean_std="", threshold=0.5, pr
         from .models.spectogram_models import Csa_AvgPooling
         heads, pos = Csa_AvgPooling.config_from_state_dict(weights)
         layers, ffn, act = Csa_AvgPooling.encoder_config_from_state_dict(weights)      # (1, 0, relu) for a one-layer checkpoint
+        norm_first, macaron = Csa_AvgPooling.block_config_from_state_dict(weights)     # (False, False: no block_config)
         model = Csa_AvgPooling(cfg.classes_num, model_config=model_config, sa_heads=heads, pos_encoding=pos, mel_bins=n_mel,
                                frontend=frontend, attention=attention, sa_layers=layers, sa_ffn=ffn, sa_activation=act,
                                sa_conv_kernel=Csa_AvgPooling.conv_config_from_state_dict(weights),      # (0: no conv_config)
                                sa_window=Csa_AvgPooling.window_config_from_state_dict(weights),          # (None: no window_config)
-                               sa_rel_pos=Csa_AvgPooling.rel_pos_config_from_state_dict(weights)).to(dev)  # (None: no rel_pos_config)
+                               sa_rel_pos=Csa_AvgPooling.rel_pos_config_from_state_dict(weights),
+                               sa_norm_first=norm_first, sa_macaron=macaron).to(dev)  # (None: no rel_pos_config)
     else:
         model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend,
                                attention=attention).to(dev)

@@ -141,6 +141,12 @@ def build_weak_parser():
                    help="--self_attention: learned relative-position bias per layer, head and bucket of the distance between two frames -- "
                         "L: distances clipped to [-L, L] (2L + 1 buckets); NB:MAXD: T5's bidirectional log buckets (NB even >= 4, "
                         "MAXD > NB / 4); usually with --no_pos_encoding; default: none")
+    p.add_argument("--sa_norm_first", action="store_true", default=False,
+                   help="--self_attention: pre-LN encoder layers (every LayerNorm in front of its sub-layer, a closing LayerNorm behind "
+                        "the last layer): trains without a learning-rate warm-up at depth")
+    p.add_argument("--sa_macaron", action="store_true", default=False,
+                   help="--sa_norm_first with --sa_ffn: the Conformer block -- a second, half-weighted feed-forward sub-layer in front of "
+                        "the attention and a closing LayerNorm on every layer")
     return p
 
 
@@ -406,7 +412,8 @@ def get_spectogram_dataset_model_and_criterion(args, device):
                                sa_conv_kernel=int(getattr(args, "sa_conv_kernel", 0)),
                                sa_dropout=float(getattr(args, "sa_dropout", 0.0)), sa_dropout_seed=getattr(args, "sa_dropout_seed", None),
                                sa_window=parse_sa_window(getattr(args, "sa_window", None)),
-                               sa_rel_pos=parse_sa_rel_pos(getattr(args, "sa_rel_pos", None)))
+                               sa_rel_pos=parse_sa_rel_pos(getattr(args, "sa_rel_pos", None)),
+                               sa_norm_first=bool(getattr(args, "sa_norm_first", False)), sa_macaron=bool(getattr(args, "sa_macaron", False)))
     else:
         model = Cnn_AvgPooling(cfg.classes_num, model_config=model_config, mel_bins=n_mel, frontend=frontend, attention=att)
     model.set_precision(args.precision)
@@ -489,10 +496,12 @@ def validate_args(args):
         from .heads import SaConfig
         SaConfig(128, getattr(args, "sa_heads", 4), True, getattr(args, "sa_layers", 1), getattr(args, "sa_ffn", 0),
                  getattr(args, "sa_activation", "relu"), getattr(args, "sa_conv_kernel", 0), getattr(args, "sa_dropout", 0.0), None,
-                 parse_sa_window(getattr(args, "sa_window", None)), parse_sa_rel_pos(getattr(args, "sa_rel_pos", None)))
+                 parse_sa_window(getattr(args, "sa_window", None)), parse_sa_rel_pos(getattr(args, "sa_rel_pos", None)),
+                 bool(getattr(args, "sa_norm_first", False)), bool(getattr(args, "sa_macaron", False)))
     else:
         for name, default in (("sa_heads", 4), ("no_pos_encoding", False), ("sa_layers", 1), ("sa_ffn", 0), ("sa_activation", "relu"),
-                              ("sa_conv_kernel", 0), ("sa_dropout", 0.0), ("sa_dropout_seed", None), ("sa_window", None), ("sa_rel_pos", None)):
+                              ("sa_conv_kernel", 0), ("sa_dropout", 0.0), ("sa_dropout_seed", None), ("sa_window", None), ("sa_rel_pos", None),
+                              ("sa_norm_first", False), ("sa_macaron", False)):
             if getattr(args, name, default) != default:
                 raise ValueError(f"--{name} configures the self-attention head: it needs --self_attention")
     for flag, value in (("--weak_pooling", weak_options(args).get("weak_pooling")), ("--eval_clip_pooling", getattr(args, "eval_clip_pooling", None))):

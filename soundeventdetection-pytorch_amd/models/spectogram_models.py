@@ -531,6 +531,28 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     (rel_pos_config_from_state_dict returns None without it); encoder_layer_state still returns TransformerEncoderLayer's keys only.
     pos_encoding is an independent switch (the expected use is pos_encoding=False with sa_rel_pos).  With sa_rel_pos = None the
     draws, the state_dict keys, the launches and the output bits are those of a model without the argument.
+    sa_norm_first = True makes every layer pre-LN: on the residual stream x [R][C] (the positional table added once before layer 0),
+    layer l is
+        [sa_macaron]      x <- x + 1/2 FFNm(LN(x))      ffn_mac_norm*, ffn_mac*
+                          x <- x + MHSA(LN(x))          attn_norm*, attn*, [rel_pos*]
+        [sa_conv_kernel]  x <- x + ConvModule(LN(x))    conv_norm*, convm*      (the module's inner arithmetic as above)
+        [sa_ffn]          x <- x + s FFN(LN(x))         ffn_norm*, ffn*;  s = 1/2 with sa_macaron, else 1
+        [closing norm]    x <- LN(x)                    out_norm*
+    The closing norm exists on every layer with sa_macaron (the Conformer block of Gulati et al. 2020: two half-weighted FFNs around
+    attention and convolution) and on the last layer only without it, which is torch.nn.TransformerEncoder(TransformerEncoderLayer(C,
+    sa_heads, D, norm_first=True), N, norm=LayerNorm(C)); event_fc / att_fc read the last closing norm's output.  One launch forms a
+    sub-layer's residual add and the next LayerNorm (sed_resid_layernorm_fwd / _bwd, csrc/sed_mhsa.hip); the attention core, the
+    convolution module's inner arithmetic and the FFN kernel are the post-LN ones.  Names: layer 0 bare, layer l >= 1 with _l{l}.
+    Registration order per layer: ffn_mac_norm, ffn_mac, attn_norm, attn, rel_pos, conv_norm, convm, ffn_norm, ffn, out_norm -- each
+    norm before its sub-layer, because its gradient completes after the sub-layer's; the backward completes the groups in exactly the
+    reverse order.  Draw order per layer: the macaron FFN (linear1.weight, linear1.bias, linear2.weight, linear2.bias), the attention,
+    the convolution module, the FFN; the LayerNorms draw nothing.  Dropout sites (stream 8 l + site): 0 - 4 as above, 5 the macaron
+    FFN's hidden activation, 6 the macaron FFN's output before its add.  A float64 buffer block_config = (norm_first, macaron) exists
+    only with sa_norm_first (block_config_from_state_dict); encoder_layer_state keeps returning TransformerEncoderLayer's keys
+    (norm1 = attn_norm, norm2 = ffn_norm), closing_norm_state(state_dict, l) returns the closing norm's entries and
+    macaron_ffn_state(state_dict, l) the macaron FFN's.  With both False the draws, the state_dict keys, the launches and the output
+    bits are those of a model without the arguments.  Refused before any draw: sa_macaron without sa_norm_first, sa_macaron with
+    sa_ffn = 0.
     Refused: sa_rel_pos a non-integer or L < 1, num_buckets odd or < 4, max_distance <= num_buckets / 4, more than 4096 buckets,
     a negative or non-integer sa_window side, sa_dropout outside [0, 1), C % sa_heads != 0, a head width other than 32 or 64, C % 4 != 0, sa_layers < 1, sa_ffn not 0 or a multiple of 32 up to
     4096 (and C > 512 with it), an activation other than relu / gelu, sa_conv_kernel even, below 3 or above 31 (before any draw)."""
@@ -539,15 +561,17 @@ class Csa_AvgPooling(Cnn_AvgPooling):
 
     def __init__(self, classes_num, model_config=DEFAULT_CHANNEL_AND_POOL, precision=None, sa_heads=4, pos_encoding=True,
                  mel_bins=None, frontend=None, attention=False, sa_layers=1, sa_ffn=0, sa_activation="relu", sa_conv_kernel=0,
-                 sa_dropout=0.0, sa_dropout_seed=None, sa_window=None, sa_rel_pos=None):
+                 sa_dropout=0.0, sa_dropout_seed=None, sa_window=None, sa_rel_pos=None, sa_norm_first=False, sa_macaron=False):
         self.sa_config = SaConfig(int(model_config[-1][0]), sa_heads, pos_encoding, sa_layers, sa_ffn, sa_activation, sa_conv_kernel,
-                                  sa_dropout, sa_dropout_seed, sa_window, sa_rel_pos)          # (checked before any draw)
-        for kw, v in self.sa_config.keywords().items():
+                                  sa_dropout, sa_dropout_seed, sa_window, sa_rel_pos, sa_norm_first, sa_macaron)   # (checked before any draw)
+        for kw, v in self.sa_config.keywords(every=True).items():
             setattr(self, kw, v)            # model.sa_heads, model.sa_dropout, ...: the checked options
         super().__init__(classes_num, model_config, precision, mel_bins=mel_bins, frontend=frontend, attention=attention)
 
     def _build_head(self, c_last, classes_num):
-        for l in range(self.sa_layers):
+        if self.sa_norm_first:
+            self._build_pre_ln_layers(c_last)
+        for l in range(0 if self.sa_norm_first else self.sa_layers):
             an, nn_, fn, fnn = CnnEngine.sa_layer_names(l)
             setattr(self, an, _MhaParams(c_last, self.sa_heads))
             if self.sa_rel_pos is not None:
@@ -573,7 +597,55 @@ class Csa_AvgPooling(Cnn_AvgPooling):
             mode = self.sa_rel_pos[0] == "log"
             self.register_buffer("rel_pos_config", torch.tensor([float(mode), float(self.sa_rel_pos[1]),
                                                                  float(self.sa_rel_pos[2]) if mode else 0.0], dtype=torch.float64))
+        if self.sa_norm_first:
+            self.register_buffer("block_config", torch.tensor([float(self.sa_norm_first), float(self.sa_macaron)], dtype=torch.float64))
         self.event_fc = _LinearParams(c_last, classes_num)
+
+    def _build_pre_ln_layers(self, c_last):
+        """sa_norm_first: per layer, every norm BEFORE its sub-layer (SaConfig.module_order); the draws in sub-layer order"""
+        cfg = self.sa_config
+        for l in range(self.sa_layers):
+            for kind, mod, norm, _, _ in cfg.sublayers(l):
+                setattr(self, norm, _LayerNormParams(c_last))
+                if kind == "attn":
+                    setattr(self, mod, _MhaParams(c_last, self.sa_heads))
+                    if self.sa_rel_pos is not None:
+                        setattr(self, CnnEngine.sa_rel_name(l), _RelPosParams(self.sa_heads, CnnEngine.rel_pos_buckets(self.sa_rel_pos)))
+                    if l == 0:
+                        self.register_buffer("attn_config", torch.tensor([float(self.sa_heads), float(self.pos_encoding)], dtype=torch.float64))
+                elif kind == "conv":
+                    setattr(self, mod, _ConvModuleParams(c_last, self.sa_conv_kernel))
+                else:
+                    setattr(self, mod, _FfnParams(c_last, self.sa_ffn))
+            if cfg.has_out_norm(l):
+                setattr(self, cfg.out_name(l), _LayerNormParams(c_last))
+
+    @staticmethod
+    def block_config_from_state_dict(weights):
+        """(sa_norm_first, sa_macaron) from a state_dict's block_config; (False, False) when the buffer is absent"""
+        if "block_config" not in weights:
+            return False, False
+        cfg = weights["block_config"].detach().cpu().double().tolist()
+        return bool(round(cfg[0])), bool(round(cfg[1]))
+
+    @staticmethod
+    def closing_norm_state(weights, layer):
+        """Layer `layer`'s closing LayerNorm entries (weight, bias) of a sa_norm_first state_dict without the module prefix: the last
+        layer's load into torch.nn.TransformerEncoder(..., norm=LayerNorm(C)).norm; {} where the layer has no closing norm"""
+        on = SaConfig.out_name(layer)
+        return {k[len(on) + 1:]: v for k, v in weights.items() if k.startswith(on + ".")}
+
+    @staticmethod
+    def macaron_ffn_state(weights, layer):
+        """Layer `layer`'s macaron FFN entries of a sa_macaron state_dict: linear1.*, linear2.* and, as norm.*, its LayerNorm's"""
+        mn, mnn = SaConfig.macaron_names(layer)
+        out = {}
+        for k, v in weights.items():
+            if k.startswith(mn + "."):
+                out[k[len(mn) + 1:]] = v
+            elif k.startswith(mnn + "."):
+                out["norm." + k[len(mnn) + 1:]] = v
+        return out
 
     def _make_engine(self, precision):
         return CnnEngine(self.classes_num, self.model_config, AUDIO_CHANNELS, precision, head="sa", mel_bins=self.mel_bins,
