@@ -29,6 +29,8 @@ Gates (derived from window_formula's, not tuned on kernel output; U = 2^-24):
             a wave, the per-wave partials in fp64, and rounds once -- at most (n_d + 2) U sum |ds| -- and each ds carries
             window_formula's ES_ij:  gate = (n_d + 2) U sum |ds_ij| + sum ES_ij over the distance's cells.
   dw        the same over the bucket's cells: (n_b + 2) U sum |ds_ij| + sum ES_ij, n_b the bucket's cell count.
+  raw dctx  (bf16, raw_dctx=True)  window_formula's terms for a dctx the kernel rounds as an operand, on the biased p; through ES they
+            reach drel and dw as every other error of ds does.
 """
 import numpy as np
 
@@ -188,9 +190,10 @@ def fold(drel, cfg, t, dtype=np.float64):
     return out
 
 
-def core_gates(q, k, v, rel, left, right, dctx, keep=None, s=1.0, mode="f32", lse=None, ctx=None, cfg=None):
+def core_gates(q, k, v, rel, left, right, dctx, keep=None, s=1.0, mode="f32", lse=None, ctx=None, cfg=None, raw_dctx=False):
     """per-element gates for ctx, lse, dq, dk, dv, drel and (with cfg) dw (module docstring): window_formula.core_gates line by line on
-    the biased p, with the score's extra rounding in delta and S."""
+    the biased p, with the score's extra rounding in delta and S.  raw_dctx (bf16): dctx is not bf16-representable and the kernel rounds
+    it where it is an MFMA operand -- window_formula's raw dctx terms on the biased p (they enter drel and dw through ES)."""
     assert mode in ("f32", "bf16")
     q, k, v, dctx = (np.asarray(a, dtype=np.float64) for a in (q, k, v, dctx))
     B, t, H, dh = q.shape
@@ -218,6 +221,10 @@ def core_gates(q, k, v, rel, left, right, dctx, keep=None, s=1.0, mode="f32", ls
     pA = p * Abar
     ES = pA * (rho_b[..., None] + (dh + 5 + e) * U + pb)
     g["dv"] = np.einsum("bhij,bihc->bjhc", ptb * (rho_b[..., None] + (n_k[None, None, None, :] + 2 + e) * U + pb), ad)
+    if raw_dctx and mode == "bf16":
+        eps = M.round_bf16(dctx).astype(np.float64) - dctx
+        ES = ES + p * ms * np.minimum(np.abs(np.einsum("bihc,bjhc->bhij", eps, v)), 2.0 ** -8 * np.einsum("bihc,bjhc->bhij", ad, av))
+        g["dv"] = g["dv"] + np.minimum(np.abs(np.einsum("bhij,bihc->bjhc", ptb, eps)), 2.0 ** -8 * np.einsum("bhij,bihc->bjhc", ptb, ad))
     g["dq"] = scale * np.einsum("bhij,bjhc->bihc", ES + (n_q[..., None] + 3) * U * pA, ak)
     g["dk"] = scale * np.einsum("bhij,bihc->bjhc", ES + (n_k[None, None, None, :] + 3) * U * pA, aq)
     n_d = B * diag_sums(np.broadcast_to(w.astype(np.float64), (H, t, t)))

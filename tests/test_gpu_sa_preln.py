@@ -47,18 +47,25 @@ def make_model(sed, K=3, precision="fp32", seed=0, **kw):
     return m.cuda()
 
 
-def oracle(sd, feat, y, state, p, opts, ratio, training=True):
-    """feat (B, t, Wf, C) float64 -> (logits, loss, parameter gradients by state_dict name, the feature gradient)"""
+def preln_encoder(opts, state, p, training=True):
+    """preln_formula.encoder on a model's options, as oracle takes it: (x, W, B, t, H, dh_out=None) -> the formula's dict"""
+    kw = dict(layers=opts["sa_layers"], ffn_width=opts.get("sa_ffn", 0), act=opts.get("sa_activation", "relu"), macaron=opts.get("sa_macaron", False),
+              conv=bool(opts.get("sa_conv_kernel", 0)), window=opts.get("sa_window") or (None, None), rel_cfg=opts.get("sa_rel_pos"), state=state, p=p,
+              pos_encoding=False, training=training)
+    return lambda x, Wn, Bc, t, H, dh_out=None: PF.encoder(x, Wn, Bc, t, H, dh_out=dh_out, **kw)
+
+
+def oracle(sd, feat, y, state, p, opts, ratio, training=True, heads=1, encoder=None):
+    """feat (B, t, Wf, C) float64 -> (logits, loss, parameter gradients by state_dict name, the feature gradient, the formula's forward
+    dict: the BatchNorms' running statistics after a training forward).  heads: the head count the formula splits by; encoder: another
+    stack than preln_encoder(opts, ...) with its call (tests/test_gpu_sa_block_at_size.py: the post-LN stack of relpos_formula)."""
     Bc, t, Wf, Cc = feat.shape
     Wn = {n: v.double().cpu().numpy() for n, v in sd.items() if n.startswith(HEAD) and "config" not in n and "num_batches" not in n}
     x = feat.mean(dim=2).reshape(Bc * t, Cc).numpy()
-    kw = dict(layers=opts["sa_layers"], ffn_width=opts.get("sa_ffn", 0), act=opts.get("sa_activation", "relu"), macaron=opts.get("sa_macaron", False),
-              conv=bool(opts.get("sa_conv_kernel", 0)), window=opts.get("sa_window") or (None, None), rel_cfg=opts.get("sa_rel_pos"), state=state, p=p,
-              pos_encoding=True, training=training)
+    enc = encoder if encoder is not None else preln_encoder(opts, state, p, training)
     # the positional table as the engine holds it: rounded once to fp32
-    pe = np.tile(PF.M.positional_table(t, Cc).astype(np.float32).astype(np.float64), (Bc, 1))
-    kw["pos_encoding"] = False
-    fwd = PF.encoder(x + pe, Wn, Bc, t, 1, **kw)
+    pe = np.tile(PF.M.positional_table(t, Cc).astype(np.float32).astype(np.float64), (Bc, 1)) if opts.get("pos_encoding", True) else 0.0
+    fwd = enc(x + pe, Wn, Bc, t, heads)
     h = torch.from_numpy(fwd["h"]).reshape(Bc, t, Cc).requires_grad_(True)
     fc = torch.nn.Linear(Cc, sd["event_fc.weight"].shape[0]).double()
     fc.load_state_dict({n[len("event_fc."):]: v.double().cpu() for n, v in sd.items() if n.startswith("event_fc.")})
@@ -66,53 +73,77 @@ def oracle(sd, feat, y, state, p, opts, ratio, training=True):
     N = min(out.shape[1], y.shape[1])
     loss = TF.binary_cross_entropy_with_logits(out[:, :N], y[:, :N], pos_weight=torch.tensor(W, dtype=torch.float64))
     loss.backward()
-    bwd = PF.encoder(x + pe, Wn, Bc, t, 1, dh_out=h.grad.reshape(Bc * t, Cc).numpy(), **kw)
+    bwd = enc(x + pe, Wn, Bc, t, heads, dh_out=h.grad.reshape(Bc * t, Cc).numpy())
     grads = {n[2:]: torch.from_numpy(np.asarray(a)) for n, a in bwd.items() if n.startswith("d_")}
     grads.update({"event_fc." + n: q.grad for n, q in fc.named_parameters()})
     dfeat = torch.from_numpy(bwd["dx"]).reshape(Bc, t, 1, Cc).expand(Bc, t, Wf, Cc) / Wf
-    return out.detach(), loss.detach(), grads, dfeat
+    return out.detach(), loss.detach(), grads, dfeat, fwd
 
 
-def compare(sed, model, opts, p=0.0):
-    """one training forward + backward of the fp32 model against the oracle; -> (out, the oracle's logits for these masks)"""
-    K = 3
-    x, y = batch(K)
+def compare(sed, model, opts, p=0.0, xy=None, cfg=CFG, mel=MEL, heads=1, training=True, encoder=None):
+    """one forward + backward of the fp32 model against the oracle; -> (out, what a second oracle call on the same step takes).
+    xy, cfg, mel, heads: another geometry than this module's; training=False: an eval forward kept for the gradient and the eval-mode
+    backward, after which every running statistic and counter keeps its bits; encoder(state): the stack oracle takes in the place of
+    preln_formula's (tests/test_gpu_sa_block_at_size.py).  The running statistics after a training step are held to
+    tests/test_gpu_sa_conformer.py's bound, 1e-4 relative L2 against the formula's, and the counter to + 1."""
+    x, y = batch(3) if xy is None else xy
+    K, Cc = y.shape[-1], cfg[-1][0]
     eng = model.engine
     sd0 = {n: v.clone() for n, v in model.state_dict().items()}
     state = eng.drop_state_words()
+    model.train(training)
     model.zero_grad()
     out = model(x)
     loss = sed.WeightedBCE(W, True)(out, y)
     loss.backward()
     plan = the_plan(model)
-    bare = sed.CnnEngine(K, CFG, 1, "fp32", head="none", mel_bins=MEL)
+    bare = sed.CnnEngine(K, cfg, 1, "fp32", head="none", mel_bins=mel)
     P0 = {n: v.cuda() for n, v in sd0.items()}
-    bp = bare.forward(x, P0, training=True, update_running_stats=False)
+    bp = bare.forward(x, P0, training=training, update_running_stats=False, keep_for_grad=not training)
     assert torch.equal(bp.y[-1], plan.y[-1])
-    feat = bp.y[-1][..., :C].double().cpu()
-    out_t, loss_t, grads, dfeat = oracle(sd0, feat, y.double().cpu(), state, p, opts, eng.ratio)
+    feat = bp.y[-1][..., :Cc].double().cpu()
+    out_t, loss_t, grads, dfeat, fwd = oracle(sd0, feat, y.double().cpu(), state, p, opts, eng.ratio, training, heads,
+                                              encoder(state) if encoder is not None else None)
     err = float((out.detach().cpu().double() - out_t).abs().max())
-    print(f"{opts} p={p}: logits max error {err:.3e}, loss error {abs(loss.item() - float(loss_t)):.3e}")
+    print(f"{opts} p={p} training={training}: logits max error {err:.3e}, loss error {abs(loss.item() - float(loss_t)):.3e}")
     assert err < 1e-3 and abs(loss.item() - float(loss_t)) < 1e-4
     mine = {n for n, _ in model.named_parameters() if not n.startswith("conv_blocks.")}
     assert mine == set(grads), mine ^ set(grads)
+    worst = 0.0
     for n, g in grads.items():
         got = model.get_parameter(n).grad
-        if n.endswith("depthwise.bias"):          # exactly zero in front of a training BatchNorm: both sides hold rounding noise
+        if training and n.endswith("depthwise.bias"):          # exactly zero in front of a training BatchNorm: both sides hold rounding noise
             scale = float(grads[n.replace(".bias", ".weight")].norm())
+            print(f"  {n}: |got| / |d weight| {float(got.norm()) / scale:.3e}, oracle {float(g.norm()) / scale:.3e}")
             assert float(got.norm()) < 3e-3 * scale and float(g.norm()) < 3e-3 * scale, n
             continue
         l2 = rel_l2(got, g.reshape(got.shape))
+        worst = max(worst, l2)
         print(f"  {n}: relative L2 {l2:.3e}")
         assert l2 < 3e-3, (n, l2)
+    # the BatchNorms' running statistics and counters
+    sd1 = model.state_dict()
+    for n in sd0:
+        if n.startswith("convm") and ".bn.running_" in n:
+            nbt = n.replace("running_mean", "num_batches_tracked").replace("running_var", "num_batches_tracked")
+            if training:
+                l2 = rel_l2(sd1[n], fwd[n])
+                print(f"  {n}: relative L2 {l2:.3e}")
+                assert l2 < 1e-4, (n, l2)
+                assert int(sd1[nbt]) == int(sd0[nbt]) + 1, nbt
+            else:
+                assert torch.equal(sd1[n], sd0[n]) and torch.equal(sd1[nbt], sd0[nbt]), (n, "an eval step changed a running statistic")
     # the oracle's feature gradient back through the pinned conv backward
     bp.dy[-1].zero_()
-    bp.dy[-1][..., :C] = dfeat.float().cuda()
+    bp.dy[-1][..., :Cc] = dfeat.float().cuda()
     names = [n for n, _ in model.named_parameters() if n.startswith("conv_blocks.")]
     G = {n: torch.full_like(P0[n], float("nan")) for n in names}
     bare.backward(bp, P0, G)
     for n in names:
-        assert rel_l2(model.get_parameter(n).grad, G[n]) < 3e-3, n
+        l2 = rel_l2(model.get_parameter(n).grad, G[n])
+        worst = max(worst, l2)
+        assert l2 < 3e-3, n
+    print(f"  worst gradient relative L2 {worst:.3e}")
     return out, (sd0, feat, y.double().cpu(), state, eng.ratio)
 
 

@@ -30,10 +30,10 @@ def rel(a, b):
     return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(1.0, np.abs(np.asarray(b)).max()))
 
 
-def randomized(sed, seed=0, heads=2, **kw):
+def randomized(sed, seed=0, heads=2, cfg=CFG, **kw):
     """a model on the CPU whose head parameters are all away from their zero / unit initial values"""
     torch.manual_seed(seed)
-    m = sed.Csa_AvgPooling(3, CFG, precision="fp32", sa_heads=heads, mel_bins=8, sa_norm_first=True, **kw)
+    m = sed.Csa_AvgPooling(3, cfg, precision="fp32", sa_heads=heads, mel_bins=8, sa_norm_first=True, **kw)
     with torch.no_grad():
         for n, p in m.named_parameters():
             if n.startswith(HEAD_PREFIXES):
@@ -85,7 +85,7 @@ class TorchConformerBlock(torch.nn.Module):
     """the macaron + convolution block out of torch modules: x + 1/2 FFN(LN x), + MHSA(LN x) with a float attn_mask (window, bias),
     + ConvModule(LN x), + 1/2 FFN(LN x), LN"""
 
-    def __init__(self, H, D, k):
+    def __init__(self, H, D, k, C=C):
         super().__init__()
         nn = torch.nn
         self.n_mac, self.n_att, self.n_conv, self.n_ffn, self.n_out = (nn.LayerNorm(C) for _ in range(5))
@@ -107,9 +107,78 @@ class TorchConformerBlock(torch.nn.Module):
 
 @pytest.mark.parametrize("layers", [1, 2])
 def test_definition_against_torch_conformer_block(sed, layers):
-    B, t, H, D, k, win, rp = 2, 9, 2, 96, 5, (3, 2), 2
-    m = randomized(sed, seed=10 + layers, heads=H, sa_layers=layers, sa_ffn=D, sa_macaron=True, sa_conv_kernel=k, sa_window=win, sa_rel_pos=rp,
+    conformer_block_against_torch(sed, layers, 2, (3, 2), 2)
+
+
+@pytest.mark.parametrize("H,win,rp", [(4, (3, 0), 2), (4, (5, 2), (8, 16)), (2, (3, 0), (8, 16))], ids=str)
+def test_conformer_block_with_more_heads_window_and_table_against_torch(sed, H, win, rp):
+    """the heads, the window and the per-layer tables together (what tests/test_gpu_sa_block_at_size.py rests on): four heads, a causal
+    window, log buckets; the tables drawn N(0, 1) so that a table read for the wrong head or layer moves the output by O(1)"""
+    conformer_block_against_torch(sed, 2, H, win, rp, table_sigma=1.0)
+
+
+@pytest.mark.parametrize("H", [2, 4])
+@pytest.mark.parametrize("win,rp", [((3, 0), 2), ((5, 2), (8, 16))], ids=str)
+def test_plain_stack_with_heads_window_and_table_against_torch_norm_first_layers(sed, H, win, rp):
+    """the plain pre-LN stack (no macaron, no module) with H heads, a window and per-layer tables against
+    TransformerEncoderLayer(norm_first=True) called layer by layer with its own float src_mask (the table's bias, -inf outside the
+    window), then the closing LayerNorm"""
+    B, t, D, layers, C = 2, 9, 96, 2, 32 * H
+    m = randomized(sed, seed=20 + H, heads=H, cfg=[(32, 2), (C, 2)], sa_layers=layers, sa_ffn=D, sa_activation="gelu", sa_window=win, sa_rel_pos=rp, pos_encoding=False)
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if n.startswith("rel_pos"):
+                p.normal_(0.0, 1.0)
+    sd = {k: v.double() for k, v in m.state_dict().items()}
+    rng = np.random.default_rng(H)
+    x, dh_out = rng.normal(0, 1, (B * t, C)), rng.normal(0, 1, (B * t, C))
+    ref = PF.encoder(x, head_weights(sd), B, t, H, layers, D, "gelu", window=win, rel_cfg=rp, pos_encoding=False, dh_out=dh_out)
+    Csa = sed.Csa_AvgPooling
+    window = torch.where(torch.from_numpy(W.in_window(t, *win)), 0.0, -np.inf).double()
+    lys, biases = [], []
+    for l in range(layers):
+        ly = torch.nn.TransformerEncoderLayer(C, H, D, dropout=0.0, activation="gelu", batch_first=True, norm_first=True).double().train()
+        ly.load_state_dict(Csa.encoder_layer_state(sd, l))
+        lys.append(ly)
+        biases.append(Csa.rel_pos_bias(sd, l, t).clone().requires_grad_(True))
+    assert not torch.equal(biases[0].detach(), biases[1].detach()) and not torch.equal(biases[0][0].detach(), biases[0][1].detach())
+    norm = torch.nn.LayerNorm(C).double()
+    norm.load_state_dict(Csa.closing_norm_state(sd, layers - 1))
+    xt = torch.from_numpy(x).view(B, t, C).clone().requires_grad_(True)
+    h = xt
+    for ly, bias in zip(lys, biases):
+        h = ly(h, src_mask=(bias + window).repeat(B, 1, 1))
+    h = norm(h)
+    h.backward(torch.from_numpy(dh_out).view(B, t, C))
+    assert rel(ref["h"], h.detach().numpy().reshape(B * t, C)) < 1e-12
+    assert rel(ref["dx"], xt.grad.numpy().reshape(B * t, C)) < 1e-12
+    back = {"self_attn": "attn", "norm1": "attn_norm", "linear1": "ffn", "linear2": "ffn", "norm2": "ffn_norm"}
+    seen = set()
+    for l, (ly, bias) in enumerate(zip(lys, biases)):
+        for n, p in ly.named_parameters():
+            top, rest = n.split(".", 1)
+            key = "d_" + back[top] + PF.sfx(l) + "." + (n if top.startswith("linear") else rest)
+            assert rel(ref[key], p.grad.numpy()) < 1e-12, key
+            seen.add(key)
+        key = "d_rel_pos" + PF.sfx(l) + ".weight"
+        assert rel(ref[key], PF.RP.fold(PF.RP.diag_sums(bias.grad.numpy()), rp, t)) < 1e-12, key
+        seen.add(key)
+    for n, p in norm.named_parameters():
+        key = "d_out_norm" + PF.sfx(layers - 1) + "." + n
+        assert rel(ref[key], p.grad.numpy()) < 1e-12, key
+        seen.add(key)
+    assert seen == {kk for kk in ref if kk.startswith("d_")}
+
+
+def conformer_block_against_torch(sed, layers, H, win, rp, table_sigma=None):
+    B, t, D, k, C = 2, 9, 96, 5, 32 * H
+    m = randomized(sed, seed=10 + layers, heads=H, cfg=[(32, 2), (C, 2)], sa_layers=layers, sa_ffn=D, sa_macaron=True, sa_conv_kernel=k, sa_window=win, sa_rel_pos=rp,
                    pos_encoding=False)
+    if table_sigma is not None:
+        with torch.no_grad():
+            for n, p in m.named_parameters():
+                if n.startswith("rel_pos"):
+                    p.normal_(0.0, table_sigma)
     sd = {kk: v.double() for kk, v in m.state_dict().items()}
     rng = np.random.default_rng(layers)
     x, dh_out = rng.normal(0, 1, (B * t, C)), rng.normal(0, 1, (B * t, C))
@@ -119,7 +188,7 @@ def test_definition_against_torch_conformer_block(sed, layers):
     Csa = sed.Csa_AvgPooling
     blocks, masks, names = [], [], []
     for l in range(layers):
-        blk = TorchConformerBlock(H, D, k).double().train()
+        blk = TorchConformerBlock(H, D, k, C).double().train()
         enc, mac, cv, out = Csa.encoder_layer_state(sd, l), Csa.macaron_ffn_state(sd, l), Csa.conv_module_state(sd, l), Csa.closing_norm_state(sd, l)
         sfx = PF.sfx(l)
         load = {"n_mac": ("ffn_mac_norm", {kk[5:]: v for kk, v in mac.items() if kk.startswith("norm.")}),

@@ -129,6 +129,108 @@ def test_encoder_against_transformer_encoder_layer_with_a_float_src_mask(window,
         assert rel(got["d_" + RF.rel_name(l) + ".weight"], tw.grad.numpy()) < 1e-11, l
 
 
+def torch_masked_stack(x, Wt, cfg, B, t, H, window, layers, k, masks):
+    """The post-LN stack with the convolution module in torch, written out with autograd: scores + table bias, -inf outside the window,
+    softmax, and the dropout masks as constant factors at dropout_formula's five sites (masks[l][site], already times s; the attention
+    site (B, H, t, t), the others (R, N)).  Wt: leaf tensors by name.  -> h (B, t, C)"""
+    TF = torch.nn.functional
+    C = x.shape[-1]
+    dh = C // H
+    idx = torch.from_numpy(RF.bucket_map(cfg, t).astype(np.int64)[RF.dist_index(t)])
+    blocked = torch.from_numpy(WF.torch_mask(t, *window))
+    ln = lambda v, name: TF.layer_norm(v, (C,), Wt[name + ".weight"], Wt[name + ".bias"], MF.EPS)
+    rows = lambda m: m.reshape(B, t, -1)
+    h = x
+    for l in range(layers):
+        an, nn_, fn, fnn = FF.layer_names(l)
+        cm, cn = RF.V.conv_names(l)
+        ms = masks[l]
+        q, kk, v = (TF.linear(h, Wt[an + ".in_proj_weight"], Wt[an + ".in_proj_bias"]).view(B, t, 3, H, dh)[:, :, i].transpose(1, 2) for i in range(3))
+        sc = q @ kk.transpose(2, 3) / np.sqrt(dh) + Wt[RF.rel_name(l) + ".weight"][:, idx][None]
+        p = torch.softmax(sc.masked_fill(blocked[None, None], float("-inf")), dim=3) * ms[DF.SITE_ATTN]
+        a = TF.linear((p @ v).transpose(1, 2).reshape(B, t, C), Wt[an + ".out_proj.weight"], Wt[an + ".out_proj.bias"])
+        h = ln(h + a * rows(ms[DF.SITE_ATTN_OUT]), nn_)
+        g = TF.glu(TF.conv1d(h.transpose(1, 2), Wt[cm + ".pointwise1.weight"], Wt[cm + ".pointwise1.bias"]), dim=1)
+        z = TF.conv1d(g, Wt[cm + ".depthwise.weight"], Wt[cm + ".depthwise.bias"], padding=(k - 1) // 2, groups=C)
+        z = TF.batch_norm(z, None, None, Wt[cm + ".bn.weight"], Wt[cm + ".bn.bias"], training=True, eps=RF.V.EPS)
+        o = TF.conv1d(TF.silu(z), Wt[cm + ".pointwise2.weight"], Wt[cm + ".pointwise2.bias"]).transpose(1, 2)
+        h = ln(h + o * rows(ms[DF.SITE_CONV_OUT]), cn)
+        u = TF.gelu(TF.linear(h, Wt[fn + ".linear1.weight"], Wt[fn + ".linear1.bias"])) * rows(ms[DF.SITE_FFN_HIDDEN])
+        h = ln(h + TF.linear(u, Wt[fn + ".linear2.weight"], Wt[fn + ".linear2.bias"]) * rows(ms[DF.SITE_FFN_OUT]), fnn)
+    return h
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1])
+@pytest.mark.parametrize("H,window,cfg", [(2, (3, 0), 5), (4, (3, 0), 5), (4, (4, 2), (8, 16))], ids=str)
+def test_encoder_with_the_module_heads_window_table_and_dropout_against_torch_autograd(H, window, cfg, p):
+    """every option of the post-LN stack at once (what tests/test_gpu_sa_block_at_size.py's configuration AR rests on): H heads, a window,
+    per-layer tables, the convolution module and, with p > 0, the masks of all five sites as constant factors in a torch graph"""
+    rng = np.random.default_rng(11 + H)
+    B, t, C, D, layers, k = 2, 12, 64, 96, 2, 7
+    R = B * t
+    W = encoder_weights(rng, C, D, layers, H, cfg)
+    for l in range(layers):
+        cm, cn = RF.V.conv_names(l)
+        W.update({cm + ".pointwise1.weight": rng.normal(0, 0.2, (2 * C, C, 1)), cm + ".pointwise1.bias": rng.normal(0, 0.1, 2 * C),
+                  cm + ".depthwise.weight": rng.normal(0, 0.3, (C, 1, k)), cm + ".depthwise.bias": rng.normal(0, 0.1, C),
+                  cm + ".bn.weight": rng.normal(1, 0.2, C), cm + ".bn.bias": rng.normal(0, 0.1, C),
+                  cm + ".bn.running_mean": rng.normal(0, 0.2, C), cm + ".bn.running_var": rng.uniform(0.5, 1.5, C),
+                  cm + ".pointwise2.weight": rng.normal(0, 0.2, (C, C, 1)), cm + ".pointwise2.bias": rng.normal(0, 0.1, C),
+                  cn + ".weight": rng.normal(1, 0.2, C), cn + ".bias": rng.normal(0, 0.1, C)})
+    x, dh = rng.normal(0, 1, (R, C)), rng.normal(0, 1, (R, C))
+    state = [0x5EDD0001, 0x00C0FFEE, 3, 0]
+    got = RF.encoder(x, W, cfg, B, t, H, *window, state=state, p=p, layers=layers, ffn_width=D, act="gelu", pos_encoding=False, conv=True, dh_out=dh)
+    s = float(DF.thr_scale(p)[1]) if p else 1.0
+    masks = []
+    for l in range(layers):
+        if p:
+            ms = {site: DF.keep_rows(state, DF.stream_id(l, site), R, D if site == DF.SITE_FFN_HIDDEN else C, p) for site in (1, 2, 3, 4)}
+            ms[DF.SITE_ATTN] = DF.keep_attn(state, DF.stream_id(l, DF.SITE_ATTN), B, H, t, p)
+            assert all(0 < int(m.sum()) < m.size for m in ms.values())
+            masks.append({site: torch.from_numpy(m.astype(np.float64) * s) for site, m in ms.items()})
+        else:
+            shapes = {0: (B, H, t, t), 1: (R, C), 2: (R, C), 3: (R, D), 4: (R, C)}
+            masks.append({site: torch.ones(shape, dtype=torch.float64) for site, shape in shapes.items()})
+    Wt = {n: torch.from_numpy(np.asarray(a, dtype=np.float64)).requires_grad_(".running_" not in n) for n, a in W.items()}
+    xt = torch.from_numpy(x.reshape(B, t, C)).requires_grad_(True)
+    h = torch_masked_stack(xt, Wt, cfg, B, t, H, window, layers, k, masks)
+    h.backward(torch.from_numpy(dh.reshape(B, t, C)))
+    assert rel(got["h"], h.detach().numpy().reshape(R, C)) < 1e-11
+    assert rel(got["dx"], xt.grad.numpy().reshape(R, C)) < 1e-11
+    want = {n for n in W if ".running_" not in n}
+    assert {n[2:] for n in got if n.startswith("d_")} == want
+    for n in sorted(want):
+        if n.endswith("depthwise.bias"):          # zero in exact arithmetic in front of a training BatchNorm: rounding noise on both sides
+            scale = np.abs(got["d_" + n.replace(".bias", ".weight")]).max()
+            assert np.abs(got["d_" + n]).max() < 1e-11 * scale and float(Wt[n].grad.abs().max()) < 1e-11 * scale
+            continue
+        assert rel(got["d_" + n].reshape(W[n].shape), Wt[n].grad.numpy()) < 1e-10, n
+
+
+@pytest.mark.parametrize("window", [(3, 0), (40, 7), (None, None)], ids=str)
+def test_raw_dctx_gate_holds_where_a_key_has_one_query(window):
+    """bf16 with a dctx that is not bf16-representable (what the engine's GEMM hands the core): dV = P~^T dctx with both operands rounded
+    to nearest even and the sum exact, against float64 on the raw dctx.  Window (3, 0) leaves the last key of a clip one query: its dv
+    moves by the whole p~ eps, up to 2^-8 p~ |dctx| -- the figure the shift is capped at (a cap of 2^-9 is missed at 1.24 gates here)."""
+    rng = np.random.default_rng(0)
+    B, t, H, dh = 4, 130, 4, 32
+    rb = lambda a: MF.round_bf16(a).astype(np.float64)
+    q, k, v = (rb(rng.normal(0, 1, (B, t, H, dh)).astype(np.float32)) for _ in range(3))
+    d = rng.normal(0, 1e-3, (B, t, H, dh)).astype(np.float32).astype(np.float64)
+    assert not np.array_equal(rb(d), d)
+    w = rng.normal(0, 1, (H, 2 * t - 1)).astype(np.float32)
+    for name, ref, gates, tight in (("biased", RF.core(q, k, v, w, *window, d), RF.core_gates(q, k, v, w, *window, d, mode="bf16", raw_dctx=True),
+                                     RF.core_gates(q, k, v, w, *window, d, mode="bf16")),
+                                    ("unbiased", WF.core(q, k, v, *window, d), WF.core_gates(q, k, v, *window, d, mode="bf16", raw_dctx=True),
+                                     WF.core_gates(q, k, v, *window, d, mode="bf16"))):
+        got = np.einsum("bhij,bihc->bjhc", rb(ref["pt_bwd"]), rb(d))
+        ratio = np.abs(got - ref["dv"]) / gates["dv"]
+        print(f"window {window}, {name}: worst dv error / gate {ratio.max():.3f}")
+        assert ratio.max() <= 1.0
+        # without the raw-dctx terms the short sums are outside: they are what holds them
+        assert window != (3, 0) or (np.abs(got - ref["dv"]) / tight["dv"]).max() > 1.0
+
+
 # ---- the gates: a plain fp32 implementation passes, mutants fail --------------------------------------------------------------------
 def gate_case(mode, t=70):
     bf = mode == "bf16"

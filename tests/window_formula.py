@@ -32,7 +32,14 @@ docstrings go through line by line with p_ij = 0 outside the window; what change
             dv_jc: sum_i p~_ij |dctx_ic| (rho'_i + (n'_j + 2 + e) U + pb) with n'_j the number of in-window QUERIES of key j (the length
                    of dv's sum)
             dq_ic: scale sum_j (ES_ij + (n_i + 3) U p_ij Abar_ij) |k_jc|;   dk_jc: scale sum_i (ES_ij + (n'_j + 3) U p_ij Abar_ij) |q_ic|
-  raw dctx  (bf16, raw_dctx=True)  mhsa_formula's terms for a dctx the kernel rounds as an operand, with p (p~) over the window.
+  raw dctx  (bf16, raw_dctx=True)  mhsa_formula's terms for a dctx the kernel rounds as an operand, with p (p~) over the window: the
+            deterministic shift |sum_i p~_ij eps_ic| on dv and p_ij ms_ij |sum_c eps_ic v_jc| on ES, eps = round(dctx) - dctx, each
+            capped by its absolute-value form at 2^-8, the half ulp of 8 significant bits at the bottom of a binade: |eps| <= 2^-8 |dctx|.
+            mhsa_formula caps at 2^-9, the top-of-binade figure, which sums over all t keys stay far below; under a window it is no
+            bound -- window (3, 0) leaves the last key of a clip ONE query, whose dv moves by its actual p~ eps, up to 2^-8 p~ |dctx|.
+            A float64 emulation of the documented rounding with exact accumulation missed the 2^-9 cap at 1.24 gates there (and
+            the kernel at 1.19, tests/test_gpu_sa_block_at_size.py's configuration AR); at 2^-8 it stands at 0.99.  Where the shift is
+            below the 2^-9 form, as in every sum of more than a few terms, the gate is the one it was.
   teacher-forced  lse=, ctx= as in mhsa_formula: the backward half takes the lse and ctx it is given.
 """
 import numpy as np
@@ -166,8 +173,8 @@ def core_gates(q, k, v, left, right, dctx, keep=None, s=1.0, mode="f32", lse=Non
     g["dv"] = np.einsum("bhij,bihc->bjhc", ptb * (rho_b[..., None] + (n_k[None, None, None, :] + 2 + e) * U + pb), ad)
     if raw_dctx and mode == "bf16":
         eps = M.round_bf16(dctx).astype(np.float64) - dctx
-        ES = ES + p * ms * np.minimum(np.abs(np.einsum("bihc,bjhc->bhij", eps, v)), 2.0 ** -9 * np.einsum("bihc,bjhc->bhij", ad, av))
-        g["dv"] = g["dv"] + np.minimum(np.abs(np.einsum("bhij,bihc->bjhc", ptb, eps)), 2.0 ** -9 * np.einsum("bhij,bihc->bjhc", ptb, ad))
+        ES = ES + p * ms * np.minimum(np.abs(np.einsum("bihc,bjhc->bhij", eps, v)), 2.0 ** -8 * np.einsum("bihc,bjhc->bhij", ad, av))
+        g["dv"] = g["dv"] + np.minimum(np.abs(np.einsum("bhij,bihc->bjhc", ptb, eps)), 2.0 ** -8 * np.einsum("bhij,bihc->bjhc", ptb, ad))
     g["dq"] = scale * np.einsum("bhij,bjhc->bihc", ES + (n_q[..., None] + 3) * U * pA, ak)
     g["dk"] = scale * np.einsum("bhij,bihc->bjhc", ES + (n_k[None, None, None, :] + 3) * U * pA, aq)
     return g
