@@ -1040,7 +1040,7 @@ int sed_att_bwd_pack(const float* dpre, const float* datt, const float* fc_w, co
 int sed_att_bwd_split(const float* dwcat, const float* dbcat, float* dfc_w, float* dfc_b, float* datt_w,
                       float* datt_b, int C, int K, void* stream);
 
-/* ---- self-attention temporal head (csrc/sed_mhsa.hip) ---------------------------------------
+/* ---- self-attention temporal head (csrc/sed_mhsa.hip; its LayerNorms csrc/sed_layernorm.hip) ---------------------------------------
  * The attention core of torch.nn.MultiheadAttention(C, H, batch_first=True) between its two projections (those are
  * sed_gemm_nt launches), and the residual LayerNorm behind it.
  * qkv [B*t][3C] fp32 (q | k | v, head g = columns [g*dh, (g+1)*dh) of each third), C = H*dh, scale = 1/sqrt(dh).  Per clip b and
@@ -1102,7 +1102,7 @@ int sed_ffn_fwd(int dtype, int act, const float* x, const float* w1, const float
                 float* y, float* u, size_t R, int C, int D, void* stream);
 int sed_ffn_act_bwd(int act, const float* u, const float* da, float* a, float* du, size_t n, void* stream);
 
-/* ---- dropout of the self-attention head (csrc/philox.h, sed_dropout.hip, the _drop twins in sed_mhsa.hip / sed_ffn.hip) ---------
+/* ---- dropout of the self-attention head (csrc/philox.h, sed_dropout.hip, the _drop twins in sed_mhsa.hip / sed_layernorm.hip / sed_ffn.hip) ---------
  * Masks are generated inside the fused kernels, forward and backward, from a counter-based generator (Philox4x32-10: multipliers
  * 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds), never stored:
  *   state  rng: four uint32 in DEVICE memory (seed_lo, seed_hi, step, 0); the kernels load it (a captured graph replays with the
@@ -1147,7 +1147,7 @@ int sed_ffn_act_bwd_drop(int act, const float* u, const float* da, float* a, flo
 int sed_dropout_mask(unsigned char* keep, int kind, size_t n0, int n1, int t, float p, const uint32_t* rng, uint32_t stream_id,
                      void* stream);
 
-/* ---- pre-LN residual LayerNorm of the self-attention head (csrc/sed_mhsa.hip) ---------------------------------------------------
+/* ---- pre-LN residual LayerNorm of the self-attention head (csrc/sed_layernorm.hip) ------------------------------------------------
  * The residual add of one sub-layer and the LayerNorm in front of the next in one launch, row-major fp32, one wave per row:
  *   forward   xsum = fma(a, s m sd, x)   (the product s * (m sd) is taken in fp32 first; m sd is sed_add_layernorm_fwd_drop's row
  *             keep factor of stream stream_id, 1 for p = 0),   y = (xsum - mean) * rstd * gamma + beta,   stats [rows][2] = (mean, rstd),

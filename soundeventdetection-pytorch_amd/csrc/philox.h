@@ -67,6 +67,15 @@ template <bool DROP> __device__ __forceinline__ DropKey drop_key(const DropArgs&
 __device__ __forceinline__ PhiloxWords drop_row_words(const DropKey& k, size_t r, uint32_t cq) {
     return philox4x32_10(cq, (uint32_t)r, (uint32_t)((uint64_t)r >> 32), k.step, k.k0, k.k1);
 }
+// where four consecutive columns (or keys) sit on the four lanes of a quad, the quad shares the counter: lane L makes one call and takes
+// word `word` of lane J's call (DPP quad permutes; every lane of the wave must be live)
+template <int J> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {      // lane J of the quad to its four lanes
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, J * 0x55, 0xF, 0xF, true);
+}
+template <int J> __device__ __forceinline__ uint32_t quad_word(const PhiloxWords& w, int word) {
+    const PhiloxWords b = {{quad_bcast<J>(w.w[0]), quad_bcast<J>(w.w[1]), quad_bcast<J>(w.w[2]), quad_bcast<J>(w.w[3])}};
+    return philox_pick(b, word);
+}
 // the four words of keys 4 * jq ... + 3 of query i of (clip, head) bh
 __device__ __forceinline__ PhiloxWords drop_attn_words(const DropKey& k, uint32_t jq, uint32_t i, uint32_t bh) {
     return philox4x32_10(jq, i, bh, k.step, k.k0, k.k1);

@@ -1,4 +1,4 @@
-// The keep mask of the self-attention head's dropout, written out: what the fused _drop kernels (sed_mhsa.hip, sed_ffn.hip) generate
+// The keep mask of the self-attention head's dropout, written out: what the fused _drop kernels (sed_mhsa.hip, sed_layernorm.hip, sed_ffn.hip) generate
 // in registers and never store.  One definition, philox.h; tests/dropout_formula.py is the same in numpy.
 //   SED_DROP_ROWS:  keep[r][c],        r < n0, c < n1           (a row tensor [R][N])
 //   SED_DROP_ATTN:  keep[b][g][i][j],  b < n0, g < n1, i, j < t (the attention probabilities)

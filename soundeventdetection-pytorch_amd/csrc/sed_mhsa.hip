@@ -1,5 +1,5 @@
-// Self-attention temporal head: the multi-head attention core (forward and backward, flash form, on the matrix pipe) and the
-// residual LayerNorm behind it.  The projections around the core are sed_gemm_nt / sed_gemm_tn launches (sed_gru.hip).
+// Self-attention temporal head: the multi-head attention core (forward and backward, flash form, on the matrix pipe).  The projections
+// around the core are sed_gemm_nt / sed_gemm_tn launches (sed_gru.hip), the LayerNorms around the sub-layers sed_layernorm.hip.
 //
 // Core, for one clip b and head g (dh = 32 or 64 columns [g*dh, (g+1)*dh) of each third of a qkv row), scale = 1/sqrt(dh):
 //   s_ij  = scale * sum_c q_ic k_jc                      i, j over the t frames of the SAME clip, no mask
@@ -38,25 +38,16 @@
 // Addressing: 64-bit clip base + 32-bit offsets inside a clip: t * 3C * 4 bytes must stay below 2^31, and B*H*ceil(t/128) below 2^31
 // workgroups.  qkv, ctx, dctx, dqkv must be 16-byte aligned (rows are read and written with 16-byte accesses).
 //
-// LayerNorm: y = ((x + a) - mean) * rstd * gamma + beta per row, mean and the centred sum of squares in two passes (biased variance,
-// rstd = 1/sqrt(var + eps)), one wave per row, each lane its columns in ascending order and one fixed wave reduction.  Backward with
-// g = dy * gamma, xhat = ((x + a) - mean) * rstd:  dres = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat)), the gradient of both x and
-// a; dgamma = sum_rows dy * xhat and dbeta = sum_rows dy through per-workgroup partials (64 rows each) in the workspace and a
-// fixed-order reduction over the workgroups.
-//
-// Dropout (the DROP instantiations behind sed_mhsa_fwd_drop / sed_mhsa_bwd_drop / sed_add_layernorm_fwd_drop / _bwd_drop; masks m and
-// scale s = 1 / (1 - p) from philox.h, generated in registers in the forward and again in the backward, never stored):
+// Dropout (the DROP instantiations behind sed_mhsa_fwd_drop / sed_mhsa_bwd_drop; masks m and scale s = 1 / (1 - p) from philox.h,
+// generated in registers in the forward and again in the backward, never stored):
 //   core       lse_i and p_ij as above, over all keys (no renormalisation);  p~_ij = m_ij s p_ij,  ctx_ic = sum_j p~_ij v_jc.  In the
 //              running form exp(s_ij - m_run) is multiplied by m_ij s in fp32 for the P V operand only (SED_BF16: the operand is
 //              bf16(p m s)); the normalising sum is still taken over the undropped fp32 probabilities.
 //              dv_jc = sum_i p~_ij dctx_ic,  dp_ij = m_ij s sum_c dctx_ic v_jc,  ds_ij = p_ij (dp_ij - D_i);  D_i = sum_c dctx_ic ctx_ic
 //              holds with the dropped ctx, so launch 1 is unchanged.
-//   LayerNorm  y = LayerNorm(x + m s a) (one fma per element);  dres (the gradient of x) as above with xhat of the dropped sum, and a
-//              second output da = m s dres (the gradient of a);  dgamma / dbeta with xhat of the dropped sum.
 // A lane of the forward and of the dQ pass holds four consecutive keys of one query in registers 4 n ... 4 n + 3: one Philox call per
-// four scores.  Where four consecutive keys / columns sit on the four lanes of a quad (the dK / dV pass, the LayerNorm kernels) the
-// quad shares the counter: every lane makes the call of another query / column step / row step and the words change places inside
-// the quad with DPP quad permutes.  The plain instantiations (DROP = false) are the code they were; a twin called with thr = 0
+// four scores.  Where four consecutive keys sit on the four lanes of a quad (the dK / dV pass) the quad shares the counter: every lane
+// makes the call of another query and the words change places inside the quad with DPP quad permutes (quad_word, philox.h).  The plain instantiations (DROP = false) are the code they were; a twin called with thr = 0
 // (p = 0) launches the plain instantiation.
 //
 // Local window (the WIN instantiations behind sed_mhsa_fwd_win / sed_mhsa_bwd_win; left, right >= 0, the same for every head): key j
@@ -97,7 +88,6 @@
 
 #define MHSA_QT 32            // queries (or keys) a wave owns
 #define MHSA_WAVES 4          // waves per workgroup, each with its own tile
-#define LN_ROWS_PER_WG 64     // rows behind one dgamma / dbeta partial
 
 namespace {
 
@@ -335,13 +325,6 @@ __device__ __forceinline__ float softmax_tile(f32x16& s, float& m, float& l, con
     m = WIN ? mx2 : mn;
     if (DROP) drop_scores_t(s, p.drop, k0, q0 + r, w.bh, h);
     return alpha;
-}
-template <int J> __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {      // lane J of the quad to its four lanes
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, J * 0x55, 0xF, 0xF, true);
-}
-template <int J> __device__ __forceinline__ uint32_t quad_word(const PhiloxWords& w, int word) {
-    const PhiloxWords b = {{quad_bcast<J>(w.w[0]), quad_bcast<J>(w.w[1]), quad_bcast<J>(w.w[2]), quad_bcast<J>(w.w[3])}};
-    return philox_pick(b, word);
 }
 // key on the lane (the dK / dV pass): registers 4 n ... 4 n + 3 are four consecutive queries q0 + 8 n + 4 h + (0 ... 3) of key j = k0 + r,
 // and the four lanes of a quad share j >> 2: lane L of the quad makes the call of query q0 + 8 n + 4 h + L, and lane j & 3 takes word
@@ -787,179 +770,6 @@ __global__ __launch_bounds__(256) void relpos_fold_kernel(const float* __restric
     if (b < nb) dw[(size_t)g * nb + b] = (float)s;
 }
 
-// ---- LayerNorm ---------------------------------------------------------------------------------------------------------------
-// m s of a lane's columns lane + 64 k of one row, k < LN_MSK, made once per row and kept in registers over the passes: the four lanes
-// of a quad own four consecutive columns, which share their counter, so lane L of the quad makes the call of step k0 + L and the words
-// change places inside the quad (quad_word): one call per lane and four steps = 256 columns.  Columns from 64 LN_MSK on take a call each.
-#define LN_MSK 8
-struct LnMask {
-    float ms[LN_MSK];
-    __device__ __forceinline__ LnMask(const DropKey& key, const DropArgs& d, size_t row, int C, int lane) {
-        const int L = lane & 3;
-#pragma unroll
-        for (int k0 = 0; k0 < LN_MSK; k0 += 4) {
-            if (64 * k0 < C) {                         // (uniform: every lane of the wave takes part in the permutes)
-                const PhiloxWords w = drop_row_words(key, row, (uint32_t)((lane >> 2) + 16 * (k0 + L)));
-                ms[k0 + 0] = drop_ms(quad_word<0>(w, L), d);
-                ms[k0 + 1] = drop_ms(quad_word<1>(w, L), d);
-                ms[k0 + 2] = drop_ms(quad_word<2>(w, L), d);
-                ms[k0 + 3] = drop_ms(quad_word<3>(w, L), d);
-            } else {
-                ms[k0 + 0] = ms[k0 + 1] = ms[k0 + 2] = ms[k0 + 3] = 0.f;
-            }
-        }
-    }
-    // f(c, m s) for this lane's columns in ascending order
-    template <typename Fn>
-    __device__ __forceinline__ void each(const DropKey& key, const DropArgs& d, size_t row, int C, int lane, Fn f) const {
-#pragma unroll
-        for (int k = 0; k < LN_MSK; ++k) {
-            const int c = lane + 64 * k;
-            if (c < C) f(c, ms[k]);
-        }
-        for (int c = lane + 64 * LN_MSK; c < C; c += 64) f(c, drop_row_ms(key, d, row, c));
-    }
-};
-
-template <bool DROP>
-__global__ __launch_bounds__(256) void add_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float* __restrict__ y, float* __restrict__ stats, size_t rows, int C, float eps,
-                                                         DropArgs drop) {
-    const int lane = threadIdx.x & 63;
-    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* __restrict__ xr = x + row * C;
-    const float* __restrict__ ar = a + row * C;
-    if (DROP) {                                        // the same sums in the same order over x + m s a (one fma per element)
-        const DropKey key(drop);
-        const LnMask mk(key, drop, row, C, lane);
-        float s = 0.f;
-        mk.each(key, drop, row, C, lane, [&](int c, float ms) { s += fmaf(ar[c], ms, xr[c]); });
-        const float mean = wave_sum(s) / (float)C;
-        float ss = 0.f;
-        mk.each(key, drop, row, C, lane, [&](int c, float ms) { const float d = fmaf(ar[c], ms, xr[c]) - mean; ss = fmaf(d, d, ss); });
-        const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)C + eps);
-        mk.each(key, drop, row, C, lane,
-                [&](int c, float ms) { y[row * C + c] = (fmaf(ar[c], ms, xr[c]) - mean) * rstd * gamma[c] + beta[c]; });
-        if (stats != nullptr && lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
-        return;
-    }
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += xr[c] + ar[c];
-    const float mean = wave_sum(s) / (float)C;
-    float ss = 0.f;
-    for (int c = lane; c < C; c += 64) { const float d = (xr[c] + ar[c]) - mean; ss = fmaf(d, d, ss); }
-    const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)C + eps);
-    for (int c = lane; c < C; c += 64) y[row * C + c] = ((xr[c] + ar[c]) - mean) * rstd * gamma[c] + beta[c];
-    if (stats != nullptr && lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
-}
-
-// DROP: xhat of x + m s a, and the second output da = m s dres (the gradient of a; dres stays the gradient of x)
-template <bool DROP>
-__global__ __launch_bounds__(256) void add_ln_bwd_dres_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                              const float* __restrict__ a, const float* __restrict__ gamma,
-                                                              const float* __restrict__ stats, float* __restrict__ dres,
-                                                              float* __restrict__ da, size_t rows, int C, DropArgs drop) {
-    const int lane = threadIdx.x & 63;
-    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* __restrict__ xr = x + row * C;
-    const float* __restrict__ ar = a + row * C;
-    const float* __restrict__ gr = dy + row * C;
-    const float mean = stats[2 * row], rstd = stats[2 * row + 1];
-    if (DROP) {
-        const DropKey key(drop);
-        const LnMask mk(key, drop, row, C, lane);
-        float s1 = 0.f, s2 = 0.f;
-        mk.each(key, drop, row, C, lane, [&](int c, float ms) {
-            const float g = gr[c] * gamma[c], xh = (fmaf(ar[c], ms, xr[c]) - mean) * rstd;
-            s1 += g;
-            s2 = fmaf(g, xh, s2);
-        });
-        const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
-        mk.each(key, drop, row, C, lane, [&](int c, float ms) {
-            const float g = gr[c] * gamma[c], xh = (fmaf(ar[c], ms, xr[c]) - mean) * rstd;
-            const float d = rstd * ((g - m1) - xh * m2);
-            dres[row * C + c] = d;
-            da[row * C + c] = d * ms;
-        });
-        return;
-    }
-    float s1 = 0.f, s2 = 0.f;
-    for (int c = lane; c < C; c += 64) {
-        const float g = gr[c] * gamma[c], xh = ((xr[c] + ar[c]) - mean) * rstd;
-        s1 += g;
-        s2 = fmaf(g, xh, s2);
-    }
-    const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
-    for (int c = lane; c < C; c += 64) {
-        const float g = gr[c] * gamma[c], xh = ((xr[c] + ar[c]) - mean) * rstd;
-        dres[row * C + c] = rstd * ((g - m1) - xh * m2);
-    }
-}
-
-// partial[chunk][0][c] = sum over the chunk's rows of dy * xhat, partial[chunk][1][c] = sum of dy: 64 columns x 4 row lanes per
-// workgroup, each row lane its rows (stride 4) in ascending order, then the four in a fixed order
-template <bool DROP>
-__global__ __launch_bounds__(256) void add_ln_bwd_part_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                              const float* __restrict__ a, const float* __restrict__ stats,
-                                                              float* __restrict__ partial, size_t rows, int C, DropArgs drop) {
-    __shared__ float sh[2][4][64];
-    const int cl = threadIdx.x & 63, ry = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    const size_t r0 = (size_t)blockIdx.y * LN_ROWS_PER_WG;
-    const size_t r1 = r0 + LN_ROWS_PER_WG < rows ? r0 + LN_ROWS_PER_WG : rows;
-    float sg = 0.f, sb = 0.f;
-    if (DROP) {
-        // a quad's four columns share the counter of a row: lane L of the quad makes the call of row step it0 + L and the words change
-        // places inside the quad; every thread takes part in the permutes, whatever its column and rows
-        const DropKey key(drop);
-        const int L = cl & 3;
-        for (int it0 = 0; it0 < LN_ROWS_PER_WG / 4; it0 += 4) {
-            const PhiloxWords w = drop_row_words(key, r0 + ry + 4 * (size_t)(it0 + L), (uint32_t)c >> 2);
-            const float ms4[4] = {drop_ms(quad_word<0>(w, L), drop), drop_ms(quad_word<1>(w, L), drop), drop_ms(quad_word<2>(w, L), drop),
-                                  drop_ms(quad_word<3>(w, L), drop)};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const size_t row = r0 + ry + 4 * (size_t)(it0 + j);
-                if (c < C && row < r1) {
-                    const float g = dy[row * C + c];
-                    const float xh = (fmaf(a[row * C + c], ms4[j], x[row * C + c]) - stats[2 * row]) * stats[2 * row + 1];
-                    sg = fmaf(g, xh, sg);
-                    sb += g;
-                }
-            }
-        }
-    } else if (c < C)
-        for (size_t row = r0 + ry; row < r1; row += 4) {
-            const float g = dy[row * C + c];
-            const float xh = ((x[row * C + c] + a[row * C + c]) - stats[2 * row]) * stats[2 * row + 1];
-            sg = fmaf(g, xh, sg);
-            sb += g;
-        }
-    sh[0][ry][cl] = sg;
-    sh[1][ry][cl] = sb;
-    __syncthreads();
-    if (ry == 0 && c < C) {
-        partial[((size_t)blockIdx.y * 2 + 0) * C + c] = (sh[0][0][cl] + sh[0][1][cl]) + (sh[0][2][cl] + sh[0][3][cl]);
-        partial[((size_t)blockIdx.y * 2 + 1) * C + c] = (sh[1][0][cl] + sh[1][1][cl]) + (sh[1][2][cl] + sh[1][3][cl]);
-    }
-}
-
-__global__ __launch_bounds__(256) void add_ln_bwd_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dgamma,
-                                                                float* __restrict__ dbeta, int nchunks, int C) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    float sg = 0.f, sb = 0.f;
-    for (int k = 0; k < nchunks; ++k) {
-        sg += partial[((size_t)k * 2 + 0) * C + c];
-        sb += partial[((size_t)k * 2 + 1) * C + c];
-    }
-    dgamma[c] = sg;
-    dbeta[c] = sb;
-}
-
 int mhsa_check(int dtype, int B, int t, int H, int dh, long long* nblocks, int* ntile) {
     SED_REQUIRE(dtype == SED_F32 || dtype == SED_BF16, "dtype must be SED_F32 or SED_BF16");
     SED_REQUIRE(B > 0 && t > 0 && H > 0, "sizes must be positive");
@@ -1210,262 +1020,6 @@ extern "C" int sed_relpos_expand(const float* w, const int* map, float* rel, int
 extern "C" int sed_relpos_fold(const float* drel, const int* map, float* dw, int H, int nb, int t, void* stream) {
     if (int rc = relpos_check(drel, map, dw, H, nb, t)) return rc;
     relpos_fold_kernel<<<dim3((unsigned)cdiv(nb, 256), (unsigned)H), 256, 0, (hipStream_t)stream>>>(drel, map, dw, nb, 2 * t - 1);
-    SED_LAUNCH_CHECK();
-    return 0;
-}
-
-namespace {
-template <bool DROP>
-int add_ln_fwd_launch(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
-                      size_t rows, int C, float eps, const DropArgs& drop, void* stream) {
-    SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
-    SED_REQUIRE(x != nullptr && a != nullptr && gamma != nullptr && beta != nullptr && y != nullptr, "x, a, gamma, beta and y are required");
-    SED_REQUIRE(cdivz(rows, 4) < ((size_t)1 << 31), "too many rows");
-    add_ln_fwd_kernel<DROP><<<(unsigned)cdivz(rows, 4), 256, 0, (hipStream_t)stream>>>(x, a, gamma, beta, y, stats, rows, C, eps, drop);
-    SED_LAUNCH_CHECK();
-    return 0;
-}
-}  // namespace
-
-extern "C" int sed_add_layernorm_fwd(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
-                                     size_t rows, int C, float eps, void* stream) {
-    return add_ln_fwd_launch<false>(x, a, gamma, beta, y, stats, rows, C, eps, DropArgs{}, stream);
-}
-
-extern "C" int sed_add_layernorm_fwd_drop(const float* x, const float* a, const float* gamma, const float* beta, float* y, float* stats,
-                                          size_t rows, int C, float eps, float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
-    SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
-    DropArgs d;
-    if (int rc = drop_require_args(p, rng, stream_id, &d)) return rc;
-    if (d.thr == 0) return add_ln_fwd_launch<false>(x, a, gamma, beta, y, stats, rows, C, eps, d, stream);
-    return add_ln_fwd_launch<true>(x, a, gamma, beta, y, stats, rows, C, eps, d, stream);
-}
-
-extern "C" size_t sed_add_layernorm_bwd_ws_floats(size_t rows, int C) {
-    if (rows == 0 || C <= 0) return 0;
-    return cdivz(rows, LN_ROWS_PER_WG) * 2 * (size_t)C;
-}
-
-namespace {
-template <bool DROP>
-int add_ln_bwd_launch(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
-                      float* dres, float* da, float* dgamma, float* dbeta, float* workspace, size_t rows, int C, const DropArgs& drop,
-                      void* stream) {
-    SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
-    SED_REQUIRE(dy != nullptr && x != nullptr && a != nullptr && gamma != nullptr && stats != nullptr && dres != nullptr &&
-                dgamma != nullptr && dbeta != nullptr && workspace != nullptr, "every pointer is required");
-    SED_REQUIRE(!DROP || da != nullptr, "da is required");
-    const size_t nchunks = cdivz(rows, LN_ROWS_PER_WG);
-    SED_REQUIRE(nchunks <= 65535, "too many rows (the partial grid takes 65535 * 64)");
-    hipStream_t st = (hipStream_t)stream;
-    add_ln_bwd_dres_kernel<DROP><<<(unsigned)cdivz(rows, 4), 256, 0, st>>>(dy, x, a, gamma, stats, dres, da, rows, C, drop);
-    SED_LAUNCH_CHECK();
-    add_ln_bwd_part_kernel<DROP><<<dim3((unsigned)cdiv(C, 64), (unsigned)nchunks), 256, 0, st>>>(dy, x, a, stats, workspace, rows, C, drop);
-    SED_LAUNCH_CHECK();
-    add_ln_bwd_reduce_kernel<<<(unsigned)cdiv(C, 256), 256, 0, st>>>(workspace, dgamma, dbeta, (int)nchunks, C);
-    SED_LAUNCH_CHECK();
-    return 0;
-}
-}  // namespace
-
-extern "C" int sed_add_layernorm_bwd(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
-                                     float* dres, float* dgamma, float* dbeta, float* workspace, size_t rows, int C, void* stream) {
-    return add_ln_bwd_launch<false>(dy, x, a, gamma, stats, dres, nullptr, dgamma, dbeta, workspace, rows, C, DropArgs{}, stream);
-}
-
-extern "C" int sed_add_layernorm_bwd_drop(const float* dy, const float* x, const float* a, const float* gamma, const float* stats,
-                                          float* dres, float* da, float* dgamma, float* dbeta, float* workspace, size_t rows, int C,
-                                          float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
-    SED_REQUIRE(rng != nullptr, "the dropout state rng is required");
-    DropArgs d;
-    if (int rc = drop_require_args(p, rng, stream_id, &d)) return rc;
-    SED_REQUIRE(da != nullptr, "da is required");
-    if (d.thr == 0) {                                  // da = dres
-        if (int rc = add_ln_bwd_launch<false>(dy, x, a, gamma, stats, dres, da, dgamma, dbeta, workspace, rows, C, d, stream)) return rc;
-        const hipError_t e = hipMemcpyAsync(da, dres, rows * (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        SED_REQUIRE(e == hipSuccess, "the copy of dres into da failed");
-        return 0;
-    }
-    return add_ln_bwd_launch<true>(dy, x, a, gamma, stats, dres, da, dgamma, dbeta, workspace, rows, C, d, stream);
-}
-
-// ---- pre-LN: the residual add of one sub-layer and the LayerNorm in front of the next, one launch each way -----------------------------
-// forward   xsum = fma(a, s m sd, x) (s m sd multiplied in fp32 first; m sd = 1 without dropout), y = LayerNorm(xsum) gamma + beta,
-//           stats = (mean, rstd); a == NULL: y = LayerNorm(x) and nothing else.  The sums, their order and the expressions are
-//           add_ln_fwd_kernel's: with s = 1 the bits of y and stats are that kernel's, plain or DROP.
-// backward  dxsum = dres_in + rstd (g - mean_c(g) - xhat mean_c(g xhat)), g = dy gamma, xhat from the STORED xsum (neither x nor a is
-//           read); da = s m sd dxsum.  A thread reads an element of dres_in before it writes the same element of dxsum: they may alias.
-//           dgamma / dbeta: partials over LN_ROWS_PER_WG rows from (dy, xsum, stats) and add_ln_bwd_reduce_kernel.
-namespace {
-template <typename Each>
-__device__ __forceinline__ void resid_ln_row(Each each, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                             float* __restrict__ yr, float* __restrict__ stats, size_t row, int C, float eps, int lane) {
-    float s = 0.f;
-    each([&](int c, float v) { s += v; });
-    const float mean = wave_sum(s) / (float)C;
-    float ss = 0.f;
-    each([&](int c, float v) { const float d = v - mean; ss = fmaf(d, d, ss); });
-    const float rstd = 1.f / sqrtf(wave_sum(ss) / (float)C + eps);
-    each([&](int c, float v) { yr[c] = (v - mean) * rstd * gamma[c] + beta[c]; });
-    if (stats != nullptr && lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
-}
-
-template <bool HAS_A, bool DROP>
-__global__ __launch_bounds__(256) void resid_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ a, float s,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float* __restrict__ xsum, float* __restrict__ y, float* __restrict__ stats,
-                                                           size_t rows, int C, float eps, DropArgs drop) {
-    const int lane = threadIdx.x & 63;
-    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* __restrict__ xr = x + row * C;
-    float* __restrict__ yr = y + row * C;
-    if (!HAS_A) {
-        resid_ln_row([&](auto f) { for (int c = lane; c < C; c += 64) f(c, xr[c]); }, gamma, beta, yr, stats, row, C, eps, lane);
-        return;
-    }
-    const float* __restrict__ ar = a + row * C;
-    float* __restrict__ sr = xsum + row * C;
-    if (DROP) {
-        const DropKey key(drop);
-        const LnMask mk(key, drop, row, C, lane);
-        auto each = [&](auto f) { mk.each(key, drop, row, C, lane, [&](int c, float ms) { f(c, fmaf(ar[c], s * ms, xr[c])); }); };
-        each([&](int c, float v) { sr[c] = v; });
-        resid_ln_row(each, gamma, beta, yr, stats, row, C, eps, lane);
-        return;
-    }
-    auto each = [&](auto f) { for (int c = lane; c < C; c += 64) f(c, fmaf(ar[c], s, xr[c])); };
-    each([&](int c, float v) { sr[c] = v; });
-    resid_ln_row(each, gamma, beta, yr, stats, row, C, eps, lane);
-}
-
-// dres_in and dxsum carry no __restrict__: they may be the same buffer
-template <bool HAS_RES, bool HAS_DA, bool DROP>
-__global__ __launch_bounds__(256) void resid_ln_bwd_row_kernel(const float* __restrict__ dy, const float* dres_in,
-                                                               const float* __restrict__ xsum, const float* __restrict__ gamma,
-                                                               const float* __restrict__ stats, float s, float* dxsum,
-                                                               float* __restrict__ da, size_t rows, int C, DropArgs drop) {
-    const int lane = threadIdx.x & 63;
-    const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* __restrict__ xr = xsum + row * C;
-    const float* __restrict__ gr = dy + row * C;
-    const float mean = stats[2 * row], rstd = stats[2 * row + 1];
-    float s1 = 0.f, s2 = 0.f;
-    for (int c = lane; c < C; c += 64) {
-        const float g = gr[c] * gamma[c], xh = (xr[c] - mean) * rstd;
-        s1 += g;
-        s2 = fmaf(g, xh, s2);
-    }
-    const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
-    auto out = [&](int c, float f) {
-        const float g = gr[c] * gamma[c], xh = (xr[c] - mean) * rstd;
-        // (the add of dres_in as an explicit fma: every instantiation rounds it the same way, whatever the compiler contracts)
-        const float in = (g - m1) - xh * m2;
-        const float d = HAS_RES ? fmaf(rstd, in, dres_in[row * C + c]) : rstd * in;
-        dxsum[row * C + c] = d;
-        if (HAS_DA) da[row * C + c] = d * f;
-    };
-    if (DROP) {
-        const DropKey key(drop);
-        const LnMask mk(key, drop, row, C, lane);
-        mk.each(key, drop, row, C, lane, [&](int c, float ms) { out(c, s * ms); });
-        return;
-    }
-    for (int c = lane; c < C; c += 64) out(c, s);
-}
-
-// add_ln_bwd_part_kernel's plain branch with xhat from the stored sum: the same partial layout, the same order
-__global__ __launch_bounds__(256) void resid_ln_bwd_part_kernel(const float* __restrict__ dy, const float* __restrict__ xsum,
-                                                                const float* __restrict__ stats, float* __restrict__ partial,
-                                                                size_t rows, int C) {
-    __shared__ float sh[2][4][64];
-    const int cl = threadIdx.x & 63, ry = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    const size_t r0 = (size_t)blockIdx.y * LN_ROWS_PER_WG;
-    const size_t r1 = r0 + LN_ROWS_PER_WG < rows ? r0 + LN_ROWS_PER_WG : rows;
-    float sg = 0.f, sb = 0.f;
-    if (c < C)
-        for (size_t row = r0 + ry; row < r1; row += 4) {
-            const float g = dy[row * C + c];
-            const float xh = (xsum[row * C + c] - stats[2 * row]) * stats[2 * row + 1];
-            sg = fmaf(g, xh, sg);
-            sb += g;
-        }
-    sh[0][ry][cl] = sg;
-    sh[1][ry][cl] = sb;
-    __syncthreads();
-    if (ry == 0 && c < C) {
-        partial[((size_t)blockIdx.y * 2 + 0) * C + c] = (sh[0][0][cl] + sh[0][1][cl]) + (sh[0][2][cl] + sh[0][3][cl]);
-        partial[((size_t)blockIdx.y * 2 + 1) * C + c] = (sh[1][0][cl] + sh[1][1][cl]) + (sh[1][2][cl] + sh[1][3][cl]);
-    }
-}
-
-// the scale and dropout arguments of an entry whose added tensor is present: s finite, p in [0, 1), rng required only for p > 0
-int resid_scale_args(float s, float p, const uint32_t* rng, uint32_t stream_id, DropArgs* d) {
-    SED_REQUIRE(isfinite(s), "the residual scale s must be finite");
-    if (int rc = drop_require_args(p, rng, stream_id, d)) return rc;
-    SED_REQUIRE(p == 0.f || rng != nullptr, "the dropout state rng is required for p > 0");
-    return 0;
-}
-}  // namespace
-
-extern "C" int sed_resid_layernorm_fwd(const float* x, const float* a, float s, const float* gamma, const float* beta, float* xsum,
-                                       float* y, float* stats, size_t rows, int C, float eps, float p, const uint32_t* rng,
-                                       uint32_t stream_id, void* stream) {
-    SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
-    SED_REQUIRE(x != nullptr && gamma != nullptr && beta != nullptr && y != nullptr, "x, gamma, beta and y are required");
-    SED_REQUIRE(cdivz(rows, 4) < ((size_t)1 << 31), "too many rows");
-    const unsigned grid = (unsigned)cdivz(rows, 4);
-    hipStream_t st = (hipStream_t)stream;
-    if (a == nullptr) {
-        resid_ln_fwd_kernel<false, false><<<grid, 256, 0, st>>>(x, nullptr, 1.f, gamma, beta, nullptr, y, stats, rows, C, eps, DropArgs{});
-    } else {
-        SED_REQUIRE(xsum != nullptr, "xsum is required with a");
-        DropArgs d;
-        if (int rc = resid_scale_args(s, p, rng, stream_id, &d)) return rc;
-        if (d.thr == 0)
-            resid_ln_fwd_kernel<true, false><<<grid, 256, 0, st>>>(x, a, s * d.scale, gamma, beta, xsum, y, stats, rows, C, eps, d);
-        else
-            resid_ln_fwd_kernel<true, true><<<grid, 256, 0, st>>>(x, a, s, gamma, beta, xsum, y, stats, rows, C, eps, d);
-    }
-    SED_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" size_t sed_resid_layernorm_bwd_ws_floats(size_t rows, int C) { return sed_add_layernorm_bwd_ws_floats(rows, C); }
-
-extern "C" int sed_resid_layernorm_bwd(const float* dy, const float* dres_in, const float* xsum, const float* gamma, const float* stats,
-                                       float s, float* dxsum, float* da, float* dgamma, float* dbeta, float* workspace, size_t rows,
-                                       int C, float p, const uint32_t* rng, uint32_t stream_id, void* stream) {
-    SED_REQUIRE(rows > 0 && C > 0, "sizes must be positive");
-    SED_REQUIRE(dy != nullptr && xsum != nullptr && gamma != nullptr && stats != nullptr && dxsum != nullptr && dgamma != nullptr &&
-                dbeta != nullptr && workspace != nullptr, "every pointer but dres_in and da is required");
-    const size_t nchunks = cdivz(rows, LN_ROWS_PER_WG);
-    SED_REQUIRE(nchunks <= 65535, "too many rows (the partial grid takes 65535 * 64)");
-    DropArgs d{};
-    if (da != nullptr)
-        if (int rc = resid_scale_args(s, p, rng, stream_id, &d)) return rc;
-    const bool drop = da != nullptr && d.thr != 0;
-    const float f = da != nullptr && !drop ? s * d.scale : s;
-    const unsigned grid = (unsigned)cdivz(rows, 4);
-    hipStream_t st = (hipStream_t)stream;
-#define SED_RESID_BWD(RES, DA, DROP) \
-    resid_ln_bwd_row_kernel<RES, DA, DROP><<<grid, 256, 0, st>>>(dy, dres_in, xsum, gamma, stats, f, dxsum, da, rows, C, d)
-    if (dres_in != nullptr) {
-        if (drop) SED_RESID_BWD(true, true, true);
-        else if (da != nullptr) SED_RESID_BWD(true, true, false);
-        else SED_RESID_BWD(true, false, false);
-    } else {
-        if (drop) SED_RESID_BWD(false, true, true);
-        else if (da != nullptr) SED_RESID_BWD(false, true, false);
-        else SED_RESID_BWD(false, false, false);
-    }
-#undef SED_RESID_BWD
-    SED_LAUNCH_CHECK();
-    resid_ln_bwd_part_kernel<<<dim3((unsigned)cdiv(C, 64), (unsigned)nchunks), 256, 0, st>>>(dy, xsum, stats, workspace, rows, C);
-    SED_LAUNCH_CHECK();
-    add_ln_bwd_reduce_kernel<<<(unsigned)cdiv(C, 256), 256, 0, st>>>(workspace, dgamma, dbeta, (int)nchunks, C);
     SED_LAUNCH_CHECK();
     return 0;
 }

@@ -53,7 +53,7 @@ class SaConfig:
     norm_first: pre-LN layers -- every sub-layer is x <- x + f(LayerNorm(x)) on a residual stream (its norm attn_norm* / conv_norm* /
     ffn_norm* in FRONT of it), and the last layer ends with a closing LayerNorm out_norm*, which event_fc reads:
     torch.nn.TransformerEncoder(TransformerEncoderLayer(norm_first=True), N, norm=LayerNorm(C)).  One launch adds sub-layer j's
-    output and normalises for sub-layer j + 1 (sed_resid_layernorm_fwd / _bwd, csrc/sed_mhsa.hip).
+    output and normalises for sub-layer j + 1 (sed_resid_layernorm_fwd / _bwd, csrc/sed_layernorm.hip).
     macaron (needs norm_first and ffn > 0): the Conformer block -- a second FFN ffn_mac* behind ffn_mac_norm* in front of the
     attention, both FFNs added with the weight 1/2, and a closing norm on EVERY layer.
     Every option at its default launches what the one-layer head always did."""
@@ -761,9 +761,74 @@ class SaHead(_Head):
         done(cm)
         self._lin_dx(g["cdg"], P[w1], g["cw1T"], dxin, R, 2 * C, C)
 
+    # ---- the sub-layers between given buffers: the post-LN loop (_forward, _backward) and the pre-LN chain (_forward_pre, _backward_pre)
+    # launch them from here, as they do the inner convolution module ---------------------------------------------------------------------
+    def _attn_forward(self, p, P, l, ly, mod, xin, keep, drop):
+        """The attention sub-layer of layer l (module mod): xin -> ly["qkv"] -> ly["ctx"] -> ly["a"]"""
+        c, eng, lib, dt, st, g = self.cfg, self.eng, self.eng.lib, self.eng.dt, _stream(), p.sa
+        Hh, t, C, R = c.heads, p.t_out, eng.cfg[-1][0], p.sa["R"]
+        eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(xin), C, L.ptr(P[mod + ".in_proj_weight"]), C, L.ptr(P[mod + ".in_proj_bias"]),
+               L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
+        if c.rel_pos is not None:
+            eng._k("sed_relpos_expand", lib.sed_relpos_expand, L.ptr(P[c.rel_name(l) + ".weight"]), L.ptr(g["rel_map"]),
+                   L.ptr(ly["rel"]), Hh, c.rel_pos_buckets(c.rel_pos), t, st)
+        self._mhsa_fwd(g, ly, l, keep, drop)
+        eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["ctx"]), C, L.ptr(P[mod + ".out_proj.weight"]), C,
+               L.ptr(P[mod + ".out_proj.bias"]), L.ptr(ly["a"]), C, R, C, C, 1, None, st)
+
+    def _attn_backward(self, p, P, G, l, ly, mod, ga, xin, dxin, drop, ks, ws, done):
+        """Backward of layer l's attention sub-layer: ga = the gradient of ly["a"] (dres, or m s dres under dropout), xin the sub-layer's
+        input -> its parameters' gradients and dxin, the gradient of xin through the sub-layer (no residual)."""
+        c, eng, lib, st, g = self.cfg, self.eng, self.eng.lib, _stream(), p.sa
+        Hh, t, C, R = c.heads, p.t_out, eng.cfg[-1][0], p.sa["R"]
+        # d out_proj.weight = ga^T . ctx, d out_proj.bias = column sums of ga;  dctx = ga . out_proj.weight
+        self._lin_dw(ga, ly["ctx"], G[mod + ".out_proj.weight"], G[mod + ".out_proj.bias"], R, C, C, t, ks, ws)
+        self._lin_dx(ga, P[mod + ".out_proj.weight"], g["woT"], g["dctx"], R, C, C)
+        self._mhsa_bwd(g, ly, l, drop)
+        if c.rel_pos is not None:
+            # ly["rel"] is the table this layer's forward read (the weights do not change between a step's forward and backward)
+            rn = c.rel_name(l)
+            eng._k("sed_relpos_fold", lib.sed_relpos_fold, L.ptr(ly["drel"]), L.ptr(g["rel_map"]), L.ptr(G[rn + ".weight"]), Hh,
+                   c.rel_pos_buckets(c.rel_pos), t, st)
+            done(rn)
+        # d in_proj_weight = dqkv^T . x', d in_proj_bias = column sums of dqkv;  dx' = dqkv . in_proj_weight
+        self._lin_dw(g["dqkv"], xin, G[mod + ".in_proj_weight"], G[mod + ".in_proj_bias"], R, 3 * C, C, t, ks, ws)
+        done(mod)
+        self._lin_dx(g["dqkv"], P[mod + ".in_proj_weight"], g["winT"], dxin, R, 3 * C, C)
+
+    def _ffn_fwd(self, g, P, fn, x, f, u, keep, drop, sid, R, C, D):
+        """f = ffn(x) of module fn, both products and the activation in one launch; u for a backward (and wherever the hidden mask is
+        drawn); sid: the hidden activation's stream"""
+        eng, lib = self.eng, self.eng.lib
+        sfx, opts = ("_drop", (drop, L.ptr(g["rng"]), sid)) if drop else ("", ())
+        eng._k("sed_ffn_fwd" + sfx, getattr(lib, "sed_ffn_fwd" + sfx), eng.dt, self.act, L.ptr(x), L.ptr(P[fn + ".linear1.weight"]),
+               L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(f),
+               L.ptr(u) if keep or drop else None, R, C, D, *opts, _stream())
+
+    def _ffn_backward(self, p, P, G, fn, ga, xin, u, sid, dxin, drop, ks, ws, done):
+        """Backward of the FFN module fn: ga = the gradient of its output (dres, or m s dres under dropout), xin its input, u its kept
+        hidden pre-activation, sid the hidden activation's stream -> its parameters' gradients and dxin, the gradient of xin through
+        the module (no residual)."""
+        eng, lib, st, g = self.eng, self.eng.lib, _stream(), p.sa
+        t, C, R, D = p.t_out, eng.cfg[-1][0], p.sa["R"], self.cfg.ffn
+        w1, w2 = fn + ".linear1.weight", fn + ".linear2.weight"
+        # da = ga . w2, then a = act(u) and du = da act'(u) (du over da; under dropout a = m s act(u), du = da m s act'(u))
+        self._lin_dx(ga, P[w2], g["w2T"], g["fda"], R, C, D)
+        if drop:
+            eng._k("sed_ffn_act_bwd_drop", lib.sed_ffn_act_bwd_drop, self.act, L.ptr(u), L.ptr(g["fda"]), L.ptr(g["ffa"]),
+                   L.ptr(g["fda"]), R, D, drop, L.ptr(g["rng"]), sid, st)
+        else:
+            eng._k("sed_ffn_act_bwd", lib.sed_ffn_act_bwd, self.act, L.ptr(u), L.ptr(g["fda"]), L.ptr(g["ffa"]),
+                   L.ptr(g["fda"]), R * D, st)
+        # d linear2.weight = ga^T . a, d linear1.weight = du^T . x, the biases' gradients their column sums;  dx = du . w1
+        self._lin_dw(ga, g["ffa"], G[w2], G[fn + ".linear2.bias"], R, C, D, t, ks, ws)
+        self._lin_dw(g["fda"], xin, G[w1], G[fn + ".linear1.bias"], R, D, C, t, ks, ws)
+        done(fn)
+        self._lin_dx(g["fda"], P[w1], g["w1T"], dxin, R, D, C)
+
     def _forward(self, p, P, feat, keep, training, update_running_stats):
         c, eng, lib, dt, st, g = self.cfg, self.eng, self.eng.lib, self.eng.dt, _stream(), p.sa
-        Hh, D = c.heads, c.ffn
+        D = c.ffn
         B, t = p.B, p.t_out
         C = eng.cfg[-1][0]
         R = g["R"]
@@ -778,14 +843,7 @@ class SaHead(_Head):
         xin = g["m"]
         for l, ly in enumerate(g["layers"]):
             an, nn_, fn, fnn = c.layer_names(l)
-            eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(xin), C, L.ptr(P[an + ".in_proj_weight"]), C, L.ptr(P[an + ".in_proj_bias"]),
-                   L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
-            if c.rel_pos is not None:
-                eng._k("sed_relpos_expand", lib.sed_relpos_expand, L.ptr(P[c.rel_name(l) + ".weight"]), L.ptr(g["rel_map"]),
-                       L.ptr(ly["rel"]), Hh, c.rel_pos_buckets(c.rel_pos), t, st)
-            self._mhsa_fwd(g, ly, l, keep, drop)
-            eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["ctx"]), C, L.ptr(P[an + ".out_proj.weight"]), C,
-                   L.ptr(P[an + ".out_proj.bias"]), L.ptr(ly["a"]), C, R, C, C, 1, None, st)
+            self._attn_forward(p, P, l, ly, an, xin, keep, drop)
             self._add_ln_fwd(g, xin, ly["a"], P[nn_ + ".weight"], P[nn_ + ".bias"], ly["h"], ly["stats"] if keep else None, R, C,
                              8 * l + 1 if drop else None)
             xin = ly["h"]
@@ -793,11 +851,7 @@ class SaHead(_Head):
                 self._conv_forward(p, P, l, ly, keep, training, update_running_stats)
                 xin = ly["hc"]
             if D:
-                # h2 = LayerNorm(h + ffn(h)): both products and the activation in one launch; u only for a backward
-                sfx, opts = ("_drop", (drop, L.ptr(g["rng"]), 8 * l + 3)) if drop else ("", ())
-                eng._k("sed_ffn_fwd" + sfx, getattr(lib, "sed_ffn_fwd" + sfx), dt, self.act, L.ptr(xin), L.ptr(P[fn + ".linear1.weight"]),
-                       L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(ly["f"]),
-                       L.ptr(ly["u"]) if keep or drop else None, R, C, D, *opts, st)
+                self._ffn_fwd(g, P, fn, xin, ly["f"], ly["u"], keep, drop, 8 * l + 3, R, C, D)       # h2 = LayerNorm(h + ffn(h))
                 self._add_ln_fwd(g, xin, ly["f"], P[fnn + ".weight"], P[fnn + ".bias"], ly["h2"], ly["stats2"] if keep else None, R, C,
                                  8 * l + 4 if drop else None)
                 xin = ly["h2"]
@@ -807,8 +861,7 @@ class SaHead(_Head):
 
     def _backward(self, p, P, G, dfeat, done):
         c, eng, lib, st, g = self.cfg, self.eng, self.eng.lib, _stream(), p.sa
-        Hh, D = c.heads, c.ffn
-        t = p.t_out
+        D = c.ffn
         C = eng.cfg[-1][0]
         R = g["R"]
         ks = max(1, min(g["ksplit"], R // 256))
@@ -823,65 +876,26 @@ class SaHead(_Head):
             an, nn_, fn, fnn = c.layer_names(l)
             fin = ly["hc"] if c.conv_kernel else ly["h"]        # the FFN sub-layer's input
             if D:
-                w1, w2 = fn + ".linear1.weight", fn + ".linear2.weight"
                 ga = self._add_ln_bwd(g, gcur, fin, ly["f"], P[fnn + ".weight"], ly["stats2"], G[fnn + ".weight"], G[fnn + ".bias"], R, C,
                                       8 * l + 4 if drop else None)
                 done(fnn)
-                # da = ga . w2 (ga: the gradient of the FFN's output -- dres, or m s dres under dropout), then a = act(u) and
-                # du = da act'(u) (du over da; under dropout a = m s act(u), du = da m s act'(u))
-                self._lin_dx(ga, P[w2], g["w2T"], g["fda"], R, C, D)
-                if drop:
-                    eng._k("sed_ffn_act_bwd_drop", lib.sed_ffn_act_bwd_drop, self.act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
-                           L.ptr(g["fda"]), R, D, drop, L.ptr(g["rng"]), 8 * l + 3, st)
-                else:
-                    eng._k("sed_ffn_act_bwd", lib.sed_ffn_act_bwd, self.act, L.ptr(ly["u"]), L.ptr(g["fda"]), L.ptr(g["ffa"]),
-                           L.ptr(g["fda"]), R * D, st)
-                # d linear2.weight = ga^T . a, d linear1.weight = du^T . h, the biases' gradients their column sums
-                self._lin_dw(ga, g["ffa"], G[w2], G[fn + ".linear2.bias"], R, C, D, t, ks, ws)
-                self._lin_dw(g["fda"], fin, G[w1], G[fn + ".linear1.bias"], R, D, C, t, ks, ws)
-                done(fn)
-                # dh = du . w1 + dres (the residual branch)
-                self._lin_dx(g["fda"], P[w1], g["w1T"], g["dh1"], R, D, C)
-                g["dh1"].add_(g["dres"])
+                self._ffn_backward(p, P, G, fn, ga, fin, ly["u"], 8 * l + 3, g["dh1"], drop, ks, ws, done)
+                g["dh1"].add_(g["dres"])                 # the residual branch
                 gcur = g["dh1"]
             if c.conv_kernel:
                 gcur = self._conv_backward(p, P, G, l, ly, gcur, not p.trained, ks, ws, done)
             ga = self._add_ln_bwd(g, gcur, xin, ly["a"], P[nn_ + ".weight"], ly["stats"], G[nn_ + ".weight"], G[nn_ + ".bias"], R, C,
                                   8 * l + 1 if drop else None)
             done(nn_)
-            # d out_proj.weight = ga^T . ctx, d out_proj.bias = column sums of ga (ga: the gradient of a -- dres, or m s dres under dropout)
-            self._lin_dw(ga, ly["ctx"], G[an + ".out_proj.weight"], G[an + ".out_proj.bias"], R, C, C, t, ks, ws)
-            # dctx = ga . out_proj.weight
-            self._lin_dx(ga, P[an + ".out_proj.weight"], g["woT"], g["dctx"], R, C, C)
-            self._mhsa_bwd(g, ly, l, drop)
-            if c.rel_pos is not None:
-                # ly["rel"] is the table this layer's forward read (the weights do not change between a step's forward and backward)
-                rn = c.rel_name(l)
-                eng._k("sed_relpos_fold", lib.sed_relpos_fold, L.ptr(ly["drel"]), L.ptr(g["rel_map"]), L.ptr(G[rn + ".weight"]), Hh,
-                       c.rel_pos_buckets(c.rel_pos), t, st)
-                done(rn)
-            # d in_proj_weight = dqkv^T . x', d in_proj_bias = column sums of dqkv
-            self._lin_dw(g["dqkv"], xin, G[an + ".in_proj_weight"], G[an + ".in_proj_bias"], R, 3 * C, C, t, ks, ws)
-            done(an)
-            # dm = dqkv . in_proj_weight + dres (the residual branch): the gradient of the layer's input
-            self._lin_dx(g["dqkv"], P[an + ".in_proj_weight"], g["winT"], g["dm"], R, 3 * C, C)
-            g["dm"].add_(g["dres"])
+            self._attn_backward(p, P, G, l, ly, an, ga, xin, g["dm"], drop, ks, ws, done)
+            g["dm"].add_(g["dres"])                      # the residual branch: the gradient of the layer's input
             gcur = g["dm"]
         # back through the mel mean
         eng._k("sed_mel_mean_bwd", lib.sed_mel_mean_bwd, eng.dt, L.ptr(g["dm"]), L.ptr(dfeat), R, p.w_out, C, pad32(C), st)
 
-    # ---- norm_first: the pre-LN chain (plan: _plan_chain) ------------------------------------------------------------------------------
-    def _ffn_fwd(self, g, P, fn, x, f, u, keep, drop, sid, R, C, D):
-        """f = ffn(x) of module fn; u for a backward (and wherever the hidden mask is drawn); sid: the hidden activation's stream"""
-        eng, lib = self.eng, self.eng.lib
-        sfx, opts = ("_drop", (drop, L.ptr(g["rng"]), sid)) if drop else ("", ())
-        eng._k("sed_ffn_fwd" + sfx, getattr(lib, "sed_ffn_fwd" + sfx), eng.dt, self.act, L.ptr(x), L.ptr(P[fn + ".linear1.weight"]),
-               L.ptr(P[fn + ".linear1.bias"]), L.ptr(P[fn + ".linear2.weight"]), L.ptr(P[fn + ".linear2.bias"]), L.ptr(f),
-               L.ptr(u) if keep or drop else None, R, C, D, *opts, _stream())
-
     def _forward_pre(self, p, P, keep, training, update_running_stats, drop):
-        c, eng, lib, dt, st, g = self.cfg, self.eng, self.eng.lib, self.eng.dt, _stream(), p.sa
-        Hh, D, t, C, R = c.heads, c.ffn, p.t_out, self.eng.cfg[-1][0], p.sa["R"]
+        c, eng, lib, st, g = self.cfg, self.eng, self.eng.lib, _stream(), p.sa
+        D, C, R = c.ffn, self.eng.cfg[-1][0], p.sa["R"]
         rng = L.ptr(g["rng"]) if drop else None
         for n in g["chain"]:
             # the previous sub-layer's add (where there is one) and this node's LayerNorm
@@ -893,14 +907,7 @@ class SaHead(_Head):
                 continue
             kind, mod, l, ly = n["sub"]
             if kind == "attn":
-                eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(n["y"]), C, L.ptr(P[mod + ".in_proj_weight"]), C,
-                       L.ptr(P[mod + ".in_proj_bias"]), L.ptr(ly["qkv"]), 3 * C, R, 3 * C, C, 1, None, st)
-                if c.rel_pos is not None:
-                    eng._k("sed_relpos_expand", lib.sed_relpos_expand, L.ptr(P[c.rel_name(l) + ".weight"]), L.ptr(g["rel_map"]),
-                           L.ptr(ly["rel"]), Hh, c.rel_pos_buckets(c.rel_pos), t, st)
-                self._mhsa_fwd(g, ly, l, keep, drop)
-                eng._k("sed_gemm_nt", lib.sed_gemm_nt, dt, L.ptr(ly["ctx"]), C, L.ptr(P[mod + ".out_proj.weight"]), C,
-                       L.ptr(P[mod + ".out_proj.bias"]), L.ptr(ly["a"]), C, R, C, C, 1, None, st)
+                self._attn_forward(p, P, l, ly, mod, n["y"], keep, drop)
             elif kind == "conv":
                 self._conv_inner_forward(p, P, l, ly, n["y"], keep, training, update_running_stats)
             elif kind == "ffn":
@@ -916,7 +923,7 @@ class SaHead(_Head):
         stream); gy: the gradient of the current node's LayerNorm output.  A node's launch adds its LayerNorm's input gradient to gs
         in place (dxsum aliases dres_in) and leaves the gradient of the sub-layer output that was added in front of it (ga)."""
         c, eng, lib, st, g = self.cfg, self.eng, self.eng.lib, _stream(), p.sa
-        Hh, D, t, C, R = c.heads, c.ffn, p.t_out, self.eng.cfg[-1][0], p.sa["R"]
+        C, R = self.eng.cfg[-1][0], p.sa["R"]
         rng = L.ptr(g["rng"]) if drop else None
         gy, gs, flip = g["dh"], None, 0
         for n in reversed(g["chain"]):
@@ -924,33 +931,12 @@ class SaHead(_Head):
                 # the sub-layer behind this node: ga (the gradient of its output) -> its parameters' gradients and gy = g["dn"]
                 kind, mod, l, ly = n["sub"]
                 if kind == "attn":
-                    self._lin_dw(ga, ly["ctx"], G[mod + ".out_proj.weight"], G[mod + ".out_proj.bias"], R, C, C, t, ks, ws)
-                    self._lin_dx(ga, P[mod + ".out_proj.weight"], g["woT"], g["dctx"], R, C, C)
-                    self._mhsa_bwd(g, ly, l, drop)
-                    if c.rel_pos is not None:
-                        rn = c.rel_name(l)
-                        eng._k("sed_relpos_fold", lib.sed_relpos_fold, L.ptr(ly["drel"]), L.ptr(g["rel_map"]), L.ptr(G[rn + ".weight"]), Hh,
-                               c.rel_pos_buckets(c.rel_pos), t, st)
-                        done(rn)
-                    self._lin_dw(g["dqkv"], n["y"], G[mod + ".in_proj_weight"], G[mod + ".in_proj_bias"], R, 3 * C, C, t, ks, ws)
-                    done(mod)
-                    self._lin_dx(g["dqkv"], P[mod + ".in_proj_weight"], g["winT"], g["dn"], R, 3 * C, C)
+                    self._attn_backward(p, P, G, l, ly, mod, ga, n["y"], g["dn"], drop, ks, ws, done)
                 elif kind == "conv":
                     self._conv_inner_backward(p, P, G, l, ly, ga, n["y"], g["dn"], not p.trained, ks, ws, done)
                 else:
                     u, hid = (ly["u"], 8 * l + 3) if kind == "ffn" else (ly["mu"], 8 * l + 5)
-                    w1, w2 = mod + ".linear1.weight", mod + ".linear2.weight"
-                    self._lin_dx(ga, P[w2], g["w2T"], g["fda"], R, C, D)
-                    if drop:
-                        eng._k("sed_ffn_act_bwd_drop", lib.sed_ffn_act_bwd_drop, self.act, L.ptr(u), L.ptr(g["fda"]), L.ptr(g["ffa"]),
-                               L.ptr(g["fda"]), R, D, drop, rng, hid, st)
-                    else:
-                        eng._k("sed_ffn_act_bwd", lib.sed_ffn_act_bwd, self.act, L.ptr(u), L.ptr(g["fda"]), L.ptr(g["ffa"]),
-                               L.ptr(g["fda"]), R * D, st)
-                    self._lin_dw(ga, g["ffa"], G[w2], G[mod + ".linear2.bias"], R, C, D, t, ks, ws)
-                    self._lin_dw(g["fda"], n["y"], G[w1], G[mod + ".linear1.bias"], R, D, C, t, ks, ws)
-                    done(mod)
-                    self._lin_dx(g["fda"], P[w1], g["w1T"], g["dn"], R, D, C)
+                    self._ffn_backward(p, P, G, mod, ga, n["y"], u, hid, g["dn"], drop, ks, ws, done)
                 gy = g["dn"]
             else:
                 # a closing norm: its output is a new stream, whose gradient is what has arrived on it (the head's for the last one)

@@ -541,7 +541,7 @@ class Csa_AvgPooling(Cnn_AvgPooling):
     The closing norm exists on every layer with sa_macaron (the Conformer block of Gulati et al. 2020: two half-weighted FFNs around
     attention and convolution) and on the last layer only without it, which is torch.nn.TransformerEncoder(TransformerEncoderLayer(C,
     sa_heads, D, norm_first=True), N, norm=LayerNorm(C)); event_fc / att_fc read the last closing norm's output.  One launch forms a
-    sub-layer's residual add and the next LayerNorm (sed_resid_layernorm_fwd / _bwd, csrc/sed_mhsa.hip); the attention core, the
+    sub-layer's residual add and the next LayerNorm (sed_resid_layernorm_fwd / _bwd, csrc/sed_layernorm.hip); the attention core, the
     convolution module's inner arithmetic and the FFN kernel are the post-LN ones.  Names: layer 0 bare, layer l >= 1 with _l{l}.
     Registration order per layer: ffn_mac_norm, ffn_mac, attn_norm, attn, rel_pos, conv_norm, convm, ffn_norm, ffn, out_norm -- each
     norm before its sub-layer, because its gradient completes after the sub-layer's; the backward completes the groups in exactly the

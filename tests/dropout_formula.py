@@ -1,4 +1,4 @@
-"""The dropout of the self-attention head (csrc/philox.h and the _drop kernels of csrc/sed_mhsa.hip / sed_ffn.hip) as plain numpy: the
+"""The dropout of the self-attention head (csrc/philox.h and the _drop kernels of csrc/sed_mhsa.hip / sed_layernorm.hip / sed_ffn.hip) as plain numpy: the
 counter-based generator, the two mask layouts, and the float64 definitions of the three masked operations with their gates.  The
 kernels are tested against this (tests/test_gpu_dropout.py, tests/test_gpu_sa_dropout.py); this file is itself checked against
 torch autograd and the undropped formula modules on the host (tests/test_dropout_host.py).

@@ -1,4 +1,4 @@
-"""The pre-LN residual LayerNorm of the self-attention head (sed_resid_layernorm_fwd / sed_resid_layernorm_bwd, csrc/sed_mhsa.hip) and the
+"""The pre-LN residual LayerNorm of the self-attention head (sed_resid_layernorm_fwd / sed_resid_layernorm_bwd, csrc/sed_layernorm.hip) and the
 pre-LN / macaron (Conformer) encoder stack of Csa_AvgPooling(sa_norm_first=True) as plain numpy: the float64 definition of the two
 kernels, forward and backward, of a layer and of a stack, and the gates.  The kernels are tested against this
 (tests/test_gpu_preln.py, tests/test_gpu_sa_preln.py); this file is itself checked against torch.nn.TransformerEncoder(

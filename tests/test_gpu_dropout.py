@@ -1,5 +1,5 @@
 """GPU: the dropout twins of the self-attention head through the C ABI (csrc/philox.h, sed_dropout.hip, the DROP instantiations of
-sed_mhsa.hip / sed_ffn.hip), per element against the float64 definitions of tests/dropout_formula.py within the gates derived in
+sed_mhsa.hip / sed_layernorm.hip / sed_ffn.hip), per element against the float64 definitions of tests/dropout_formula.py within the gates derived in
 that file's docstring, at p in {0.1, 0.5}, SED_F32 and SED_BF16.
 
   mask       sed_dropout_mask equals the numpy masks cell for cell (rows and attention), and a probe reads the mask out of the fused

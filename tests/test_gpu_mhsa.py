@@ -1,4 +1,4 @@
-"""GPU: the self-attention core and the residual LayerNorm of csrc/sed_mhsa.hip through the C ABI, per element against the float64
+"""GPU: the self-attention core of csrc/sed_mhsa.hip and the residual LayerNorm of csrc/sed_layernorm.hip through the C ABI, per element against the float64
 definition in tests/mhsa_formula.py, within the gates derived in that file's docstring (SED_F32 and SED_BF16).
 
 Shapes: B = 2 different clips (leakage between clips shows), t on, under and over the tile edges of the kernels (a wave owns 32

@@ -1,4 +1,4 @@
-"""GPU: sed_resid_layernorm_fwd / sed_resid_layernorm_bwd (csrc/sed_mhsa.hip) through the C ABI, per element against the float64
+"""GPU: sed_resid_layernorm_fwd / sed_resid_layernorm_bwd (csrc/sed_layernorm.hip) through the C ABI, per element against the float64
 definitions of tests/preln_formula.py within the gates derived in that file's docstring.
 
   shapes     rows in {1, 3, 4, 5, 63, 64, 65, 257} (four rows per workgroup, 64-row partial chunks) x C in {4, 60, 64, 68, 128, 260, 512,
@@ -8,6 +8,9 @@ definitions of tests/preln_formula.py within the gates derived in that file's do
   arguments  a NULL / given; dres_in NULL / given / aliased to dxsum; da NULL / given; stats NULL gives the same y bits
   bit-equal  s = 1, p = 0: y and stats are sed_add_layernorm_fwd(x, a)'s and xsum the IEEE fp32 sum; s = 1, p > 0: sed_add_layernorm_fwd_drop's;
              dres_in NULL, s = 1: dxsum, dgamma, dbeta are sed_add_layernorm_bwd's on (xsum, zeros)
+             (not asserted: with da given and p = 0.3 on the forward's xsum and stats, dgamma and dbeta are sed_add_layernorm_bwd_drop(x, a)'s
+             bits at every BIT_CASES shape, and so are dxsum / dres and da up to C = 512; at C = 516 they differ in the last place in
+             columns 512 ... 515, the columns behind the register mask, where the two instantiations' compiled code rounds differently)
   dropout    the keep cells are the ones sed_dropout_mask reports (and dropout_formula's)
   everywhere repeats give the same bits, inputs lie between NaN regions and outputs between canaries, refusals leave the outputs untouched
 Run with -s for the worst error / gate of every check."""

@@ -1,5 +1,5 @@
 """GPU: Csa_AvgPooling(sa_norm_first=True[, sa_macaron=True]) -- pre-LN layers, the macaron half-step FFNs and the closing norms
-(sed_resid_layernorm_fwd / _bwd, csrc/sed_mhsa.hip) -- through the model, the engine, FusedTrainer and infer.py, on the tiny configuration
+(sed_resid_layernorm_fwd / _bwd, csrc/sed_layernorm.hip) -- through the model, the engine, FusedTrainer and infer.py, on the tiny configuration
 of tests/test_gpu_sa_encoder.py (C = 32, one head, t = 10 frames per clip).
 
 fp32 parity as in that file: the conv-stack output of a head='none' engine on the same parameters is fed to the float64 oracle

@@ -1,4 +1,4 @@
-"""Times of the self-attention head's dropout twins (csrc/philox.h; the DROP instantiations of csrc/sed_mhsa.hip / sed_ffn.hip):
+"""Times of the self-attention head's dropout twins (csrc/philox.h; the DROP instantiations of csrc/sed_mhsa.hip / sed_layernorm.hip / sed_ffn.hip):
 every _drop launch beside its plain twin of the same build, and the train step with and without dropout.
 
   python tools/dropout_time.py [--reps 20] [--warmup 3] [--out profiles/dropout_time.json]

@@ -1,4 +1,4 @@
-"""Times of the pre-LN residual LayerNorm pair (sed_resid_layernorm_fwd / _bwd, csrc/sed_mhsa.hip) against the composed route, and the
+"""Times of the pre-LN residual LayerNorm pair (sed_resid_layernorm_fwd / _bwd, csrc/sed_layernorm.hip) against the composed route, and the
 train step of the self-attention head post-LN against pre-LN and macaron.
 
   python tools/sa_preln_time.py [--reps 20] [--warmup 3] [--out profiles/sa_preln_time.json]
