@@ -400,6 +400,49 @@ int sed_adam_step_ex_dev(float* p, const float* g, float* m, float* v, float* vm
                          int* step, float beta1, float beta2, float eps, float grad_scale, float lr_decay,
                          int decay_every, float weight_decay, int decoupled, const float* coef, void* stream);
 
+/* ---- the grouped step: parameter groups, frozen groups and a learning-rate schedule evaluated on the device (csrc/sed_optim.hip)
+ * The flat buffers are the ones above (n a multiple of 4: FlatParams pads every parameter's start to 4 floats, so an aligned float4
+ * belongs to one parameter).  Two tables in device memory, 16-byte aligned:
+ *   tiles  int32 [nt][4] = {start4, count4, group, 0}: units of 4 floats, 1 <= count4 <= SED_OPT_TILE4, ascending and disjoint,
+ *                          start4 + count4 <= n / 4, 0 <= group < ng, no tile across a parameter boundary
+ *   groups float [ng][4] = {lr_scale, weight_decay, frozen (0 / 1), 0}, 1 <= ng <= SED_OPT_MAX_GROUPS
+ * PRECONDITION: the library cannot read the tile table on the host; the caller validates it (train.py's build_tiles does).  The
+ * kernels clip a tile to the buffer and skip a group index outside the table, so a damaged table cannot store out of bounds, but
+ * what it computes is then undefined.
+ * Schedule, all fp64, s = the 1-based step, W = warmup, w(s) = min(1, s / W) for W > 0 else 1, u = clamp((s - W)/(total - W), 0, 1):
+ *   SED_SCHED_CONST    d = 1
+ *   SED_SCHED_STEP     d = gamma^floor((s - 1) / every)
+ *   SED_SCHED_COSINE   d = floor + (1 - floor) * (1 + cos(pi u)) / 2
+ *   SED_SCHED_LINEAR   d = floor + (1 - floor) * (1 - u)
+ *   SED_SCHED_INVSQRT  d = sqrt(max(W, 1) / max(s, W, 1))
+ *   lr(s) = base_lr * w(s) * d(s)
+ * sed_adam_groups_step makes two launches.  The first (one workgroup, one thread per group) does s = ++*step and writes
+ *   hyper[0] = (float)lr(s), hyper[1] = (float)(1 / sqrt(1 - beta2^s)), hyper[2] = (float)lr(s + 1)        (hyper: 3 floats)
+ *   gh[g]    = {(float)(lr(s) scale_g / (1 - beta1^s)), (float)(1 - lr(s) scale_g wd_g), 0, 0}             (gh: ng x 4 floats)
+ * the second runs one workgroup of 256 threads per tile with sed_adam_step_ex's element arithmetic: a tile of a frozen group
+ * returns at once (p, m, v, vmax keep their bits whatever g holds); wd_g == 0 runs the expressions without decay (no 0 * p term);
+ * else L2 (decoupled == 0) or AdamW decay.  vmax NULL = amsgrad off; coef as in sed_adam_step_ex.  There is no host-scalar twin:
+ * eager and captured steps run these two kernels.  With one group {1, wd, 0}, SED_SCHED_CONST and base_lr an fp32 value the
+ * results are the bits of sed_adam_step_ex_dev(decay_every = 0). */
+#define SED_OPT_TILE4 1024
+#define SED_OPT_MAX_GROUPS 64
+#define SED_SCHED_CONST 0
+#define SED_SCHED_STEP 1
+#define SED_SCHED_COSINE 2
+#define SED_SCHED_LINEAR 3
+#define SED_SCHED_INVSQRT 4
+int sed_opt_tile4(void);
+int sed_adam_groups_step(float* p, const float* g, float* m, float* v, float* vmax, size_t n, const int* tiles, int nt,
+                         const float* groups, int ng, float* gh, float* hyper, int* step, double base_lr, int sched_kind,
+                         int warmup, int total, int every, double gamma, double floor_lr, float beta1, float beta2, float eps,
+                         float grad_scale, int decoupled, const float* coef, void* stream);
+/* sed_grad_norm over the tiles of the non-frozen groups only (clip_grad_norm_ sees only parameters that have gradients): one
+ * workgroup per tile leaves one fp64 partial through the same fixed LDS tree (a frozen tile writes 0.0), one workgroup folds the nt
+ * partials in a fixed order; out as sed_grad_norm's.  partial: nt doubles.  No atomics; two runs give the same bits.  The group
+ * index of a tile must lie below the number of rows of `groups` (at most SED_OPT_MAX_GROUPS). */
+int sed_grad_norm_groups(const float* g, size_t n, const int* tiles, int nt, const float* groups, float grad_scale,
+                         float max_norm, double* partial, float* out, void* stream);
+
 /* ---- log-mel front-end ---------------------------------------------------------------------
  * multichannel_stft + multichannel_complex_to_log_mel (+ transform) for one channel batch
  * (dataset/spectogram/preprocess.py:21-45, spectograms_dataset.py:104-108):

@@ -14,6 +14,6 @@ from .models.frontend_layers import PCEN  # noqa: F401
 from .m5_engine import M5Engine  # noqa: F401
 from .utils.common import WeakBCE, WeightedBCE  # noqa: F401
 from . import train  # noqa: F401,E402
-from .train import FusedTrainer, FusedAdamAmsgrad  # noqa: F401,E402
+from .train import FusedTrainer, FusedAdamAmsgrad, LRSchedule, lr_at, no_decay_groups  # noqa: F401,E402
 
 __all__ = ["M5", "PCEN", "Cnn_AvgPooling", "Crnn_AvgPooling", "Csa_AvgPooling", "ConvBlock", "WeightedBCE", "WeakBCE", "CnnEngine", "interpolate", "init_layer", "init_bn"]

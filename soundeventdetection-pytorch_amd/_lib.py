@@ -15,6 +15,8 @@ PCM_I16, PCM_I32, PCM_F32 = 0, 1, 2
 POOL_MAX, POOL_MEAN, POOL_LINEAR, POOL_EXP = 0, 1, 2, 3
 POOL_MODES = {"max": POOL_MAX, "mean": POOL_MEAN, "linear": POOL_LINEAR, "exp": POOL_EXP}
 CRIT_BCE, CRIT_MSE = 0, 1
+OPT_TILE4, OPT_MAX_GROUPS = 1024, 64     # SED_OPT_TILE4 / SED_OPT_MAX_GROUPS: the grouped optimizer step's tile size and group limit
+SCHED_KINDS = {"const": 0, "step": 1, "cosine": 2, "linear": 3, "invsqrt": 4}       # SED_SCHED_*
 WIN_UNBOUNDED = 0x7FFFFFFF          # SED_WIN_UNBOUNDED: a side of sed_mhsa_fwd_win / _bwd_win that reaches the clip's end
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -122,6 +124,10 @@ PROTOTYPES = {
     "sed_grad_norm": (_I, [_P, _Z, _F, _F, _P, _I, _P, _P]),
     "sed_adam_step_ex": (_I, [_P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _I, _F, _F, _I, _P, _P]),
     "sed_adam_step_ex_dev": (_I, [_P, _P, _P, _P, _P, _Z, _P, _P, _F, _F, _F, _F, _F, _I, _F, _I, _P, _P]),
+    "sed_opt_tile4": (_I, []),
+    "sed_adam_groups_step": (_I, [_P, _P, _P, _P, _P, _Z, _P, _I, _P, _I, _P, _P, _P, _D, _I, _I, _I, _I, _D, _D, _F, _F, _F, _F, _I,
+                                  _P, _P]),
+    "sed_grad_norm_groups": (_I, [_P, _Z, _P, _I, _P, _F, _F, _P, _P, _P]),
     "sed_logmel_ws_bytes": (_Z, [_I, _I, _I, _I]),
     "sed_logmel_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sed_stft_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),

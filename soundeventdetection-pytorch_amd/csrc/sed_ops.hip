@@ -2,6 +2,7 @@
 // norm / clip factor, weight decay, AdamW) and layout utilities for gfx950.  All HBM-bound: 16-byte vector accesses, fp32 math, deterministic
 // two-stage reductions (per-workgroup partials + fixed-order finalise), no float atomics.
 #include "common.h"
+#include "adam_common.h"
 
 #include <math.h>
 #include <algorithm>
@@ -1196,17 +1197,7 @@ static inline int grad_norm_nparts(size_t n) {
     return (int)(g < 1 ? 1 : (g > SED_GNORM_MAX_PARTS ? SED_GNORM_MAX_PARTS : g));
 }
 
-__device__ __forceinline__ double block256_sum_f64(double t, double* sh) {
-    sh[threadIdx.x] = t;
-    __syncthreads();
-#pragma unroll
-    for (int s = 128; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
+// (block256_sum_f64, the fixed LDS tree: adam_common.h)
 __global__ __launch_bounds__(256) void grad_sqsum_kernel(const float* __restrict__ g, size_t n, float grad_scale,
                                                          double* __restrict__ partial) {
     __shared__ double sh[256];
@@ -1270,29 +1261,7 @@ extern "C" int sed_absmax(const float* x, size_t n, float* out, void* stream) {
 // arithmetic IS the existing kernels' -- whatever the compiler contracts -- and the results are the same bits.
 //   WD 0: none   1: L2, gr += wd * p (torch.optim.Adam(weight_decay=))   2: decoupled, p *= 1 - lr * wd first (torch.optim.AdamW)
 // ---------------------------------------------------------------------------------------------
-// The decay terms are new arithmetic, and the file is compiled with -ffp-contract=fast: left to the compiler, gr + wd * p becomes
-// fma(g, gse, wd * p) in the vectorised body and fma(wd, p, g * gse) in the scalar one, and the host and device forms disagree in
-// the last bit of m.  rounded() hands a value through an empty asm, so it is an fp32 number of its own that nothing fuses across:
-// the decay terms round where torch's do, in every form alike.  The WD 0 path does not use it.
-__device__ __forceinline__ float rounded(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-
-template <bool AMS, int WD>
-__device__ __forceinline__ void adam_ex_elem(float& p, const float g, float& m, float& v, float& x, const float gse, const float wd,
-                                             const float decay, const float one_minus_b1, const float b2, const float one_minus_b2,
-                                             const float eps, const float step_size, const float inv_sqrt_bc2) {
-    float gr = g * gse;
-    if (WD == 1) gr = rounded(gr) + rounded(wd * p);                   // grad.add(param, alpha=wd): product and sum each rounded
-    if (WD == 2) p = rounded(p * decay);                               // param.mul_(1 - lr * wd), rounded before the update
-    m = m + one_minus_b1 * (gr - m);
-    v = v * b2 + (one_minus_b2 * gr) * gr;
-    if (AMS) x = fmaxf(x, v);
-    const float denom = sqrtf(AMS ? x : v) * inv_sqrt_bc2 + eps;
-    p = p - step_size * (m / denom);
-}
-
+// rounded() and adam_ex_elem, the per-element expressions: adam_common.h, shared with the grouped step (sed_optim.hip).
 template <bool AMS, int WD>
 __global__ __launch_bounds__(256) void adam_ex_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                       float* __restrict__ v, float* __restrict__ vmax, size_t n, float one_minus_b1,

@@ -211,6 +211,23 @@ class OptimizerExtMixin:
                 float(grad_scale), float(lr_decay), int(decay_every), float(weight_decay), int(bool(decoupled)), L.ptr(coef),
                 _stream())
 
+    def grad_norm_groups(self, flat_g, tiles, groups, partial, out, grad_scale: float = 1.0, max_norm: float = 0.0):
+        """grad_norm() over the tiles of the non-frozen groups (train.py's build_tiles makes the two tables); partial: float64
+        workspace of one element per tile."""
+        self._k("sed_grad_norm_groups", self.lib.sed_grad_norm_groups, L.ptr(flat_g), flat_g.numel(), L.ptr(tiles), tiles.shape[0],
+                L.ptr(groups), float(grad_scale), float(max_norm), L.ptr(partial), L.ptr(out), _stream())
+
+    def adam_groups_step(self, flat_p, flat_g, flat_m, flat_v, flat_vmax, tiles, groups, gh, hyper, step_dev, base_lr: float,
+                         schedule, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8, decoupled: bool = False,
+                         coef=None):
+        """the grouped step (sed_hip.h): the step counter, the schedule's learning rate and every group's scalars stay in device
+        memory, for eager and captured steps alike.  schedule: train.py's LRSchedule; gh: fp32 (NG, 4); hyper: fp32 (>= 3,)"""
+        self._k("sed_adam_groups_step", self.lib.sed_adam_groups_step, L.ptr(flat_p), L.ptr(flat_g), L.ptr(flat_m), L.ptr(flat_v),
+                L.ptr(flat_vmax), flat_p.numel(), L.ptr(tiles), tiles.shape[0], L.ptr(groups), groups.shape[0], L.ptr(gh),
+                L.ptr(hyper), L.ptr(step_dev), float(base_lr), L.SCHED_KINDS[schedule.kind], int(schedule.warmup),
+                int(schedule.total), int(schedule.every), float(schedule.gamma), float(schedule.floor), float(betas[0]),
+                float(betas[1]), float(eps), float(grad_scale), int(bool(decoupled)), L.ptr(coef), _stream())
+
 
 class CnnEngine(OptimizerExtMixin):
     def __init__(self, classes_num: int, model_config: Sequence[Tuple[int, int]], in_channels: int = 1,

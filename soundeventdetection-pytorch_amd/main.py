@@ -237,13 +237,91 @@ def build_pcen_parser():
     return p
 
 
+def build_schedule_parser():
+    """The learning-rate schedule and parameter-group options (this build only): train.py's LRSchedule / param_groups, the kernels
+    of csrc/sed_optim.hip.  In a parser of their own like the event options."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--lr_schedule", default="reference", choices=["reference", "constant", "step", "cosine", "linear", "invsqrt"],
+                   help="this build only: the learning-rate schedule -- reference: lr *= 0.997 every 200 steps, the reference's (the "
+                        "default, today's path); constant; step (the same rule in closed form); cosine / linear decay to --lr_floor x "
+                        "lr at --lr_total_steps; invsqrt (Noam's rule); all of them after --warmup_steps of linear warm-up")
+    p.add_argument("--warmup_steps", type=int, default=0, help="--lr_schedule: steps of linear warm-up from lr / W to lr (0 = none)")
+    p.add_argument("--lr_total_steps", type=int, default=None,
+                   help="--lr_schedule cosine / linear: the step at which the decay reaches the floor (default: --num_train_steps)")
+    p.add_argument("--lr_floor", type=float, default=0.0, help="--lr_schedule cosine / linear: the final rate as a fraction of lr, in [0, 1]")
+    p.add_argument("--no_decay_norm_bias", action="store_true", default=False,
+                   help="this build only: no weight decay on biases and BatchNorm / LayerNorm / PCEN vectors (every parameter with "
+                        "ndim <= 1), the usual AdamW recipe")
+    p.add_argument("--freeze", type=str, default=None, metavar="PREFIX[,PREFIX...]",
+                   help="this build only: parameters under these name prefixes (e.g. conv_blocks) are not updated")
+    p.add_argument("--lr_scale", action="append", default=None, metavar="PREFIX=SCALE",
+                   help="this build only: the learning rate of the parameters under PREFIX is SCALE x lr (repeatable; the first match wins)")
+    return p
+
+
 def build_full_parser():
     """What main() parses: build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser(),
-    build_semi_parser(), build_ranking_parser(), build_psds_parser() and build_pcen_parser() together."""
+    build_semi_parser(), build_ranking_parser(), build_psds_parser(), build_pcen_parser() and build_schedule_parser() together."""
     return argparse.ArgumentParser(description="SED training on MI355X",
                                    parents=[build_parser(), build_event_parser(), build_augment_parser(), build_weak_parser(),
-                                            build_semi_parser(), build_ranking_parser(), build_psds_parser(), build_pcen_parser()],
+                                            build_semi_parser(), build_ranking_parser(), build_psds_parser(), build_pcen_parser(),
+                                            build_schedule_parser()],
                                    conflict_handler="resolve")
+
+
+def parse_lr_scale(items):
+    """--lr_scale PREFIX=SCALE ... -> [(prefix, scale)]; a ValueError for anything else (the range is train.py's to check)"""
+    out = []
+    for it in items or []:
+        pre, sep, val = str(it).rpartition("=")
+        try:
+            out.append((pre.strip(), float(val)))
+        except ValueError:
+            sep = ""
+        if not sep or not pre.strip():
+            raise ValueError(f"--lr_scale takes PREFIX=SCALE, got {it!r}")
+    return out
+
+
+def schedule_options(args, model=None):
+    """train()'s lr_schedule / param_groups of --lr_schedule ... --lr_scale; {} with every flag at its default, the reference's path
+    (a Namespace built by hand may lack any of them).  Group order: --freeze, then --lr_scale in the order given, then the
+    undecayed remainder (--no_decay_norm_bias needs the model's names; without a model those groups are left out: validate_args
+    checks the rest before a model exists)."""
+    from .train import LRSchedule, no_decay_groups, selector_matches
+    kind = getattr(args, "lr_schedule", "reference")
+    sched = None
+    if kind != "reference":
+        total = getattr(args, "lr_total_steps", None)
+        sched = LRSchedule({"constant": "const"}.get(kind, kind), warmup=getattr(args, "warmup_steps", 0),
+                           total=int(getattr(args, "num_train_steps", 0)) if total is None else total, floor=getattr(args, "lr_floor", 0.0))
+    elif getattr(args, "warmup_steps", 0) or getattr(args, "lr_floor", 0.0) or getattr(args, "lr_total_steps", None) is not None:
+        raise ValueError("--warmup_steps / --lr_total_steps / --lr_floor need an --lr_schedule other than reference")
+    groups = []
+    frozen = [v.strip() for v in (getattr(args, "freeze", None) or "").split(",") if v.strip()]
+    if getattr(args, "freeze", None) is not None and not frozen:
+        raise ValueError("--freeze takes one or more name prefixes")
+    if frozen:
+        groups.append({"params": frozen, "frozen": True})
+    # --no_decay_norm_bias splits every --lr_scale group and the remainder in two: the first match wins, so the undecayed half of a
+    # prefix (its biases and norm vectors, by name) goes in front of the prefix itself
+    split = getattr(args, "no_decay_norm_bias", False) and model is not None
+    free = [n for n in no_decay_groups(model)[0]["params"] if not selector_matches(frozen, n)] if split and no_decay_groups(model) else []
+    for pre, scale in parse_lr_scale(getattr(args, "lr_scale", None)):
+        half = [n for n in free if selector_matches([pre], n)]
+        if half:
+            groups.append({"params": half, "lr_scale": scale, "weight_decay": 0.0})
+            free = [n for n in free if n not in half]
+        if not half or any(selector_matches([pre], n) and n not in half for n, _ in model.named_parameters()):
+            groups.append({"params": [pre], "lr_scale": scale})      # (not for a prefix that holds undecayed vectors only)
+    if free:
+        groups.append({"params": free, "weight_decay": 0.0})
+    out = {}
+    if sched is not None:
+        out["lr_schedule"] = sched
+    if groups or getattr(args, "no_decay_norm_bias", False):
+        out["param_groups"] = groups
+    return out
 
 
 def pcen_options(args):
@@ -462,6 +540,10 @@ def validate_args(args):
         raise ValueError(f"--clip_grad_norm must be >= 0 (0 = off), {args.clip_grad_norm} given")
     from .train import check_optimizer_options
     check_optimizer_options(**optimizer_options(args))
+    from .train import resolve_param_groups
+    sched = schedule_options(args)              # the schedule's own checks; the selectors meet the model's names in train()
+    for g in sched.get("param_groups", []):     # each group's scale range, against a stand-in name
+        resolve_param_groups(["_"], [dict(g, params=["_"], frozen=False)])
     for name in ("median_window", "max_gap", "min_event", "collar"):
         if getattr(args, name, 0.0) < 0:
             raise ValueError(f"--{name} must be >= 0 seconds, {getattr(args, name)} given")
@@ -635,7 +717,7 @@ def main(argv=None):
           log_freq=args.log_freq, event_eval=event_eval_options(args, frames_per_second(args)),
           batch_augment=synthetic_batch_augment(args), ranking_eval=ranking_eval_options(args),
           psds_eval=psds_eval_options(args, frames_per_second(args)), **optimizer_options(args),
-          **weak_options(args), **semi_options(args))
+          **weak_options(args), **semi_options(args), **schedule_options(args, model))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

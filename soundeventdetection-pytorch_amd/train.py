@@ -309,6 +309,246 @@ def check_optimizer_options(weight_decay=0.0, decoupled_weight_decay=False, amsg
     return wd, dec, ams, mgn, (wd != 0.0 or not ams or mgn is not None)
 
 
+# ---- learning-rate schedules and parameter groups (this build only; the kernels are csrc/sed_optim.hip) -------------------------
+TILE4 = L.OPT_TILE4              # float4s per tile of the grouped step, SED_OPT_TILE4
+MAX_GROUPS = L.OPT_MAX_GROUPS    # SED_OPT_MAX_GROUPS
+SCHEDULE_KINDS = tuple(L.SCHED_KINDS)
+
+
+def _is_int(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+class LRSchedule:
+    """Linear warm-up over the first `warmup` steps times a decay d(s) of the 1-based step s (lr_at is the definition):
+        const    1
+        step     gamma^floor((s - 1) / every)                          (the reference's rule in closed form: every=200, gamma=0.997)
+        cosine   floor + (1 - floor) (1 + cos(pi u)) / 2,  u = clamp((s - warmup) / (total - warmup), 0, 1)
+        linear   floor + (1 - floor) (1 - u)
+        invsqrt  sqrt(max(warmup, 1) / max(s, warmup, 1))              (Noam's rule after the warm-up)
+    Validated here, on the host, before anything else happens."""
+
+    def __init__(self, kind: str, warmup: int = 0, total: int = 0, every: int = LR_DECAY_FREQ, gamma: float = LR_DECAY,
+                 floor: float = 0.0):
+        if kind not in SCHEDULE_KINDS:
+            raise ValueError(f"lr schedule kind must be one of {', '.join(SCHEDULE_KINDS)} (got {kind!r})")
+        for name, v in (("warmup", warmup), ("total", total), ("every", every)):
+            if not _is_int(v) or not -2 ** 31 < v < 2 ** 31:
+                raise ValueError(f"lr schedule: {name} is a number of steps, an integer (got {v!r})")
+        if warmup < 0:
+            raise ValueError(f"lr schedule: warmup must be >= 0 (got {warmup})")
+        if kind in ("cosine", "linear") and total <= warmup:
+            raise ValueError(f"lr schedule: {kind} needs total > warmup (got total={total}, warmup={warmup})")
+        if kind == "step" and every < 1:
+            raise ValueError(f"lr schedule: step needs every >= 1 (got {every})")
+        g, f = float(gamma), float(floor)
+        if not (0.0 < g < float("inf")):
+            raise ValueError(f"lr schedule: gamma must be finite and > 0 (got {gamma!r})")
+        if not (0.0 <= f <= 1.0):
+            raise ValueError(f"lr schedule: floor must lie in [0, 1] (got {floor!r})")
+        self.kind, self.warmup, self.total, self.every, self.gamma, self.floor = kind, int(warmup), int(total), int(every), g, f
+
+    def as_dict(self) -> dict:
+        return {"kind": self.kind, "warmup": self.warmup, "total": self.total, "every": self.every, "gamma": self.gamma,
+                "floor": self.floor}
+
+    def __repr__(self):
+        return "LRSchedule(" + ", ".join(f"{k}={v!r}" for k, v in self.as_dict().items()) + ")"
+
+
+def lr_at(base_lr: float, s: int, schedule: LRSchedule) -> float:
+    """The learning rate of the 1-based step s in float64: base_lr * w(s) * d(s), w(s) = min(1, s / warmup) (1 without warm-up).
+    The device evaluates the same expressions in double (adam_groups_hyper_kernel); this one is for logging and for the tests."""
+    s = int(s)
+    if s < 1:
+        raise ValueError(f"steps are 1-based (got {s})")
+    W, kind = schedule.warmup, schedule.kind
+    w = min(1.0, s / W) if W > 0 else 1.0
+    d = 1.0
+    if kind == "step":
+        d = schedule.gamma ** float((s - 1) // schedule.every)
+    elif kind in ("cosine", "linear"):
+        u = min(1.0, max(0.0, (s - W) / (schedule.total - W)))
+        shape = 0.5 * (1.0 + math.cos(math.pi * u)) if kind == "cosine" else 1.0 - u
+        d = schedule.floor + (1.0 - schedule.floor) * shape
+    elif kind == "invsqrt":
+        d = math.sqrt(max(W, 1) / max(s, W, 1))
+    return float(base_lr) * w * d
+
+
+def selector_matches(selector, name: str) -> bool:
+    """A selector is a callable name -> bool, or a list of name prefixes matched at dot boundaries: 'conv_blocks.1' takes
+    'conv_blocks.1.conv1.weight' and not 'conv_blocks.10.conv1.weight'."""
+    if callable(selector):
+        return bool(selector(name))
+    for pre in selector:
+        pre = pre.rstrip(".")
+        if name == pre or name.startswith(pre + "."):
+            return True
+    return False
+
+
+def resolve_param_groups(names, param_groups, weight_decay: float = 0.0):
+    """param_groups -> (specs, assignment): specs[g] = (lr_scale, weight_decay, frozen) with g = 0 the unmatched remainder (scale 1,
+    the trainer's decay) and g = i + 1 the i-th given group; assignment[k] = the group of names[k], the first match.  Host only:
+    refuses a selector that matches nothing, a negative or non-finite scale or decay, more than 64 groups and everything frozen."""
+    names = list(names)
+    specs = [(1.0, float(np.float32(weight_decay)), False)]
+    given = list(param_groups or [])
+    if len(given) + 1 > MAX_GROUPS:
+        raise ValueError(f"at most {MAX_GROUPS} parameter groups, the unmatched remainder included (got {len(given)} + 1)")
+    for i, pg in enumerate(given):
+        if not isinstance(pg, dict) or "params" not in pg:
+            raise ValueError(f"param_groups[{i}] must be a dict with a 'params' selector")
+        extra = set(pg) - {"params", "lr_scale", "weight_decay", "frozen"}
+        if extra:
+            raise ValueError(f"param_groups[{i}]: unknown keys {sorted(extra)} (params, lr_scale, weight_decay, frozen)")
+        sel = pg["params"]
+        if not callable(sel) and (isinstance(sel, str) or not all(isinstance(s, str) for s in sel)):
+            raise ValueError(f"param_groups[{i}]: 'params' is a list of name prefixes or a callable name -> bool")
+        scale = float(pg.get("lr_scale", 1.0))
+        wd = pg.get("weight_decay")
+        wd = float(weight_decay) if wd is None else float(wd)
+        if not (0.0 <= scale < float("inf")):
+            raise ValueError(f"param_groups[{i}]: lr_scale must be finite and >= 0 (got {pg.get('lr_scale')!r})")
+        if not (0.0 <= wd < float("inf")):
+            raise ValueError(f"param_groups[{i}]: weight_decay must be finite and >= 0 (got {pg.get('weight_decay')!r})")
+        # (the group table is fp32, as a float argument of the C ABI is: the specs carry the values the device multiplies with)
+        specs.append((float(np.float32(scale)), float(np.float32(wd)), bool(pg.get("frozen", False))))
+    assignment, hit = [], [False] * len(given)
+    for n in names:
+        g = 0
+        for i, pg in enumerate(given):
+            if selector_matches(pg["params"], n):
+                g, hit[i] = i + 1, True
+                break
+        assignment.append(g)
+    # (a group whose every match was taken by an earlier group is as empty as one that matches nothing)
+    for i, h in enumerate(hit):
+        if not h:
+            raise ValueError(f"param_groups[{i}]: the selector matches no parameter that an earlier group has not taken")
+    if all(specs[g][2] for g in assignment):
+        raise ValueError("every parameter is frozen: there is nothing to train")
+    return specs, assignment
+
+
+def no_decay_groups(model) -> list:
+    """The usual AdamW split as a param_groups list: every parameter with ndim <= 1 -- biases, BatchNorm / LayerNorm weight and bias,
+    PCEN's vectors -- gets weight_decay 0; the rest stays in the remainder with the trainer's weight_decay."""
+    names = [n for n, p in model.named_parameters() if p.ndim <= 1]
+    return [{"params": names, "weight_decay": 0.0}] if names else []
+
+
+def check_tiles(tiles, groups, flat, assignment) -> None:
+    """Validate a tile table against the layout (what sed_adam_groups_step cannot do on the host): int32 (NT, 4) rows
+    {start4, count4, group, 0}, ascending, covering [0, numel / 4) exactly, 1 <= count4 <= TILE4, no tile across a parameter, every
+    tile in its parameter's group; groups float32 (NG, 4), 1 <= NG <= MAX_GROUPS."""
+    tiles, groups = np.asarray(tiles), np.asarray(groups)
+    if tiles.dtype != np.int32 or tiles.ndim != 2 or tiles.shape[1] != 4 or tiles.shape[0] < 1:
+        raise ValueError("tile table must be int32 (NT, 4) with NT >= 1")
+    if groups.dtype != np.float32 or groups.ndim != 2 or groups.shape[1] != 4 or not 1 <= groups.shape[0] <= MAX_GROUPS:
+        raise ValueError(f"group table must be float32 (NG, 4) with 1 <= NG <= {MAX_GROUPS}")
+    if flat.numel % 4:
+        raise ValueError("the flat buffer's length must be a multiple of 4")
+    if len(assignment) != len(flat.names):
+        raise ValueError("one group index per parameter")
+    bounds = []                       # (first float4, one past the last, group) per parameter, in buffer order
+    for n, g in zip(flat.names, assignment):
+        o, k = flat.offsets[n], int(flat.P[n].numel())
+        if o % 4:
+            raise ValueError(f"parameter {n} does not start on a float4")
+        if not 0 <= int(g) < groups.shape[0]:
+            raise ValueError(f"parameter {n}: group {g} outside the group table")
+        if k:
+            bounds.append((o // 4, (o + k + 3) // 4, int(g), n))
+    pos, bi = 0, 0
+    for t, (s4, c4, g, z) in enumerate(tiles.tolist()):
+        if s4 != pos:
+            raise ValueError(f"tile {t}: starts at float4 {s4}, expected {pos} (tiles ascend and cover the buffer without gaps)")
+        if not 1 <= c4 <= TILE4:
+            raise ValueError(f"tile {t}: count4 {c4} outside 1..{TILE4}")
+        if z != 0:
+            raise ValueError(f"tile {t}: the fourth word must be 0")
+        while bi < len(bounds) and bounds[bi][1] <= s4:
+            bi += 1
+        if bi == len(bounds) or s4 < bounds[bi][0] or s4 + c4 > bounds[bi][1]:
+            raise ValueError(f"tile {t}: [{s4}, {s4 + c4}) crosses a parameter boundary")
+        if g != bounds[bi][2]:
+            raise ValueError(f"tile {t}: group {g}, but parameter {bounds[bi][3]} is in group {bounds[bi][2]}")
+        pos = s4 + c4
+    if pos != flat.numel // 4:
+        raise ValueError(f"the tiles cover {pos} float4s of {flat.numel // 4}")
+
+
+def build_tiles(flat, assignment, specs=None):
+    """The two tables of the grouped step for a FlatParams layout, as numpy arrays: tiles int32 (NT, 4) = {start4, count4, group, 0}
+    -- every parameter cut into runs of at most TILE4 float4s, its padding lanes included -- and groups float32 (NG, 4) =
+    {lr_scale, weight_decay, frozen, 0}.  assignment: one group index per parameter in flat.names order; specs: (lr_scale,
+    weight_decay, frozen) per group (None: max(assignment) + 1 groups of (1, 0, False)).  Checked with check_tiles before return."""
+    assignment = [int(g) for g in assignment]
+    if len(assignment) != len(flat.names):
+        raise ValueError("one group index per parameter")
+    if specs is None:
+        specs = [(1.0, 0.0, False)] * (max(assignment) + 1)
+    if not 1 <= len(specs) <= MAX_GROUPS:
+        raise ValueError(f"1..{MAX_GROUPS} groups (got {len(specs)})")
+    if min(assignment) < 0 or max(assignment) >= len(specs):
+        raise ValueError("group index outside the group table")
+    rows = []
+    for n, g in zip(flat.names, assignment):
+        s4, c4 = flat.offsets[n] // 4, (int(flat.P[n].numel()) + 3) // 4
+        while c4 > 0:
+            c = min(c4, TILE4)
+            rows.append((s4, c, g, 0))
+            s4, c4 = s4 + c, c4 - c
+    tiles = np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+    groups = np.asarray([(float(s), float(w), 1.0 if f else 0.0, 0.0) for s, w, f in specs], dtype=np.float32).reshape(-1, 4)
+    check_tiles(tiles, groups, flat, assignment)
+    return tiles, groups
+
+
+def grouped_param_groups(template: dict, specs, assignment, next_lr: float, base_lr: float) -> list:
+    """state_dict()'s 'param_groups' on the grouped path, torch's multi-group layout: one dict per NON-EMPTY group in group order,
+    `template`'s keys (betas, eps, amsgrad, ...) with 'params' = the indices in model.parameters() order, 'lr' = next_lr * lr_scale,
+    'initial_lr' = base_lr * lr_scale, the group's 'weight_decay', and 'lr_scale' / 'frozen'."""
+    out = []
+    for gi, (scale, wd, frozen) in enumerate(specs):
+        idx = [i for i, g in enumerate(assignment) if g == gi]
+        if idx:
+            out.append(dict(template, lr=next_lr * scale, initial_lr=base_lr * scale, weight_decay=wd if wd != 0.0 else 0,
+                            lr_scale=scale, frozen=frozen, params=idx))
+    return out
+
+
+def state_index_map(state_groups, own_groups) -> dict:
+    """{id in the state: index in model.parameters() order} for a multi-group optimizer state, matched by POSITION as
+    torch.optim.Optimizer.load_state_dict does: the k-th parameter of the j-th group of the state is the k-th of the j-th own group.
+    A torch optimizer numbers its parameters group after group, this trainer in model.parameters() order; both load.  Refuses
+    another number of groups or of parameters in a group."""
+    if [len(g["params"]) for g in state_groups] != [len(g["params"]) for g in own_groups]:
+        raise ValueError("optimizer state does not have this trainer's parameter groups "
+                         f"(sizes {[len(g['params']) for g in state_groups]}, expected {[len(g['params']) for g in own_groups]})")
+    return {int(a): int(b) for sg, og in zip(state_groups, own_groups) for a, b in zip(sg["params"], og["params"])}
+
+
+def check_group_options(model, lr, lr_schedule=None, param_groups=None, weight_decay=0.0):
+    """Validate lr_schedule / param_groups of FusedTrainer / train() (host only, before the model is touched).  Returns None when
+    both are None -- the step then launches exactly what it always did -- else (schedule, specs, assignment); without a schedule
+    the groups run the reference's decay as LRSchedule('step', every=200, gamma=0.997)."""
+    if lr_schedule is None and param_groups is None:
+        return None
+    if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+        raise TypeError(f"lr_schedule must be an LRSchedule or None (got {type(lr_schedule).__name__})")
+    if not math.isfinite(float(lr)):
+        raise ValueError(f"lr must be finite (got {lr!r})")
+    specs, assignment = resolve_param_groups([n for n, _ in model.named_parameters()], param_groups, weight_decay)
+    eng = getattr(model, "engine", None)
+    if eng is not None and not hasattr(eng, "adam_groups_step"):
+        raise RuntimeError(f"lr_schedule / param_groups need an engine with the grouped optimizer step ({type(model).__name__} has "
+                           "none)")
+    return lr_schedule if lr_schedule is not None else LRSchedule("step"), specs, assignment
+
+
 def check_weak_options(weak_pooling=None, weak_weight=1.0, weak_only=False, model=None):
     """Validate the weak-label options of FusedTrainer / train() (host only, before any device work).  Returns None when
     weak_pooling is None -- the step then launches exactly what it always did -- else the (mode, weight, only) triple of
@@ -410,7 +650,8 @@ class FusedTrainer:
                  weight_decay: float = 0.0, decoupled_weight_decay: bool = False, amsgrad: bool = True,
                  max_grad_norm: Optional[float] = None, weak_pooling: Optional[str] = None, weak_weight: float = 1.0,
                  weak_only: bool = False, mean_teacher: bool = False, ema_decay: float = 0.999, consistency_weight: float = 2.0,
-                 consistency_rampup: int = 0, teacher_augment=None):
+                 consistency_rampup: int = 0, teacher_augment=None, lr_schedule: Optional["LRSchedule"] = None,
+                 param_groups: Optional[list] = None):
         """graph=True (single process): after two eager steps per input shape the whole step -- forward, loss, backward,
         Adam-amsgrad with its step counter, learning rate and bias corrections in device memory -- is captured into a HIP
         graph and replayed.  For the reference's own small shapes (T = 30 crops, batch 4: ~90 launches of a few microseconds
@@ -440,7 +681,25 @@ class FusedTrainer:
         probabilities and, with a weak_pooling, its pooled clip probabilities: MSE terms over all clips times
         consistency_weight, ramped up over the first consistency_rampup steps (consistency_weight_at).  After the optimizer step
         teacher <- a_n teacher + (1 - a_n) student, a_n = ema_factor(n, ema_decay).  self.last_consistency is a device (2,)
-        tensor, the frame and clip terms of the last step.  Single process, eager steps only."""
+        tensor, the frame and clip terms of the last step.  Single process, eager steps only.
+
+        lr_schedule: None, or an LRSchedule -- linear warm-up, then const / step / cosine / linear / invsqrt decay.  param_groups:
+        None, or a list of {"params": selector, "lr_scale": 1.0, "weight_decay": None, "frozen": False}; a selector is a list of
+        name prefixes matched against named_parameters() at dot boundaries, or a callable name -> bool; the first match wins, the
+        unmatched parameters form group 0 (scale 1, the trainer's weight_decay), weight_decay None inherits the trainer's
+        (no_decay_groups(model) is the usual AdamW split).  A frozen group's parameters and optimizer state keep their bits and its
+        gradients are left out of the clipping norm, as torch does for a parameter without a gradient; its backward still runs, and
+        the BatchNorm running statistics of a frozen block still follow the training-mode forwards, as in torch (model.eval() with
+        the eval-mode backward pins them).  With both None the trainer does what it always did.  With either given, eager and
+        graph=True steps alike run sed_grad_norm_groups (if clipping) and sed_adam_groups_step: the step counter, the schedule's
+        learning rate and every group's scalars live in device memory and the host keeps no second copy of the schedule.
+        param_groups without a schedule run the reference's decay as LRSchedule("step", every=200, gamma=0.997): the closed form
+        lr * 0.997^floor((s - 1) / 200) in float64, NOT claimed bit-equal to the legacy path's fp32 recurrence lr *= 0.997.
+        trainer.lr is then lr_at(base_lr, step_count + 1, schedule), the next step's rate as before, and trainer.last_lr the device
+        view of the rate the last step used.  Works under a process group (every rank applies the same elementwise step to the same
+        all-reduced buffer; only world size 1 is exercised), with label kinds, weak pooling, the mean teacher (the EMA runs over the
+        whole buffer), a PCEN front-end, the M5 engine and all four precisions.  FusedAdamAmsgrad does not take these options."""
+        self._grouped = check_group_options(model, lr, lr_schedule, param_groups, weight_decay)
         self.semi = check_semi_options(mean_teacher, ema_decay, consistency_weight, consistency_rampup, model)
         # every refusal comes before the teacher is made and before the model's parameters move into the flat buffer: a refused
         # constructor leaves the model as it found it
@@ -470,14 +729,27 @@ class FusedTrainer:
         self.m = torch.zeros_like(self.flat.p)
         self.v = torch.zeros_like(self.flat.p)
         self.vmax = torch.zeros_like(self.flat.p) if self.amsgrad else None
-        self.lr = float(lr)
+        self._lr = self.base_lr = float(lr)
+        self.lr_schedule = self.group_specs = self.group_of = self.last_lr = None
         self.betas, self.eps = betas, eps
         self.recall_factor = float(recall_factor)
         # clipping workspace, allocated once: fp64 partial sums, out = [norm, clip factor]; last_grad_norm is a view of out
         self._gn_partial = self._gn_out = self._coef = self.last_grad_norm = None
+        if self._grouped is not None:
+            # the grouped step: tile and group tables, the per-group scalars, the schedule's three floats and the step counter,
+            # all in device memory for eager and captured steps alike
+            dev = self.flat.p.device
+            self.lr_schedule, self.group_specs, self.group_of = self._grouped
+            tiles, groups = build_tiles(self.flat, self.group_of, self.group_specs)
+            self._tiles, self._groups = torch.from_numpy(tiles).to(dev), torch.from_numpy(groups).to(dev)
+            self._gh = torch.zeros(len(self.group_specs), 4, dtype=torch.float32, device=dev)
+            self.hyper = torch.zeros(4, dtype=torch.float32, device=dev)
+            self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.last_lr = self.hyper[0:1]              # device (1,), the learning rate the last step used; no sync
         if self.max_grad_norm is not None:
             dev = self.flat.p.device
-            self._gn_partial = torch.zeros(L.lib().sed_grad_norm_nparts(self.flat.numel), dtype=torch.float64, device=dev)
+            nparts = L.lib().sed_grad_norm_nparts(self.flat.numel) if self._grouped is None else self._tiles.shape[0]
+            self._gn_partial = torch.zeros(nparts, dtype=torch.float64, device=dev)
             self._gn_out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)
             self._coef = self._gn_out[1:2]
             self.last_grad_norm = self._gn_out[0:1]     # device (1,), norm of the last step's averaged gradient; no sync
@@ -511,10 +783,34 @@ class FusedTrainer:
                 raise RuntimeError("graph=True is the single-process path (the gradient collectives are not captured)")
             if not hasattr(self.engine, "adam_step_dev"):
                 raise RuntimeError("graph=True needs an engine with a device-scalar optimizer step (Cnn_AvgPooling / Crnn_AvgPooling)")
-            dev = self.flat.p.device
-            # (the extended device step keeps this step's learning rate in a fourth slot, sed_hip.h)
-            self.hyper = torch.tensor([self.lr, 0.0, 0.0] + ([self.lr] if self._opt_ext else []), dtype=torch.float32, device=dev)
-            self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            if self._grouped is None:
+                dev = self.flat.p.device
+                # (the extended device step keeps this step's learning rate in a fourth slot, sed_hip.h)
+                self.hyper = torch.tensor([self.lr, 0.0, 0.0] + ([self.lr] if self._opt_ext else []), dtype=torch.float32, device=dev)
+                self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    @property
+    def lr(self) -> float:
+        """The learning rate of the NEXT step: the host's scalar on the default path, lr_at(base_lr, step_count + 1, schedule) --
+        float64, for logging -- with lr_schedule / param_groups (the device computes its own from the step counter)."""
+        if self._grouped is None:
+            return self._lr
+        return lr_at(self.base_lr, self.step_count + 1, self.lr_schedule)
+
+    @lr.setter
+    def lr(self, value: float):
+        if self._grouped is not None:
+            raise AttributeError("with lr_schedule / param_groups the learning rate follows the schedule from base_lr")
+        self._lr = float(value)
+
+    def _groups_step(self, scale: float):
+        """the grouped path's optimizer launches, eager or captured: [norm over the non-frozen tiles,] hyper kernel + update"""
+        if self.max_grad_norm is not None:
+            self.engine.grad_norm_groups(self.flat.g, self._tiles, self._groups, self._gn_partial, self._gn_out, scale,
+                                         self.max_grad_norm)
+        self.engine.adam_groups_step(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self._tiles, self._groups, self._gh,
+                                     self.hyper, self.step_dev, self.base_lr, self.lr_schedule, grad_scale=scale, betas=self.betas,
+                                     eps=self.eps, decoupled=self.decoupled_weight_decay, coef=self._coef)
 
     def _check_alias(self):
         if not self.flat.aliased():
@@ -580,7 +876,9 @@ class FusedTrainer:
     def optimizer_step(self):
         scale = self.reducer.finish()
         self.step_count += 1
-        if not self._opt_ext:
+        if self._grouped is not None:
+            self._groups_step(scale)
+        elif not self._opt_ext:
             self.engine.adam_step(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self.lr, self.step_count,
                                   grad_scale=scale, betas=self.betas, eps=self.eps)
         else:
@@ -593,12 +891,15 @@ class FusedTrainer:
         if self.teacher is not None:
             self.engine._k("sed_ema_update", self.engine.lib.sed_ema_update, L.ptr(self.teacher_flat.p), L.ptr(self.flat.p),
                            self.flat.numel, ema_factor(self.step_count, self.semi[0]), torch.cuda.current_stream().cuda_stream)
-        if self.step_count % LR_DECAY_FREQ == 0:       # train.py:108-110 (after that iteration's step)
+        if self._grouped is None and self.step_count % LR_DECAY_FREQ == 0:       # train.py:108-110 (after that iteration's step)
             self.lr *= LR_DECAY
 
     def _step_dev(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """forward + loss + backward + optimizer step with device-resident scalars: kernel launches only (capturable)."""
         loss = self.forward_backward(x, y)
+        if self._grouped is not None:
+            self._groups_step(1.0)
+            return loss
         if not self._opt_ext:
             self.engine.adam_step_dev(self.flat.p, self.flat.g, self.m, self.v, self.vmax, self.hyper, self.step_dev, 1.0,
                                       LR_DECAY, LR_DECAY_FREQ, betas=self.betas, eps=self.eps)
@@ -612,7 +913,7 @@ class FusedTrainer:
 
     def _host_mirror(self):
         self.step_count += 1
-        if self.step_count % LR_DECAY_FREQ == 0:
+        if self._grouped is None and self.step_count % LR_DECAY_FREQ == 0:
             self.lr *= LR_DECAY
 
     def train_step(self, x: torch.Tensor, y: torch.Tensor, kind: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -651,8 +952,11 @@ class FusedTrainer:
         return ent[3]
 
     def _sync_host_scalars(self):
-        """graph mode keeps the authoritative step counter / learning rate on the device."""
-        if self.use_graph and self._graphs:
+        """graph mode keeps the authoritative step counter / learning rate on the device; the grouped path keeps the counter there
+        in every mode, and the learning rate is a function of it: only the counter is read."""
+        if self._grouped is not None:
+            self.step_count = int(self.step_dev.item())
+        elif self.use_graph and self._graphs:
             self.step_count = int(self.step_dev.item())
             self.lr = float(self.hyper[0].item())
 
@@ -661,10 +965,17 @@ class FusedTrainer:
         train.py:123-126): {'state': {i: {'step', 'exp_avg', 'exp_avg_sq', 'max_exp_avg_sq'}}, 'param_groups': [...]}, the
         parameters numbered in model.parameters() order -- loadable into torch.optim.Adam and back into this trainer.
         The param group carries the trainer's weight_decay / amsgrad / decoupled_weight_decay (load a decoupled one into
-        torch.optim.AdamW); without amsgrad there is no 'max_exp_avg_sq'.  max_grad_norm is not optimizer state."""
+        torch.optim.AdamW); without amsgrad there is no 'max_exp_avg_sq'.  max_grad_norm is not optimizer state.
+
+        With lr_schedule / param_groups the layout is torch's multi-group one: one entry per non-empty group in group order (the
+        unmatched remainder first), 'params' the indices in model.parameters() order, 'lr' that group's rate for the next step,
+        'initial_lr' = base_lr * lr_scale, its 'weight_decay', plus 'lr_scale' and 'frozen'; no 'state' entries for frozen
+        parameters; a top-level 'lr_schedule' dict.  It loads into torch.optim.Adam / AdamW built with the same groups."""
         self._sync_host_scalars()
         state = {}
         for i, n in enumerate(self.flat.names):
+            if self._grouped is not None and self.group_specs[self.group_of[i]][2]:
+                continue                    # frozen: torch keeps no state for a parameter that never had a gradient
             o, shp = self.flat.offsets[n], self.flat.P[n].shape
             k = self.flat.P[n].numel()
             state[i] = {"step": torch.tensor(float(self.step_count)),
@@ -677,6 +988,9 @@ class FusedTrainer:
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "decoupled_weight_decay": self.decoupled_weight_decay, "params": list(range(len(self.flat.names)))}
         sd = {"state": state, "param_groups": [group]}
+        if self._grouped is not None:
+            sd["param_groups"] = grouped_param_groups(group, self.group_specs, self.group_of, self.lr, self.base_lr)
+            sd["lr_schedule"] = dict(self.lr_schedule.as_dict(), base_lr=self.base_lr)
         if self.teacher is not None:        # the mean teacher's parameters and BatchNorm buffers
             sd["teacher"] = {k: v.clone() for k, v in self.teacher.state_dict().items()}
         deng = _dropout_engine(self.model)
@@ -691,12 +1005,24 @@ class FusedTrainer:
         is this trainer's.  lr, betas and eps come from the state; weight decay, its kind and max_grad_norm stay as the
         trainer was built.  The mean teacher is restored from `teacher` (a checkpoint of train() keeps it beside the optimizer
         state: trainer.load_state_dict(ck['optimizer'], teacher=ck.get('teacher'))), else from sd['teacher'], else -- a state
-        from before the teacher -- it starts as a copy of the student as the model is now."""
+        from before the teacher -- it starts as a copy of the student as the model is now.
+
+        With lr_schedule / param_groups the state must have this trainer's group structure (as many groups, as many parameters in
+        each: its own state_dict() or that of a torch optimizer built with the same groups, matched by position as torch does,
+        state_index_map); the base learning rate, the scales, the decays and the SCHEDULE are the trainer's, not the state's
+        (sd['lr_schedule'] and the groups' 'lr' are not read): only betas, eps, the moments and the step counter are restored, the
+        counter on the device too."""
         groups = sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(self.flat.names):
+        grouped = getattr(self, "_grouped", None) is not None
+        if grouped:
+            ids = state_index_map(groups, grouped_param_groups({}, self.group_specs, self.group_of, 0.0, 0.0))
+            sd = dict(sd, state={ids[k]: st for k, st in sd["state"].items()})
+        elif len(groups) != 1 or len(groups[0]["params"]) != len(self.flat.names):
             raise ValueError("optimizer state does not match this model's parameter list")
-        check_state_amsgrad(groups[0], self.amsgrad)
-        self.lr = float(groups[0]["lr"])
+        for g in groups:
+            check_state_amsgrad(g, self.amsgrad)
+        if not grouped:
+            self.lr = float(groups[0]["lr"])
         self.betas, self.eps = tuple(groups[0]["betas"]), float(groups[0]["eps"])
         step = 0
         for i, n in enumerate(self.flat.names):
@@ -725,14 +1051,17 @@ class FusedTrainer:
                     continue
                 words = [int(v) for v in sd[key].tolist()] if key in sd else eng.drop_state_words()[:2] + [0, 0]
                 eng.set_drop_state(words)
-        if self.use_graph:
+        if grouped:
+            self.step_dev.fill_(step)
+        elif self.use_graph:
             self.hyper[0] = self.lr
             self.step_dev.fill_(step)
 
 
 class FusedAdamAmsgrad:
     """torch.optim-like facade over the fused kernel for code that calls loss.backward() itself
-    (gradients in p.grad): zero_grad() / step().  The four optimizer options are FusedTrainer's."""
+    (gradients in p.grad): zero_grad() / step().  The four optimizer options are FusedTrainer's; lr_schedule / param_groups are
+    not offered here (set param_groups[0]["lr"] between steps for a schedule)."""
 
     def __init__(self, model, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  decoupled_weight_decay: bool = False, amsgrad: bool = True, max_grad_norm: Optional[float] = None):
@@ -966,7 +1295,8 @@ def summarize_validation(val_losses, recal_sets, precision_sets, APs):
 def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, device, *, weight_decay=0.0,
           decoupled_weight_decay=False, amsgrad=True, max_grad_norm=None, event_eval=None, batch_augment=None,
           weak_pooling=None, weak_weight=1.0, weak_only=False, mean_teacher=False, ema_decay=0.999, consistency_weight=2.0,
-          consistency_rampup=0, teacher_augment=None, eval_teacher=False, ranking_eval=None, psds_eval=None):
+          consistency_rampup=0, teacher_augment=None, eval_teacher=False, ranking_eval=None, psds_eval=None, lr_schedule=None,
+          param_groups=None):
     """train.py:77-131.  `criterion` must be this package's WeightedBCE(multi_frame=True) (its
     recall_factor feeds the fused loss kernel).  The keyword-only optimizer options are FusedTrainer's (this build only; their
     defaults are the reference's Adam(amsgrad=True) without decay or clipping).  event_eval: None, or the keyword arguments of
@@ -983,9 +1313,11 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
     {'clip_pooling': ...}): the periodic evaluation then also logs that dict under 'ranking' (the teacher's with eval_teacher);
     None launches nothing new.  psds_eval: None, or the keyword arguments of eval_psds ({'fps': ...} and optionally scenario,
     thresholds, median_window): the periodic evaluation then also logs that dict under 'psds' (the teacher's with eval_teacher);
-    None launches nothing new."""
+    None launches nothing new.  lr_schedule / param_groups: FusedTrainer's (an LRSchedule; a list of group dicts, e.g.
+    no_decay_groups(model)); both None keep the reference's step decay and single group."""
     from .utils.common import WeakBCE, WeightedBCE
     check_optimizer_options(weight_decay, decoupled_weight_decay, amsgrad, max_grad_norm)
+    check_group_options(model, lr, lr_schedule, param_groups, weight_decay)
     if isinstance(criterion, WeakBCE):
         if weak_pooling is not None and weak_pooling != criterion.pooling:
             raise ValueError(f"criterion pools with {criterion.pooling!r} but weak_pooling={weak_pooling!r}")
@@ -1027,7 +1359,7 @@ def train(model, data_loader, criterion, num_steps, lr, log_freq, outputs_dir, d
                            decoupled_weight_decay=decoupled_weight_decay, amsgrad=amsgrad, max_grad_norm=max_grad_norm,
                            weak_pooling=weak_pooling, weak_weight=weak_weight, weak_only=weak_only, mean_teacher=mean_teacher,
                            ema_decay=ema_decay, consistency_weight=consistency_weight, consistency_rampup=consistency_rampup,
-                           teacher_augment=teacher_augment)
+                           teacher_augment=teacher_augment, lr_schedule=lr_schedule, param_groups=param_groups)
     eval_model = trainer.teacher if eval_teacher else model
     rank0 = (not trainer.reducer.enabled) or trainer.reducer.dist.get_rank() == 0
     log_path = os.path.join(outputs_dir, "progress.jsonl")
